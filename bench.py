@@ -8,12 +8,17 @@
   step     one frame through fdh_render_frame: the scene tree goes in, the RGBA8 surface comes out (C++ tree walk,
            draw records, 90 KB upload, binning, tile compositing, both blurs), as the reference's benchmark times
            renderFrame per frame (examples/windy_non_clip_benchmark.nim:113-147); frames_in_flight contexts per GPU.
-           Beside it: the same frames through the ~710-call BackendContext seam (`per_call_path`), the GPU work
-           alone from resident records (`replay_resident_records`), one frame at a time
+  plain    `bench.py --gpus 1 --steps N --warmup W`: set up, pick the host-thread mode on short untimed batches, W frames of
+           warm-up, ONE timed batch of exactly N frames, the headline line (`value`, `ms_per_step`, ...), nothing else.
+           --dump-outputs DIR writes the frame of the last timed step.
+  --full   everything else: the median of --repeats (default 7) batches and, measured after them, the in-flight and oracle
+           checks, the same frames through the ~710-call BackendContext seam (`per_call_path`), the GPU work alone from
+           resident records (`replay_resident_records`), one frame at a time, per-kernel times, rooflines, the retained
+           path, the CPU baseline and, on N > 1 ranks, the gather legs
 
 N > 1 (launched by torch.distributed.run, one rank per GPU), two ways to shard:
   --mode frames   (default) frames are independent, so rank r renders its own frames with no data-path collective --
-                  weak scaling.  After the timed region the ranks' final frames are gathered to rank 0 with ONE RCCL
+                  weak scaling.  With --full, after the timed region the ranks' final frames are gathered to rank 0 with ONE RCCL
                   gather over xGMI; its time is reported separately and is not part of `value`.
   --mode stripes  BASELINE.json configs[4] (run it with --width 7680 --height 4320): a batch of 8 frames (frame = 0..7 in
                   rotation), every rank renders rows stripe_rows(H, N, r) of EVERY frame (with its redundant blur halo) and
@@ -42,6 +47,9 @@ HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2.0
 # FP32 vector peak (/opt/skills/guides/MI355X_MICROARCH.md): 256 CUs x 4 SIMDs x 64 lanes x 2 flops (FMA) per 2 cycles x 2.4 GHz
 VALU_PEAK_TFLOPS = 157.3
+# The host-thread calibration times batches of --steps frames, at most this many (~0.1 s at 4K): enough to rank the candidates,
+# and the calibration stays within seconds whatever --steps is.
+CALIBRATION_FRAMES = 2000
 
 
 def frame_tensor(ctx):
@@ -55,6 +63,24 @@ def frame_tensor(ctx):
                                     "strides": (pitch, 4, 1)}
 
     return torch.as_tensor(_Surf(), device=f"cuda:{ctx.device}")
+
+
+DUMP_SAMPLE_PIXELS = 1 << 20  # 16 MB of float32 RGBA + 8 MB of float64 indices: a dump stays within 64 MB at any frame size
+
+
+def dump_frame(out_dir, frame):
+    """--dump-outputs: the (h, w, 4) RGBA8 frame the last timed step produced, as .npy files that the same command on another build
+    can be compared with file for file (a 4K frame as float32 would be 133 MB, so the pixels are a fixed sample):
+      frame_sample.npy        (n, 4) float32: RGBA of a seeded sample of n = min(h * w, DUMP_SAMPLE_PIXELS) pixels, in index order
+      frame_sample_index.npy  (n,) float64: their flat indices y * w + x
+      frame_row_sums.npy      (h, 4) float64: every row's channel sums over all of its pixels (exact)"""
+    os.makedirs(out_dir, exist_ok=True)
+    h, w = frame.shape[:2]
+    n = min(h * w, DUMP_SAMPLE_PIXELS)
+    idx = np.arange(h * w) if n == h * w else np.sort(np.random.default_rng(12345).choice(h * w, size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), frame.reshape(h * w, 4)[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "frame_row_sums.npy"), frame.sum(axis=1, dtype=np.float64))
 
 
 def setup_comm(ctxs, dist, rank, world):
@@ -202,37 +228,38 @@ def run_stripes(args, dist, rank, local_rank, world, on_host, gather):
         return None
     last_k = args.steps - 1
     last_i = last_k % F
-    if use_c_abi:
-        ctxs[last_i].W, ctxs[last_i].H = w, h
-        got = ctxs[last_i].read_pixels()
-    elif use_host:
-        got = None  # (every rank holds its own rows: rank 0 checks its stripe against the oracle's)
-    else:
-        got = full[last_i].cpu().numpy()
-    if got is not None:
-        assert int(got[..., 3].min()) == 255, "the gathered frame has unwritten pixels"
+    # rank 0's image of the last frame: read back only for --full's checks and --dump-outputs
+    got = None
+    if use_host:
+        got = stripe_host[last_i].numpy()[: y1 - y0]  # (every rank holds its own rows: rank 0's stripe is what it computed)
+    elif args.full or args.dump_outputs:
+        if use_c_abi:
+            ctxs[last_i].W, ctxs[last_i].H = w, h
+            got = ctxs[last_i].read_pixels()
+        else:
+            got = full[last_i].cpu().numpy()
+        if args.full:
+            assert int(got[..., 3].min()) == 255, "the gathered frame has unwritten pixels"
+    if args.dump_outputs:
+        dump_frame(args.dump_outputs, got)
     check = None
-    if use_host and not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:  # the last frame against the oracle (outside the timed region)
         from oracle import oracle as O
 
         orc = O.Oracle(threads=min(os.cpu_count() or 1, 16))
         orc.render_frame(scenes[last_k % NS], w, h)
-        mine = stripe_host[last_i].numpy()[: y1 - y0]
-        d = np.abs(mine.astype(int) - orc.read_pixels()[y0:y1].astype(int))
-        check = {"frame": last_k % NS, "rows_checked": [y0, y1], "parity_max_lsb": int(d.max()), "parity_pixels_differing": int((d.max(axis=2) > 0).sum())}
-        if check["parity_max_lsb"] > 1:
-            print(json.dumps({"error": "rank 0's stripe (read back by the host) disagrees with the oracle", "check": check}))
-            sys.exit(1)
-    elif not args.no_cpu_baseline:  # the gathered image of the last frame against the oracle (outside the timed region)
-        from oracle import oracle as O
-
-        orc = O.Oracle(threads=min(os.cpu_count() or 1, 16))
-        orc.render_frame(scenes[last_k % NS], w, h)
-        d = np.abs(got.astype(int) - orc.read_pixels().astype(int))
-        check = {"frame": last_k % NS, "parity_max_lsb": int(d.max()), "parity_pixels_differing": int((d.max(axis=2) > 0).sum())}
-        if check["parity_max_lsb"] > 1:
-            print(json.dumps({"error": "gathered frame disagrees with the oracle", "check": check}))
-            sys.exit(1)
+        if use_host:
+            d = np.abs(got.astype(int) - orc.read_pixels()[y0:y1].astype(int))
+            check = {"frame": last_k % NS, "rows_checked": [y0, y1], "parity_max_lsb": int(d.max()), "parity_pixels_differing": int((d.max(axis=2) > 0).sum())}
+            if check["parity_max_lsb"] > 1:
+                print(json.dumps({"error": "rank 0's stripe (read back by the host) disagrees with the oracle", "check": check}))
+                sys.exit(1)
+        else:
+            d = np.abs(got.astype(int) - orc.read_pixels().astype(int))
+            check = {"frame": last_k % NS, "parity_max_lsb": int(d.max()), "parity_pixels_differing": int((d.max(axis=2) > 0).sum())}
+            if check["parity_max_lsb"] > 1:
+                print(json.dumps({"error": "gathered frame disagrees with the oracle", "check": check}))
+                sys.exit(1)
     st = ctxs[0].frame_stats()
     ms_step = 1e3 * elapsed / args.steps
     out = {
@@ -296,12 +323,12 @@ def write_provisional(out):
 
 def stripes_main(args, dist, rank, local_rank, world, on_host):
     """--mode stripes: one leg per gather.  With --gather both (the default on several ranks) the torch.distributed leg runs first and
-    owns `value`; the library's fdh_gather_stripes leg follows under the watchdog and is reported as `c_abi_gather`."""
+    owns `value`; with --full the library's fdh_gather_stripes leg follows under the watchdog and is reported as `c_abi_gather`."""
     first = "torch" if args.gather == "both" else args.gather
     out = run_stripes(args, dist, rank, local_rank, world, on_host, first)
     if rank == 0:
         out["torch_world_size"] = dist.get_world_size() if dist is not None else 1
-    if args.gather == "both" and world > 1:
+    if args.full and args.gather == "both" and world > 1:
         can = not on_host or bool(os.environ.get("FDH_RCCL_LIB"))
         if not can:
             if rank == 0:
@@ -315,7 +342,8 @@ def stripes_main(args, dist, rank, local_rank, world, on_host):
 
             with Watchdog(args.gather_timeout, rank, late):
                 try:
-                    leg = run_stripes(args, dist, rank, local_rank, world, on_host, "c_abi")
+                    # (--dump-outputs holds the frame of the leg that owns `value`)
+                    leg = run_stripes(argparse.Namespace(**dict(vars(args), dump_outputs=None)), dist, rank, local_rank, world, on_host, "c_abi")
                     if rank == 0:
                         out["c_abi_gather"] = {"value": leg["value"], "unit": leg["unit"], "ms_per_step": leg["ms_per_step"], "batches_ms": leg["batches_ms"],
                                                "gather_ms": leg["gather_ms"], "gather": leg["config"]["gather"], "rccl_ranks_seen": leg["config"]["rccl_ranks_seen"],
@@ -388,18 +416,27 @@ def main():
                          "child); under a launcher it must equal WORLD_SIZE")
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=7, help="timed batches of --steps frames each; the median batch is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed batches of --steps frames each; the median batch is reported (default: 1, with --full 7)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the median of --repeats batches, the in-flight and oracle checks, the per-call, "
+                         "resident-record and one-frame-at-a-time legs, per-kernel times, rooflines, the CPU baseline and the gather legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last timed step produced to DIR/*.npy (a seeded sample of its pixels, "
+                         "float32, their indices and every row's channel sums)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for the 1-GPU self-test)")
     ap.add_argument("--all-ranks-on-device0", action="store_true", help="self-test of the N>1 code path on a 1-GPU box")
     ap.add_argument("--frames-in-flight", type=int, default=4,
                     help="independent render contexts per GPU (own stream + surfaces) whose frames overlap; 1 = strictly one frame at a time")
-    ap.add_argument("--host-threads", type=int, default=0, help="host threads driving the contexts of `value` (0 = one per context in flight)")
+    ap.add_argument("--host-threads", type=int, default=0,
+                    help="host threads driving the contexts of `value` (0 = one calling thread or one per context, whichever an untimed calibration "
+                         "finds faster)")
     ap.add_argument("--gather", choices=["c_abi", "torch", "host", "both"], default=None,
                     help="who moves the finished rows / frames to rank 0: c_abi = the library's own fdh_gather_* (RCCL through the C ABI, stream-ordered, "
                          "north_star's single RCCL gather); torch = torch.distributed; host (--mode stripes) = no gather: every rank reads its stripe back "
                          "over its OWN PCIe link (fdh_read_pixels) -- the consumer is the host; both = the torch leg first (its figures are `value` / "
-                         "`gather_ms`), then the c_abi leg under a watchdog, reported beside it.  Default: c_abi on one rank, both on several")
+                         "`gather_ms`), then with --full the c_abi leg under a watchdog, reported beside it.  Default: c_abi on one rank, both on several")
     ap.add_argument("--gather-timeout", type=float, default=180.0, help="seconds the gather legs of an N > 1 run may take before they are given up")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
@@ -420,6 +457,7 @@ def main():
     args.mode = args.mode or "frames"
     args.width, args.height = args.width or W, args.height or H
     args.steps = args.steps or 200
+    args.repeats = args.repeats or (7 if args.full else 1)
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus is None:
@@ -548,6 +586,7 @@ def main():
         T = max(1, min(args.host_threads, F))
     else:
         calibration = {}
+        n_cal = min(args.steps, CALIBRATION_FRAMES)
         for cand, pool_n in [(1, pool_default), (F, pool_default), (1, 0)]:
             key = f"{cand}" if pool_n == pool_default else f"{cand}, walk pool off"
             if key in calibration:
@@ -555,12 +594,12 @@ def main():
             for c in ctxs:
                 c.set_walk_threads(pool_n)
             fn = make_run(cand)
-            fn(max(args.warmup, args.steps))  # (a whole batch untimed first: a candidate's first batches carry its one-offs -- pool threads' first wake-up, staging growth)
+            fn(min(max(args.warmup, args.steps), CALIBRATION_FRAMES))  # (a whole batch untimed first: a candidate's first batches carry its one-offs -- pool threads' first wake-up, staging growth)
             # (five batches: with two, one late wake-up of a pool thread in both 1.3-ms batches of the driver's command once put the
             # run on the slowest candidate -- 116.7 Gpixel/s where the runs before and after it measured 134 - 139.  And their MEDIAN,
             # round 5: a thread per context has the occasional fast batch and a slow typical one -- its best of five beat the single
             # thread's by 0.7 % in one driver-style run, which then measured 131.8 Gpixel/s against 144.8 - 148.9 on the same box)
-            ts5 = sorted(timed(fn, args.steps) for _ in range(5))  # (max over ranks inside timed)
+            ts5 = sorted(timed(fn, n_cal) for _ in range(5))  # (max over ranks inside timed)
             calibration[key] = round(1e3 * ts5[2], 4)
         # the first candidate (one calling thread, the walk pool beside it: the library's default) unless another is clearly faster
         default_key = next(iter(calibration))
@@ -575,8 +614,8 @@ def main():
                 for c in ctxs:
                     c.set_walk_threads(pool_n)
                 fn = make_run(cand)
-                fn(args.steps)
-                again = sorted(timed(fn, args.steps) for _ in range(5))[2]
+                fn(n_cal)
+                again = sorted(timed(fn, n_cal) for _ in range(5))[2]
                 calibration[key + ", second run"] = round(1e3 * again, 4)
                 calibration[key] = min(calibration[key], round(1e3 * again, 4))
             if calibration[best] > 0.98 * calibration[default_key]:
@@ -588,6 +627,47 @@ def main():
     run_dynamic = make_run(T)
     run_dynamic(args.warmup)
     elapsed, batch_ms = batches(run_dynamic, args.steps, args.repeats)
+    mpix = world * w * h * args.steps / elapsed / 1e6
+    ms_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_frame(args.dump_outputs, ctxs[(args.steps - 1) % F].read_pixels())  # (the last timed step: frame steps - 1 on its context)
+
+    def headline(st):
+        """the fields of the line that every run prints: the figure, how it was timed, the workload"""
+        return {
+            "metric": "Mpixels/s composited @3840x2160, 300 SDF rects+shadows; % HBM roofline",
+            "value": round(mpix, 1),
+            "unit": "Mpixels/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 4),
+            "repeats": args.repeats,
+            "batches_ms": batch_ms,
+            "timing": (f"median of {args.repeats} timed batches of exactly {args.steps} frames each" if args.repeats > 1 else
+                       f"one timed batch of exactly {args.steps} frames") + ", every batch bracketed by barrier + synchronize "
+                      "(`batches_ms`: all of them, sorted); `value` = pixels of one batch / the median batch's wall time",
+            "step": "one frame through fdh_render_frame: scene tree in -> RGBA8 surface out (C++ tree walk, draw records, upload, binning, both blurs, "
+                    "compositing), frame k of the animation on context k % frames_in_flight; the loop is C (tools/call_player.c), on one calling thread or "
+                    "one host thread per context, " + ("whichever an untimed calibration found faster on this host" if calibration is not None else
+                                                       "as --host-threads sets it") + " (config.host_threads_per_gpu)",
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32 (blur taps: u8 x f16 -> f32 MFMA)",
+            "data": "synthetic",
+            "config": {"workload": f"S300@4K: renderlist_100 scene at {w}x{h}, 300 shadowed SDF rects + full-frame and 360x240 "
+                                   f"2-pass Gaussian backdrop blur(18) (BASELINE.json configs[2])",
+                       "draws": st.n_draws, "phases": st.n_phases, "blur_nodes": st.n_blurs, "fragments": int(st.fragments),
+                       "parallelism": f"frame-parallel x{world}" if world > 1 else "single GPU", "frames_in_flight_per_gpu": F, "host_threads_per_gpu": T,
+                       "walk_pool_threads": pool, "walk_pool_threads_default": pool_default},
+            "host_threads_calibration": calibration,
+        }
+
+    if not args.full:  # a plain run stops here: everything below is --full's
+        if rank == 0:
+            print(json.dumps(headline(ctx.frame_stats())), flush=True)
+        return
     # Integrity of the frames-in-flight mode (outside the timed region): every context must hold exactly the frame it
     # renders with the GPU to itself.  (Wrong pixels once came from a packed-FP32 misread beside another context's MFMAs:
     # DESIGN.md section 4.)  Context i rendered frame (last k with k % F == i) of the batch.
@@ -603,7 +683,6 @@ def main():
         c.sync()
         in_flight_differing += int((got_in_flight != c.read_pixels()).any(axis=2).sum())
     in_flight_vs_oracle = None
-    ms_step = 1e3 * elapsed / args.steps
     for c in ctxs:
         c.set_walk_threads(-1)  # (the legs below run with the library's default)
 
@@ -825,8 +904,6 @@ def main():
                     pass  # (rank 0 reports its own side; a rank that failed here leaves rank 0 to the watchdog)
         return
 
-    mpix = world * w * h * args.steps / elapsed / 1e6
-
     def hbm(bytes_, ms):
         gbs = bytes_ / (ms * 1e-3) / 1e9
         return {"achieved": round(gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 5)}
@@ -993,34 +1070,9 @@ def main():
             in_flight_vs_oracle = {"context": F - 1, "animation_frame": rank + world * in_flight_scene[F - 1], "parity_max_lsb": int(d.max()),
                                    "parity_pixels_differing": int((d.max(axis=2) > 0).sum())}
 
-    out = {
-        "metric": "Mpixels/s composited @3840x2160, 300 SDF rects+shadows; % HBM roofline",
-        "value": round(mpix, 1),
-        "unit": "Mpixels/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 4),
-        "repeats": args.repeats,
-        "batches_ms": batch_ms,
-        "timing": f"median of {args.repeats} timed batches of exactly {args.steps} frames each, every batch bracketed by barrier + synchronize "
-                  "(`batches_ms`: all of them, sorted); `value` = pixels of one batch / the median batch's wall time",
-        "step": "one frame through fdh_render_frame: scene tree in -> RGBA8 surface out (C++ tree walk, draw records, upload, binning, both blurs, "
-                "compositing), frame k of the animation on context k % frames_in_flight; the loop is C (tools/call_player.c), on one calling thread or "
-                "one host thread per context, whichever an untimed calibration found faster on this host (config.host_threads_per_gpu)",
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32 (blur taps: u8 x f16 -> f32 MFMA)",
-        "data": "synthetic",
-        "config": {"workload": f"S300@4K: renderlist_100 scene at {w}x{h}, 300 shadowed SDF rects + full-frame and 360x240 "
-                               f"2-pass Gaussian backdrop blur(18) (BASELINE.json configs[2])",
-                   "draws": st.n_draws, "phases": st.n_phases, "blur_nodes": st.n_blurs, "fragments": int(st.fragments),
-                   "parallelism": f"frame-parallel x{world}" if world > 1 else "single GPU", "frames_in_flight_per_gpu": F, "host_threads_per_gpu": T,
-                   "walk_pool_threads": pool, "walk_pool_threads_default": pool_default},
+    out = dict(headline(st), **{
         "frames_in_flight_check": {"contexts": F, "identical_to_each_frame_rendered_alone": in_flight_differing == 0,
                                    "pixels_differing": in_flight_differing, "in_flight_frame_vs_oracle": in_flight_vs_oracle},
-        "host_threads_calibration": calibration,
         "per_call_path": per_call,
         "replay_resident_records": replay,
         "one_frame_at_a_time": {"value": round(w * h * args.steps / sd_elapsed / 1e6, 1), "unit": "Mpixels/s (this rank)",
@@ -1043,7 +1095,7 @@ def main():
                   "host_decompose_upload_first_frame_ms": round(1e3 * (t_host1 - t_host0), 2)},
         "dynamic_path": dynamic,
         "cpu_baseline": cpu_baseline,
-    }
+    })
     if gather_ms is not None:
         out["gather_ms"] = round(gather_ms, 3)
         out["gather"] = gather_how

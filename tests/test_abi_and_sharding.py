@@ -422,9 +422,9 @@ def test_blur_weight_fragments_blur_like_the_reference(radius):
 
 def _run_bench_two_ranks(extra, port):
     """bench.py's N > 1 path on a one-GPU box: two ranks on device 0, gloo for the process group (tensors go through host
-    memory; RCCL needs one GPU per rank)."""
+    memory; RCCL needs one GPU per rank).  With --full: the checks and gather legs the callers read are --full's."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE="2")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--all-ranks-on-device0", "--backend", "gloo"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--all-ranks-on-device0", "--backend", "gloo", "--full"] + extra
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE) for r in range(2)]
     outs = [p.communicate(timeout=900) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1].decode()[-2000:] for o in outs]
@@ -503,7 +503,7 @@ def test_bench_stripes_mode_one_rank_gathers_through_the_c_abi():
     import json
 
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "stripes", "--width", "1920", "--height", "1080", "--steps", "9",
-                        "--warmup", "2", "--repeats", "2"], capture_output=True, text=True, timeout=900)
+                        "--warmup", "2", "--repeats", "2", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and "fdh_gather_stripes" in d["config"]["gather"] and d["config"]["rows_per_rank"] == [1080]
@@ -519,7 +519,7 @@ def test_bench_stripes_mode_with_the_host_as_consumer():
     import json
 
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "stripes", "--gather", "host", "--width", "1920", "--height", "1080",
-                        "--steps", "9", "--warmup", "2", "--repeats", "2"], capture_output=True, text=True, timeout=900)
+                        "--steps", "9", "--warmup", "2", "--repeats", "2", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and "own PCIe link" in d["config"]["gather"] and d["config"]["rccl_ranks_seen"] is None
@@ -606,6 +606,67 @@ def test_bench_config_5_selects_the_baseline_stripes_run():
     assert 'args.steps = args.steps or 8' in src
 
 
+def test_bench_dump_of_a_4k_frame_is_a_fixed_sample_within_64_mb(tmp_path):
+    """--dump-outputs (no GPU): a frame too large to write whole as float32 is written as the same seeded pixel sample every time,
+    float32 / float64 only, at most 64 MB, plus row sums over every pixel; a frame that fits is written pixel for pixel."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    h, w = 2160, 3840
+    frame = np.random.default_rng(1).integers(0, 256, size=(h, w, 4), dtype=np.uint8)
+    for d in ("a", "b"):
+        bench.dump_frame(str(tmp_path / d), frame)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["frame_row_sums.npy", "frame_sample.npy", "frame_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert got[f].dtype in (np.float32, np.float64), f
+        assert np.array_equal(got[f], np.load(tmp_path / "b" / f)), f  # (the same sample on every run)
+    idx = got["frame_sample_index.npy"].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE_PIXELS and (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < h * w
+    assert np.array_equal(got["frame_sample.npy"], frame.reshape(-1, 4)[idx].astype(np.float32))
+    assert np.array_equal(got["frame_row_sums.npy"], frame.astype(np.float64).sum(axis=1))
+    small = frame[:360, :640]
+    bench.dump_frame(str(tmp_path / "s"), small)
+    assert np.array_equal(np.load(tmp_path / "s" / "frame_sample_index.npy"), np.arange(360 * 640))
+    assert np.array_equal(np.load(tmp_path / "s" / "frame_sample.npy"), small.reshape(-1, 4).astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_frame(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W`: one timed batch of exactly N frames and the headline line only (what --full adds
+    is absent); --dump-outputs holds the frame of the last timed step -- the same pixels a --full run dumps, and the oracle's."""
+    from figdraw_amd.scenes import make_render_tree_100
+    from oracle import oracle as O
+
+    w, h, steps = 1280, 720, 6
+    common = ["--gpus", "1", "--steps", str(steps), "--warmup", "2", "--width", str(w), "--height", str(h)]
+    r, d = _bench(common + ["--dump-outputs", str(tmp_path / "plain")], timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == steps and d["repeats"] == 1 and len(d["batches_ms"]) == 1
+    assert abs(d["batches_ms"][0] / steps - d["ms_per_step"]) < 1e-3
+    for k in ("frames_in_flight_check", "per_call_path", "roofline", "cpu_baseline"):
+        assert k not in d, k
+    r, f = _bench(common + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert f["repeats"] == 7 and f["frames_in_flight_check"]["pixels_differing"] == 0 and "per_call_path" in f
+    names = ("frame_sample.npy", "frame_sample_index.npy", "frame_row_sums.npy")
+    dump = {n: np.load(tmp_path / "plain" / n) for n in names}
+    for n in names:
+        assert np.array_equal(dump[n], np.load(tmp_path / "full" / n)), n
+    # the last timed step is frame steps - 1 of the animation (rank 0 of 1); at 1280x720 the sample is every pixel
+    orc = O.Oracle(threads=8)
+    orc.render_frame(make_render_tree_100(w, h, frame=steps - 1, full_frame_blur=True), w, h)
+    want = orc.read_pixels().reshape(-1, 4).astype(np.float32)
+    assert np.array_equal(dump["frame_sample_index.npy"], np.arange(w * h))
+    diff = np.abs(dump["frame_sample.npy"] - want)
+    assert diff.max() <= 1 and (diff.max(axis=1) > 0).sum() <= 0.005 * w * h, (diff.max(), (diff.max(axis=1) > 0).sum())
+    assert np.abs(dump["frame_row_sums.npy"] - want.reshape(h, w, 4).sum(axis=1)).max() <= w
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["frames", "config5"])
 def test_bench_self_launch_runs_both_gather_legs(mode):
@@ -616,7 +677,7 @@ def test_bench_self_launch_runs_both_gather_legs(mode):
     env = {"FDH_RCCL_LIB": _mock_rccl(), "MASTER_PORT": "29551" if mode == "frames" else "29553"}
     if mode == "frames":
         r, d = _bench(["--gpus", "2", "--backend", "gloo", "--all-ranks-on-device0", "--width", "1280", "--height", "720", "--steps", "8", "--warmup", "2",
-                       "--repeats", "3", "--no-cpu-baseline"], env)
+                       "--repeats", "3", "--no-cpu-baseline", "--full"], env)
         assert r.returncode == 0, (r.stderr[-2000:], r.stdout[-2000:])
         assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["torch_world_size"] == 2 and d["rccl_ranks_seen"] == 2
         assert "torch.distributed.gather" in d["gather"] and d["gather_ms"] > 0
@@ -625,7 +686,7 @@ def test_bench_self_launch_runs_both_gather_legs(mode):
         assert d["frames_in_flight_check"]["pixels_differing"] == 0
     else:
         r, d = _bench(["--gpus", "2", "--backend", "gloo", "--all-ranks-on-device0", "--config", "5", "--width", "1920", "--height", "1080", "--warmup", "2",
-                       "--repeats", "3"], env)
+                       "--repeats", "3", "--full"], env)
         assert r.returncode == 0, (r.stderr[-2000:], r.stdout[-2000:])
         assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["steps"] == 8 and d["config"]["mode"] == "stripes"
         assert d["torch_world_size"] == 2 and d["config"]["rccl_ranks_seen"] == 2

@@ -5,7 +5,7 @@ root=$(pwd); cd /tmp; export TMPDIR=/tmp
 for rep in 1 2; do for v in "$@"; do
   lib=$root/build/libfigdraw_hip_$v.so; [ $v = tree ] && lib=$root/figdraw_amd/libfigdraw_hip.so
   rm -rf /tmp/prof_$v
-  FIGDRAW_HIP_LIB=$lib rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$v -o r -- python3 $root/bench.py --steps 40 --warmup 5 --no-cpu-baseline --frames-in-flight 1 > /dev/null 2>&1
+  FIGDRAW_HIP_LIB=$lib rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$v -o r -- python3 $root/bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --frames-in-flight 1 > /dev/null 2>&1
   python3 - $v <<'PY'
 import csv, glob, sys
 f = glob.glob('/tmp/prof_%s/**/*kernel_stats.csv' % sys.argv[1], recursive=True)[0]

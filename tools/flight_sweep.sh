@@ -1,7 +1,7 @@
 #!/bin/bash
 # value / per-call / replay against the number of contexts in flight (bench.py --frames-in-flight)
 for f in "$@"; do
-  python bench.py --no-cpu-baseline --frames-in-flight $f --repeats 5 2>/dev/null | tail -1 > /tmp/fs.json
+  python bench.py --full --no-cpu-baseline --frames-in-flight $f --repeats 5 2>/dev/null | tail -1 > /tmp/fs.json
   python - "$f" <<'PY'
 import json, sys
 j = json.load(open("/tmp/fs.json"))

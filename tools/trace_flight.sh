@@ -2,7 +2,7 @@
 # GPU-box helper: per-dispatch trace of a short run with four contexts in flight (bench.py default), reduced to: how much of the timed
 # window has 0 / 1 / 2 / 3+ kernels running, and per kernel the median gap to the previous dispatch OF ITS OWN QUEUE.
 root=$(pwd); export TMPDIR=/tmp; out=$root/gpurun_out/trace_flight; rm -rf $out; mkdir -p $out
-(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $out -o r -- python3 $root/bench.py --steps 200 --warmup 20 --repeats 1 --host-threads 1 --no-cpu-baseline > /dev/null 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $out -o r -- python3 $root/bench.py --full --steps 200 --warmup 20 --repeats 1 --host-threads 1 --no-cpu-baseline > /dev/null 2>&1)
 python3 - $(ls $out/*kernel_trace.csv $out/*/*kernel_trace.csv 2>/dev/null | head -1) <<'PY'
 import csv, sys, collections
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU-box helper: per-dispatch trace of a short one-frame-at-a-time run, reduced to the gap in front of every kernel of a frame (median over frames)
 root=$(pwd); export TMPDIR=/tmp; out=$root/gpurun_out/trace_gaps; rm -rf $out; mkdir -p $out
-(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $out -o r -- python3 $root/bench.py --steps 40 --warmup 5 --repeats 1 --frames-in-flight 1 --no-cpu-baseline > /dev/null 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $out -o r -- python3 $root/bench.py --full --steps 40 --warmup 5 --repeats 1 --frames-in-flight 1 --no-cpu-baseline > /dev/null 2>&1)
 python3 - $(ls $out/*kernel_trace.csv $out/*/*kernel_trace.csv 2>/dev/null | head -1) <<'PY'
 import csv, sys, collections
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
