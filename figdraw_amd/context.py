@@ -151,6 +151,12 @@ def load():
     L.fdh_replay_timed.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.fdh_profile.argtypes = [vp, C.c_int]
     L.fdh_get_frame_stats.argtypes = [vp, C.POINTER(FrameStats)]
+    # damage tracking (include/figdraw_hip_damage.h; absent from libraries built before it, which FIGDRAW_HIP_LIB may name for an A/B)
+    if hasattr(L, "fdh_set_damage_tracking"):
+        L.fdh_set_damage_tracking.argtypes = [vp, C.c_int]
+        L.fdh_damage_bins.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.fdh_damage_changed_bins.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.fdh_damage_closure.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     assert L.fdh_sizeof_fig() == C.sizeof(S.CFig), (L.fdh_sizeof_fig(), C.sizeof(S.CFig))
     assert L.fdh_sizeof_glyph() == C.sizeof(S.CGlyph)
     assert L.fdh_sizeof_draw_op() == C.sizeof(S.CDrawOp)
@@ -519,6 +525,44 @@ class HipContext:
     def set_blur_route(self, route: int):
         """blur routes: 1 the one-kernel routes (k_blur_fx / k_blur_small), 0 two passes per node, -1 the library's default = the one-kernel routes (same pixels either way)"""
         self._ck(self.L.fdh_set_blur_route(self.h, int(route)))
+
+    # ---- damage tracking (include/figdraw_hip_damage.h)
+    def set_damage_tracking(self, on: bool):
+        """composite only the 64x64 bins whose inputs changed since this context's previous frame (the rest of the surface keeps its
+        bytes); the surface is bit for bit what a full render of the last frame gives.  Refused on record-only contexts and under
+        set_stripe."""
+        self._ck(self.L.fdh_set_damage_tracking(self.h, 1 if on else 0))
+
+    def _bins(self, fn) -> np.ndarray:
+        bx, by, n = C.c_int(), C.c_int(), C.c_int()
+        self._ck(fn(self.h, None, 0, C.byref(bx), C.byref(by), C.byref(n)))
+        m = np.zeros((by.value, bx.value), dtype=np.uint8)
+        self._ck(fn(self.h, m.ctypes.data, m.size, C.byref(bx), C.byref(by), C.byref(n)))
+        return m.astype(bool)
+
+    def damage_bins(self) -> np.ndarray:
+        """which bins the last submitted frame composited: bool array (bins_y, bins_x); every bin for a frame rendered in full"""
+        return self._bins(self.L.fdh_damage_bins)
+
+    def damage_changed_bins(self) -> np.ndarray:
+        """the bins whose signature changed, before the blur rule (diagnostic)"""
+        return self._bins(self.L.fdh_damage_changed_bins)
+
+    @staticmethod
+    def damage_closure(changed, nodes=()) -> np.ndarray:
+        """the blur rule on the host: changed = bool array (bins_y, bins_x), nodes = [((x0, y0, x1, y1), radius), ...] (footprints in
+        pixels, exclusive ends; radius as given to draw_backdrop_blur) -> the closed damage, bool array of the same shape"""
+        L = load()
+        ch = np.ascontiguousarray(np.asarray(changed, dtype=bool).astype(np.uint8))
+        by, bx = ch.shape
+        rects = np.ascontiguousarray(np.array([r for r, _ in nodes], dtype=np.int32).reshape(-1, 4))
+        radii = np.ascontiguousarray(np.array([rad for _, rad in nodes], dtype=np.float32))
+        out = np.zeros_like(ch)
+        rc = L.fdh_damage_closure(ch.ctypes.data, bx, by, rects.ctypes.data if len(nodes) else None, radii.ctypes.data if len(nodes) else None,
+                                  len(nodes), out.ctypes.data)
+        if rc != 0:
+            raise FigdrawHipError(rc, L.fdh_last_error().decode())
+        return out.astype(bool)
 
     @staticmethod
     def comm_unique_id() -> bytes:

@@ -3,6 +3,7 @@
 #include <string>
 
 #include "fdh_context.h"
+#include "../../include/figdraw_hip_damage.h"
 
 using fdh::Context;
 
@@ -286,6 +287,16 @@ int fdh_gather_stripes(FdhContext* c, int dst_rank, void* dst_image) { return gu
 int fdh_gather_frames(FdhContext* c, int dst_rank, void* const* dst_images) { return guard([&] { C(c)->gather_frames(dst_rank, dst_images); }); }
 int fdh_set_blur_route(FdhContext* c, int route) { return guard([&] { C(c)->set_blur_route(route); }); }
 int fdh_set_stripe(FdhContext* c, int y0, int y1) { return guard([&] { C(c)->set_stripe(y0, y1); }); }
+int fdh_set_damage_tracking(FdhContext* c, int on) { return guard([&] { C(c)->set_damage_tracking(on != 0); }); }
+int fdh_damage_bins(FdhContext* c, uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged) {
+  return guard([&] { C(c)->damage_bins(mask, cap, bins_x, bins_y, n_damaged, false); });
+}
+int fdh_damage_changed_bins(FdhContext* c, uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_changed) {
+  return guard([&] { C(c)->damage_bins(mask, cap, bins_x, bins_y, n_changed, true); });
+}
+int fdh_damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out) {
+  return guard([&] { fdh::damage_closure(changed, bins_x, bins_y, rects, radii, n_nodes, out); });
+}
 int fdh_set_cull(FdhContext* c, int mode) { return guard([&] { C(c)->set_cull(mode); }); }
 int fdh_debug_host_times(FdhContext* c, int64_t out_ns[12]) {
   return guard([&] {

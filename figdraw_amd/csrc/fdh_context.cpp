@@ -6,6 +6,7 @@
 // fragment shaders.  Clip masks become push/pop records evaluated analytically per pixel, backdrop
 // blurs split the list into phases (a blur is a global barrier in painter's order, glcontext.nim:1788-1841).
 #include "fdh_context.h"
+#include "fdh_damage.h"
 #include "fdh_host.h"
 #include "fdh_walkpool.h"
 
@@ -194,6 +195,7 @@ Context::~Context() {
   if (alt_) (void)hipFree(alt_);
   if (dbg_snap_) (void)hipFree(dbg_snap_);
   d_frame_.release(); d_lists_.release(); d_counts_.release(); d_order_[0].release(); d_order_[1].release();
+  d_dmg_sig_.release(); d_dmg_changed_.release(); d_dmg_mask_.release(); d_dmg_run_.release(); d_dmg_list_.release(); d_dmg_count_.release(); d_dmg_keep_.release();
   glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); d_mask_spill_.release();
   for (auto& set : lanes_) set.clear();  // (pinned arrays: freed while the device is still this thread's)
   for (auto& m : misc_) m.release();
@@ -861,6 +863,25 @@ void Context::prepare(LaunchJob& J) {
     }
   }
   stats_.clear_folded = folded ? 1.0f : 0.0f;
+  // ---- damage tracking: the frame key -- everything a bin's pixels depend on besides its lists and the records they index.  A tracked frame
+  // whose key differs from the last tracked frame's is rendered in full (Context::launch_frame), and so is one the tracking launches cannot
+  // take: no clear (its starting pixels are not this frame's to rebuild), a full-frame blur that renders out of place (k_blur_fx flips the
+  // frame surface), more blur nodes than k_damage_resolve takes.  (atlas_epoch_ moves with every put, update, remove and reset: any atlas
+  // change is a full frame, on purpose.)
+  J.n_exts = (int)n_ext;
+  J.damage = damage_on_;
+  J.damage_force = !clear_ || J.n_fused > 0 || J.blurs.size() > (size_t)kDamageMaxNodes;
+  {
+    uint64_t k = 1469598103934665603ull;
+    auto mix = [&k](uint64_t v) { for (int b = 0; b < 8; b++) { k ^= (v >> (8 * b)) & 255u; k *= 1099511628211ull; } };
+    uint32_t aa_bits = 0, ps_bits = 0;
+    std::memcpy(&aa_bits, &ctx_aa_, 4); std::memcpy(&ps_bits, &pixel_scale_, 4);
+    mix((uint64_t)(uint32_t)W_ << 32 | (uint32_t)H_); mix((uint64_t)(uint32_t)J.bins_x << 32 | (uint32_t)J.bins_y);
+    mix((uint64_t)J.clear_rgba8 << 1 | (clear_ ? 1u : 0u)); mix((uint64_t)aa_bits << 32 | ps_bits);
+    mix(atlas_epoch_); mix((uint64_t)(uint32_t)atlas_size_);
+    mix((uint64_t)(latency_routes_ ? 1u : 0u) << 8 | (uint64_t)(uint32_t)cull_mode_);
+    J.damage_key = k;
+  }
   // ---- the slot's small print: chunk boxes, phase table, then the blur weight tables (when the device block does not hold them already)
   std::vector<size_t> layout{total, o_recs, o_ext, o_bb, o_box, o_chunk, o_pf, n, n_ext};
   for (size_t i = 0; i < J.blurs.size(); i++) { layout.push_back(o_mxh[i]); layout.push_back(o_mxv[i]); }
@@ -1145,7 +1166,7 @@ static bool direct_frame(const LaunchJob& J) {
     const int forced = f ? std::atoi(f) : 0;
     return (!e || std::atoi(e) != 0) && forced != 3 && forced != 8 && forced != 19;
   }();
-  if (!on || J.phases.empty()) return false;
+  if (!on || J.phases.empty() || J.damage) return false;  // (a tracked frame: its signatures are folded over the bin lists)
   for (const Phase& ph : J.phases)
     if (ph.count > 64 || ph.has_rot || ph.has_slow) return false;
   return true;
@@ -1247,11 +1268,73 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
   }
   if (!direct) launch_bin(stream_, B);
   span_end();
+  // Damage tracking (fdh_damage.h): the bins whose signatures changed since this context's last tracked frame, closed under the blur rule,
+  // as a compact list the compositor launches walk.  A frame whose key differs from that frame's is rendered in full (its signatures are
+  // still taken: the next frame compares against them).
+  const bool tracked = J.damage && nb > 0 && np > 0;
+  // the signatures this frame leaves describe it whole only when every one of its blur nodes was folded in (more nodes than
+  // kDamageMaxNodes: the frame is rendered in full, and so is the next)
+  const bool sig_whole = J.blurs.size() <= (size_t)kDamageMaxNodes;
+  // whatever this launch renders, the signatures and the surface stop matching until a tracked frame has been launched whole: a frame
+  // rendered without tracking leaves its pixels, not the signatures' frame, in the surface
+  const bool was_valid = dmg_valid_;
+  dmg_valid_ = false;
+  bool partial = false;
+  if (tracked) {
+    const bool full = J.damage_force || !sig_whole || !was_valid || dmg_key_ != J.damage_key;
+    const bool keep = !full && [&] { for (const BlurJob& j : J.blurs) if (j.fuse_draw >= 0) return true; return false; }();
+    if (d_dmg_sig_.cap < (size_t)nb || d_dmg_count_.cap == 0 || (keep && d_dmg_keep_.cap < (size_t)J.W * J.H)) {
+      FDH_HIP(hipStreamSynchronize(stream_));  // (a buffer that grows is freed: nothing in flight may still use it)
+      d_dmg_sig_.reserve(nb); d_dmg_changed_.reserve(nb); d_dmg_mask_.reserve(nb); d_dmg_list_.reserve(nb);
+      d_dmg_count_.reserve(1); d_dmg_run_.reserve(kDamageMaxNodes);
+      if (keep) d_dmg_keep_.reserve((size_t)J.W * J.H);
+    }
+    DamageSignParams S;
+    S.lists = J.lists; S.counts = J.counts; S.draws = dv_.recs; S.exts = dv_.exts; S.sig = d_dmg_sig_.ptr; S.changed = d_dmg_changed_.ptr;
+    S.n_phases = np; S.bins_x = bins_x_; S.bins_y = bins_y_; S.stride = list_stride_; S.n_draws = J.n_recs; S.n_exts = J.n_exts;
+    S.force = full ? 1 : 0;
+    S.sub_n = B.sub_n;
+    for (int p = 0; p < kDamageMaxPhases; p++) {
+      const bool in = p < B.sub_n;
+      S.sub_x0[p] = in ? B.sub_x0[p] : 0; S.sub_y0[p] = in ? B.sub_y0[p] : 0; S.sub_nx[p] = in ? B.sub_nx[p] : 0;
+      S.sub_ny[p] = in ? (B.sub_first[p + 1] - B.sub_first[p]) / std::max(1, B.sub_nx[p]) : 0;
+    }
+    S.n_nodes = std::min((int)J.blurs.size(), kDamageMaxNodes);
+    for (int i = 0; i < S.n_nodes; i++) {
+      const BlurJob& j = J.blurs[(size_t)i];
+      int phase = -1;
+      for (int p = 0; p < np; p++) if (J.phases[p].blur == i) phase = p;
+      uint32_t rbits = 0;
+      std::memcpy(&rbits, &j.radius, 4);
+      uint64_t k = 1469598103934665603ull;
+      for (uint32_t v : {(uint32_t)phase, (uint32_t)j.x0, (uint32_t)j.y0, (uint32_t)j.x1, (uint32_t)j.y1, rbits, (uint32_t)j.taps.reach, (uint32_t)(j.fuse_draw >= 0)})
+        for (int b = 0; b < 4; b++) { k ^= (v >> (8 * b)) & 255u; k *= 1099511628211ull; }
+      S.foot[i] = damage_region(j.x0, j.y0, j.x1, j.y1, 0, bins_x_, bins_y_);
+      S.node_key[i] = k;
+    }
+    DamageResolveParams R;
+    R.changed = d_dmg_changed_.ptr; R.mask = d_dmg_mask_.ptr; R.list = d_dmg_list_.ptr; R.count = d_dmg_count_.ptr; R.run = d_dmg_run_.ptr;
+    R.bins_x = bins_x_; R.bins_y = bins_y_; R.n_nodes = std::min((int)J.blurs.size(), kDamageMaxNodes);  // (more: a full frame, every bin changed)
+    for (int i = 0; i < R.n_nodes; i++) {
+      const BlurJob& j = J.blurs[(size_t)i];
+      R.reg[i] = damage_region(j.x0, j.y0, j.x1, j.y1, j.taps.reach, bins_x_, bins_y_);
+    }
+    span_begin(0);
+    launch_damage_sign(stream_, S);
+    span_end();
+    span_begin(0);
+    launch_damage_resolve(stream_, R);
+    span_end();
+    partial = !full;
+    dmg_bx_ = bins_x_; dmg_by_ = bins_y_;
+  }
+  dmg_last_ = tracked;
+  const int dmg_grid = nb * 16;  // (the compositor launches of a partial frame: one wave per strip of the frame, k_composite_damage)
   // Phase 0's full-grid composite takes its bins longest-list first, in the order its predecessor sorted (an extra
   // wavefront of that launch); it sorts this frame's counts for its successor.  Any permutation is a correct schedule.
   const int order_key = bins_x_ * 65536 + bins_y_;  // entries are (row << 16 | column) of THIS grid
   if (order_valid_ && order_nb_ != order_key) order_valid_ = false;  // frame size changed
-  const bool sorting = J.clear && np > 0 && nb <= 8192 && J.phases[0].count > 0 && !direct;  // (a direct frame has no counts to sort by)
+  const bool sorting = J.clear && np > 0 && nb <= 8192 && J.phases[0].count > 0 && !direct && !partial;  // (a direct frame has no counts to sort by)
   const int* order_now = (sorting && order_valid_) ? d_order_[order_read_].ptr : nullptr;
   int* order_next = nullptr;
   if (sorting) {
@@ -1328,6 +1411,10 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
         bp.fuse_draw = -1;
         bp.src = cur; bp.dst = blur_tmp_;
         bp.x0 = j.x0; bp.x1 = j.x1; bp.y0 = std::max(0, vy0 - j.taps.reach); bp.y1 = std::min(J.H, vy1 + j.taps.reach);
+        // a partial frame: a V pass that composites its quad into the surface runs whether the node took damage or not -- when it did not,
+        // its footprint is kept aside and put back (k_damage_guard: both return at once when the node's run flag is set)
+        const bool guard = partial && j.fuse_draw >= 0;
+        if (guard) launch_damage_guard(stream_, d_dmg_run_.ptr, ph.blur, false, cur, d_dmg_keep_.ptr, J.W, j.x0, vy0, j.x1, vy1);
         span_begin(ph.blur == big_blur_ ? 5 : 3);
         launch_blur_h(stream_, bp);
         span_end();
@@ -1338,6 +1425,7 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
         span_begin(ph.blur == big_blur_ ? 6 : 4);
         launch_blur_v(stream_, bp, dv_.recs, dv_.exts);
         span_end();
+        if (guard) launch_damage_guard(stream_, d_dmg_run_.ptr, ph.blur, true, cur, d_dmg_keep_.ptr, J.W, j.x0, vy0, j.x1, vy1);
         }
       }
     }
@@ -1373,10 +1461,12 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
     C.has_masks = ph.has_masks ? 1 : 0;
     C.mask_spill = J.mask_spill; C.spill_stride = J.spill_stride;
     span_begin(p == 0 ? 1 : 2);
-    launch_composite(stream_, dv_.recs, dv_.exts, C);
+    if (partial) launch_composite_damage(stream_, dv_.recs, dv_.exts, C, d_dmg_list_.ptr, d_dmg_count_.ptr, dmg_grid);
+    else launch_composite(stream_, dv_.recs, dv_.exts, C);
     span_end();
   }
   if (cur != fb_) std::swap(fb_, alt_);  // the frame ended in the other surface: it is the frame surface now
+  if (tracked && sig_whole) { dmg_valid_ = true; dmg_key_ = J.damage_key; }
   FDH_HIP(hipGetLastError());
 }
 
@@ -1482,6 +1572,48 @@ void Context::debug_read_surface(int which, uint8_t* out) {
   FDH_HIP(hipStreamSynchronize(stream_));
   FDH_HIP(hipMemcpy(out, src, (size_t)W_ * H_ * 4, hipMemcpyDeviceToHost));
 }
+// ------------------------------------------------------------------ damage tracking (include/figdraw_hip_damage.h)
+void Context::set_damage_tracking(bool on) {
+  if (on && host_only_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_tracking: a record-only context composites nothing");
+  drain();
+  if (on && stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_tracking: not under fdh_set_stripe");
+  damage_on_ = on;
+}
+void Context::damage_bins(uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged, bool changed_only) {
+  need_device("fdh_damage_bins");
+  drain();
+  if (!have_frame_) throw Error(FDH_ERR_INVALID, "fdh_damage_bins: no frame has been submitted");
+  const int gx = job_.bins_x, gy = job_.bins_y, nb = gx * gy;
+  if (mask && cap < nb) throw Error(FDH_ERR_INVALID, "fdh_damage_bins: the mask holds fewer bytes than the frame has bins");
+  FDH_HIP(hipSetDevice(device_));
+  FDH_HIP(hipStreamSynchronize(stream_));
+  std::vector<uint8_t> m((size_t)nb, 1);  // a frame rendered without tracking: every bin
+  if (dmg_last_ && dmg_bx_ == gx && dmg_by_ == gy && nb > 0)
+    FDH_HIP(hipMemcpy(m.data(), changed_only ? d_dmg_changed_.ptr : d_dmg_mask_.ptr, (size_t)nb, hipMemcpyDeviceToHost));
+  int n = 0;
+  for (uint8_t v : m) n += v ? 1 : 0;
+  if (mask) std::memcpy(mask, m.data(), (size_t)nb);
+  if (bins_x) *bins_x = gx;
+  if (bins_y) *bins_y = gy;
+  if (n_damaged) *n_damaged = n;
+}
+void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out) {
+  if (bins_x < 0 || bins_y < 0 || n_nodes < 0 || n_nodes > kDamageMaxNodes) throw Error(FDH_ERR_INVALID, "fdh_damage_closure: bad grid or node count");
+  const size_t nb = (size_t)bins_x * bins_y;
+  if (nb && (!changed || !out)) throw Error(FDH_ERR_INVALID, "fdh_damage_closure: null mask");
+  if (n_nodes && (!rects || !radii)) throw Error(FDH_ERR_INVALID, "fdh_damage_closure: null node arrays");
+  std::vector<DamageRegion> reg((size_t)n_nodes);
+  for (int i = 0; i < n_nodes; i++) {
+    const int* r = rects + 4 * i;
+    const int reach = radii[i] > 0.0f ? make_taps(radii[i]).reach : 0;
+    reg[(size_t)i] = damage_region(r[0], r[1], r[2], r[3], reach, bins_x, bins_y);
+  }
+  std::vector<uint8_t> m(nb), run((size_t)n_nodes + 1);
+  for (size_t b = 0; b < nb; b++) m[b] = changed[b] ? 1 : 0;
+  damage_close(m.data(), bins_x, reg.data(), n_nodes, run.data(), DamageHostTeam());
+  if (nb) std::memcpy(out, m.data(), nb);
+}
+
 void Context::frame_device_ptr(void** p, int* w, int* h, int64_t* pitch_bytes) {
   need_device("frame_device_ptr");
   drain();

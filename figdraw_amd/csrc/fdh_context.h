@@ -392,6 +392,11 @@ struct LaunchJob {
   UploadTable table;       // (filled from `runs` when the frame is issued)
   void* d_dst = nullptr;
   int staging_slot = -1;
+  // damage tracking (fdh_set_damage_tracking): the frame is tracked; it is rendered in full whatever its key (no clear, a fused full-frame
+  // blur, more blur nodes than the resolve takes); the frame key (Context::prepare: everything outside the lists a bin's pixels depend on)
+  bool damage = false, damage_force = false;
+  uint64_t damage_key = 0;
+  int n_exts = 0;
 };
 
 class Context : public Recorder {
@@ -456,7 +461,14 @@ class Context : public Recorder {
   int comm_world() const { return comm_ ? comm_world_ : 1; }
 
   // multi-GPU / measurement
-  void set_stripe(int y0, int y1) { drain(); stripe_y0_ = y0; stripe_y1_ = y1; }
+  void set_stripe(int y0, int y1) {
+    drain();
+    if (damage_on_ && y1 > y0) throw Error(FDH_ERR_INVALID, "fdh_set_stripe: damage tracking is on (fdh_set_damage_tracking: not under row stripes)");
+    stripe_y0_ = y0; stripe_y1_ = y1;
+  }
+  // damage tracking (include/figdraw_hip_damage.h)
+  void set_damage_tracking(bool on);
+  void damage_bins(uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged, bool changed_only);
   // Culling (fdh_set_cull): draws whose pixel bounds miss the frame -- or, under fdh_set_stripe, the stripe's rows widened by the
   // reach of the scene's blur nodes -- are not recorded, and the scene front-end skips the content of a clipping node whose mask
   // lies outside.  0 off, 1 on (default; off while the call recorder runs, so that recorded streams stay the reference's), 2 on
@@ -601,6 +613,17 @@ class Context : public Recorder {
   DeviceBuf<uint2> d_lists_;
   DeviceBuf<uint32_t> d_counts_;
   DeviceBuf<int> d_order_[2];  // phase 0's bins, longest list first: read by this frame's launch / written for the next
+  // damage tracking (submission side): the per-bin signatures of the last tracked frame, what its resolve left, the footprint a fused V
+  // pass of a node that did not run writes over (k_damage_guard); dmg_valid_: the surface holds the frame of key dmg_key_ and the
+  // signatures are that frame's
+  bool damage_on_ = false;  // (calling thread: fdh_set_damage_tracking)
+  bool dmg_valid_ = false, dmg_last_ = false;
+  uint64_t dmg_key_ = 0;
+  int dmg_bx_ = 0, dmg_by_ = 0;
+  DeviceBuf<uint64_t> d_dmg_sig_;
+  DeviceBuf<uint8_t> d_dmg_changed_, d_dmg_mask_, d_dmg_run_;
+  DeviceBuf<int> d_dmg_list_;
+  DeviceBuf<uint32_t> d_dmg_count_, d_dmg_keep_;
   int order_read_ = 0, order_nb_ = 0;
   bool order_valid_ = false;
   // kStaging sets of lanes in rotation, each released when the upload that reads it has run (the bin launch behind it says so
@@ -657,6 +680,7 @@ void record_host_form(DrawRec& r);  // undo the device form of a committed recor
 void stripe_rows(int height, int world, int rank, int* y0, int* y1);
 void comm_unique_id(uint8_t out[FDH_COMM_ID_BYTES]);
 void blur_weight_fragments(float blur_radius, bool vertical, float* dense, uint16_t* frag_bits, int* reach, int* k_steps);
+void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out);
 void saturated_core_of(const float rect[4], const float rx[4], const float ry[4], int mode, float factor, float spread,
                        const float shape[2], float aa, int out[4]);
 

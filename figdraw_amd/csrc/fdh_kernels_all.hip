@@ -5,3 +5,4 @@
 #include "k_blur_valu.hip"
 #include "k_blur_mx.hip"
 #include "k_atlas_upload.hip"
+#include "k_damage.hip"

@@ -21,6 +21,7 @@
 // build, and the note at shadow_profile() says how the source keeps it so.  Instrumented builds (FDH_STATS, FDH_TIMING:
 // device-side counters) are single-unit builds (`make variant SINGLE=1`).
 #include "fdh_device.h"
+#include "fdh_damage.h"
 
 #ifndef FDH_TU
 #define FDH_TU 0
@@ -523,7 +524,82 @@ __device__ __forceinline__ void composite_strip(const CompositeParams& P, const 
 #include "k_composite_strip.inc"
 }
 
+// The compositor launch of a tracked frame (fdh_set_damage_tracking, fdh_damage.h): its waves take their strips from the compact list of
+// damaged bins k_damage_resolve left (16 strips per listed bin) instead of from the launch's bin box or `order`; a listed bin outside this
+// launch's box (a later phase's) is not this launch's.  The strip is shaded as k_composite_tiles shades it (composite_strip, the same build
+// per kPaths); no sorting wave, no deep strips.  The grid is sized on the host before the count is known: one wave per strip of the frame,
+// those beyond the list exiting at once.  (A fixed grid whose waves walk the listed strips was the first form: the loop around the strip
+// puts the strip's divergent epilogue inside the draw loop nest, which the uniform-regions unit must not have -- tools/lint_isa.py --, and
+// it spilled; profiles/damage_bench.txt.)
+template <int kPaths, bool kFull>
+__global__ __launch_bounds__(64, (kPaths & 16) ? kSlowAtlasWaves : (kPaths & 1) ? kSlowWaves : kPaths == 4 ? kUniformWaves : (kPaths & 2) ? kAtlasWaves : (kPaths & 8) ? kRotWaves : kFastWaves) void k_composite_damage(
+    const int* __restrict__ dmg_list, const uint32_t* __restrict__ dmg_count, const DrawRec* __restrict__ draws, const QuadExt* __restrict__ exts,
+    const CompositeParams P_in) {
+  constexpr int kStripsPerBin = kWgsPerBin * kWavesPerWg;  // 16
+  const int i = (int)blockIdx.x;
+  if (i >= (int)dmg_count[0] * kStripsPerBin) return;
+  CompositeParams P = P_in;
+  P.order = nullptr; P.order_next = nullptr; P.deep_k8 = 0; P.deep_out = nullptr; P.direct = 0;
+  if (kFull) P.load_fb = 0;
+  extern __shared__ uint32_t composite_lds[];
+  const int lane = threadIdx.x & 63;
+  const int bin = dmg_list[i / kStripsPerBin];
+  const int sidx = i % kStripsPerBin;
+  const int bin_y = bin / P.bins_x, bin_x = bin - bin_y * P.bins_x;
+  if (bin_x < P.bin_x0 || bin_x >= P.bin_x0 + P.bin_nx || bin_y < P.bin_y0 || bin_y >= P.bin_y0 + P.bin_ny) return;
+  const int j = sidx >> 2, wave = sidx & 3;
+  const int sbit = j * 4 + wave;
+  const int tx0 = bin_x * kBin + (j & 1) * kWgW;
+  const int ty0 = bin_y * kBin + (j >> 1) * kWgH + wave * kTileH;
+  if (tx0 >= P.W) return;
+  asm volatile("");
+  if (ty0 >= P.H) return;
+  asm volatile("");
+  if (ty0 + kTileH <= P.row_lo) return;
+  asm volatile("");
+  if (ty0 >= P.row_hi) return;
+  composite_strip<kPaths, kFull, 0>(P, draws, exts, composite_lds, bin, sidx, sbit, tx0, ty0, lane, 0);
+}
+template <int kPaths>
+static void launch_damage_paths(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts,
+                                const CompositeParams& P, const int* list, const uint32_t* count) {
+  if (P.load_fb == 0) {
+    if (e0) hipExtLaunchKernelGGL((k_composite_damage<kPaths, true>), dim3(grid), dim3(64), lds, s, e0, e1, 0, list, count, draws, exts, P);
+    else hipLaunchKernelGGL((k_composite_damage<kPaths, true>), dim3(grid), dim3(64), lds, s, list, count, draws, exts, P);
+  } else {
+    if (e0) hipExtLaunchKernelGGL((k_composite_damage<kPaths, false>), dim3(grid), dim3(64), lds, s, e0, e1, 0, list, count, draws, exts, P);
+    else hipLaunchKernelGGL((k_composite_damage<kPaths, false>), dim3(grid), dim3(64), lds, s, list, count, draws, exts, P);
+  }
+}
+
 #if FDH_TU == 0
+void launch_composite_damage_uniform(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts,
+                                     const CompositeParams& P, const int* list, const uint32_t* count, int paths);  // FDH_TU 1
+void launch_composite_damage(hipStream_t s, const DrawRec* draws, const QuadExt* exts, CompositeParams P, const int* list, const uint32_t* count,
+                             int grid) {
+  if (grid <= 0 || P.bin_nx <= 0 || P.bin_ny <= 0) return;
+  // (the build choice and FDH_FORCE_KERNEL_PATHS as launch_composite makes them)
+  static const int force = [] { const char* e = std::getenv("FDH_FORCE_KERNEL_PATHS"); return e ? std::atoi(e) : 0; }();
+  if (force == 3) { P.has_slow = 1; P.has_slow_atlas = 0; }
+  if (force == 19) { P.has_slow = 1; P.has_slow_atlas = 1; }
+  if (force == 8) P.has_rot = 1;
+  if (force == 2) P.has_atlas = 1;
+  if (force == 1) P.has_masks = 1;
+  const size_t lds = (P.has_masks ? sizeof(uint32_t) * kMaskDepth * 64 : sizeof(uint32_t) * 256) +
+                     ((P.has_atlas || P.has_slow || (P.has_rot && P.has_atlas)) ? sizeof(uint32_t) * kWinRows * kWinStride : 0);
+  P.n_wg = grid;
+  hipEvent_t e0 = t_prof_start, e1 = t_prof_stop;
+  if (P.has_slow || (P.has_rot && P.has_atlas)) { if (P.has_slow_atlas) launch_damage_paths<19>(s, e0, e1, grid, lds, draws, exts, P, list, count); else launch_damage_paths<3>(s, e0, e1, grid, lds, draws, exts, P, list, count); }
+  else if (P.has_rot) launch_damage_paths<8>(s, e0, e1, grid, lds, draws, exts, P, list, count);
+#if FDH_SPLIT_UNIFORM
+  else launch_composite_damage_uniform(s, e0, e1, grid, lds, draws, exts, P, list, count, P.has_atlas ? 2 : P.has_masks ? 0 : 4);
+#else
+  else if (P.has_atlas) launch_damage_paths<2>(s, e0, e1, grid, lds, draws, exts, P, list, count);
+  else if (P.has_masks) launch_damage_paths<0>(s, e0, e1, grid, lds, draws, exts, P, list, count);
+  else launch_damage_paths<4>(s, e0, e1, grid, lds, draws, exts, P, list, count);
+#endif
+  if (e0) t_prof_used = true;
+}
 void launch_composite_uniform(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P, int paths);  // FDH_TU 1
 void launch_composite(hipStream_t s, const DrawRec* draws, const QuadExt* exts, CompositeParams P) {
   const int n = P.bin_nx * P.bin_ny * kWgsPerBin;
@@ -599,6 +675,12 @@ void launch_composite_uniform(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int g
   if (paths == 2) launch_uniform<2>(s, e0, e1, grid, lds, draws, exts, P);
   else if (paths == 0) launch_uniform<0>(s, e0, e1, grid, lds, draws, exts, P);
   else launch_uniform<4>(s, e0, e1, grid, lds, draws, exts, P);
+}
+void launch_composite_damage_uniform(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts,
+                                     const CompositeParams& P, const int* list, const uint32_t* count, int paths) {
+  if (paths == 2) launch_damage_paths<2>(s, e0, e1, grid, lds, draws, exts, P, list, count);
+  else if (paths == 0) launch_damage_paths<0>(s, e0, e1, grid, lds, draws, exts, P, list, count);
+  else launch_damage_paths<4>(s, e0, e1, grid, lds, draws, exts, P, list, count);
 }
 #endif  // FDH_TU
 }  // namespace fdh
