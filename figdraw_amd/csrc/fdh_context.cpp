@@ -864,7 +864,7 @@ void Context::prepare(LaunchJob& J) {
   }
   stats_.clear_folded = folded ? 1.0f : 0.0f;
   // ---- damage tracking: the frame key -- everything a bin's pixels depend on besides its lists and the records they index.  A tracked frame
-  // whose key differs from the last tracked frame's is rendered in full (Context::launch_frame), and so is one the tracking launches cannot
+  // whose key differs from the last tracked frame's is rendered in full (Context::launch_damage), and so is one the tracking launches cannot
   // take: no clear (its starting pixels are not this frame's to rebuild), a full-frame blur that renders out of place (k_blur_fx flips the
   // frame surface), more blur nodes than k_damage_resolve takes.  (atlas_epoch_ moves with every put, update, remove and reset: any atlas
   // change is a full frame, on purpose.)
@@ -1160,13 +1160,10 @@ int Context::walk_threads() const { return walk_threads_ >= 0 ? walk_threads_ : 
 static bool direct_frame(const LaunchJob& J) {
   // (FDH_FORCE_KERNEL_PATHS=3 / 19 / 8, the test hook that puts a frame on the builds with the slot path / the rotated-quad path: those
   // have no direct form)
-  static const bool on = [] {
-    const char* e = std::getenv("FDH_DIRECT");
-    const char* f = std::getenv("FDH_FORCE_KERNEL_PATHS");
-    const int forced = f ? std::atoi(f) : 0;
-    return (!e || std::atoi(e) != 0) && forced != 3 && forced != 8 && forced != 19;
-  }();
-  if (!on || J.phases.empty() || J.damage) return false;  // (a tracked frame: its signatures are folded over the bin lists)
+  static const bool on = [] { const char* e = std::getenv("FDH_DIRECT"); return !e || std::atoi(e) != 0; }();
+  const int forced = forced_kernel_paths();
+  if (!on || forced == 3 || forced == 8 || forced == 19) return false;
+  if (J.phases.empty() || J.damage) return false;  // (a tracked frame: its signatures are folded over the bin lists)
   for (const Phase& ph : J.phases)
     if (ph.count > 64 || ph.has_rot || ph.has_slow) return false;
   return true;
@@ -1216,40 +1213,38 @@ void Context::issue(LaunchJob& J) {
 }
 
 
-void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq) {
-  const int bins_x_ = J.bins_x, bins_y_ = J.bins_y, list_stride_ = J.list_stride, binbox_shift_ = J.binbox_shift, big_blur_ = J.big_blur;
-  const std::vector<const uint4*>&mx_w_h_ = J.mx_w_h, &mx_w_v_ = J.mx_w_v;
-  const LaunchJob::View& dv_ = J.dv;
-  const int nb = bins_x_ * bins_y_;
+// ---- launch_frame's stages
+// profile mode: every launch stamps its own pair of events (set_launch_events: the kernel's execution time, no gaps)
+void Context::span_begin(SpanKind kind) { if (profiling_) { Span sp{kind, next_event(), next_event()}; set_launch_events(sp.a, sp.b); spans_.push_back(sp); } }
+void Context::span_end() { if (profiling_) { if (!launch_events_used()) spans_.pop_back(); set_launch_events(nullptr, nullptr); } }
+
+// rows each phase has to produce: the stripe, widened by the vertical reach of every later blur
+void Context::phase_rows(const LaunchJob& J, std::vector<int>& lo, std::vector<int>& hi) const {
   const int np = (int)J.phases.size();
-  // rows each phase has to produce: the stripe, widened by the vertical reach of every later blur
   int s0 = 0, s1 = J.H;
   if (stripe_y1_ > stripe_y0_) { s0 = std::max(0, stripe_y0_); s1 = std::min(J.H, stripe_y1_); }
-  std::vector<int> lo(np), hi(np);
-  {
-    int l = s0, h = s1;
-    for (int p = np - 1; p >= 0; p--) {
-      lo[p] = l; hi[p] = h;
-      if (J.phases[p].blur >= 0) {
-        const int reach = J.blurs[J.phases[p].blur].taps.reach;
-        l = std::max(0, l - reach);
-        h = std::min(J.H, h + reach);
-      }
+  lo.assign(np, 0); hi.assign(np, 0);
+  int l = s0, h = s1;
+  for (int p = np - 1; p >= 0; p--) {
+    lo[p] = l; hi[p] = h;
+    if (J.phases[p].blur >= 0) {
+      const int reach = J.blurs[J.phases[p].blur].taps.reach;
+      l = std::max(0, l - reach);
+      h = std::min(J.H, h + reach);
     }
-    // the records were culled to rows [rec_y0, rec_y1) when they were made (fdh_set_cull): every row a phase produces must lie inside
-    if (s1 > s0 && (l < J.rec_y0 || h > J.rec_y1))
-      throw Error(FDH_ERR_INVALID, "the resident draw records were culled to another row stripe: render the frame again after fdh_set_stripe (or fdh_set_cull(0))");
   }
-  // profile mode: every launch stamps its own pair of events (set_launch_events: the kernel's execution time, no gaps)
-  auto span_begin = [&](int kind) { if (profile) { Span sp{kind, next_event(), next_event()}; set_launch_events(sp.a, sp.b); spans_.push_back(sp); } };
-  auto span_end = [&]() { if (profile) { if (!launch_events_used()) spans_.pop_back(); set_launch_events(nullptr, nullptr); } };
-  const bool direct = direct_frame(J);
-  span_begin(0);
+  // the records were culled to rows [rec_y0, rec_y1) when they were made (fdh_set_cull): every row a phase produces must lie inside
+  if (s1 > s0 && (l < J.rec_y0 || h > J.rec_y1))
+    throw Error(FDH_ERR_INVALID, "the resident draw records were culled to another row stripe: render the frame again after fdh_set_stripe (or fdh_set_cull(0))");
+}
+
+BinParams Context::bin_params(const LaunchJob& J, uint32_t upload_seq) const {
+  const int np = (int)J.phases.size();
   BinParams B;
-  B.binrec = dv_.binrecs; B.binbox = dv_.binbox; B.chunkbox = dv_.chunkbox; B.n_draws = J.n_recs; B.binbox_shift = binbox_shift_; B.lists = J.lists; B.counts = J.counts; B.phase_first = dv_.phase_first; B.draws = dv_.recs; B.exts = dv_.exts;
+  B.binrec = J.dv.binrecs; B.binbox = J.dv.binbox; B.chunkbox = J.dv.chunkbox; B.n_draws = J.n_recs; B.binbox_shift = J.binbox_shift; B.lists = J.lists; B.counts = J.counts; B.phase_first = J.dv.phase_first; B.draws = J.dv.recs; B.exts = J.dv.exts;
   B.refine = 0;
   for (const Phase& ph : J.phases) if (ph.has_rot || ph.has_slow) B.refine = 1;
-  B.n_phases = np; B.bins_x = bins_x_; B.bins_y = bins_y_; B.stride = list_stride_;
+  B.n_phases = np; B.bins_x = J.bins_x; B.bins_y = J.bins_y; B.stride = J.list_stride;
   if (upload_seq) { B.seq_out = const_cast<uint32_t*>(seq_host_); B.seq = upload_seq; }
   static const bool sub_on = [] { const char* e = std::getenv("FDH_BIN_SUBGRIDS"); return !e || std::atoi(e) != 0; }();
   if (sub_on && np >= 1 && np <= BinParams::kBinSubs) {  // later phases: the bins their compositor launch reads (the same Phase::bin_* box)
@@ -1258,7 +1253,7 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
       const Phase& ph = J.phases[p];
       const bool whole = p == 0;
       const int x0 = whole ? 0 : std::max(0, ph.bin_x0), y0 = whole ? 0 : std::max(0, ph.bin_y0);
-      const int x1 = whole ? bins_x_ : std::min(bins_x_, ph.bin_x1), y1 = whole ? bins_y_ : std::min(bins_y_, ph.bin_y1);
+      const int x1 = whole ? J.bins_x : std::min(J.bins_x, ph.bin_x1), y1 = whole ? J.bins_y : std::min(J.bins_y, ph.bin_y1);
       const int nx = std::max(0, x1 - x0), ny = std::max(0, y1 - y0);
       B.sub_first[p] = at; B.sub_x0[p] = x0; B.sub_y0[p] = y0; B.sub_nx[p] = std::max(1, nx);
       at += nx * ny;
@@ -1266,81 +1261,79 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
     B.sub_first[np] = at;
     B.sub_n = np;
   }
-  if (!direct) launch_bin(stream_, B);
-  span_end();
-  // Damage tracking (fdh_damage.h): the bins whose signatures changed since this context's last tracked frame, closed under the blur rule,
-  // as a compact list the compositor launches walk.  A frame whose key differs from that frame's is rendered in full (its signatures are
-  // still taken: the next frame compares against them).
+  return B;
+}
+
+// the signatures a tracked frame leaves describe it whole only when every one of its blur nodes was folded in (more nodes than
+// kDamageMaxNodes: the frame is rendered in full, and so is the next)
+static bool damage_sig_whole(const LaunchJob& J) { return J.blurs.size() <= (size_t)kDamageMaxNodes; }
+
+// Damage tracking (fdh_damage.h): the bins whose signatures changed since this context's last tracked frame, closed under the blur rule,
+// as a compact list the compositor launches walk.  A frame whose key differs from that frame's is rendered in full (its signatures are
+// still taken: the next frame compares against them).
+bool Context::launch_damage(const LaunchJob& J, const BinParams& B) {
+  const int nb = J.bins_x * J.bins_y, np = (int)J.phases.size();
   const bool tracked = J.damage && nb > 0 && np > 0;
-  // the signatures this frame leaves describe it whole only when every one of its blur nodes was folded in (more nodes than
-  // kDamageMaxNodes: the frame is rendered in full, and so is the next)
-  const bool sig_whole = J.blurs.size() <= (size_t)kDamageMaxNodes;
   // whatever this launch renders, the signatures and the surface stop matching until a tracked frame has been launched whole: a frame
   // rendered without tracking leaves its pixels, not the signatures' frame, in the surface
   const bool was_valid = dmg_valid_;
   dmg_valid_ = false;
-  bool partial = false;
-  if (tracked) {
-    const bool full = J.damage_force || !sig_whole || !was_valid || dmg_key_ != J.damage_key;
-    const bool keep = !full && [&] { for (const BlurJob& j : J.blurs) if (j.fuse_draw >= 0) return true; return false; }();
-    if (d_dmg_sig_.cap < (size_t)nb || d_dmg_count_.cap == 0 || (keep && d_dmg_keep_.cap < (size_t)J.W * J.H)) {
-      FDH_HIP(hipStreamSynchronize(stream_));  // (a buffer that grows is freed: nothing in flight may still use it)
-      d_dmg_sig_.reserve(nb); d_dmg_changed_.reserve(nb); d_dmg_mask_.reserve(nb); d_dmg_list_.reserve(nb);
-      d_dmg_count_.reserve(1); d_dmg_run_.reserve(kDamageMaxNodes);
-      if (keep) d_dmg_keep_.reserve((size_t)J.W * J.H);
-    }
-    DamageSignParams S;
-    S.lists = J.lists; S.counts = J.counts; S.draws = dv_.recs; S.exts = dv_.exts; S.sig = d_dmg_sig_.ptr; S.changed = d_dmg_changed_.ptr;
-    S.n_phases = np; S.bins_x = bins_x_; S.bins_y = bins_y_; S.stride = list_stride_; S.n_draws = J.n_recs; S.n_exts = J.n_exts;
-    S.force = full ? 1 : 0;
-    S.sub_n = B.sub_n;
-    for (int p = 0; p < kDamageMaxPhases; p++) {
-      const bool in = p < B.sub_n;
-      S.sub_x0[p] = in ? B.sub_x0[p] : 0; S.sub_y0[p] = in ? B.sub_y0[p] : 0; S.sub_nx[p] = in ? B.sub_nx[p] : 0;
-      S.sub_ny[p] = in ? (B.sub_first[p + 1] - B.sub_first[p]) / std::max(1, B.sub_nx[p]) : 0;
-    }
-    S.n_nodes = std::min((int)J.blurs.size(), kDamageMaxNodes);
-    for (int i = 0; i < S.n_nodes; i++) {
-      const BlurJob& j = J.blurs[(size_t)i];
-      int phase = -1;
-      for (int p = 0; p < np; p++) if (J.phases[p].blur == i) phase = p;
-      uint32_t rbits = 0;
-      std::memcpy(&rbits, &j.radius, 4);
-      uint64_t k = 1469598103934665603ull;
-      for (uint32_t v : {(uint32_t)phase, (uint32_t)j.x0, (uint32_t)j.y0, (uint32_t)j.x1, (uint32_t)j.y1, rbits, (uint32_t)j.taps.reach, (uint32_t)(j.fuse_draw >= 0)})
-        for (int b = 0; b < 4; b++) { k ^= (v >> (8 * b)) & 255u; k *= 1099511628211ull; }
-      S.foot[i] = damage_region(j.x0, j.y0, j.x1, j.y1, 0, bins_x_, bins_y_);
-      S.node_key[i] = k;
-    }
-    DamageResolveParams R;
-    R.changed = d_dmg_changed_.ptr; R.mask = d_dmg_mask_.ptr; R.list = d_dmg_list_.ptr; R.count = d_dmg_count_.ptr; R.run = d_dmg_run_.ptr;
-    R.bins_x = bins_x_; R.bins_y = bins_y_; R.n_nodes = std::min((int)J.blurs.size(), kDamageMaxNodes);  // (more: a full frame, every bin changed)
-    for (int i = 0; i < R.n_nodes; i++) {
-      const BlurJob& j = J.blurs[(size_t)i];
-      R.reg[i] = damage_region(j.x0, j.y0, j.x1, j.y1, j.taps.reach, bins_x_, bins_y_);
-    }
-    span_begin(0);
-    launch_damage_sign(stream_, S);
-    span_end();
-    span_begin(0);
-    launch_damage_resolve(stream_, R);
-    span_end();
-    partial = !full;
-    dmg_bx_ = bins_x_; dmg_by_ = bins_y_;
+  if (!tracked) { dmg_last_ = false; return false; }
+  const bool full = J.damage_force || !damage_sig_whole(J) || !was_valid || dmg_key_ != J.damage_key;
+  const bool keep = !full && [&] { for (const BlurJob& j : J.blurs) if (j.fuse_draw >= 0) return true; return false; }();
+  if (d_dmg_sig_.cap < (size_t)nb || d_dmg_count_.cap == 0 || (keep && d_dmg_keep_.cap < (size_t)J.W * J.H)) {
+    FDH_HIP(hipStreamSynchronize(stream_));  // (a buffer that grows is freed: nothing in flight may still use it)
+    d_dmg_sig_.reserve(nb); d_dmg_changed_.reserve(nb); d_dmg_mask_.reserve(nb); d_dmg_list_.reserve(nb);
+    d_dmg_count_.reserve(1); d_dmg_run_.reserve(kDamageMaxNodes);
+    if (keep) d_dmg_keep_.reserve((size_t)J.W * J.H);
   }
-  dmg_last_ = tracked;
-  const int dmg_grid = nb * 16;  // (the compositor launches of a partial frame: one wave per strip of the frame, k_composite_damage)
-  // Phase 0's full-grid composite takes its bins longest-list first, in the order its predecessor sorted (an extra
-  // wavefront of that launch); it sorts this frame's counts for its successor.  Any permutation is a correct schedule.
-  const int order_key = bins_x_ * 65536 + bins_y_;  // entries are (row << 16 | column) of THIS grid
+  DamageSignParams S;
+  S.lists = J.lists; S.counts = J.counts; S.draws = J.dv.recs; S.exts = J.dv.exts; S.sig = d_dmg_sig_.ptr; S.changed = d_dmg_changed_.ptr;
+  S.n_phases = np; S.bins_x = J.bins_x; S.bins_y = J.bins_y; S.stride = J.list_stride; S.n_draws = J.n_recs; S.n_exts = J.n_exts;
+  S.force = full ? 1 : 0;
+  S.sub_n = B.sub_n;
+  for (int p = 0; p < kDamageMaxPhases; p++) {
+    const bool in = p < B.sub_n;
+    S.sub_x0[p] = in ? B.sub_x0[p] : 0; S.sub_y0[p] = in ? B.sub_y0[p] : 0; S.sub_nx[p] = in ? B.sub_nx[p] : 0;
+    S.sub_ny[p] = in ? (B.sub_first[p + 1] - B.sub_first[p]) / std::max(1, B.sub_nx[p]) : 0;
+  }
+  DamageResolveParams R;
+  R.changed = d_dmg_changed_.ptr; R.mask = d_dmg_mask_.ptr; R.list = d_dmg_list_.ptr; R.count = d_dmg_count_.ptr; R.run = d_dmg_run_.ptr;
+  R.bins_x = J.bins_x; R.bins_y = J.bins_y;
+  S.n_nodes = R.n_nodes = std::min((int)J.blurs.size(), kDamageMaxNodes);  // (more: a full frame, every bin changed)
+  for (int i = 0; i < S.n_nodes; i++) {
+    const BlurJob& j = J.blurs[(size_t)i];
+    int phase = -1;
+    for (int p = 0; p < np; p++) if (J.phases[p].blur == i) phase = p;
+    uint32_t rbits = 0;
+    std::memcpy(&rbits, &j.radius, 4);
+    uint64_t k = 1469598103934665603ull;
+    for (uint32_t v : {(uint32_t)phase, (uint32_t)j.x0, (uint32_t)j.y0, (uint32_t)j.x1, (uint32_t)j.y1, rbits, (uint32_t)j.taps.reach, (uint32_t)(j.fuse_draw >= 0)})
+      for (int b = 0; b < 4; b++) { k ^= (v >> (8 * b)) & 255u; k *= 1099511628211ull; }
+    S.foot[i] = damage_region(j.x0, j.y0, j.x1, j.y1, 0, J.bins_x, J.bins_y);
+    S.node_key[i] = k;
+    R.reg[i] = damage_region(j.x0, j.y0, j.x1, j.y1, j.taps.reach, J.bins_x, J.bins_y);
+  }
+  span_begin(kSpanBin); launch_damage_sign(stream_, S); span_end();
+  span_begin(kSpanBin); launch_damage_resolve(stream_, R); span_end();
+  dmg_bx_ = J.bins_x; dmg_by_ = J.bins_y;
+  dmg_last_ = true;
+  return !full;
+}
+
+// Phase 0's full-grid composite takes its bins longest-list first, in the order its predecessor sorted (an extra wavefront of that
+// launch); it sorts this frame's counts for its successor.  Any permutation is a correct schedule.
+Context::Schedule Context::schedule(const LaunchJob& J, bool direct, bool partial) {
+  const int nb = J.bins_x * J.bins_y;
+  Schedule S;
+  const int order_key = J.bins_x * 65536 + J.bins_y;  // entries are (row << 16 | column) of THIS grid
   if (order_valid_ && order_nb_ != order_key) order_valid_ = false;  // frame size changed
-  const bool sorting = J.clear && np > 0 && nb <= 8192 && J.phases[0].count > 0 && !direct && !partial;  // (a direct frame has no counts to sort by)
-  const int* order_now = (sorting && order_valid_) ? d_order_[order_read_].ptr : nullptr;
-  int* order_next = nullptr;
+  const bool sorting = J.clear && !J.phases.empty() && nb <= 8192 && J.phases[0].count > 0 && !direct && !partial;  // (a direct frame has no counts to sort by)
   if (sorting) {
+    S.order_now = order_valid_ ? d_order_[order_read_].ptr : nullptr;
     const int wr = order_valid_ ? 1 - order_read_ : order_read_;
     d_order_[wr].reserve(nb);
-    order_next = d_order_[wr].ptr;
+    S.order_next = d_order_[wr].ptr;
     order_read_ = wr;
     order_nb_ = order_key;
     order_valid_ = true;
@@ -1353,120 +1346,134 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
   // fdh_render_frame (profiles/r06_deep_in_flight.txt): one context, 1080p, 49.7 us per frame without deep strips, 46.6 with bins of >= 24
   // draws, 46.4 with >= 40; four contexts in flight 30.3 / 31.1 / 28.9 us -- so 24 for a device's only context, 40 beside others.
   static const int deep_env = [] { const char* e = std::getenv("FDH_DEEP_MIN"); return e ? std::atoi(e) : -1; }();
-  const int deep_min = deep_env >= 0 ? deep_env : (vram_contexts_alive(device_) > 1 ? kDeepMinInFlight : kDeepMinDefault);
-  int deep_k8 = 0;
-  if (sorting && deep_min > 0) {
+  S.deep_min = deep_env >= 0 ? deep_env : (vram_contexts_alive(device_) > 1 ? kDeepMinInFlight : kDeepMinDefault);
+  if (sorting && S.deep_min > 0) {
     if (!deep_host_) {
       FDH_HIP(hipHostMalloc((void**)&deep_host_, 64, hipHostMallocDefault));
       for (int c = 0; c < 8; c++) deep_host_[c] = 0;
     }
-    if (order_now) {
+    if (S.order_now) {
       uint32_t most = 0;
       for (int c = 0; c < 8; c++) most = std::max(most, (uint32_t)deep_host_[c]);
-      deep_k8 = 8 * (int)std::min<uint32_t>(most, 1024u);
+      S.deep_k8 = 8 * (int)std::min<uint32_t>(most, 1024u);
     }
   }
+  return S;
+}
+
+// Phase p's blur node, ahead of its composite: both passes as one kernel out of place (a full-frame node: the surface flips), one kernel into
+// the backdrop surface (a small region), or the two passes.  Returns the surface the phase composites into.
+uint32_t* Context::launch_blur(const LaunchJob& J, int p, uint32_t* cur, int row_lo, int row_hi, bool partial) {
+  const Phase& ph = J.phases[p];
+  if (ph.blur < 0) return cur;
+  const BlurJob& j = J.blurs[ph.blur];
+  const bool big = ph.blur == J.big_blur;
+  // V output: footprint rows this phase must produce; H output: those rows widened by the tap reach
+  const int vy0 = std::max(j.y0, row_lo), vy1 = std::min(j.y1, row_hi);
+  if (vy1 <= vy0 || j.x1 <= j.x0) return cur;
+  BlurParams bp;
+  bp.W = J.W; bp.H = J.H; bp.pitch = J.W;
+  bp.taps = j.taps;
+  bp.node_pixels = (long long)(j.x1 - j.x0) * (j.y1 - j.y0);
+  bp.fuse_draw = -1;
+  bp.mx_w = (size_t)ph.blur < J.mx_w_h.size() ? J.mx_w_h[ph.blur] : nullptr;
+  bp.x0 = j.x0; bp.x1 = j.x1; bp.y0 = vy0; bp.y1 = vy1;
+  if ((size_t)ph.blur < J.blur_fused.size() && J.blur_fused[ph.blur]) {
+    uint32_t* other = cur == fb_ ? alt_ : fb_;
+    bp.src = cur; bp.dst = other;
+    bp.fuse_draw = j.fuse_draw;
+    span_begin(kSpanBlurFused);
+    const bool done = launch_blur_fused(stream_, bp, J.mx_w_v[ph.blur], J.dv.recs, J.dv.exts);
+    span_end();
+    if (!done) throw Error(FDH_ERR_HIP, "fused blur: no kernel for this filter width (blur_fused_supported out of step with the launcher)");
+    return other;
+  }
+  if (j.fuse_draw < 0 && J.latency_routes && blur_one_kernel_ok(j.x1 - j.x0, j.y1 - j.y0, j.taps.reach)) {
+    // a small region: one kernel, source window -> LDS -> horizontal -> LDS -> vertical -> the backdrop surface
+    bp.src = cur; bp.dst = backdrop_;
+    span_begin(big ? kSpanBigBlurV : kSpanBlurV);
+    launch_blur_small(stream_, bp);
+    span_end();
+    return cur;
+  }
+  bp.src = cur; bp.dst = blur_tmp_;
+  bp.y0 = std::max(0, vy0 - j.taps.reach); bp.y1 = std::min(J.H, vy1 + j.taps.reach);
+  // a partial frame: a V pass that composites its quad into the surface runs whether the node took damage or not -- when it did not,
+  // its footprint is kept aside and put back (k_damage_guard: both return at once when the node's run flag is set)
+  const bool guard = partial && j.fuse_draw >= 0;
+  if (guard) launch_damage_guard(stream_, d_dmg_run_.ptr, ph.blur, false, cur, d_dmg_keep_.ptr, J.W, j.x0, vy0, j.x1, vy1);
+  span_begin(big ? kSpanBigBlurH : kSpanBlurH);
+  launch_blur_h(stream_, bp);
+  span_end();
+  bp.src = blur_tmp_; bp.dst = j.fuse_draw >= 0 ? cur : backdrop_;
+  bp.mx_w = (size_t)ph.blur < J.mx_w_v.size() ? J.mx_w_v[ph.blur] : nullptr;
+  bp.fuse_draw = j.fuse_draw;
+  bp.y0 = vy0; bp.y1 = vy1;
+  span_begin(big ? kSpanBigBlurV : kSpanBlurV);
+  launch_blur_v(stream_, bp, J.dv.recs, J.dv.exts);
+  span_end();
+  if (guard) launch_damage_guard(stream_, d_dmg_run_.ptr, ph.blur, true, cur, d_dmg_keep_.ptr, J.W, j.x0, vy0, j.x1, vy1);
+  return cur;
+}
+
+// phase p's compositor launch into `cur`: the whole grid from the clear colour for the launch that starts the frame, with the schedule;
+// the phase's bin box over what the surface holds for a later phase
+CompositeParams Context::composite_params(const LaunchJob& J, int p, uint32_t* cur, int row_lo, int row_hi, bool direct, const Schedule& S) const {
+  const Phase& ph = J.phases[p];
+  const int nb = J.bins_x * J.bins_y;
+  const bool full = p == 0 && J.clear;
+  CompositeParams C;
+  C.lists = J.lists + (size_t)p * nb * J.list_stride;
+  C.counts = J.counts + (size_t)p * nb;
+  C.backdrop = backdrop_;
+  C.fb = cur;
+  for (int l = 0; l < kMaxMips; l++) C.atlas.level[l] = atlas_levels_[l];
+  C.atlas.size = atlas_size_; C.atlas.n_levels = n_levels_;
+  C.W = J.W; C.H = J.H; C.pitch = J.W;
+  C.bins_x = J.bins_x; C.stride = J.list_stride;
+  C.bin_x0 = full ? 0 : ph.bin_x0; C.bin_y0 = full ? 0 : ph.bin_y0;
+  C.bin_nx = full ? J.bins_x : ph.bin_x1 - ph.bin_x0; C.bin_ny = full ? J.bins_y : ph.bin_y1 - ph.bin_y0;
+  C.row_lo = row_lo; C.row_hi = row_hi;
+  C.load_fb = full ? 0 : 1;
+  C.clear_rgba8 = J.clear_rgba8;
+  C.direct = direct ? 1 : 0; C.direct_first = ph.first; C.direct_n = ph.count; C.binrec = J.dv.binrecs;
+  C.order = full ? S.order_now : nullptr; C.order_next = full ? S.order_next : nullptr;
+  C.deep_k8 = full ? S.deep_k8 : 0; C.deep_min = S.deep_min;
+  static const int deep_strip_min = [] { const char* e = std::getenv("FDH_DEEP_STRIP_MIN"); return e ? std::atoi(e) : kDeepStripMinDefault; }();
+  C.deep_strip_min = deep_strip_min;
+  C.deep_out = (full && S.order_next && S.deep_min > 0) ? const_cast<uint32_t*>(deep_host_) : nullptr;
+  C.has_slow = ph.has_slow; C.has_slow_atlas = ph.has_slow_atlas; C.has_rot = ph.has_rot; C.has_atlas = ph.has_atlas; C.has_masks = ph.has_masks;
+  C.mask_spill = J.mask_spill; C.spill_stride = J.spill_stride;
+  return C;
+}
+
+// The launches of a frame, in stream order: binning, damage tracking's, then per phase its blur node and its compositor launch.
+void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq) {
+  profiling_ = profile;
+  std::vector<int> lo, hi;
+  phase_rows(J, lo, hi);
+  const bool direct = direct_frame(J);
+  const BinParams B = bin_params(J, upload_seq);
+  span_begin(kSpanBin); if (!direct) launch_bin(stream_, B); span_end();
+  const bool partial = launch_damage(J, B);
+  const Schedule S = schedule(J, direct, partial);
   // The surface that holds the live image.  A fused full-frame blur renders out of place and flips it; a frame that flips an odd
   // number of times ends in alt_, and the two pointers trade places: the frame surface IS the one the frame ended in
   // (fdh_frame_device_ptr is asked again after every frame).  Phase 0 always starts in fb_, i.e. on the surface the previous
   // frame's last pass WROTE: starting in the other one -- the surface that pass had only read -- cost the phase-0 launch 2 us
   // (32.1 against 30.2: its 33 MB of stores then land on lines other XCDs' L2s hold clean copies of).
   uint32_t* cur = fb_;
-  for (int p = 0; p < np; p++) {
-    const Phase& ph = J.phases[p];
-    if (ph.blur >= 0) {
-      const BlurJob& j = J.blurs[ph.blur];
-      // V output: footprint rows this phase must produce; H output: those rows widened by the tap reach
-      const int vy0 = std::max(j.y0, lo[p]), vy1 = std::min(j.y1, hi[p]);
-      if (vy1 > vy0 && j.x1 > j.x0) {
-        BlurParams bp;
-        bp.W = J.W; bp.H = J.H; bp.pitch = J.W;
-        bp.taps = j.taps;
-        bp.node_pixels = (long long)(j.x1 - j.x0) * (j.y1 - j.y0);
-        bp.fuse_draw = -1;
-        bp.mx_w = (size_t)ph.blur < mx_w_h_.size() ? mx_w_h_[ph.blur] : nullptr;
-        bool done = false;
-        if ((size_t)ph.blur < J.blur_fused.size() && J.blur_fused[ph.blur]) {
-          uint32_t* other = cur == fb_ ? alt_ : fb_;
-          bp.src = cur; bp.dst = other;
-          bp.fuse_draw = j.fuse_draw;
-          bp.x0 = j.x0; bp.x1 = j.x1; bp.y0 = vy0; bp.y1 = vy1;
-          span_begin(7);
-          done = launch_blur_fused(stream_, bp, mx_w_v_[ph.blur], dv_.recs, dv_.exts);
-          span_end();
-          if (!done) throw Error(FDH_ERR_HIP, "fused blur: no kernel for this filter width (blur_fused_supported out of step with the launcher)");
-          cur = other;
-        }
-        if (!done && j.fuse_draw < 0 && J.latency_routes && blur_one_kernel_ok(j.x1 - j.x0, j.y1 - j.y0, j.taps.reach)) {
-          // a small region: one kernel, source window -> LDS -> horizontal -> LDS -> vertical -> the backdrop surface
-          bp.fuse_draw = -1;
-          bp.src = cur; bp.dst = backdrop_;
-          bp.x0 = j.x0; bp.x1 = j.x1; bp.y0 = vy0; bp.y1 = vy1;
-          span_begin(ph.blur == big_blur_ ? 6 : 4);
-          launch_blur_small(stream_, bp);
-          span_end();
-          done = true;
-        }
-        if (!done) {
-        bp.fuse_draw = -1;
-        bp.src = cur; bp.dst = blur_tmp_;
-        bp.x0 = j.x0; bp.x1 = j.x1; bp.y0 = std::max(0, vy0 - j.taps.reach); bp.y1 = std::min(J.H, vy1 + j.taps.reach);
-        // a partial frame: a V pass that composites its quad into the surface runs whether the node took damage or not -- when it did not,
-        // its footprint is kept aside and put back (k_damage_guard: both return at once when the node's run flag is set)
-        const bool guard = partial && j.fuse_draw >= 0;
-        if (guard) launch_damage_guard(stream_, d_dmg_run_.ptr, ph.blur, false, cur, d_dmg_keep_.ptr, J.W, j.x0, vy0, j.x1, vy1);
-        span_begin(ph.blur == big_blur_ ? 5 : 3);
-        launch_blur_h(stream_, bp);
-        span_end();
-        bp.src = blur_tmp_; bp.dst = j.fuse_draw >= 0 ? cur : backdrop_;
-        bp.mx_w = (size_t)ph.blur < mx_w_v_.size() ? mx_w_v_[ph.blur] : nullptr;
-        bp.fuse_draw = j.fuse_draw;
-        bp.y0 = vy0; bp.y1 = vy1;
-        span_begin(ph.blur == big_blur_ ? 6 : 4);
-        launch_blur_v(stream_, bp, dv_.recs, dv_.exts);
-        span_end();
-        if (guard) launch_damage_guard(stream_, d_dmg_run_.ptr, ph.blur, true, cur, d_dmg_keep_.ptr, J.W, j.x0, vy0, j.x1, vy1);
-        }
-      }
-    }
-    CompositeParams C;
-    C.lists = J.lists + (size_t)p * nb * list_stride_;
-    C.counts = J.counts + (size_t)p * nb;
-    C.backdrop = backdrop_;
-    C.fb = cur;
-    for (int l = 0; l < kMaxMips; l++) C.atlas.level[l] = atlas_levels_[l];
-    C.atlas.size = atlas_size_; C.atlas.n_levels = n_levels_;
-    C.W = J.W; C.H = J.H; C.pitch = J.W;
-    C.bins_x = bins_x_; C.stride = list_stride_;
-    const bool full = (p == 0 && J.clear);
-    C.bin_x0 = full ? 0 : ph.bin_x0; C.bin_y0 = full ? 0 : ph.bin_y0;
-    C.bin_nx = full ? bins_x_ : ph.bin_x1 - ph.bin_x0; C.bin_ny = full ? bins_y_ : ph.bin_y1 - ph.bin_y0;
-    C.row_lo = lo[p]; C.row_hi = hi[p];
-    C.load_fb = full ? 0 : 1;
-    C.clear_rgba8 = J.clear_rgba8;
-    C.n_wg = 0;
-    C.direct = direct ? 1 : 0; C.direct_first = ph.first; C.direct_n = ph.count; C.binrec = dv_.binrecs;
-    C.order = full ? order_now : nullptr;
-    C.order_next = full ? order_next : nullptr;
-    C.deep_k8 = full ? deep_k8 : 0;
-    if (full) stats_.deep_bins = (float)((ph.has_slow || ph.has_rot || ph.has_atlas || ph.has_masks || !order_now || !order_next) ? 0 : std::min(deep_k8, 8 * ((nb + 7) / 8)));
-    C.deep_min = deep_min;
-    static const int deep_strip_min = [] { const char* e = std::getenv("FDH_DEEP_STRIP_MIN"); return e ? std::atoi(e) : kDeepStripMinDefault; }();
-    C.deep_strip_min = deep_strip_min;
-    C.deep_out = (full && order_next && deep_min > 0) ? const_cast<uint32_t*>(deep_host_) : nullptr;
-    C.has_slow = ph.has_slow ? 1 : 0;
-    C.has_slow_atlas = ph.has_slow_atlas ? 1 : 0;
-    C.has_rot = ph.has_rot ? 1 : 0;
-    C.has_atlas = ph.has_atlas ? 1 : 0;
-    C.has_masks = ph.has_masks ? 1 : 0;
-    C.mask_spill = J.mask_spill; C.spill_stride = J.spill_stride;
-    span_begin(p == 0 ? 1 : 2);
-    if (partial) launch_composite_damage(stream_, dv_.recs, dv_.exts, C, d_dmg_list_.ptr, d_dmg_count_.ptr, dmg_grid);
-    else launch_composite(stream_, dv_.recs, dv_.exts, C);
+  for (int p = 0; p < (int)J.phases.size(); p++) {
+    cur = launch_blur(J, p, cur, lo[p], hi[p], partial);
+    CompositeParams C = composite_params(J, p, cur, lo[p], hi[p], direct, S);
+    if (C.load_fb == 0) stats_.deep_bins = (float)composite_build(C).deep_k8;  // (the launch that starts the frame: its deep strips)
+    span_begin(p == 0 ? kSpanCompositeMain : kSpanCompositeLater);
+    if (partial) launch_composite_damage(stream_, J.dv.recs, J.dv.exts, C, d_dmg_list_.ptr, d_dmg_count_.ptr, J.bins_x * J.bins_y * 16);  // (a wave per strip)
+    else launch_composite(stream_, J.dv.recs, J.dv.exts, C);
     span_end();
   }
   if (cur != fb_) std::swap(fb_, alt_);  // the frame ended in the other surface: it is the frame surface now
-  if (tracked && sig_whole) { dmg_valid_ = true; dmg_key_ = J.damage_key; }
+  if (dmg_last_ && damage_sig_whole(J)) { dmg_valid_ = true; dmg_key_ = J.damage_key; }
   FDH_HIP(hipGetLastError());
 }
 
@@ -1530,7 +1537,7 @@ void Context::profile(int times) {
   if (!have_frame_) throw Error(FDH_ERR_INVALID, "profile: no frame has been submitted");
   FDH_HIP(hipSetDevice(device_));
   if (times <= 0) return;
-  double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double acc[kSpanKinds] = {};
   for (int i = 0; i < times; i++) {
     ev_used_ = 0;
     spans_.clear();
@@ -1542,14 +1549,14 @@ void Context::profile(int times) {
       else (void)hipGetLastError();
     }
   }
-  stats_.ms_bin = (float)(acc[0] / times);
-  stats_.ms_composite_main = (float)(acc[1] / times);
-  stats_.ms_composite = (float)((acc[1] + acc[2]) / times);
-  stats_.ms_blur_h = (float)((acc[3] + acc[5]) / times);
-  stats_.ms_blur_v = (float)((acc[4] + acc[6]) / times);
-  stats_.ms_blur_big_h = (float)(acc[5] / times);
-  stats_.ms_blur_big_v = (float)(acc[6] / times);
-  stats_.ms_blur_fused = (float)(acc[7] / times);
+  stats_.ms_bin = (float)(acc[kSpanBin] / times);
+  stats_.ms_composite_main = (float)(acc[kSpanCompositeMain] / times);
+  stats_.ms_composite = (float)((acc[kSpanCompositeMain] + acc[kSpanCompositeLater]) / times);
+  stats_.ms_blur_h = (float)((acc[kSpanBlurH] + acc[kSpanBigBlurH]) / times);
+  stats_.ms_blur_v = (float)((acc[kSpanBlurV] + acc[kSpanBigBlurV]) / times);
+  stats_.ms_blur_big_h = (float)(acc[kSpanBigBlurH] / times);
+  stats_.ms_blur_big_v = (float)(acc[kSpanBigBlurV] / times);
+  stats_.ms_blur_fused = (float)(acc[kSpanBlurFused] / times);
 }
 
 // ------------------------------------------------------------------ readback (glcontext.nim:2094-2135)

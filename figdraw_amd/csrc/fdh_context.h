@@ -104,7 +104,7 @@ bool vram_staging(int device);  // large-BAR device and FDH_VRAM_STAGING != 0, d
 void* vram_block_acquire(int device, size_t bytes, size_t* size_class);  // throws Error on failure
 void vram_block_release(int device, void* p, size_t size_class);
 size_t vram_store_bytes(int device);   // bytes the store of a device holds (released blocks)
-int vram_contexts_alive(int device);   // device contexts alive on `device` (the deep strips' threshold goes by it: Context::launch_frame)
+int vram_contexts_alive(int device);   // device contexts alive on `device` (the deep strips' threshold goes by it: Context::schedule)
 void vram_context_born(int device);    // a device context exists on `device` ...
 void vram_context_gone(int device);    // ... and is gone: with the last one, the device's store is trimmed to kVramStoreKeep
 constexpr size_t kVramStoreKeep = (size_t)16 << 20;
@@ -501,6 +501,14 @@ class Context : public Recorder {
   void prepare(LaunchJob& J);  // calling thread: recorded frame -> run table + launch description
   void issue(LaunchJob& J);    // submit thread: upload + kernel launches
   void launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq = 0);  // upload_seq: the bin launch reports it to the host
+  // launch_frame's stages, in the order it takes them
+  struct Schedule { const int* order_now = nullptr; int* order_next = nullptr; int deep_min = 0, deep_k8 = 0; };  // of the full-frame launch
+  void phase_rows(const LaunchJob& J, std::vector<int>& lo, std::vector<int>& hi) const;
+  BinParams bin_params(const LaunchJob& J, uint32_t upload_seq) const;
+  bool launch_damage(const LaunchJob& J, const BinParams& B);  // true: a partial frame
+  Schedule schedule(const LaunchJob& J, bool direct, bool partial);
+  uint32_t* launch_blur(const LaunchJob& J, int p, uint32_t* cur, int row_lo, int row_hi, bool partial);
+  CompositeParams composite_params(const LaunchJob& J, int p, uint32_t* cur, int row_lo, int row_hi, bool direct, const Schedule& S) const;
   template <typename Buf> void reserve_quiet(Buf& buf, size_t n);
   void drain();        // wait until the submit thread is idle; rethrows what its last job threw
   void worker_main();
@@ -534,8 +542,13 @@ class Context : public Recorder {
   hipEvent_t ev_[2] = {};
   std::vector<hipEvent_t> ev_pool_;
   size_t ev_used_ = 0;
-  struct Span { int kind; hipEvent_t a, b; };  // kind: 0 bin, 1 composite main, 2 composite later, 3 blur h, 4 blur v, 5 / 6 largest node's h / v, 7 fused h + v
+  // profile mode (fdh_profile): a launch's own start / end events, summed per kind -- the bin launch (and damage tracking's), phase 0's
+  // composite, the later phases', a blur node's H / V pass (the frame's largest node: kinds of their own), a node's fused H + V kernel
+  enum SpanKind { kSpanBin, kSpanCompositeMain, kSpanCompositeLater, kSpanBlurH, kSpanBlurV, kSpanBigBlurH, kSpanBigBlurV, kSpanBlurFused, kSpanKinds };
+  struct Span { SpanKind kind; hipEvent_t a, b; };
   std::vector<Span> spans_;
+  bool profiling_ = false;  // the frame being launched is fdh_profile's
+  void span_begin(SpanKind kind); void span_end();
 
   // frame state
   int W_ = 0, H_ = 0;

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "fdh_types.h"
 
 namespace fdh {
@@ -88,6 +90,15 @@ struct BlurParams {
 void set_launch_events(hipEvent_t start, hipEvent_t stop);
 bool launch_events_used();
 void launch_bin(hipStream_t s, const BinParams& P);
+// FDH_FORCE_KERNEL_PATHS=1|2|3|8|19 (a test hook, tests/test_hip_parity.py: every build must give the same pixels): compositor launches on
+// a more general build than their phase needs -- <0> with clip masks, <2>, <3>, <8>, <3> at 168 registers <19> (composite_build)
+inline int forced_kernel_paths() { static const int v = [] { const char* e = std::getenv("FDH_FORCE_KERNEL_PATHS"); return e ? std::atoi(e) : 0; }(); return v; }
+// What a compositor launch of P takes (k_composite.hip): the build k_composite_tiles<paths> / k_composite_damage<paths>, its dynamic LDS
+// bytes, and the deep strips -- P.deep_k8 (a multiple of 8, at most the launch's bins rounded up to 8) where the launch can have them: the
+// full-frame launch of build <4> with both order pointers, then k_composite_deep's (deep); 0 elsewhere.  Applies FDH_FORCE_KERNEL_PATHS
+// to P's phase flags first (the kernels read them).
+struct CompositeBuild { int paths = 4; size_t lds = 0; int deep_k8 = 0; bool deep = false; };
+CompositeBuild composite_build(CompositeParams& P);
 void launch_composite(hipStream_t s, const DrawRec* draws, const QuadExt* exts, CompositeParams P);
 void launch_blur_h(hipStream_t s, const BlurParams& P);
 void launch_blur_v(hipStream_t s, const BlurParams& P, const DrawRec* draws, const QuadExt* exts);

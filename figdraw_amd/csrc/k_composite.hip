@@ -8,8 +8,8 @@
 //   k_composite_deep   the full-frame launch of a frame with deep lists (round 6): workgroups of four waves, the strips of the deepest
 //                      bins shaded by three waves and blended by a fourth
 //
-// Two translation units from this one file (csrc/Makefile).  FDH_TU 0 (this file as it is): the builds <3> and <8> and the launcher.
-// FDH_TU 1 (k_composite_uniform.hip): <0>, <2>, <4>, k_composite_deep and their launcher only, compiled with
+// Two translation units from this one file (csrc/Makefile).  FDH_TU 0 (this file as it is): the builds <3>, <19> and <8> and the
+// dispatch (composite_build).  FDH_TU 1 (k_composite_uniform.hip): <0>, <2>, <4>, k_composite_deep and their launchers only, compiled with
 // -structurizecfg-skip-uniform-regions.  hipcc structurizes EVERY region of a kernel's control flow, uniform branches
 // included; in the draw loop that turns each wave-uniform branch into a predicate in an SGPR pair (s_cselect_b64 / s_and_b64
 // / s_cbranch_vccnz where one s_cbranch_scc would do) and keeps the texels that merge at the loop latch out of the
@@ -560,127 +560,94 @@ __global__ __launch_bounds__(64, (kPaths & 16) ? kSlowAtlasWaves : (kPaths & 1) 
   if (ty0 >= P.row_hi) return;
   composite_strip<kPaths, kFull, 0>(P, draws, exts, composite_lds, bin, sidx, sbit, tx0, ty0, lane, 0);
 }
+// ---- The launches, all through FDH_LAUNCH (fdh_profile's events, when set, stamp them).  Which build a launch takes is composite_build's
+// decision (FDH_TU 0); the uniform unit's builds and k_composite_deep are launched from that unit.
+template <int kPaths, bool kFull, bool kDirect>
+static void launch_tiles(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P) {
+  FDH_LAUNCH((k_composite_tiles<kPaths, kFull, kDirect>), dim3(grid), dim3(64), b.lds, s, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0,
+             P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P);
+}
+template <int kPaths>  // (kFull: the launch that starts a frame)
+static void launch_damage(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P,
+                          const int* list, const uint32_t* count) {
+  if (P.load_fb == 0) FDH_LAUNCH((k_composite_damage<kPaths, true>), dim3(grid), dim3(64), b.lds, s, list, count, draws, exts, P);
+  else FDH_LAUNCH((k_composite_damage<kPaths, false>), dim3(grid), dim3(64), b.lds, s, list, count, draws, exts, P);
+}
+// build kPaths of P's launch: the launch that starts a frame (kFull) or a later phase's, from the lists or direct (the uniform unit's builds)
 template <int kPaths>
-static void launch_damage_paths(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts,
-                                const CompositeParams& P, const int* list, const uint32_t* count) {
-  if (P.load_fb == 0) {
-    if (e0) hipExtLaunchKernelGGL((k_composite_damage<kPaths, true>), dim3(grid), dim3(64), lds, s, e0, e1, 0, list, count, draws, exts, P);
-    else hipLaunchKernelGGL((k_composite_damage<kPaths, true>), dim3(grid), dim3(64), lds, s, list, count, draws, exts, P);
-  } else {
-    if (e0) hipExtLaunchKernelGGL((k_composite_damage<kPaths, false>), dim3(grid), dim3(64), lds, s, e0, e1, 0, list, count, draws, exts, P);
-    else hipLaunchKernelGGL((k_composite_damage<kPaths, false>), dim3(grid), dim3(64), lds, s, list, count, draws, exts, P);
-  }
+static void launch_tiles_build(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P) {
+  constexpr bool kHasDirect = kPaths == 0 || kPaths == 2 || kPaths == 4;
+  const bool direct = kHasDirect && P.direct;
+  if (P.load_fb == 0) direct ? launch_tiles<kPaths, true, kHasDirect>(s, b, grid, draws, exts, P) : launch_tiles<kPaths, true, false>(s, b, grid, draws, exts, P);
+  else direct ? launch_tiles<kPaths, false, kHasDirect>(s, b, grid, draws, exts, P) : launch_tiles<kPaths, false, false>(s, b, grid, draws, exts, P);
 }
 
+// the uniform unit's builds <0|2|4>: its own launchers (and the single-unit build's)
+void launch_composite_uniform(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P);
+void launch_composite_damage_uniform(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P,
+                                     const int* list, const uint32_t* count);
+#if FDH_TU == 1 || !FDH_SPLIT_UNIFORM
+void launch_composite_uniform(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P) {
+  if (b.deep) {  // build <4>'s full-frame launch with deep bins: four-wave workgroups (a direct frame has no sort, so no deep strips)
+    const int bins8 = (P.bin_nx * P.bin_ny + 7) / 8;
+    FDH_LAUNCH((k_composite_deep<FDH_TU>), dim3(8 + P.deep_k8 * 16 + 8 * bins8 * kWgsPerBin), dim3(256), b.lds, s, draws, exts, P);
+  } else if (b.paths == 2) launch_tiles_build<2>(s, b, grid, draws, exts, P);
+  else if (b.paths == 0) launch_tiles_build<0>(s, b, grid, draws, exts, P);
+  else launch_tiles_build<4>(s, b, grid, draws, exts, P);
+}
+void launch_composite_damage_uniform(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P,
+                                     const int* list, const uint32_t* count) {
+  if (b.paths == 2) launch_damage<2>(s, b, grid, draws, exts, P, list, count);
+  else if (b.paths == 0) launch_damage<0>(s, b, grid, draws, exts, P, list, count);
+  else launch_damage<4>(s, b, grid, draws, exts, P, list, count);
+}
+#endif
+
 #if FDH_TU == 0
-void launch_composite_damage_uniform(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts,
-                                     const CompositeParams& P, const int* list, const uint32_t* count, int paths);  // FDH_TU 1
+CompositeBuild composite_build(CompositeParams& P) {
+  switch (forced_kernel_paths()) {
+    case 3: P.has_slow = 1; P.has_slow_atlas = 0; break;  // (<3> itself, also where the phase would take its 168-register form)
+    case 19: P.has_slow = 1; P.has_slow_atlas = 1; break;
+    case 8: P.has_rot = 1; break;
+    case 2: P.has_atlas = 1; break;
+    case 1: P.has_masks = 1; break;  // (the build with mask registers and the 4-KB stack, even where no clip is open)
+  }
+  CompositeBuild b;
+  if (P.has_slow || (P.has_rot && P.has_atlas)) b.paths = P.has_slow_atlas ? 19 : 3;
+  else if (P.has_rot) b.paths = 8;
+  else b.paths = P.has_atlas ? 2 : P.has_masks ? 0 : 4;
+  // deep strips (k_composite_deep): only beside the no-clip build's full-frame launch, and only with the order at hand
+  const int bins8 = (P.bin_nx * P.bin_ny + 7) / 8;  // bins per XCD
+  if (b.paths == 4 && P.load_fb == 0 && P.order && P.order_next) b.deep_k8 = std::min(P.deep_k8 & ~7, 8 * bins8);
+  b.deep = b.deep_k8 > 0;
+  // the clip stack (4 KB; 1 KB, what the bin-ordering wavefront needs, without clips) + the texel window of the atlas path; the deep launch: its ring
+  b.lds = b.deep ? sizeof(uint32_t) * kDeepLdsDwords
+                 : (P.has_masks ? sizeof(uint32_t) * kMaskDepth * 64 : sizeof(uint32_t) * 256) +
+                       (P.has_atlas || P.has_slow ? sizeof(uint32_t) * kWinRows * kWinStride : 0);
+  return b;
+}
 void launch_composite_damage(hipStream_t s, const DrawRec* draws, const QuadExt* exts, CompositeParams P, const int* list, const uint32_t* count,
                              int grid) {
   if (grid <= 0 || P.bin_nx <= 0 || P.bin_ny <= 0) return;
-  // (the build choice and FDH_FORCE_KERNEL_PATHS as launch_composite makes them)
-  static const int force = [] { const char* e = std::getenv("FDH_FORCE_KERNEL_PATHS"); return e ? std::atoi(e) : 0; }();
-  if (force == 3) { P.has_slow = 1; P.has_slow_atlas = 0; }
-  if (force == 19) { P.has_slow = 1; P.has_slow_atlas = 1; }
-  if (force == 8) P.has_rot = 1;
-  if (force == 2) P.has_atlas = 1;
-  if (force == 1) P.has_masks = 1;
-  const size_t lds = (P.has_masks ? sizeof(uint32_t) * kMaskDepth * 64 : sizeof(uint32_t) * 256) +
-                     ((P.has_atlas || P.has_slow || (P.has_rot && P.has_atlas)) ? sizeof(uint32_t) * kWinRows * kWinStride : 0);
+  const CompositeBuild b = composite_build(P);  // (a tracked frame's partial launches have no order: no deep strips)
   P.n_wg = grid;
-  hipEvent_t e0 = t_prof_start, e1 = t_prof_stop;
-  if (P.has_slow || (P.has_rot && P.has_atlas)) { if (P.has_slow_atlas) launch_damage_paths<19>(s, e0, e1, grid, lds, draws, exts, P, list, count); else launch_damage_paths<3>(s, e0, e1, grid, lds, draws, exts, P, list, count); }
-  else if (P.has_rot) launch_damage_paths<8>(s, e0, e1, grid, lds, draws, exts, P, list, count);
-#if FDH_SPLIT_UNIFORM
-  else launch_composite_damage_uniform(s, e0, e1, grid, lds, draws, exts, P, list, count, P.has_atlas ? 2 : P.has_masks ? 0 : 4);
-#else
-  else if (P.has_atlas) launch_damage_paths<2>(s, e0, e1, grid, lds, draws, exts, P, list, count);
-  else if (P.has_masks) launch_damage_paths<0>(s, e0, e1, grid, lds, draws, exts, P, list, count);
-  else launch_damage_paths<4>(s, e0, e1, grid, lds, draws, exts, P, list, count);
-#endif
-  if (e0) t_prof_used = true;
+  if (b.paths == 19) launch_damage<19>(s, b, grid, draws, exts, P, list, count);
+  else if (b.paths == 3) launch_damage<3>(s, b, grid, draws, exts, P, list, count);
+  else if (b.paths == 8) launch_damage<8>(s, b, grid, draws, exts, P, list, count);
+  else launch_composite_damage_uniform(s, b, grid, draws, exts, P, list, count);
 }
-void launch_composite_uniform(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P, int paths);  // FDH_TU 1
 void launch_composite(hipStream_t s, const DrawRec* draws, const QuadExt* exts, CompositeParams P) {
   const int n = P.bin_nx * P.bin_ny * kWgsPerBin;
   if (n <= 0) return;
+  const CompositeBuild b = composite_build(P);
   P.n_wg = n;
+  P.deep_k8 = b.deep_k8;
   const int bins8 = (P.bin_nx * P.bin_ny + 7) / 8;  // bins per XCD
-  const int grid = 8 * bins8 * kWgsPerBin * kWavesPerWg + (P.order_next ? 8 : 0);  // 16 strips per bin, one wavefront each (+ the sorting one)
-  const dim3 blk(64);
-  // FDH_FORCE_KERNEL_PATHS=3 (or 2, or 1): run a more general build than the phase needs -- a test hook: every build must give
-  // the same pixels (tests/test_hip_parity.py)
-  static const int force = [] { const char* e = std::getenv("FDH_FORCE_KERNEL_PATHS"); return e ? std::atoi(e) : 0; }();
-  if (force == 3) { P.has_slow = 1; P.has_slow_atlas = 0; }  // (<3> itself, also where the phase would take its 168-register form)
-  if (force == 19) { P.has_slow = 1; P.has_slow_atlas = 1; }
-  if (force == 8) P.has_rot = 1;
-  if (force == 2) P.has_atlas = 1;
-  if (force == 1) P.has_masks = 1;  // (the build with mask registers and the 4-KB stack, even where no clip is open)
-  const size_t lds = (P.has_masks ? sizeof(uint32_t) * kMaskDepth * 64 : sizeof(uint32_t) * 256) +
-                     ((P.has_atlas || P.has_slow || (P.has_rot && P.has_atlas)) ? sizeof(uint32_t) * kWinRows * kWinStride : 0);  // + the texel window of the atlas path
-  const bool full = P.load_fb == 0;  // the launch that starts a frame (k_composite_tiles<., true>)
-  // deep strips (k_composite_deep): only beside the no-clip build's full-frame launch, and only with the order at hand
-  if (!(full && P.order && P.order_next && !P.has_slow && !P.has_rot && !P.has_atlas && !P.has_masks)) P.deep_k8 = 0;
-  P.deep_k8 = std::min(P.deep_k8 & ~7, 8 * bins8);
-#define FDH_COMPOSITE_DIRECT(paths) \
-  do { if (full) FDH_LAUNCH((k_composite_tiles<paths, true, true>), dim3(grid), blk, lds, s, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0, P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P); \
-       else FDH_LAUNCH((k_composite_tiles<paths, false, true>), dim3(grid), blk, lds, s, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0, P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P); } while (0)
-#define FDH_COMPOSITE(paths) \
-  do { if (full) FDH_LAUNCH((k_composite_tiles<paths, true>), dim3(grid), blk, lds, s, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0, P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P); \
-       else FDH_LAUNCH((k_composite_tiles<paths, false>), dim3(grid), blk, lds, s, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0, P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P); } while (0)
-#if FDH_SPLIT_UNIFORM
-  if (P.has_slow || (P.has_rot && P.has_atlas)) { if (P.has_slow_atlas) FDH_COMPOSITE(19); else FDH_COMPOSITE(3); }
-  else if (P.has_rot) FDH_COMPOSITE(8);
-  else { launch_composite_uniform(s, t_prof_start, t_prof_stop, grid, lds, draws, exts, P, P.has_atlas ? 2 : P.has_masks ? 0 : 4); if (t_prof_start) t_prof_used = true; }
-#else
-  if (P.has_slow || (P.has_rot && P.has_atlas)) { if (P.has_slow_atlas) FDH_COMPOSITE(19); else FDH_COMPOSITE(3); }
-  else if (P.has_rot) FDH_COMPOSITE(8);
-  else if (P.direct) { if (P.has_atlas) FDH_COMPOSITE_DIRECT(2); else if (!P.has_masks) FDH_COMPOSITE_DIRECT(4); else FDH_COMPOSITE_DIRECT(0); }
-  else if (P.has_atlas) FDH_COMPOSITE(2);
-  else if (!P.has_masks) {
-    if (P.deep_k8 > 0 && P.order && P.order_next) {  // a frame with deep bins: the launch of four-wave workgroups
-      const dim3 g(8 + P.deep_k8 * 16 + 8 * bins8 * kWgsPerBin);
-      FDH_LAUNCH((k_composite_deep<0>), g, dim3(256), sizeof(uint32_t) * kDeepLdsDwords, s, draws, exts, P);
-    } else FDH_COMPOSITE(4);
-  }
-  else FDH_COMPOSITE(0);
-#endif
-#undef FDH_COMPOSITE
-#undef FDH_COMPOSITE_DIRECT
-}
-#else  // FDH_TU 1: the one launcher of this unit
-template <int kPaths, bool kFull>
-static void launch_uniform2(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P) {
-  if (kPaths == 4 && kFull && P.deep_k8 > 0 && P.order && P.order_next) {  // a frame with deep bins: the launch of four-wave workgroups
-    const int bins8 = (P.bin_nx * P.bin_ny + 7) / 8;
-    const dim3 g(8 + P.deep_k8 * 16 + 8 * bins8 * kWgsPerBin);
-    if (e0) hipExtLaunchKernelGGL((k_composite_deep<1>), g, dim3(256), sizeof(uint32_t) * kDeepLdsDwords, s, e0, e1, 0, draws, exts, P);
-    else hipLaunchKernelGGL((k_composite_deep<1>), g, dim3(256), sizeof(uint32_t) * kDeepLdsDwords, s, draws, exts, P);
-    return;
-  }
-  if (P.direct) {  // a frame without a bin launch: the builds whose waves make their list entries themselves
-    if (e0) hipExtLaunchKernelGGL((k_composite_tiles<kPaths, kFull, true>), dim3(grid), dim3(64), lds, s, e0, e1, 0, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0, P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P);
-    else hipLaunchKernelGGL((k_composite_tiles<kPaths, kFull, true>), dim3(grid), dim3(64), lds, s, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0, P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P);
-    return;
-  }
-  if (e0) hipExtLaunchKernelGGL((k_composite_tiles<kPaths, kFull>), dim3(grid), dim3(64), lds, s, e0, e1, 0, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0, P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P);
-  else hipLaunchKernelGGL((k_composite_tiles<kPaths, kFull>), dim3(grid), dim3(64), lds, s, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0, P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P);
-}
-template <int kPaths>
-static void launch_uniform(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P) {
-  if (P.load_fb == 0) launch_uniform2<kPaths, true>(s, e0, e1, grid, lds, draws, exts, P);  // the launch that starts a frame
-  else launch_uniform2<kPaths, false>(s, e0, e1, grid, lds, draws, exts, P);
-}
-void launch_composite_uniform(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P, int paths) {
-  if (paths == 2) launch_uniform<2>(s, e0, e1, grid, lds, draws, exts, P);
-  else if (paths == 0) launch_uniform<0>(s, e0, e1, grid, lds, draws, exts, P);
-  else launch_uniform<4>(s, e0, e1, grid, lds, draws, exts, P);
-}
-void launch_composite_damage_uniform(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int grid, size_t lds, const DrawRec* draws, const QuadExt* exts,
-                                     const CompositeParams& P, const int* list, const uint32_t* count, int paths) {
-  if (paths == 2) launch_damage_paths<2>(s, e0, e1, grid, lds, draws, exts, P, list, count);
-  else if (paths == 0) launch_damage_paths<0>(s, e0, e1, grid, lds, draws, exts, P, list, count);
-  else launch_damage_paths<4>(s, e0, e1, grid, lds, draws, exts, P, list, count);
+  const int grid = 8 * bins8 * kWgsPerBin * kWavesPerWg + (P.order_next ? 8 : 0);  // 16 strips per bin, one wavefront each (+ the sorting ones)
+  if (b.paths == 19) launch_tiles_build<19>(s, b, grid, draws, exts, P);
+  else if (b.paths == 3) launch_tiles_build<3>(s, b, grid, draws, exts, P);
+  else if (b.paths == 8) launch_tiles_build<8>(s, b, grid, draws, exts, P);
+  else launch_composite_uniform(s, b, grid, draws, exts, P);
 }
 #endif  // FDH_TU
 }  // namespace fdh

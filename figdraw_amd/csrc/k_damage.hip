@@ -118,7 +118,7 @@ void launch_damage_sign(hipStream_t s, const DamageSignParams& P) {
   FDH_LAUNCH(k_damage_sign, dim3(nb), dim3(64), 0, s, P);
 }
 void launch_damage_resolve(hipStream_t s, const DamageResolveParams& P) {
-  if (P.bins_x * P.bins_y <= 0 || P.n_nodes < 0 || P.n_nodes > kDamageMaxNodes) return;  // (Context::launch_frame clamps n_nodes)
+  if (P.bins_x * P.bins_y <= 0 || P.n_nodes < 0 || P.n_nodes > kDamageMaxNodes) return;  // (Context::launch_damage clamps n_nodes)
   FDH_LAUNCH(k_damage_resolve, dim3(1), dim3(kResolveThreads), 0, s, P);
 }
 void launch_damage_guard(hipStream_t s, const uint8_t* run, int node, bool restore, uint32_t* surf, uint32_t* keep, int pitch, int x0, int y0,
