@@ -157,6 +157,13 @@ def load():
         L.fdh_damage_bins.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.fdh_damage_changed_bins.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.fdh_damage_closure.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
+    # picking (include/figdraw_hip_pick.h; likewise absent from older libraries)
+    if hasattr(L, "fdh_set_pick"):
+        L.fdh_set_pick.argtypes = [vp, C.c_int]
+        L.fdh_set_pick_tag.argtypes = [vp, C.c_int32, C.c_int32]
+        L.fdh_pick_points.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp]
+        L.fdh_pick_region.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, vp]
+        L.fdh_pick_draw_tags.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     assert L.fdh_sizeof_fig() == C.sizeof(S.CFig), (L.fdh_sizeof_fig(), C.sizeof(S.CFig))
     assert L.fdh_sizeof_glyph() == C.sizeof(S.CGlyph)
     assert L.fdh_sizeof_draw_op() == C.sizeof(S.CDrawOp)
@@ -563,6 +570,62 @@ class HipContext:
         if rc != 0:
             raise FigdrawHipError(rc, L.fdh_last_error().decode())
         return out.astype(bool)
+
+    # ---- picking (include/figdraw_hip_pick.h)
+    PICK_SHADOWS = 1  # FDH_PICK_SHADOWS
+    PICK_HIT = np.dtype([("zlevel", "<i4"), ("id", "<i4"), ("draw", "<i4"), ("alpha", "u1"), ("mode", "u1"), ("reserved", "<u2")])
+
+    def set_pick(self, on: bool):
+        """keep each frame's record tags from the next frame begun on, so that pick_points / pick_region can say which draw and which
+        node owns a pixel of the last submitted frame"""
+        self._ck(self.L.fdh_set_pick(self.h, 1 if on else 0))
+
+    def set_pick_tag(self, zlevel: int, id: int):
+        """the tag (zlevel, id) of the draw calls that follow (call-level frames; begin_frame resets it to (-1, -1))"""
+        self._ck(self.L.fdh_set_pick_tag(self.h, int(zlevel), int(id)))
+
+    def pick_points(self, xy, threshold: int = 128, flags: int = 0, max_hits: int = 1):
+        """hits at points xy (N x 2, frame pixels), front to back: (hits, counts) -- hits a structured array (N, max_hits) of PICK_HIT,
+        counts[i] the hits of point i"""
+        pts = np.ascontiguousarray(np.asarray(xy, dtype=np.float32).reshape(-1, 2))
+        n = pts.shape[0]
+        hits = np.zeros((n, int(max_hits)), dtype=self.PICK_HIT)
+        counts = np.zeros(n, dtype=np.int32)
+        self._ck(self.L.fdh_pick_points(self.h, pts.ctypes.data, n, int(threshold), int(flags), int(max_hits), hits.ctypes.data, counts.ctypes.data))
+        return hits, counts
+
+    def top_node_at(self, x: float, y: float, threshold: int = 128):
+        """(zlevel, id) of the front-most draw that hits pixel (x, y), or None (topFigAtPoint)"""
+        hits, counts = self.pick_points([(x, y)], threshold=threshold, max_hits=1)
+        return (int(hits[0, 0]["zlevel"]), int(hits[0, 0]["id"])) if counts[0] else None
+
+    def pick_region(self, x: int = 0, y: int = 0, w: Optional[int] = None, h: Optional[int] = None, threshold: int = 128, flags: int = 0) -> np.ndarray:
+        """the front-most hit's draw index per pixel of the rectangle (default: the whole frame), -1 where nothing hits: int32 (h, w)"""
+        w = self.W - x if w is None else int(w)
+        h = self.H - y if h is None else int(h)
+        out = np.empty((max(h, 0), max(w, 0)), dtype=np.int32)
+        self._ck(self.L.fdh_pick_region(self.h, int(x), int(y), w, h, int(threshold), int(flags), out.ctypes.data))
+        return out
+
+    def pick_draw_tags(self) -> np.ndarray:
+        """the tag of every record of the last frame, painter's order: int32 (n, 2) of (zlevel, id); works on record-only contexts"""
+        n = C.c_int()
+        self._ck(self.L.fdh_pick_draw_tags(self.h, None, None, 0, C.byref(n)))
+        z = np.zeros(n.value, dtype=np.int32)
+        i = np.zeros(n.value, dtype=np.int32)
+        self._ck(self.L.fdh_pick_draw_tags(self.h, z.ctypes.data, i.ctypes.data, n.value, C.byref(n)))
+        return np.stack([z, i], axis=1)
+
+    def visible_pixels(self, threshold: int = 128, flags: int = 0) -> dict:
+        """exact visibility (figVisibility): {(zlevel, id): pixels of the frame whose front-most hit is a draw of that tag}"""
+        region = self.pick_region(threshold=threshold, flags=flags)
+        tags = self.pick_draw_tags()
+        draws, n = np.unique(region[region >= 0], return_counts=True)
+        out: dict = {}
+        for d, c in zip(draws.tolist(), n.tolist()):
+            key = (int(tags[d, 0]), int(tags[d, 1]))
+            out[key] = out.get(key, 0) + int(c)
+        return out
 
     @staticmethod
     def comm_unique_id() -> bytes:

@@ -4,6 +4,7 @@
 
 #include "fdh_context.h"
 #include "../../include/figdraw_hip_damage.h"
+#include "../../include/figdraw_hip_pick.h"
 
 using fdh::Context;
 
@@ -288,6 +289,19 @@ int fdh_gather_frames(FdhContext* c, int dst_rank, void* const* dst_images) { re
 int fdh_set_blur_route(FdhContext* c, int route) { return guard([&] { C(c)->set_blur_route(route); }); }
 int fdh_set_stripe(FdhContext* c, int y0, int y1) { return guard([&] { C(c)->set_stripe(y0, y1); }); }
 int fdh_set_damage_tracking(FdhContext* c, int on) { return guard([&] { C(c)->set_damage_tracking(on != 0); }); }
+// picking (include/figdraw_hip_pick.h)
+static_assert(sizeof(FdhPickHit) == 16, "FdhPickHit is 16 bytes");
+int fdh_set_pick(FdhContext* c, int on) { return guard([&] { C(c)->set_pick(on != 0); }); }
+int fdh_set_pick_tag(FdhContext* c, int32_t zlevel, int32_t id) { return guard([&] { C(c)->set_pick_tag(zlevel, id); }); }
+int fdh_pick_points(FdhContext* c, const float* xy, int n, int threshold, uint32_t flags, int max_hits, FdhPickHit* out, int* counts) {
+  return guard([&] { C(c)->pick_points(xy, n, threshold, flags, max_hits, out, counts); });
+}
+int fdh_pick_region(FdhContext* c, int x, int y, int w, int h, int threshold, uint32_t flags, int32_t* out_draw) {
+  return guard([&] { C(c)->pick_region(x, y, w, h, threshold, flags, out_draw); });
+}
+int fdh_pick_draw_tags(FdhContext* c, int32_t* zlevels, int32_t* ids, int cap, int* n) {
+  return guard([&] { C(c)->pick_draw_tags(zlevels, ids, cap, n); });
+}
 int fdh_damage_bins(FdhContext* c, uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged) {
   return guard([&] { C(c)->damage_bins(mask, cap, bins_x, bins_y, n_damaged, false); });
 }

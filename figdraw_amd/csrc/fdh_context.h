@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/figdraw_hip.h"
+#include "../../include/figdraw_hip_pick.h"
 #include "fdh_kernels.h"
 
 namespace fdh {
@@ -197,6 +198,8 @@ struct BlurJob {
 // the 24-byte BinRec the bin kernel reads (pixel bounds, saturated core, list-entry flags), the quad extensions: nothing is
 // built a second time at submit.  A LANE is what one thread records: lane 0 belongs to the thread that calls the context,
 // lanes 1.. to the walk pool's threads (fdh_frontend.cpp: large sibling groups of the scene tree are decomposed in parallel).
+// Picking (include/figdraw_hip_pick.h): each record's tag, kept beside the records of its lane while the frame has picking on.
+struct PickTag { int32_t z, id; };
 // The frame in painter's order is a list of PIECES, each a run of consecutive records of one lane.  A finished piece is
 // PUBLISHED -- copied, by the thread that recorded it, into the lane's pinned mirror arrays -- and the upload kernel gathers the
 // published pieces into the dense device arrays (k_upload_frame).
@@ -209,6 +212,7 @@ struct Lane {
   HostVec<DrawRec> up_recs;  // pinned mirrors (device contexts): what the GPU reads; element i = element i of the array above
   HostVec<BinRec> up_bins;
   HostVec<QuadExt> up_exts;
+  HostVec<PickTag> tags;    // picking frames only: tags[i] = the tag of record i (host memory, never uploaded)
   bool device = false;
   const uint8_t *d_recs = nullptr, *d_bins = nullptr, *d_exts = nullptr;  // the mirrors as the device sees them (taken when a mirror is allocated)
   size_t pub_recs = 0, pub_exts = 0;  // elements below these may have been published this frame (kept across a mirror's growth)
@@ -225,7 +229,7 @@ struct Lane {
     up_recs.vram = up_bins.vram = up_exts.vram = on && vram_staging(dev);
     up_recs.dev = up_bins.dev = up_exts.dev = dev;
   }
-  void clear() { recs.clear(); bins.clear(); exts.clear(); boxes.clear(); pub_recs = pub_exts = 0; }
+  void clear() { recs.clear(); bins.clear(); exts.clear(); boxes.clear(); tags.clear(); pub_recs = pub_exts = 0; }
   void publish(uint32_t first, uint32_t n, uint32_t ext_first, uint32_t n_ext);  // records / extensions are final: copy them to the mirrors
   void publish_bytes(int array, size_t at, size_t len);                          // ... a byte range of one array (0 recs, 1 bins, 2 exts)
   void count_begin(int bins_x, int bins_y);
@@ -311,6 +315,7 @@ class Recorder {
   PhaseSum sum_;                    // of the records committed since the last take_sum()
   int64_t fragments_ = 0, culled_draws_ = 0;
   int phase_floor_ = 0;             // lane index of the first record of the current phase in this lane (LE_SHARE never crosses it)
+  PickTag tag_{-1, -1};             // the tag of the records this recorder makes next (picking frames: fdh_set_pick_tag, the front-end)
 
  protected:
   DrawRec& next_rec();  // the lane's next record slot, zeroed (counted by emit_* when the draw survives culling)
@@ -335,6 +340,8 @@ struct RetainedRoot {
   std::vector<DrawRec> recs;     // in device form (Recorder::push_rec)
   std::vector<BinRec> bins;      // bounds, cores, list-entry flags (the last record's LE_SHARE is decided again at every splice)
   std::vector<QuadExt> exts;     // of this root's records, DrawRec::ext relative to exts.front()
+  std::vector<PickTag> tags;     // of this root's records, when it was walked in a picking frame (tagged)
+  bool tagged = false;
   PhaseSum sum;
   int64_t fragments = 0;
   bool cacheable = false;        // no blur node inside (those split the frame into phases: re-walked every frame)
@@ -397,6 +404,11 @@ struct LaunchJob {
   bool damage = false, damage_force = false;
   uint64_t damage_key = 0;
   int n_exts = 0;
+  // picking (include/figdraw_hip_pick.h): the frame was recorded with picking on; its records' tags in painter's order; its deepest clip
+  // nesting (what the pick kernels' clip stacks need)
+  bool pick = false;
+  std::vector<PickTag> pick_tags;
+  int pick_depth = 0;
 };
 
 class Context : public Recorder {
@@ -469,6 +481,12 @@ class Context : public Recorder {
   // damage tracking (include/figdraw_hip_damage.h)
   void set_damage_tracking(bool on);
   void damage_bins(uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged, bool changed_only);
+  // picking (include/figdraw_hip_pick.h; fdh_context.cpp)
+  void set_pick(bool on) { pick_on_ = on; }
+  void set_pick_tag(int32_t z, int32_t id) { tag_ = PickTag{z, id}; }
+  void pick_points(const float* xy, int n, int threshold, uint32_t flags, int max_hits, FdhPickHit* out, int* counts);
+  void pick_region(int x, int y, int w, int h, int threshold, uint32_t flags, int32_t* out_draw);
+  void pick_draw_tags(int32_t* zlevels, int32_t* ids, int cap, int* n);
   // Culling (fdh_set_cull): draws whose pixel bounds miss the frame -- or, under fdh_set_stripe, the stripe's rows widened by the
   // reach of the scene's blur nodes -- are not recorded, and the scene front-end skips the content of a clipping node whose mask
   // lies outside.  0 off, 1 on (default; off while the call recorder runs, so that recorded streams stay the reference's), 2 on
@@ -630,6 +648,11 @@ class Context : public Recorder {
   // pass of a node that did not run writes over (k_damage_guard); dmg_valid_: the surface holds the frame of key dmg_key_ and the
   // signatures are that frame's
   bool damage_on_ = false;  // (calling thread: fdh_set_damage_tracking)
+  // picking: fdh_set_pick (calling thread), latched per frame at begin_frame (pick_frame_: the lanes keep tags); the pick launches' buffers
+  bool pick_on_ = false, pick_frame_ = false;
+  void pick_check(const char* who, int threshold, uint32_t flags);
+  DeviceBuf<uint8_t> d_pick_, d_pick_spill_;
+  PinnedBuf<uint8_t> h_pick_;
   bool dmg_valid_ = false, dmg_last_ = false;
   uint64_t dmg_key_ = 0;
   int dmg_bx_ = 0, dmg_by_ = 0;

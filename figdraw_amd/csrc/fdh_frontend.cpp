@@ -540,6 +540,10 @@ struct Walker {
     // (the walk recurses like the reference's: a chain of thousands of only children would run the thread's stack out)
     if (depth >= 2048) throw Error(FDH_ERR_UNSUPPORTED, "scene: nodes nested deeper than 2048");
     struct Deeper { int& d; explicit Deeper(int& x) : d(x) { d++; } ~Deeper() { d--; } } deeper(depth);
+    // picking: this node owns every record its stage makes -- shadows, fill, stroke, glyph / image quads, curve spans, the blur
+    // composite, its clip and rect-mask records (its children's records carry their own tags)
+    const PickTag own{L.zlevel, idx};
+    ctx.tag_ = own;
     float box[4], rx[4], ry[4];
     box_of(n, box);
     radii(n, rx, ry);
@@ -627,6 +631,7 @@ struct Walker {
         }
       }
     }
+    ctx.tag_ = own;
     if (rmask) ctx.pop_rect_mask();
     if (clip) ctx.pop_mask();
     if (xf) ctx.restore_transform();
@@ -728,6 +733,7 @@ bool ParallelWalk::group(Walker& mw, const FdhLayer& L, const int* items, int n)
     R.sum_ = PhaseSum{};
     R.fragments_ = 0; R.culled_draws_ = 0;
     R.phase_floor_ = (int)Ln.recs.n;
+    R.tag_ = base.tag_;
     o.p.lane = slot + 1; o.p.first = (uint32_t)Ln.recs.n; o.p.ext_first = (uint32_t)Ln.exts.n;
     try {
       Walker w{R, mw.scene, mw.ui, mw.links, false};
@@ -752,7 +758,11 @@ bool ParallelWalk::group(Walker& mw, const FdhLayer& L, const int* items, int n)
   std::exception_ptr err;
   for (const Out& o : outs) { if (o.serial_only || o.err) failed = true; if (o.err && !err) err = o.err; }
   if (failed) {  // nothing of the group stays: the calling thread walks it itself (or the frame ends with the error)
-    for (int s = 0; s < slots; s++) { Lane& Ln = C.lane(s + 1); Ln.recs.n = Ln.bins.n = Ln.boxes.n = marks[(size_t)s].recs; Ln.exts.n = marks[(size_t)s].exts; }
+    for (int s = 0; s < slots; s++) {
+      Lane& Ln = C.lane(s + 1);
+      Ln.recs.n = Ln.bins.n = Ln.boxes.n = marks[(size_t)s].recs; Ln.exts.n = marks[(size_t)s].exts;
+      if (C.pick_frame_) Ln.tags.n = marks[(size_t)s].recs;
+    }
     C.open_piece();
     if (err) std::rethrow_exception(err);
     return false;
@@ -1049,6 +1059,10 @@ void Context::scene_replace_root(int layer, int slot, const FdhFig* subtree, int
     for (size_t i = 0; i < D.nodes.size(); i++)
       if (ro[i] != old_root) { remap[i] = (int)kept.size(); kept.push_back(D.nodes[i]); }
     for (FdhFig& f : kept) if (f.parent >= 0) f.parent = remap[(size_t)f.parent];
+    // (the other roots' caches stay clean, and their records' tags name nodes by index: they move with the compaction)
+    for (size_t s = 0; s < D.cache.size(); s++)
+      if ((int)s != slot)
+        for (PickTag& g : D.cache[s].tags) if (g.id >= 0 && (size_t)g.id < remap.size()) g.id = remap[(size_t)g.id];
     // (a root slot whose node hangs inside the removed subtree -- fdh_scene_update_nodes may have given a listed root a parent --
     // goes with it: it would name a node that no longer exists)
     for (size_t s = D.roots.size(); s-- > 0;) {
@@ -1114,7 +1128,8 @@ void Context::scene_render() {
       for (size_t s = 0; s < D.roots.size(); s++) {
         RetainedRoot& C = D.cache[s];
         // (cached records were culled to the rows in force when they were made: good for any frame that produces no row beyond them)
-        if (!C.dirty && C.cacheable && !config_changed && C.cull_y0 <= cull_y0_ && C.cull_y1 >= cull_y1_ && C.atlas_epoch == atlas_epoch_) {
+        if (!C.dirty && C.cacheable && !config_changed && C.cull_y0 <= cull_y0_ && C.cull_y1 >= cull_y1_ && C.atlas_epoch == atlas_epoch_ &&
+            (C.tagged || !pick_frame_)) {
           splice_cached(C);
           R.roots_reused++;
           continue;
@@ -1130,8 +1145,10 @@ void Context::scene_render() {
         C.atlas_epoch = atlas_epoch_;
         C.cull_y0 = cull_y0_; C.cull_y1 = cull_y1_;
         C.cacheable = phases_.size() == p0 && blurs_.size() == b0;
-        C.recs.clear(); C.bins.clear(); C.exts.clear();
+        C.recs.clear(); C.bins.clear(); C.exts.clear(); C.tags.clear();
+        C.tagged = pick_frame_;
         if (C.cacheable) {
+          if (pick_frame_) C.tags.assign(L0.tags.p + r0, L0.tags.p + L0.tags.n);
           C.recs.assign(L0.recs.p + r0, L0.recs.p + L0.recs.n);
           C.bins.assign(L0.bins.p + r0, L0.bins.p + L0.bins.n);
           C.exts.assign(L0.exts.p + e0, L0.exts.p + L0.exts.n);

@@ -6,3 +6,4 @@
 #include "k_blur_mx.hip"
 #include "k_atlas_upload.hip"
 #include "k_damage.hip"
+#include "k_pick.hip"

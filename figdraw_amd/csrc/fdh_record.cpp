@@ -146,6 +146,7 @@ void Recorder::push_rec(BBox b) {  // (by value: callers pass bounds that live i
   lane_->recs.n++;
   lane_->bins.n++;
   lane_->boxes.n++;
+  if (cx_->pick_frame_) { *lane_->tags.slot() = tag_; lane_->tags.n++; }
 }
 
 // What k_bin_draws scans: 7-bit inclusive bounds in bin units, upper bounds complemented (x0 | y0 << 8 | (127 - x1) << 16 |
@@ -1205,6 +1206,8 @@ void Context::begin_frame(int w, int h, bool clear, const float rgba[4]) {  // g
   frame_begun_ = true;
   mask_begun_ = false;
   mask_depth_ = 0;
+  pick_frame_ = pick_on_;
+  tag_ = PickTag{-1, -1};
   rect_masks_.clear();
   open_ops_.clear();
   outer_rect_masks_ = 0;
@@ -1264,6 +1267,20 @@ void Context::end_frame() {  // glcontext.nim:1982-1989
   host_record_ms_ = std::chrono::duration<float, std::milli>(t1 - t_begin_frame_).count() - (float)host_ns_[1] * 1e-6f;
   // a list entry carries the draw index in 25 bits beside its path code and flags (k_bin_draws, LE_INDEX)
   if (n_total_ >= LE_INDEX) throw Error(FDH_ERR_INVALID, "more than 33 554 430 draw records in one frame");
+  {  // picking: the frame's tag table, in painter's order, goes with the frame (a record-only context keeps it as its last frame)
+    LaunchJob& T = host_only_ ? job_ : next_;
+    T.pick = pick_frame_;
+    T.pick_depth = deepest_clip_;
+    T.pick_tags.clear();
+    if (pick_frame_) {
+      T.pick_tags.resize(n_total_);
+      size_t o = 0;
+      for (const Piece& p : pieces_) {
+        if (p.n) std::memcpy(static_cast<void*>(T.pick_tags.data() + o), lane(p.lane).tags.p + p.first, p.n * sizeof(PickTag));
+        o += p.n;
+      }
+    }
+  }
   if (host_only_) return;
   // prepare() notes what the device block will hold once this frame's upload has run (blur tables, the retained path's shadow):
   // if the frame is dropped before it is handed over -- prepare or the wait for the previous frame's launches throws, or an
@@ -1435,6 +1452,7 @@ void Context::splice_cached(const RetainedRoot& C) {
   L.recs.append(C.recs.data(), C.recs.size());
   L.bins.append(C.bins.data(), C.bins.size());
   L.exts.append(C.exts.data(), C.exts.size());
+  if (pick_frame_) L.tags.append(C.tags.data(), C.tags.size());  // (scene_render splices only tagged roots into a picking frame)
   if (!C.exts.empty())
     for (size_t i = r0; i < L.recs.n; i++) if (L.recs[i].op_mode & F_GENERAL) L.recs[i].ext += e0;
   L.boxes.reserve(L.bins.n);
