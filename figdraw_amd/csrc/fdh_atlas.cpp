@@ -1,0 +1,335 @@
+// fdh_atlas.cpp -- the image atlas: skyline packer, level chains, glyph images and outlines, the Flippy container.
+#include "fdh_context.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace fdh {
+
+// ------------------------------------------------------------------ atlas (glcontext.nim:536-641, textures.nim:88-119)
+void Context::alloc_atlas(int size) {
+  int s = 1;
+  while (s < size) s <<= 1;  // the samplers mask coordinates: keep the atlas a power of two
+  for (auto& l : atlas_levels_) { if (l) (void)hipFree(l); l = nullptr; }
+  atlas_size_ = s;
+  n_levels_ = 0;
+  for (int ls = s; ls >= 1 && n_levels_ < kMaxMips; ls >>= 1) {
+    if (!host_only_) {
+      FDH_HIP(hipMalloc((void**)&atlas_levels_[n_levels_], (size_t)ls * ls * 4));
+      FDH_HIP(hipMemsetAsync(atlas_levels_[n_levels_], 0, (size_t)ls * ls * 4, stream_));
+    }
+    n_levels_++;
+    if (ls == 1) break;
+  }
+  heights_.assign((size_t)s, 0);
+  entries_.clear();
+  atlas_epoch_++;  // cached draw records of image nodes carry atlas positions (RetainedRoot::atlas_epoch)
+}
+void Context::reset_atlas(int minimum_size) {
+  sync();
+  int s = initial_atlas_size_;
+  while (s < minimum_size) s *= 2;  // plannedAtlasSize
+  alloc_atlas(s);
+}
+int64_t Context::atlas_packed_area() const {
+  int64_t a = 0;
+  for (auto h : heights_) a += h;
+  return a;
+}
+void Context::find_empty_rect(int w, int h, int* ox, int* oy) {  // glcontext.nim:541-579
+  for (;;) {
+    const int S = atlas_size_, M = atlas_margin_;
+    const int iw = w + M * 2, ih = h + M * 2;
+    int lowest = S, at = 0;
+    for (int i = 0; i < S; i++) {
+      int v = heights_[i];
+      if (v < lowest) {
+        bool fit = true;
+        for (int j = 0; j <= iw; j++) {
+          if (i + j >= S) { fit = false; break; }
+          if ((int)heights_[i + j] > v) { fit = false; break; }
+        }
+        if (fit) { lowest = v; at = i; }
+      }
+    }
+    if (lowest + ih > S) {
+      if (S >= 16384) throw Error(FDH_ERR_ATLAS_FULL, "atlas full at 16384^2");
+      sync();
+      alloc_atlas(S * 2);  // grow(): resetImageAtlas(atlasSize * 2) drops every entry (glcontext.nim:536-539)
+      continue;
+    }
+    for (int j = at; j < at + iw; j++) heights_[j] = (uint16_t)(lowest + ih + M * 2);
+    *ox = at + M;
+    *oy = lowest + M;
+    return;
+  }
+}
+void Context::upload_atlas_rect(int level, int x, int y, int w, int h, const uint8_t* rgba) {
+  const int LS = atlas_size_ >> level;
+  if (x < 0 || y < 0 || x + w > LS || y + h > LS || w <= 0 || h <= 0 || host_only_) return;
+  FDH_HIP(hipMemcpy2D(atlas_levels_[level] + (size_t)y * LS + x, (size_t)LS * 4, rgba, (size_t)w * 4, (size_t)w * 4, h,
+                      hipMemcpyHostToDevice));  // synchronous: image uploads are rare and the source is pageable
+}
+// pixie's Image.minifyBy2 on premultiplied RGBA8 (the arithmetic the reference's data/img1.flippy pins: its stored levels are this
+// chain): box SUM div 4; an odd extent rounds the result size up, the extra column / row holding mix(a, b, 0.5) * 0.5 of the last
+// source column / row (mix = (127 a + 128 b) div 255, * 0.5 = (128 v) div 255) and the extra corner the last texel * 0.25 =
+// (64 v) div 255.  k_minify2 is the device form of the same step.
+static void minify_by2_host(const uint8_t* src, int w, int h, uint8_t* dst) {
+  const int nw = (w + 1) / 2, nh = (h + 1) / 2;
+  auto at = [&](int x, int y, int k) -> unsigned { return src[((size_t)y * w + x) * 4 + k]; };
+  for (int y = 0; y < nh; y++) {
+    const bool row_pair = 2 * y + 1 < h;
+    for (int x = 0; x < nw; x++) {
+      const bool col_pair = 2 * x + 1 < w;
+      for (int k = 0; k < 4; k++) {
+        unsigned v;
+        if (col_pair && row_pair) v = (at(2 * x, 2 * y, k) + at(2 * x + 1, 2 * y, k) + at(2 * x + 1, 2 * y + 1, k) + at(2 * x, 2 * y + 1, k)) >> 2;
+        else if (row_pair) v = ((at(w - 1, 2 * y, k) * 127u + at(w - 1, 2 * y + 1, k) * 128u) / 255u) * 128u / 255u;
+        else if (col_pair) v = ((at(2 * x, h - 1, k) * 127u + at(2 * x + 1, h - 1, k) * 128u) / 255u) * 128u / 255u;
+        else v = at(w - 1, h - 1, k) * 64u / 255u;
+        dst[((size_t)y * nw + x) * 4 + k] = (uint8_t)v;
+      }
+    }
+  }
+}
+void Context::put_levels(int x, int y, int w, int h, const uint8_t* rgba) {
+  // updateSubImage: level chain by repeated minifyBy2 while width > 1 and height > 1 (textures.nim:106-119).
+  std::vector<uint8_t> cur(rgba, rgba + (size_t)w * h * 4), nxt;
+  int cw = w, ch = h, lx = x, ly = y, level = 0;
+  while (cw > 1 && ch > 1 && level < n_levels_) {
+    upload_atlas_rect(level, lx, ly, cw, ch, cur.data());
+    const int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
+    nxt.assign((size_t)nw * nh * 4, 0);
+    minify_by2_host(cur.data(), cw, ch, nxt.data());
+    cur.swap(nxt);
+    cw = nw; ch = nh; lx /= 2; ly /= 2; level++;
+  }
+}
+// the ink boxes of an image whose texels the host holds (AtlasEntry): one pass, sixteen running boxes
+static void measure_ink(AtlasEntry& e, const uint8_t* rgba) {
+  // Glyph- and icon-sized images only (a 48 x 48 MSDF cell, a 20 px glyph): that is where a draw covers a fraction of its quad, and
+  // the pass stays in the microseconds.  A photograph is opaque to its edges and would cost a pass over megapixels for nothing.
+  e.has_ink = false;
+  if (e.w > 128 || e.h > 128) return;
+  for (int k = 0; k < kInkLevels; k++) e.ink_a[k] = e.ink_rgb[k] = InkBox{32767, 32767, 0, 0};
+  auto grow = [](InkBox& b, int x, int y) {
+    b.x0 = (int16_t)std::min<int>(b.x0, x); b.y0 = (int16_t)std::min<int>(b.y0, y);
+    b.x1 = (int16_t)std::max<int>(b.x1, x + 1); b.y1 = (int16_t)std::max<int>(b.y1, y + 1);
+  };
+  for (int y = 0; y < e.h; y++) {
+    const uint8_t* row = rgba + (size_t)y * e.w * 4;
+    for (int x = 0; x < e.w; x++) {
+      const int a = row[4 * x + 3], m = std::max<int>(row[4 * x], std::max<int>(row[4 * x + 1], row[4 * x + 2]));
+      // levels the value exceeds: t = 0, 16, .. below it.  The boxes are nested (level k's holds level k + 1's): a texel inside
+      // the highest one it counts for is inside them all.
+      const int la = std::min((a + 15) >> 4, kInkLevels), lm = std::min((m + 15) >> 4, kInkLevels);
+      auto inside = [&](const InkBox& b) { return x >= b.x0 && x < b.x1 && y >= b.y0 && y < b.y1; };
+      if (la > 0 && !inside(e.ink_a[la - 1])) for (int k = 0; k < la; k++) grow(e.ink_a[k], x, y);
+      if (lm > 0 && !inside(e.ink_rgb[lm - 1])) for (int k = 0; k < lm; k++) grow(e.ink_rgb[k], x, y);
+    }
+  }
+  for (int k = 0; k < kInkLevels; k++) {  // nothing above the level: an empty box at the origin
+    if (e.ink_a[k].x1 <= e.ink_a[k].x0) e.ink_a[k] = InkBox{0, 0, 0, 0};
+    if (e.ink_rgb[k].x1 <= e.ink_rgb[k].x0) e.ink_rgb[k] = InkBox{0, 0, 0, 0};
+  }
+  e.has_ink = true;
+}
+void Context::put_image(int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]) {
+  if (w <= 0 || h <= 0 || !rgba) throw Error(FDH_ERR_INVALID, "put_image: empty image");
+  if (!host_only_) FDH_HIP(hipSetDevice(device_));
+  int x, y;
+  find_empty_rect(w, h, &x, &y);
+  AtlasEntry ent{x, y, w, h};
+  measure_ink(ent, rgba);
+  entries_[key] = ent;
+  atlas_epoch_++;
+  sync();  // a frame in flight may still sample the atlas
+  put_levels(x, y, w, h, rgba);
+  if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
+}
+// A rasterised glyph on its way into the atlas, processed on the device: optional LCD filter (applyLcdFilter, common/
+// textrasters/pixie_raster.nim:12-43, what renderPixieGlyph does between fillText and loadGlyphImage :83-91), then the
+// level chain of updateSubImage (textures.nim:106-119) -- every step a kernel on the context's stream.
+void Context::put_glyph_image(int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]) {
+  if (w <= 0 || h <= 0 || !rgba) throw Error(FDH_ERR_INVALID, "put_glyph_image: empty image");
+  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) throw Error(FDH_ERR_INVALID, "put_glyph_image: unknown flag");
+  if (flags & FDH_GLYPH_LCD_CONTEXT) flags = text_lcd_filtering_ ? FDH_GLYPH_LCD_FILTER : 0u;  // as setTextLcdFilteringEnabled said
+  int x, y;
+  find_empty_rect(w, h, &x, &y);
+  entries_[key] = AtlasEntry{x, y, w, h, false, {}, {}};
+  atlas_epoch_++;
+  if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
+  if (host_only_) return;
+  FDH_HIP(hipSetDevice(device_));
+  sync();  // a frame in flight may still sample the atlas
+  const size_t n = (size_t)w * h;
+  glyph_a_.reserve(n);
+  glyph_b_.reserve(n);
+  FDH_HIP(hipMemcpyAsync(glyph_a_.ptr, rgba, n * 4, hipMemcpyHostToDevice, stream_));
+  glyph_to_atlas(glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, flags);
+}
+// device image -> (LCD filter) -> atlas level chain, all on the context's stream; waits for it (the caller's buffers are free after)
+void Context::glyph_to_atlas(uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags) {
+  if (flags & FDH_GLYPH_LCD_FILTER) { launch_lcd_filter(stream_, cur, nxt, w, h); std::swap(cur, nxt); }
+  int cw = w, ch = h, lx = x, ly = y, level = 0;
+  while (cw > 1 && ch > 1 && level < n_levels_) {
+    launch_atlas_blit(stream_, atlas_levels_[level], atlas_size_ >> level, lx, ly, cur, cw, ch);
+    const int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
+    launch_minify2(stream_, cur, nxt, cw, ch);
+    std::swap(cur, nxt);
+    cw = nw; ch = nh; lx /= 2; ly /= 2; level++;
+  }
+  FDH_HIP(hipStreamSynchronize(stream_));
+  FDH_HIP(hipGetLastError());
+}
+
+// generateGlyph's job (common/fontglyphs.nim:61-106) with an own rasteriser in pixie's place: a glyph OUTLINE (quadratic segments in
+// pixel units of the w x h image, y down; cx = NaN marks a straight line) becomes coverage on the device and goes into the atlas.
+// The curves are flattened here on the host (chord error <= 0.025 px; the same float formula as oracle/figdraw_oracle.c,
+// fo_flatten_outline), the area accumulation runs in k_rasterize_lines.  pixie's texels are third-party and unpinned
+// (SURVEY.md 8c): parity is defined against the oracle's restatement of the same published algorithm.
+static int flatten_count(const float* q) {
+  const float ddx = q[0] - 2.0f * q[2] + q[4], ddy = q[1] - 2.0f * q[3] + q[5];
+  const float dev = std::sqrt(ddx * ddx + ddy * ddy);
+  const int n = (int)std::ceil(std::sqrt(dev * 10.0f));  // error of n chords = dev / (4 n^2) <= 0.025 px
+  return n < 1 ? 1 : (n > 64 ? 64 : n);
+}
+void Context::put_glyph_outline(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) {
+  if (w <= 0 || h <= 0 || w > 4096 || h > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_outline: image size must be in 1..4096");
+  if (n < 0 || (n > 0 && !segs)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: bad outline");
+  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: unknown flag");
+  if (flags & FDH_GLYPH_LCD_CONTEXT) flags = text_lcd_filtering_ ? FDH_GLYPH_LCD_FILTER : 0u;
+  std::vector<float> lines;
+  lines.reserve((size_t)n * 16);
+  for (int i = 0; i < n; i++) {
+    const float* q = segs + 6 * (size_t)i;
+    if (q[2] != q[2]) { lines.insert(lines.end(), {q[0], q[1], q[4], q[5]}); continue; }
+    const int k = flatten_count(q);
+    float px = q[0], py = q[1];
+    for (int j = 1; j <= k; j++) {
+      const float t = (float)j / (float)k, u = 1.0f - t;
+      const float x = j == k ? q[4] : (u * u) * q[0] + (2.0f * u * t) * q[2] + (t * t) * q[4];
+      const float y = j == k ? q[5] : (u * u) * q[1] + (2.0f * u * t) * q[3] + (t * t) * q[5];
+      lines.insert(lines.end(), {px, py, x, y});
+      px = x; py = y;
+    }
+  }
+  int x, y;
+  find_empty_rect(w, h, &x, &y);
+  entries_[key] = AtlasEntry{x, y, w, h, false, {}, {}};
+  atlas_epoch_++;
+  if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
+  if (host_only_) return;
+  FDH_HIP(hipSetDevice(device_));
+  sync();
+  const size_t npx = (size_t)w * h, m = lines.size() / 4;
+  glyph_a_.reserve(npx);
+  glyph_b_.reserve(npx);
+  glyph_lines_.reserve(std::max<size_t>(lines.size(), 4));
+  glyph_acc_.reserve((size_t)h * (w + 2));
+  if (m) FDH_HIP(hipMemcpyAsync(glyph_lines_.ptr, lines.data(), lines.size() * sizeof(float), hipMemcpyHostToDevice, stream_));
+  launch_rasterize_lines(stream_, reinterpret_cast<const float4*>(glyph_lines_.ptr), (int)m, w, h, glyph_acc_.ptr, glyph_a_.ptr);
+  glyph_to_atlas(glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, flags);  // (synchronises: `lines` stays alive until then)
+}
+// Flippy: figdraw's mip-mapped image container (common/formatflippy.nim:77-149).  Layout: "flip", u32 version (1), then per
+// mip level "mip!", u32 width, u32 height, u32 zlen, and a raw-snappy block holding straight RGBA8.  The reference
+// converts every texel to pixie's premultiplied ColorRGBX on load and uploads level l at (x >> l, y >> l)
+// (putFlippy glcontext.nim:610-620) instead of rebuilding the chain with minifyBy2.
+static std::vector<uint8_t> snappy_uncompress(const uint8_t* in, size_t n) {
+  size_t i = 0, len = 0;
+  for (int shift = 0;; shift += 7) {
+    if (i >= n || shift > 35) throw Error(FDH_ERR_INVALID, "flippy: bad snappy length");
+    const uint8_t c = in[i++];
+    len |= (size_t)(c & 0x7f) << shift;
+    if (c < 0x80) break;
+  }
+  std::vector<uint8_t> out;
+  out.reserve(len);
+  auto need = [&](size_t k) { if (i + k > n) throw Error(FDH_ERR_INVALID, "flippy: truncated snappy block"); };
+  while (i < n) {
+    const uint8_t tag = in[i++];
+    const int t = tag & 3;
+    if (t == 0) {  // literal
+      size_t l = tag >> 2;
+      if (l < 60) l += 1;
+      else {
+        const int nb = (int)l - 59;
+        need(nb);
+        l = 0;
+        for (int k = 0; k < nb; k++) l |= (size_t)in[i + k] << (8 * k);
+        l += 1;
+        i += nb;
+      }
+      need(l);
+      out.insert(out.end(), in + i, in + i + l);
+      i += l;
+    } else {  // copy with 1-, 2- or 4-byte offset
+      size_t l, off;
+      if (t == 1) { need(1); l = ((tag >> 2) & 7) + 4; off = ((size_t)(tag >> 5) << 8) | in[i]; i += 1; }
+      else if (t == 2) { need(2); l = (tag >> 2) + 1; off = in[i] | ((size_t)in[i + 1] << 8); i += 2; }
+      else { need(4); l = (tag >> 2) + 1; off = in[i] | ((size_t)in[i + 1] << 8) | ((size_t)in[i + 2] << 16) | ((size_t)in[i + 3] << 24); i += 4; }
+      if (off == 0 || off > out.size()) throw Error(FDH_ERR_INVALID, "flippy: bad snappy copy offset");
+      for (size_t k = 0; k < l; k++) out.push_back(out[out.size() - off]);
+    }
+  }
+  if (out.size() != len) throw Error(FDH_ERR_INVALID, "flippy: snappy length mismatch");
+  return out;
+}
+void Context::put_mips(int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]) {
+  // putFlippy glcontext.nim:610-620: level l goes to (x >> l, y >> l) with the size the container stored for it
+  if (n <= 0 || !ws || !hs || !premul_rgba) throw Error(FDH_ERR_INVALID, "put_mips: no mip levels");
+  for (int l = 0; l < n; l++)
+    if (ws[l] <= 0 || hs[l] <= 0 || !premul_rgba[l]) throw Error(FDH_ERR_INVALID, "put_mips: bad mip level");
+  if (!host_only_) FDH_HIP(hipSetDevice(device_));
+  int rx = 0, ry = 0;
+  find_empty_rect(ws[0], hs[0], &rx, &ry);
+  entries_[key] = AtlasEntry{rx, ry, ws[0], hs[0], false, {}, {}};
+  atlas_epoch_++;
+  if (out_rect) { out_rect[0] = rx; out_rect[1] = ry; out_rect[2] = ws[0]; out_rect[3] = hs[0]; }
+  sync();
+  for (int l = 0; l < n && l < n_levels_; l++) upload_atlas_rect(l, rx >> l, ry >> l, ws[l], hs[l], premul_rgba[l]);
+}
+void Context::put_flippy(int64_t key, const uint8_t* data, size_t n, int out_rect[4]) {
+  auto u32 = [&](size_t at) { return (uint32_t)data[at] | ((uint32_t)data[at + 1] << 8) | ((uint32_t)data[at + 2] << 16) | ((uint32_t)data[at + 3] << 24); };
+  if (!data || n < 8 || std::memcmp(data, "flip", 4) != 0) throw Error(FDH_ERR_INVALID, "Invalid Flippy header");
+  if (u32(4) != 1) throw Error(FDH_ERR_INVALID, "Invalid Flippy version");
+  std::vector<std::vector<uint8_t>> mips;
+  std::vector<int> ws, hs;
+  size_t i = 8;
+  while (i < n) {
+    if (i + 16 > n || std::memcmp(data + i, "mip!", 4) != 0) throw Error(FDH_ERR_INVALID, "Invalid Flippy sub header");
+    const int w = (int)u32(i + 4), h = (int)u32(i + 8);
+    const size_t z = u32(i + 12);
+    i += 16;
+    if (i + z > n || w <= 0 || h <= 0) throw Error(FDH_ERR_INVALID, "Flippy read error");
+    std::vector<uint8_t> px = snappy_uncompress(data + i, z);
+    i += z;
+    if (px.size() != (size_t)w * h * 4) throw Error(FDH_ERR_INVALID, "Flippy mip size mismatch");
+    for (size_t k = 0; k < (size_t)w * h; k++) {  // ColorRGBA -> premultiplied ColorRGBX
+      const unsigned a = px[4 * k + 3];
+      px[4 * k + 0] = (uint8_t)((px[4 * k + 0] * a) / 255);
+      px[4 * k + 1] = (uint8_t)((px[4 * k + 1] * a) / 255);
+      px[4 * k + 2] = (uint8_t)((px[4 * k + 2] * a) / 255);
+    }
+    mips.push_back(std::move(px));
+    ws.push_back(w);
+    hs.push_back(h);
+  }
+  if (mips.empty()) throw Error(FDH_ERR_INVALID, "Flippy has no mip levels");
+  std::vector<const uint8_t*> ptrs;
+  for (auto& m : mips) ptrs.push_back(m.data());
+  put_mips(key, (int)mips.size(), ws.data(), hs.data(), ptrs.data(), out_rect);
+}
+void Context::update_image(int64_t key, int w, int h, const uint8_t* rgba) {  // glcontext.nim:591-604
+  auto it = entries_.find(key);
+  if (it == entries_.end()) throw Error(FDH_ERR_INVALID, "update_image: unknown key");
+  if (it->second.w != w || it->second.h != h) throw Error(FDH_ERR_INVALID, "update_image: size mismatch");
+  if (!rgba) throw Error(FDH_ERR_INVALID, "update_image: null image");
+  sync();
+  measure_ink(it->second, rgba);  // the new texels have bounds of their own (draws shrink to them: shrink_to_ink) ...
+  atlas_epoch_++;                 // ... and records cached for retained scenes hold the old ones
+  put_levels(it->second.x, it->second.y, w, h, rgba);
+}
+
+}  // namespace fdh

@@ -95,7 +95,7 @@ struct PinnedBuf {
 // own memory instead of fetching it over the link with a round trip per lane: k_upload_frame 7.1 -> ~3 us.  Write-only for the
 // CPU -- a load from it crosses the link uncached -- so growth does NOT carry contents over (callers set n = 0 first, as the pinned
 // mirrors always did), and a store fence (store_fence()) precedes the hand-over to whoever launches the kernels.
-bool vram_staging(int device);  // large-BAR device and FDH_VRAM_STAGING != 0, decided per device ordinal (fdh_context.cpp)
+bool vram_staging(int device);  // large-BAR device and FDH_VRAM_STAGING != 0, decided per device ordinal (fdh_vram.cpp)
 // Device blocks for staging come from, and go back to, a process-wide store by size class (powers of two from 4 KB): they are
 // never handed back to the driver while the process lives.  A block the driver recycles may be memory another allocation's
 // kernels wrote through the L2s; the host's stores reach memory BESIDE those caches, and a line written back later lands on top
@@ -208,7 +208,7 @@ struct Lane {
   HostVec<BinRec> bins;   // bins[i].box IS the bounds of record i (clip pushes: the union of their content, final at the pop)
   HostVec<QuadExt> exts;  // DrawRec::ext of an F_GENERAL record indexes THIS array; the upload re-bases it
   HostVec<uint32_t> boxes;  // the records' 4-byte bin boxes (what k_bin_draws scans; the device derives its own from the BinRecs):
-                            // kept here for the chunk boxes -- the union box of every 256 draws -- which prepare builds over the pieces
+                            // kept here for the chunk boxes -- the union box of every 256 draws -- which Context::build_misc builds over the pieces
   HostVec<DrawRec> up_recs;  // pinned mirrors (device contexts): what the GPU reads; element i = element i of the array above
   HostVec<BinRec> up_bins;
   HostVec<QuadExt> up_exts;
@@ -371,6 +371,21 @@ struct RetainedScene {
   int64_t roots_walked = 0, roots_reused = 0;  // of the last fdh_scene_render
 };
 
+// Where everything lies in a frame's device block: records | extensions | bin records | bin boxes | chunk boxes | phase table | blur
+// weight tables, byte offsets on 256-byte boundaries.  Laid out once per frame (Context::layout_frame_block) and kept with the frame.
+struct FrameLayout {
+  size_t recs = 0, exts = 0, binrecs = 0, boxes = 0, chunks = 0, phase_first = 0, tables = 0, total = 0;
+  size_t n = 0, n_ext = 0, n_chunks = 1;  // records, extensions, chunk boxes (one per 256 records)
+  std::vector<size_t> mx_h, mx_v;         // per blur node: its H / V weight table (0: none -- a filter too wide for the matrix-pipe passes)
+  size_t misc() const { return chunks; }  // "from the chunk boxes on": what a staging slot's misc buffer holds (Context::build_misc)
+  void lay_out(size_t n_recs, size_t n_exts, size_t n_phases, const std::vector<BlurJob>& blurs);  // fdh_prepare.cpp
+  // two frames put everything at the same place (`tables` and `n_chunks` follow from the fields compared)
+  bool operator==(const FrameLayout& o) const {
+    return total == o.total && recs == o.recs && exts == o.exts && binrecs == o.binrecs && boxes == o.boxes && chunks == o.chunks &&
+           phase_first == o.phase_first && n == o.n && n_ext == o.n_ext && mx_h == o.mx_h && mx_v == o.mx_v;
+  }
+};
+
 // What the launch side needs of one frame: filled by Context::prepare on the calling thread (which also fills the run table
 // the upload kernel works through), consumed by Context::issue / launch_frame on the context's submit thread, and kept
 // for fdh_replay / fdh_profile.
@@ -387,7 +402,8 @@ struct LaunchJob {
   std::vector<char> blur_fused;              // per blur job: both passes run as ONE out-of-place kernel (full-frame nodes)
   int n_fused = 0;
   int n_recs = 0;
-  View dv;                 // typed views into the device frame block
+  FrameLayout layout;      // of the device frame block, as this frame was prepared
+  View dv;                 // typed views into it
   uint32_t* mask_spill = nullptr;  // clip levels beyond kMaskDepth, [level][strip][lane]; spill_stride dwords per level
   size_t spill_stride = 0;
   uint2* lists = nullptr;  // bin lists / counts (device)
@@ -400,7 +416,7 @@ struct LaunchJob {
   void* d_dst = nullptr;
   int staging_slot = -1;
   // damage tracking (fdh_set_damage_tracking): the frame is tracked; it is rendered in full whatever its key (no clear, a fused full-frame
-  // blur, more blur nodes than the resolve takes); the frame key (Context::prepare: everything outside the lists a bin's pixels depend on)
+  // blur, more blur nodes than the resolve takes); the frame key (Context::damage_frame_key: everything outside the lists a bin's pixels depend on)
   bool damage = false, damage_force = false;
   uint64_t damage_key = 0;
   int n_exts = 0;
@@ -460,8 +476,9 @@ class Context : public Recorder {
   void scene_render();
   void scene_stats(int64_t* walked, int64_t* reused) const { *walked = retained_.roots_walked; *reused = retained_.roots_reused; }
   int64_t uploaded_bytes() { drain(); return uploaded_bytes_; }
-  void debug_verify_upload(uint32_t out[24]);
-  void debug_bin_digest(uint64_t out[8]);        // fdh_debug_bin_digest (fdh_record.cpp)  // fdh_debug_verify_upload (fdh_record.cpp)
+  // fault hunting (fdh_debug.cpp)
+  void debug_verify_upload(uint32_t out[24]);  // fdh_debug_verify_upload
+  void debug_bin_digest(uint64_t out[8]);      // fdh_debug_bin_digest
   uint64_t record_digest();  // FNV-1a over the last frame's draw records (diagnostic: works on record-only contexts)
 
   // multi-GPU: the gather over RCCL (fdh_comm.cpp)
@@ -481,7 +498,7 @@ class Context : public Recorder {
   // damage tracking (include/figdraw_hip_damage.h)
   void set_damage_tracking(bool on);
   void damage_bins(uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged, bool changed_only);
-  // picking (include/figdraw_hip_pick.h; fdh_context.cpp)
+  // picking (include/figdraw_hip_pick.h; fdh_pick.cpp)
   void set_pick(bool on) { pick_on_ = on; }
   void set_pick_tag(int32_t z, int32_t id) { tag_ = PickTag{z, id}; }
   void pick_points(const float* xy, int n, int threshold, uint32_t flags, int max_hits, FdhPickHit* out, int* counts);
@@ -512,11 +529,47 @@ class Context : public Recorder {
  private:
   friend class Recorder;
   friend struct ParallelWalk;
+  void release_device_state();  // the destructor's device half (also a constructor that fails half way)
+  void rec_begin_frame(bool clear, const float rgba[4]);  // begin_frame / end_frame as the call recorder sees them (fdh_record.cpp)
+  void rec_end_frame();
+  // atlas (fdh_atlas.cpp)
   void alloc_atlas(int size);
   void upload_atlas_rect(int level, int x, int y, int w, int h, const uint8_t* rgba);
   void put_levels(int x, int y, int w, int h, const uint8_t* rgba);
   void find_empty_rect(int w, int h, int* ox, int* oy);
-  void prepare(LaunchJob& J);  // calling thread: recorded frame -> run table + launch description
+  // fold_clear's guard: puts a folded draw's bounds back into its lane when prepare is left, by return or by exception
+  struct FoldGuard {
+    BinRec* br = nullptr;
+    BBox box{0, 0, 0, 0};
+    FoldGuard() = default;
+    FoldGuard(FoldGuard&& o) noexcept : br(o.br), box(o.box) { o.br = nullptr; }
+    FoldGuard(const FoldGuard&) = delete;
+    FoldGuard& operator=(const FoldGuard&) = delete;
+    ~FoldGuard() { if (br) br->box = box; }
+  };
+
+  // calling thread: recorded frame -> run table + launch description (fdh_prepare.cpp)
+  void prepare(LaunchJob& J);
+  // prepare's stages, in the order it takes them.  The order is part of their contract:
+  //  - consolidate_pieces (a frame of more pieces than the run table holds) runs BEFORE fold_clear: the copy would carry the emptied box,
+  //    and the guard restores the original lane only -- fdh_debug_record_digest would find an empty box for record 0 of such a frame;
+  //  - fold_clear runs before damage_frame_key: the key mixes the folded clear colour;
+  //  - patch_runs / gather_runs read a lane's device views after the lane was published (the mirrors are then where they will stay);
+  //  - fence_staging comes last: everything this thread and the pool's threads stored into device memory is behind it.
+  void describe_frame(LaunchJob& J);
+  void size_bin_buffers(LaunchJob& J);       // bin lists, counts, the clip spill plane
+  void layout_frame_block(LaunchJob& J);     // J.layout; the block itself; views, table pointers and upload offsets from it
+  void choose_fused_blurs(LaunchJob& J);
+  void consolidate_pieces();                 // (only a frame of more pieces than the upload's run table holds)
+  FoldGuard fold_clear(LaunchJob& J);
+  void damage_frame_key(LaunchJob& J) const;
+  bool shadow_usable(const LaunchJob& J);
+  bool tables_resident(const LaunchJob& J, bool shadow_ok);
+  void build_misc(const LaunchJob& J, bool tables_resident);
+  bool patch_runs(LaunchJob& J, bool shadow_ok);          // retained scenes: upload what differs from the shadow; false: not this frame
+  void gather_runs(LaunchJob& J, bool tables_resident);   // every piece whole (+ the shadow's refresh)
+  void account_frame(LaunchJob& J);
+  void fence_staging();
   void issue(LaunchJob& J);    // submit thread: upload + kernel launches
   void launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq = 0);  // upload_seq: the bin launch reports it to the host
   // launch_frame's stages, in the order it takes them
@@ -527,7 +580,7 @@ class Context : public Recorder {
   Schedule schedule(const LaunchJob& J, bool direct, bool partial);
   uint32_t* launch_blur(const LaunchJob& J, int p, uint32_t* cur, int row_lo, int row_hi, bool partial);
   CompositeParams composite_params(const LaunchJob& J, int p, uint32_t* cur, int row_lo, int row_hi, bool direct, const Schedule& S) const;
-  template <typename Buf> void reserve_quiet(Buf& buf, size_t n);
+  template <typename Buf> void reserve_quiet(Buf& buf, size_t n);  // (defined below the class)
   void drain();        // wait until the submit thread is idle; rethrows what its last job threw
   void worker_main();
   hipEvent_t next_event();
@@ -545,7 +598,6 @@ class Context : public Recorder {
   Lane& lane(int i) { return i < 0 ? *merge_lane_[(size_t)staging_i_] : *lanes_[(size_t)staging_i_][(size_t)i]; }  // (-1: consolidate_pieces' lane)
   Lane& ensure_lane(int i);
   void splice_cached(const RetainedRoot& C);
-  void consolidate_pieces();
   void pick_routes();                       // begin_frame: the one-kernel blur routes (a frame alone) or the two-pass ones (frames in flight)
   void pool_slots(int slots);               // lanes 1 .. slots and their recorders, ready for a sibling group
 
@@ -603,8 +655,8 @@ class Context : public Recorder {
   std::atomic<float> launch_ms_{0.0f};
   alignas(128) LaunchJob next_; // the frame being prepared (calling thread)
   const void* tables_dev_ = nullptr;  // the device block whose tail holds the blur weight tables described by ...
-  std::vector<size_t> tables_layout_;
-  std::vector<float> tables_sig_;
+  FrameLayout tables_layout_;
+  std::vector<float> tables_sig_, tables_sig_next_;  // the filters behind those tables; ... behind the frame being prepared
 
   // recorded frame (calling thread)
   alignas(128) bool rec_diff_upload_ = false;
@@ -640,7 +692,7 @@ class Context : public Recorder {
   int surf_w_ = 0, surf_h_ = 0;
   // records, quad extensions, bin records and phase offsets of a frame live in ONE device block; the typed views point into it
   DeviceBuf<uint8_t> d_frame_;
-  DeviceBuf<uint32_t> d_mask_spill_;  // clip-stack levels beyond kMaskDepth (Context::prepare sizes it)
+  DeviceBuf<uint32_t> d_mask_spill_;  // clip-stack levels beyond kMaskDepth (Context::size_bin_buffers sizes it)
   DeviceBuf<uint2> d_lists_;
   DeviceBuf<uint32_t> d_counts_;
   DeviceBuf<int> d_order_[2];  // phase 0's bins, longest list first: read by this frame's launch / written for the next
@@ -673,12 +725,12 @@ class Context : public Recorder {
   std::vector<std::unique_ptr<Recorder>> pool_recs_;  // the pool threads' recorders (slot s records into lane s + 1)
   uint64_t frame_no_ = 0;
   HostVec<uint8_t> misc_[kStaging];   // per slot (pinned): phase table, blur weight tables
-  std::vector<uint8_t> misc_host_;    // ... as prepare builds them
+  std::vector<uint8_t> misc_host_;    // ... as build_misc builds them
   const uint8_t* misc_dev_[kStaging] = {};   // the pinned buffers' device views (hipHostGetDevicePointer costs a third of a microsecond)
   const uint8_t* misc_dev_host_[kStaging] = {};
-  // retained scenes: host copy of what the device's frame block holds (prepare: upload only what differs)
+  // retained scenes: host copy of what the device's frame block holds (patch_runs: upload only what differs; gather_runs refreshes it)
   std::vector<uint8_t> shadow_;
-  std::vector<size_t> shadow_layout_; // the offsets that block was laid out with
+  FrameLayout shadow_layout_;         // the offsets that block was laid out with
   const void* shadow_dev_ = nullptr;  // ... and where it lives
   int64_t uploaded_bytes_ = 0;        // by the last submit
   hipEvent_t staging_ev_[kStaging] = {};
@@ -711,6 +763,14 @@ class Context : public Recorder {
   std::chrono::steady_clock::time_point t_begin_frame_, t_walk_begin_;
   float host_record_ms_ = 0.0f;
 };
+
+// a device buffer the frame in submission may still use: wait for it before the block moves
+template <typename Buf> void Context::reserve_quiet(Buf& buf, size_t n) {
+  if (n <= buf.cap) return;
+  drain();
+  FDH_HIP(hipStreamSynchronize(stream_));
+  buf.reserve(n);
+}
 
 void record_host_form(DrawRec& r);  // undo the device form of a committed record's colours (fdh_record.cpp)
 void stripe_rows(int height, int world, int rank, int* y0, int* y1);

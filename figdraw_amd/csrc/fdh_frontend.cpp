@@ -1115,7 +1115,7 @@ void Context::scene_render() {
   R.roots_walked = R.roots_reused = 0;
   if (stripe_y1_ > stripe_y0_ && culling()) pending_reach_ = scene_blur_reach(view, ui_scale_);
   begin_frame((int)w, (int)h, R.clear, R.rgba);
-  rec_diff_upload_ = true;  // consecutive frames of a retained scene differ in a few records: Context::prepare uploads the difference
+  rec_diff_upload_ = true;  // consecutive frames of a retained scene differ in a few records: Context::patch_runs uploads the difference
   try {
     save_transform();
     scale(pixel_scale_, pixel_scale_);
@@ -1166,6 +1166,34 @@ void Context::scene_render() {
     throw;
   }
   end_frame();
+}
+
+// A retained root's cached records take their place in lane 0 (fdh_scene_render): a memcpy per array, the extension indices
+// moved to where the extensions landed, the list-stride count and the phase summary brought up to date.
+void Context::splice_cached(const RetainedRoot& C) {
+  Lane& L = lane(0);
+  const uint32_t r0 = (uint32_t)L.recs.n, e0 = (uint32_t)L.exts.n;
+  L.recs.append(C.recs.data(), C.recs.size());
+  L.bins.append(C.bins.data(), C.bins.size());
+  L.exts.append(C.exts.data(), C.exts.size());
+  if (pick_frame_) L.tags.append(C.tags.data(), C.tags.size());  // (scene_render splices only tagged roots into a picking frame)
+  if (!C.exts.empty())
+    for (size_t i = r0; i < L.recs.n; i++) if (L.recs[i].op_mode & F_GENERAL) L.recs[i].ext += e0;
+  L.boxes.reserve(L.bins.n);
+  for (size_t i = r0; i < L.bins.n; i++) { L.count_add(L.bins[i].box); L.boxes[i] = bin_box_of(L.bins[i].box, 6 + binbox_shift_); }
+  L.boxes.n = L.bins.n;
+  bbox_union(sum_.u, C.sum.u);
+  sum_.has_masks = sum_.has_masks || C.sum.has_masks;
+  sum_.has_atlas = sum_.has_atlas || C.sum.has_atlas;
+  sum_.has_slow = sum_.has_slow || C.sum.has_slow;
+  sum_.has_slow_atlas = sum_.has_slow_atlas || C.sum.has_slow_atlas;
+  sum_.has_rot = sum_.has_rot || C.sum.has_rot;
+  sum_.deepest = std::max(sum_.deepest, depth_now_ + C.sum.deepest);
+  for (int k = 0; k < 4; k++) sum_.frag_mode[k] += C.sum.frag_mode[k];
+  sum_.frag_ellip += C.sum.frag_ellip;
+  sum_.frag_other += C.sum.frag_other;
+  fragments_ += C.fragments;
+  if (!C.recs.empty()) link_share(r0);  // the record in front of the splice may share its distance field with the first one here
 }
 
 }  // namespace fdh

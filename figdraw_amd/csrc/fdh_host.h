@@ -8,6 +8,7 @@ namespace fdh {
 
 inline float nim_round(float x) { return x >= 0.0f ? std::floor(x + 0.5f) : -std::floor(-x + 0.5f); }  // Nim math.round
 inline float clampf(float x, float lo, float hi) { return !(x >= lo) ? lo : (x > hi ? hi : x); }  // (a NaN comes out as lo)
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }  // sub-blocks of a device block start on 256-byte boundaries
 inline uint32_t pack_color(FdhColor c) { return (uint32_t)c.r | ((uint32_t)c.g << 8) | ((uint32_t)c.b << 16) | ((uint32_t)c.a << 24); }
 
 inline Aff aff_mul(const Aff& m, const Aff& n) {

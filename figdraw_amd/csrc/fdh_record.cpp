@@ -102,6 +102,8 @@ const char* Context::record_json() {
   rec_on_ = false;
   return rec_.c_str();
 }
+void Context::rec_begin_frame(bool clear, const float rgba[4]) { FDH_REC("begin_frame").i(clear ? 1 : 0).fv(rgba, 4); }
+void Context::rec_end_frame() { FDH_REC("end_frame"); }
 void Recorder::set_aa(float aa) { { FDH_REC("set_aa_factor").f(aa); } aa_ = aa; }
 void Recorder::set_subpixel_shift(float s) { { FDH_REC("set_text_subpixel_shift").f(s); } subpixel_shift_ = s; }  // setTextSubpixelShift figbackend.nim:663-686
 bool Recorder::subpixel_enabled() const { return cx_->subpixel_enabled_; }
@@ -933,7 +935,7 @@ void Recorder::begin_mask(const float rect[4], const float rx[4], const float ry
   if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   if (mask_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginMask has already been called.");
   mask_begun_ = true;
-  mask_depth_++;  // (beyond kMaskDepth levels the compositor's stack spills to a global plane: Context::prepare)
+  mask_depth_++;  // (beyond kMaskDepth levels the compositor's stack spills to a global plane: Context::size_bin_buffers)
   const FdhColor red{255, 0, 0, 255}, zero{0, 0, 0, 0};
   const FdhColor cols[4] = {red, red, red, red};
   const float shape[2] = {0, 0};
@@ -1176,300 +1178,6 @@ void Context::split_phase(int blur) {
   next.blur = blur;
   phases_.push_back(next);
   phase_floor_ = (int)lane(0).recs.n;
-}
-
-void Context::begin_frame(int w, int h, bool clear, const float rgba[4]) {  // glcontext.nim:2080-2092, 1951-1980
-  { FDH_REC("begin_frame").i(clear ? 1 : 0).fv(rgba, 4); }
-  if (frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has already been called.");
-  if (w <= 0 || h <= 0 || w > 16384 || h > 16384) throw Error(FDH_ERR_INVALID, "beginFrame: frame size must be in 1..16384");
-  t_begin_frame_ = std::chrono::steady_clock::now();
-  for (auto& v : host_ns_) v = 0;
-  if (!host_only_) FDH_HIP(hipSetDevice(device_));
-  W_ = w;
-  H_ = h;
-  ensure_surfaces();
-  clear_ = clear;
-  if (clear) {
-    auto q = [](float v) { return (uint32_t)std::floor(clampf(v, 0.0f, 1.0f) * 255.0f + 0.5f); };
-    clear_rgba8_ = q(rgba[0]) | (q(rgba[1]) << 8) | (q(rgba[2]) << 16) | (q(rgba[3]) << 24);
-  }
-  // The records of this frame go into the next set of lanes: the set's last user was the frame kStaging frames ago, whose upload
-  // kernel has run by now (that frame's issue was waited for by the end_frame after it: the event is recorded).
-  staging_i_ = (staging_i_ + 1) % kStaging;
-  frame_no_++;
-  if (!host_only_ && staging_busy_[staging_i_]) { HostTimer t(host_ns_[1]); wait_staging(staging_i_); }
-  Lane& L0 = ensure_lane(0);
-  L0.clear();
-  L0.count_begin((w + kBin - 1) / kBin, (h + kBin - 1) / kBin);
-  binbox_shift_ = ((w + kBin - 1) / kBin > 128 || (h + kBin - 1) / kBin > 128) ? 1 : 0;
-  lane_ = &L0;
-  frame_begun_ = true;
-  mask_begun_ = false;
-  mask_depth_ = 0;
-  pick_frame_ = pick_on_;
-  tag_ = PickTag{-1, -1};
-  rect_masks_.clear();
-  open_ops_.clear();
-  outer_rect_masks_ = 0;
-  outer_open_ = false;
-  outer_union_ = BBox{0, 0, 0, 0};
-  depth_now_ = 0;
-  sum_ = PhaseSum{};
-  fragments_ = 0;
-  culled_draws_ = 0;
-  pieces_.clear();
-  n_total_ = n_ext_total_ = 0;
-  piece_open_ = false;
-  phases_.clear();
-  phases_.push_back(Phase{});
-  blurs_.clear();
-  phase_u_ = BBox{0, 0, 0, 0};
-  stride_max_ = 1;
-  phase_extra_ = 0;
-  deepest_clip_ = 0;
-  for (auto& f : frag_mode_) f = 0;
-  frag_ellip_ = frag_other_ = 0;
-  parallel_groups_ = 0;
-  rec_diff_upload_ = false;
-  open_piece();
-  pick_routes();
-  // rows a draw has to reach: the frame's, or -- under fdh_set_stripe, when the front-end has told how far the scene's blur nodes
-  // reach (render_frame: the per-call path cannot know what is still to come) -- the stripe's, widened by that reach
-  cull_y0_ = 0; cull_y1_ = H_;
-  if (stripe_y1_ > stripe_y0_ && pending_reach_ >= 0) {
-    cull_y0_ = std::max(0, std::min(H_, stripe_y0_) - pending_reach_);
-    cull_y1_ = std::min(H_, std::max(0, stripe_y1_) + pending_reach_);
-  }
-  pending_reach_ = -1;
-  t_walk_begin_ = std::chrono::steady_clock::now();
-  host_ns_[0] = std::chrono::duration_cast<std::chrono::nanoseconds>(t_walk_begin_ - t_begin_frame_).count();
-}
-
-// end_frame = prepare (this thread) + issue (the context's submit thread).
-//   prepare  lays the frame block out and lists the runs the upload kernel gathers; everything per record was produced while the
-//            frame was recorded (commit_bins).  It runs on the CALLING thread.
-//   issue    launches the upload kernel and the frame's kernels (~20 us of HIP runtime calls) from the submit thread, so the
-//            caller is already walking the next frame's tree.  FDH_CREATE_SYNC_SUBMIT contexts run it inline.
-void Context::end_frame() {  // glcontext.nim:1982-1989
-  { FDH_REC("end_frame"); }
-  if (!frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame was not called first.");
-  if (mask_depth_ != 0) throw Error(FDH_ERR_INVALID, "Not all masks have been popped.");
-  if (!rect_masks_.empty()) throw Error(FDH_ERR_INVALID, "Not all rect masks have been popped.");
-  frame_begun_ = false;
-  const auto t0 = std::chrono::steady_clock::now();
-  host_ns_[2] = std::chrono::duration_cast<std::chrono::nanoseconds>(t0 - t_walk_begin_).count();
-  close_phase();
-  close_piece();
-  culled_total_ = culled_draws_;
-  const auto t1 = std::chrono::steady_clock::now();
-  host_ns_[3] = std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
-  // (without what begin_frame waited for the GPU -- the lane set's previous upload: back-pressure, not work)
-  host_record_ms_ = std::chrono::duration<float, std::milli>(t1 - t_begin_frame_).count() - (float)host_ns_[1] * 1e-6f;
-  // a list entry carries the draw index in 25 bits beside its path code and flags (k_bin_draws, LE_INDEX)
-  if (n_total_ >= LE_INDEX) throw Error(FDH_ERR_INVALID, "more than 33 554 430 draw records in one frame");
-  {  // picking: the frame's tag table, in painter's order, goes with the frame (a record-only context keeps it as its last frame)
-    LaunchJob& T = host_only_ ? job_ : next_;
-    T.pick = pick_frame_;
-    T.pick_depth = deepest_clip_;
-    T.pick_tags.clear();
-    if (pick_frame_) {
-      T.pick_tags.resize(n_total_);
-      size_t o = 0;
-      for (const Piece& p : pieces_) {
-        if (p.n) std::memcpy(static_cast<void*>(T.pick_tags.data() + o), lane(p.lane).tags.p + p.first, p.n * sizeof(PickTag));
-        o += p.n;
-      }
-    }
-  }
-  if (host_only_) return;
-  // prepare() notes what the device block will hold once this frame's upload has run (blur tables, the retained path's shadow):
-  // if the frame is dropped before it is handed over -- prepare or the wait for the previous frame's launches throws, or an
-  // inline issue fails -- those notes are void (a later frame would skip uploads the device never received)
-  try {
-    { HostTimer t(host_ns_[4]); prepare(next_); }
-    { HostTimer t(host_ns_[6]); drain(); }  // the previous frame's launches (normally long issued: they ran while this frame was being recorded)
-    std::swap(job_, next_);
-    have_frame_ = true;
-    if (!worker_.joinable()) { issue(job_); return; }
-  } catch (...) {
-    tables_dev_ = nullptr; shadow_dev_ = nullptr; have_frame_ = false;
-    throw;
-  }
-  {
-    std::lock_guard<std::mutex> lk(mu_);
-    pending_.store(true, std::memory_order_release);
-  }
-  cv_job_.notify_one();
-}
-
-// FNV-1a over the last frame's records in painter's order, in the form the calls produced them (four vertex colours, extension
-// indices counted over the whole frame), their bounds, extensions and the phase table: two frames with equal digests hand the
-// kernels identical input, however many threads recorded them.
-uint64_t Context::record_digest() {
-  drain();
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void* p, size_t n) { const uint8_t* b = static_cast<const uint8_t*>(p); for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } };
-  const uint64_t n = n_total_;
-  mix(&n, sizeof n);
-  uint32_t ext_base = 0;
-  for (const Piece& p : pieces_) {
-    const Lane& L = lane(p.lane);
-    for (uint32_t i = 0; i < p.n; i++) {
-      DrawRec r = L.recs[p.first + i];
-      record_host_form(r);
-      if (r.op_mode & F_GENERAL) r.ext = r.ext - p.ext_first + ext_base;
-      mix(&r, sizeof r);
-    }
-    ext_base += p.n_ext;
-  }
-  for (const Piece& p : pieces_) { const Lane& L = lane(p.lane); for (uint32_t i = 0; i < p.n; i++) mix(&L.bins[p.first + i].box, sizeof(BBox)); }
-  for (const Piece& p : pieces_) { const Lane& L = lane(p.lane); for (uint32_t i = 0; i < p.n_ext; i++) mix(&L.exts[p.ext_first + i], sizeof(QuadExt)); }
-  for (const Phase& ph : phases_) { mix(&ph.first, sizeof ph.first); mix(&ph.count, sizeof ph.count); mix(&ph.blur, sizeof ph.blur); }
-  return h;
-}
-
-// Fault hunting (fdh_debug_verify_upload): the device's frame block -- what k_upload_frame gathered for the frame last submitted --
-// read back and compared with the lanes the records were made in (ordinary host memory, untouched until the staging set comes
-// round again).  out[0..2] = bytes that differ in records / bin records / extensions, out[3] = bytes compared; out[4..9] describe the
-// first difference: array (0, 1, 2), byte offset in the device array, the piece's lane, device dword, host dword, dwords of the
-// device run that are zero; out[10] = pieces, out[11] = records.
-void Context::debug_verify_upload(uint32_t out[24]) {
-  need_device("debug_verify_upload");
-  drain();
-  FDH_HIP(hipSetDevice(device_));
-  FDH_HIP(hipStreamSynchronize(stream_));
-  for (int i = 0; i < 24; i++) out[i] = 0;
-  const LaunchJob& J = job_;
-  out[10] = (uint32_t)pieces_.size(); out[11] = n_total_;
-  if (!J.dv.recs || n_total_ == 0) return;
-  std::vector<DrawRec> recs(n_total_);
-  std::vector<BinRec> bins(n_total_);
-  std::vector<QuadExt> exts(n_ext_total_);
-  FDH_HIP(hipMemcpy(recs.data(), J.dv.recs, recs.size() * sizeof(DrawRec), hipMemcpyDeviceToHost));
-  FDH_HIP(hipMemcpy(bins.data(), J.dv.binrecs, bins.size() * sizeof(BinRec), hipMemcpyDeviceToHost));
-  if (!exts.empty()) FDH_HIP(hipMemcpy(exts.data(), J.dv.exts, exts.size() * sizeof(QuadExt), hipMemcpyDeviceToHost));
-  bool first = true;
-  auto cmp = [&](int array, int lane_no, const void* dev, const void* host, size_t bytes, size_t dev_off) {
-    const uint32_t* d = static_cast<const uint32_t*>(dev);
-    const uint32_t* h = static_cast<const uint32_t*>(host);
-    out[3] += (uint32_t)bytes;
-    for (size_t i = 0; i < bytes / 4; i++) {
-      if (d[i] == h[i]) continue;
-      out[array] += 4;
-      if (first) {
-        first = false;
-        out[4] = (uint32_t)array; out[5] = (uint32_t)(dev_off + 4 * i); out[6] = (uint32_t)lane_no; out[7] = d[i]; out[8] = h[i];
-        uint32_t z = 0;
-        for (size_t k = 0; k < bytes / 4; k++) z += d[k] == 0u;
-        out[9] = z;
-      }
-    }
-  };
-  uint32_t r0 = 0, e0 = 0;
-  for (const Piece& p : pieces_) {
-    const Lane& L = lane(p.lane);
-    std::vector<DrawRec> want(L.recs.p + p.first, L.recs.p + p.first + p.n);
-    for (DrawRec& r : want) if (r.op_mode & F_GENERAL) r.ext = r.ext - p.ext_first + e0;
-    cmp(0, p.lane, recs.data() + r0, want.data(), (size_t)p.n * sizeof(DrawRec), (size_t)r0 * sizeof(DrawRec));
-    cmp(1, p.lane, bins.data() + r0, L.bins.p + p.first, (size_t)p.n * sizeof(BinRec), (size_t)r0 * sizeof(BinRec));
-    if (p.n_ext) cmp(2, p.lane, exts.data() + e0, L.exts.p + p.ext_first, (size_t)p.n_ext * sizeof(QuadExt), (size_t)e0 * sizeof(QuadExt));
-    r0 += p.n; e0 += p.n_ext;
-  }
-  // the block from the chunk boxes on (chunk boxes, phase table, blur weight tables as far as this frame staged them): out[12] bytes
-  // that differ, out[13] first offset (in that block), out[14] device dword, out[15] host dword, out[16] bytes compared
-  {
-    const size_t o_misc = (size_t)(reinterpret_cast<const uint8_t*>(J.dv.chunkbox) - d_frame_.ptr);
-    std::vector<uint8_t> dev(misc_host_.size());
-    if (!dev.empty()) FDH_HIP(hipMemcpy(dev.data(), d_frame_.ptr + o_misc, dev.size(), hipMemcpyDeviceToHost));
-    out[16] = (uint32_t)dev.size();
-    for (size_t i = 0; i + 4 <= dev.size(); i += 4) {
-      uint32_t a, b;
-      std::memcpy(&a, dev.data() + i, 4); std::memcpy(&b, misc_host_.data() + i, 4);
-      if (a == b) continue;
-      if (!out[12]) { out[13] = (uint32_t)i; out[14] = a; out[15] = b; }
-      out[12] += 4;
-    }
-  }
-  // the bin boxes the upload kernel derives from the bin records: out[17] boxes that differ from the host's, out[18] first index,
-  // out[19] device value, out[20] host value
-  {
-    std::vector<uint32_t> box(n_total_);
-    FDH_HIP(hipMemcpy(box.data(), J.dv.binbox, box.size() * 4, hipMemcpyDeviceToHost));
-    uint32_t g0 = 0;
-    for (const Piece& p : pieces_) {
-      const Lane& L = lane(p.lane);
-      for (uint32_t i = 0; i < p.n; i++, g0++) {
-        if (g0 == 0 && out[1]) continue;  // (a folded clear emptied record 0's box on the device side)
-        if (box[g0] == L.boxes.p[p.first + i]) continue;
-        if (!out[17]) { out[18] = g0; out[19] = box[g0]; out[20] = L.boxes.p[p.first + i]; }
-        out[17]++;
-      }
-    }
-  }
-}
-
-// Fault hunting (fdh_debug_bin_digest): what the bin kernel left for the frame last submitted -- per phase and bin the count and the
-// list entries it covers.  out[0] = FNV-1a over them, out[1] = sum of the counts, out[2] = bins with count 0, out[3] = list entries
-// whose first word is 0, out[4] = bins whose count exceeds the list stride (garbage).
-void Context::debug_bin_digest(uint64_t out[8]) {
-  need_device("debug_bin_digest");
-  drain();
-  FDH_HIP(hipSetDevice(device_));
-  FDH_HIP(hipStreamSynchronize(stream_));
-  for (int i = 0; i < 8; i++) out[i] = 0;
-  const LaunchJob& J = job_;
-  const size_t nb = (size_t)J.bins_x * J.bins_y, np = J.phases.size(), stride = (size_t)J.list_stride;
-  if (!nb || !np || !J.counts || !J.lists) return;
-  std::vector<uint32_t> counts(np * nb);
-  std::vector<uint2> lists(np * nb * stride);
-  FDH_HIP(hipMemcpy(counts.data(), J.counts, counts.size() * 4, hipMemcpyDeviceToHost));
-  FDH_HIP(hipMemcpy(lists.data(), J.lists, lists.size() * sizeof(uint2), hipMemcpyDeviceToHost));
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](uint32_t v) { for (int k = 0; k < 4; k++) { h ^= (v >> (8 * k)) & 255u; h *= 1099511628211ull; } };
-  for (size_t p = 0; p < np; p++) {
-    const Phase& ph = J.phases[p];
-    const bool whole = p == 0;
-    for (int by = 0; by < J.bins_y; by++)
-      for (int bx = 0; bx < J.bins_x; bx++) {
-        if (!whole && (bx < ph.bin_x0 || bx >= ph.bin_x1 || by < ph.bin_y0 || by >= ph.bin_y1)) continue;  // (bins the phase's launches never look at)
-        const size_t b = p * nb + (size_t)by * J.bins_x + bx;
-        const uint32_t c = counts[b];
-        mix(c);
-        out[1] += c;
-        if (c == 0) out[2]++;
-        if (c > stride) { out[4]++; continue; }
-        for (uint32_t e = 0; e < c; e++) { const uint2 v = lists[b * stride + e]; mix(v.x); mix(v.y); if (v.x == 0) out[3]++; }
-      }
-  }
-  out[0] = h;
-}
-
-// A retained root's cached records take their place in lane 0 (fdh_scene_render): a memcpy per array, the extension indices
-// moved to where the extensions landed, the list-stride count and the phase summary brought up to date.
-void Context::splice_cached(const RetainedRoot& C) {
-  Lane& L = lane(0);
-  const uint32_t r0 = (uint32_t)L.recs.n, e0 = (uint32_t)L.exts.n;
-  L.recs.append(C.recs.data(), C.recs.size());
-  L.bins.append(C.bins.data(), C.bins.size());
-  L.exts.append(C.exts.data(), C.exts.size());
-  if (pick_frame_) L.tags.append(C.tags.data(), C.tags.size());  // (scene_render splices only tagged roots into a picking frame)
-  if (!C.exts.empty())
-    for (size_t i = r0; i < L.recs.n; i++) if (L.recs[i].op_mode & F_GENERAL) L.recs[i].ext += e0;
-  L.boxes.reserve(L.bins.n);
-  for (size_t i = r0; i < L.bins.n; i++) { L.count_add(L.bins[i].box); L.boxes[i] = bin_box_of(L.bins[i].box, 6 + binbox_shift_); }
-  L.boxes.n = L.bins.n;
-  bbox_union(sum_.u, C.sum.u);
-  sum_.has_masks = sum_.has_masks || C.sum.has_masks;
-  sum_.has_atlas = sum_.has_atlas || C.sum.has_atlas;
-  sum_.has_slow = sum_.has_slow || C.sum.has_slow;
-  sum_.has_slow_atlas = sum_.has_slow_atlas || C.sum.has_slow_atlas;
-  sum_.has_rot = sum_.has_rot || C.sum.has_rot;
-  sum_.deepest = std::max(sum_.deepest, depth_now_ + C.sum.deepest);
-  for (int k = 0; k < 4; k++) sum_.frag_mode[k] += C.sum.frag_mode[k];
-  sum_.frag_ellip += C.sum.frag_ellip;
-  sum_.frag_other += C.sum.frag_other;
-  fragments_ += C.fragments;
-  if (!C.recs.empty()) link_share(r0);  // the record in front of the splice may share its distance field with the first one here
 }
 
 }  // namespace fdh

@@ -668,7 +668,7 @@ def random_scene(seed: int, w: float, h: float, n: int = 40, clips: bool = True,
 
 # Hostile content for the backdrop blur (glsl/blur.frag:11-32): the product's matrix-pipe passes multiply each tap as one f16, so their
 # error is largest where neighbouring texels are uncorrelated.  Opaque white noise and a 0 / 255 checkerboard of 1-pixel cells, at a size
-# that takes the matrix-pipe kernels without being forced to (>= 384 K pixels, fdh_context.cpp Context::prepare).  The sources are rebuilt
+# that takes the matrix-pipe kernels without being forced to (>= 384 K pixels, fdh_prepare.cpp Context::choose_fused_blurs).  The sources are rebuilt
 # from this recipe; tests/golden/ss_blur_big_<kind>_r<radius>.png holds what the reference's blur.frag makes of them on SwiftShader.
 # Powers of two on purpose: SwiftShader samples on a 16-bit normalised coordinate grid (oracle.texcoord_model), on which the texel centres
 # of a 1024 x 512 surface lie exactly.  At 896 x 448 they do not, and with radius 64 -- tap step 8 px: every tap ON a texel centre, the

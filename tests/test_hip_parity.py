@@ -1458,7 +1458,7 @@ def test_draw_image_adj_and_the_lcd_flag_through_the_seam():
 
 def test_clear_folding_changes_no_pixel():
     """A cleared frame whose first draw is one colour at full coverage over the whole frame starts, in effect, from
-    blend(clear, colour): Context::prepare folds that draw into the clear colour (FDH_FOLD_CLEAR=0 turns it off; read once per
+    blend(clear, colour): Context::fold_clear folds that draw into the clear colour (FDH_FOLD_CLEAR=0 turns it off; read once per
     process, hence the child processes).  Same frames bit for bit -- translucent and opaque backgrounds over several clear colours,
     and backgrounds that must NOT be folded (rounded corners, a gradient, smaller than the frame, a clip opened first)."""
     import os
