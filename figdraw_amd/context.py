@@ -157,6 +157,12 @@ def load():
         L.fdh_damage_bins.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.fdh_damage_changed_bins.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.fdh_damage_closure.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
+    # damage readback (include/figdraw_hip_readback.h; likewise)
+    if hasattr(L, "fdh_set_damage_readback"):
+        L.fdh_set_damage_readback.argtypes = [vp, C.c_int]
+        L.fdh_read_damage.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.fdh_read_damage_into.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.fdh_apply_damage.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int]
     # picking (include/figdraw_hip_pick.h; likewise absent from older libraries)
     if hasattr(L, "fdh_set_pick"):
         L.fdh_set_pick.argtypes = [vp, C.c_int]
@@ -570,6 +576,56 @@ class HipContext:
         if rc != 0:
             raise FigdrawHipError(rc, L.fdh_last_error().decode())
         return out.astype(bool)
+
+    # ---- damage readback (include/figdraw_hip_readback.h)
+    TILE_PX, TILE_PITCH, TILE_BYTES = 64, 256, 16384  # FDH_TILE_*
+
+    def set_damage_readback(self, on: bool):
+        """keep the set of bins composited since the last read_damage / read_damage_into, so that a read moves only those to the host.
+        Turning it on makes every bin pending.  Refused on record-only contexts and under set_stripe."""
+        self._ck(self.L.fdh_set_damage_readback(self.h, 1 if on else 0))
+
+    def read_damage(self):
+        """the pending bins of the last frame -> (tiles int32 (n, 4): x, y, w, h in row-major bin order; pixels uint8 (n, 64, 64, 4):
+        tile i's w x h pixels at [i, :h, :w], zeros beyond; full: every bin of the grid is among them).  The arrays are copies: the
+        library's buffer is reused by the next read.  Empties the pending set."""
+        t, p = C.c_void_p(), C.c_void_p()
+        n, full = C.c_int(), C.c_int()
+        self._ck(self.L.fdh_read_damage(self.h, C.byref(t), C.byref(p), C.byref(n), None, None, C.byref(full)))
+        k = n.value
+        if k == 0:
+            return np.zeros((0, 4), np.int32), np.zeros((0, self.TILE_PX, self.TILE_PX, 4), np.uint8), bool(full.value)
+        tiles = np.ctypeslib.as_array(C.cast(t, C.POINTER(C.c_int32)), shape=(k, 4)).copy()
+        pixels = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(k, self.TILE_PX, self.TILE_PX, 4)).copy()
+        return tiles, pixels, bool(full.value)
+
+    def read_damage_into(self, image: np.ndarray) -> int:
+        """read_damage applied to `image`, the application's mirror of the frame: uint8 (H, W, 4), rows contiguous (any row stride).
+        Returns the number of tiles copied.  An image of another size than the last frame is refused and nothing is consumed."""
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 4 or image.strides[2] != 1 or image.strides[1] != 4:
+            raise ValueError("read_damage_into: the image must be uint8 (H, W, 4) with contiguous rows")
+        if not image.flags.writeable:
+            raise ValueError("read_damage_into: the image is read-only")
+        n = C.c_int()
+        self._ck(self.L.fdh_read_damage_into(self.h, image.ctypes.data, image.strides[0], image.shape[1], image.shape[0], C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def apply_damage(image: np.ndarray, tiles, pixels) -> None:
+        """host only (no context, no GPU): copy the tiles read_damage returned into `image`, uint8 (H, W, 4) with contiguous rows"""
+        L = load()
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 4 or image.strides[2] != 1 or image.strides[1] != 4:
+            raise ValueError("apply_damage: the image must be uint8 (H, W, 4) with contiguous rows")
+        if not image.flags.writeable:
+            raise ValueError("apply_damage: the image is read-only")
+        t = np.ascontiguousarray(np.asarray(tiles, dtype=np.int32).reshape(-1, 4))
+        px = np.ascontiguousarray(np.asarray(pixels, dtype=np.uint8))
+        if px.size != len(t) * HipContext.TILE_BYTES:
+            raise ValueError("apply_damage: pixels must hold 16384 bytes per tile")
+        rc = L.fdh_apply_damage(image.ctypes.data, image.strides[0], image.shape[1], image.shape[0], t.ctypes.data if len(t) else None,
+                                px.ctypes.data if len(t) else None, len(t))
+        if rc != 0:
+            raise FigdrawHipError(rc, L.fdh_last_error().decode())
 
     # ---- picking (include/figdraw_hip_pick.h)
     PICK_SHADOWS = 1  # FDH_PICK_SHADOWS

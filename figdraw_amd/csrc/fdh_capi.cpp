@@ -5,6 +5,7 @@
 #include "fdh_context.h"
 #include "../../include/figdraw_hip_damage.h"
 #include "../../include/figdraw_hip_pick.h"
+#include "../../include/figdraw_hip_readback.h"
 
 using fdh::Context;
 
@@ -310,6 +311,18 @@ int fdh_damage_changed_bins(FdhContext* c, uint8_t* mask, int cap, int* bins_x, 
 }
 int fdh_damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out) {
   return guard([&] { fdh::damage_closure(changed, bins_x, bins_y, rects, radii, n_nodes, out); });
+}
+// damage readback (include/figdraw_hip_readback.h)
+static_assert(sizeof(FdhDamageTile) == 16 && FDH_TILE_PITCH == FDH_TILE_PX * 4 && FDH_TILE_BYTES == FDH_TILE_PX * FDH_TILE_PITCH, "a tile is 64 rows of 256 bytes");
+int fdh_set_damage_readback(FdhContext* c, int on) { return guard([&] { C(c)->set_damage_readback(on != 0); }); }
+int fdh_read_damage(FdhContext* c, const FdhDamageTile** tiles, const uint8_t** pixels, int* n_tiles, int* frame_w, int* frame_h, int* full) {
+  return guard([&] { C(c)->read_damage(tiles, pixels, n_tiles, frame_w, frame_h, full); });
+}
+int fdh_read_damage_into(FdhContext* c, uint8_t* image_rgba8, int64_t pitch_bytes, int w, int h, int* n_tiles) {
+  return guard([&] { C(c)->read_damage_into(image_rgba8, pitch_bytes, w, h, n_tiles); });
+}
+int fdh_apply_damage(uint8_t* image_rgba8, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles) {
+  return guard([&] { fdh::apply_damage(image_rgba8, pitch_bytes, w, h, tiles, pixels, n_tiles); });
 }
 int fdh_set_cull(FdhContext* c, int mode) { return guard([&] { C(c)->set_cull(mode); }); }
 int fdh_debug_host_times(FdhContext* c, int64_t out_ns[12]) {

@@ -92,6 +92,8 @@ void Context::release_device_state() {
   if (dbg_snap_) (void)hipFree(dbg_snap_);
   d_frame_.release(); d_lists_.release(); d_counts_.release(); d_order_[0].release(); d_order_[1].release();
   d_dmg_sig_.release(); d_dmg_changed_.release(); d_dmg_mask_.release(); d_dmg_run_.release(); d_dmg_list_.release(); d_dmg_count_.release(); d_dmg_keep_.release();
+  d_rb_stamp_.release(); release_readback();
+  if (rb_count_host_) (void)hipHostFree((void*)rb_count_host_);
   glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); d_mask_spill_.release();
   d_pick_.release(); d_pick_spill_.release(); h_pick_.release();
   for (auto& set : lanes_) set.clear();  // (pinned arrays: freed while the device is still this thread's)
@@ -473,7 +475,11 @@ bool Context::launch_damage(const LaunchJob& J, const BinParams& B) {
   // rendered without tracking leaves its pixels, not the signatures' frame, in the surface
   const bool was_valid = dmg_valid_;
   dmg_valid_ = false;
-  if (!tracked) { dmg_last_ = false; return false; }
+  if (!tracked) {
+    dmg_last_ = false;
+    if (readback_on_) rb_all_ = true;  // (every bin is composited: no mask to accumulate, and no launch)
+    return false;
+  }
   const bool full = J.damage_force || !damage_sig_whole(J) || !was_valid || dmg_key_ != J.damage_key;
   const bool keep = !full && [&] { for (const BlurJob& j : J.blurs) if (j.fuse_draw >= 0) return true; return false; }();
   if (d_dmg_sig_.cap < (size_t)nb || d_dmg_count_.cap == 0 || (keep && d_dmg_keep_.cap < (size_t)J.W * J.H)) {
@@ -511,6 +517,12 @@ bool Context::launch_damage(const LaunchJob& J, const BinParams& B) {
   }
   span_begin(kSpanBin); launch_damage_sign(stream_, S); span_end();
   span_begin(kSpanBin); launch_damage_resolve(stream_, R); span_end();
+  if (readback_on_) {
+    // damage readback: the mask joins the pending set -- unless everything is pending already, or the stamps are those of another frame
+    // size (read_damage lays them out anew)
+    if (rb_all_ || rb_w_ != J.W || rb_h_ != J.H || d_rb_stamp_.cap < (size_t)nb) rb_all_ = true;
+    else { span_begin(kSpanBin); launch_damage_accumulate(stream_, d_dmg_mask_.ptr, d_rb_stamp_.ptr, rb_epoch_, nb, const_cast<uint32_t*>(rb_count_host_)); span_end(); }
+  }
   dmg_bx_ = J.bins_x; dmg_by_ = J.bins_y;
   dmg_last_ = true;
   return !full;
@@ -805,6 +817,131 @@ void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* r
   for (size_t b = 0; b < nb; b++) m[b] = changed[b] ? 1 : 0;
   damage_close(m.data(), bins_x, reg.data(), n_nodes, run.data(), DamageHostTeam());
   if (nb) std::memcpy(out, m.data(), nb);
+}
+
+// ------------------------------------------------------------------ damage readback (include/figdraw_hip_readback.h)
+void Context::release_readback() {
+  h_rb_pixels_.release(); h_rb_tiles_.release();
+  h_rb_pixels_dev_ = nullptr; h_rb_tiles_dev_ = nullptr;
+}
+void Context::set_damage_readback(bool on) {
+  if (on && host_only_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_readback: a record-only context composites nothing");
+  if (host_only_) return;
+  drain();
+  if (on && stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_readback: not under fdh_set_stripe");
+  FDH_HIP(hipSetDevice(device_));
+  if (on && !readback_on_) {
+    if (!rb_count_host_) {
+      FDH_HIP(hipHostMalloc((void**)&rb_count_host_, 64, hipHostMallocDefault));
+      rb_count_host_[0] = rb_count_host_[1] = 0;
+    }
+    rb_all_ = true;  // what the application holds is unknown: the first read brings every bin
+  }
+  if (!on && readback_on_) {
+    FDH_HIP(hipStreamSynchronize(stream_));
+    release_readback();
+  }
+  readback_on_ = on;
+}
+// What a read starts with: the last frame is complete, and this many of its bins are pending (`all`: every one, whatever the stamps say)
+int Context::readback_pending(const char* who, bool* all) {
+  need_device(who);
+  drain();
+  if (!readback_on_) throw Error(FDH_ERR_INVALID, std::string(who) + ": damage readback is off (fdh_set_damage_readback)");
+  if (!have_frame_ || !fb_) throw Error(FDH_ERR_INVALID, std::string(who) + ": no frame has been submitted");
+  FDH_HIP(hipSetDevice(device_));
+  FDH_HIP(hipStreamSynchronize(stream_));
+  const int nb = job_.bins_x * job_.bins_y;
+  *all = rb_all_ || rb_w_ != job_.W || rb_h_ != job_.H;
+  const int n = *all ? nb : (int)rb_count_host_[0];
+  if (n < 0 || n > nb) throw Error(FDH_ERR_HIP, std::string(who) + ": the pending count is out of range");
+  return n;
+}
+// ... and ends with (the stream is idle): the set is empty, the stamps are laid out for the last frame's grid
+void Context::readback_consumed() {
+  const size_t nb = (size_t)job_.bins_x * job_.bins_y;
+  // the next epoch's stamp is on no bin; fresh stamps, or an epoch that wrapped, start over (epochs start at 1)
+  if (d_rb_stamp_.cap < nb || rb_epoch_ + 1 == 0) {
+    d_rb_stamp_.reserve(nb);
+    FDH_HIP(hipMemset(d_rb_stamp_.ptr, 0, d_rb_stamp_.cap * sizeof(uint32_t)));
+    rb_epoch_ = 0;
+  }
+  rb_epoch_++;
+  rb_all_ = false; rb_w_ = job_.W; rb_h_ = job_.H;
+  rb_count_host_[0] = 0;
+}
+void Context::read_damage(const FdhDamageTile** tiles, const uint8_t** pixels, int* n_tiles, int* frame_w, int* frame_h, int* full) {
+  bool all = false;
+  const int n = readback_pending("fdh_read_damage", &all);
+  const int W = job_.W, H = job_.H, gx = job_.bins_x, gy = job_.bins_y, nb = gx * gy;
+  if (n > 0) {
+    const size_t need = (size_t)nb * FDH_TILE_BYTES;
+    if (h_rb_pixels_.cap < need) {  // the whole grid, exactly (PinnedBuf::reserve doubles: 33.4 MB would become 64)
+      release_readback();
+      FDH_HIP(hipHostMalloc((void**)&h_rb_pixels_.ptr, need, hipHostMallocDefault));
+      h_rb_pixels_.cap = need;
+      h_rb_tiles_.reserve((size_t)nb);
+      FDH_HIP(hipHostGetDevicePointer((void**)&h_rb_pixels_dev_, h_rb_pixels_.ptr, 0));
+      FDH_HIP(hipHostGetDevicePointer((void**)&h_rb_tiles_dev_, h_rb_tiles_.ptr, 0));
+    }
+    DamagePackParams P;
+    P.surf = fb_; P.stamp = d_rb_stamp_.ptr;  // (`all`: the stamps are not read, and may not exist yet)
+    P.pixels = h_rb_pixels_dev_;
+    P.tiles = reinterpret_cast<int4*>(h_rb_tiles_dev_);
+    P.n_tiles = const_cast<uint32_t*>(rb_count_host_) + 1;
+    P.epoch = rb_epoch_; P.W = W; P.H = H; P.bins_x = gx; P.bins_y = gy; P.all = all ? 1 : 0;
+    rb_count_host_[1] = 0xFFFFFFFFu;
+    launch_damage_pack(stream_, P);
+    FDH_HIP(hipGetLastError());
+    FDH_HIP(hipStreamSynchronize(stream_));
+    if (rb_count_host_[1] != (uint32_t)n) throw Error(FDH_ERR_HIP, "fdh_read_damage: the pack's tile count differs from the pending count");
+    readback_consumed();
+  }
+  if (tiles) *tiles = h_rb_tiles_.ptr;
+  if (pixels) *pixels = h_rb_pixels_.ptr;
+  if (n_tiles) *n_tiles = n;
+  if (frame_w) *frame_w = W;
+  if (frame_h) *frame_h = H;
+  if (full) *full = (nb > 0 && n == nb) ? 1 : 0;
+}
+// Tiles cross the link at no more bytes than they hold, but reach the mirror through a second pass on the CPU (fdh_apply_damage out of
+// page-locked memory: ~0.7 - 1 us a tile), which a whole-frame copy into the caller's memory does not pay (~0.3 us a bin).  From
+// kReadbackWholeNum / kReadbackWholeDen of the grid on, the whole frame is the cheaper way to the same mirror
+// (profiles/damage_readback.txt: the crossover sits at 0.26 - 0.36 of the grid at 4K and 1080p).
+constexpr int kReadbackWholeNum = 3, kReadbackWholeDen = 10;
+void Context::read_damage_into(uint8_t* image, int64_t pitch_bytes, int w, int h, int* n_tiles) {
+  bool all = false;
+  const int n = readback_pending("fdh_read_damage_into", &all);
+  if (!image) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: null image");
+  if (w != job_.W || h != job_.H) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: the image is not the size of the last frame");
+  if (pitch_bytes < (int64_t)4 * w) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: the pitch is shorter than a row");
+  const int nb = job_.bins_x * job_.bins_y;
+  if (n > 0 && (int64_t)n * kReadbackWholeDen >= (int64_t)nb * kReadbackWholeNum) {
+    FDH_HIP(hipMemcpy2D(image, (size_t)pitch_bytes, fb_, (size_t)w * 4, (size_t)w * 4, (size_t)h, hipMemcpyDeviceToHost));
+    readback_consumed();
+  } else {
+    const FdhDamageTile* t = nullptr;
+    const uint8_t* px = nullptr;
+    read_damage(&t, &px, nullptr, nullptr, nullptr, nullptr);  // (the same n: nothing was submitted in between)
+    apply_damage(image, pitch_bytes, w, h, t, px, n);
+  }
+  if (n_tiles) *n_tiles = n;
+}
+void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles) {
+  if (n_tiles < 0) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: negative tile count");
+  if (w < 0 || h < 0 || pitch_bytes < (int64_t)4 * w) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: the pitch is shorter than a row");
+  if (n_tiles == 0) return;
+  if (!image || !tiles || !pixels) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: null image, tiles or pixels");
+  for (int i = 0; i < n_tiles; i++) {  // every tile is checked before any byte is written
+    const FdhDamageTile& t = tiles[i];
+    if (t.w < 1 || t.w > FDH_TILE_PX || t.h < 1 || t.h > FDH_TILE_PX || t.x < 0 || t.y < 0 || (int64_t)t.x + t.w > w || (int64_t)t.y + t.h > h)
+      throw Error(FDH_ERR_INVALID, "fdh_apply_damage: tile " + std::to_string(i) + " is not a bin inside the image");
+  }
+  for (int i = 0; i < n_tiles; i++) {
+    const FdhDamageTile& t = tiles[i];
+    const uint8_t* src = pixels + (size_t)i * FDH_TILE_BYTES;
+    for (int r = 0; r < t.h; r++) std::memcpy(image + (int64_t)(t.y + r) * pitch_bytes + (int64_t)4 * t.x, src + (size_t)r * FDH_TILE_PITCH, (size_t)4 * t.w);
+  }
 }
 
 void Context::frame_device_ptr(void** p, int* w, int* h, int64_t* pitch_bytes) {

@@ -21,6 +21,7 @@
 
 #include "../../include/figdraw_hip.h"
 #include "../../include/figdraw_hip_pick.h"
+#include "../../include/figdraw_hip_readback.h"
 #include "fdh_kernels.h"
 
 namespace fdh {
@@ -493,11 +494,16 @@ class Context : public Recorder {
   void set_stripe(int y0, int y1) {
     drain();
     if (damage_on_ && y1 > y0) throw Error(FDH_ERR_INVALID, "fdh_set_stripe: damage tracking is on (fdh_set_damage_tracking: not under row stripes)");
+    if (readback_on_ && y1 > y0) throw Error(FDH_ERR_INVALID, "fdh_set_stripe: damage readback is on (fdh_set_damage_readback: not under row stripes)");
     stripe_y0_ = y0; stripe_y1_ = y1;
   }
   // damage tracking (include/figdraw_hip_damage.h)
   void set_damage_tracking(bool on);
   void damage_bins(uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged, bool changed_only);
+  // damage readback (include/figdraw_hip_readback.h)
+  void set_damage_readback(bool on);
+  void read_damage(const FdhDamageTile** tiles, const uint8_t** pixels, int* n_tiles, int* frame_w, int* frame_h, int* full);
+  void read_damage_into(uint8_t* image, int64_t pitch_bytes, int w, int h, int* n_tiles);
   // picking (include/figdraw_hip_pick.h; fdh_pick.cpp)
   void set_pick(bool on) { pick_on_ = on; }
   void set_pick_tag(int32_t z, int32_t id) { tag_ = PickTag{z, id}; }
@@ -712,6 +718,22 @@ class Context : public Recorder {
   DeviceBuf<uint8_t> d_dmg_changed_, d_dmg_mask_, d_dmg_run_;
   DeviceBuf<int> d_dmg_list_;
   DeviceBuf<uint32_t> d_dmg_count_, d_dmg_keep_;
+  // damage readback (include/figdraw_hip_readback.h).  rb_all_: every bin is pending whatever the stamps say -- written by whoever
+  // launches a frame (launch_damage: the submit thread, or replay's caller after a drain), read by read_damage after drain().  The
+  // stamps d_rb_stamp_ describe a frame of rb_w_ x rb_h_ pixels; rb_epoch_ is the stamp of a pending bin (fdh_damage.h).
+  bool readback_on_ = false;  // (calling thread: fdh_set_damage_readback)
+  bool rb_all_ = true;
+  uint32_t rb_epoch_ = 1;
+  int rb_w_ = 0, rb_h_ = 0;
+  DeviceBuf<uint32_t> d_rb_stamp_;
+  PinnedBuf<uint8_t> h_rb_pixels_;          // [tile][64][256]: what fdh_read_damage returns
+  PinnedBuf<FdhDamageTile> h_rb_tiles_;
+  uint8_t* h_rb_pixels_dev_ = nullptr;      // their device views
+  FdhDamageTile* h_rb_tiles_dev_ = nullptr;
+  volatile uint32_t* rb_count_host_ = nullptr;  // pinned, 2 words: pending bins after the last k_damage_accumulate; tiles of the last k_damage_pack
+  void release_readback();
+  int readback_pending(const char* who, bool* all);
+  void readback_consumed();
   int order_read_ = 0, order_nb_ = 0;
   bool order_valid_ = false;
   // kStaging sets of lanes in rotation, each released when the upload that reads it has run (the bin launch behind it says so
@@ -777,6 +799,7 @@ void stripe_rows(int height, int world, int rank, int* y0, int* y1);
 void comm_unique_id(uint8_t out[FDH_COMM_ID_BYTES]);
 void blur_weight_fragments(float blur_radius, bool vertical, float* dense, uint16_t* frag_bits, int* reach, int* k_steps);
 void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out);
+void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles);
 void saturated_core_of(const float rect[4], const float rx[4], const float ry[4], int mode, float factor, float spread,
                        const float shape[2], float aa, int out[4]);
 

@@ -114,4 +114,24 @@ void launch_damage_guard(hipStream_t s, const uint8_t* run, int node, bool resto
 void launch_composite_damage(hipStream_t s, const DrawRec* draws, const QuadExt* exts, CompositeParams P, const int* list, const uint32_t* count,
                              int grid);
 
+// Damage readback (include/figdraw_hip_readback.h).  The pending set is a stamp per bin: a bin is pending when stamp[bin] == epoch, the
+// number of the read that will fetch it.  A read moves the epoch on, which empties the set without a store (no launch clears a mask that
+// other workgroups of the pack are still counting).
+// k_damage_accumulate: ONE workgroup, after k_damage_resolve: stamps the bins of the frame's mask and leaves the number of pending bins
+// in *n_pending (page-locked host memory: the host reads it after the stream's synchronise and launches nothing when it is 0).
+void launch_damage_accumulate(hipStream_t s, const uint8_t* mask, uint32_t* stamp, uint32_t epoch, int bins, uint32_t* n_pending);
+// k_damage_pack: a workgroup per bin.  A pending bin's rank among the pending bins in row-major order is its slot: tiles[rank] = the
+// bin clipped to the frame (x, y, w, h), slot rank of `pixels` (16 KB: 64 rows of 256 bytes) = its pixels, zeros past the tile's edge.
+// `all`: every bin is pending whatever its stamp.  The last bin's workgroup leaves the number of tiles in *n_tiles.
+struct DamagePackParams {
+  const uint32_t* surf;    // the frame surface, pitch W pixels
+  const uint32_t* stamp;   // [bin]
+  uint8_t* pixels;         // [tile][64][256], 16-byte aligned
+  int4* tiles;             // [tile]
+  uint32_t* n_tiles;
+  uint32_t epoch;
+  int W, H, bins_x, bins_y, all;
+};
+void launch_damage_pack(hipStream_t s, const DamagePackParams& P);
+
 }  // namespace fdh

@@ -49,7 +49,8 @@ FDH_API int fdh_set_damage_tracking(FdhContext*, int on);
  * composited (NULL: not wanted; otherwise cap >= bins_x * bins_y bytes), the bin grid in *bins_x / *bins_y and the number of
  * composited bins in *n_damaged (each may be NULL).  A frame rendered in full -- tracking off, or a full frame above -- reports every
  * bin.  An application presents or reads back only these: bin (bx, by) is the pixels [64 bx, min(64 bx + 64, W)) x [64 by,
- * min(64 by + 64, H)).  FDH_ERR_INVALID before the first frame; FDH_ERR_NO_DEVICE on a record-only context. */
+ * min(64 by + 64, H)) -- figdraw_hip_readback.h brings exactly these to the host, packed, in one transfer, and keeps count of them
+ * across frames the application did not read.  FDH_ERR_INVALID before the first frame; FDH_ERR_NO_DEVICE on a record-only context. */
 FDH_API int fdh_damage_bins(FdhContext*, uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged);
 /* Diagnostic: the same for the bins whose signature changed, before the blur rule grew them (every bin of a full frame). */
 FDH_API int fdh_damage_changed_bins(FdhContext*, uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_changed);
