@@ -163,6 +163,13 @@ def load():
         L.fdh_read_damage.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.fdh_read_damage_into.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.fdh_apply_damage.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int]
+    # coded damage readback (include/figdraw_hip_stream.h; likewise)
+    if hasattr(L, "fdh_read_damage_coded"):
+        L.fdh_read_damage_coded.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int)]
+        L.fdh_decode_damage.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int64]
+        L.fdh_coded_damage_bound.argtypes = [C.c_int, C.c_int]
+        L.fdh_coded_damage_bound.restype = C.c_int64
     # picking (include/figdraw_hip_pick.h; likewise absent from older libraries)
     if hasattr(L, "fdh_set_pick"):
         L.fdh_set_pick.argtypes = [vp, C.c_int]
@@ -626,6 +633,44 @@ class HipContext:
                                 px.ctypes.data if len(t) else None, len(t))
         if rc != 0:
             raise FigdrawHipError(rc, L.fdh_last_error().decode())
+
+    # ---- coded damage readback (include/figdraw_hip_stream.h)
+    TILE_SOLID, TILE_PAL, TILE_RUNS, TILE_RAW = 0, 1, 2, 3  # FDH_TILE_*
+    CODED_TILE = np.dtype([("x", "<i2"), ("y", "<i2"), ("w", "<i2"), ("h", "<i2"), ("mode", "u1"), ("bits", "u1"), ("n", "<u2"), ("offset", "<u4"),
+                           ("size", "<u4"), ("solid", "<u4")])  # FdhCodedTile
+
+    def read_damage_coded(self):
+        """the pending bins of the last frame, coded on the GPU -> (tiles: structured array (n,) of CODED_TILE in row-major bin order;
+        payload: bytes, the blob the tiles' offsets point into; full: every bin of the grid is among them).  Copies: the library's
+        buffers are reused by the next read.  Empties the pending set, as read_damage does."""
+        t, p = C.c_void_p(), C.c_void_p()
+        n, full, nbytes = C.c_int(), C.c_int(), C.c_int64()
+        self._ck(self.L.fdh_read_damage_coded(self.h, C.byref(t), C.byref(p), C.byref(n), C.byref(nbytes), None, None, C.byref(full)))
+        if n.value == 0:
+            return np.zeros(0, self.CODED_TILE), b"", bool(full.value)
+        tiles = np.frombuffer(C.string_at(t.value, n.value * self.CODED_TILE.itemsize), self.CODED_TILE).copy()
+        return tiles, C.string_at(p.value, nbytes.value) if nbytes.value else b"", bool(full.value)
+
+    @staticmethod
+    def decode_damage(image: np.ndarray, tiles, payload) -> None:
+        """host only (no context, no GPU): decode what read_damage_coded returned -- or what arrived over a wire -- into `image`, uint8
+        (H, W, 4) with contiguous rows.  A stream that does not validate raises FigdrawHipError and leaves the image as it was."""
+        L = load()
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 4 or image.strides[2] != 1 or image.strides[1] != 4:
+            raise ValueError("decode_damage: the image must be uint8 (H, W, 4) with contiguous rows")
+        if not image.flags.writeable:
+            raise ValueError("decode_damage: the image is read-only")
+        t = np.ascontiguousarray(np.asarray(tiles, dtype=HipContext.CODED_TILE).reshape(-1))
+        blob = np.frombuffer(bytes(payload), np.uint8) if not isinstance(payload, np.ndarray) else np.ascontiguousarray(payload, np.uint8).reshape(-1)
+        rc = L.fdh_decode_damage(image.ctypes.data, image.strides[0], image.shape[1], image.shape[0], t.ctypes.data if len(t) else None, len(t),
+                                 blob.ctypes.data if blob.size else None, blob.size)
+        if rc != 0:
+            raise FigdrawHipError(rc, L.fdh_last_error().decode())
+
+    @staticmethod
+    def coded_damage_bound(w: int, h: int) -> int:
+        """an upper bound of a coded read's payload bytes for a w x h frame"""
+        return int(load().fdh_coded_damage_bound(int(w), int(h)))
 
     # ---- picking (include/figdraw_hip_pick.h)
     PICK_SHADOWS = 1  # FDH_PICK_SHADOWS

@@ -6,6 +6,7 @@
 #include "../../include/figdraw_hip_damage.h"
 #include "../../include/figdraw_hip_pick.h"
 #include "../../include/figdraw_hip_readback.h"
+#include "../../include/figdraw_hip_stream.h"
 
 using fdh::Context;
 
@@ -324,6 +325,17 @@ int fdh_read_damage_into(FdhContext* c, uint8_t* image_rgba8, int64_t pitch_byte
 int fdh_apply_damage(uint8_t* image_rgba8, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles) {
   return guard([&] { fdh::apply_damage(image_rgba8, pitch_bytes, w, h, tiles, pixels, n_tiles); });
 }
+// coded damage readback (include/figdraw_hip_stream.h)
+static_assert(sizeof(FdhCodedTile) == 24, "a directory entry is 24 bytes");
+int fdh_read_damage_coded(FdhContext* c, const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w,
+                          int* frame_h, int* full) {
+  return guard([&] { C(c)->read_damage_coded(tiles, payload, n_tiles, payload_bytes, frame_w, frame_h, full); });
+}
+int fdh_decode_damage(uint8_t* image_rgba8, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload,
+                      int64_t payload_bytes) {
+  return guard([&] { fdh::decode_damage(image_rgba8, pitch_bytes, w, h, tiles, n_tiles, payload, payload_bytes); });
+}
+int64_t fdh_coded_damage_bound(int w, int h) { return fdh::coded_damage_bound(w, h); }
 int fdh_set_cull(FdhContext* c, int mode) { return guard([&] { C(c)->set_cull(mode); }); }
 int fdh_debug_host_times(FdhContext* c, int64_t out_ns[12]) {
   return guard([&] {

@@ -823,6 +823,8 @@ void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* r
 void Context::release_readback() {
   h_rb_pixels_.release(); h_rb_tiles_.release();
   h_rb_pixels_dev_ = nullptr; h_rb_tiles_dev_ = nullptr;
+  h_rb_code_.release(); h_rb_dir_.release(); d_rb_cursor_.release();
+  h_rb_code_dev_ = nullptr; h_rb_dir_dev_ = nullptr;
 }
 void Context::set_damage_readback(bool on) {
   if (on && host_only_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_readback: a record-only context composites nothing");

@@ -22,6 +22,7 @@
 #include "../../include/figdraw_hip.h"
 #include "../../include/figdraw_hip_pick.h"
 #include "../../include/figdraw_hip_readback.h"
+#include "../../include/figdraw_hip_stream.h"
 #include "fdh_kernels.h"
 
 namespace fdh {
@@ -504,6 +505,8 @@ class Context : public Recorder {
   void set_damage_readback(bool on);
   void read_damage(const FdhDamageTile** tiles, const uint8_t** pixels, int* n_tiles, int* frame_w, int* frame_h, int* full);
   void read_damage_into(uint8_t* image, int64_t pitch_bytes, int w, int h, int* n_tiles);
+  // coded damage readback (include/figdraw_hip_stream.h; fdh_stream.cpp)
+  void read_damage_coded(const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w, int* frame_h, int* full);
   // picking (include/figdraw_hip_pick.h; fdh_pick.cpp)
   void set_pick(bool on) { pick_on_ = on; }
   void set_pick_tag(int32_t z, int32_t id) { tag_ = PickTag{z, id}; }
@@ -730,7 +733,13 @@ class Context : public Recorder {
   PinnedBuf<FdhDamageTile> h_rb_tiles_;
   uint8_t* h_rb_pixels_dev_ = nullptr;      // their device views
   FdhDamageTile* h_rb_tiles_dev_ = nullptr;
-  volatile uint32_t* rb_count_host_ = nullptr;  // pinned, 2 words: pending bins after the last k_damage_accumulate; tiles of the last k_damage_pack
+  volatile uint32_t* rb_count_host_ = nullptr;  // pinned, 3 words: pending bins after the last k_damage_accumulate; tiles of the last k_damage_pack / k_damage_encode; the latter's payload bytes
+  // coded reads (fdh_stream.cpp): directory and payload blob, page-locked and written by k_damage_encode; the blob's cursor on the device
+  PinnedBuf<uint8_t> h_rb_code_;
+  PinnedBuf<FdhCodedTile> h_rb_dir_;
+  uint8_t* h_rb_code_dev_ = nullptr;
+  FdhCodedTile* h_rb_dir_dev_ = nullptr;
+  DeviceBuf<uint32_t> d_rb_cursor_;
   void release_readback();
   int readback_pending(const char* who, bool* all);
   void readback_consumed();
@@ -800,6 +809,8 @@ void comm_unique_id(uint8_t out[FDH_COMM_ID_BYTES]);
 void blur_weight_fragments(float blur_radius, bool vertical, float* dense, uint16_t* frag_bits, int* reach, int* k_steps);
 void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out);
 void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles);
+void decode_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload, int64_t payload_bytes);
+int64_t coded_damage_bound(int w, int h);
 void saturated_core_of(const float rect[4], const float rx[4], const float ry[4], int mode, float factor, float spread,
                        const float shape[2], float aa, int out[4]);
 

@@ -133,5 +133,22 @@ struct DamagePackParams {
   int W, H, bins_x, bins_y, all;
 };
 void launch_damage_pack(hipStream_t s, const DamagePackParams& P);
+// k_damage_encode (k_damage_codec.hip; include/figdraw_hip_stream.h is the format): k_damage_pack's shape -- a workgroup per bin, rank
+// among the pending bins = directory slot, the last bin's workgroup leaves the number of tiles -- but a pending bin's workgroup codes its
+// tile in the cheapest of the four modes, claims the payload's space (its size rounded up to 16 bytes) with one atomic add on *cursor
+// (device memory, zeroed in stream order before the launch) and stores entry and payload.  The workgroup that makes the last of the
+// n_pending claims leaves the blob's size in *payload_bytes.
+struct DamageEncodeParams {
+  const uint32_t* surf;    // the frame surface, pitch W pixels
+  const uint32_t* stamp;   // [bin]
+  uint8_t* payload;        // bins * 16384 bytes, 16-byte aligned
+  uint2* dir;              // [tile] FdhCodedTile, 24 bytes each
+  uint32_t* n_tiles;
+  uint32_t* payload_bytes;
+  unsigned long long* cursor;
+  uint32_t epoch, n_pending;
+  int W, H, bins_x, bins_y, all;
+};
+void launch_damage_encode(hipStream_t s, const DamageEncodeParams& P);
 
 }  // namespace fdh

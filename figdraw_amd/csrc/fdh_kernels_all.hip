@@ -7,3 +7,4 @@
 #include "k_atlas_upload.hip"
 #include "k_damage.hip"
 #include "k_pick.hip"
+#include "k_damage_codec.hip"
