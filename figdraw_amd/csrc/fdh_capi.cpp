@@ -3,6 +3,7 @@
 #include <string>
 
 #include "fdh_context.h"
+#include "fdh_damage.h"
 #include "../../include/figdraw_hip_damage.h"
 #include "../../include/figdraw_hip_pick.h"
 #include "../../include/figdraw_hip_readback.h"

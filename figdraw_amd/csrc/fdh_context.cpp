@@ -1,9 +1,8 @@
 // fdh_context.cpp -- a context's life and a frame's way through it: creation and teardown, the submit thread, begin_frame /
-// end_frame, and the launches of a prepared frame (issue, launch_frame and its stages, replay / profile), readback, damage tracking's
-// entry points.  The draw calls between begin_frame and end_frame are fdh_record.cpp's; what end_frame does on the calling thread
+// end_frame, and the launches of a prepared frame (issue, launch_frame and its stages, replay / profile), readback, and the context's
+// part of the damage entry points (the rest of those is fdh_damage.cpp's).  The draw calls between begin_frame and end_frame are fdh_record.cpp's; what end_frame does on the calling thread
 // before the hand-over is fdh_prepare.cpp's.
 #include "fdh_context.h"
-#include "fdh_damage.h"
 #include "fdh_host.h"
 #include "fdh_walkpool.h"
 
@@ -91,9 +90,7 @@ void Context::release_device_state() {
   if (alt_) (void)hipFree(alt_);
   if (dbg_snap_) (void)hipFree(dbg_snap_);
   d_frame_.release(); d_lists_.release(); d_counts_.release(); d_order_[0].release(); d_order_[1].release();
-  d_dmg_sig_.release(); d_dmg_changed_.release(); d_dmg_mask_.release(); d_dmg_run_.release(); d_dmg_list_.release(); d_dmg_count_.release(); d_dmg_keep_.release();
-  d_rb_stamp_.release(); release_readback();
-  if (rb_count_host_) (void)hipHostFree((void*)rb_count_host_);
+  damage_.release(); readback_.release();
   glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); d_mask_spill_.release();
   d_pick_.release(); d_pick_spill_.release(); h_pick_.release();
   for (auto& set : lanes_) set.clear();  // (pinned arrays: freed while the device is still this thread's)
@@ -461,73 +458,6 @@ BinParams Context::bin_params(const LaunchJob& J, uint32_t upload_seq) const {
   return B;
 }
 
-// the signatures a tracked frame leaves describe it whole only when every one of its blur nodes was folded in (more nodes than
-// kDamageMaxNodes: the frame is rendered in full, and so is the next)
-static bool damage_sig_whole(const LaunchJob& J) { return J.blurs.size() <= (size_t)kDamageMaxNodes; }
-
-// Damage tracking (fdh_damage.h): the bins whose signatures changed since this context's last tracked frame, closed under the blur rule,
-// as a compact list the compositor launches walk.  A frame whose key differs from that frame's is rendered in full (its signatures are
-// still taken: the next frame compares against them).
-bool Context::launch_damage(const LaunchJob& J, const BinParams& B) {
-  const int nb = J.bins_x * J.bins_y, np = (int)J.phases.size();
-  const bool tracked = J.damage && nb > 0 && np > 0;
-  // whatever this launch renders, the signatures and the surface stop matching until a tracked frame has been launched whole: a frame
-  // rendered without tracking leaves its pixels, not the signatures' frame, in the surface
-  const bool was_valid = dmg_valid_;
-  dmg_valid_ = false;
-  if (!tracked) {
-    dmg_last_ = false;
-    if (readback_on_) rb_all_ = true;  // (every bin is composited: no mask to accumulate, and no launch)
-    return false;
-  }
-  const bool full = J.damage_force || !damage_sig_whole(J) || !was_valid || dmg_key_ != J.damage_key;
-  const bool keep = !full && [&] { for (const BlurJob& j : J.blurs) if (j.fuse_draw >= 0) return true; return false; }();
-  if (d_dmg_sig_.cap < (size_t)nb || d_dmg_count_.cap == 0 || (keep && d_dmg_keep_.cap < (size_t)J.W * J.H)) {
-    FDH_HIP(hipStreamSynchronize(stream_));  // (a buffer that grows is freed: nothing in flight may still use it)
-    d_dmg_sig_.reserve(nb); d_dmg_changed_.reserve(nb); d_dmg_mask_.reserve(nb); d_dmg_list_.reserve(nb);
-    d_dmg_count_.reserve(1); d_dmg_run_.reserve(kDamageMaxNodes);
-    if (keep) d_dmg_keep_.reserve((size_t)J.W * J.H);
-  }
-  DamageSignParams S;
-  S.lists = J.lists; S.counts = J.counts; S.draws = J.dv.recs; S.exts = J.dv.exts; S.sig = d_dmg_sig_.ptr; S.changed = d_dmg_changed_.ptr;
-  S.n_phases = np; S.bins_x = J.bins_x; S.bins_y = J.bins_y; S.stride = J.list_stride; S.n_draws = J.n_recs; S.n_exts = J.n_exts;
-  S.force = full ? 1 : 0;
-  S.sub_n = B.sub_n;
-  for (int p = 0; p < kDamageMaxPhases; p++) {
-    const bool in = p < B.sub_n;
-    S.sub_x0[p] = in ? B.sub_x0[p] : 0; S.sub_y0[p] = in ? B.sub_y0[p] : 0; S.sub_nx[p] = in ? B.sub_nx[p] : 0;
-    S.sub_ny[p] = in ? (B.sub_first[p + 1] - B.sub_first[p]) / std::max(1, B.sub_nx[p]) : 0;
-  }
-  DamageResolveParams R;
-  R.changed = d_dmg_changed_.ptr; R.mask = d_dmg_mask_.ptr; R.list = d_dmg_list_.ptr; R.count = d_dmg_count_.ptr; R.run = d_dmg_run_.ptr;
-  R.bins_x = J.bins_x; R.bins_y = J.bins_y;
-  S.n_nodes = R.n_nodes = std::min((int)J.blurs.size(), kDamageMaxNodes);  // (more: a full frame, every bin changed)
-  for (int i = 0; i < S.n_nodes; i++) {
-    const BlurJob& j = J.blurs[(size_t)i];
-    int phase = -1;
-    for (int p = 0; p < np; p++) if (J.phases[p].blur == i) phase = p;
-    uint32_t rbits = 0;
-    std::memcpy(&rbits, &j.radius, 4);
-    uint64_t k = 1469598103934665603ull;
-    for (uint32_t v : {(uint32_t)phase, (uint32_t)j.x0, (uint32_t)j.y0, (uint32_t)j.x1, (uint32_t)j.y1, rbits, (uint32_t)j.taps.reach, (uint32_t)(j.fuse_draw >= 0)})
-      for (int b = 0; b < 4; b++) { k ^= (v >> (8 * b)) & 255u; k *= 1099511628211ull; }
-    S.foot[i] = damage_region(j.x0, j.y0, j.x1, j.y1, 0, J.bins_x, J.bins_y);
-    S.node_key[i] = k;
-    R.reg[i] = damage_region(j.x0, j.y0, j.x1, j.y1, j.taps.reach, J.bins_x, J.bins_y);
-  }
-  span_begin(kSpanBin); launch_damage_sign(stream_, S); span_end();
-  span_begin(kSpanBin); launch_damage_resolve(stream_, R); span_end();
-  if (readback_on_) {
-    // damage readback: the mask joins the pending set -- unless everything is pending already, or the stamps are those of another frame
-    // size (read_damage lays them out anew)
-    if (rb_all_ || rb_w_ != J.W || rb_h_ != J.H || d_rb_stamp_.cap < (size_t)nb) rb_all_ = true;
-    else { span_begin(kSpanBin); launch_damage_accumulate(stream_, d_dmg_mask_.ptr, d_rb_stamp_.ptr, rb_epoch_, nb, const_cast<uint32_t*>(rb_count_host_)); span_end(); }
-  }
-  dmg_bx_ = J.bins_x; dmg_by_ = J.bins_y;
-  dmg_last_ = true;
-  return !full;
-}
-
 // Phase 0's full-grid composite takes its bins longest-list first, in the order its predecessor sorted (an extra wavefront of that
 // launch); it sorts this frame's counts for its successor.  Any permutation is a correct schedule.
 Context::Schedule Context::schedule(const LaunchJob& J, bool direct, bool partial) {
@@ -605,10 +535,8 @@ uint32_t* Context::launch_blur(const LaunchJob& J, int p, uint32_t* cur, int row
   }
   bp.src = cur; bp.dst = blur_tmp_;
   bp.y0 = std::max(0, vy0 - j.taps.reach); bp.y1 = std::min(J.H, vy1 + j.taps.reach);
-  // a partial frame: a V pass that composites its quad into the surface runs whether the node took damage or not -- when it did not,
-  // its footprint is kept aside and put back (k_damage_guard: both return at once when the node's run flag is set)
-  const bool guard = partial && j.fuse_draw >= 0;
-  if (guard) launch_damage_guard(stream_, d_dmg_run_.ptr, ph.blur, false, cur, d_dmg_keep_.ptr, J.W, j.x0, vy0, j.x1, vy1);
+  const bool guard = partial && j.fuse_draw >= 0;  // (a V pass that composites its quad runs whether its node took damage or not)
+  if (guard) damage_.guard(stream_, J, ph.blur, false, cur, vy0, vy1);
   span_begin(big ? kSpanBigBlurH : kSpanBlurH);
   launch_blur_h(stream_, bp);
   span_end();
@@ -619,7 +547,7 @@ uint32_t* Context::launch_blur(const LaunchJob& J, int p, uint32_t* cur, int row
   span_begin(big ? kSpanBigBlurV : kSpanBlurV);
   launch_blur_v(stream_, bp, J.dv.recs, J.dv.exts);
   span_end();
-  if (guard) launch_damage_guard(stream_, d_dmg_run_.ptr, ph.blur, true, cur, d_dmg_keep_.ptr, J.W, j.x0, vy0, j.x1, vy1);
+  if (guard) damage_.guard(stream_, J, ph.blur, true, cur, vy0, vy1);
   return cur;
 }
 
@@ -662,7 +590,7 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
   const bool direct = direct_frame(J);
   const BinParams B = bin_params(J, upload_seq);
   span_begin(kSpanBin); if (!direct) launch_bin(stream_, B); span_end();
-  const bool partial = launch_damage(J, B);
+  const bool partial = damage_.launch(stream_, J, B, readback_, [this](bool begin) { if (begin) span_begin(kSpanBin); else span_end(); });
   const Schedule S = schedule(J, direct, partial);
   // The surface that holds the live image.  A fused full-frame blur renders out of place and flips it; a frame that flips an odd
   // number of times ends in alt_, and the two pointers trade places: the frame surface IS the one the frame ended in
@@ -675,12 +603,12 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
     CompositeParams C = composite_params(J, p, cur, lo[p], hi[p], direct, S);
     if (C.load_fb == 0) stats_.deep_bins = (float)composite_build(C).deep_k8;  // (the launch that starts the frame: its deep strips)
     span_begin(p == 0 ? kSpanCompositeMain : kSpanCompositeLater);
-    if (partial) launch_composite_damage(stream_, J.dv.recs, J.dv.exts, C, d_dmg_list_.ptr, d_dmg_count_.ptr, J.bins_x * J.bins_y * 16);  // (a wave per strip)
+    if (partial) damage_.composite(stream_, J, C);
     else launch_composite(stream_, J.dv.recs, J.dv.exts, C);
     span_end();
   }
   if (cur != fb_) std::swap(fb_, alt_);  // the frame ended in the other surface: it is the frame surface now
-  if (dmg_last_ && damage_sig_whole(J)) { dmg_valid_ = true; dmg_key_ = J.damage_key; }
+  damage_.launched_whole(J);
   FDH_HIP(hipGetLastError());
 }
 
@@ -777,12 +705,12 @@ void Context::read_pixels(int x, int y, int w, int h, uint8_t* out) {
   FDH_HIP(hipStreamSynchronize(stream_));
   FDH_HIP(hipMemcpy2D(out, (size_t)w * 4, fb_ + (size_t)y * W_ + x, (size_t)W_ * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost));
 }
-// ------------------------------------------------------------------ damage tracking (include/figdraw_hip_damage.h)
+// ------------------------------------------------------------------ damage tracking, damage readback: the context's part (fdh_damage.cpp)
 void Context::set_damage_tracking(bool on) {
   if (on && host_only_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_tracking: a record-only context composites nothing");
   drain();
   if (on && stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_tracking: not under fdh_set_stripe");
-  damage_on_ = on;
+  damage_.on = on;
 }
 void Context::damage_bins(uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged, bool changed_only) {
   need_device("fdh_damage_bins");
@@ -792,9 +720,7 @@ void Context::damage_bins(uint8_t* mask, int cap, int* bins_x, int* bins_y, int*
   if (mask && cap < nb) throw Error(FDH_ERR_INVALID, "fdh_damage_bins: the mask holds fewer bytes than the frame has bins");
   FDH_HIP(hipSetDevice(device_));
   FDH_HIP(hipStreamSynchronize(stream_));
-  std::vector<uint8_t> m((size_t)nb, 1);  // a frame rendered without tracking: every bin
-  if (dmg_last_ && dmg_bx_ == gx && dmg_by_ == gy && nb > 0)
-    FDH_HIP(hipMemcpy(m.data(), changed_only ? d_dmg_changed_.ptr : d_dmg_mask_.ptr, (size_t)nb, hipMemcpyDeviceToHost));
+  const std::vector<uint8_t> m = damage_.bins(gx, gy, changed_only);
   int n = 0;
   for (uint8_t v : m) n += v ? 1 : 0;
   if (mask) std::memcpy(mask, m.data(), (size_t)nb);
@@ -802,148 +728,31 @@ void Context::damage_bins(uint8_t* mask, int cap, int* bins_x, int* bins_y, int*
   if (bins_y) *bins_y = gy;
   if (n_damaged) *n_damaged = n;
 }
-void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out) {
-  if (bins_x < 0 || bins_y < 0 || n_nodes < 0 || n_nodes > kDamageMaxNodes) throw Error(FDH_ERR_INVALID, "fdh_damage_closure: bad grid or node count");
-  const size_t nb = (size_t)bins_x * bins_y;
-  if (nb && (!changed || !out)) throw Error(FDH_ERR_INVALID, "fdh_damage_closure: null mask");
-  if (n_nodes && (!rects || !radii)) throw Error(FDH_ERR_INVALID, "fdh_damage_closure: null node arrays");
-  std::vector<DamageRegion> reg((size_t)n_nodes);
-  for (int i = 0; i < n_nodes; i++) {
-    const int* r = rects + 4 * i;
-    const int reach = radii[i] > 0.0f ? make_taps(radii[i]).reach : 0;
-    reg[(size_t)i] = damage_region(r[0], r[1], r[2], r[3], reach, bins_x, bins_y);
-  }
-  std::vector<uint8_t> m(nb), run((size_t)n_nodes + 1);
-  for (size_t b = 0; b < nb; b++) m[b] = changed[b] ? 1 : 0;
-  damage_close(m.data(), bins_x, reg.data(), n_nodes, run.data(), DamageHostTeam());
-  if (nb) std::memcpy(out, m.data(), nb);
-}
-
-// ------------------------------------------------------------------ damage readback (include/figdraw_hip_readback.h)
-void Context::release_readback() {
-  h_rb_pixels_.release(); h_rb_tiles_.release();
-  h_rb_pixels_dev_ = nullptr; h_rb_tiles_dev_ = nullptr;
-  h_rb_code_.release(); h_rb_dir_.release(); d_rb_cursor_.release();
-  h_rb_code_dev_ = nullptr; h_rb_dir_dev_ = nullptr;
-}
 void Context::set_damage_readback(bool on) {
   if (on && host_only_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_readback: a record-only context composites nothing");
   if (host_only_) return;
   drain();
   if (on && stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_readback: not under fdh_set_stripe");
   FDH_HIP(hipSetDevice(device_));
-  if (on && !readback_on_) {
-    if (!rb_count_host_) {
-      FDH_HIP(hipHostMalloc((void**)&rb_count_host_, 64, hipHostMallocDefault));
-      rb_count_host_[0] = rb_count_host_[1] = 0;
-    }
-    rb_all_ = true;  // what the application holds is unknown: the first read brings every bin
-  }
-  if (!on && readback_on_) {
-    FDH_HIP(hipStreamSynchronize(stream_));
-    release_readback();
-  }
-  readback_on_ = on;
+  readback_.turn(on, stream_);
 }
-// What a read starts with: the last frame is complete, and this many of its bins are pending (`all`: every one, whatever the stamps say)
-int Context::readback_pending(const char* who, bool* all) {
+ReadFrame Context::read_frame(const char* who) {
   need_device(who);
   drain();
-  if (!readback_on_) throw Error(FDH_ERR_INVALID, std::string(who) + ": damage readback is off (fdh_set_damage_readback)");
+  if (!readback_.on) throw Error(FDH_ERR_INVALID, std::string(who) + ": damage readback is off (fdh_set_damage_readback)");
   if (!have_frame_ || !fb_) throw Error(FDH_ERR_INVALID, std::string(who) + ": no frame has been submitted");
   FDH_HIP(hipSetDevice(device_));
   FDH_HIP(hipStreamSynchronize(stream_));
-  const int nb = job_.bins_x * job_.bins_y;
-  *all = rb_all_ || rb_w_ != job_.W || rb_h_ != job_.H;
-  const int n = *all ? nb : (int)rb_count_host_[0];
-  if (n < 0 || n > nb) throw Error(FDH_ERR_HIP, std::string(who) + ": the pending count is out of range");
-  return n;
-}
-// ... and ends with (the stream is idle): the set is empty, the stamps are laid out for the last frame's grid
-void Context::readback_consumed() {
-  const size_t nb = (size_t)job_.bins_x * job_.bins_y;
-  // the next epoch's stamp is on no bin; fresh stamps, or an epoch that wrapped, start over (epochs start at 1)
-  if (d_rb_stamp_.cap < nb || rb_epoch_ + 1 == 0) {
-    d_rb_stamp_.reserve(nb);
-    FDH_HIP(hipMemset(d_rb_stamp_.ptr, 0, d_rb_stamp_.cap * sizeof(uint32_t)));
-    rb_epoch_ = 0;
-  }
-  rb_epoch_++;
-  rb_all_ = false; rb_w_ = job_.W; rb_h_ = job_.H;
-  rb_count_host_[0] = 0;
+  return ReadFrame{stream_, fb_, job_.W, job_.H, job_.bins_x, job_.bins_y};
 }
 void Context::read_damage(const FdhDamageTile** tiles, const uint8_t** pixels, int* n_tiles, int* frame_w, int* frame_h, int* full) {
-  bool all = false;
-  const int n = readback_pending("fdh_read_damage", &all);
-  const int W = job_.W, H = job_.H, gx = job_.bins_x, gy = job_.bins_y, nb = gx * gy;
-  if (n > 0) {
-    const size_t need = (size_t)nb * FDH_TILE_BYTES;
-    if (h_rb_pixels_.cap < need) {  // the whole grid, exactly (PinnedBuf::reserve doubles: 33.4 MB would become 64)
-      release_readback();
-      FDH_HIP(hipHostMalloc((void**)&h_rb_pixels_.ptr, need, hipHostMallocDefault));
-      h_rb_pixels_.cap = need;
-      h_rb_tiles_.reserve((size_t)nb);
-      FDH_HIP(hipHostGetDevicePointer((void**)&h_rb_pixels_dev_, h_rb_pixels_.ptr, 0));
-      FDH_HIP(hipHostGetDevicePointer((void**)&h_rb_tiles_dev_, h_rb_tiles_.ptr, 0));
-    }
-    DamagePackParams P;
-    P.surf = fb_; P.stamp = d_rb_stamp_.ptr;  // (`all`: the stamps are not read, and may not exist yet)
-    P.pixels = h_rb_pixels_dev_;
-    P.tiles = reinterpret_cast<int4*>(h_rb_tiles_dev_);
-    P.n_tiles = const_cast<uint32_t*>(rb_count_host_) + 1;
-    P.epoch = rb_epoch_; P.W = W; P.H = H; P.bins_x = gx; P.bins_y = gy; P.all = all ? 1 : 0;
-    rb_count_host_[1] = 0xFFFFFFFFu;
-    launch_damage_pack(stream_, P);
-    FDH_HIP(hipGetLastError());
-    FDH_HIP(hipStreamSynchronize(stream_));
-    if (rb_count_host_[1] != (uint32_t)n) throw Error(FDH_ERR_HIP, "fdh_read_damage: the pack's tile count differs from the pending count");
-    readback_consumed();
-  }
-  if (tiles) *tiles = h_rb_tiles_.ptr;
-  if (pixels) *pixels = h_rb_pixels_.ptr;
-  if (n_tiles) *n_tiles = n;
-  if (frame_w) *frame_w = W;
-  if (frame_h) *frame_h = H;
-  if (full) *full = (nb > 0 && n == nb) ? 1 : 0;
+  readback_.read_raw(read_frame("fdh_read_damage"), tiles, pixels, n_tiles, frame_w, frame_h, full);
 }
-// Tiles cross the link at no more bytes than they hold, but reach the mirror through a second pass on the CPU (fdh_apply_damage out of
-// page-locked memory: ~0.7 - 1 us a tile), which a whole-frame copy into the caller's memory does not pay (~0.3 us a bin).  From
-// kReadbackWholeNum / kReadbackWholeDen of the grid on, the whole frame is the cheaper way to the same mirror
-// (profiles/damage_readback.txt: the crossover sits at 0.26 - 0.36 of the grid at 4K and 1080p).
-constexpr int kReadbackWholeNum = 3, kReadbackWholeDen = 10;
 void Context::read_damage_into(uint8_t* image, int64_t pitch_bytes, int w, int h, int* n_tiles) {
-  bool all = false;
-  const int n = readback_pending("fdh_read_damage_into", &all);
-  if (!image) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: null image");
-  if (w != job_.W || h != job_.H) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: the image is not the size of the last frame");
-  if (pitch_bytes < (int64_t)4 * w) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: the pitch is shorter than a row");
-  const int nb = job_.bins_x * job_.bins_y;
-  if (n > 0 && (int64_t)n * kReadbackWholeDen >= (int64_t)nb * kReadbackWholeNum) {
-    FDH_HIP(hipMemcpy2D(image, (size_t)pitch_bytes, fb_, (size_t)w * 4, (size_t)w * 4, (size_t)h, hipMemcpyDeviceToHost));
-    readback_consumed();
-  } else {
-    const FdhDamageTile* t = nullptr;
-    const uint8_t* px = nullptr;
-    read_damage(&t, &px, nullptr, nullptr, nullptr, nullptr);  // (the same n: nothing was submitted in between)
-    apply_damage(image, pitch_bytes, w, h, t, px, n);
-  }
-  if (n_tiles) *n_tiles = n;
+  readback_.read_into(read_frame("fdh_read_damage_into"), image, pitch_bytes, w, h, n_tiles);
 }
-void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles) {
-  if (n_tiles < 0) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: negative tile count");
-  if (w < 0 || h < 0 || pitch_bytes < (int64_t)4 * w) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: the pitch is shorter than a row");
-  if (n_tiles == 0) return;
-  if (!image || !tiles || !pixels) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: null image, tiles or pixels");
-  for (int i = 0; i < n_tiles; i++) {  // every tile is checked before any byte is written
-    const FdhDamageTile& t = tiles[i];
-    if (t.w < 1 || t.w > FDH_TILE_PX || t.h < 1 || t.h > FDH_TILE_PX || t.x < 0 || t.y < 0 || (int64_t)t.x + t.w > w || (int64_t)t.y + t.h > h)
-      throw Error(FDH_ERR_INVALID, "fdh_apply_damage: tile " + std::to_string(i) + " is not a bin inside the image");
-  }
-  for (int i = 0; i < n_tiles; i++) {
-    const FdhDamageTile& t = tiles[i];
-    const uint8_t* src = pixels + (size_t)i * FDH_TILE_BYTES;
-    for (int r = 0; r < t.h; r++) std::memcpy(image + (int64_t)(t.y + r) * pitch_bytes + (int64_t)4 * t.x, src + (size_t)r * FDH_TILE_PITCH, (size_t)4 * t.w);
-  }
+void Context::read_damage_coded(const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w, int* frame_h, int* full) {
+  readback_.read_coded(read_frame("fdh_read_damage_coded"), tiles, payload, n_tiles, payload_bytes, frame_w, frame_h, full);
 }
 
 void Context::frame_device_ptr(void** p, int* w, int* h, int64_t* pitch_bytes) {

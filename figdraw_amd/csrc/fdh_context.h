@@ -67,21 +67,25 @@ struct DeviceBuf {
 
 template <typename T>
 struct PinnedBuf {
-  T* ptr = nullptr;
+  T *ptr = nullptr, *dev = nullptr;  // the block as the host addresses it, and as the device does (taken once, when the block is allocated)
   size_t cap = 0;
   void reserve(size_t n) {
     if (n <= cap) return;
     size_t want = cap ? cap : 256;
     while (want < n) want *= 2;
-    T* fresh = nullptr;
-    FDH_HIP(hipHostMalloc((void**)&fresh, want * sizeof(T), hipHostMallocDefault));
+    reserve_exact(want);
+  }
+  void reserve_exact(size_t n) {  // no doubling: a block of tens of megabytes is the size that was asked for
+    if (n <= cap) return;
+    T *fresh = nullptr, *fresh_dev = nullptr;
+    FDH_HIP(hipHostMalloc((void**)&fresh, n * sizeof(T), hipHostMallocDefault));
+    if (hipError_t e = hipHostGetDevicePointer((void**)&fresh_dev, fresh, 0)) { (void)hipHostFree(fresh); FDH_HIP(e); }
     if (ptr) (void)hipHostFree(ptr);
-    ptr = fresh;
-    cap = want;
+    ptr = fresh; dev = fresh_dev; cap = n;
   }
   void release() {
     if (ptr) (void)hipHostFree(ptr);
-    ptr = nullptr;
+    ptr = dev = nullptr;
     cap = 0;
   }
 };
@@ -429,6 +433,10 @@ struct LaunchJob {
   int pick_depth = 0;
 };
 
+}  // namespace fdh
+#include "fdh_damage_host.h"  // DamageTracker, DamageReadback: two members of Context
+namespace fdh {
+
 class Context : public Recorder {
  public:
   Context(int atlas_size, float pixel_scale, int device, uint32_t flags);
@@ -494,18 +502,16 @@ class Context : public Recorder {
   // multi-GPU / measurement
   void set_stripe(int y0, int y1) {
     drain();
-    if (damage_on_ && y1 > y0) throw Error(FDH_ERR_INVALID, "fdh_set_stripe: damage tracking is on (fdh_set_damage_tracking: not under row stripes)");
-    if (readback_on_ && y1 > y0) throw Error(FDH_ERR_INVALID, "fdh_set_stripe: damage readback is on (fdh_set_damage_readback: not under row stripes)");
+    if (damage_.on && y1 > y0) throw Error(FDH_ERR_INVALID, "fdh_set_stripe: damage tracking is on (fdh_set_damage_tracking: not under row stripes)");
+    if (readback_.on && y1 > y0) throw Error(FDH_ERR_INVALID, "fdh_set_stripe: damage readback is on (fdh_set_damage_readback: not under row stripes)");
     stripe_y0_ = y0; stripe_y1_ = y1;
   }
-  // damage tracking (include/figdraw_hip_damage.h)
+  // damage tracking, damage readback and coded damage readback: the context's part of each entry point; the rest is fdh_damage.cpp's
   void set_damage_tracking(bool on);
   void damage_bins(uint8_t* mask, int cap, int* bins_x, int* bins_y, int* n_damaged, bool changed_only);
-  // damage readback (include/figdraw_hip_readback.h)
   void set_damage_readback(bool on);
   void read_damage(const FdhDamageTile** tiles, const uint8_t** pixels, int* n_tiles, int* frame_w, int* frame_h, int* full);
   void read_damage_into(uint8_t* image, int64_t pitch_bytes, int w, int h, int* n_tiles);
-  // coded damage readback (include/figdraw_hip_stream.h; fdh_stream.cpp)
   void read_damage_coded(const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w, int* frame_h, int* full);
   // picking (include/figdraw_hip_pick.h; fdh_pick.cpp)
   void set_pick(bool on) { pick_on_ = on; }
@@ -585,7 +591,6 @@ class Context : public Recorder {
   struct Schedule { const int* order_now = nullptr; int* order_next = nullptr; int deep_min = 0, deep_k8 = 0; };  // of the full-frame launch
   void phase_rows(const LaunchJob& J, std::vector<int>& lo, std::vector<int>& hi) const;
   BinParams bin_params(const LaunchJob& J, uint32_t upload_seq) const;
-  bool launch_damage(const LaunchJob& J, const BinParams& B);  // true: a partial frame
   Schedule schedule(const LaunchJob& J, bool direct, bool partial);
   uint32_t* launch_blur(const LaunchJob& J, int p, uint32_t* cur, int row_lo, int row_hi, bool partial);
   CompositeParams composite_params(const LaunchJob& J, int p, uint32_t* cur, int row_lo, int row_hi, bool direct, const Schedule& S) const;
@@ -705,44 +710,14 @@ class Context : public Recorder {
   DeviceBuf<uint2> d_lists_;
   DeviceBuf<uint32_t> d_counts_;
   DeviceBuf<int> d_order_[2];  // phase 0's bins, longest list first: read by this frame's launch / written for the next
-  // damage tracking (submission side): the per-bin signatures of the last tracked frame, what its resolve left, the footprint a fused V
-  // pass of a node that did not run writes over (k_damage_guard); dmg_valid_: the surface holds the frame of key dmg_key_ and the
-  // signatures are that frame's
-  bool damage_on_ = false;  // (calling thread: fdh_set_damage_tracking)
+  DamageTracker damage_;
+  DamageReadback readback_;
+  ReadFrame read_frame(const char* who);  // a read's first steps: the last frame is complete; what the read needs of it
   // picking: fdh_set_pick (calling thread), latched per frame at begin_frame (pick_frame_: the lanes keep tags); the pick launches' buffers
   bool pick_on_ = false, pick_frame_ = false;
   void pick_check(const char* who, int threshold, uint32_t flags);
   DeviceBuf<uint8_t> d_pick_, d_pick_spill_;
   PinnedBuf<uint8_t> h_pick_;
-  bool dmg_valid_ = false, dmg_last_ = false;
-  uint64_t dmg_key_ = 0;
-  int dmg_bx_ = 0, dmg_by_ = 0;
-  DeviceBuf<uint64_t> d_dmg_sig_;
-  DeviceBuf<uint8_t> d_dmg_changed_, d_dmg_mask_, d_dmg_run_;
-  DeviceBuf<int> d_dmg_list_;
-  DeviceBuf<uint32_t> d_dmg_count_, d_dmg_keep_;
-  // damage readback (include/figdraw_hip_readback.h).  rb_all_: every bin is pending whatever the stamps say -- written by whoever
-  // launches a frame (launch_damage: the submit thread, or replay's caller after a drain), read by read_damage after drain().  The
-  // stamps d_rb_stamp_ describe a frame of rb_w_ x rb_h_ pixels; rb_epoch_ is the stamp of a pending bin (fdh_damage.h).
-  bool readback_on_ = false;  // (calling thread: fdh_set_damage_readback)
-  bool rb_all_ = true;
-  uint32_t rb_epoch_ = 1;
-  int rb_w_ = 0, rb_h_ = 0;
-  DeviceBuf<uint32_t> d_rb_stamp_;
-  PinnedBuf<uint8_t> h_rb_pixels_;          // [tile][64][256]: what fdh_read_damage returns
-  PinnedBuf<FdhDamageTile> h_rb_tiles_;
-  uint8_t* h_rb_pixels_dev_ = nullptr;      // their device views
-  FdhDamageTile* h_rb_tiles_dev_ = nullptr;
-  volatile uint32_t* rb_count_host_ = nullptr;  // pinned, 3 words: pending bins after the last k_damage_accumulate; tiles of the last k_damage_pack / k_damage_encode; the latter's payload bytes
-  // coded reads (fdh_stream.cpp): directory and payload blob, page-locked and written by k_damage_encode; the blob's cursor on the device
-  PinnedBuf<uint8_t> h_rb_code_;
-  PinnedBuf<FdhCodedTile> h_rb_dir_;
-  uint8_t* h_rb_code_dev_ = nullptr;
-  FdhCodedTile* h_rb_dir_dev_ = nullptr;
-  DeviceBuf<uint32_t> d_rb_cursor_;
-  void release_readback();
-  int readback_pending(const char* who, bool* all);
-  void readback_consumed();
   int order_read_ = 0, order_nb_ = 0;
   bool order_valid_ = false;
   // kStaging sets of lanes in rotation, each released when the upload that reads it has run (the bin launch behind it says so
@@ -807,10 +782,6 @@ void record_host_form(DrawRec& r);  // undo the device form of a committed recor
 void stripe_rows(int height, int world, int rank, int* y0, int* y1);
 void comm_unique_id(uint8_t out[FDH_COMM_ID_BYTES]);
 void blur_weight_fragments(float blur_radius, bool vertical, float* dense, uint16_t* frag_bits, int* reach, int* k_steps);
-void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out);
-void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles);
-void decode_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload, int64_t payload_bytes);
-int64_t coded_damage_bound(int w, int h);
 void saturated_core_of(const float rect[4], const float rx[4], const float ry[4], int mode, float factor, float spread,
                        const float shape[2], float aa, int out[4]);
 

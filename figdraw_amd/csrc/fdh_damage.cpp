@@ -1,0 +1,364 @@
+// fdh_damage.cpp -- damage tracking, damage readback and coded damage readback on the host: the two components a device context holds
+// (DamageTracker, DamageReadback: fdh_damage_host.h) -- every launch of k_damage.hip and k_damage_codec.hip, the pending set, the
+// page-locked buffers a read returns -- and the host-only functions behind fdh_damage_closure, fdh_apply_damage, fdh_decode_damage and
+// fdh_coded_damage_bound.  What belongs to the context of an entry point (its refusals, the wait for the last frame) is fdh_context.cpp's.
+#include "fdh_context.h"
+#include "fdh_damage.h"
+#include "fdh_host.h"
+
+#include <cstring>
+
+namespace fdh {
+
+// ------------------------------------------------------------------ damage tracking (include/figdraw_hip_damage.h)
+// the signatures a tracked frame leaves describe it whole only when every one of its blur nodes was folded in (more nodes than
+// kDamageMaxNodes: the frame is rendered in full, and so is the next)
+static bool damage_sig_whole(const LaunchJob& J) { return J.blurs.size() <= (size_t)kDamageMaxNodes; }
+
+// The bins whose signatures changed since the context's last tracked frame, closed under the blur rule (fdh_damage.h), as a compact list
+// the compositor launches walk.  A frame whose key differs from that frame's is rendered in full (its signatures are still taken: the
+// next frame compares against them).
+bool DamageTracker::launch(hipStream_t s, const LaunchJob& J, const BinParams& B, DamageReadback& rb, const LaunchSpan& span) {
+  const int nb = J.bins_x * J.bins_y, np = (int)J.phases.size();
+  const bool tracked = J.damage && nb > 0 && np > 0;
+  // whatever this launch renders, the signatures and the surface stop matching until a tracked frame has been launched whole: a frame
+  // rendered without tracking leaves its pixels, not the signatures' frame, in the surface
+  const bool was_valid = valid;
+  valid = false;
+  if (!tracked) {
+    last = false;
+    rb.frame_whole();
+    return false;
+  }
+  const bool full = J.damage_force || !damage_sig_whole(J) || !was_valid || key != J.damage_key;
+  const bool keeps = !full && [&] { for (const BlurJob& j : J.blurs) if (j.fuse_draw >= 0) return true; return false; }();
+  if (sig.cap < (size_t)nb || count.cap == 0 || (keeps && keep.cap < (size_t)J.W * J.H)) {
+    FDH_HIP(hipStreamSynchronize(s));  // (a buffer that grows is freed: nothing in flight may still use it)
+    sig.reserve(nb); changed.reserve(nb); mask.reserve(nb); list.reserve(nb);
+    count.reserve(1); run.reserve(kDamageMaxNodes);
+    if (keeps) keep.reserve((size_t)J.W * J.H);
+  }
+  DamageSignParams S;
+  S.lists = J.lists; S.counts = J.counts; S.draws = J.dv.recs; S.exts = J.dv.exts; S.sig = sig.ptr; S.changed = changed.ptr;
+  S.n_phases = np; S.bins_x = J.bins_x; S.bins_y = J.bins_y; S.stride = J.list_stride; S.n_draws = J.n_recs; S.n_exts = J.n_exts;
+  S.force = full ? 1 : 0;
+  S.sub_n = B.sub_n;
+  for (int p = 0; p < kDamageMaxPhases; p++) {
+    const bool in = p < B.sub_n;
+    S.sub_x0[p] = in ? B.sub_x0[p] : 0; S.sub_y0[p] = in ? B.sub_y0[p] : 0; S.sub_nx[p] = in ? B.sub_nx[p] : 0;
+    S.sub_ny[p] = in ? (B.sub_first[p + 1] - B.sub_first[p]) / std::max(1, B.sub_nx[p]) : 0;
+  }
+  DamageResolveParams R;
+  R.changed = changed.ptr; R.mask = mask.ptr; R.list = list.ptr; R.count = count.ptr; R.run = run.ptr;
+  R.bins_x = J.bins_x; R.bins_y = J.bins_y;
+  S.n_nodes = R.n_nodes = std::min((int)J.blurs.size(), kDamageMaxNodes);  // (more: a full frame, every bin changed)
+  for (int i = 0; i < S.n_nodes; i++) {
+    const BlurJob& j = J.blurs[(size_t)i];
+    int phase = -1;
+    for (int p = 0; p < np; p++) if (J.phases[p].blur == i) phase = p;
+    uint32_t rbits = 0;
+    std::memcpy(&rbits, &j.radius, 4);
+    uint64_t k = 1469598103934665603ull;
+    for (uint32_t v : {(uint32_t)phase, (uint32_t)j.x0, (uint32_t)j.y0, (uint32_t)j.x1, (uint32_t)j.y1, rbits, (uint32_t)j.taps.reach, (uint32_t)(j.fuse_draw >= 0)})
+      for (int b = 0; b < 4; b++) { k ^= (v >> (8 * b)) & 255u; k *= 1099511628211ull; }
+    S.foot[i] = damage_region(j.x0, j.y0, j.x1, j.y1, 0, J.bins_x, J.bins_y);
+    S.node_key[i] = k;
+    R.reg[i] = damage_region(j.x0, j.y0, j.x1, j.y1, j.taps.reach, J.bins_x, J.bins_y);
+  }
+  span(true); launch_damage_sign(s, S); span(false);
+  span(true); launch_damage_resolve(s, R); span(false);
+  rb.accumulate(s, J, mask.ptr, span);
+  bins_x = J.bins_x; bins_y = J.bins_y;
+  last = true;
+  return !full;
+}
+void DamageTracker::launched_whole(const LaunchJob& J) {
+  if (last && damage_sig_whole(J)) { valid = true; key = J.damage_key; }
+}
+// a partial frame: a V pass that composites its quad into the surface runs whether the node took damage or not -- when it did not,
+// its footprint is kept aside and put back (k_damage_guard: both return at once when the node's run flag is set)
+void DamageTracker::guard(hipStream_t s, const LaunchJob& J, int node, bool restore, uint32_t* surf, int y0, int y1) const {
+  const BlurJob& j = J.blurs[(size_t)node];
+  launch_damage_guard(s, run.ptr, node, restore, surf, keep.ptr, J.W, j.x0, y0, j.x1, y1);
+}
+void DamageTracker::composite(hipStream_t s, const LaunchJob& J, const CompositeParams& C) const {
+  launch_composite_damage(s, J.dv.recs, J.dv.exts, C, list.ptr, count.ptr, J.bins_x * J.bins_y * 16);  // (a wave per strip)
+}
+std::vector<uint8_t> DamageTracker::bins(int gx, int gy, bool changed_only) const {
+  const int nb = gx * gy;
+  std::vector<uint8_t> m((size_t)nb, 1);  // a frame rendered without tracking: every bin
+  if (last && bins_x == gx && bins_y == gy && nb > 0)
+    FDH_HIP(hipMemcpy(m.data(), changed_only ? changed.ptr : mask.ptr, (size_t)nb, hipMemcpyDeviceToHost));
+  return m;
+}
+void DamageTracker::release() {
+  sig.release(); changed.release(); mask.release(); run.release(); list.release(); count.release(); keep.release();
+}
+void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out) {
+  if (bins_x < 0 || bins_y < 0 || n_nodes < 0 || n_nodes > kDamageMaxNodes) throw Error(FDH_ERR_INVALID, "fdh_damage_closure: bad grid or node count");
+  const size_t nb = (size_t)bins_x * bins_y;
+  if (nb && (!changed || !out)) throw Error(FDH_ERR_INVALID, "fdh_damage_closure: null mask");
+  if (n_nodes && (!rects || !radii)) throw Error(FDH_ERR_INVALID, "fdh_damage_closure: null node arrays");
+  std::vector<DamageRegion> reg((size_t)n_nodes);
+  for (int i = 0; i < n_nodes; i++) {
+    const int* r = rects + 4 * i;
+    const int reach = radii[i] > 0.0f ? make_taps(radii[i]).reach : 0;
+    reg[(size_t)i] = damage_region(r[0], r[1], r[2], r[3], reach, bins_x, bins_y);
+  }
+  std::vector<uint8_t> m(nb), run((size_t)n_nodes + 1);
+  for (size_t b = 0; b < nb; b++) m[b] = changed[b] ? 1 : 0;
+  damage_close(m.data(), bins_x, reg.data(), n_nodes, run.data(), DamageHostTeam());
+  if (nb) std::memcpy(out, m.data(), nb);
+}
+
+// ------------------------------------------------------------------ damage readback (include/figdraw_hip_readback.h, figdraw_hip_stream.h)
+void DamageReadback::release() {
+  pixels.release(); tiles.release(); code.release(); dir.release(); cursor.release(); stamp.release();
+  if (count) (void)hipHostFree((void*)count);
+  count = nullptr;
+}
+void DamageReadback::turn(bool on_now, hipStream_t s) {
+  if (on_now && !on) {
+    if (!count) {
+      FDH_HIP(hipHostMalloc((void**)&count, 64, hipHostMallocDefault));
+      count[0] = count[1] = 0;
+    }
+    all = true;  // what the application holds is unknown: the first read brings every bin
+  }
+  if (!on_now && on) {
+    FDH_HIP(hipStreamSynchronize(s));
+    release();
+  }
+  on = on_now;
+}
+// the mask joins the pending set -- unless everything is pending already, or the stamps are those of another frame size (a read lays
+// them out anew)
+void DamageReadback::accumulate(hipStream_t s, const LaunchJob& J, const uint8_t* mask, const LaunchSpan& span) {
+  if (!on) return;
+  const int nb = J.bins_x * J.bins_y;
+  if (all || w != J.W || h != J.H || stamp.cap < (size_t)nb) all = true;
+  else { span(true); launch_damage_accumulate(s, mask, stamp.ptr, epoch, nb, const_cast<uint32_t*>(count)); span(false); }
+}
+int DamageReadback::pending(const char* who, const ReadFrame& F, bool* every) const {
+  const int nb = F.bins_x * F.bins_y;
+  *every = all || w != F.W || h != F.H;
+  const int n = *every ? nb : (int)count[0];
+  if (n < 0 || n > nb) throw Error(FDH_ERR_HIP, std::string(who) + ": the pending count is out of range");
+  return n;
+}
+void DamageReadback::consumed(const ReadFrame& F) {
+  const size_t nb = (size_t)F.bins_x * F.bins_y;
+  // the next epoch's stamp is on no bin; fresh stamps, or an epoch that wrapped, start over (epochs start at 1)
+  if (stamp.cap < nb || epoch + 1 == 0) {
+    stamp.reserve(nb);
+    FDH_HIP(hipMemset(stamp.ptr, 0, stamp.cap * sizeof(uint32_t)));
+    epoch = 0;
+  }
+  epoch++;
+  all = false; w = F.W; h = F.H;
+  count[0] = 0;
+}
+int64_t coded_damage_bound(int w, int h) {
+  if (w <= 0 || h <= 0) return 0;
+  return (int64_t)((w + FDH_TILE_PX - 1) / FDH_TILE_PX) * ((h + FDH_TILE_PX - 1) / FDH_TILE_PX) * FDH_TILE_BYTES;
+}
+// Both buffers of a read hold the whole grid's worst case, exactly (doubled, a 4K frame's 33.4 MB would become 64): a read of n tiles
+// never moves them, so the pointers of the other kind of read stay where they are.
+int DamageReadback::read(const char* who, const ReadFrame& F, int64_t* payload_bytes) {
+  const bool coded = payload_bytes != nullptr;
+  bool every = false;
+  const int n = pending(who, F, &every);
+  const int nb = F.bins_x * F.bins_y;
+  const size_t bound = (size_t)coded_damage_bound(F.W, F.H);  // (= nb tiles of FDH_TILE_BYTES)
+  if (coded && (F.W > INT16_MAX || F.H > INT16_MAX || bound > (size_t)UINT32_MAX))
+    throw Error(FDH_ERR_INVALID, "fdh_read_damage_coded: a directory entry holds coordinates up to 32767 and offsets of 32 bits");
+  if (coded) *payload_bytes = 0;
+  if (n <= 0) return n;
+  uint32_t* const words = const_cast<uint32_t*>(count);
+  count[1] = count[2] = 0xFFFFFFFFu;
+  if (coded) {
+    code.reserve_exact(bound); dir.reserve_exact((size_t)nb); cursor.reserve(2);
+    DamageEncodeParams P;
+    P.surf = F.surf; P.stamp = stamp.ptr;  // (`every`: the stamps are not read, and may not exist yet)
+    P.payload = code.dev; P.dir = reinterpret_cast<uint2*>(dir.dev);
+    P.n_tiles = words + 1; P.payload_bytes = words + 2;
+    P.cursor = reinterpret_cast<unsigned long long*>(cursor.ptr);
+    P.epoch = epoch; P.n_pending = (uint32_t)n; P.W = F.W; P.H = F.H; P.bins_x = F.bins_x; P.bins_y = F.bins_y; P.all = every ? 1 : 0;
+    FDH_HIP(hipMemsetAsync(cursor.ptr, 0, 2 * sizeof(uint32_t), F.stream));
+    launch_damage_encode(F.stream, P);
+  } else {
+    pixels.reserve_exact(bound); tiles.reserve_exact((size_t)nb);
+    DamagePackParams P;
+    P.surf = F.surf; P.stamp = stamp.ptr;
+    P.pixels = pixels.dev; P.tiles = reinterpret_cast<int4*>(tiles.dev);
+    P.n_tiles = words + 1;
+    P.epoch = epoch; P.W = F.W; P.H = F.H; P.bins_x = F.bins_x; P.bins_y = F.bins_y; P.all = every ? 1 : 0;
+    launch_damage_pack(F.stream, P);
+  }
+  FDH_HIP(hipGetLastError());
+  FDH_HIP(hipStreamSynchronize(F.stream));
+  if (count[1] != (uint32_t)n) throw Error(FDH_ERR_HIP, std::string(who) + ": the " + (coded ? "encoder's" : "pack's") + " tile count differs from the pending count");
+  if (coded) {
+    *payload_bytes = (int64_t)count[2];  // (the directory is not read here: the CPU's loads from page-locked memory are slow)
+    if (*payload_bytes > (int64_t)bound || *payload_bytes % 16 != 0) throw Error(FDH_ERR_HIP, "fdh_read_damage_coded: the encoder left no valid payload size");
+  }
+  consumed(F);
+  return n;
+}
+// what every read tells beside its buffers
+static void report(const ReadFrame& F, int n, int* n_tiles, int* frame_w, int* frame_h, int* full) {
+  const int nb = F.bins_x * F.bins_y;
+  if (n_tiles) *n_tiles = n;
+  if (frame_w) *frame_w = F.W;
+  if (frame_h) *frame_h = F.H;
+  if (full) *full = (nb > 0 && n == nb) ? 1 : 0;
+}
+void DamageReadback::read_raw(const ReadFrame& F, const FdhDamageTile** t, const uint8_t** px, int* n_tiles, int* frame_w, int* frame_h, int* full) {
+  const int n = read("fdh_read_damage", F, nullptr);
+  if (t) *t = tiles.ptr;
+  if (px) *px = pixels.ptr;
+  report(F, n, n_tiles, frame_w, frame_h, full);
+}
+void DamageReadback::read_coded(const ReadFrame& F, const FdhCodedTile** t, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w,
+                                int* frame_h, int* full) {
+  int64_t bytes = 0;
+  const int n = read("fdh_read_damage_coded", F, &bytes);
+  if (t) *t = dir.ptr;
+  if (payload) *payload = code.ptr;
+  if (payload_bytes) *payload_bytes = bytes;
+  report(F, n, n_tiles, frame_w, frame_h, full);
+}
+// Tiles cross the link at no more bytes than they hold, but reach the mirror through a second pass on the CPU (fdh_apply_damage out of
+// page-locked memory: ~0.7 - 1 us a tile), which a whole-frame copy into the caller's memory does not pay (~0.3 us a bin).  From
+// kReadbackWholeNum / kReadbackWholeDen of the grid on, the whole frame is the cheaper way to the same mirror
+// (profiles/damage_readback.txt: the crossover sits at 0.26 - 0.36 of the grid at 4K and 1080p).
+constexpr int kReadbackWholeNum = 3, kReadbackWholeDen = 10;
+void DamageReadback::read_into(const ReadFrame& F, uint8_t* image, int64_t pitch_bytes, int iw, int ih, int* n_tiles) {
+  bool every = false;
+  const int n = pending("fdh_read_damage_into", F, &every);
+  if (!image) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: null image");
+  if (iw != F.W || ih != F.H) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: the image is not the size of the last frame");
+  if (pitch_bytes < (int64_t)4 * iw) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: the pitch is shorter than a row");
+  const int nb = F.bins_x * F.bins_y;
+  if (n > 0 && (int64_t)n * kReadbackWholeDen >= (int64_t)nb * kReadbackWholeNum) {
+    FDH_HIP(hipMemcpy2D(image, (size_t)pitch_bytes, F.surf, (size_t)iw * 4, (size_t)iw * 4, (size_t)ih, hipMemcpyDeviceToHost));
+    consumed(F);
+  } else {
+    read("fdh_read_damage", F, nullptr);  // (the same n: nothing was submitted in between)
+    apply_damage(image, pitch_bytes, iw, ih, tiles.ptr, pixels.ptr, n);
+  }
+  if (n_tiles) *n_tiles = n;
+}
+
+// ------------------------------------------------------------------ host only: the receiver's side of both reads
+// is (x, y, tw, th) a bin clipped to an image of w x h pixels?
+static bool tile_in_image(int64_t x, int64_t y, int64_t tw, int64_t th, int w, int h) {
+  return tw >= 1 && tw <= FDH_TILE_PX && th >= 1 && th <= FDH_TILE_PX && x >= 0 && y >= 0 && x + tw <= w && y + th <= h;
+}
+void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles) {
+  if (n_tiles < 0) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: negative tile count");
+  if (w < 0 || h < 0 || pitch_bytes < (int64_t)4 * w) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: the pitch is shorter than a row");
+  if (n_tiles == 0) return;
+  if (!image || !tiles || !pixels) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: null image, tiles or pixels");
+  for (int i = 0; i < n_tiles; i++)  // every tile is checked before any byte is written
+    if (!tile_in_image(tiles[i].x, tiles[i].y, tiles[i].w, tiles[i].h, w, h))
+      throw Error(FDH_ERR_INVALID, "fdh_apply_damage: tile " + std::to_string(i) + " is not a bin inside the image");
+  for (int i = 0; i < n_tiles; i++) {
+    const FdhDamageTile& t = tiles[i];
+    const uint8_t* src = pixels + (size_t)i * FDH_TILE_BYTES;
+    for (int r = 0; r < t.h; r++) std::memcpy(image + (int64_t)(t.y + r) * pitch_bytes + (int64_t)4 * t.x, src + (size_t)r * FDH_TILE_PITCH, (size_t)4 * t.w);
+  }
+}
+
+namespace {
+inline uint32_t load32(const uint8_t* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
+inline uint16_t load16(const uint8_t* p) { uint16_t v; std::memcpy(&v, p, 2); return v; }
+inline int pal_bits(int n) { return n <= 2 ? 1 : n <= 4 ? 2 : n <= 16 ? 4 : 8; }
+
+// what (mode, n, w, h) give as the payload's size; the tile's fields are in range when this is called
+inline uint32_t coded_size(const FdhCodedTile& t) {
+  const uint32_t px = (uint32_t)t.w * (uint32_t)t.h;
+  switch (t.mode) {
+    case FDH_TILE_PAL: return 4u * t.n + 4u * ((px * (uint32_t)pal_bits(t.n) + 31u) / 32u);
+    case FDH_TILE_RUNS: return 4u * ((6u * t.n + 3u) / 4u);
+    case FDH_TILE_RAW: return 4u * px;
+    default: return 0;
+  }
+}
+// nullptr, or why tile t of a w x h image with payload_bytes of payload cannot be decoded
+const char* coded_tile_fault(const FdhCodedTile& t, int w, int h, const uint8_t* payload, int64_t payload_bytes) {
+  if (!tile_in_image(t.x, t.y, t.w, t.h, w, h)) return "is not a bin inside the image";
+  const uint32_t px = (uint32_t)t.w * (uint32_t)t.h;
+  if (t.mode > FDH_TILE_RAW) return "has an unknown mode";
+  if (t.mode == FDH_TILE_PAL) {
+    if (t.n < 1 || t.n > 256) return "has a palette of no or of more than 256 colours";
+    if (t.bits != pal_bits(t.n)) return "has bits that do not match its palette's size";
+  } else if (t.bits != 0) return "has bits outside PAL";
+  if (t.mode == FDH_TILE_RUNS && (t.n < 1 || t.n > px)) return "has no runs, or more runs than pixels";
+  if ((t.mode == FDH_TILE_SOLID || t.mode == FDH_TILE_RAW) && t.n != 0) return "has a count its mode does not use";
+  if (t.mode != FDH_TILE_SOLID && t.solid != 0) return "has a colour outside SOLID";
+  if (t.size != coded_size(t)) return "has a size that is not its mode's";
+  if (t.mode == FDH_TILE_SOLID) return t.offset != 0 ? "has an offset without a payload" : nullptr;
+  if (t.offset % 16 != 0) return "has an offset that is not a multiple of 16";
+  if ((int64_t)t.offset + (int64_t)t.size > payload_bytes) return "reaches beyond the payload";
+  const uint8_t* p = payload + t.offset;
+  if (t.mode == FDH_TILE_PAL) {
+    const uint8_t* idx = p + 4 * (size_t)t.n;
+    const uint32_t mask = (1u << t.bits) - 1u;
+    for (uint32_t i = 0; i < px; i++) {
+      const uint32_t at = i * t.bits;
+      if (((load32(idx + 4 * (size_t)(at >> 5)) >> (at & 31u)) & mask) >= t.n) return "has a palette index beyond its palette";
+    }
+  } else if (t.mode == FDH_TILE_RUNS) {
+    const uint8_t* len = p + 4 * (size_t)t.n;
+    uint64_t sum = 0;
+    for (uint32_t k = 0; k < t.n; k++) sum += (uint64_t)load16(len + 2 * (size_t)k) + 1u;
+    if (sum != px) return "has run lengths that do not sum to its pixels";
+  }
+  return nullptr;
+}
+}  // namespace
+
+void decode_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload, int64_t payload_bytes) {
+  if (n_tiles < 0) throw Error(FDH_ERR_INVALID, "fdh_decode_damage: negative tile count");
+  if (payload_bytes < 0) throw Error(FDH_ERR_INVALID, "fdh_decode_damage: negative payload size");
+  if (w < 0 || h < 0 || pitch_bytes < (int64_t)4 * w) throw Error(FDH_ERR_INVALID, "fdh_decode_damage: the pitch is shorter than a row");
+  if (n_tiles == 0) return;
+  if (!image || !tiles || (!payload && payload_bytes > 0)) throw Error(FDH_ERR_INVALID, "fdh_decode_damage: null image, tiles or payload");
+  for (int i = 0; i < n_tiles; i++)  // every tile is checked, its payload included, before any byte is written
+    if (const char* why = coded_tile_fault(tiles[i], w, h, payload, payload_bytes))
+      throw Error(FDH_ERR_INVALID, "fdh_decode_damage: tile " + std::to_string(i) + " " + why);
+  uint32_t px[FDH_TILE_PX * FDH_TILE_PX];  // a tile, tight
+  for (int i = 0; i < n_tiles; i++) {
+    const FdhCodedTile& t = tiles[i];
+    const uint32_t n_px = (uint32_t)t.w * (uint32_t)t.h;
+    const uint8_t* p = t.mode == FDH_TILE_SOLID ? nullptr : payload + t.offset;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(px);
+    if (t.mode == FDH_TILE_SOLID) {
+      for (uint32_t k = 0; k < n_px; k++) px[k] = t.solid;
+    } else if (t.mode == FDH_TILE_PAL) {
+      uint32_t pal[256];
+      std::memcpy(pal, p, 4 * (size_t)t.n);
+      const uint8_t* idx = p + 4 * (size_t)t.n;
+      const uint32_t bits = t.bits, mask = (1u << bits) - 1u, per = 32u / bits;
+      for (uint32_t k = 0; k < n_px; k += per) {  // a word of indices at a time
+        uint32_t v = load32(idx + 4 * (size_t)(k / per));
+        const uint32_t m = n_px - k < per ? n_px - k : per;
+        for (uint32_t j = 0; j < m; j++, v >>= bits) px[k + j] = pal[v & mask];
+      }
+    } else if (t.mode == FDH_TILE_RUNS) {
+      const uint8_t* len = p + 4 * (size_t)t.n;
+      uint32_t at = 0;
+      for (uint32_t k = 0; k < t.n; k++) {
+        const uint32_t c = load32(p + 4 * (size_t)k), m = (uint32_t)load16(len + 2 * (size_t)k) + 1u;
+        for (uint32_t j = 0; j < m; j++) px[at + j] = c;
+        at += m;
+      }
+    } else {
+      src = p;
+    }
+    for (int r = 0; r < t.h; r++) std::memcpy(image + (int64_t)(t.y + r) * pitch_bytes + (int64_t)4 * t.x, src + (size_t)r * 4 * t.w, (size_t)4 * t.w);
+  }
+}
+
+}  // namespace fdh

@@ -1,5 +1,6 @@
-// fdh_damage.h -- damage tracking (fdh_set_damage_tracking): the blur rule, ONE definition for the host (fdh_damage_closure, the CPU
-// tests) and the device (k_damage_resolve, k_damage.hip), and the parameter blocks of the tracking launches.
+// fdh_damage.h -- damage tracking (fdh_set_damage_tracking) and damage readback: the blur rule, ONE definition for the host
+// (fdh_damage_closure, the CPU tests) and the device (k_damage_resolve, k_damage.hip), the parameter blocks and launchers of the tracking
+// launches, the pending set's rule, and the host-only functions of fdh_damage.cpp.  The read kernels' blocks are fdh_damage_read.h's.
 //
 // A bin's pixels are a function of its (phase, bin) lists, the content of every listed draw and the frame-level state the host hashes
 // into its frame key -- except where a backdrop blur reads them: a blurred pixel depends on the PHASE-k intermediate over the node's
@@ -11,6 +12,10 @@
 #include <stdint.h>
 
 #include "fdh_kernels.h"
+#include "fdh_damage_read.h"  // the read kernels: k_damage_pack, k_damage_encode
+
+struct FdhDamageTile;  // include/figdraw_hip_readback.h
+struct FdhCodedTile;   // include/figdraw_hip_stream.h
 
 #if defined(__HIPCC__)
 #define FDH_HD __host__ __device__
@@ -120,35 +125,11 @@ void launch_composite_damage(hipStream_t s, const DrawRec* draws, const QuadExt*
 // k_damage_accumulate: ONE workgroup, after k_damage_resolve: stamps the bins of the frame's mask and leaves the number of pending bins
 // in *n_pending (page-locked host memory: the host reads it after the stream's synchronise and launches nothing when it is 0).
 void launch_damage_accumulate(hipStream_t s, const uint8_t* mask, uint32_t* stamp, uint32_t epoch, int bins, uint32_t* n_pending);
-// k_damage_pack: a workgroup per bin.  A pending bin's rank among the pending bins in row-major order is its slot: tiles[rank] = the
-// bin clipped to the frame (x, y, w, h), slot rank of `pixels` (16 KB: 64 rows of 256 bytes) = its pixels, zeros past the tile's edge.
-// `all`: every bin is pending whatever its stamp.  The last bin's workgroup leaves the number of tiles in *n_tiles.
-struct DamagePackParams {
-  const uint32_t* surf;    // the frame surface, pitch W pixels
-  const uint32_t* stamp;   // [bin]
-  uint8_t* pixels;         // [tile][64][256], 16-byte aligned
-  int4* tiles;             // [tile]
-  uint32_t* n_tiles;
-  uint32_t epoch;
-  int W, H, bins_x, bins_y, all;
-};
-void launch_damage_pack(hipStream_t s, const DamagePackParams& P);
-// k_damage_encode (k_damage_codec.hip; include/figdraw_hip_stream.h is the format): k_damage_pack's shape -- a workgroup per bin, rank
-// among the pending bins = directory slot, the last bin's workgroup leaves the number of tiles -- but a pending bin's workgroup codes its
-// tile in the cheapest of the four modes, claims the payload's space (its size rounded up to 16 bytes) with one atomic add on *cursor
-// (device memory, zeroed in stream order before the launch) and stores entry and payload.  The workgroup that makes the last of the
-// n_pending claims leaves the blob's size in *payload_bytes.
-struct DamageEncodeParams {
-  const uint32_t* surf;    // the frame surface, pitch W pixels
-  const uint32_t* stamp;   // [bin]
-  uint8_t* payload;        // bins * 16384 bytes, 16-byte aligned
-  uint2* dir;              // [tile] FdhCodedTile, 24 bytes each
-  uint32_t* n_tiles;
-  uint32_t* payload_bytes;
-  unsigned long long* cursor;
-  uint32_t epoch, n_pending;
-  int W, H, bins_x, bins_y, all;
-};
-void launch_damage_encode(hipStream_t s, const DamageEncodeParams& P);
+
+// Host only (fdh_damage.cpp): what fdh_damage_closure, fdh_apply_damage, fdh_decode_damage and fdh_coded_damage_bound run.
+void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out);
+void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles);
+void decode_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload, int64_t payload_bytes);
+int64_t coded_damage_bound(int w, int h);
 
 }  // namespace fdh

@@ -1,0 +1,61 @@
+// fdh_damage_host.h -- the host side of damage tracking and damage readback (fdh_damage.cpp): two components of a device context, each one
+// member of Context.  The context hands them its stream, the frame's LaunchJob and surface, and profile mode's bracket around a launch
+// of the bin kind (span(true) before it, span(false) after); they do not know the context.
+// A part of fdh_context.h, which includes it below DeviceBuf, PinnedBuf and LaunchJob: not a header to include on its own.
+#pragma once
+#include <functional>
+
+namespace fdh {
+
+using LaunchSpan = std::function<void(bool)>;
+struct DamageReadback;
+// Damage tracking (include/figdraw_hip_damage.h; submission side but for `on`): the per-bin signatures of the last tracked frame, what its
+// resolve left, and the footprint a fused V pass of a node that did not run writes over (k_damage_guard).
+struct DamageTracker {
+  bool on = false;                   // (calling thread: fdh_set_damage_tracking)
+  bool valid = false, last = false;  // the surface holds the frame of key `key` and the signatures are that frame's; the last launch was tracked
+  uint64_t key = 0;
+  int bins_x = 0, bins_y = 0;        // the grid the mask belongs to
+  DeviceBuf<uint64_t> sig;
+  DeviceBuf<uint8_t> changed, mask, run;
+  DeviceBuf<int> list;
+  DeviceBuf<uint32_t> count, keep;
+  // a frame's sign + resolve launches, behind its bin launch (B); its mask joins rb's pending set.  true: a partial frame
+  bool launch(hipStream_t s, const LaunchJob& J, const BinParams& B, DamageReadback& rb, const LaunchSpan& span);
+  void launched_whole(const LaunchJob& J);  // every launch of the frame is enqueued: the signatures are its
+  // the pair around the fused V pass of J's blur node `node` in a partial frame (rows y0 .. y1 of its footprint, in `surf`)
+  void guard(hipStream_t s, const LaunchJob& J, int node, bool restore, uint32_t* surf, int y0, int y1) const;
+  void composite(hipStream_t s, const LaunchJob& J, const CompositeParams& C) const;  // a partial frame's compositor launch, over the list
+  std::vector<uint8_t> bins(int gx, int gy, bool changed_only) const;  // fdh_damage_bins' mask of the last frame (the stream is idle)
+  void release();
+};
+// what a read needs of the context, whose stream is idle: the surface, size and grid of the last frame
+struct ReadFrame { hipStream_t stream; const uint32_t* surf; int W, H, bins_x, bins_y; };
+// Damage readback (include/figdraw_hip_readback.h, figdraw_hip_stream.h): the pending set (fdh_damage.h) and the page-locked buffers the
+// reads return.  `all`, `epoch`, `w`, `h`: written by whoever launches a frame (the submit thread, or replay's caller after a drain)
+// and by a read, which runs after the context's drain.
+struct DamageReadback {
+  bool on = false;     // (calling thread: fdh_set_damage_readback)
+  bool all = true;     // every bin is pending whatever the stamps say
+  uint32_t epoch = 1;  // the stamp of a pending bin
+  int w = 0, h = 0;    // the frame size the stamps describe
+  DeviceBuf<uint32_t> stamp, cursor;   // [bin]; k_damage_encode's claim counter
+  volatile uint32_t* count = nullptr;  // pinned, 3 words: pending bins after the last k_damage_accumulate; tiles of the last read; a coded read's payload bytes
+  PinnedBuf<uint8_t> pixels, code;     // what the reads return: [tile][64][256] with its tiles; the coded payload with its directory
+  PinnedBuf<FdhDamageTile> tiles;
+  PinnedBuf<FdhCodedTile> dir;
+  void turn(bool on_now, hipStream_t s);
+  void frame_whole() { if (on) all = true; }  // the frame composited every bin: no mask to accumulate, and no launch
+  void accumulate(hipStream_t s, const LaunchJob& J, const uint8_t* mask, const LaunchSpan& span);  // a tracked frame's mask joins the set
+  int pending(const char* who, const ReadFrame& F, bool* every) const;  // what a read starts with: this many bins of F are pending
+  void consumed(const ReadFrame& F);  // ... and ends with: the set is empty, the stamps are laid out for F's grid
+  // the one read routine: k_damage_pack into pixels / tiles, or (`payload_bytes`) k_damage_encode into code / dir.  Returns the tile count.
+  int read(const char* who, const ReadFrame& F, int64_t* payload_bytes);
+  // fdh_read_damage, fdh_read_damage_coded, fdh_read_damage_into
+  void read_raw(const ReadFrame& F, const FdhDamageTile** t, const uint8_t** px, int* n_tiles, int* frame_w, int* frame_h, int* full);
+  void read_coded(const ReadFrame& F, const FdhCodedTile** t, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w, int* frame_h, int* full);
+  void read_into(const ReadFrame& F, uint8_t* image, int64_t pitch_bytes, int iw, int ih, int* n_tiles);
+  void release();  // (the stream is idle)
+};
+
+}  // namespace fdh

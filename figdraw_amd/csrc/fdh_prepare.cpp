@@ -259,12 +259,12 @@ Context::FoldGuard Context::fold_clear(LaunchJob& J) {
 }
 
 // Damage tracking: the frame key -- everything a bin's pixels depend on besides its lists and the records they index.  A tracked frame
-// whose key differs from the last tracked frame's is rendered in full (Context::launch_damage), and so is one the tracking launches cannot
+// whose key differs from the last tracked frame's is rendered in full (DamageTracker::launch), and so is one the tracking launches cannot
 // take: no clear (its starting pixels are not this frame's to rebuild), a full-frame blur that renders out of place (k_blur_fx flips the
 // frame surface), more blur nodes than k_damage_resolve takes.  (atlas_epoch_ moves with every put, update, remove and reset: any atlas
 // change is a full frame, on purpose.)
 void Context::damage_frame_key(LaunchJob& J) const {
-  J.damage = damage_on_;
+  J.damage = damage_.on;
   J.damage_force = !clear_ || J.n_fused > 0 || J.blurs.size() > (size_t)kDamageMaxNodes;
   uint64_t k = 1469598103934665603ull;
   auto mix = [&k](uint64_t v) { for (int b = 0; b < 8; b++) { k ^= (v >> (8 * b)) & 255u; k *= 1099511628211ull; } };

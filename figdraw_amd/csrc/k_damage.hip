@@ -112,17 +112,6 @@ __global__ __launch_bounds__(256) void k_damage_guard(const uint8_t* __restrict_
   }
 }
 
-// the workgroup's sum of v (every thread gets it); s_part holds a word per wave
-__device__ __forceinline__ uint32_t workgroup_sum(uint32_t v, uint32_t* s_part) {
-#pragma unroll
-  for (int sh = 32; sh >= 1; sh >>= 1) v += __shfl_xor(v, sh, 64);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t sum = 0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); w++) sum += s_part[w];
-  return sum;
-}
-
 // Damage readback's per-frame launch (one workgroup): the frame's damaged bins become pending -- stamped with the epoch of the read that
 // will fetch them -- and the host finds the size of the pending set in *n_pending.
 __global__ __launch_bounds__(kResolveThreads) void k_damage_accumulate(const uint8_t* __restrict__ mask, uint32_t* __restrict__ stamp,
@@ -135,52 +124,38 @@ __global__ __launch_bounds__(kResolveThreads) void k_damage_accumulate(const uin
     else if (stamp[b] != epoch) continue;
     c++;
   }
-  c = workgroup_sum(c, s_part);
+  c = workgroup_sum<false>(c, s_part);
   if (threadIdx.x == 0) n_pending[0] = c;
 }
 
 // Damage readback's read: a workgroup per bin; those of bins that are not pending leave at once.  A tile is 64 rows of 256 contiguous
-// bytes = 1024 16-byte words, four per thread: consecutive threads take consecutive words of a surface row and of the slot.
+// bytes = 1024 16-byte words, four per thread, in the slot as tile_walk takes them from the surface (fdh_damage_read.h).
 constexpr int kPackThreads = 256;
 __global__ __launch_bounds__(kPackThreads) void k_damage_pack(const DamagePackParams P) {
   __shared__ uint32_t s_part[kPackThreads / 64];
   const int nb = P.bins_x * P.bins_y;
   const int bin = (int)blockIdx.x, t = (int)threadIdx.x;
   if (bin >= nb) return;
-  const bool last = bin == nb - 1;
-  const bool mine = P.all || P.stamp[bin] == P.epoch;
-  if (!mine && !last) return;
-  uint32_t rank = (uint32_t)bin;  // the pending bins ahead of this one, in row-major order
-  if (!P.all) {
-    uint32_t c = 0;
-    for (int b = t; b < bin; b += kPackThreads) c += P.stamp[b] == P.epoch ? 1u : 0u;
-    rank = workgroup_sum(c, s_part);
-  }
-  if (last && t == 0) P.n_tiles[0] = rank + (mine ? 1u : 0u);
-  if (!mine) return;
-  const int by = bin / P.bins_x, bx = bin - by * P.bins_x;
-  const int x0 = bx * kBin, y0 = by * kBin;
-  const int w = min(kBin, P.W - x0), h = min(kBin, P.H - y0);
-  if (t == 0) P.tiles[rank] = make_int4(x0, y0, w, h);
+  uint32_t rank;
+  if (!pending_slot<kPackThreads, false>(P.stamp, P.epoch, P.all, bin, nb, P.n_tiles, s_part, rank)) return;
+  const TileBox b = tile_box(bin, P.bins_x, P.W, P.H);
+  if (t == 0) P.tiles[rank] = make_int4(b.x0, b.y0, b.w, b.h);
   uint4* __restrict__ dst = reinterpret_cast<uint4*>(P.pixels + (size_t)rank * (kBin * kBin * 4));
   const bool rows_aligned = (P.W & 3) == 0;  // every surface row starts on a 16-byte boundary
-#pragma unroll
-  for (int k = 0; k < kBin * kBin / 4 / kPackThreads; k++) {
-    const int i = t + k * kPackThreads;
-    const int r = i >> 4, c = (i & 15) * 4;
+  // (captures by value: by reference the kernel takes 18 registers instead of 14)
+  tile_walk<kPackThreads>(P.surf, P.W, b, [=](int i, int, int c, bool inside, const uint32_t* __restrict__ src) {
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (r < h && c < w) {
-      const uint32_t* __restrict__ src = P.surf + (size_t)(y0 + r) * P.W + x0 + c;
-      if (rows_aligned && c + 4 <= w) v = *reinterpret_cast<const uint4*>(src);
+    if (inside) {
+      if (rows_aligned && c + 4 <= b.w) v = *reinterpret_cast<const uint4*>(src);
       else {
         v.x = src[0];
-        if (c + 1 < w) v.y = src[1];
-        if (c + 2 < w) v.z = src[2];
-        if (c + 3 < w) v.w = src[3];
+        if (c + 1 < b.w) v.y = src[1];
+        if (c + 2 < b.w) v.z = src[2];
+        if (c + 3 < b.w) v.w = src[3];
       }
     }
     dst[i] = v;
-  }
+  });
 }
 
 void launch_damage_accumulate(hipStream_t s, const uint8_t* mask, uint32_t* stamp, uint32_t epoch, int bins, uint32_t* n_pending) {
@@ -199,7 +174,7 @@ void launch_damage_sign(hipStream_t s, const DamageSignParams& P) {
   FDH_LAUNCH(k_damage_sign, dim3(nb), dim3(64), 0, s, P);
 }
 void launch_damage_resolve(hipStream_t s, const DamageResolveParams& P) {
-  if (P.bins_x * P.bins_y <= 0 || P.n_nodes < 0 || P.n_nodes > kDamageMaxNodes) return;  // (Context::launch_damage clamps n_nodes)
+  if (P.bins_x * P.bins_y <= 0 || P.n_nodes < 0 || P.n_nodes > kDamageMaxNodes) return;  // (DamageTracker::launch clamps n_nodes)
   FDH_LAUNCH(k_damage_resolve, dim3(1), dim3(kResolveThreads), 0, s, P);
 }
 void launch_damage_guard(hipStream_t s, const uint8_t* run, int node, bool restore, uint32_t* surf, uint32_t* keep, int pitch, int x0, int y0,

@@ -25,19 +25,6 @@ struct EncShared {
 
 __device__ __forceinline__ uint32_t enc_hash(uint32_t c) { return (c * 0x9E3779B1u) >> 22; }
 
-// the number of pending bins ahead (every thread gets the sum of v); part holds a word per wave
-__device__ __forceinline__ uint32_t enc_sum(uint32_t v, uint32_t* part) {
-#pragma unroll
-  for (int sh = 32; sh >= 1; sh >>= 1) v += __shfl_xor(v, sh, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t sum = 0;
-#pragma unroll
-  for (int w = 0; w < kEncThreads / 64; w++) sum += part[w];
-  __syncthreads();  // (part is used again)
-  return sum;
-}
-
 // Colour c joins the set.  Gives up once more than kEncMaxColours have arrived: every thread then has at most one insertion under way,
 // so no more than 2 * kEncMaxColours slots are taken and a probe always meets an empty one.
 __device__ __forceinline__ void enc_insert(EncShared& S, uint32_t c) {
@@ -82,40 +69,25 @@ __global__ __launch_bounds__(kEncThreads) void k_damage_encode(const DamageEncod
   const int nb = P.bins_x * P.bins_y;
   const int bin = (int)blockIdx.x, t = (int)threadIdx.x;
   if (bin >= nb) return;
-  const bool last = bin == nb - 1;
-  const bool mine = P.all || P.stamp[bin] == P.epoch;
-  if (!mine && !last) return;
-  uint32_t slot_dir = (uint32_t)bin;  // the pending bins ahead of this one, in row-major order
-  if (!P.all) {
-    uint32_t c = 0;
-    for (int b = t; b < bin; b += kEncThreads) c += P.stamp[b] == P.epoch ? 1u : 0u;
-    slot_dir = enc_sum(c, S.part);
-  }
-  if (last && t == 0) P.n_tiles[0] = slot_dir + (mine ? 1u : 0u);
-  if (!mine) return;
-  const int by = bin / P.bins_x, bx = bin - by * P.bins_x;
-  const int x0 = bx * kBin, y0 = by * kBin;
-  const int w = min(kBin, P.W - x0), h = min(kBin, P.H - y0);
+  uint32_t slot_dir;
+  if (!pending_slot<kEncThreads, true>(P.stamp, P.epoch, P.all, bin, nb, P.n_tiles, S.part, slot_dir)) return;
+  const TileBox box = tile_box(bin, P.bins_x, P.W, P.H);
+  const int x0 = box.x0, y0 = box.y0, w = box.w, h = box.h;
   const int n_px = w * h;
 
-  // 1. the tile, tight, into LDS: k_damage_pack's walk (consecutive threads take consecutive 16-byte words of a surface row)
+  // 1. the tile, tight, into LDS
   const bool rows_aligned = (P.W & 3) == 0;
-#pragma unroll
-  for (int k = 0; k < kBin * kBin / 4 / kEncThreads; k++) {
-    const int i = t + k * kEncThreads;
-    const int r = i >> 4, c = (i & 15) * 4;
-    if (r < h && c < w) {
-      const uint32_t* __restrict__ src = P.surf + (size_t)(y0 + r) * P.W + x0 + c;
-      uint32_t* d = S.buf + r * w + c;
-      if (rows_aligned && w == kBin) *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(src);
-      else {
-        d[0] = src[0];
-        if (c + 1 < w) d[1] = src[1];
-        if (c + 2 < w) d[2] = src[2];
-        if (c + 3 < w) d[3] = src[3];
-      }
+  tile_walk<kEncThreads>(P.surf, P.W, box, [&](int, int r, int c, bool inside, const uint32_t* __restrict__ src) {
+    if (!inside) return;
+    uint32_t* d = S.buf + r * w + c;
+    if (rows_aligned && w == kBin) *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(src);
+    else {
+      d[0] = src[0];
+      if (c + 1 < w) d[1] = src[1];
+      if (c + 2 < w) d[2] = src[2];
+      if (c + 3 < w) d[3] = src[3];
     }
-  }
+  });
   if (t == 0) { S.n_colours = 0; S.has_empty = 0; }
   __syncthreads();
 

@@ -20,10 +20,12 @@ struct uint2 { uint32_t x, y; };
 struct uint4 { uint32_t x, y, z, w; };
 struct int4 { int x, y, z, w; };
 inline uint2 make_uint2(uint32_t a, uint32_t b) { return {a, b}; }
+inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return {a, b, c, d}; }
 struct dim3 { int x; dim3(int v) : x(v) {} };
 typedef void* hipStream_t;
 struct Idx { int x; };
 inline thread_local Idx threadIdx, blockIdx;
+constexpr Idx blockDim{256};
 inline std::barrier<>* g_bar;
 inline uint32_t g_xchg[256];
 inline void __syncthreads() { g_bar->arrive_and_wait(); }
