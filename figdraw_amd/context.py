@@ -170,6 +170,10 @@ def load():
         L.fdh_decode_damage.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int64]
         L.fdh_coded_damage_bound.argtypes = [C.c_int, C.c_int]
         L.fdh_coded_damage_bound.restype = C.c_int64
+    # exact damage readback (include/figdraw_hip_exact.h; likewise)
+    if hasattr(L, "fdh_set_damage_exact"):
+        L.fdh_set_damage_exact.argtypes = [vp, C.c_int]
+        L.fdh_damage_exact_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     # picking (include/figdraw_hip_pick.h; likewise absent from older libraries)
     if hasattr(L, "fdh_set_pick"):
         L.fdh_set_pick.argtypes = [vp, C.c_int]
@@ -671,6 +675,20 @@ class HipContext:
     def coded_damage_bound(w: int, h: int) -> int:
         """an upper bound of a coded read's payload bytes for a w x h frame"""
         return int(load().fdh_coded_damage_bound(int(w), int(h)))
+
+    # ---- exact damage readback (include/figdraw_hip_exact.h)
+    def set_damage_exact(self, on: bool):
+        """a sub-mode of damage readback: every read first drops the pending bins whose pixels are what the last read left with the
+        application (a device mirror of that frame, one more buffer of the grid's size), so its tiles are exactly the bins that
+        changed.  Acts while damage readback is on; the first read afterwards is a fresh one.  Refused on record-only contexts."""
+        self._ck(self.L.fdh_set_damage_exact(self.h, 1 if on else 0))
+
+    def damage_exact_stats(self):
+        """the last read with exact damage readback on -> (n_pending: bins pending before the filter, n_changed: bins it kept,
+        fresh: the read filled the mirror and filtered nothing)"""
+        a, b, f = C.c_int(), C.c_int(), C.c_int()
+        self._ck(self.L.fdh_damage_exact_stats(self.h, C.byref(a), C.byref(b), C.byref(f)))
+        return a.value, b.value, bool(f.value)
 
     # ---- picking (include/figdraw_hip_pick.h)
     PICK_SHADOWS = 1  # FDH_PICK_SHADOWS

@@ -8,6 +8,7 @@
 #include "../../include/figdraw_hip_pick.h"
 #include "../../include/figdraw_hip_readback.h"
 #include "../../include/figdraw_hip_stream.h"
+#include "../../include/figdraw_hip_exact.h"
 
 using fdh::Context;
 
@@ -337,6 +338,11 @@ int fdh_decode_damage(uint8_t* image_rgba8, int64_t pitch_bytes, int w, int h, c
   return guard([&] { fdh::decode_damage(image_rgba8, pitch_bytes, w, h, tiles, n_tiles, payload, payload_bytes); });
 }
 int64_t fdh_coded_damage_bound(int w, int h) { return fdh::coded_damage_bound(w, h); }
+// exact damage readback (include/figdraw_hip_exact.h)
+int fdh_set_damage_exact(FdhContext* c, int on) { return guard([&] { C(c)->set_damage_exact(on != 0); }); }
+int fdh_damage_exact_stats(FdhContext* c, int* n_pending, int* n_changed, int* fresh) {
+  return guard([&] { C(c)->damage_exact_stats(n_pending, n_changed, fresh); });
+}
 int fdh_set_cull(FdhContext* c, int mode) { return guard([&] { C(c)->set_cull(mode); }); }
 int fdh_debug_host_times(FdhContext* c, int64_t out_ns[12]) {
   return guard([&] {

@@ -754,6 +754,17 @@ void Context::read_damage_into(uint8_t* image, int64_t pitch_bytes, int w, int h
 void Context::read_damage_coded(const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w, int* frame_h, int* full) {
   readback_.read_coded(read_frame("fdh_read_damage_coded"), tiles, payload, n_tiles, payload_bytes, frame_w, frame_h, full);
 }
+void Context::set_damage_exact(bool on) {
+  if (on && host_only_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_exact: a record-only context composites nothing");
+  if (host_only_) return;
+  drain();
+  FDH_HIP(hipSetDevice(device_));
+  readback_.turn_exact(on, stream_);
+}
+void Context::damage_exact_stats(int* n_pending, int* n_changed, int* fresh) {
+  drain();
+  readback_.exact_stats(n_pending, n_changed, fresh);
+}
 
 void Context::frame_device_ptr(void** p, int* w, int* h, int64_t* pitch_bytes) {
   need_device("frame_device_ptr");

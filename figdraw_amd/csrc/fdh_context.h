@@ -58,6 +58,15 @@ struct DeviceBuf {
     ptr = fresh;
     cap = want;
   }
+  void reserve_exact(size_t n) {  // no doubling: a block of tens of megabytes is the size that was asked for
+    if (n <= cap) return;
+    T* fresh = nullptr;
+    FDH_HIP(hipMalloc((void**)&fresh, n * sizeof(T)));
+    poison_fresh(fresh, n * sizeof(T));
+    if (ptr) (void)hipFree(ptr);
+    ptr = fresh;
+    cap = n;
+  }
   void release() {
     if (ptr) (void)hipFree(ptr);
     ptr = nullptr;
@@ -513,6 +522,8 @@ class Context : public Recorder {
   void read_damage(const FdhDamageTile** tiles, const uint8_t** pixels, int* n_tiles, int* frame_w, int* frame_h, int* full);
   void read_damage_into(uint8_t* image, int64_t pitch_bytes, int w, int h, int* n_tiles);
   void read_damage_coded(const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w, int* frame_h, int* full);
+  void set_damage_exact(bool on);
+  void damage_exact_stats(int* n_pending, int* n_changed, int* fresh);
   // picking (include/figdraw_hip_pick.h; fdh_pick.cpp)
   void set_pick(bool on) { pick_on_ = on; }
   void set_pick_tag(int32_t z, int32_t id) { tag_ = PickTag{z, id}; }

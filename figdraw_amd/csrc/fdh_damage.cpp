@@ -1,6 +1,6 @@
-// fdh_damage.cpp -- damage tracking, damage readback and coded damage readback on the host: the two components a device context holds
-// (DamageTracker, DamageReadback: fdh_damage_host.h) -- every launch of k_damage.hip and k_damage_codec.hip, the pending set, the
-// page-locked buffers a read returns -- and the host-only functions behind fdh_damage_closure, fdh_apply_damage, fdh_decode_damage and
+// fdh_damage.cpp -- damage tracking, damage readback, coded and exact damage readback on the host: the two components a device context holds
+// (DamageTracker, DamageReadback: fdh_damage_host.h) -- every launch of k_damage.hip, k_damage_codec.hip and k_damage_filter.hip, the
+// pending set, the page-locked buffers a read returns, exact mode's mirror -- and the host-only functions behind fdh_damage_closure, fdh_apply_damage, fdh_decode_damage and
 // fdh_coded_damage_bound.  What belongs to the context of an entry point (its refusals, the wait for the last frame) is fdh_context.cpp's.
 #include "fdh_context.h"
 #include "fdh_damage.h"
@@ -111,9 +111,11 @@ void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* r
   if (nb) std::memcpy(out, m.data(), nb);
 }
 
-// ------------------------------------------------------------------ damage readback (include/figdraw_hip_readback.h, figdraw_hip_stream.h)
+// ------------------------------------------------------------------ damage readback (include/figdraw_hip_readback.h, figdraw_hip_stream.h, figdraw_hip_exact.h)
 void DamageReadback::release() {
   pixels.release(); tiles.release(); code.release(); dir.release(); cursor.release(); stamp.release();
+  mirror.release(); arrivals.release();
+  mirror_valid = false;
   if (count) (void)hipHostFree((void*)count);
   count = nullptr;
 }
@@ -124,6 +126,7 @@ void DamageReadback::turn(bool on_now, hipStream_t s) {
       count[0] = count[1] = 0;
     }
     all = true;  // what the application holds is unknown: the first read brings every bin
+    mirror_valid = have_stats = false;
   }
   if (!on_now && on) {
     FDH_HIP(hipStreamSynchronize(s));
@@ -138,6 +141,22 @@ void DamageReadback::accumulate(hipStream_t s, const LaunchJob& J, const uint8_t
   const int nb = J.bins_x * J.bins_y;
   if (all || w != J.W || h != J.H || stamp.cap < (size_t)nb) all = true;
   else { span(true); launch_damage_accumulate(s, mask, stamp.ptr, epoch, nb, const_cast<uint32_t*>(count)); span(false); }
+}
+// exact mode keeps its flag while readback is off; the mirror lives only while both are on
+void DamageReadback::turn_exact(bool on_now, hipStream_t s) {
+  if (on_now && !exact) mirror_valid = have_stats = false;
+  if (!on_now && exact) {
+    if (mirror.ptr) FDH_HIP(hipStreamSynchronize(s));
+    mirror.release(); arrivals.release();
+    mirror_valid = false;
+  }
+  exact = on_now;
+}
+void DamageReadback::exact_stats(int* n_pending, int* n_changed, int* fresh) const {
+  if (!have_stats) throw Error(FDH_ERR_INVALID, "fdh_damage_exact_stats: no read with exact damage readback on yet (fdh_set_damage_exact)");
+  if (n_pending) *n_pending = stat_pending;
+  if (n_changed) *n_changed = stat_changed;
+  if (fresh) *fresh = stat_fresh;
 }
 int DamageReadback::pending(const char* who, const ReadFrame& F, bool* every) const {
   const int nb = F.bins_x * F.bins_y;
@@ -162,18 +181,72 @@ int64_t coded_damage_bound(int w, int h) {
   if (w <= 0 || h <= 0) return 0;
   return (int64_t)((w + FDH_TILE_PX - 1) / FDH_TILE_PX) * ((h + FDH_TILE_PX - 1) / FDH_TILE_PX) * FDH_TILE_BYTES;
 }
+void DamageReadback::lost() {
+  mirror_valid = false;
+  all = true;
+}
+// The first read after the mirror became invalid (the mode or readback turned on, another frame size, a lost read) is a fresh one: the
+// pending set passes unfiltered, and the mirror takes the whole surface in one launch (k_damage_filter's fill form: the tile-major copy).
+// Every other read costs one launch and one synchronise in front of pack / encode: the host needs the count for the tile count, for
+// the check of the buffers and for fdh_read_damage_into's choice.
+int DamageReadback::filter(const char* who, const ReadFrame& F, int n, bool* every) {
+  if (!exact) return n;
+  stat_pending = stat_changed = n; stat_fresh = 0;
+  have_stats = true;
+  if (n <= 0) return n;
+  const int nb = F.bins_x * F.bins_y;
+  const bool fresh = !mirror_valid || mirror_w != F.W || mirror_h != F.H;
+  try {
+    mirror_valid = false;
+    mirror.reserve_exact((size_t)nb * (kBin * kBin));  // (the stream is idle: a block that grows may be freed)
+    arrivals.reserve(1);
+    if (*every) stamp.reserve((size_t)nb);  // (every workgroup writes its stamp: none needs a value first)
+    uint32_t* const words = const_cast<uint32_t*>(count);
+    DamageFilterParams P;
+    P.surf = F.surf; P.mirror = mirror.ptr; P.stamp = stamp.ptr; P.arrivals = arrivals.ptr; P.n_changed = words + 3;
+    P.epoch = epoch; P.n_pending = (uint32_t)n; P.W = F.W; P.H = F.H; P.bins_x = F.bins_x; P.bins_y = F.bins_y;
+    P.all = (fresh || *every) ? 1 : 0; P.fill = fresh ? 1 : 0;
+    if (fresh) {
+      launch_damage_filter(F.stream, P);
+      FDH_HIP(hipGetLastError());
+      mirror_valid = true; mirror_w = F.W; mirror_h = F.H;
+      stat_fresh = 1;
+      return n;
+    }
+    count[3] = 0xFFFFFFFFu;
+    FDH_HIP(hipMemsetAsync(arrivals.ptr, 0, sizeof(unsigned long long), F.stream));
+    launch_damage_filter(F.stream, P);
+    FDH_HIP(hipGetLastError());
+    FDH_HIP(hipStreamSynchronize(F.stream));
+    const uint32_t kept = count[3];
+    if (kept > (uint32_t)n) throw Error(FDH_ERR_HIP, std::string(who) + ": the filter left no valid count");
+    mirror_valid = true;
+    *every = false;  // the set lives in the stamps from here on
+    stat_changed = (int)kept;
+    if (kept == 0) consumed(F);
+    return (int)kept;
+  } catch (...) {
+    lost();
+    throw;
+  }
+}
 // Both buffers of a read hold the whole grid's worst case, exactly (doubled, a 4K frame's 33.4 MB would become 64): a read of n tiles
 // never moves them, so the pointers of the other kind of read stay where they are.
 int DamageReadback::read(const char* who, const ReadFrame& F, int64_t* payload_bytes) {
   const bool coded = payload_bytes != nullptr;
   bool every = false;
-  const int n = pending(who, F, &every);
-  const int nb = F.bins_x * F.bins_y;
-  const size_t bound = (size_t)coded_damage_bound(F.W, F.H);  // (= nb tiles of FDH_TILE_BYTES)
-  if (coded && (F.W > INT16_MAX || F.H > INT16_MAX || bound > (size_t)UINT32_MAX))
+  int n = pending(who, F, &every);
+  if (coded && (F.W > INT16_MAX || F.H > INT16_MAX || (size_t)coded_damage_bound(F.W, F.H) > (size_t)UINT32_MAX))
     throw Error(FDH_ERR_INVALID, "fdh_read_damage_coded: a directory entry holds coordinates up to 32767 and offsets of 32 bits");
   if (coded) *payload_bytes = 0;
+  n = filter(who, F, n, &every);
   if (n <= 0) return n;
+  return fetch(who, F, n, every, payload_bytes);
+}
+int DamageReadback::fetch(const char* who, const ReadFrame& F, int n, bool every, int64_t* payload_bytes) try {
+  const bool coded = payload_bytes != nullptr;
+  const int nb = F.bins_x * F.bins_y;
+  const size_t bound = (size_t)coded_damage_bound(F.W, F.H);  // (= nb tiles of FDH_TILE_BYTES)
   uint32_t* const words = const_cast<uint32_t*>(count);
   count[1] = count[2] = 0xFFFFFFFFu;
   if (coded) {
@@ -204,6 +277,9 @@ int DamageReadback::read(const char* who, const ReadFrame& F, int64_t* payload_b
   }
   consumed(F);
   return n;
+} catch (...) {
+  if (exact) lost();  // the filter has run: the mirror holds tiles the application never got
+  throw;
 }
 // what every read tells beside its buffers
 static void report(const ReadFrame& F, int n, int* n_tiles, int* frame_w, int* frame_h, int* full) {
@@ -235,16 +311,20 @@ void DamageReadback::read_coded(const ReadFrame& F, const FdhCodedTile** t, cons
 constexpr int kReadbackWholeNum = 3, kReadbackWholeDen = 10;
 void DamageReadback::read_into(const ReadFrame& F, uint8_t* image, int64_t pitch_bytes, int iw, int ih, int* n_tiles) {
   bool every = false;
-  const int n = pending("fdh_read_damage_into", F, &every);
+  int n = pending("fdh_read_damage_into", F, &every);
   if (!image) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: null image");
   if (iw != F.W || ih != F.H) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: the image is not the size of the last frame");
   if (pitch_bytes < (int64_t)4 * iw) throw Error(FDH_ERR_INVALID, "fdh_read_damage_into: the pitch is shorter than a row");
   const int nb = F.bins_x * F.bins_y;
+  n = filter("fdh_read_damage_into", F, n, &every);  // (exact mode: the rule below weighs what is left; the mirror is already the frame)
   if (n > 0 && (int64_t)n * kReadbackWholeDen >= (int64_t)nb * kReadbackWholeNum) {
-    FDH_HIP(hipMemcpy2D(image, (size_t)pitch_bytes, F.surf, (size_t)iw * 4, (size_t)iw * 4, (size_t)ih, hipMemcpyDeviceToHost));
+    if (hipError_t e = hipMemcpy2D(image, (size_t)pitch_bytes, F.surf, (size_t)iw * 4, (size_t)iw * 4, (size_t)ih, hipMemcpyDeviceToHost)) {
+      if (exact) lost();
+      FDH_HIP(e);
+    }
     consumed(F);
   } else {
-    read("fdh_read_damage", F, nullptr);  // (the same n: nothing was submitted in between)
+    if (n > 0) fetch("fdh_read_damage", F, n, every, nullptr);
     apply_damage(image, pitch_bytes, iw, ih, tiles.ptr, pixels.ptr, n);
   }
   if (n_tiles) *n_tiles = n;

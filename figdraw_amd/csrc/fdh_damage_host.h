@@ -31,8 +31,8 @@ struct DamageTracker {
 };
 // what a read needs of the context, whose stream is idle: the surface, size and grid of the last frame
 struct ReadFrame { hipStream_t stream; const uint32_t* surf; int W, H, bins_x, bins_y; };
-// Damage readback (include/figdraw_hip_readback.h, figdraw_hip_stream.h): the pending set (fdh_damage.h) and the page-locked buffers the
-// reads return.  `all`, `epoch`, `w`, `h`: written by whoever launches a frame (the submit thread, or replay's caller after a drain)
+// Damage readback (include/figdraw_hip_readback.h, figdraw_hip_stream.h, figdraw_hip_exact.h): the pending set (fdh_damage.h), the
+// page-locked buffers the reads return and, in exact mode, the device mirror of what the application holds.  `all`, `epoch`, `w`, `h`: written by whoever launches a frame (the submit thread, or replay's caller after a drain)
 // and by a read, which runs after the context's drain.
 struct DamageReadback {
   bool on = false;     // (calling thread: fdh_set_damage_readback)
@@ -44,13 +44,28 @@ struct DamageReadback {
   PinnedBuf<uint8_t> pixels, code;     // what the reads return: [tile][64][256] with its tiles; the coded payload with its directory
   PinnedBuf<FdhDamageTile> tiles;
   PinnedBuf<FdhCodedTile> dir;
+  // exact mode (fdh_set_damage_exact; acts while `on`): the frame as of the last read, tile-major [bin][64][64], valid for a frame of
+  // mirror_w x mirror_h; k_damage_filter's arrival counter; what fdh_damage_exact_stats tells of the last read
+  bool exact = false, mirror_valid = false, have_stats = false;
+  int mirror_w = 0, mirror_h = 0;
+  DeviceBuf<uint32_t> mirror;
+  DeviceBuf<unsigned long long> arrivals;
+  int stat_pending = 0, stat_changed = 0, stat_fresh = 0;
   void turn(bool on_now, hipStream_t s);
+  void turn_exact(bool on_now, hipStream_t s);
+  void exact_stats(int* n_pending, int* n_changed, int* fresh) const;
   void frame_whole() { if (on) all = true; }  // the frame composited every bin: no mask to accumulate, and no launch
   void accumulate(hipStream_t s, const LaunchJob& J, const uint8_t* mask, const LaunchSpan& span);  // a tracked frame's mask joins the set
   int pending(const char* who, const ReadFrame& F, bool* every) const;  // what a read starts with: this many bins of F are pending
   void consumed(const ReadFrame& F);  // ... and ends with: the set is empty, the stamps are laid out for F's grid
-  // the one read routine: k_damage_pack into pixels / tiles, or (`payload_bytes`) k_damage_encode into code / dir.  Returns the tile count.
+  // exact mode's step between pending() and fetch(): n bins of F are pending (`*every`: all of them, whatever the stamps say) -> the
+  // number that stay pending, which the stamps then hold (*every = false).  A fresh read fills the mirror and returns n.  Mode off: n.
+  int filter(const char* who, const ReadFrame& F, int n, bool* every);
+  void lost();  // exact mode: a read failed after the filter ran -- the mirror is invalid, every bin is pending
+  // the one read routine: pending(), filter(), fetch().  Returns the tile count.
   int read(const char* who, const ReadFrame& F, int64_t* payload_bytes);
+  // its last step, over n > 0 pending bins: k_damage_pack into pixels / tiles, or (`payload_bytes`) k_damage_encode into code / dir; consumed()
+  int fetch(const char* who, const ReadFrame& F, int n, bool every, int64_t* payload_bytes);
   // fdh_read_damage, fdh_read_damage_coded, fdh_read_damage_into
   void read_raw(const ReadFrame& F, const FdhDamageTile** t, const uint8_t** px, int* n_tiles, int* frame_w, int* frame_h, int* full);
   void read_coded(const ReadFrame& F, const FdhCodedTile** t, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w, int* frame_h, int* full);

@@ -1,5 +1,5 @@
-// fdh_damage_read.h -- damage readback's read kernels (k_damage_pack in k_damage.hip, k_damage_encode in k_damage_codec.hip): their
-// parameter blocks, and the device code the two share.  Included through fdh_damage.h; it names nothing but kBin, the vector types and
+// fdh_damage_read.h -- damage readback's read kernels (k_damage_pack in k_damage.hip, k_damage_encode in k_damage_codec.hip, and
+// k_damage_filter in k_damage_filter.hip, which runs in front of either): their parameter blocks, and the device code they share.  Included through fdh_damage.h; it names nothing but kBin, the vector types and
 // hipStream_t, so the host shim of tests/codec_emu compiles against this very file.
 #pragma once
 #include <stdint.h>
@@ -35,6 +35,23 @@ struct DamageEncodeParams {
   int W, H, bins_x, bins_y, all;
 };
 void launch_damage_encode(hipStream_t s, const DamageEncodeParams& P);
+// k_damage_filter (k_damage_filter.hip; include/figdraw_hip_exact.h): the launch in front of either read when exact damage readback is
+// on.  k_damage_pack's shape; a pending bin's workgroup compares its tile with the mirror's -- the frame as the application last read it,
+// tile-major: slot `bin` is k_damage_pack's slot of that bin, zeros past the tile's edge -- and leaves the bin pending (stamp = epoch)
+// with the mirror updated when they differ, not pending (stamp = epoch - 1) when they are equal.  Each workgroup reads and writes its
+// own stamp only.  `all`: every bin is pending whatever its stamp, and every bin's stamp is written.  The workgroup that is the last of
+// the n_pending to arrive at *arrivals (device memory, zeroed in stream order before the launch) leaves the number of bins that stay
+// pending in *n_changed.  `fill`: no compare, no stamp, no count -- every tile is stored into the mirror (with `all`: a fresh read).
+struct DamageFilterParams {
+  const uint32_t* surf;    // the frame surface, pitch W pixels
+  uint32_t* mirror;        // [bin][64][64], 16-byte aligned
+  uint32_t* stamp;         // [bin]
+  unsigned long long* arrivals;
+  uint32_t* n_changed;
+  uint32_t epoch, n_pending;
+  int W, H, bins_x, bins_y, all, fill;
+};
+void launch_damage_filter(hipStream_t s, const DamageFilterParams& P);
 
 #if defined(__device__)  // (a macro under hipcc and under the shim)
 // the workgroup's sum of v (every thread gets it); part holds a word per wave.  kReuse: the caller writes part again afterwards, so a

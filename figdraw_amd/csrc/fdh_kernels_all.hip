@@ -8,3 +8,4 @@
 #include "k_damage.hip"
 #include "k_pick.hip"
 #include "k_damage_codec.hip"
+#include "k_damage_filter.hip"
