@@ -348,11 +348,13 @@ class HipContext:
         self._ck(self.L.fdh_put_image(self.h, int(key), rgba.shape[1], rgba.shape[0], rgba.ctypes.data, out))
         return tuple(out)
 
-    def put_glyph_outline(self, key, segs: np.ndarray, w: int, h: int, lcd_filter: bool = False):
-        """rasterise a glyph outline (n x 6: x0, y0, cx, cy, x1, y1; cx = NaN for a line) on the device into the atlas"""
+    def put_glyph_outline(self, key, segs: np.ndarray, w: int, h: int, lcd_filter: bool = False, mtsdf: bool = False, sdf_range: int = 0):
+        """a glyph outline (n x 6: x0, y0, cx, cy, x1, y1; cx = NaN for a line) into the atlas, made on the device: coverage, or with
+        mtsdf=True a multi-channel + true signed distance field of `sdf_range` texels (0: 4) for draw_msdf (FDH_GLYPH_MTSDF)"""
         segs = np.ascontiguousarray(segs, dtype=np.float32).reshape(-1, 6)
         out = (C.c_int * 4)()
-        self._ck(self.L.fdh_put_glyph_outline(self.h, int(key), int(w), int(h), segs.ctypes.data, len(segs), 1 if lcd_filter else 0, out))
+        flags = (1 if lcd_filter else 0) | (4 if mtsdf else 0) | (int(sdf_range) << 8)
+        self._ck(self.L.fdh_put_glyph_outline(self.h, int(key), int(w), int(h), segs.ctypes.data, len(segs), flags, out))
         return tuple(out)
 
     def put_glyph_image(self, key, rgba: np.ndarray, lcd_filter=False):
@@ -417,8 +419,12 @@ class HipContext:
         return json.loads(self.L.fdh_record_json(self.h).decode())
 
     def debug_read_surface(self, which: int) -> np.ndarray:
-        """0: frame, 1: horizontal blur pass output, 2: blurred snapshot (diagnostic)"""
-        out = np.zeros((self.H, self.W, 4), dtype=np.uint8)
+        """0: frame, 1: horizontal blur pass output, 2: blurred snapshot, 4: level 0 of the atlas, atlas_size x atlas_size (diagnostic)"""
+        if which == 4:
+            s = self.atlas_size()
+            out = np.zeros((s, s, 4), dtype=np.uint8)
+        else:
+            out = np.zeros((self.H, self.W, 4), dtype=np.uint8)
         self._ck(self.L.fdh_debug_read_surface(self.h, which, out.ctypes.data))
         return out
 

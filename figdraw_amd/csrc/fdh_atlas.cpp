@@ -1,5 +1,6 @@
 // fdh_atlas.cpp -- the image atlas: skyline packer, level chains, glyph images and outlines, the Flippy container.
 #include "fdh_context.h"
+#include "fdh_msdf_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -198,7 +199,14 @@ static int flatten_count(const float* q) {
 void Context::put_glyph_outline(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) {
   if (w <= 0 || h <= 0 || w > 4096 || h > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_outline: image size must be in 1..4096");
   if (n < 0 || (n > 0 && !segs)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: bad outline");
-  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: unknown flag");
+  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT | FDH_GLYPH_MTSDF | 0xFF00u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: unknown flag");
+  const uint32_t sdf_range = (flags >> 8) & 255u;
+  if (sdf_range && (!(flags & FDH_GLYPH_MTSDF) || sdf_range > 64u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance range needs FDH_GLYPH_MTSDF and is at most 64");
+  if (flags & FDH_GLYPH_MTSDF) {
+    if (flags & (FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field takes no LCD filter");
+    put_glyph_mtsdf(key, w, h, segs, n, sdf_range ? (float)sdf_range : 4.0f, out_rect);
+    return;
+  }
   if (flags & FDH_GLYPH_LCD_CONTEXT) flags = text_lcd_filtering_ ? FDH_GLYPH_LCD_FILTER : 0u;
   std::vector<float> lines;
   lines.reserve((size_t)n * 16);
@@ -231,6 +239,31 @@ void Context::put_glyph_outline(int64_t key, int w, int h, const float* segs, in
   if (m) FDH_HIP(hipMemcpyAsync(glyph_lines_.ptr, lines.data(), lines.size() * sizeof(float), hipMemcpyHostToDevice, stream_));
   launch_rasterize_lines(stream_, reinterpret_cast<const float4*>(glyph_lines_.ptr), (int)m, w, h, glyph_acc_.ptr, glyph_a_.ptr);
   glyph_to_atlas(glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, flags);  // (synchronises: `lines` stays alive until then)
+}
+// fdh_put_glyph_outline with FDH_GLYPH_MTSDF (the specification: include/figdraw_hip.h at that flag).  The host makes contours, the
+// orientation and the coloured edges (fdh_msdf_host.h), the device the texels (k_msdf_generate): one copy, one launch, then the level
+// chain every glyph image takes.  Nothing is premultiplied and nothing filtered: the four bytes of a texel are four distances.
+void Context::put_glyph_mtsdf(int64_t key, int w, int h, const float* segs, int n, float range, int out_rect[4]) {
+  if (n > msdf::kMaxSegments) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field takes at most 65535 segments");
+  msdf::Shape shape;
+  if (!msdf::build_shape(segs, n, &shape)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field needs closed contours");
+  int x, y;
+  find_empty_rect(w, h, &x, &y);
+  entries_[key] = AtlasEntry{x, y, w, h, false, {}, {}};
+  atlas_epoch_++;
+  if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
+  if (host_only_) return;
+  FDH_HIP(hipSetDevice(device_));
+  sync();  // a frame in flight may still sample the atlas
+  std::vector<float> rec;
+  msdf::edge_records(shape, &rec);
+  const size_t npx = (size_t)w * h;
+  glyph_a_.reserve(npx);
+  glyph_b_.reserve(npx);
+  glyph_edges_.reserve(std::max<size_t>(rec.size(), msdf::kEdgeFloats));
+  if (!rec.empty()) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, stream_));
+  launch_msdf_generate(stream_, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, glyph_a_.ptr);
+  glyph_to_atlas(glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
 }
 // Flippy: figdraw's mip-mapped image container (common/formatflippy.nim:77-149).  Layout: "flip", u32 version (1), then per
 // mip level "mip!", u32 width, u32 height, u32 zlen, and a raw-snappy block holding straight RGBA8.  The reference

@@ -704,7 +704,8 @@ class Context : public Recorder {
   uint32_t* alt_ = nullptr;  // second frame surface: a fused full-frame blur renders out of place, phases alternate between fb_ and this
   uint32_t* dbg_snap_ = nullptr;
   void glyph_to_atlas(uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags);
-  DeviceBuf<float> glyph_lines_, glyph_acc_;
+  void put_glyph_mtsdf(int64_t key, int w, int h, const float* segs, int n, float range, int out_rect[4]);
+  DeviceBuf<float> glyph_lines_, glyph_acc_, glyph_edges_;  // (glyph_edges_: the edge records of a distance-field put, fdh_msdf_host.h)
   DeviceBuf<uint32_t> glyph_a_, glyph_b_;  // put_glyph_image: the raster and its filtered / minified successors
   RetainedScene retained_;
   uint64_t atlas_epoch_ = 1;

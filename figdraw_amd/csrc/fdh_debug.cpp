@@ -150,6 +150,12 @@ void Context::debug_bin_digest(uint64_t out[8]) {
 void Context::debug_read_surface(int which, uint8_t* out) {
   need_device("debug_read_surface");
   drain();
+  if (which == 4) {  // level 0 of the atlas, atlas_size x atlas_size
+    FDH_HIP(hipSetDevice(device_));
+    FDH_HIP(hipStreamSynchronize(stream_));
+    FDH_HIP(hipMemcpy(out, atlas_levels_[0], (size_t)atlas_size_ * atlas_size_ * 4, hipMemcpyDeviceToHost));
+    return;
+  }
   const uint32_t* src = which == 0 ? fb_ : which == 1 ? blur_tmp_ : which == 2 ? backdrop_ : which == 3 ? dbg_snap_ : nullptr;
   if (!src) throw Error(FDH_ERR_INVALID, "debug_read_surface: no such surface (or no frame yet)");
   FDH_HIP(hipSetDevice(device_));

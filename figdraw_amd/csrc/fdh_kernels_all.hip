@@ -9,3 +9,4 @@
 #include "k_pick.hip"
 #include "k_damage_codec.hip"
 #include "k_damage_filter.hip"
+#include "k_msdf.hip"

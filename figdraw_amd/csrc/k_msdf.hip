@@ -1,0 +1,175 @@
+// k_msdf.hip -- distance-field generation: fdh_put_glyph_outline with FDH_GLYPH_MTSDF (the specification is the comment at that flag in
+// include/figdraw_hip.h; this file is its step 4).  The host has split the outline into coloured edges (fdh_msdf_host.h); here one lane
+// owns one texel, one wave an 8 x 8 tile of them, and walks every edge.  The edge records are wave-uniform -- their index is the loop
+// counter -- so they arrive through scalar loads and what depends on the edge alone costs nothing per lane.  A lane keeps four running
+// candidates (the channels R, G, B and the true distance): squared distance, orthogonality, edge and parameter; signs and
+// pseudo-distances are made once, after the loop, from the winners.
+#include "fdh_device.h"
+#include "fdh_msdf_host.h"
+
+namespace fdh {
+
+#ifndef FDH_MSDF_NO_CULL
+#define FDH_MSDF_NO_CULL 0  // tools/msdf_bench.py's second build: every tile walks every edge
+#endif
+
+// E = B(t) - p and the tangent direction at t of edge r, t in [0, 1]; at t = 0 and t = 1 the point IS the stored end, so that the two
+// edges that meet in a corner give a texel beyond it bit-identical distances (the tie the orthogonality then breaks)
+__device__ __forceinline__ void msdf_at(const float* __restrict__ r, float t, float px, float py, float& Ex, float& Ey, float& Tx, float& Ty) {
+#pragma clang fp contract(off)
+  const float dx = r[0] - px, dy = r[1] - py;
+  float ex, ey;
+  if (r[7] == 0.0f) {  // a line: P0 + e t
+    ex = dx + r[8] * t; ey = dy + r[9] * t;
+    Tx = r[8]; Ty = r[9];
+  } else {
+    ex = dx + (2.0f * r[8] + r[10] * t) * t; ey = dy + (2.0f * r[9] + r[11] * t) * t;
+    Tx = r[8] + r[10] * t; Ty = r[9] + r[11] * t;
+  }
+  const float e1x = r[4] - px, e1y = r[5] - py;
+  Ex = t <= 0.0f ? dx : (t >= 1.0f ? e1x : ex);
+  Ey = t <= 0.0f ? dy : (t >= 1.0f ? e1y : ey);
+}
+__device__ __forceinline__ float msdf_d2(const float* __restrict__ r, float t, float px, float py) {
+  float Ex, Ey, Tx, Ty;
+  msdf_at(r, t, px, py, Ex, Ey, Tx, Ty);
+  return Ex * Ex + Ey * Ey;
+}
+// the parameter of the point of edge r nearest to p.  A quadratic: the closed-form solve of sd_bezierN (fdh_device.h) -- both cases
+// evaluated, one selected -- which leaves a distance; here the parameter is the product, and it has to be good: the comparison is
+// with a float64 reference, and the one-root case cancels (see the comment in sd_bezierN: IEEE division and square root, nothing
+// contracted, up to the roots).  What the cancellation still costs is mended by two Newton steps on the geometric form
+// g(t) = E(t) . T(t), whose rounding error does not grow with the cubic's coefficients; a step is kept only if it came nearer.
+__device__ __forceinline__ float msdf_nearest_t(const float* __restrict__ r, float px, float py) {
+#pragma clang fp contract(off)
+  const float dx = r[0] - px, dy = r[1] - py;
+  if (r[7] == 0.0f) return clamp01(-(dx * r[8] + dy * r[9]) * r[12]);  // wave-uniform
+  const float ax = r[8], ay = r[9], bx = r[10], by = r[11], kk = r[12], kx = r[13], aa2 = r[14];
+  const float ky = kk * (aa2 + (dx * bx + dy * by)) / 3.0f;
+  const float kz = kk * (dx * ax + dy * ay);
+  const float p = ky - kx * kx;
+  const float p3 = p * p * p;
+  const float q = kx * (2.0f * kx * kx - 3.0f * ky) + kz;
+  const float h = q * q + 4.0f * p3;
+  // h >= 0: one real root
+  const float hs = __builtin_sqrtf(__builtin_fmaxf(h, 0.0f));
+  const float tA = cbrt_signed((hs - q) * 0.5f) + cbrt_signed((-hs - q) * 0.5f) - kx;
+  // h < 0 (then p < 0): three, the outer two are minima
+  const float z = __builtin_sqrtf(__builtin_fmaxf(-p, 0.0f));
+  const float den = p * z * 2.0f;
+  const float arg = __builtin_fminf(__builtin_fmaxf(q / (den == 0.0f ? 1.0f : den), -1.0f), 1.0f);
+  const float v = acos_poly(den == 0.0f ? 0.0f : arg) * (1.0f / 3.0f);
+  const float v2 = v * v;
+  float cm = -1.0f / 3628800.0f, sn = -1.0f / 39916800.0f;
+  cm = __builtin_fmaf(cm, v2, 1.0f / 40320.0f); cm = __builtin_fmaf(cm, v2, -1.0f / 720.0f); cm = __builtin_fmaf(cm, v2, 1.0f / 24.0f); cm = __builtin_fmaf(cm, v2, -0.5f); cm = __builtin_fmaf(cm, v2, 1.0f);
+  sn = __builtin_fmaf(sn, v2, 1.0f / 362880.0f); sn = __builtin_fmaf(sn, v2, -1.0f / 5040.0f); sn = __builtin_fmaf(sn, v2, 1.0f / 120.0f); sn = __builtin_fmaf(sn, v2, -1.0f / 6.0f); sn = __builtin_fmaf(sn, v2, 1.0f);
+  const float m = cm, n = sn * v * 1.732050808f;
+  const float t1 = (m + m) * z - kx, t2 = (-n - m) * z - kx;
+  float best_t = 0.0f, best_d2 = 3.0e38f;
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const float t0 = h >= 0.0f ? tA : (k == 0 ? t1 : t2);
+    float tn = t0;
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+      const float Ex = dx + (2.0f * ax + bx * tn) * tn, Ey = dy + (2.0f * ay + by * tn) * tn;
+      const float Tx = ax + bx * tn, Ty = ay + by * tn;
+      const float g = Ex * Tx + Ey * Ty, gp = 2.0f * (Tx * Tx + Ty * Ty) + (Ex * bx + Ey * by);
+      const float step = g * frcp(gp);
+      tn = gp > 0.0f ? tn - step : tn;
+    }
+    const float ca = clamp01(t0), cb = clamp01(tn);
+    const float da = msdf_d2(r, ca, px, py), db = msdf_d2(r, cb, px, py);
+    const float tk = db < da ? cb : ca, dk = db < da ? db : da;
+    if (dk < best_d2) { best_d2 = dk; best_t = tk; }
+  }
+  return best_t;
+}
+
+__global__ __launch_bounds__(64) void k_msdf_generate(const float* __restrict__ edges, int n_edges, int w, int h, float orient, float inv_range,
+                                                      uint32_t* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int tx0 = blockIdx.x * 8, ty0 = blockIdx.y * 8;
+  const int x = tx0 + (threadIdx.x & 7), y = ty0 + (threadIdx.x >> 3);
+  if (x >= w || y >= h) return;
+  const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+#if !FDH_MSDF_NO_CULL
+  // The tile's texel centres lie within kHalfDiag of its middle.  An end point of an edge at distance u from the middle is at most
+  // u + kHalfDiag from every texel: an upper bound for each channel the edge carries.  An edge whose control box is farther than that from
+  // every texel, for every channel it carries, cannot win anywhere in the tile (the true distance takes all edges: its bound is the
+  // smallest of the three, so the largest bound among the carried channels decides).  Range culls nothing: a far texel's sign still
+  // comes from its nearest edge.
+  constexpr float kHalfDiag = 4.9497475f + 1.0e-3f;
+  const float mx = (float)tx0 + 4.0f, my = (float)ty0 + 4.0f;
+  float ub[3] = {3.0e38f, 3.0e38f, 3.0e38f};
+  for (int i = 0; i < n_edges; i++) {
+    const float* __restrict__ r = edges + (size_t)i * msdf::kEdgeFloats;
+    const float ux = r[0] - mx, uy = r[1] - my, vx = r[4] - mx, vy = r[5] - my;
+    const float u = fsqrt(__builtin_fminf(ux * ux + uy * uy, vx * vx + vy * vy)) + kHalfDiag;
+    const int mask = (int)r[6];
+#pragma unroll
+    for (int c = 0; c < 3; c++) if ((mask >> c) & 1) ub[c] = __builtin_fminf(ub[c], u);
+  }
+#endif
+  float bd2[4], bo[4], bt[4];
+  int be[4];
+#pragma unroll
+  for (int c = 0; c < 4; c++) { bd2[c] = 3.0e38f; bo[c] = -1.0f; bt[c] = 0.0f; be[c] = -1; }
+  for (int i = 0; i < n_edges; i++) {
+    const float* __restrict__ r = edges + (size_t)i * msdf::kEdgeFloats;
+    const int mask = (int)r[6];
+#if !FDH_MSDF_NO_CULL
+    {
+      const float gx = __builtin_fmaxf(__builtin_fmaxf(r[20] - mx, mx - r[22]), 0.0f), gy = __builtin_fmaxf(__builtin_fmaxf(r[21] - my, my - r[23]), 0.0f);
+      const float lb = fsqrt(gx * gx + gy * gy) - kHalfDiag;
+      float um = 0.0f;
+#pragma unroll
+      for (int c = 0; c < 3; c++) if ((mask >> c) & 1) um = __builtin_fmaxf(um, ub[c]);
+      if (lb > um * 1.0001f) continue;  // wave-uniform
+    }
+#endif
+    const float t = msdf_nearest_t(r, px, py);
+    float Ex, Ey, Tx, Ty;
+    msdf_at(r, t, px, py, Ex, Ey, Tx, Ty);
+    const float d2 = Ex * Ex + Ey * Ey;
+    // orthogonality: |cross(unit tangent, unit vector to the texel)|; 0 on the curve itself
+    const float cr = Tx * Ey - Ty * Ex, den = (Tx * Tx + Ty * Ty) * d2;
+    const float ortho = den > 0.0f ? __builtin_fabsf(cr) * frcp(fsqrt(den)) : 0.0f;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      if (c < 3 && !((mask >> c) & 1)) continue;  // wave-uniform
+      const bool better = d2 < bd2[c] || (d2 == bd2[c] && ortho > bo[c]);
+      bd2[c] = better ? d2 : bd2[c]; bo[c] = better ? ortho : bo[c]; bt[c] = better ? t : bt[c]; be[c] = better ? i : be[c];
+    }
+  }
+  uint32_t word = 0;
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    float d = -3.0e38f;  // no edge: outside
+    if (be[c] >= 0) {
+      const float* __restrict__ r = edges + (size_t)be[c] * msdf::kEdgeFloats;
+      float Ex, Ey, Tx, Ty;
+      msdf_at(r, bt[c], px, py, Ex, Ey, Tx, Ty);
+      // the vector to the texel is -E: cross(T, p - N) = Ty Ex - Tx Ey
+      const float cr = Ty * Ex - Tx * Ey;
+      d = fsqrt(bd2[c]);
+      d = cr >= 0.0f ? d : -d;
+      if (c < 3 && (bt[c] <= 0.0f || bt[c] >= 1.0f)) {  // the nearest point is an end: the distance to the tangent line there
+        const float ux = bt[c] <= 0.0f ? r[16] : r[18], uy = bt[c] <= 0.0f ? r[17] : r[19];
+        const float pd = uy * Ex - ux * Ey;
+        d = __builtin_fabsf(pd) <= __builtin_fabsf(d) ? pd : d;
+      }
+      d *= orient;
+    }
+    const float v = clamp01(0.5f + d * inv_range);
+    word |= (uint32_t)__builtin_floorf(255.0f * v + 0.5f) << (8 * c);
+  }
+  out[(size_t)y * w + x] = word;
+}
+
+void launch_msdf_generate(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, uint32_t* out) {
+  if (w <= 0 || h <= 0) return;
+  FDH_LAUNCH(k_msdf_generate, dim3((w + 7) / 8, (h + 7) / 8), dim3(64), 0, s, edges, n_edges, w, h, orient, 1.0f / range, out);
+}
+
+}  // namespace fdh

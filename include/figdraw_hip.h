@@ -246,8 +246,10 @@ FDH_API int fdh_put_image(FdhContext*, int64_t key, int width, int height, const
  * weights 8, 77, 86, 77, 8 over x-2 .. x+2, columns clamped to the image, per channel (sum + 128) >> 8 -- then the image and
  * its minifyBy2 chain go into the atlas like fdh_put_image's.  Integer arithmetic, bit-exact with the reference's. */
 enum { FDH_GLYPH_LCD_FILTER = 1,
-       FDH_GLYPH_LCD_CONTEXT = 2 /* filter iff fdh_set_text_lcd_filtering is on: what renderText's generateGlyph call does with
-                                    ctx.textLcdFilteringEnabled() (figrender.nim:420) */ };
+       FDH_GLYPH_LCD_CONTEXT = 2, /* filter iff fdh_set_text_lcd_filtering is on: what renderText's generateGlyph call does with
+                                     ctx.textLcdFilteringEnabled() (figrender.nim:420) */
+       FDH_GLYPH_MTSDF = 4            /* fdh_put_glyph_outline: store a multi-channel + true signed distance field, not coverage */ };
+#define FDH_GLYPH_SDF_RANGE(r) ((uint32_t)(r) << 8)   /* bits 8..15: the distance range in texels, 1..64; 0 = 4 */
 FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height, const uint8_t* rgba8, uint32_t flags, int out_rect[4]);
 /* A glyph OUTLINE rasterised on the device into the atlas -- generateGlyph's job (common/fontglyphs.nim:61-106; the reference calls
  * pixie's fillText for it, common/textrasters/pixie_raster.nim:83-87).  segs: n x 6 floats {x0, y0, cx, cy, x1, y1} in pixel units of
@@ -256,6 +258,42 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  * (pixie_raster.nim:69-72).  Coverage = exact-area scanline accumulation (curves flattened to <= 0.025 px chord error), stored
  * premultiplied white like pixie's white paint; flags as for fdh_put_glyph_image.  pixie's own texels are third-party and
  * unpinned: the oracle restates the same published algorithm and the two agree bit for bit. */
+/* DISTANCE FIELDS.  With flags = FDH_GLYPH_MTSDF | FDH_GLYPH_SDF_RANGE(R) the same call stores, instead of coverage, the width x height
+ * RGBA8 image that fdh_draw_msdf(key, ..., px_range = R, sd_threshold = 0.5, mtsdf = 0 or 1) expects -- what the reference gets at run time
+ * from the third-party sdfy (generateMsdfPath / generateMtsdfPath, examples/windy_msdf_star.nim:279-286).  R, G, B hold the three channels'
+ * signed pseudo-distances, A the true signed distance; a distance d, in texels, positive inside, taken at the texel centre
+ * (x + 0.5, y + 0.5), is stored as floor(255 * clamp(0.5 + d / R, 0, 1) + 0.5).  Nothing is premultiplied; the image is packed and its
+ * level chain built like any other.  FDH_GLYPH_MTSDF with an LCD flag, a range without FDH_GLYPH_MTSDF or above 64, more than 65535
+ * segments and an open contour are FDH_ERR_INVALID; a record-only context packs the rectangle and makes no texels.
+ * The construction is Chlumsky's multi-channel distance field (V. Chlumsky, "Shape Decomposition for Multi-channel Distance Fields",
+ * 2015; the "simple" edge colouring of his msdfgen), restated here; this comment is the specification, tests/msdf_ref.py implements it
+ * in float64 and the device (figdraw_amd/csrc/fdh_msdf_host.h, k_msdf.hip) is held to that within 1 LSB.  All host decisions (steps 1 - 3)
+ * are taken in double on the float32 coordinates passed.
+ * 1. Edges and contours.  A quadratic whose second difference b = P0 - 2 P1 + P2 has |b|^2 <= 1e-6 becomes the line P0 P2; a line
+ *    with P0 = P2 is dropped.  Consecutive edges, each starting where (float equality) the one before ended, form a contour; it closes
+ *    where an end equals the contour's first start, and the next edge starts a new contour.  A contour left open: FDH_ERR_INVALID.
+ * 2. Orientation.  o = +1 if the total signed area is >= 0, else -1: the sum over all edges of (x0 y1 - x1 y0) / 2 plus, for a
+ *    quadratic, cross(P1 - P0, P2 - P0) / 3, with cross(u, v) = ux vy - uy vx.  Every signed distance is multiplied by o, so the field
+ *    is positive inside whichever way the font winds, provided holes wind against their outer contour.  Overlapping contours are out
+ *    of scope (msdfgen without its overlap mode).
+ * 3. Colours (R = 1, G = 2, B = 4; magenta = R|B, yellow = R|G, cyan = G|B, white = all), per contour of m edges e_0 .. e_(m-1).  The
+ *    tangent direction of an edge at its start is P1 - P0, at its end P2 - P1, and P2 - P0 for a line or where that vector is zero.
+ *    Vertex i (where e_(i-1) ends and e_i starts, cyclically) is a corner when the unit tangents in and out have dot <= 0 or
+ *    |cross| > sin(3.0).  No corner: every edge white.  Two or more corners, n of them: starting at the corner of lowest index and
+ *    going round, the edges between two corners form run k = 0 .. n - 1 and take magenta, yellow, cyan for k mod 3 = 0, 1, 2; only
+ *    when n mod 3 = 1 the last run takes yellow (its neighbours are cyan and magenta).  One corner: the edges are taken from the
+ *    corner round; if m < 3 each is first split into the three parts t in [0, 1/3], [1/3, 2/3], [2/3, 1] (de Casteljau with
+ *    lerp(a, b, t) = a + (b - a) t: new end points B(t) = lerp(lerp(P0, P1, t), lerp(P1, P2, t), t), a part's control point
+ *    lerp(lerp(P0, P1, t0), lerp(P1, P2, t0), t1), each rounded to float32; the original ends are kept as they are); then edge j of the
+ *    m' gets magenta, yellow, cyan for floor(3 j / m') = 0, 1, 2.
+ * 4. Per texel p and per channel: among the edges carrying the channel, the one whose nearest point N = B(t), t in [0, 1], has the
+ *    smallest |p - N| (at t = 0 and t = 1, N is the stored end point itself, so two edges meeting in a corner tie exactly for a texel
+ *    beyond it); ties go to the larger orthogonality |cross(T / |T|, (p - N) / |p - N|)|, T = the tangent at N.  The signed distance is
+ *    o * sign(cross(T, p - N)) * |p - N|, sign(0) = +1.  If t is 0 or 1 it is replaced by the pseudo-distance o * cross(U, p - N), U the
+ *    unit tangent of step 3 at that end, when that is not larger in magnitude.  A takes all edges and no pseudo-distance.  An outline
+ *    without edges gives an all-zero image.
+ * Out of scope: msdfgen's error-correction pass (thin features and near-tangent corners keep the artefacts it would mend), overlapping
+ * contours, cubic segments (the outline format has none), a batched multi-glyph call (it would be a new entry point). */
 FDH_API int fdh_put_glyph_outline(FdhContext*, int64_t key, int width, int height, const float* segs, int n_segs, uint32_t flags, int out_rect[4]);
 /* putFlippy (glcontext.nim:610-620): `bytes` is a whole .flippy file (common/formatflippy.nim:77-149: "flip", version 1, then per
  * mip "mip!", w, h, zlen, raw-snappy straight RGBA8); every stored level is uploaded as is at (x >> l, y >> l). */
@@ -455,7 +493,8 @@ FDH_API const char* fdh_record_json(FdhContext*);
 
 /* Diagnostic: copy one of the context's working surfaces to the host (W x H RGBA8, tightly packed) after waiting for its
  * stream.  which = 0: the frame (= fdh_read_pixels), 1: the horizontal blur pass's output (the reference's intermediate blur
- * texture, glcontext.nim:1743-1786) as the last blur node left it, 2: the blurred snapshot of the last unfused blur node.
+ * texture, glcontext.nim:1743-1786) as the last blur node left it, 2: the blurred snapshot of the last unfused blur node,
+ * 4: level 0 of the atlas (atlas_size x atlas_size RGBA8, not W x H): the exact texels an upload or fdh_put_glyph_outline left.
  * tools/race_contexts.py uses it to tell which pass a wrong pixel came from. */
 FDH_API int fdh_debug_read_surface(FdhContext*, int which, uint8_t* out_rgba8);
 /* Diagnostic, host-only (no device, no context): the pixel rectangle [x0,x1) x [y0,y1) the submission path marks as the

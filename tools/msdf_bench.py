@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""What a distance-field put costs (fdh_put_glyph_outline with FDH_GLYPH_MTSDF, k_msdf_generate), on an MI355X -> profiles/msdf.txt.
+
+  msdf_bench.py --all OUT [--nocull-lib LIB]   every step as a child process under its own time limit, in turn, nothing started after a
+                                               failure; writes the report.  LIB: the library built with -DFDH_MSDF_NO_CULL=1
+                                               (make -C figdraw_amd/csrc variant NAME=msdf_nocull DEFS=-DFDH_MSDF_NO_CULL=1)
+  msdf_bench.py --time CASE                    the whole call on the host clock, profiler off: 200 timed calls after 20; one JSON line
+  msdf_bench.py --trace CASE [--calls N]       N calls (run it under rocprofv3 --kernel-trace --stats -f csv); one JSON line
+
+Cases: small = one glyph outline ('g' of the fixture, scaled to a 32 x 32 field, range 4); large = six glyph outlines scaled and laid side by
+side in a 256 x 256 field (about 200 segments)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from damage_readback_bench import _stats, _step  # noqa: E402
+
+CASES = {"small": "32 x 32, one glyph", "large": "256 x 256, six glyphs side by side"}
+
+
+def outline(case):
+    """-> (segs float32 (n, 6), w, h)"""
+    import numpy as np
+
+    z = np.load(os.path.join(ROOT, "tests", "golden", "outlines_ubuntu20.npz"))
+    if case == "small":
+        segs, (w, h) = z["segs_103"].astype(np.float32), z["size_103"]
+        s = np.float32(24.0 / max(int(w), int(h)))
+        return segs * s + np.float32(4), 32, 32
+    parts = []
+    for i, code in enumerate((66, 82, 103, 109, 56, 38)):  # 3 columns x 2 rows of 85 x 128 cells
+        segs, (w, h) = z[f"segs_{code}"].astype(np.float32), z[f"size_{code}"]
+        s = np.float32(76.0 / max(int(w), int(h)))
+        part = segs * s
+        part[:, 0::2] += np.float32(6 + 85 * (i % 3))
+        part[:, 1::2] += np.float32(20 + 128 * (i // 3))
+        parts.append(part)
+    return np.concatenate(parts).astype(np.float32), 256, 256
+
+
+def _context():
+    from figdraw_amd.context import HipContext
+
+    return HipContext(atlas_size=4096, device=0)
+
+
+def time_case(case, timed=200, warm=20):
+    segs, w, h = outline(case)
+    ctx = _context()
+    us = []
+    for k in range(warm + timed):
+        if k % 100 == 0:
+            ctx.reset_atlas()  # (the packer's search grows with what is packed; every call packs a new rectangle)
+        t1 = time.perf_counter()
+        ctx.put_glyph_outline(1 + k, segs, w, h, mtsdf=True, sdf_range=4)
+        t2 = time.perf_counter()
+        if k >= warm:
+            us.append((t2 - t1) * 1e6)
+    ctx.close()
+    print(json.dumps({"case": case, "segments": len(segs), "calls": timed, "median_us": statistics.median(us), "p10_us": sorted(us)[len(us) // 10],
+                      "p90_us": sorted(us)[9 * len(us) // 10]}))
+
+
+def trace_case(case, calls):
+    segs, w, h = outline(case)
+    ctx = _context()
+    for k in range(calls):
+        ctx.put_glyph_outline(1 + k, segs, w, h, mtsdf=True, sdf_range=4)
+    ctx.close()
+    print(json.dumps({"case": case, "segments": len(segs), "calls": calls}))
+
+
+HEAD = """tools/msdf_bench.py -- a distance-field put (fdh_put_glyph_outline with FDH_GLYPH_MTSDF), MI355X.
+whole call = host clock around the call, profiler off, 200 timed calls after 20 (it packs, builds the edge records, copies them, launches
+k_msdf_generate and the level chain's blits and minifies, and synchronises); kernel = k_msdf_generate alone from a
+rocprofv3 --kernel-trace --stats run of its own, 60 calls.  cull / no cull: the product library / the -DFDH_MSDF_NO_CULL=1 build.
+
+Hypotheses, stated before the numbers (nothing had been timed when they were written):
+  1. small (32 x 32, one glyph): the whole call is launch plus synchronise latency -- the kernel is a few microseconds of a call of
+     many tens, and culling changes nothing that can be seen in the call.
+  2. large (256 x 256, about 200 segments): the kernel is VALU-bound on the cubic solve (1024 waves x 200 edges x ~300 VALU
+     instructions per quadratic without culling); culling removes most edges per 8 x 8 tile and the kernel's time with it.
+"""
+
+
+def run_all(out_path, nocull_lib, trace_dir):
+    me = [sys.executable, os.path.abspath(__file__)]
+    lines = HEAD.splitlines() + [""]
+    libs = [("cull", None)] + ([("no cull", os.path.abspath(nocull_lib))] if nocull_lib else [])
+    ok = True
+    for case in CASES:
+        for tag, lib in libs:
+            env = dict(os.environ)
+            if lib:
+                env["FIGDRAW_HIP_LIB"] = lib
+            got = _step(me + ["--time", case], 300, env)
+            if got is None:
+                ok = False
+                break
+            r = json.loads([ln for ln in got.strip().splitlines() if ln.startswith("{")][-1])
+            d = os.path.join(trace_dir, case + "_" + tag.replace(" ", ""))
+            got = _step(["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "-o", "t", "--"] + me + ["--trace", case, "--calls", "60"], 300, env)
+            if got is None:
+                ok = False
+                break
+            kern = _stats(d, "*kernel_stats.csv")
+            calls, us, longest = kern.get("k_msdf_generate", (0, 0.0, 0.0))
+            others = ", ".join(f"{k} {v[1] / 60:.1f}" for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1]) if k != "k_msdf_generate")
+            lines.append(f"{case} ({CASES[case]}, {r['segments']} segments), {tag}: whole call median {r['median_us']:.1f} us (p10 {r['p10_us']:.1f}, p90 {r['p90_us']:.1f}); "
+                         f"kernel {us / max(calls, 1):.2f} us per launch over {calls} launches, the longest {longest:.1f}")
+            lines.append(f"    other kernels of the call, us per call: {others}")
+            print(lines[-2], flush=True)
+        if not ok:
+            break
+    if not ok:
+        lines += ["", "INCOMPLETE: a step failed; nothing was started after it"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--all", metavar="OUT")
+    ap.add_argument("--nocull-lib")
+    ap.add_argument("--trace-dir", default=os.path.join(ROOT, "build", "msdf_trace"))
+    ap.add_argument("--time", choices=list(CASES))
+    ap.add_argument("--trace", choices=list(CASES))
+    ap.add_argument("--calls", type=int, default=60)
+    a = ap.parse_args()
+    if a.all:
+        sys.exit(run_all(a.all, a.nocull_lib, a.trace_dir))
+    elif a.time:
+        time_case(a.time)
+    elif a.trace:
+        trace_case(a.trace, a.calls)
+    else:
+        ap.error("nothing to do")
