@@ -263,6 +263,9 @@ void Context::put_glyph_mtsdf(int64_t key, int w, int h, const float* segs, int 
   glyph_edges_.reserve(std::max<size_t>(rec.size(), msdf::kEdgeFloats));
   if (!rec.empty()) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, stream_));
   launch_msdf_generate(stream_, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, glyph_a_.ptr);
+  // The level chain (updateSubImage's, textures.nim:106-119) stores nothing of an image 1 texel wide or high, not even level 0.  A field is
+  // sampled at level 0 alone, and these texels have no other home: such a field gets that level.
+  if (w == 1 || h == 1) launch_atlas_blit(stream_, atlas_levels_[0], atlas_size_, x, y, glyph_a_.ptr, w, h);
   glyph_to_atlas(glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
 }
 // Flippy: figdraw's mip-mapped image container (common/formatflippy.nim:77-149).  Layout: "flip", u32 version (1), then per

@@ -121,9 +121,12 @@ inline bool build_shape(const float* segs, int n, Shape* out) {
     e.line = q[2] != q[2];
     e.p[0] = q[0]; e.p[1] = q[1]; e.p[4] = q[4]; e.p[5] = q[5];
     e.p[2] = e.line ? q[0] : q[2]; e.p[3] = e.line ? q[1] : q[3];
-    if (!e.line) {  // a quadratic without curvature is the line between its ends
+    if (!e.line) {  // a quadratic without curvature is the line between its ends; so is one whose control point lies on their line, on an end or beyond it
       const double bx = (double)q[0] - 2.0 * (double)q[2] + (double)q[4], by = (double)q[1] - 2.0 * (double)q[3] + (double)q[5];
-      if (bx * bx + by * by <= 1e-6) { e.line = true; e.p[2] = e.p[0]; e.p[3] = e.p[1]; }
+      const double ax = (double)q[2] - q[0], ay = (double)q[3] - q[1], cx = (double)q[4] - q[0], cy = (double)q[5] - q[1];
+      const double ex = (double)q[4] - q[2], ey = (double)q[5] - q[3];
+      const bool folded = ax * cy == ay * cx && !(ax * ex > 0.0 || ay * ey > 0.0);  // (products compared one by one: nothing to contract)
+      if (bx * bx + by * by <= 1e-6 || folded) { e.line = true; e.p[2] = e.p[0]; e.p[3] = e.p[1]; }
     }
     if (e.line && e.p[0] == e.p[4] && e.p[1] == e.p[5]) continue;  // zero length
     if (!cur.empty() && (cur.back().p[4] != e.p[0] || cur.back().p[5] != e.p[1])) return false;

@@ -83,7 +83,13 @@ __device__ __forceinline__ float msdf_nearest_t(const float* __restrict__ r, flo
     const float tk = db < da ? cb : ca, dk = db < da ? db : da;
     if (dk < best_d2) { best_d2 = dk; best_t = tk; }
   }
-  return best_t;
+  // An interior point counts only where it is nearer than both ends.  Towards a control point that lies on its end point the curve slows
+  // to a halt -- B(t) - P2 = (P0 - P2) (1 - t)^2 -- so a root 1e-6 short of 1 is the end itself to the last bit, and left at that the
+  // texel would miss the end's pseudo-distance.
+  const float e1x = r[4] - px, e1y = r[5] - py;
+  const float d0 = dx * dx + dy * dy, d1 = e1x * e1x + e1y * e1y;
+  const float te = d1 < d0 ? 1.0f : 0.0f, de = d1 < d0 ? d1 : d0;
+  return de <= best_d2 ? te : best_t;
 }
 
 __global__ __launch_bounds__(64) void k_msdf_generate(const float* __restrict__ edges, int n_edges, int w, int h, float orient, float inv_range,

@@ -263,15 +263,21 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  * from the third-party sdfy (generateMsdfPath / generateMtsdfPath, examples/windy_msdf_star.nim:279-286).  R, G, B hold the three channels'
  * signed pseudo-distances, A the true signed distance; a distance d, in texels, positive inside, taken at the texel centre
  * (x + 0.5, y + 0.5), is stored as floor(255 * clamp(0.5 + d / R, 0, 1) + 0.5).  Nothing is premultiplied; the image is packed and its
- * level chain built like any other.  FDH_GLYPH_MTSDF with an LCD flag, a range without FDH_GLYPH_MTSDF or above 64, more than 65535
- * segments and an open contour are FDH_ERR_INVALID; a record-only context packs the rectangle and makes no texels.
+ * level chain built like any other (a field 1 texel wide or high, of which that chain stores nothing, gets level 0: all a field is sampled
+ * at). FDH_GLYPH_MTSDF with an LCD flag, a range without FDH_GLYPH_MTSDF or above 64, more than 65535 segments and an open contour are
+ * FDH_ERR_INVALID; a record-only context packs the rectangle and makes no texels.
  * The construction is Chlumsky's multi-channel distance field (V. Chlumsky, "Shape Decomposition for Multi-channel Distance Fields",
  * 2015; the "simple" edge colouring of his msdfgen), restated here; this comment is the specification, tests/msdf_ref.py implements it
  * in float64 and the device (figdraw_amd/csrc/fdh_msdf_host.h, k_msdf.hip) is held to that within 1 LSB.  All host decisions (steps 1 - 3)
  * are taken in double on the float32 coordinates passed.
- * 1. Edges and contours.  A quadratic whose second difference b = P0 - 2 P1 + P2 has |b|^2 <= 1e-6 becomes the line P0 P2; a line
- *    with P0 = P2 is dropped.  Consecutive edges, each starting where (float equality) the one before ended, form a contour; it closes
- *    where an end equals the contour's first start, and the next edge starts a new contour.  A contour left open: FDH_ERR_INVALID.
+ * 1. Edges and contours.  A quadratic whose second difference b = P0 - 2 P1 + P2 has |b|^2 <= 1e-6 becomes the line P0 P2.  So does one
+ *    whose control point lies on the line of its ends, on an end point or beyond one: with u = P1 - P0, v = P2 - P0, w = P2 - P1, when
+ *    u.x v.y = u.y v.x and neither u.x w.x nor u.y w.y is positive, each product taken and compared in double.  Such a curve halts at
+ *    that end or runs past it and comes back over itself; the stretch it covers twice encloses nothing under non-zero winding and has
+ *    no tangent at its tip to take a sign from, so it is left out.  (A control point on that line strictly between the ends leaves an
+ *    ordinary curve, and it stays one.)  A line with P0 = P2 is dropped, such a quadratic with P0 = P2 with it.  Consecutive edges,
+ *    each starting where (float equality) the one before ended, form a contour; it closes where an end equals the contour's first
+ *    start, and the next edge starts a new contour.  A contour left open: FDH_ERR_INVALID.
  * 2. Orientation.  o = +1 if the total signed area is >= 0, else -1: the sum over all edges of (x0 y1 - x1 y0) / 2 plus, for a
  *    quadratic, cross(P1 - P0, P2 - P0) / 3, with cross(u, v) = ux vy - uy vx.  Every signed distance is multiplied by o, so the field
  *    is positive inside whichever way the font winds, provided holes wind against their outer contour.  Overlapping contours are out
@@ -288,10 +294,11 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  *    m' gets magenta, yellow, cyan for floor(3 j / m') = 0, 1, 2.
  * 4. Per texel p and per channel: among the edges carrying the channel, the one whose nearest point N = B(t), t in [0, 1], has the
  *    smallest |p - N| (at t = 0 and t = 1, N is the stored end point itself, so two edges meeting in a corner tie exactly for a texel
- *    beyond it); ties go to the larger orthogonality |cross(T / |T|, (p - N) / |p - N|)|, T = the tangent at N.  The signed distance is
+ *    beyond it; an interior point of an edge is its nearest only where it is strictly nearer than both ends, and of two ends equally
+ *    near it is P0); ties go to the larger orthogonality |cross(T / |T|, (p - N) / |p - N|)|, T = the tangent at N.  The signed distance is
  *    o * sign(cross(T, p - N)) * |p - N|, sign(0) = +1.  If t is 0 or 1 it is replaced by the pseudo-distance o * cross(U, p - N), U the
  *    unit tangent of step 3 at that end, when that is not larger in magnitude.  A takes all edges and no pseudo-distance.  An outline
- *    without edges gives an all-zero image.
+ *    without edges -- n_segs = 0, or every segment dropped by step 1 -- is no error: it gives an all-zero image.
  * Out of scope: msdfgen's error-correction pass (thin features and near-tangent corners keep the artefacts it would mend), overlapping
  * contours, cubic segments (the outline format has none), a batched multi-glyph call (it would be a new entry point). */
 FDH_API int fdh_put_glyph_outline(FdhContext*, int64_t key, int width, int height, const float* segs, int n_segs, uint32_t flags, int out_rect[4]);

@@ -119,7 +119,9 @@ def build_shape(segs):
         p1 = p0 if line else q[2:4]
         if not line:
             b = p0 - 2.0 * p1 + p2
-            if b[0] * b[0] + b[1] * b[1] <= 1e-6:
+            a, c, e = p1 - p0, p2 - p0, p2 - p1
+            folded = a[0] * c[1] == a[1] * c[0] and not (a[0] * e[0] > 0.0 or a[1] * e[1] > 0.0)
+            if b[0] * b[0] + b[1] * b[1] <= 1e-6 or folded:
                 line, p1 = True, p0
         if line and p0[0] == p2[0] and p0[1] == p2[1]:
             continue

@@ -1,5 +1,6 @@
 """Distance-field generation on the device (fdh_put_glyph_outline with FDH_GLYPH_MTSDF, k_msdf_generate): the texels against the float64
-reference tests/msdf_ref.py, rendering with those texels against the oracle, and the atlas's other users undisturbed."""
+reference tests/msdf_ref.py -- the font set and the hostile outlines of msdf_cases.hostile_inputs() --, rendering with those texels against
+the oracle, and the atlas's other users undisturbed."""
 import math
 
 import numpy as np
@@ -52,6 +53,66 @@ def test_sign_of_the_device_texels(generated):
     texels, _ = generated
     for name, segs, w, h, R in MC.inputs():
         MC.check_sign(name, texels[name][1], segs, w, h, R)
+
+
+SQUARE = MC.poly([(2, 2), (10, 2), (10, 9), (2, 9)])  # in 12 x 11, as on the record-only context (test_msdf_host.py)
+DEVICE_ONLY = [("16383 copies of one square", np.tile(SQUARE, (16383, 1)), 12, 11, 4),  # 65532 segments: the most whole squares the call accepts
+               ("0 segments", np.zeros((0, 6), np.float32), 12, 11, 4)]
+
+
+@pytest.fixture(scope="module")
+def hostile():
+    """every hostile input and the two device-only ones through the flagged call into one 2048 atlas ->
+    {name: (rect, texels, the reference's texels, its true distances or None)}, and level 0 itself.  The reference runs once per input, here."""
+    from figdraw_amd.context import HipContext
+
+    ctx = HipContext(atlas_size=2048, device=0)
+    rects = {}
+    for i, (name, segs, w, h, R) in enumerate([c[:5] for c in MC.hostile_inputs()] + DEVICE_ONLY):
+        rects[name] = ctx.put_glyph_outline(8000 + i, segs, w, h, mtsdf=True, sdf_range=R)
+        assert rects[name][2:] == (w, h)
+    assert ctx.atlas_size() == 2048
+    atlas = ctx.debug_read_surface(4)
+    ctx.close()
+    assert atlas.shape == (2048, 2048, 4)
+    want = {}
+    for name, segs, w, h, R, _ in MC.hostile_inputs():
+        d = M.distances(M.build_shape(segs), w, h)
+        want[name] = (M.encode(d, R), d[..., 3])
+    # duplicates change no texel ("a square twice" among the hostile inputs shows it): 65532 edges are not fed to numpy
+    want[DEVICE_ONLY[0][0]] = (M.generate(SQUARE, 12, 11, 4), None)
+    want[DEVICE_ONLY[1][0]] = (M.generate(DEVICE_ONLY[1][1], 12, 11, 4), None)
+    return {name: (r, atlas[r[1]:r[1] + r[3], r[0]:r[0] + r[2]].copy()) + want[name] for name, r in rects.items()}, atlas
+
+
+def test_hostile_texels_against_the_reference(hostile):
+    texels, atlas = hostile
+    over = {}
+    written = np.zeros(atlas.shape[:2], bool)
+    assert len(texels) == len(MC.hostile_inputs()) + 2
+    for name, ((x, y, w, h), got, want, _) in texels.items():
+        n = MC.over_tolerance(got, want)
+        if n:
+            over[name] = n
+        assert n <= MC.CAP, f"{name}: {n} texels are more than 1 LSB from the reference"
+        written[y:y + h, x:x + w] = True
+    print(f"texels beyond 1 LSB per image (cap {MC.CAP}): {over or 'none in any image'}")
+    assert not texels["0 segments"][1].any() and not texels["0 segments"][2].any()  # what the header promises for an outline without edges
+    assert not texels["one edge doubling back on itself"][1].any()
+    for name, ((x, y, w, h), _, _, _) in texels.items():
+        ring = atlas[max(y - 4, 0):y + h + 4, max(x - 4, 0):x + w + 4].copy()
+        ring[y - max(y - 4, 0):y - max(y - 4, 0) + h, x - max(x - 4, 0):x - max(x - 4, 0) + w] = 0
+        assert not ring.any(), f"{name}: the margin was written"
+    assert not atlas[~written].any()
+
+
+def test_hostile_sign_of_the_device_texels(hostile):
+    texels, _ = hostile
+    for name, segs, w, h, R, simple in MC.hostile_inputs():
+        if simple:
+            assert MC.check_sign(name, texels[name][1], segs, w, h, R, texels[name][3]) > 0
+    name, _, w, h, R = DEVICE_ONLY[0]
+    MC.check_sign(name, texels[name][1], SQUARE, w, h, R)
 
 
 def _scene(ctx, keys, sizes):

@@ -1,7 +1,8 @@
 """Distance-field generation (fdh_put_glyph_outline with FDH_GLYPH_MTSDF), what a CPU can check: the flag on a record-only context, known
 answers for the reference tests/msdf_ref.py itself, the source of k_msdf_generate and fdh_msdf_host.h under the host shim of
-tests/msdf_emu against that reference on all 94 + 12 inputs, the sign of the field against the winding test, and how well the field
-reconstructs coverage through the oracle's draw_msdf (measured: profiles/msdf.txt)."""
+tests/msdf_emu against that reference on all 94 + 12 inputs, the sign of the field against the winding test, the same on the hostile
+outlines of msdf_cases.hostile_inputs(), and how well the field reconstructs coverage through the oracle's draw_msdf (measured:
+profiles/msdf.txt)."""
 import ctypes as C
 import os
 import re
@@ -59,6 +60,17 @@ def test_flag_on_a_record_only_context():
     # the diagnostic's new value needs a device like the others
     buf = (C.c_uint8 * 16)()
     assert ctx.L.fdh_debug_read_surface(ctx.h, 4, buf) == ctx.L.fdh_debug_read_surface(ctx.h, 0, buf) != 0
+    ctx.close()
+
+
+def test_an_empty_outline_on_a_record_only_context():
+    """an outline without edges is no error (step 4 of the specification): 0 segments, and segments that step 1 all drops, pack like any other"""
+    ctx = HipContext(record_only=True)
+    assert ctx.put_glyph_outline(90, np.zeros((0, 6), np.float32), 12, 11, mtsdf=True, sdf_range=4)[2:] == (12, 11) and ctx.has_image(90)
+    out = (C.c_int * 4)()
+    assert ctx.L.fdh_put_glyph_outline(ctx.h, 91, 12, 11, None, 0, MTSDF | RANGE(4), out) == 0 and tuple(out)[2:] == (12, 11)  # no pointer is needed for none
+    back = np.array([[6, 5, 40, 5.5, 6, 5], [3, 3, MC.NAN, MC.NAN, 3, 3]], np.float32)
+    assert ctx.put_glyph_outline(92, back, 12, 11, mtsdf=True)[2:] == (12, 11) and ctx.has_image(92)
     ctx.close()
 
 
@@ -128,8 +140,8 @@ def test_reference_known_answers():
 
 # ------------------------------------------------------------------------------------------------------------------ 3 - 5. the kernel's source on a CPU
 @pytest.fixture(scope="module")
-def emulated(tmp_path_factory):
-    """every input through k_msdf.hip + fdh_msdf_host.h compiled as plain C++ -> {name: (texels, edge records, orientation, texels of the build without culling)}"""
+def shim(tmp_path_factory):
+    """k_msdf.hip + fdh_msdf_host.h compiled as plain C++, with and without tile culling -> the directory of ./emu and ./emu_nocull"""
     tmp = tmp_path_factory.mktemp("msdf_emu")
     for name in ("fdh_device.h", "emu.cpp"):  # the shim
         shutil.copy(os.path.join(ROOT, "tests", "msdf_emu", name), tmp)
@@ -142,20 +154,42 @@ def emulated(tmp_path_factory):
     assert subprocess.run(["./alone"], cwd=tmp).returncode == 0
     # the build without tile culling (tools/msdf_bench.py's second library): culling must not change a texel
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", "-DFDH_MSDF_NO_CULL=1", "-x", "c++", "emu.cpp", "-o", "emu_nocull"], cwd=tmp)
+    return tmp
+
+
+@pytest.fixture(scope="module")
+def emulated(shim):
+    """every font input through the shim -> {name: (texels, edge records, orientation, texels of the build without culling)}"""
     out = {}
     for name, segs, w, h, R in MC.inputs():
-        segs.tofile(tmp / "segs.raw")
-        r = subprocess.run(["./emu_nocull", str(w), str(h), str(R), "segs.raw"], cwd=tmp, capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, f"{name}: {r.returncode} {r.stdout}{r.stderr}"
-        nocull = np.fromfile(tmp / "texels.raw", np.uint8).reshape(h, w, 4)
-        r = subprocess.run(["./emu", str(w), str(h), str(R), "segs.raw"], cwd=tmp, capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, f"{name}: {r.returncode} {r.stdout}{r.stderr}"
-        rec = np.fromfile(tmp / "edges.raw", np.float32)
-        out[name] = (np.fromfile(tmp / "texels.raw", np.uint8).reshape(h, w, 4), rec[:-1].reshape(-1, 24), float(rec[-1]), nocull)
+        out[name] = _through_the_shim(shim, name, segs, w, h, R)
     # an open contour is refused by the host code too
-    MC.poly([(1, 1), (5, 1), (5, 5)])[:2].tofile(tmp / "segs.raw")
-    assert subprocess.run(["./emu", "8", "8", "4", "segs.raw"], cwd=tmp).returncode == 3
+    MC.poly([(1, 1), (5, 1), (5, 5)])[:2].tofile(shim / "segs.raw")
+    assert subprocess.run(["./emu", "8", "8", "4", "segs.raw"], cwd=shim).returncode == 3
     return out
+
+
+@pytest.fixture(scope="module")
+def hostile(shim):
+    """every hostile input through the shim and, once, through the float64 reference ->
+    {name: (texels, edge records, orientation, texels without culling, the reference's shape, its distances in float64)}"""
+    out = {}
+    for name, segs, w, h, R, _ in MC.hostile_inputs():
+        sh = M.build_shape(segs)
+        out[name] = _through_the_shim(shim, name, segs, w, h, R) + (sh, M.distances(sh, w, h))
+    return out
+
+
+def _through_the_shim(tmp, name, segs, w, h, R):
+    """-> (texels, edge records, orientation, texels of the build without culling)"""
+    segs.tofile(tmp / "segs.raw")
+    r = subprocess.run(["./emu_nocull", str(w), str(h), str(R), "segs.raw"], cwd=tmp, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, f"{name}: {r.returncode} {r.stdout}{r.stderr}"
+    nocull = np.fromfile(tmp / "texels.raw", np.uint8).reshape(h, w, 4)
+    r = subprocess.run(["./emu", str(w), str(h), str(R), "segs.raw"], cwd=tmp, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, f"{name}: {r.returncode} {r.stdout}{r.stderr}"
+    rec = np.fromfile(tmp / "edges.raw", np.float32)
+    return np.fromfile(tmp / "texels.raw", np.uint8).reshape(h, w, 4), rec[:-1].reshape(-1, 24), float(rec[-1]), nocull
 
 
 def test_the_reference_in_float32_stays_inside_the_cap():
@@ -197,6 +231,70 @@ def test_sign_against_the_winding_number(emulated):
         checked += MC.check_sign(name + " (reference)", M.generate(segs, w, h, R), segs, w, h, R)
         MC.check_sign(name + " (kernel source)", emulated[name][0], segs, w, h, R)
     assert checked > 100000
+
+
+# ------------------------------------------------------------------------------------------------------------------ 6. hostile outlines
+def test_hostile_the_reference_in_float32_stays_inside_the_cap(hostile):
+    """(a) the same condition on the hostile inputs: one that fails it is replaced, never excused"""
+    over = {}
+    for name, segs, w, h, R, _ in MC.hostile_inputs():
+        sh, d64 = hostile[name][4:6]
+        n = MC.over_tolerance(M.encode(M.distances(sh, w, h, np.float32), R), M.encode(d64, R))
+        if n:
+            over[name] = n
+        assert n <= MC.CAP, f"{name}: {n} texels of the float32 reference are more than 1 LSB from the float64 reference"
+    print(f"float32 reference against float64, texels beyond 1 LSB per image (cap {MC.CAP}): {over or 'none in any image'}")
+
+
+def test_hostile_the_kernel_source_under_a_host_shim(hostile):
+    """(b)"""
+    over = {}
+    for name, segs, w, h, R, _ in MC.hostile_inputs():
+        got, rec, orient, _, sh, d64 = hostile[name]
+        assert [int(c) for c in rec[:, 6]] == sh.colours(), f"{name}: the edge colours"
+        assert np.array_equal(rec[:, 0:6].astype(np.float64), np.array([e.p.ravel() for e in sh.edges]).reshape(-1, 6)), f"{name}: the edges"
+        assert orient == sh.orient, f"{name}: the orientation"
+        n = MC.over_tolerance(got, M.encode(d64, R))
+        if n:
+            over[name] = n
+        assert n <= MC.CAP, f"{name}: {n} texels are more than 1 LSB from the reference"
+    print(f"texels beyond 1 LSB per image (cap {MC.CAP}): {over or 'none in any image'}")
+    assert len(hostile) == len(MC.hostile_inputs()) >= 70
+
+
+def test_hostile_tile_culling_changes_no_texel(hostile):
+    """(c)"""
+    for name, (texels, _, _, nocull, _, _) in hostile.items():
+        assert np.array_equal(texels, nocull), f"{name}: {int((texels != nocull).any(axis=2).sum())} texels differ with culling off"
+
+
+def test_hostile_sign_against_the_winding_number(hostile):
+    """(d) on every outline that does not cross itself.  Where the reference and the winding number disagree the winding number is right:
+    that is what made step 1 of the specification turn folded quadratics into lines."""
+    checked = 0
+    for name, segs, w, h, R, simple in MC.hostile_inputs():
+        if not simple:
+            continue
+        got, _, _, _, _, d64 = hostile[name]
+        inside = MC.winding(segs, w, h) != 0
+        n = MC.check_sign(name + " (reference)", M.encode(d64, R), segs, w, h, R, d64[..., 3], inside)
+        assert n == MC.check_sign(name + " (kernel source)", got, segs, w, h, R, d64[..., 3], inside) > 0
+        checked += n
+    print(f"{checked} texels checked")
+
+
+def test_hostile_folded_quadratics_are_lines(hostile):
+    """step 1 on the cases that made it: the reference's shape (which the shim's records equal, see above)"""
+    rect = M.build_shape(MC.poly([(4, 4), (28, 4), (28, 20), (4, 20)]))
+    sh = hostile["quadratic folded onto its line"][4]
+    assert all(e.line for e in sh.edges) and np.array_equal([e.p for e in sh.edges], [e.p for e in rect.edges]) and sh.colours() == rect.colours()
+    assert [e.line for e in hostile["collinear control point inside the chord"][4].edges] == [False, True, True, True]  # an ordinary curve: kept
+    for name in ("control point on P2", "control point on P0"):
+        assert [e.line for e in hostile[name][4].edges] == [True] * 4, name
+    for name, k in (("control point 1e-05 from P2", 1), ("control point 1e-05 from P0", 1), ("control point 0.001 off the chord", 0)):  # off the line: kept
+        assert [e.line for e in hostile[name][4].edges] == [i != k for i in range(4)], name
+    texels, rec, _, _, sh, _ = hostile["one edge doubling back on itself"]
+    assert not sh.edges and rec.size == 0 and not texels.any()
 
 
 def test_reconstruction_through_draw_msdf(emulated):
