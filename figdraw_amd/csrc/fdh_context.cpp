@@ -514,6 +514,9 @@ uint32_t* Context::launch_blur(const LaunchJob& J, int p, uint32_t* cur, int row
   bp.node_pixels = (long long)(j.x1 - j.x0) * (j.y1 - j.y0);
   bp.fuse_draw = -1;
   bp.mx_w = (size_t)ph.blur < J.mx_w_h.size() ? J.mx_w_h[ph.blur] : nullptr;
+  // every pass below reads this frame's surface (`cur`) or, the V pass, what the H pass made of it (blur_tmp_): on an opaque frame the
+  // matrix-pipe kernels filter three channels (the fragments' sum was checked when they were built: Context::build_misc)
+  bp.opaque = J.opaque ? 1 : 0;
   bp.x0 = j.x0; bp.x1 = j.x1; bp.y0 = vy0; bp.y1 = vy1;
   if ((size_t)ph.blur < J.blur_fused.size() && J.blur_fused[ph.blur]) {
     uint32_t* other = cur == fb_ ? alt_ : fb_;
@@ -571,6 +574,7 @@ CompositeParams Context::composite_params(const LaunchJob& J, int p, uint32_t* c
   C.row_lo = row_lo; C.row_hi = row_hi;
   C.load_fb = full ? 0 : 1;
   C.clear_rgba8 = J.clear_rgba8;
+  C.opaque = J.opaque ? 1 : 0;
   C.direct = direct ? 1 : 0; C.direct_first = ph.first; C.direct_n = ph.count; C.binrec = J.dv.binrecs;
   C.order = full ? S.order_now : nullptr; C.order_next = full ? S.order_next : nullptr;
   C.deep_k8 = full ? S.deep_k8 : 0; C.deep_min = S.deep_min;

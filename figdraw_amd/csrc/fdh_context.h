@@ -411,6 +411,7 @@ struct LaunchJob {
   bool clear = true;
   bool latency_routes = true;  // the frame was recorded for the one-kernel blur routes (Context::pick_routes)
   uint32_t clear_rgba8 = 0xFFFFFFFFu;
+  bool opaque = false;     // the surface holds alpha 255 from the frame's first launch to its last (Context::decide_opaque)
   std::vector<Phase> phases;
   std::vector<BlurJob> blurs;
   std::vector<const uint4*> mx_w_h, mx_w_v;  // per blur job: weight fragments of the matrix-pipe passes (in the frame block), or null
@@ -579,7 +580,7 @@ class Context : public Recorder {
   // prepare's stages, in the order it takes them.  The order is part of their contract:
   //  - consolidate_pieces (a frame of more pieces than the run table holds) runs BEFORE fold_clear: the copy would carry the emptied box,
   //    and the guard restores the original lane only -- fdh_debug_record_digest would find an empty box for record 0 of such a frame;
-  //  - fold_clear runs before damage_frame_key: the key mixes the folded clear colour;
+  //  - fold_clear runs before damage_frame_key and decide_opaque: both read the folded clear colour;
   //  - patch_runs / gather_runs read a lane's device views after the lane was published (the mirrors are then where they will stay);
   //  - fence_staging comes last: everything this thread and the pool's threads stored into device memory is behind it.
   void describe_frame(LaunchJob& J);
@@ -588,6 +589,7 @@ class Context : public Recorder {
   void choose_fused_blurs(LaunchJob& J);
   void consolidate_pieces();                 // (only a frame of more pieces than the upload's run table holds)
   FoldGuard fold_clear(LaunchJob& J);
+  void decide_opaque(LaunchJob& J) const;    // J.opaque, from the FOLDED clear colour
   void damage_frame_key(LaunchJob& J) const;
   bool shadow_usable(const LaunchJob& J);
   bool tables_resident(const LaunchJob& J, bool shadow_ok);
@@ -735,7 +737,7 @@ class Context : public Recorder {
   // kStaging sets of lanes in rotation, each released when the upload that reads it has run (the bin launch behind it says so
   // through *seq_host_, Context::issue; an event where a frame has no bin launch): the host records
   // frames N + 1 .. while frame N's upload has not run yet (one set forced a stream sync per frame)
-  struct MxTables { int reach; std::vector<float> dense; std::vector<uint8_t> h, v; };  // k_blur_mx weight fragments of one filter
+  struct MxTables { int reach; std::vector<float> dense; std::vector<uint8_t> h, v; bool keeps_opaque = false; };  // k_blur_mx weight fragments of one filter
   std::vector<MxTables> mx_cache_;
   static constexpr int kStaging = 4;
   std::vector<std::unique_ptr<Lane>> lanes_[kStaging];

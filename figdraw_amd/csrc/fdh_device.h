@@ -539,6 +539,44 @@ __device__ __forceinline__ void blend_black(F4& F, float A, float ia) {
   F.x = __builtin_rintf(F.x * ia); F.y = __builtin_rintf(F.y * ia); F.z = __builtin_rintf(F.z * ia); F.w = __builtin_rintf(__builtin_fmaf(F.w, ia, A));
 }
 
+// ---- A texel of a surface KNOWN to be opaque (CompositeParams::opaque, the compositor builds <4 | 32>): three floats.  Every draw
+// reaches the surface through the blends above, and with A = 255 their alpha lane, rint(fma(255, 1 - sa, 255 sa)), is 255 for every
+// float sa in [-2^-10, 1 + 2^-10] (tests/test_opaque_host.py tries them all): the lane is a constant, so it is not kept.  Whatever reads
+// `.w` reads the literal -- the same IEEE operations on the same value as the four-float form runs.
+struct F4o {
+  float x, y, z;
+  static constexpr float w = 255.0f;
+  __host__ __device__ operator F4() const { return F4{x, y, z, 255.0f}; }
+};
+template <class T> __device__ __forceinline__ T unpack_texel(uint32_t c);
+template <> __device__ __forceinline__ F4 unpack_texel<F4>(uint32_t c) { return unpack255(c); }
+template <> __device__ __forceinline__ F4o unpack_texel<F4o>(uint32_t c) {  // (the alpha byte is 255 by the launch's contract: not looked at)
+  F4o r;
+  r.x = (float)(c & 255u);
+  r.y = (float)((c >> 8) & 255u);
+  r.z = (float)((c >> 16) & 255u);
+  return r;
+}
+__device__ __forceinline__ uint32_t pack255(F4o f) {  // three byte inserts into a word that holds the alpha byte already
+  uint32_t o = __builtin_amdgcn_cvt_pk_u8_f32(f.x, 0, 0xFF000000u);
+  o = __builtin_amdgcn_cvt_pk_u8_f32(f.y, 1, o);
+  return __builtin_amdgcn_cvt_pk_u8_f32(f.z, 2, o);
+}
+__device__ __forceinline__ void blend(F4o& F, float r, float g, float b, float sa) {
+  const float ia = 1.0f - sa, A = 255.0f * sa;
+  F.x = __builtin_rintf(__builtin_fmaf(F.x, ia, r * A));
+  F.y = __builtin_rintf(__builtin_fmaf(F.y, ia, g * A));
+  F.z = __builtin_rintf(__builtin_fmaf(F.z, ia, b * A));
+}
+__device__ __forceinline__ void blend_pre(F4o& F, f2 c_rg, f2 c_ba, float ia) {  // (c_ba.y, the alpha term, is not used)
+  F.x = __builtin_rintf(__builtin_fmaf(F.x, ia, c_rg.x));
+  F.y = __builtin_rintf(__builtin_fmaf(F.y, ia, c_rg.y));
+  F.z = __builtin_rintf(__builtin_fmaf(F.z, ia, c_ba.x));
+}
+__device__ __forceinline__ void blend_black(F4o& F, float /*A*/, float ia) {
+  F.x = __builtin_rintf(F.x * ia); F.y = __builtin_rintf(F.y * ia); F.z = __builtin_rintf(F.z * ia);
+}
+
 // atlas_rect_mask.frag:222-237
 __device__ __forceinline__ float rect_mask_alpha(const DrawRec& r, float cx, float cy) {
   float lx = (r.ox * cx + r.oy * cy) + r.inv_w;

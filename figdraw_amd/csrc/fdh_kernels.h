@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdlib>
 
 #include "fdh_types.h"
@@ -66,8 +67,13 @@ struct CompositeParams {
   int deep_k8 = 0;
   int deep_strip_min = 0;   // ... those of their strips that have at least this many draws to SHADE (strip_shade_count); the others keep their one wave
   int deep_min = 0;
+  // the surface is opaque when the launch starts and stays so (LaunchJob::opaque: a cleared frame whose folded clear colour has alpha 255):
+  // composite_build may take a build that does not carry the alpha lane, k_composite_tiles<4 | 32>.  (In the four bytes that were padding
+  // in front of `deep_out`: the block keeps its size and every field its place -- the builds that hold it in scratch keep their frames.)
+  int opaque = 0;
   uint32_t* deep_out = nullptr;
 };
+static_assert(offsetof(CompositeParams, deep_out) == offsetof(CompositeParams, opaque) + 4 && offsetof(CompositeParams, deep_out) + 8 == sizeof(CompositeParams), "`opaque` sits in what was padding");
 
 struct BlurParams {
   const uint32_t* src;
@@ -84,6 +90,10 @@ struct BlurParams {
   // pixels of the NODE's whole footprint (0: of this launch's region): which passes take the launch -- matrix pipe or VALU -- goes by
   // it, so that a row stripe of a large node runs the kernels the whole frame runs (their sums differ in the last bits)
   long long node_pixels = 0;
+  // every texel the pass reads has alpha 255 (an opaque frame's surface, or the H pass's output of one) and the weight fragments sum to
+  // the scale closely enough that the filtered alpha rounds to 255 (kMxOpaqueSumBound): the matrix-pipe kernels then filter three
+  // channels and write the constant.  The VALU passes do not look at it.
+  int opaque = 0;
 };
 
 // profile mode: the next launch_* call stamps these events with its kernel's own start / end (nullptr: plain launches)
@@ -97,7 +107,7 @@ inline int forced_kernel_paths() { static const int v = [] { const char* e = std
 // bytes, and the deep strips -- P.deep_k8 (a multiple of 8, at most the launch's bins rounded up to 8) where the launch can have them: the
 // full-frame launch of build <4> with both order pointers, then k_composite_deep's (deep); 0 elsewhere.  Applies FDH_FORCE_KERNEL_PATHS
 // to P's phase flags first (the kernels read them).
-struct CompositeBuild { int paths = 4; size_t lds = 0; int deep_k8 = 0; bool deep = false; };
+struct CompositeBuild { int paths = 4; size_t lds = 0; int deep_k8 = 0; bool deep = false; };  // (paths: 4 | 32 = <4> for an opaque surface)
 CompositeBuild composite_build(CompositeParams& P);
 void launch_composite(hipStream_t s, const DrawRec* draws, const QuadExt* exts, CompositeParams P);
 void launch_blur_h(hipStream_t s, const BlurParams& P);

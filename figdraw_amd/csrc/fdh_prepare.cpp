@@ -55,11 +55,14 @@ static void quantise_taps_f16(const BlurTaps& t, float* q) {
     q[k] = q[2 * r - k] = v;
   }
 }
-static void build_mx_weights(const BlurTaps& t, bool vertical, uint8_t* out) {
+// Returns how far the fragments' weights, summed per output over the whole window as the kernels sum them, lie from the scale (1024) at
+// most: what decides whether an all-255 plane filters to 255 (kMxOpaqueSumBound, fdh_context.h).
+static float build_mx_weights(const BlurTaps& t, bool vertical, uint8_t* out) {
   const int nk = mx_nk(t.reach, vertical), delta = mx_delta(t.reach, vertical);
   uint16_t* o = reinterpret_cast<uint16_t*>(out);
   float q[2 * kMaxBlurReach + 1];
   quantise_taps_f16(t, q);
+  double sum[32] = {};
   for (int m = 0; m < nk; m++)
     for (int lane = 0; lane < 64; lane++) {
       const int j = lane & 31, g = lane >> 5;
@@ -77,8 +80,12 @@ static void build_mx_weights(const BlurTaps& t, bool vertical, uint8_t* out) {
 #endif
         o[(((size_t)(2 * m) * 64 + lane) * 8) + e] = hi;
         o[(((size_t)(2 * m + 1) * 64 + lane) * 8) + e] = lo;
+        sum[j] += (double)half_value(hi) + (double)half_value(lo);
       }
     }
+  double dev = 0.0;
+  for (int j = 0; j < 32; j++) dev = std::max(dev, std::fabs(sum[j] - 1024.0));
+  return (float)dev;
 }
 
 void blur_weight_fragments(float blur_radius, bool vertical, float* dense, uint16_t* frag_bits, int* reach, int* k_steps) {
@@ -123,6 +130,7 @@ void Context::prepare(LaunchJob& J) {
   choose_fused_blurs(J);
   if (pieces_.size() * 3 + 2 > (size_t)kMaxUploadRuns) consolidate_pieces();  // more pieces than the upload's kernel-argument table holds
   const FoldGuard fold = fold_clear(J);
+  decide_opaque(J);
   damage_frame_key(J);
   const bool shadow_ok = shadow_usable(J), resident = tables_resident(J, shadow_ok);
   build_misc(J, resident);
@@ -258,6 +266,18 @@ Context::FoldGuard Context::fold_clear(LaunchJob& J) {
   return g;
 }
 
+// AN OPAQUE SURFACE.  A frame that is cleared with a colour of alpha 255 -- after clear folding: a translucent clear under an opaque
+// background panel counts -- holds alpha 255 on every pixel from its first launch to its last: every draw reaches the surface through
+// A' = rint(fma(A, 1 - sa, 255 sa)), which is 255 for A = 255 and every float sa the shading can produce (tests/test_opaque_host.py tries
+// every float in [-2^-10, 1 + 2^-10]), and the blur of an all-255 plane is 255 (the weight fragments sum to the scale: build_mx_weights,
+// kMxOpaqueSumBound).  The launches of such a frame may take kernels that do not carry the alpha channel: k_composite_tiles<4 | 32>, the
+// kOpaque forms of k_blur_mx / k_blur_fx.  Decided per frame and never carried over: a frame that is not cleared starts from a surface
+// others may have written (fdh_frame_device_ptr).  FDH_OPAQUE=0 turns it off (same pixels; one of the switches tools/suite_off_defaults.sh runs).
+void Context::decide_opaque(LaunchJob& J) const {
+  static const bool opaque_on = [] { const char* e = std::getenv("FDH_OPAQUE"); return !e || std::atoi(e) != 0; }();
+  J.opaque = opaque_on && clear_ && (J.clear_rgba8 >> 24) == 255u;
+}
+
 // Damage tracking: the frame key -- everything a bin's pixels depend on besides its lists and the records they index.  A tracked frame
 // whose key differs from the last tracked frame's is rendered in full (DamageTracker::launch), and so is one the tracking launches cannot
 // take: no clear (its starting pixels are not this frame's to rebuild), a full-frame blur that renders out of place (k_blur_fx flips the
@@ -333,11 +353,13 @@ void Context::build_misc(const LaunchJob& J, bool tables_resident) {
         c.reach = t.reach;
         c.dense.assign(t.dense + kBlurPad, t.dense + kBlurPad + 2 * t.reach + 1);
         c.h.resize(bh); c.v.resize(bv);
-        build_mx_weights(t, false, c.h.data());
-        build_mx_weights(t, true, c.v.data());
+        const float dev_h = build_mx_weights(t, false, c.h.data());
+        const float dev_v = build_mx_weights(t, true, c.v.data());
+        c.keeps_opaque = std::max(dev_h, dev_v) <= kMxOpaqueSumBound;
         mx_cache_.push_back(std::move(c));
         hit = &mx_cache_.back();
       }
+      if (!hit->keeps_opaque) throw Error(FDH_ERR_INVALID, "blur weights: the fragments' sum misses the scale (an opaque surface would not stay opaque)");
       std::memcpy(misc.data() + (F.mx_h[i] - o_misc), hit->h.data(), bh);
       std::memcpy(misc.data() + (F.mx_v[i] - o_misc), hit->v.data(), bv);
     }

@@ -170,6 +170,11 @@ __host__ __device__
 #endif
 inline int mx_krow(int g, int e, bool vertical) { return vertical ? (e & 3) + 8 * (e >> 2) + 4 * g : 8 * g + e; }
 constexpr size_t mx_table_bytes(int nk) { return (size_t)nk * 2 * 64 * 16; }  // [k-step][hi, lo][lane] x 8 halves
+// How far from the scale (1024) the weights an output meets may sum for an all-255 plane to filter to 255: the pass stores
+// round(255 sum / 1024), which is 255 while |sum - 1024| < 1024 x 0.5 / 255 = 2.0078.  Half of that for the weights (at 1.0 the exact value
+// lies within 0.25 of 255); the other half covers the f32 accumulation of the at most 16 kMxMaxNK = 176 products -- 176 x 2^-24 relative,
+// 0.003 in 255.  The carried rounding of quantise_taps_f16 keeps the sum to ~1e-7: the margin is seven orders of magnitude.
+constexpr float kMxOpaqueSumBound = 1.0f;
 
 struct AtlasView {
   const uint32_t* level[kMaxMips];

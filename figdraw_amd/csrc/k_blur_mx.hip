@@ -63,6 +63,20 @@ __device__ __forceinline__ void lds_dma4(const void* src, uint32_t lds) {
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(m0_saved) : "v"(src), "s"(lds) : "memory");
 }
+// An OPAQUE pass (BlurParams::opaque, template parameter kOpaque of both kernels below): every texel the pass reads has alpha 255 and the
+// weight fragments sum to the scale (fdh_prepare.cpp: build_mx_weights, kMxOpaqueSumBound), so the filtered alpha is 255 on every pixel.  Its operand
+// halves, its MFMA per k-step, its accumulator tile and its share of the hand-over and of the epilogue do not exist: three channels of four.
+constexpr int mx_channels(bool opaque) { return opaque ? 3 : 4; }
+// a block's texel from its accumulators: scale, RGBA8 (pack2); the opaque form inserts three bytes into a word that holds the alpha byte
+template <bool kOpaque, int NC> __device__ __forceinline__ uint32_t mx_texel(const f32x16 (&acc)[NC], int rr) {
+  if constexpr (kOpaque) {
+    uint32_t o = __builtin_amdgcn_cvt_pk_u8_f32(acc[0][rr] * kMxScale, 0, 0xFF000000u);
+    o = __builtin_amdgcn_cvt_pk_u8_f32(acc[1][rr] * kMxScale, 1, o);
+    return __builtin_amdgcn_cvt_pk_u8_f32(acc[2][rr] * kMxScale, 2, o);
+  } else {
+    return pack2(f2{acc[0][rr] * kMxScale, acc[1][rr] * kMxScale}, f2{acc[2][rr] * kMxScale, acc[3][rr] * kMxScale});
+  }
+}
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // One wave walks `T` blocks of 32 outputs along the filter direction over 32 lines (columns for the vertical pass, rows
@@ -78,9 +92,10 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 // never produced here: they were compositor pixels misread by packed-FP32 instructions while these kernels' v_mfma shared
 // the SIMD (tools/microbench/pk_vs_mfma.hip); the merged body merely ran slowly enough to hide it.
 // The library is now built without packed-FP32 instructions (csrc/Makefile, tools/lint_isa.py).
-template <int NK, bool kV>
+template <int NK, bool kV, bool kOpaque>
 __global__ __launch_bounds__(64 * mx_wg(NK, kV), kMxWaves) void k_blur_mx(BlurParams P, const DrawRec* __restrict__ draws, const QuadExt* __restrict__ exts, int T) {
   constexpr int R = mx_ring_slots(NK, kV);
+  constexpr int NC = mx_channels(kOpaque);
   extern __shared__ __attribute__((aligned(16))) uint32_t ring_wg[];  // R slots per wave
   constexpr int kWG = mx_wg(NK, kV);
   const int wave_in_wg = kWG > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
@@ -243,9 +258,9 @@ __global__ __launch_bounds__(64 * mx_wg(NK, kV), kMxWaves) void k_blur_mx(BlurPa
 #if FDH_TIMING
     const unsigned long long Tc = FDH_NOW();
 #endif
-    f32x16 acc[4];
+    f32x16 acc[NC];
 #pragma unroll
-    for (int c = 0; c < 4; c++)
+    for (int c = 0; c < NC; c++)
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[c][e] = 0.0f;
 #pragma unroll
@@ -261,33 +276,35 @@ __global__ __launch_bounds__(64 * mx_wg(NK, kV), kMxWaves) void k_blur_mx(BlurPa
         const uint4 lo4 = row4[(2 * g) ^ sw], hi4 = row4[(2 * g + 1) ^ sw];
         t8[0] = lo4.x; t8[1] = lo4.y; t8[2] = lo4.z; t8[3] = lo4.w; t8[4] = hi4.x; t8[5] = hi4.y; t8[6] = hi4.z; t8[7] = hi4.w;
       }
-      const h8 f0 = mx_frag<0>(t8), f1 = mx_frag<1>(t8), f2_ = mx_frag<2>(t8), f3 = mx_frag<3>(t8);
+      const h8 f0 = mx_frag<0>(t8), f1 = mx_frag<1>(t8), f2_ = mx_frag<2>(t8);
+      [[maybe_unused]] h8 f3 = f2_;
+      if constexpr (!kOpaque) f3 = mx_frag<3>(t8);
       if (kV) {  // weights x texels: D[output row][column]
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi[m], f0, acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi[m], f1, acc[1], 0, 0, 0);
         acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi[m], f2_, acc[2], 0, 0, 0);
-        acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi[m], f3, acc[3], 0, 0, 0);
+        if constexpr (!kOpaque) acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi[m], f3, acc[3], 0, 0, 0);
 #if FDH_MX_LO
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo[m], f0, acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo[m], f1, acc[1], 0, 0, 0);
         acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo[m], f2_, acc[2], 0, 0, 0);
-        acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo[m], f3, acc[3], 0, 0, 0);
+        if constexpr (!kOpaque) acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo[m], f3, acc[3], 0, 0, 0);
 #endif
       } else {   // texels x weights: D[row][output column]
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f0, whi[m], acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f1, whi[m], acc[1], 0, 0, 0);
         acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f2_, whi[m], acc[2], 0, 0, 0);
-        acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f3, whi[m], acc[3], 0, 0, 0);
+        if constexpr (!kOpaque) acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f3, whi[m], acc[3], 0, 0, 0);
 #if FDH_MX_LO
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f0, wlo[m], acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f1, wlo[m], acc[1], 0, 0, 0);
         acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f2_, wlo[m], acc[2], 0, 0, 0);
-        acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f3, wlo[m], acc[3], 0, 0, 0);
+        if constexpr (!kOpaque) acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f3, wlo[m], acc[3], 0, 0, 0);
 #endif
       }
     }
 #if FDH_TIMING
-    const unsigned long long Td = FDH_NOW() + (__builtin_amdgcn_readfirstlane(__float_as_uint(acc[0][0] + acc[1][0] + acc[2][0] + acc[3][0])) & 0u);
+    const unsigned long long Td = FDH_NOW() + (__builtin_amdgcn_readfirstlane(__float_as_uint(acc[0][0] + acc[1][0] + acc[2][0] + acc[NC - 1][0])) & 0u);
 #endif
     // the block's 32 x 32 pixels: lane = x, register rr = row (rr & 3) + 8 (rr >> 2) + 4 g
     const int bx = kV ? lb : as + 32 * b, by = kV ? as + 32 * b : lb;
@@ -296,7 +313,7 @@ __global__ __launch_bounds__(64 * mx_wg(NK, kV), kMxWaves) void k_blur_mx(BlurPa
     const bool x_ok = x >= P.x0 && x < P.x1;
 #pragma unroll
     for (int rr = 0; rr < 16; rr++)  // (scalar multiplies: the four channels sit in four accumulator tiles, a packed multiply would need two moves first)
-      pend[rr] = pack2(f2{acc[0][rr] * kMxScale, acc[1][rr] * kMxScale}, f2{acc[2][rr] * kMxScale, acc[3][rr] * kMxScale});
+      pend[rr] = mx_texel<kOpaque>(acc, rr);
     if (bx >= P.x0 && bx + 32 <= P.x1 && by >= P.y0 && by + 32 <= P.y1) {  // wave-uniform: the whole block lies in the region
       pmask = 0xffffu;
     } else {
@@ -312,8 +329,8 @@ __global__ __launch_bounds__(64 * mx_wg(NK, kV), kMxWaves) void k_blur_mx(BlurPa
       // coverage are plain replacements (the blend is exact there) and need nothing more.
       const bool core = bx >= core_x0 && bx + 32 <= core_x1 && by >= core_y0 && by + 32 <= core_y1;  // coverage alpha == 1 (wave-uniform)
       // the common block -- inside the core, every blurred texel opaque -- is done: one AND chain and one ballot decide it
-      bool replace_all = false;
-      if (core) {
+      bool replace_all = kOpaque && core;  // (an opaque pass: every blurred texel IS opaque)
+      if (!kOpaque && core) {
         uint32_t conj = pend[0];
 #pragma unroll
         for (int rr = 1; rr < 16; rr++) conj &= pend[rr];
@@ -386,7 +403,7 @@ __global__ __launch_bounds__(64 * mx_wg(NK, kV), kMxWaves) void k_blur_mx(BlurPa
           const float alpha = core ? 1.0f : __uint_as_float((rr < 8 ? sc0 : sc1)[(rr & 7) * 64 + lane]);
           const F4 bl = unpack255(pend[rr]);
           F4 Fd = unpack255(dstv[rr]);
-          const float sa = bl.w * k * alpha, A = 255.0f * sa;
+          const float sa = (kOpaque ? 255.0f : bl.w) * k * alpha, A = 255.0f * sa;
           // = blend(F, b.rgb / 255, sa) (blend_pre's arithmetic, FMA for FMA), kept scalar: in an earlier arrangement of this
           // block (coverage evaluated in a rolled 16-step loop) the packed f2 form gave red = 0 in lanes 48-63 of a few dozen
           // wavefronts per 4K frame while the scalar form was exact; the cause was never found and the current arrangement
@@ -465,10 +482,11 @@ constexpr int fx_wg_ksteps(int nkh) { return nkh + 2 * (kFxWaves - 1); }  // k-s
 // 2-KB LDS slots per WORKGROUP: both weight tables + the shared source window of one H-block row, twice (block i is read while block i + 1 lands)
 constexpr int fx_slots(int nkh, int nkv) { return nkh + nkv + 2 * fx_wg_ksteps(nkh); }
 constexpr float kMxMagic = 12582912.0f;  // 1.5 * 2^23: x + this, as f32, is round-to-nearest-even(x) in the low mantissa bits (|x| < 2^22)
-template <int NKH, int NKV>
+template <int NKH, int NKV, bool kOpaque>
 __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, const uint4* __restrict__ w_v, const DrawRec* __restrict__ draws, const QuadExt* __restrict__ exts, int T) {
   constexpr int HB = fx_vblocks(NKV);      // V block b reads H-blocks b .. b + HB - 1
   constexpr int NKW = fx_wg_ksteps(NKH);   // k-steps of the workgroup's shared source window
+  constexpr int NC = mx_channels(kOpaque);  // channels filtered
   extern __shared__ __attribute__((aligned(16))) uint32_t ring[];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint4* const hw = reinterpret_cast<const uint4*>(ring);                   // [2 NKH fragments][64 lanes] x 16 bytes
@@ -570,9 +588,9 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
 
   // the stash: k-step 2 p + s of it = rows 16 s .. 16 s + 15 of the H-block whose number is p mod HB, one operand (four VGPRs of
   // f16 pairs) per channel.  Indexed by constants only (phase<PH>): it lives in registers.
-  uint32_t stash[2 * HB][4][4];  // [k-step][channel][VGPR of f16 pairs]
+  uint32_t stash[2 * HB][NC][4];  // [k-step][channel][VGPR of f16 pairs]
   auto operand = [](const uint32_t (&u)[4]) { H8Bits o; o.u[0] = u[0]; o.u[1] = u[1]; o.u[2] = u[2]; o.u[3] = u[3]; return o.v; };
-  f32x16 acc[4];
+  f32x16 acc[NC];
   // phase PH = (H-block number) mod HB: round the horizontal product into the stash, then -- `vertical` -- multiply the block
   // that this H-block completes
   auto phase = [&](auto ph_tag, bool vertical) __attribute__((always_inline)) {
@@ -581,7 +599,7 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
     // front of the branch and turns "which stash slot" into 96 v_cndmask per block)
     asm volatile("; k_blur_fx: phase %0" ::"n"(PH));
 #pragma unroll
-    for (int c = 0; c < 4; c++)
+    for (int c = 0; c < NC; c++)
 #pragma unroll
       for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
@@ -593,17 +611,17 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
     // (pinned here: the half of the H-block this V block does not read would otherwise be rounded BEHIND the vertical product --
     // the optimizer sinks it towards its first use -- with its 32 accumulator registers alive all the way)
 #pragma unroll
-    for (int c = 0; c < 4; c++)
+    for (int c = 0; c < NC; c++)
 #pragma unroll
       for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
         for (int qq = 0; qq < 4; qq++) asm volatile("" : "+v"(stash[2 * PH + s2][c][qq]));
 #if FDH_TIMING
-    T_cv_mark = FDH_NOW() + (__builtin_amdgcn_readfirstlane(stash[2 * PH][0][0] ^ stash[2 * PH + 1][3][3]) & 0u);
+    T_cv_mark = FDH_NOW() + (__builtin_amdgcn_readfirstlane(stash[2 * PH][0][0] ^ stash[2 * PH + 1][NC - 1][3]) & 0u);
 #endif
     if (!vertical) return;
 #pragma unroll
-    for (int c = 0; c < 4; c++)
+    for (int c = 0; c < NC; c++)
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[c][e] = 0.0f;
     constexpr int first = (PH + 1) % HB;  // the V block's first H-block: number i - (HB - 1), i.e. (PH + 1) mod HB
@@ -619,12 +637,12 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi.v, operand(stash[slot][0]), acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi.v, operand(stash[slot][1]), acc[1], 0, 0, 0);
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi.v, operand(stash[slot][2]), acc[2], 0, 0, 0);
-      acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi.v, operand(stash[slot][3]), acc[3], 0, 0, 0);
+      if constexpr (!kOpaque) acc[NC - 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi.v, operand(stash[slot][NC - 1]), acc[NC - 1], 0, 0, 0);
 #if FDH_MX_LO
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo.v, operand(stash[slot][0]), acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo.v, operand(stash[slot][1]), acc[1], 0, 0, 0);
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo.v, operand(stash[slot][2]), acc[2], 0, 0, 0);
-      acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo.v, operand(stash[slot][3]), acc[3], 0, 0, 0);
+      if constexpr (!kOpaque) acc[NC - 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo.v, operand(stash[slot][NC - 1]), acc[NC - 1], 0, 0, 0);
 #endif
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -651,7 +669,7 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
 #endif
     // ---- horizontal product of H-block i: rows ws + 32 i .. + 31, columns xb .. xb + 31
 #pragma unroll
-    for (int c = 0; c < 4; c++)
+    for (int c = 0; c < NC; c++)
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[c][e] = 0.0f;
     {
@@ -667,13 +685,14 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
         lo4 = rowq[(2 * g) ^ sw]; hi4 = rowq[(2 * g + 1) ^ sw];
       };
       uint4 tl[3], th[3], wa[2], wb[2];  // raw texels of k-steps m, m + 1, m + 2 (rotating); weight fragments of k-steps m, m + 1
-      h8 fr[2][4];                       // operand halves of k-steps m, m + 1
+      h8 fr[2][NC];                      // operand halves of k-steps m, m + 1
       texels(0, tl[0], th[0]);
       wa[0] = hw[lane]; wb[0] = hw[64 + lane];
       if (NKH > 1) { texels(1, tl[1], th[1]); wa[1] = hw[2 * 64 + lane]; wb[1] = hw[3 * 64 + lane]; }
       {
         const uint32_t t8[8] = {tl[0].x, tl[0].y, tl[0].z, tl[0].w, th[0].x, th[0].y, th[0].z, th[0].w};
-        fr[0][0] = mx_frag<0>(t8); fr[0][1] = mx_frag<1>(t8); fr[0][2] = mx_frag<2>(t8); fr[0][3] = mx_frag<3>(t8);
+        fr[0][0] = mx_frag<0>(t8); fr[0][1] = mx_frag<1>(t8); fr[0][2] = mx_frag<2>(t8);
+        if constexpr (!kOpaque) fr[0][NC - 1] = mx_frag<3>(t8);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -686,25 +705,27 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][0], whi.v, acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][1], whi.v, acc[1], 0, 0, 0);
         acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][2], whi.v, acc[2], 0, 0, 0);
-        acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][3], whi.v, acc[3], 0, 0, 0);
+        if constexpr (!kOpaque) acc[NC - 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][NC - 1], whi.v, acc[NC - 1], 0, 0, 0);
         if (m + 1 < NKH) {
           const uint4 &a4 = tl[(m + 1) % 3], &b4 = th[(m + 1) % 3];
           const uint32_t t8[8] = {a4.x, a4.y, a4.z, a4.w, b4.x, b4.y, b4.z, b4.w};
-          fr[nxt][0] = mx_frag<0>(t8); fr[nxt][1] = mx_frag<1>(t8); fr[nxt][2] = mx_frag<2>(t8); fr[nxt][3] = mx_frag<3>(t8);
+          fr[nxt][0] = mx_frag<0>(t8); fr[nxt][1] = mx_frag<1>(t8); fr[nxt][2] = mx_frag<2>(t8);
+          if constexpr (!kOpaque) fr[nxt][NC - 1] = mx_frag<3>(t8);
         }
 #if FDH_MX_LO
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][0], wlo.v, acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][1], wlo.v, acc[1], 0, 0, 0);
         acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][2], wlo.v, acc[2], 0, 0, 0);
-        acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][3], wlo.v, acc[3], 0, 0, 0);
+        if constexpr (!kOpaque) acc[NC - 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[cur][NC - 1], wlo.v, acc[NC - 1], 0, 0, 0);
 #endif
         if (m + 2 < NKH) { wa[cur] = hw[(2 * m + 4) * 64 + lane]; wb[cur] = hw[(2 * m + 5) * 64 + lane]; }  // (this k-step's weights are in the MFMAs' hands)
         // the order above, made binding: DS reads (texels m + 2) | 4 MFMA | 16 VALU | [4 MFMA of the low halves |] DS reads (weights m + 2)
+        // (NC MFMA / 4 NC v_perm per k-step: 3 / 12 in an opaque pass)
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, NC, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4 * NC, 0);
 #if FDH_MX_LO
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, NC, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
 #else
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -713,7 +734,7 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
       }
     }
 #if FDH_TIMING
-    const unsigned long long Tc = FDH_NOW() + (__builtin_amdgcn_readfirstlane(__float_as_uint(acc[0][0] + acc[1][0] + acc[2][0] + acc[3][0])) & 0u);
+    const unsigned long long Tc = FDH_NOW() + (__builtin_amdgcn_readfirstlane(__float_as_uint(acc[0][0] + acc[1][0] + acc[2][0] + acc[NC - 1][0])) & 0u);
     T_wait += Tb - Ta; T_h += Tc - Tb;
 #endif
     const int b = i - (HB - 1);  // the V block whose last H-block this is
@@ -725,7 +746,7 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
 #endif
     phase(ph_tag, b >= 0);
 #if FDH_TIMING
-    const unsigned long long Td = FDH_NOW() + (__builtin_amdgcn_readfirstlane(__float_as_uint(acc[0][0] + acc[1][0] + acc[2][0] + acc[3][0])) & 0u);
+    const unsigned long long Td = FDH_NOW() + (__builtin_amdgcn_readfirstlane(__float_as_uint(acc[0][0] + acc[1][0] + acc[2][0] + acc[NC - 1][0])) & 0u);
     T_v += Td - Tc; T_cv += T_cv_mark - Tc2; T_dma += Tc2 - Tc;
 #endif
     if (b < 0) return;
@@ -735,7 +756,7 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
     uint32_t pmask = 0;
 #pragma unroll
     for (int rr = 0; rr < 16; rr++)
-      pend[rr] = pack2(f2{acc[0][rr] * kMxScale, acc[1][rr] * kMxScale}, f2{acc[2][rr] * kMxScale, acc[3][rr] * kMxScale});
+      pend[rr] = mx_texel<kOpaque>(acc, rr);
     if (bx >= P.x0 && bx + 32 <= P.x1 && by >= P.y0 && by + 32 <= P.y1) {
       pmask = 0xffffu;
     } else {
@@ -748,8 +769,8 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
     if (P.fuse_draw >= 0) {
       // atlas.frag:381-388 on the blurred texel just produced, blended over the live texel (src: dst is another surface, so
       // every pixel of the region is written: where the quad does not cover, the live texel passes through the blend unchanged)
-      bool replace_all = false;
-      if (core) {
+      bool replace_all = kOpaque && core;  // (an opaque pass: every blurred texel IS opaque)
+      if (!kOpaque && core) {
         uint32_t conj = pend[0];
 #pragma unroll
         for (int rr = 1; rr < 16; rr++) conj &= pend[rr];
@@ -823,7 +844,7 @@ __global__ __launch_bounds__(64 * kFxWaves, 2) void k_blur_fx(BlurParams P, cons
             const float alpha = al16[rr];
             const F4 bl = unpack255(pend[rr]);
             F4 Fd = unpack255(dstv[rr]);
-            const float sa = bl.w * k * alpha, A = 255.0f * sa, ia = 1.0f - sa;
+            const float sa = (kOpaque ? 255.0f : bl.w) * k * alpha, A = 255.0f * sa, ia = 1.0f - sa;
             Fd.x = __builtin_rintf(__builtin_fmaf(Fd.x, ia, bl.x * k * A));
             Fd.y = __builtin_rintf(__builtin_fmaf(Fd.y, ia, bl.y * k * A));
             Fd.z = __builtin_rintf(__builtin_fmaf(Fd.z, ia, bl.z * k * A));
@@ -892,43 +913,45 @@ static int mx_pick_t(long long per_cu, long long outputs_along, long long lines)
   for (int t = 1; t < 64; t++) if (line_groups * ((along_blocks + t - 1) / t) <= slots) return t;
   return 64;
 }
-template <int NK, bool kV> static void launch_blur_mx(hipStream_t s, const BlurParams& P, const DrawRec* draws, const QuadExt* exts) {
+template <int NK, bool kV, bool kOpaque> static void launch_blur_mx(hipStream_t s, const BlurParams& P, const DrawRec* draws, const QuadExt* exts) {
   constexpr size_t lds = (size_t)mx_ring_slots(NK, kV) * kMxSlot * sizeof(uint32_t);
   constexpr int kWG = mx_wg(NK, kV);
   static const int per_cu = [] {  // waves resident per CU, asked once per instantiation
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_blur_mx<NK, kV>, 64 * kWG, lds * kWG) != hipSuccess || n <= 0) n = std::min<int>(4 * kMxWaves, 160 / (mx_ring_slots(NK, kV) * 2)) / kWG;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_blur_mx<NK, kV, kOpaque>, 64 * kWG, lds * kWG) != hipSuccess || n <= 0) n = std::min<int>(4 * kMxWaves, 160 / (mx_ring_slots(NK, kV) * 2)) / kWG;
     return n * kWG;  // (waves)
   }();
   const int t = kV ? mx_pick_t(per_cu, P.y1 - P.y0, P.x1 - P.x0) : mx_pick_t(per_cu, P.x1 - P.x0, P.y1 - P.y0);
   const int a_lo = kV ? P.y0 : P.x0, a_hi = kV ? P.y1 : P.x1, l_lo = kV ? (P.x0 & ~31) : P.y0, l_hi = kV ? P.x1 : P.y1;
   const int total = ((a_hi - (a_lo & ~31) + 32 * t - 1) / (32 * t)) * ((l_hi - l_lo + 31) / 32);
-  FDH_LAUNCH((k_blur_mx<NK, kV>), dim3(8 * ((total + 8 * kWG - 1) / (8 * kWG))), dim3(64 * kWG), lds * kWG, s, P, draws, exts, t);
+  FDH_LAUNCH((k_blur_mx<NK, kV, kOpaque>), dim3(8 * ((total + 8 * kWG - 1) / (8 * kWG))), dim3(64 * kWG), lds * kWG, s, P, draws, exts, t);
 }
 template <bool kV> static bool launch_blur_mx_nk(hipStream_t s, const BlurParams& P, const DrawRec* draws, const QuadExt* exts) {
   // LDS-DMA moves 16-byte pieces: rows have to start on 16-byte boundaries
   if (!P.mx_w || (P.pitch & 3) || (reinterpret_cast<uintptr_t>(P.src) & 15) || P.W < 4) return false;
   const int nk = mx_nk(P.taps.reach, kV);
+#define FDH_MX(n) (P.opaque ? launch_blur_mx<n, kV, true>(s, P, draws, exts) : launch_blur_mx<n, kV, false>(s, P, draws, exts))
   switch (nk) {
-    case 3: launch_blur_mx<3, kV>(s, P, draws, exts); return true;
-    case 4: launch_blur_mx<4, kV>(s, P, draws, exts); return true;
-    case 5: launch_blur_mx<5, kV>(s, P, draws, exts); return true;
-    case 6: launch_blur_mx<6, kV>(s, P, draws, exts); return true;
-    case 7: launch_blur_mx<7, kV>(s, P, draws, exts); return true;
-    case 8: launch_blur_mx<8, kV>(s, P, draws, exts); return true;
-    case 9: launch_blur_mx<9, kV>(s, P, draws, exts); return true;
-    case 10: launch_blur_mx<10, kV>(s, P, draws, exts); return true;
-    case 11: launch_blur_mx<11, kV>(s, P, draws, exts); return true;  // reach 66 = the widest filter (radius clamp 64)
+    case 3: FDH_MX(3); return true;
+    case 4: FDH_MX(4); return true;
+    case 5: FDH_MX(5); return true;
+    case 6: FDH_MX(6); return true;
+    case 7: FDH_MX(7); return true;
+    case 8: FDH_MX(8); return true;
+    case 9: FDH_MX(9); return true;
+    case 10: FDH_MX(10); return true;
+    case 11: FDH_MX(11); return true;  // reach 66 = the widest filter (radius clamp 64)
     default: return false;
   }
+#undef FDH_MX
 }
 // Both passes in one kernel (k_blur_fx): instantiated for the filter widths whose two rings fit five waves' worth of LDS per CU
 // (NKH <= 6: tap reach <= 22, blur radius <= ~21); wider filters keep the two-pass route.
-template <int NKH, int NKV> static void launch_blur_fx(hipStream_t s, const BlurParams& P, const uint4* w_v, const DrawRec* draws, const QuadExt* exts) {
+template <int NKH, int NKV, bool kOpaque> static void launch_blur_fx(hipStream_t s, const BlurParams& P, const uint4* w_v, const DrawRec* draws, const QuadExt* exts) {
   constexpr size_t lds = (size_t)fx_slots(NKH, NKV) * kMxSlot * sizeof(uint32_t);  // per workgroup of kFxWaves waves
   static const int wg_per_cu = [] {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_blur_fx<NKH, NKV>, 64 * kFxWaves, lds) != hipSuccess || n <= 0) n = std::min<int>(8 / kFxWaves, (int)(160 * 1024 / lds));
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_blur_fx<NKH, NKV, kOpaque>, 64 * kFxWaves, lds) != hipSuccess || n <= 0) n = std::min<int>(8 / kFxWaves, (int)(160 * 1024 / lds));
     return n;
   }();
   const int n_strips = (P.x1 - (P.x0 & ~31) + 31) >> 5, n_sg = (n_strips + kFxWaves - 1) / kFxWaves, blocks = (P.y1 - (P.y0 & ~31) + 31) >> 5;
@@ -936,7 +959,7 @@ template <int NKH, int NKV> static void launch_blur_fx(hipStream_t s, const Blur
   int t = 2;  // (a one-block segment would filter three H-blocks per output block)
   while (t < 64 && (long long)n_sg * ((blocks + t - 1) / t) > slots) t++;
   const int total = n_sg * ((blocks + t - 1) / t), per = (total + 7) / 8;
-  FDH_LAUNCH((k_blur_fx<NKH, NKV>), dim3(8 * per), dim3(64 * kFxWaves), lds, s, P, w_v, draws, exts, t);
+  FDH_LAUNCH((k_blur_fx<NKH, NKV, kOpaque>), dim3(8 * per), dim3(64 * kFxWaves), lds, s, P, w_v, draws, exts, t);
 }
 bool blur_fused_supported(int reach, int W, int pitch) {
   const int nkh = mx_nk(reach, false), nkv = mx_nk(reach, true);
@@ -946,7 +969,7 @@ bool launch_blur_fused(hipStream_t s, const BlurParams& P, const uint4* w_v, con
   if (P.x1 <= P.x0 || P.y1 <= P.y0) return true;
   if (!P.mx_w || !w_v || !blur_fused_supported(P.taps.reach, P.W, P.pitch) || (reinterpret_cast<uintptr_t>(P.src) & 15)) return false;
   const int nkh = mx_nk(P.taps.reach, false), nkv = mx_nk(P.taps.reach, true);
-#define FDH_FX(a, b) if (nkh == a && nkv == b) { launch_blur_fx<a, b>(s, P, w_v, draws, exts); return true; }
+#define FDH_FX(a, b) if (nkh == a && nkv == b) { P.opaque ? launch_blur_fx<a, b, true>(s, P, w_v, draws, exts) : launch_blur_fx<a, b, false>(s, P, w_v, draws, exts); return true; }
   FDH_FX(3, 3) FDH_FX(4, 3) FDH_FX(4, 4) FDH_FX(5, 4) FDH_FX(5, 5) FDH_FX(6, 5) FDH_FX(6, 6)
 #undef FDH_FX
   return false;

@@ -200,6 +200,10 @@ constexpr int kWinCols = 64, kWinRows = 12, kWinStride = 68;
 // build <8>, for phases whose only draws off the fast paths are such quads (a rotated panel does not drag the slot path in);
 // bit 0 = the one-pixel-slot path (rotated / skewed quads, bezier strokes, rect-mask setup, minified images),
 // bit 1 = the 4-wide atlas path (axis-aligned glyphs, images at >= 1:1, MSDF).  0: SDF draws, clips and rect masks only.
+// bit 5 = the surface is known opaque (CompositeParams::opaque): <4 | 32>, the no-clip build without the texels' alpha lane (F4o,
+// fdh_device.h) -- same pixels as <4>, two of eight blend instructions per pixel and draw fewer.  Launches that walk lists only: a direct
+// launch (its opaque form came out with two spilled vector registers where <4, ., direct> has none, and a frame of a handful of draws is
+// latency, not arithmetic), a deep launch and a tracked frame's launches keep the generic <4>.
 // kFull: the launch that starts a frame -- every bin of the grid, from the clear colour (nothing is loaded), bins taken longest
 // list first, with the sort for the next frame riding along.  A symbol of its own, so that the dominant launch of a frame is a
 // row of its own in a rocprofv3 kernel summary (the later phases' launches cover a blur node's footprint and take microseconds).
@@ -264,7 +268,7 @@ __device__ __forceinline__ void composite_strip(const CompositeParams& P, const 
                                                 const int lane, const int shader_id);
 
 template <int kPaths, bool kFull, bool kDirect = false>
-__global__ __launch_bounds__(64, (kPaths & 16) ? kSlowAtlasWaves : (kPaths & 1) ? kSlowWaves : kPaths == 4 ? kUniformWaves : (kPaths & 2) ? kAtlasWaves : (kPaths & 8) ? kRotWaves : kFastWaves) void k_composite_tiles(
+__global__ __launch_bounds__(64, (kPaths & 16) ? kSlowAtlasWaves : (kPaths & 1) ? kSlowWaves : (kPaths & ~32) == 4 ? kUniformWaves : (kPaths & 2) ? kAtlasWaves : (kPaths & 8) ? kRotWaves : kFastWaves) void k_composite_tiles(
     // the sixteen dwords a wave needs before anything else, as leading scalar arguments: with kernel-argument preloading
     // (-amdgpu-kernarg-preload-count, csrc/Makefile) they arrive in SGPRs with the wave instead of through a first s_load
     const int* __restrict__ a_order, int* __restrict__ a_order_next, const uint32_t* __restrict__ a_counts, const uint2* __restrict__ a_lists,
@@ -298,7 +302,7 @@ __global__ __launch_bounds__(64, (kPaths & 16) ? kSlowAtlasWaves : (kPaths & 1) 
     // One extra wavefront per full-frame launch sorts THIS frame's bin counts for the NEXT frame's launch (any
     // permutation is a correct schedule, and list lengths barely change from frame to frame).  As a kernel of its own the
     // sort was a ~6 us serial step of every frame; here it runs beside 32 000 compositing waves.
-    order_bins_wave(P.counts, P.order_next, P.bin_nx, P.bin_nx * P.bin_ny, &mask_stack[0][0][0], threadIdx.x, (int)blockIdx.x, kPaths == 4 ? P.deep_min : 0, kPaths == 4 ? P.deep_out : nullptr);
+    order_bins_wave(P.counts, P.order_next, P.bin_nx, P.bin_nx * P.bin_ny, &mask_stack[0][0][0], threadIdx.x, (int)blockIdx.x, (kPaths & ~32) == 4 ? P.deep_min : 0, (kPaths & ~32) == 4 ? P.deep_out : nullptr);
     return;
   }
   int bin_local = xcd + 8 * (q / kStripsPerBin);
@@ -474,6 +478,7 @@ void launch_composite_uniform(hipStream_t s, const CompositeBuild& b, int grid, 
     FDH_LAUNCH((k_composite_deep<FDH_TU>), dim3(8 + P.deep_k8 * 16 + 8 * bins8 * kWgsPerBin), dim3(256), b.lds, s, draws, exts, P);
   } else if (b.paths == 2) launch_tiles_build<2>(s, b, grid, draws, exts, P);
   else if (b.paths == 0) launch_tiles_build<0>(s, b, grid, draws, exts, P);
+  else if (b.paths == (4 | 32)) launch_tiles_build<4 | 32>(s, b, grid, draws, exts, P);
   else launch_tiles_build<4>(s, b, grid, draws, exts, P);
 }
 void launch_composite_damage_uniform(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P,
@@ -501,6 +506,9 @@ CompositeBuild composite_build(CompositeParams& P) {
   const int bins8 = (P.bin_nx * P.bin_ny + 7) / 8;  // bins per XCD
   if (b.paths == 4 && P.load_fb == 0 && P.order && P.order_next) b.deep_k8 = std::min(P.deep_k8 & ~7, 8 * bins8);
   b.deep = b.deep_k8 > 0;
+  // an opaque surface (Context::prepare decides per frame): the no-clip build without the alpha lane, where the launch walks lists with one
+  // wave per strip.  (FDH_FORCE_KERNEL_PATHS has set the phase flags above: a forced build is not <4> and stays what was asked for.)
+  if (b.paths == 4 && P.opaque && !b.deep && !P.direct) b.paths = 4 | 32;
   // the clip stack (4 KB; 1 KB, what the bin-ordering wavefront needs, without clips) + the texel window of the atlas path; the deep launch: its ring
   b.lds = b.deep ? sizeof(uint32_t) * kDeepLdsDwords
                  : (P.has_masks ? sizeof(uint32_t) * kMaskDepth * 64 : sizeof(uint32_t) * 256) +
@@ -510,6 +518,7 @@ CompositeBuild composite_build(CompositeParams& P) {
 void launch_composite_damage(hipStream_t s, const DrawRec* draws, const QuadExt* exts, CompositeParams P, const int* list, const uint32_t* count,
                              int grid) {
   if (grid <= 0 || P.bin_nx <= 0 || P.bin_ny <= 0) return;
+  P.opaque = 0;  // (k_composite_damage has the generic builds only: same pixels)
   const CompositeBuild b = composite_build(P);  // (a tracked frame's partial launches have no order: no deep strips)
   P.n_wg = grid;
   if (b.paths == 19) launch_damage<19>(s, b, grid, draws, exts, P, list, count);

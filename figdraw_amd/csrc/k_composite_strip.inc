@@ -7,6 +7,11 @@
   constexpr int kStripsPerBin = kWgsPerBin * kWavesPerWg;  // 16
   constexpr int mslot = 0;
   constexpr bool kBlender = kRole == 1, kShader = kRole == 2;
+  // <4 | 32>: the no-clip build for a frame whose surface is known opaque (CompositeParams::opaque) -- the strip's texels are three floats
+  // (F4o, fdh_device.h): no alpha lane in any blend, a constant alpha byte in the pack
+  constexpr bool kOpaque = (kPaths & 32) != 0;
+  static_assert(!kOpaque || (kPaths == (4 | 32) && kRole == 0), "the opaque form exists for the no-clip build only");
+  using FT = std::conditional_t<kOpaque, F4o, F4>;
   uint32_t (*mask_stack)[kMaskDepth][64] = reinterpret_cast<uint32_t (*)[kMaskDepth][64]>(composite_lds);
   const DeepRing ring(composite_lds);
   uint32_t rank = 0, unit = 0;  // deep strips: source terms / shading units (a draw, or a run of draws over one distance field) so far in the list
@@ -46,17 +51,17 @@
   const bool row_ok = py < P.H;
   const bool vec_ok = row_ok && px0 + 3 < P.W && (P.pitch & 3) == 0;  // whole 16-byte group inside the frame
   const size_t pix = (size_t)py * P.pitch + px0;
-  F4 F0, F1, F2, F3;
-  F0 = F1 = F2 = F3 = unpack255(P.clear_rgba8);
+  FT F0, F1, F2, F3;
+  F0 = F1 = F2 = F3 = unpack_texel<FT>(P.clear_rgba8);
   if (!kFull && P.load_fb) {
     if (vec_ok) {
       const uint4 q = *reinterpret_cast<const uint4*>(P.fb + pix);
-      F0 = unpack255(q.x); F1 = unpack255(q.y); F2 = unpack255(q.z); F3 = unpack255(q.w);
+      F0 = unpack_texel<FT>(q.x); F1 = unpack_texel<FT>(q.y); F2 = unpack_texel<FT>(q.z); F3 = unpack_texel<FT>(q.w);
     } else if (row_ok) {
-      if (px0 + 0 < P.W) F0 = unpack255(P.fb[pix + 0]);
-      if (px0 + 1 < P.W) F1 = unpack255(P.fb[pix + 1]);
-      if (px0 + 2 < P.W) F2 = unpack255(P.fb[pix + 2]);
-      if (px0 + 3 < P.W) F3 = unpack255(P.fb[pix + 3]);
+      if (px0 + 0 < P.W) F0 = unpack_texel<FT>(P.fb[pix + 0]);
+      if (px0 + 1 < P.W) F1 = unpack_texel<FT>(P.fb[pix + 1]);
+      if (px0 + 2 < P.W) F2 = unpack_texel<FT>(P.fb[pix + 2]);
+      if (px0 + 3 < P.W) F3 = unpack_texel<FT>(P.fb[pix + 3]);
     }
   }
   float mk0 = 1.0f, mk1 = 1.0f, mk2 = 1.0f, mk3 = 1.0f;  // NfClipContent stack product (1 = maskTexEnabled false)
@@ -235,7 +240,7 @@
     // inq (wave-uniform, from the list entry): the strip lies wholly inside the quad's pixel bounds
     // (rk: a deep strip's shader puts the draw's source alphas into the ring as source term rk instead of blending them -- deep_consume is the rest)
     auto edge_blend = [&](const DrawRec& r, const uint32_t mode, const bool ellip, const bool inq, const float m_p2, const float m_p3, const float m_f0, const float m_f1,
-                          const u32x4 m_col, const f2 lxa, const f2 lxb, const float pyy, const f2 da, const f2 db, F4& A0, F4& A1, F4& A2, F4& A3, const uint32_t rk) __attribute__((always_inline)) {
+                          const u32x4 m_col, const f2 lxa, const f2 lxb, const float pyy, const f2 da, const f2 db, FT& A0, FT& A1, FT& A2, FT& A3, const uint32_t rk) __attribute__((always_inline)) {
       f2 ala, alb;  // coverage
       if (mode == 3u) {
         ala = {cover_aa(da.x, r.aa), cover_aa(da.y, r.aa)}; alb = {cover_aa(db.x, r.aa), cover_aa(db.y, r.aa)};
@@ -381,7 +386,7 @@
             colL.z = tri_lerp(tl.z, c0u.z, br.z, tr.z, s0, t) * inv255;
             colL.w = tri_lerp(tl.w, c0u.w, br.w, tr.w, s0, t) * inv255;
           }
-          auto texel_px = [&](const int k, F4& F, const float mk, const float rm) __attribute__((always_inline)) {
+          auto texel_px = [&](const int k, FT& F, const float mk, const float rm) __attribute__((always_inline)) {
             const F4 a = unpack255(run.v[k]);
             F4 col = colL;
             if (!lane_col) {  // wave-uniform
@@ -490,7 +495,7 @@
           colL.w = tri_lerp(tl.w, c0u.w, br.w, tr.w, sK[0], t) * inv255;
         }
         const bool msdf3 = msdf && !is_mtsdf;  // the distance is the median of r, g, b: the alpha channel is not sampled
-        auto pixel = [&](const int k, F4& F, const float mk, const float rm) __attribute__((always_inline)) {
+        auto pixel = [&](const int k, FT& F, const float mk, const float rm) __attribute__((always_inline)) {
           const F4 a = unpack255(q00[k]), b = unpack255(q01[k]), c = unpack255(q10[k]), d = unpack255(q11[k]);
           const float ax = axK[k];
           F4 col = colL;
@@ -1001,7 +1006,7 @@
         for (int k = 0; k < 4; k++) {
           const F4 fc = eval_fill_rec(r, colv[k], fill_mode, u[k], vv[k]);
           const float mkk = k == 0 ? mk0 : k == 1 ? mk1 : k == 2 ? mk2 : mk3, rmk = k == 0 ? rm0 : k == 1 ? rm1 : k == 2 ? rm2 : rm3;
-          F4& F = k == 0 ? F0 : k == 1 ? F1 : k == 2 ? F2 : F3;
+          FT& F = k == 0 ? F0 : k == 1 ? F1 : k == 2 ? F2 : F3;
           blend(F, fc.x, fc.y, fc.z, cov[k] ? fc.w * alpha[k] * mkk * rmk : 0.0f);
         }
         return;
@@ -1031,7 +1036,7 @@
               blend(F0, s.r, s.g, s.b, a);
             }
           }
-          { const F4 t = F0; F0 = F1; F1 = F2; F2 = F3; F3 = t; }
+          { const FT t = F0; F0 = F1; F1 = F2; F2 = F3; F3 = t; }
           { const float t = mk0; mk0 = mk1; mk1 = mk2; mk2 = mk3; mk3 = t; }
           { const float t = rm0; rm0 = rm1; rm1 = rm2; rm2 = rm3; rm3 = t; }
         }

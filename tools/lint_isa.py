@@ -7,7 +7,7 @@ for every `pair * other.y` broadcast) now and then reads that operand as 0 in la
 same SIMD is issuing v_mfma.  figdraw's matrix-pipe blur passes of one context run beside the compositor waves of the
 others, so the product is built with -packed-fp32-ops (measured: not slower) and this script keeps it that way.
 
-Second check: k_composite_tiles<0|2|4> are compiled with -structurizecfg-skip-uniform-regions (csrc/Makefile, the FDH_TU note in
+Second check: k_composite_tiles<0|2|4|36> are compiled with -structurizecfg-skip-uniform-regions (csrc/Makefile, the FDH_TU note in
 k_composite.hip), which is only sound while its draw loop nest holds no divergent branch.  The loop nest -- every backward
 branch whose range holds the draw loop's s_ff1_i32_b64 -- must therefore not write the exec mask.
 
@@ -42,7 +42,7 @@ def code_objects(blob: bytes):
         at += len(MAGIC)
 
 
-UNIFORM_KERNELS = tuple("k_composite_tilesILi%dELb%dE" % (paths, full) for paths in (4, 0, 2) for full in (1, 0)) + ("k_composite_deepILi1EE",) + \
+UNIFORM_KERNELS = tuple("k_composite_tilesILi%dELb%dE" % (paths, full) for paths in (4, 0, 2, 36) for full in (1, 0)) + ("k_composite_deepILi1EE",) + \
     tuple("k_composite_damageILi%dELb%dE" % (paths, full) for paths in (4, 0, 2) for full in (1, 0))  # (damage tracking's launches, same unit)
 # writes of the exec mask: s_*saveexec*, any scalar instruction whose destination is exec / exec_lo / exec_hi, and the VOPC
 # compares that write exec directly (v_cmpx_*)
