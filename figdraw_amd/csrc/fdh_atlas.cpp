@@ -1,4 +1,4 @@
-// fdh_atlas.cpp -- the image atlas: skyline packer, level chains, glyph images and outlines, the Flippy container.
+// fdh_atlas.cpp -- class Atlas (fdh_atlas.h), the image atlas: directory and skyline packer, level chains, glyph images and outlines, the Flippy container.
 #include "fdh_context.h"
 #include "fdh_msdf_host.h"
 
@@ -8,39 +8,69 @@
 
 namespace fdh {
 
-// ------------------------------------------------------------------ atlas (glcontext.nim:536-641, textures.nim:88-119)
-void Context::alloc_atlas(int size) {
-  int s = 1;
-  while (s < size) s <<= 1;  // the samplers mask coordinates: keep the atlas a power of two
-  for (auto& l : atlas_levels_) { if (l) (void)hipFree(l); l = nullptr; }
-  atlas_size_ = s;
-  n_levels_ = 0;
-  for (int ls = s; ls >= 1 && n_levels_ < kMaxMips; ls >>= 1) {
-    if (!host_only_) {
-      FDH_HIP(hipMalloc((void**)&atlas_levels_[n_levels_], (size_t)ls * ls * 4));
-      FDH_HIP(hipMemsetAsync(atlas_levels_[n_levels_], 0, (size_t)ls * ls * 4, stream_));
+// ------------------------------------------------------------------ directory and packer (glcontext.nim:536-641, textures.nim:88-119)
+void Atlas::init(int size, bool device, hipStream_t s) {
+  device_ = device;
+  initial_size_ = size > 0 ? size : 1024;  // newContext default, glcontext.nim:255-261
+  alloc(initial_size_, s);
+}
+// An empty atlas of `size` (rounded up to a power of two) takes the place of this one.  The new levels are allocated FIRST (DeviceBuf::reserve's
+// rule): a failing hipMalloc frees what it got and leaves the old atlas whole -- levels, entries, skyline, size and epoch.  For the
+// length of a grow both atlases exist: peak memory is the new one plus the old one.
+void Atlas::alloc(int size, hipStream_t s) {
+  int sz = 1;
+  while (sz < size) sz <<= 1;  // the samplers mask coordinates: keep the atlas a power of two
+  uint32_t* fresh[kMaxMips] = {};
+  int n = 0;
+  try {
+    for (int ls = sz; ls >= 1 && n < kMaxMips; ls >>= 1) {
+      if (device_) {
+        FDH_HIP(hipMalloc((void**)&fresh[n], (size_t)ls * ls * 4));
+        FDH_HIP(hipMemsetAsync(fresh[n], 0, (size_t)ls * ls * 4, s));
+      }
+      n++;
     }
-    n_levels_++;
-    if (ls == 1) break;
+    if (device_) FDH_HIP(hipStreamSynchronize(s));  // host uploads (upload_rect) are not ordered behind the stream: the zeros are there first
+  } catch (...) {
+    for (auto l : fresh) if (l) (void)hipFree(l);
+    throw;
   }
-  heights_.assign((size_t)s, 0);
+  release_levels();
+  std::copy(fresh, fresh + kMaxMips, levels_);
+  size_ = sz;
+  n_levels_ = n;
+  heights_.assign((size_t)sz, 0);
   entries_.clear();
-  atlas_epoch_++;  // cached draw records of image nodes carry atlas positions (RetainedRoot::atlas_epoch)
+  epoch_++;
 }
-void Context::reset_atlas(int minimum_size) {
-  sync();
-  int s = initial_atlas_size_;
-  while (s < minimum_size) s *= 2;  // plannedAtlasSize
-  alloc_atlas(s);
+void Atlas::release_levels() {
+  for (auto& l : levels_) { if (l) (void)hipFree(l); l = nullptr; }
 }
-int64_t Context::atlas_packed_area() const {
+void Atlas::release() {
+  release_levels();
+  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release();
+}
+void Atlas::reset(int minimum_size, hipStream_t s) {
+  int sz = initial_size_;
+  while (sz < minimum_size) sz *= 2;  // plannedAtlasSize
+  alloc(sz, s);
+}
+int64_t Atlas::packed_area() const {
   int64_t a = 0;
   for (auto h : heights_) a += h;
   return a;
 }
-void Context::find_empty_rect(int w, int h, int* ox, int* oy) {  // glcontext.nim:541-579
+AtlasView Atlas::view() const {
+  AtlasView v{};
+  for (int l = 0; l < kMaxMips; l++) v.level[l] = levels_[l];
+  v.size = size_; v.n_levels = n_levels_;
+  return v;
+}
+// Every put's way into the directory: the skyline search (glcontext.nim:541-579), growing until the image fits, then the entry, the
+// epoch and the caller's out_rect.  The returned entry has no ink boxes.
+AtlasEntry& Atlas::place(hipStream_t s, int64_t key, int w, int h, int out_rect[4]) {
   for (;;) {
-    const int S = atlas_size_, M = atlas_margin_;
+    const int S = size_, M = margin_;
     const int iw = w + M * 2, ih = h + M * 2;
     int lowest = S, at = 0;
     for (int i = 0; i < S; i++) {
@@ -56,20 +86,21 @@ void Context::find_empty_rect(int w, int h, int* ox, int* oy) {  // glcontext.ni
     }
     if (lowest + ih > S) {
       if (S >= 16384) throw Error(FDH_ERR_ATLAS_FULL, "atlas full at 16384^2");
-      sync();
-      alloc_atlas(S * 2);  // grow(): resetImageAtlas(atlasSize * 2) drops every entry (glcontext.nim:536-539)
+      alloc(S * 2, s);  // grow(): resetImageAtlas(atlasSize * 2) drops every entry (glcontext.nim:536-539)
       continue;
     }
     for (int j = at; j < at + iw; j++) heights_[j] = (uint16_t)(lowest + ih + M * 2);
-    *ox = at + M;
-    *oy = lowest + M;
-    return;
+    const int x = at + M, y = lowest + M;
+    AtlasEntry& e = entries_[key] = AtlasEntry{x, y, w, h, false, {}, {}};
+    epoch_++;
+    if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
+    return e;
   }
 }
-void Context::upload_atlas_rect(int level, int x, int y, int w, int h, const uint8_t* rgba) {
-  const int LS = atlas_size_ >> level;
-  if (x < 0 || y < 0 || x + w > LS || y + h > LS || w <= 0 || h <= 0 || host_only_) return;
-  FDH_HIP(hipMemcpy2D(atlas_levels_[level] + (size_t)y * LS + x, (size_t)LS * 4, rgba, (size_t)w * 4, (size_t)w * 4, h,
+void Atlas::upload_rect(int level, int x, int y, int w, int h, const uint8_t* rgba) {
+  const int LS = size_ >> level;
+  if (x < 0 || y < 0 || x + w > LS || y + h > LS || w <= 0 || h <= 0 || !device_) return;
+  FDH_HIP(hipMemcpy2D(levels_[level] + (size_t)y * LS + x, (size_t)LS * 4, rgba, (size_t)w * 4, (size_t)w * 4, h,
                       hipMemcpyHostToDevice));  // synchronous: image uploads are rare and the source is pageable
 }
 // pixie's Image.minifyBy2 on premultiplied RGBA8 (the arithmetic the reference's data/img1.flippy pins: its stored levels are this
@@ -94,18 +125,14 @@ static void minify_by2_host(const uint8_t* src, int w, int h, uint8_t* dst) {
     }
   }
 }
-void Context::put_levels(int x, int y, int w, int h, const uint8_t* rgba) {
-  // updateSubImage: level chain by repeated minifyBy2 while width > 1 and height > 1 (textures.nim:106-119).
+void Atlas::put_levels(int x, int y, int w, int h, const uint8_t* rgba) {  // the level chain by repeated minifyBy2
   std::vector<uint8_t> cur(rgba, rgba + (size_t)w * h * 4), nxt;
-  int cw = w, ch = h, lx = x, ly = y, level = 0;
-  while (cw > 1 && ch > 1 && level < n_levels_) {
-    upload_atlas_rect(level, lx, ly, cw, ch, cur.data());
-    const int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
-    nxt.assign((size_t)nw * nh * 4, 0);
+  each_level(x, y, w, h, [&](int level, int lx, int ly, int cw, int ch) {
+    upload_rect(level, lx, ly, cw, ch, cur.data());
+    nxt.assign((size_t)((cw + 1) / 2) * ((ch + 1) / 2) * 4, 0);
     minify_by2_host(cur.data(), cw, ch, nxt.data());
     cur.swap(nxt);
-    cw = nw; ch = nh; lx /= 2; ly /= 2; level++;
-  }
+  });
 }
 // the ink boxes of an image whose texels the host holds (AtlasEntry): one pass, sixteen running boxes
 static void measure_ink(AtlasEntry& e, const uint8_t* rgba) {
@@ -136,52 +163,34 @@ static void measure_ink(AtlasEntry& e, const uint8_t* rgba) {
   }
   e.has_ink = true;
 }
-void Context::put_image(int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]) {
+void Atlas::put_image(hipStream_t s, int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]) {
   if (w <= 0 || h <= 0 || !rgba) throw Error(FDH_ERR_INVALID, "put_image: empty image");
-  if (!host_only_) FDH_HIP(hipSetDevice(device_));
-  int x, y;
-  find_empty_rect(w, h, &x, &y);
-  AtlasEntry ent{x, y, w, h};
-  measure_ink(ent, rgba);
-  entries_[key] = ent;
-  atlas_epoch_++;
-  sync();  // a frame in flight may still sample the atlas
-  put_levels(x, y, w, h, rgba);
-  if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
+  AtlasEntry& e = place(s, key, w, h, out_rect);
+  measure_ink(e, rgba);
+  put_levels(e.x, e.y, w, h, rgba);
 }
 // A rasterised glyph on its way into the atlas, processed on the device: optional LCD filter (applyLcdFilter, common/
 // textrasters/pixie_raster.nim:12-43, what renderPixieGlyph does between fillText and loadGlyphImage :83-91), then the
 // level chain of updateSubImage (textures.nim:106-119) -- every step a kernel on the context's stream.
-void Context::put_glyph_image(int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]) {
+void Atlas::put_glyph_image(hipStream_t s, int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]) {
   if (w <= 0 || h <= 0 || !rgba) throw Error(FDH_ERR_INVALID, "put_glyph_image: empty image");
   if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) throw Error(FDH_ERR_INVALID, "put_glyph_image: unknown flag");
-  if (flags & FDH_GLYPH_LCD_CONTEXT) flags = text_lcd_filtering_ ? FDH_GLYPH_LCD_FILTER : 0u;  // as setTextLcdFilteringEnabled said
-  int x, y;
-  find_empty_rect(w, h, &x, &y);
-  entries_[key] = AtlasEntry{x, y, w, h, false, {}, {}};
-  atlas_epoch_++;
-  if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
-  if (host_only_) return;
-  FDH_HIP(hipSetDevice(device_));
-  sync();  // a frame in flight may still sample the atlas
   const size_t n = (size_t)w * h;
-  glyph_a_.reserve(n);
-  glyph_b_.reserve(n);
-  FDH_HIP(hipMemcpyAsync(glyph_a_.ptr, rgba, n * 4, hipMemcpyHostToDevice, stream_));
-  glyph_to_atlas(glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, flags);
+  if (device_) { glyph_a_.reserve(n); glyph_b_.reserve(n); }
+  const AtlasEntry& e = place(s, key, w, h, out_rect);
+  if (!device_) return;
+  FDH_HIP(hipMemcpyAsync(glyph_a_.ptr, rgba, n * 4, hipMemcpyHostToDevice, s));
+  glyph_to_atlas(s, glyph_a_.ptr, glyph_b_.ptr, w, h, e.x, e.y, flags);
 }
 // device image -> (LCD filter) -> atlas level chain, all on the context's stream; waits for it (the caller's buffers are free after)
-void Context::glyph_to_atlas(uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags) {
-  if (flags & FDH_GLYPH_LCD_FILTER) { launch_lcd_filter(stream_, cur, nxt, w, h); std::swap(cur, nxt); }
-  int cw = w, ch = h, lx = x, ly = y, level = 0;
-  while (cw > 1 && ch > 1 && level < n_levels_) {
-    launch_atlas_blit(stream_, atlas_levels_[level], atlas_size_ >> level, lx, ly, cur, cw, ch);
-    const int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
-    launch_minify2(stream_, cur, nxt, cw, ch);
+void Atlas::glyph_to_atlas(hipStream_t s, uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags) {
+  if (flags & FDH_GLYPH_LCD_FILTER) { launch_lcd_filter(s, cur, nxt, w, h); std::swap(cur, nxt); }
+  each_level(x, y, w, h, [&](int level, int lx, int ly, int cw, int ch) {
+    launch_atlas_blit(s, levels_[level], size_ >> level, lx, ly, cur, cw, ch);
+    launch_minify2(s, cur, nxt, cw, ch);
     std::swap(cur, nxt);
-    cw = nw; ch = nh; lx /= 2; ly /= 2; level++;
-  }
-  FDH_HIP(hipStreamSynchronize(stream_));
+  });
+  FDH_HIP(hipStreamSynchronize(s));
   FDH_HIP(hipGetLastError());
 }
 
@@ -196,7 +205,7 @@ static int flatten_count(const float* q) {
   const int n = (int)std::ceil(std::sqrt(dev * 10.0f));  // error of n chords = dev / (4 n^2) <= 0.025 px
   return n < 1 ? 1 : (n > 64 ? 64 : n);
 }
-void Context::put_glyph_outline(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) {
+void Atlas::put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) {
   if (w <= 0 || h <= 0 || w > 4096 || h > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_outline: image size must be in 1..4096");
   if (n < 0 || (n > 0 && !segs)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: bad outline");
   if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT | FDH_GLYPH_MTSDF | 0xFF00u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: unknown flag");
@@ -204,10 +213,9 @@ void Context::put_glyph_outline(int64_t key, int w, int h, const float* segs, in
   if (sdf_range && (!(flags & FDH_GLYPH_MTSDF) || sdf_range > 64u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance range needs FDH_GLYPH_MTSDF and is at most 64");
   if (flags & FDH_GLYPH_MTSDF) {
     if (flags & (FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field takes no LCD filter");
-    put_glyph_mtsdf(key, w, h, segs, n, sdf_range ? (float)sdf_range : 4.0f, out_rect);
+    put_glyph_mtsdf(s, key, w, h, segs, n, sdf_range ? (float)sdf_range : 4.0f, out_rect);
     return;
   }
-  if (flags & FDH_GLYPH_LCD_CONTEXT) flags = text_lcd_filtering_ ? FDH_GLYPH_LCD_FILTER : 0u;
   std::vector<float> lines;
   lines.reserve((size_t)n * 16);
   for (int i = 0; i < n; i++) {
@@ -223,50 +231,43 @@ void Context::put_glyph_outline(int64_t key, int w, int h, const float* segs, in
       px = x; py = y;
     }
   }
-  int x, y;
-  find_empty_rect(w, h, &x, &y);
-  entries_[key] = AtlasEntry{x, y, w, h, false, {}, {}};
-  atlas_epoch_++;
-  if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
-  if (host_only_) return;
-  FDH_HIP(hipSetDevice(device_));
-  sync();
   const size_t npx = (size_t)w * h, m = lines.size() / 4;
-  glyph_a_.reserve(npx);
-  glyph_b_.reserve(npx);
-  glyph_lines_.reserve(std::max<size_t>(lines.size(), 4));
-  glyph_acc_.reserve((size_t)h * (w + 2));
-  if (m) FDH_HIP(hipMemcpyAsync(glyph_lines_.ptr, lines.data(), lines.size() * sizeof(float), hipMemcpyHostToDevice, stream_));
-  launch_rasterize_lines(stream_, reinterpret_cast<const float4*>(glyph_lines_.ptr), (int)m, w, h, glyph_acc_.ptr, glyph_a_.ptr);
-  glyph_to_atlas(glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, flags);  // (synchronises: `lines` stays alive until then)
+  if (device_) {
+    glyph_a_.reserve(npx);
+    glyph_b_.reserve(npx);
+    glyph_lines_.reserve(std::max<size_t>(lines.size(), 4));
+    glyph_acc_.reserve((size_t)h * (w + 2));
+  }
+  const AtlasEntry& e = place(s, key, w, h, out_rect);
+  if (!device_) return;
+  if (m) FDH_HIP(hipMemcpyAsync(glyph_lines_.ptr, lines.data(), lines.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  launch_rasterize_lines(s, reinterpret_cast<const float4*>(glyph_lines_.ptr), (int)m, w, h, glyph_acc_.ptr, glyph_a_.ptr);
+  glyph_to_atlas(s, glyph_a_.ptr, glyph_b_.ptr, w, h, e.x, e.y, flags);  // (synchronises: `lines` stays alive until then)
 }
 // fdh_put_glyph_outline with FDH_GLYPH_MTSDF (the specification: include/figdraw_hip.h at that flag).  The host makes contours, the
 // orientation and the coloured edges (fdh_msdf_host.h), the device the texels (k_msdf_generate): one copy, one launch, then the level
 // chain every glyph image takes.  Nothing is premultiplied and nothing filtered: the four bytes of a texel are four distances.
-void Context::put_glyph_mtsdf(int64_t key, int w, int h, const float* segs, int n, float range, int out_rect[4]) {
+void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, float range, int out_rect[4]) {
   if (n > msdf::kMaxSegments) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field takes at most 65535 segments");
   msdf::Shape shape;
   if (!msdf::build_shape(segs, n, &shape)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field needs closed contours");
-  int x, y;
-  find_empty_rect(w, h, &x, &y);
-  entries_[key] = AtlasEntry{x, y, w, h, false, {}, {}};
-  atlas_epoch_++;
-  if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
-  if (host_only_) return;
-  FDH_HIP(hipSetDevice(device_));
-  sync();  // a frame in flight may still sample the atlas
   std::vector<float> rec;
-  msdf::edge_records(shape, &rec);
-  const size_t npx = (size_t)w * h;
-  glyph_a_.reserve(npx);
-  glyph_b_.reserve(npx);
-  glyph_edges_.reserve(std::max<size_t>(rec.size(), msdf::kEdgeFloats));
-  if (!rec.empty()) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, stream_));
-  launch_msdf_generate(stream_, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, glyph_a_.ptr);
+  if (device_) {
+    msdf::edge_records(shape, &rec);
+    const size_t npx = (size_t)w * h;
+    glyph_a_.reserve(npx);
+    glyph_b_.reserve(npx);
+    glyph_edges_.reserve(std::max<size_t>(rec.size(), msdf::kEdgeFloats));
+  }
+  const AtlasEntry& e = place(s, key, w, h, out_rect);
+  if (!device_) return;
+  const int x = e.x, y = e.y;
+  if (!rec.empty()) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  launch_msdf_generate(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, glyph_a_.ptr);
   // The level chain (updateSubImage's, textures.nim:106-119) stores nothing of an image 1 texel wide or high, not even level 0.  A field is
   // sampled at level 0 alone, and these texels have no other home: such a field gets that level.
-  if (w == 1 || h == 1) launch_atlas_blit(stream_, atlas_levels_[0], atlas_size_, x, y, glyph_a_.ptr, w, h);
-  glyph_to_atlas(glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
+  if (w == 1 || h == 1) launch_atlas_blit(s, levels_[0], size_, x, y, glyph_a_.ptr, w, h);
+  glyph_to_atlas(s, glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
 }
 // Flippy: figdraw's mip-mapped image container (common/formatflippy.nim:77-149).  Layout: "flip", u32 version (1), then per
 // mip level "mip!", u32 width, u32 height, u32 zlen, and a raw-snappy block holding straight RGBA8.  The reference
@@ -312,21 +313,15 @@ static std::vector<uint8_t> snappy_uncompress(const uint8_t* in, size_t n) {
   if (out.size() != len) throw Error(FDH_ERR_INVALID, "flippy: snappy length mismatch");
   return out;
 }
-void Context::put_mips(int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]) {
+void Atlas::put_mips(hipStream_t s, int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]) {
   // putFlippy glcontext.nim:610-620: level l goes to (x >> l, y >> l) with the size the container stored for it
   if (n <= 0 || !ws || !hs || !premul_rgba) throw Error(FDH_ERR_INVALID, "put_mips: no mip levels");
   for (int l = 0; l < n; l++)
     if (ws[l] <= 0 || hs[l] <= 0 || !premul_rgba[l]) throw Error(FDH_ERR_INVALID, "put_mips: bad mip level");
-  if (!host_only_) FDH_HIP(hipSetDevice(device_));
-  int rx = 0, ry = 0;
-  find_empty_rect(ws[0], hs[0], &rx, &ry);
-  entries_[key] = AtlasEntry{rx, ry, ws[0], hs[0], false, {}, {}};
-  atlas_epoch_++;
-  if (out_rect) { out_rect[0] = rx; out_rect[1] = ry; out_rect[2] = ws[0]; out_rect[3] = hs[0]; }
-  sync();
-  for (int l = 0; l < n && l < n_levels_; l++) upload_atlas_rect(l, rx >> l, ry >> l, ws[l], hs[l], premul_rgba[l]);
+  const AtlasEntry& e = place(s, key, ws[0], hs[0], out_rect);
+  for (int l = 0; l < n && l < n_levels_; l++) upload_rect(l, e.x >> l, e.y >> l, ws[l], hs[l], premul_rgba[l]);
 }
-void Context::put_flippy(int64_t key, const uint8_t* data, size_t n, int out_rect[4]) {
+void Atlas::put_flippy(hipStream_t s, int64_t key, const uint8_t* data, size_t n, int out_rect[4]) {
   auto u32 = [&](size_t at) { return (uint32_t)data[at] | ((uint32_t)data[at + 1] << 8) | ((uint32_t)data[at + 2] << 16) | ((uint32_t)data[at + 3] << 24); };
   if (!data || n < 8 || std::memcmp(data, "flip", 4) != 0) throw Error(FDH_ERR_INVALID, "Invalid Flippy header");
   if (u32(4) != 1) throw Error(FDH_ERR_INVALID, "Invalid Flippy version");
@@ -355,16 +350,15 @@ void Context::put_flippy(int64_t key, const uint8_t* data, size_t n, int out_rec
   if (mips.empty()) throw Error(FDH_ERR_INVALID, "Flippy has no mip levels");
   std::vector<const uint8_t*> ptrs;
   for (auto& m : mips) ptrs.push_back(m.data());
-  put_mips(key, (int)mips.size(), ws.data(), hs.data(), ptrs.data(), out_rect);
+  put_mips(s, key, (int)mips.size(), ws.data(), hs.data(), ptrs.data(), out_rect);
 }
-void Context::update_image(int64_t key, int w, int h, const uint8_t* rgba) {  // glcontext.nim:591-604
+void Atlas::update_image(int64_t key, int w, int h, const uint8_t* rgba) {  // glcontext.nim:591-604
   auto it = entries_.find(key);
   if (it == entries_.end()) throw Error(FDH_ERR_INVALID, "update_image: unknown key");
   if (it->second.w != w || it->second.h != h) throw Error(FDH_ERR_INVALID, "update_image: size mismatch");
   if (!rgba) throw Error(FDH_ERR_INVALID, "update_image: null image");
-  sync();
   measure_ink(it->second, rgba);  // the new texels have bounds of their own (draws shrink to them: shrink_to_ink) ...
-  atlas_epoch_++;                 // ... and records cached for retained scenes hold the old ones
+  epoch_++;                       // ... and records cached for retained scenes hold the old ones
   put_levels(it->second.x, it->second.y, w, h, rgba);
 }
 

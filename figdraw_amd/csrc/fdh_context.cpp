@@ -33,8 +33,7 @@ void poison_fresh(void* p, size_t bytes) {
 Context::Context(int atlas_size, float pixel_scale, int device, uint32_t flags) : Recorder(this, true), device_(device), flags_(flags), pixel_scale_(pixel_scale) {
   host_only_ = (flags & FDH_CREATE_RECORD_ONLY) != 0;
   if (host_only_) {  // a call recorder: the front-end and the atlas packer run, nothing is drawn, no device is touched
-    initial_atlas_size_ = atlas_size > 0 ? atlas_size : 1024;
-    alloc_atlas(initial_atlas_size_);
+    atlas_.init(atlas_size, false, nullptr);
     return;
   }
   int n = 0;
@@ -56,8 +55,7 @@ Context::Context(int atlas_size, float pixel_scale, int device, uint32_t flags) 
     stream_ = own_stream_;
     for (auto& e : ev_) FDH_HIP(hipEventCreate(&e));
     for (auto& e : staging_ev_) FDH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    initial_atlas_size_ = atlas_size > 0 ? atlas_size : 1024;  // newContext default, glcontext.nim:255-261
-    alloc_atlas(initial_atlas_size_);
+    atlas_.init(atlas_size, true, stream_);
     static const bool env_sync = [] { const char* e = std::getenv("FDH_SYNC_SUBMIT"); return e && std::atoi(e) != 0; }();
     if (!(flags & FDH_CREATE_SYNC_SUBMIT) && !env_sync) worker_ = std::thread([this] { worker_main(); });
   } catch (...) {
@@ -83,7 +81,7 @@ void Context::release_device_state() {
   if (stream_) (void)hipStreamSynchronize(stream_);
   for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
   for (auto& e : ev_pool_) (void)hipEventDestroy(e);
-  for (auto& l : atlas_levels_) if (l) (void)hipFree(l);
+  atlas_.release();
   if (fb_) (void)hipFree(fb_);
   if (backdrop_) (void)hipFree(backdrop_);
   if (blur_tmp_) (void)hipFree(blur_tmp_);
@@ -91,7 +89,7 @@ void Context::release_device_state() {
   if (dbg_snap_) (void)hipFree(dbg_snap_);
   d_frame_.release(); d_lists_.release(); d_counts_.release(); d_order_[0].release(); d_order_[1].release();
   damage_.release(); readback_.release();
-  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); d_mask_spill_.release();
+  d_mask_spill_.release();
   d_pick_.release(); d_pick_spill_.release(); h_pick_.release();
   for (auto& set : lanes_) set.clear();  // (pinned arrays: freed while the device is still this thread's)
   for (auto& m : misc_) m.release();
@@ -565,8 +563,7 @@ CompositeParams Context::composite_params(const LaunchJob& J, int p, uint32_t* c
   C.counts = J.counts + (size_t)p * nb;
   C.backdrop = backdrop_;
   C.fb = cur;
-  for (int l = 0; l < kMaxMips; l++) C.atlas.level[l] = atlas_levels_[l];
-  C.atlas.size = atlas_size_; C.atlas.n_levels = n_levels_;
+  C.atlas = atlas_.view();
   C.W = J.W; C.H = J.H; C.pitch = J.W;
   C.bins_x = J.bins_x; C.stride = J.list_stride;
   C.bin_x0 = full ? 0 : ph.bin_x0; C.bin_y0 = full ? 0 : ph.bin_y0;

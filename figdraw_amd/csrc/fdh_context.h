@@ -178,18 +178,9 @@ struct HostVec {
   void append(const T* src, size_t k) { if (!k) return; reserve(n + k); std::memcpy(static_cast<void*>(p + n), static_cast<const void*>(src), k * sizeof(T)); n += k; }
 };
 
-// An atlas entry and, when its level-0 texels were seen on the host (fdh_put_image), the bounds of what is IN it: for eight
-// levels t = 0, 16, .. 112 the box (entry-relative texels, x1 / y1 exclusive) of texels whose alpha, and whose largest colour
-// channel, exceeds t.  A draw whose coverage is exactly 0 wherever the sampled value is <= t (a glyph image: alpha 0; an MSDF
-// image: distance below threshold - 0.5 / screen range) shrinks its pixel bounds to the image of that box: the strips outside
-// would blend with alpha 0, which leaves every texel as it is (Recorder::shrink_to_ink).
-constexpr int kInkLevels = 8;
-struct InkBox { int16_t x0, y0, x1, y1; };
-struct AtlasEntry {
-  int x, y, w, h;
-  bool has_ink = false;
-  InkBox ink_a[kInkLevels], ink_rgb[kInkLevels];
-};
+}  // namespace fdh
+#include "fdh_atlas.h"  // AtlasEntry, Atlas: one member of Context
+namespace fdh {
 
 struct Phase {
   int first = 0, count = 0;
@@ -343,7 +334,12 @@ class Recorder {
   void commit_bins(uint32_t idx);  // the record's bounds are final: list-entry flags, list-stride count, phase summary
   void link_share(uint32_t idx);   // LE_SHARE on idx - 1 when record idx is drawn over the same quad with the same shape
   bool bbox_visible(const BBox& b) const;
-  const AtlasEntry& rect_entry();
+  struct EntryUV { const AtlasEntry* e; float S, x, y, w, h; };  // an atlas entry, the atlas size, the entry's rect / size
+  EntryUV entry_uv(int64_t key) const;
+  struct PixelQuad { float x0, y0, x1, y1, w, h; };
+  PixelQuad axis_lod(DrawRec& r, float S, float x0, float y0, float x1, float y1) const;
+  void rect_entry();  // the 4x4 white image exists from here on (SerialOnly on a pool thread that finds it missing)
+  void white_texel_uv(DrawRec& r) const;
   void shrink_to_ink(const AtlasEntry& e, bool use_alpha, int level_t);
   friend class Context;
 };
@@ -462,18 +458,19 @@ class Context : public Recorder {
   bool text_lcd_filtering() const { return text_lcd_filtering_; }
   void comm_info(int* rank, int* world) const { *rank = comm_ ? comm_rank_ : 0; *world = comm_ ? comm_world_ : 1; }
 
-  // atlas
-  void put_image(int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]);
-  void put_glyph_image(int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]);
-  void put_glyph_outline(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]);
-  void update_image(int64_t key, int w, int h, const uint8_t* rgba);
-  void put_mips(int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]);
-  void put_flippy(int64_t key, const uint8_t* data, size_t n, int out_rect[4]);
-  void remove_image(int64_t key) { entries_.erase(key); atlas_epoch_++; }
-  bool has_image(int64_t key) const { return entries_.count(key) != 0; }
-  void reset_atlas(int minimum_size);
-  int atlas_size() const { return atlas_size_; }
-  int64_t atlas_packed_area() const;
+  // atlas (fdh_atlas.h): the context's part of a call that changes texels is sync() -- a frame in flight may still sample the atlas -- and
+  // what FDH_GLYPH_LCD_CONTEXT means here; the rest is atlas_'s
+  void put_image(int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]) { sync(); atlas_.put_image(stream_, key, w, h, rgba, out_rect); }
+  void put_glyph_image(int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]) { sync(); atlas_.put_glyph_image(stream_, key, w, h, rgba, resolve_lcd(flags), out_rect); }
+  void put_glyph_outline(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) { sync(); atlas_.put_glyph_outline(stream_, key, w, h, segs, n, resolve_lcd(flags), out_rect); }
+  void update_image(int64_t key, int w, int h, const uint8_t* rgba) { sync(); atlas_.update_image(key, w, h, rgba); }
+  void put_mips(int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]) { sync(); atlas_.put_mips(stream_, key, n, ws, hs, premul_rgba, out_rect); }
+  void put_flippy(int64_t key, const uint8_t* data, size_t n, int out_rect[4]) { sync(); atlas_.put_flippy(stream_, key, data, n, out_rect); }
+  void remove_image(int64_t key) { atlas_.remove(key); }
+  bool has_image(int64_t key) const { return atlas_.has(key); }
+  void reset_atlas(int minimum_size) { sync(); atlas_.reset(minimum_size, stream_); }
+  int atlas_size() const { return atlas_.size(); }
+  int64_t atlas_packed_area() const { return atlas_.packed_area(); }
 
   // readback / interop
   void read_pixels(int x, int y, int w, int h, uint8_t* out);
@@ -559,11 +556,12 @@ class Context : public Recorder {
   void release_device_state();  // the destructor's device half (also a constructor that fails half way)
   void rec_begin_frame(bool clear, const float rgba[4]);  // begin_frame / end_frame as the call recorder sees them (fdh_record.cpp)
   void rec_end_frame();
-  // atlas (fdh_atlas.cpp)
-  void alloc_atlas(int size);
-  void upload_atlas_rect(int level, int x, int y, int w, int h, const uint8_t* rgba);
-  void put_levels(int x, int y, int w, int h, const uint8_t* rgba);
-  void find_empty_rect(int w, int h, int* ox, int* oy);
+  // FDH_GLYPH_LCD_CONTEXT: the LCD filter as setTextLcdFilteringEnabled said.  (With FDH_GLYPH_MTSDF the flags pass as they are: a distance
+  // field takes neither LCD flag, and the atlas refuses them.)
+  uint32_t resolve_lcd(uint32_t flags) const {
+    if (!(flags & FDH_GLYPH_LCD_CONTEXT) || (flags & FDH_GLYPH_MTSDF)) return flags;
+    return (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) | (text_lcd_filtering_ ? FDH_GLYPH_LCD_FILTER : 0u);
+  }
   // fold_clear's guard: puts a folded draw's bounds back into its lane when prepare is left, by return or by exception
   struct FoldGuard {
     BinRec* br = nullptr;
@@ -705,12 +703,7 @@ class Context : public Recorder {
   uint32_t *backdrop_ = nullptr, *blur_tmp_ = nullptr;
   uint32_t* alt_ = nullptr;  // second frame surface: a fused full-frame blur renders out of place, phases alternate between fb_ and this
   uint32_t* dbg_snap_ = nullptr;
-  void glyph_to_atlas(uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags);
-  void put_glyph_mtsdf(int64_t key, int w, int h, const float* segs, int n, float range, int out_rect[4]);
-  DeviceBuf<float> glyph_lines_, glyph_acc_, glyph_edges_;  // (glyph_edges_: the edge records of a distance-field put, fdh_msdf_host.h)
-  DeviceBuf<uint32_t> glyph_a_, glyph_b_;  // put_glyph_image: the raster and its filtered / minified successors
   RetainedScene retained_;
-  uint64_t atlas_epoch_ = 1;
   void rebase_side(FdhFig* nodes, int n, const FdhScene* side);
   void compact_side();
   bool host_only_ = false;  // FDH_CREATE_RECORD_ONLY
@@ -762,11 +755,7 @@ class Context : public Recorder {
   void wait_staging(int slot);             // calling thread: until the set's last upload has run
   int staging_i_ = 0;
 
-  // atlas
-  int atlas_size_ = 0, initial_atlas_size_ = 0, atlas_margin_ = 4, n_levels_ = 0;
-  uint32_t* atlas_levels_[kMaxMips] = {};
-  std::vector<uint16_t> heights_;
-  std::unordered_map<int64_t, AtlasEntry> entries_;
+  Atlas atlas_;  // (fdh_atlas.h)
 
   FdhFrameStats stats_ = {};
  public:

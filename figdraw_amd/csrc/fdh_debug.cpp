@@ -153,7 +153,7 @@ void Context::debug_read_surface(int which, uint8_t* out) {
   if (which == 4) {  // level 0 of the atlas, atlas_size x atlas_size
     FDH_HIP(hipSetDevice(device_));
     FDH_HIP(hipStreamSynchronize(stream_));
-    FDH_HIP(hipMemcpy(out, atlas_levels_[0], (size_t)atlas_size_ * atlas_size_ * 4, hipMemcpyDeviceToHost));
+    FDH_HIP(hipMemcpy(out, atlas_.level0(), (size_t)atlas_.size() * atlas_.size() * 4, hipMemcpyDeviceToHost));
     return;
   }
   const uint32_t* src = which == 0 ? fb_ : which == 1 ? blur_tmp_ : which == 2 ? backdrop_ : which == 3 ? dbg_snap_ : nullptr;

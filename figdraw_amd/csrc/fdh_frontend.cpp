@@ -1128,7 +1128,7 @@ void Context::scene_render() {
       for (size_t s = 0; s < D.roots.size(); s++) {
         RetainedRoot& C = D.cache[s];
         // (cached records were culled to the rows in force when they were made: good for any frame that produces no row beyond them)
-        if (!C.dirty && C.cacheable && !config_changed && C.cull_y0 <= cull_y0_ && C.cull_y1 >= cull_y1_ && C.atlas_epoch == atlas_epoch_ &&
+        if (!C.dirty && C.cacheable && !config_changed && C.cull_y0 <= cull_y0_ && C.cull_y1 >= cull_y1_ && C.atlas_epoch == atlas_.epoch() &&
             (C.tagged || !pick_frame_)) {
           splice_cached(C);
           R.roots_reused++;
@@ -1142,7 +1142,7 @@ void Context::scene_render() {
         wk.node(views[l], D.roots[s]);
         R.roots_walked++;
         C.dirty = false;
-        C.atlas_epoch = atlas_epoch_;
+        C.atlas_epoch = atlas_.epoch();
         C.cull_y0 = cull_y0_; C.cull_y1 = cull_y1_;
         C.cacheable = phases_.size() == p0 && blurs_.size() == b0;
         C.recs.clear(); C.bins.clear(); C.exts.clear(); C.tags.clear();

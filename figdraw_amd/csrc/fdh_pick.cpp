@@ -70,10 +70,7 @@ void Context::pick_points(const float* xy, int n, int threshold, uint32_t flags,
   std::memcpy(h + o_xy, txy.data(), txy.size() * sizeof(int2));
   const int levels = std::max(J.pick_depth - kPickDepth, 0);
   if (levels) reserve_quiet(d_pick_spill_, (size_t)levels * groups * kPickThreads);
-  AtlasView atlas{};
-  for (int l = 0; l < kMaxMips; l++) atlas.level[l] = atlas_levels_[l];
-  atlas.size = atlas_size_; atlas.n_levels = n_levels_;
-  PickParams P = pick_params(J, atlas, threshold, flags);
+  PickParams P = pick_params(J, atlas_.view(), threshold, flags);
   uint8_t* d = d_pick_.ptr;
   P.pts = reinterpret_cast<const int2*>(d + o_pts); P.tile_first = reinterpret_cast<const int*>(d + o_first); P.tile_xy = reinterpret_cast<const int2*>(d + o_xy);
   P.max_hits = max_hits;
@@ -112,10 +109,7 @@ void Context::pick_region(int x, int y, int w, int h, int threshold, uint32_t fl
   reserve_quiet(d_pick_, (size_t)w * h * sizeof(int32_t));
   const int levels = std::max(J.pick_depth - kPickDepth, 0);
   if (levels) reserve_quiet(d_pick_spill_, (size_t)levels * groups * kPickThreads);
-  AtlasView atlas{};
-  for (int l = 0; l < kMaxMips; l++) atlas.level[l] = atlas_levels_[l];
-  atlas.size = atlas_size_; atlas.n_levels = n_levels_;
-  PickParams P = pick_params(J, atlas, threshold, flags);
+  PickParams P = pick_params(J, atlas_.view(), threshold, flags);
   P.x0 = x; P.y0 = y; P.w = w; P.h = h; P.tiles_x = tiles_x;
   P.region_out = reinterpret_cast<int32_t*>(d_pick_.ptr);
   P.spill = levels ? d_pick_spill_.ptr : nullptr;

@@ -281,7 +281,7 @@ void Context::decide_opaque(LaunchJob& J) const {
 // Damage tracking: the frame key -- everything a bin's pixels depend on besides its lists and the records they index.  A tracked frame
 // whose key differs from the last tracked frame's is rendered in full (DamageTracker::launch), and so is one the tracking launches cannot
 // take: no clear (its starting pixels are not this frame's to rebuild), a full-frame blur that renders out of place (k_blur_fx flips the
-// frame surface), more blur nodes than k_damage_resolve takes.  (atlas_epoch_ moves with every put, update, remove and reset: any atlas
+// frame surface), more blur nodes than k_damage_resolve takes.  (the atlas epoch moves with every put, update, remove and reset: any atlas
 // change is a full frame, on purpose.)
 void Context::damage_frame_key(LaunchJob& J) const {
   J.damage = damage_.on;
@@ -292,7 +292,7 @@ void Context::damage_frame_key(LaunchJob& J) const {
   std::memcpy(&aa_bits, &ctx_aa_, 4); std::memcpy(&ps_bits, &pixel_scale_, 4);
   mix((uint64_t)(uint32_t)W_ << 32 | (uint32_t)H_); mix((uint64_t)(uint32_t)J.bins_x << 32 | (uint32_t)J.bins_y);
   mix((uint64_t)J.clear_rgba8 << 1 | (clear_ ? 1u : 0u)); mix((uint64_t)aa_bits << 32 | ps_bits);
-  mix(atlas_epoch_); mix((uint64_t)(uint32_t)atlas_size_);
+  mix(atlas_.epoch()); mix((uint64_t)(uint32_t)atlas_.size());
   mix((uint64_t)(latency_routes_ ? 1u : 0u) << 8 | (uint64_t)(uint32_t)cull_mode_);
   J.damage_key = k;
 }

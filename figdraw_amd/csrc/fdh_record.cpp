@@ -29,7 +29,7 @@ void Recorder::shrink_to_ink(const AtlasEntry& e, bool use_alpha, int level_t) {
   if ((r.op_mode & F_GENERAL) || b.x1 <= b.x0 || b.y1 <= b.y0) return;
   const InkBox ib = (use_alpha ? e.ink_a : e.ink_rgb)[std::min(level_t / 16, kInkLevels - 1)];
   if (ib.x1 <= ib.x0 || ib.y1 <= ib.y0) { b = BBox{0, 0, 0, 0}; r.bx0 = r.by0 = r.bx1 = r.by1 = 0; return; }  // nothing in the image reaches the level
-  const double S = (double)cx_->atlas_size_;
+  const double S = (double)cx_->atlas_.size();
   auto range = [&](double ua, double ut, double o, double inv, double lo_t, double hi_t, int& p0, int& p1) {
     // texel coordinate at pixel centre c: t(c) = (ua + (ut - ua) (c - o) inv) S - 0.5; pixels whose t lies in [lo_t - 3, hi_t + 2]
     const double A = (ut - ua) * inv * S, B = ua * S - 0.5 - A * o;
@@ -240,7 +240,7 @@ void Recorder::commit_bins(uint32_t idx) {
   const bool atlas_mode = mode == 0u || (mode >= 13u && mode <= 16u);
   if (op != OP_DRAW) sum_.has_masks = true;
   // 4-wide atlas path for axis-aligned atlas quads sampled from level 0
-  const bool atlas4 = atlas_mode && !(om & F_GENERAL) && op == OP_DRAW && !(mode == 0u && r.aux2 > 0.0f && cx_->n_levels_ >= 2);
+  const bool atlas4 = atlas_mode && !(om & F_GENERAL) && op == OP_DRAW && !(mode == 0u && r.aux2 > 0.0f && cx_->atlas_.n_levels() >= 2);
   if (atlas4) sum_.has_atlas = true;
   // (a rect mask under a rotated transform -- matY.x != 0 -- is set up one pixel slot at a time; an upright one runs 4-wide)
   else if ((op == OP_DRAW || op == OP_MASK_PUSH) && (om & F_GENERAL) && (om & F_EDGE32) && !atlas_mode && mode < 18u) sum_.has_rot = true;
@@ -560,7 +560,7 @@ bool Recorder::emit_corners(DrawRec& r, const QuadPx& q, bool count_fragments) {
         const double dvdx = (dv1 * e2y - dv2 * e1y) / det, dvdy = (dv2 * e1x - dv1 * e2x) / det;
         q.fw_u[t] = (float)(std::fabs(dudx) + std::fabs(dudy));
         q.fw_v[t] = (float)(std::fabs(dvdx) + std::fabs(dvdy));
-        const double S = (double)cx_->atlas_size_;
+        const double S = (double)cx_->atlas_.size();
         const double rho = std::max(std::sqrt(dudx * dudx + dvdx * dvdx), std::sqrt(dudy * dudy + dvdy * dvdy)) * S;
         q.lod[t] = rho > 0.0 ? (float)std::log2(rho) : 0.0f;
       } else {
@@ -731,15 +731,35 @@ void Recorder::draw_rounded_rect_fill(const float rect[4], const FdhFill& fill, 
   }
 }
 
+// An image's entry and its uv rect: entries = rect / atlasSize.  e == nullptr: "missing image in context", warn + no-op (glcontext.nim:1310-1315)
+Recorder::EntryUV Recorder::entry_uv(int64_t key) const {
+  EntryUV u{cx_->atlas_.find(key), (float)cx_->atlas_.size(), 0.0f, 0.0f, 0.0f, 0.0f};
+  if (u.e) { u.x = (float)u.e->x / u.S; u.y = (float)u.e->y / u.S; u.w = (float)u.e->w / u.S; u.h = (float)u.e->h / u.S; }
+  return u;
+}
+// LOD of the axis-aligned form of an atlas quad whose uv rect is set: rho = max(|du/dx|, |dv/dy|) in level-0 texels per pixel -> r.aux2.
+// Returns the quad's pixel corners and extent.
+Recorder::PixelQuad Recorder::axis_lod(DrawRec& r, float S, float x0, float y0, float x1, float y1) const {
+  PixelQuad q;
+  q.x0 = std::ceil(mat_.a * x0 + mat_.tx);
+  q.y0 = std::ceil(mat_.d * y0 + mat_.ty);
+  q.x1 = std::ceil(mat_.a * x1 + mat_.tx); q.y1 = std::ceil(mat_.d * y1 + mat_.ty);
+  q.w = std::fabs(q.x1 - q.x0); q.h = std::fabs(q.y1 - q.y0);
+  if (q.w > 0.0f && q.h > 0.0f) {
+    const float rho = std::max(std::fabs(r.r[2] - r.r[0]) * S / q.w, std::fabs(r.r[3] - r.r[1]) * S / q.h);
+    r.aux2 = rho > 0.0f ? std::log2(rho) : 0.0f;
+  }
+  return q;
+}
+
 // drawImage / drawUvRect: glcontext.nim:1236-1302, 1350-1367
 void Recorder::draw_image(int64_t key, const float pos[2], const FdhColor colors[4], const float size[2], bool flip_y) {
   { FDH_REC("draw_image").i(key).fv(pos, 2).cols(colors).fv(size, 2).i(flip_y ? 1 : 0); }
   if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
-  auto it = cx_->entries_.find(key);
-  if (it == cx_->entries_.end()) return;  // "missing image in context": warn + no-op (glcontext.nim:1310-1315)
-  const AtlasEntry& e = it->second;
-  const float S = (float)cx_->atlas_size_;
-  const float ex = (float)e.x / S, ey = (float)e.y / S, ew = (float)e.w / S, eh = (float)e.h / S;  // entries = rect / atlasSize
+  const EntryUV u = entry_uv(key);
+  if (!u.e) return;
+  const AtlasEntry& e = *u.e;
+  const float S = u.S, ex = u.x, ey = u.y, ew = u.w, eh = u.h;
   const bool sized = size[0] > 0.0f && size[1] > 0.0f;
   const float dw = sized ? size[0] : ew * S, dh = sized ? size[1] : eh * S;
   DrawRec& r = next_rec();
@@ -754,29 +774,17 @@ void Recorder::draw_image(int64_t key, const float pos[2], const FdhColor colors
     r.op_mode |= F_SUBPIXEL;
     r.aux = std::max(0.0f, std::min(subpixel_shift_, 0.999f));  // activeSubpixelShift glcontext.nim:819-822
   }
-  // LOD for the axis-aligned form: rho = max(|du/dx|, |dv/dy|) in level-0 texels per pixel
   const float x0 = pos[0], y0 = pos[1], x1 = pos[0] + dw, y1 = pos[1] + dh;
-  bool one_to_one = false;
-  float qx0 = 0.0f, qy0 = 0.0f;
-  {
-    qx0 = std::ceil(mat_.a * x0 + mat_.tx);
-    qy0 = std::ceil(mat_.d * y0 + mat_.ty);
-    const float qx1 = std::ceil(mat_.a * x1 + mat_.tx), qy1 = std::ceil(mat_.d * y1 + mat_.ty);
-    const float rw = std::fabs(qx1 - qx0), rh = std::fabs(qy1 - qy0);
-    if (rw > 0.0f && rh > 0.0f) {
-      const float rho = std::max(std::fabs(r.r[2] - r.r[0]) * S / rw, std::fabs(r.r[3] - r.r[1]) * S / rh);
-      r.aux2 = rho > 0.0f ? std::log2(rho) : 0.0f;
-    }
-    // texels 1:1 on pixels (a glyph as renderText places it): the quad is as large as the image, upright, unshifted
-    one_to_one = !flip_y && qx1 > qx0 && qy1 > qy0 && rw == (float)e.w && rh == (float)e.h && (!subpixel_enabled_ || r.aux == 0.0f) &&
-                 mat_.b == 0.0f && mat_.c == 0.0f && std::fabs(qx0) < 1.0e6f && std::fabs(qy0) < 1.0e6f;
-  }
+  const PixelQuad q = axis_lod(r, S, x0, y0, x1, y1);
+  // texels 1:1 on pixels (a glyph as renderText places it): the quad is as large as the image, upright, unshifted
+  const bool one_to_one = !flip_y && q.x1 > q.x0 && q.y1 > q.y0 && q.w == (float)e.w && q.h == (float)e.h && (!subpixel_enabled_ || r.aux == 0.0f) &&
+                          mat_.b == 0.0f && mat_.c == 0.0f && std::fabs(q.x0) < 1.0e6f && std::fabs(q.y0) < 1.0e6f;
   if (!emit_quad(r, x0, y0, x1, y1, true)) return;
   if (one_to_one && !(r.op_mode & F_GENERAL)) {
     DrawRec& rr = r;
     rr.op_mode |= F_TEXEL_1TO1;
-    rr.ext = (uint32_t)(int32_t)(e.x - (int)qx0);   // texel x = pixel x + tdx
-    rr._pad = (uint32_t)(int32_t)(e.y - (int)qy0);  // texel y = pixel y + tdy
+    rr.ext = (uint32_t)(int32_t)(e.x - (int)q.x0);   // texel x = pixel x + tdx
+    rr._pad = (uint32_t)(int32_t)(e.y - (int)q.y0);  // texel y = pixel y + tdy
   }
   // atlas.frag:284-295: the source alpha is texel alpha x vertex alpha -- 0 wherever all four taps have alpha 0.  (Level 0 only:
   // a minified image, aux2 > 0, takes its taps from coarser levels.)
@@ -788,11 +796,9 @@ void Recorder::draw_image(int64_t key, const float pos[2], const FdhColor colors
 void Recorder::draw_image_adj(int64_t key, const float pos[2], FdhColor color, const float size[2]) {
   { FDH_REC("draw_image_adj").i(key).fv(pos, 2).col(color).fv(size, 2); }
   if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
-  auto it = cx_->entries_.find(key);
-  if (it == cx_->entries_.end()) return;
-  const AtlasEntry& e = it->second;
-  const float S = (float)cx_->atlas_size_;
-  const float ex = (float)e.x / S, ey = (float)e.y / S, ew = (float)e.w / S, eh = (float)e.h / S, adj = 2.0f / S;
+  const EntryUV u = entry_uv(key);
+  if (!u.e) return;
+  const float S = u.S, ex = u.x, ey = u.y, ew = u.w, eh = u.h, adj = 2.0f / S;
   DrawRec& r = next_rec();
   r.op_mode = FDH_SDF_ATLAS | F_SOLID;
   r.r[0] = ex + adj; r.r[1] = ey + adj; r.r[2] = ex + ew - adj; r.r[3] = ey + eh - adj;
@@ -803,15 +809,7 @@ void Recorder::draw_image_adj(int64_t key, const float pos[2], FdhColor color, c
     r.aux = std::max(0.0f, std::min(subpixel_shift_, 0.999f));
   }
   const float x0 = pos[0], y0 = pos[1], x1 = pos[0] + size[0], y1 = pos[1] + size[1];
-  {  // LOD of the axis-aligned form, as in draw_image
-    const float qx0 = std::ceil(mat_.a * x0 + mat_.tx), qy0 = std::ceil(mat_.d * y0 + mat_.ty);
-    const float qx1 = std::ceil(mat_.a * x1 + mat_.tx), qy1 = std::ceil(mat_.d * y1 + mat_.ty);
-    const float rw = std::fabs(qx1 - qx0), rh = std::fabs(qy1 - qy0);
-    if (rw > 0.0f && rh > 0.0f) {
-      const float rho = std::max(std::fabs(r.r[2] - r.r[0]) * S / rw, std::fabs(r.r[3] - r.r[1]) * S / rh);
-      r.aux2 = rho > 0.0f ? std::log2(rho) : 0.0f;
-    }
-  }
+  axis_lod(r, S, x0, y0, x1, y1);
   if (emit_quad(r, x0, y0, x1, y1, true)) commit_bins((uint32_t)lane_->recs.n - 1);
 }
 
@@ -820,11 +818,10 @@ void Recorder::draw_msdf(int64_t key, const float pos[2], FdhColor color, const 
                         float stroke_weight, bool mtsdf, bool flip_y) {
   { FDH_REC("draw_msdf").i(key).fv(pos, 2).col(color).fv(size, 2).f(px_range).f(sd_threshold).f(stroke_weight).i(mtsdf ? 1 : 0).i(flip_y ? 1 : 0); }
   if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
-  auto it = cx_->entries_.find(key);
-  if (it == cx_->entries_.end()) return;
-  const AtlasEntry& e = it->second;
-  const float S = (float)cx_->atlas_size_;
-  const float ex = (float)e.x / S, ey = (float)e.y / S, ew = (float)e.w / S, eh = (float)e.h / S;
+  const EntryUV u = entry_uv(key);
+  if (!u.e) return;
+  const AtlasEntry& e = *u.e;
+  const float S = u.S, ex = u.x, ey = u.y, ew = u.w, eh = u.h;
   const float sw = std::max(0.0f, stroke_weight);
   DrawRec& r = next_rec();
   r.op_mode = (uint32_t)(mtsdf ? (sw > 0.0f ? FDH_SDF_MTSDF_ANNULAR : FDH_SDF_MTSDF) : (sw > 0.0f ? FDH_SDF_MSDF_ANNULAR : FDH_SDF_MSDF)) | F_SOLID;
@@ -885,31 +882,26 @@ void Recorder::draw_quadratic_bezier_sdf(const float rect[4], const FdhFill& fil
 // The 4x4 white "rect" atlas image drawRect / drawFilledQuad sample (glcontext.nim:966-970, 1411-1415); it takes
 // atlas space on first use exactly like the reference's -- on the calling thread: a pool thread that finds it missing hands its
 // sibling group back (SerialOnly).
-const AtlasEntry& Recorder::rect_entry() {
-  auto it = cx_->entries_.find(kRectImageKey);
-  if (it == cx_->entries_.end()) {
-    if (!is_main_) throw SerialOnly{};
-    uint8_t white[4 * 4 * 4];
-    std::memset(white, 255, sizeof white);
-    cx_->put_image(kRectImageKey, 4, 4, white, nullptr);
-    it = cx_->entries_.find(kRectImageKey);
-  }
-  return it->second;
+void Recorder::rect_entry() {
+  if (cx_->atlas_.has(kRectImageKey)) return;
+  if (!is_main_) throw SerialOnly{};
+  uint8_t white[4 * 4 * 4];
+  std::memset(white, 255, sizeof white);
+  cx_->put_image(kRectImageKey, 4, 4, white, nullptr);
 }
-static void white_texel_uv(const AtlasEntry& e, int atlas_size, DrawRec& r) {
-  const float S = (float)atlas_size;
-  const float ex = (float)e.x / S, ey = (float)e.y / S, ew = (float)e.w / S, eh = (float)e.h / S;
-  r.r[0] = r.r[2] = ex + ew / 2.0f;  // uvAt = uvTo = the image centre
-  r.r[1] = r.r[3] = ey + eh / 2.0f;
+void Recorder::white_texel_uv(DrawRec& r) const {
+  const EntryUV u = entry_uv(kRectImageKey);
+  r.r[0] = r.r[2] = u.x + u.w / 2.0f;  // uvAt = uvTo = the image centre
+  r.r[1] = r.r[3] = u.y + u.h / 2.0f;
 }
 // drawFilledQuad: glcontext.nim:963-982 (+ drawQuad :908-961): an arbitrary quad textured with one white texel
 void Recorder::draw_filled_quad(const float verts[8], const FdhColor colors[4]) {
   { FDH_REC("draw_filled_quad").fv(verts, 8).cols(colors); }
   if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
-  const AtlasEntry& white = rect_entry();  // (may upload the image: before the record slot is taken)
+  rect_entry();  // (may upload the image: before the record slot is taken)
   DrawRec& r = next_rec();
   r.op_mode = FDH_SDF_ATLAS;
-  white_texel_uv(white, cx_->atlas_size_, r);
+  white_texel_uv(r);
   for (int i = 0; i < 4; i++) r.col[i] = pack_color(colors[i]);
   if (r.col[0] == r.col[1] && r.col[1] == r.col[2] && r.col[2] == r.col[3]) r.op_mode |= F_SOLID;
   r.aa = aa_;
@@ -920,10 +912,10 @@ void Recorder::draw_filled_quad(const float verts[8], const FdhColor colors[4]) 
 void Recorder::draw_rect(const float rect[4], FdhColor color) {
   { FDH_REC("draw_rect").fv(rect, 4).col(color); }
   if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
-  const AtlasEntry& white = rect_entry();
+  rect_entry();
   DrawRec& r = next_rec();
   r.op_mode = FDH_SDF_ATLAS | F_SOLID;
-  white_texel_uv(white, cx_->atlas_size_, r);
+  white_texel_uv(r);
   for (int i = 0; i < 4; i++) r.col[i] = pack_color(color);
   r.aa = aa_;
   if (emit_quad(r, rect[0], rect[1], rect[0] + rect[2], rect[1] + rect[3], true)) commit_bins((uint32_t)lane_->recs.n - 1);

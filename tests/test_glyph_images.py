@@ -182,3 +182,44 @@ def test_device_rasteriser_matches_oracle(lcd):
     assert got[..., :3].max() > 200  # something was drawn
     assert np.array_equal(got, want)
     ctx.close()
+
+
+@pytest.mark.gpu
+def test_atlas_growth_through_the_device_glyph_path():
+    """The atlas doubles under a put whose texels the DEVICE makes (test_atlas_grow_and_update grows under host texels): a 20 x 20 glyph
+    image into a 64 atlas, then a 60 x 60 outline with the LCD filter, which needs 68 rows.  Level 0 of the new atlas holds the oracle's
+    texels of that glyph at the returned rect and zeros everywhere else -- nothing is left of the first glyph at its old place -- and a
+    frame that draws the glyph 1:1 is the oracle's."""
+    import os
+
+    from conftest import GOLDEN, diff_stats
+    from figdraw_amd.context import HipContext
+
+    z = np.load(os.path.join(GOLDEN, "outlines_ubuntu20.npz"))
+    segs, (gw, gh) = z[f"segs_{ord('g')}"], z[f"size_{ord('g')}"]
+    segs = (segs * np.float32(min(58.0 / gw, 58.0 / gh))).astype(np.float32)  # the glyph 'g' blown up to fill 60 x 60 (NaN control points stay NaN)
+    ctx = HipContext(atlas_size=64, device=0)
+    first = ctx.put_glyph_image(1, np.full((20, 20, 4), 255, np.uint8))
+    assert ctx.atlas_size() == 64 and (ctx.debug_read_surface(4)[first[1]:first[1] + 20, first[0]:first[0] + 20] == 255).all()
+    rect = ctx.put_glyph_outline(2, segs, 60, 60, lcd_filter=True)
+    assert ctx.atlas_size() == 128 and ctx.has_image(2) and not ctx.has_image(1)
+    orc = O.Oracle(atlas_size=128, threads=4)
+    assert rect == orc.put_glyph_outline(2, segs, 60, 60, lcd_filter=True)
+    want = np.zeros((128, 128, 4), np.uint8)
+    want[rect[1]:rect[1] + 60, rect[0]:rect[0] + 60] = O.lcd_filter(O.rasterize_outline(segs, 60, 60))
+    assert want[..., 3].max() == 255 and (want[..., 3] > 0).sum() > 400  # a glyph, not an empty image
+    level0 = ctx.debug_read_surface(4)
+    assert np.array_equal(level0, want), diff_stats(level0, want)
+    # the first glyph's old place lies inside the new glyph's rect: nothing of its 255s is left where the new glyph has no ink
+    old, blank = level0[first[1]:first[1] + 20, first[0]:first[0] + 20], want[first[1]:first[1] + 20, first[0]:first[0] + 20] == 0
+    assert blank.sum() > 400 and not old[blank].any()
+    for c in (ctx, orc):
+        c.begin_frame(64, 64, True, (0, 0, 0, 1))
+        c.draw_image(2, (2, 2), [(255, 255, 255, 255)] * 4)
+        c.end_frame()
+    got, ref = ctx.read_pixels(), orc.read_pixels()
+    mx, n0, n1 = diff_stats(got, ref)
+    print(f"frame against the oracle: max {mx} LSB, {n0} pixels differ, {n1} by more than 1")
+    assert got[..., :3].max() > 200 and np.array_equal(got, ref)  # (1:1 at an integer position: the frame is the atlas content, as above)
+    ctx.close()
+    orc.close()
