@@ -208,12 +208,13 @@ static int flatten_count(const float* q) {
 void Atlas::put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) {
   if (w <= 0 || h <= 0 || w > 4096 || h > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_outline: image size must be in 1..4096");
   if (n < 0 || (n > 0 && !segs)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: bad outline");
-  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT | FDH_GLYPH_MTSDF | 0xFF00u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: unknown flag");
+  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT | FDH_GLYPH_MTSDF | FDH_GLYPH_MTSDF_CORRECT | 0xFF00u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: unknown flag");
   const uint32_t sdf_range = (flags >> 8) & 255u;
   if (sdf_range && (!(flags & FDH_GLYPH_MTSDF) || sdf_range > 64u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance range needs FDH_GLYPH_MTSDF and is at most 64");
+  if ((flags & FDH_GLYPH_MTSDF_CORRECT) && !(flags & FDH_GLYPH_MTSDF)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: FDH_GLYPH_MTSDF_CORRECT needs FDH_GLYPH_MTSDF");
   if (flags & FDH_GLYPH_MTSDF) {
     if (flags & (FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field takes no LCD filter");
-    put_glyph_mtsdf(s, key, w, h, segs, n, sdf_range ? (float)sdf_range : 4.0f, out_rect);
+    put_glyph_mtsdf(s, key, w, h, segs, n, sdf_range ? (float)sdf_range : 4.0f, (flags & FDH_GLYPH_MTSDF_CORRECT) != 0, out_rect);
     return;
   }
   std::vector<float> lines;
@@ -247,7 +248,8 @@ void Atlas::put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const fl
 // fdh_put_glyph_outline with FDH_GLYPH_MTSDF (the specification: include/figdraw_hip.h at that flag).  The host makes contours, the
 // orientation and the coloured edges (fdh_msdf_host.h), the device the texels (k_msdf_generate): one copy, one launch, then the level
 // chain every glyph image takes.  Nothing is premultiplied and nothing filtered: the four bytes of a texel are four distances.
-void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, float range, int out_rect[4]) {
+// `correct` (FDH_GLYPH_MTSDF_CORRECT, step 5): one more launch on the same stream, k_msdf_correct from one glyph buffer into the other.
+void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, float range, bool correct, int out_rect[4]) {
   if (n > msdf::kMaxSegments) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field takes at most 65535 segments");
   msdf::Shape shape;
   if (!msdf::build_shape(segs, n, &shape)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field needs closed contours");
@@ -263,11 +265,16 @@ void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const floa
   if (!device_) return;
   const int x = e.x, y = e.y;
   if (!rec.empty()) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, s));
-  launch_msdf_generate(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, glyph_a_.ptr);
+  uint32_t *field = glyph_a_.ptr, *spare = glyph_b_.ptr;
+  launch_msdf_generate(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, field);
+  if (correct) {
+    launch_msdf_correct(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, field, spare);
+    std::swap(field, spare);
+  }
   // The level chain (updateSubImage's, textures.nim:106-119) stores nothing of an image 1 texel wide or high, not even level 0.  A field is
   // sampled at level 0 alone, and these texels have no other home: such a field gets that level.
-  if (w == 1 || h == 1) launch_atlas_blit(s, levels_[0], size_, x, y, glyph_a_.ptr, w, h);
-  glyph_to_atlas(s, glyph_a_.ptr, glyph_b_.ptr, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
+  if (w == 1 || h == 1) launch_atlas_blit(s, levels_[0], size_, x, y, field, w, h);
+  glyph_to_atlas(s, field, spare, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
 }
 // Flippy: figdraw's mip-mapped image container (common/formatflippy.nim:77-149).  Layout: "flip", u32 version (1), then per
 // mip level "mip!", u32 width, u32 height, u32 zlen, and a raw-snappy block holding straight RGBA8.  The reference

@@ -130,6 +130,9 @@ void launch_atlas_blit(hipStream_t s, uint32_t* level, int LS, int x, int y, con
 // distance-field generation (k_msdf.hip): n_edges records of msdf::kEdgeFloats floats (fdh_msdf_host.h) -> a w x h RGBA8 image, R, G, B the
 // channels' signed pseudo-distances, A the true signed distance, each 0.5 + d / range in 8 bits; orient = the sign of the outline's area
 void launch_msdf_generate(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, uint32_t* out);
+// step 5 of the same specification, the correction pass of FDH_GLYPH_MTSDF_CORRECT (k_msdf_correct): the generated image `in` -> `out` (another
+// buffer: every decision reads `in`), same edge records; a texel convicted of carrying a false median between itself and a neighbour gets R = G = B = median
+void launch_msdf_correct(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out);
 // The frame upload (k_upload_frame): a table of runs, each `bytes` of pinned host memory (its device view) going to byte offset
 // dst_off of the frame block.  kind 0: 16-byte units; 1: BinRecs -- copied in 8-byte units, and the lane that carries a record's
 // pixel bounds also writes the draw's 4-byte bin box; 2: DrawRecs -- 16-byte units, and the `ext` of every F_GENERAL record gets

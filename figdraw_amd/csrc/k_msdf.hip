@@ -4,6 +4,8 @@
 // counter -- so they arrive through scalar loads and what depends on the edge alone costs nothing per lane.  A lane keeps four running
 // candidates (the channels R, G, B and the true distance): squared distance, orthogonality, edge and parameter; signs and
 // pseudo-distances are made once, after the loop, from the winners.
+// k_msdf_correct is step 5, the correction pass behind FDH_GLYPH_MTSDF_CORRECT: the same mapping over the quantised image; integers find the
+// few places where interpolation between two texels carries the median across 0.5, and only a wave that holds one walks the edges again.
 #include "fdh_device.h"
 #include "fdh_msdf_host.h"
 
@@ -92,6 +94,20 @@ __device__ __forceinline__ float msdf_nearest_t(const float* __restrict__ r, flo
   return de <= best_d2 ? te : best_t;
 }
 
+// what one edge offers a point p: the parameter of its nearest point, the squared distance, the orthogonality there and
+// side = cross(T, p - N), whose sign is the side of the edge p lies on
+__device__ __forceinline__ void msdf_edge(const float* __restrict__ r, float px, float py, float& t, float& d2, float& ortho, float& side) {
+#pragma clang fp contract(off)
+  t = msdf_nearest_t(r, px, py);
+  float Ex, Ey, Tx, Ty;
+  msdf_at(r, t, px, py, Ex, Ey, Tx, Ty);
+  d2 = Ex * Ex + Ey * Ey;
+  // orthogonality: |cross(unit tangent, unit vector to the texel)|; 0 on the curve itself
+  const float cr = Tx * Ey - Ty * Ex, den = (Tx * Tx + Ty * Ty) * d2;
+  ortho = den > 0.0f ? __builtin_fabsf(cr) * frcp(fsqrt(den)) : 0.0f;
+  side = Ty * Ex - Tx * Ey;  // the vector to the point is -E
+}
+
 __global__ __launch_bounds__(64) void k_msdf_generate(const float* __restrict__ edges, int n_edges, int w, int h, float orient, float inv_range,
                                                       uint32_t* __restrict__ out) {
 #pragma clang fp contract(off)
@@ -134,13 +150,8 @@ __global__ __launch_bounds__(64) void k_msdf_generate(const float* __restrict__ 
       if (lb > um * 1.0001f) continue;  // wave-uniform
     }
 #endif
-    const float t = msdf_nearest_t(r, px, py);
-    float Ex, Ey, Tx, Ty;
-    msdf_at(r, t, px, py, Ex, Ey, Tx, Ty);
-    const float d2 = Ex * Ex + Ey * Ey;
-    // orthogonality: |cross(unit tangent, unit vector to the texel)|; 0 on the curve itself
-    const float cr = Tx * Ey - Ty * Ex, den = (Tx * Tx + Ty * Ty) * d2;
-    const float ortho = den > 0.0f ? __builtin_fabsf(cr) * frcp(fsqrt(den)) : 0.0f;
+    float t, d2, ortho, side;
+    msdf_edge(r, px, py, t, d2, ortho, side);
 #pragma unroll
     for (int c = 0; c < 4; c++) {
       if (c < 3 && !((mask >> c) & 1)) continue;  // wave-uniform
@@ -176,6 +187,108 @@ __global__ __launch_bounds__(64) void k_msdf_generate(const float* __restrict__ 
 void launch_msdf_generate(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, uint32_t* out) {
   if (w <= 0 || h <= 0) return;
   FDH_LAUNCH(k_msdf_generate, dim3((w + 7) / 8, (h + 7) / 8), dim3(64), 0, s, edges, n_edges, w, h, orient, 1.0f / range, out);
+}
+
+// ------------------------------------------------------------------ step 5 of the specification: the correction pass
+__device__ __forceinline__ int msdf_ch(uint32_t v, int k) { return (int)((v >> (8 * k)) & 255u); }
+__device__ __forceinline__ int msdf_median(int a, int b, int c) {
+  const int lo = a < b ? a : b, hi = a < b ? b : a;
+  const int m = hi < c ? hi : c;
+  return lo > m ? lo : m;
+}
+__device__ __forceinline__ int msdf_median(uint32_t v) { return msdf_median(msdf_ch(v, 0), msdf_ch(v, 1), msdf_ch(v, 2)); }
+// how far a texel's median is from the outline's value 127.5, doubled
+__device__ __forceinline__ int msdf_depth(uint32_t v) { const int e = 2 * msdf_median(v) - 255; return e < 0 ? -e : e; }
+// The pair (a, b) of texels, a the left or upper one, and the channels (R, G), (G, B), (R, B) for cp = 0, 1, 2: do they cross between the two
+// centres, and is that crossing a candidate -- both medians on one side of 127.5 and the interpolated one on the other?  Then it is at
+// N / D of the way from a to b, and `inside` says on which side the interpolated median lies.  Integers only: whichever lane asks, and
+// the reference, get the same answer.
+__device__ __forceinline__ bool msdf_candidate(uint32_t a, uint32_t b, int cp, int& N, int& D, bool& inside) {
+  const int i = cp == 1 ? 1 : 0, j = cp == 0 ? 1 : 2;
+  N = msdf_ch(a, i) - msdf_ch(a, j);
+  D = N - (msdf_ch(b, i) - msdf_ch(b, j));
+  if (D < 0) { N = -N; D = -D; }
+  int V[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) V[k] = msdf_ch(a, k) * D + N * (msdf_ch(b, k) - msdf_ch(a, k));  // D times channel k at the crossing
+  const int X = msdf_median(V[0], V[1], V[2]), ma = msdf_median(a), mb = msdf_median(b);
+  inside = 2 * X > 255 * D;
+  const bool outside = 2 * X < 255 * D;
+  const bool crosses = (D > 0) & (N > 0) & (N < D);  // (&, |: a handful of compares, nothing to branch around)
+  return crosses & (((2 * ma > 255) & (2 * mb > 255) & outside) | ((2 * ma < 255) & (2 * mb < 255) & inside));
+}
+
+// The one cross-lane operation of this file: does any lane of the wave say yes?  On the device a ballot.  A host build that emulates the
+// 64 lanes of a wave together brings its own (tests/msdf_correct_emu); one that runs a lane at a time (tests/msdf_emu, which launches the
+// generator only) has waves of one lane, and the lane's own word is the answer.
+#ifndef FDH_MSDF_ANY
+#ifdef __HIP__
+#define FDH_MSDF_ANY(p) (__ballot(p) != 0)
+#else
+#define FDH_MSDF_ANY(p) (p)
+#endif
+#endif
+
+// One lane per texel of the quantised image `in`, one wave per 8 x 8 tile, as in k_msdf_generate.  Phase 1: a lane looks at its four pairs
+// (left, right, upper, lower neighbour; the neighbour may belong to another tile, `in` is only read) and notes the candidates in `todo`,
+// bit 3 pair + channel pair.  Phase 2, for as long as any lane of the wave holds one: every lane takes its next candidate's point q -- always
+// from the pair's left / upper texel, so that the two lanes of a pair ask about the bit-identical point and agree -- and the wave walks all
+// edges once for the true distance there.  No culling: q needs every edge.  A convicted crossing marks this lane's texel when its median
+// is at least as far from 127.5 as the other's; a marked texel leaves with R = G = B = median.  Lanes outside the image carry no
+// candidate but stay until the last ballot.
+__global__ __launch_bounds__(64) void k_msdf_correct(const float* __restrict__ edges, int n_edges, int w, int h, float orient, float step,
+                                                     const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int x = blockIdx.x * 8 + (threadIdx.x & 7), y = blockIdx.y * 8 + (threadIdx.x >> 3);
+  const bool live = x < w && y < h;
+  const int cx = x < w ? x : w - 1, cy = y < h ? y : h - 1;  // what is loaded lies inside the image whatever the lane
+  const int xl = cx > 0 ? cx - 1 : 0, xr = cx + 1 < w ? cx + 1 : w - 1, yu = cy > 0 ? cy - 1 : 0, yd = cy + 1 < h ? cy + 1 : h - 1;
+  const uint32_t c = in[(size_t)cy * w + cx];
+  const uint32_t nb[4] = {in[(size_t)cy * w + xl], in[(size_t)cy * w + xr], in[(size_t)yu * w + cx], in[(size_t)yd * w + cx]};
+  const bool has[4] = {live && x > 0, live && x + 1 < w, live && y > 0, live && y + 1 < h};
+  uint32_t todo = 0;
+#pragma unroll
+  for (int p = 0; p < 4; p++) {
+#pragma unroll
+    for (int cp = 0; cp < 3; cp++) {
+      int N, D;
+      bool inside;
+      const bool cand = msdf_candidate((p & 1) ? c : nb[p], (p & 1) ? nb[p] : c, cp, N, D, inside);
+      todo |= (uint32_t)(cand & has[p] & (n_edges > 0)) << (3 * p + cp);
+    }
+  }
+  const int depth = msdf_depth(c);
+  bool mark = false;
+  while (FDH_MSDF_ANY(todo != 0)) {  // wave-uniform
+    const int bit = todo ? __builtin_ctz(todo) : 0, p = bit / 3, cp = bit - 3 * p;
+    const uint32_t other = p == 0 ? nb[0] : (p == 1 ? nb[1] : (p == 2 ? nb[2] : nb[3]));
+    int N, D;
+    bool inside;
+    const bool cand = msdf_candidate((p & 1) ? c : other, (p & 1) ? other : c, cp, N, D, inside) & (todo != 0);
+    const float t = cand ? (float)N / (float)D : 0.0f;
+    const float ax = (float)(x - (p == 0 ? 1 : 0)) + 0.5f, ay = (float)(y - (p == 2 ? 1 : 0)) + 0.5f;
+    const float qx = p < 2 ? ax + t : ax, qy = p < 2 ? ay : ay + t;
+    float bd2 = 3.0e38f, bo = -1.0f, bs = 0.0f;
+    for (int i = 0; i < n_edges; i++) {
+      const float* __restrict__ r = edges + (size_t)i * msdf::kEdgeFloats;
+      float te, d2, ortho, side;
+      msdf_edge(r, qx, qy, te, d2, ortho, side);
+      const bool better = d2 < bd2 || (d2 == bd2 && ortho > bo);
+      bd2 = better ? d2 : bd2; bo = better ? ortho : bo; bs = better ? side : bs;
+    }
+    float d = fsqrt(bd2);
+    d = (bs >= 0.0f ? d : -d) * orient;
+    // a point within one quantisation step of the outline convicts nobody
+    const bool artefact = cand && (inside ? d < -step : d > step);
+    mark = mark | (artefact & (depth >= msdf_depth(other)));
+    todo &= todo - 1u;
+  }
+  if (live) out[(size_t)y * w + x] = mark ? ((c & 0xFF000000u) | (uint32_t)msdf_median(c) * 0x010101u) : c;
+}
+
+void launch_msdf_correct(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out) {
+  if (w <= 0 || h <= 0) return;
+  FDH_LAUNCH(k_msdf_correct, dim3((w + 7) / 8, (h + 7) / 8), dim3(64), 0, s, edges, n_edges, w, h, orient, range / 255.0f, in, out);
 }
 
 }  // namespace fdh

@@ -248,7 +248,8 @@ FDH_API int fdh_put_image(FdhContext*, int64_t key, int width, int height, const
 enum { FDH_GLYPH_LCD_FILTER = 1,
        FDH_GLYPH_LCD_CONTEXT = 2, /* filter iff fdh_set_text_lcd_filtering is on: what renderText's generateGlyph call does with
                                      ctx.textLcdFilteringEnabled() (figrender.nim:420) */
-       FDH_GLYPH_MTSDF = 4            /* fdh_put_glyph_outline: store a multi-channel + true signed distance field, not coverage */ };
+       FDH_GLYPH_MTSDF = 4,           /* fdh_put_glyph_outline: store a multi-channel + true signed distance field, not coverage */
+       FDH_GLYPH_MTSDF_CORRECT = 8    /* with FDH_GLYPH_MTSDF only: run the correction pass over the field (step 5 below) */ };
 #define FDH_GLYPH_SDF_RANGE(r) ((uint32_t)(r) << 8)   /* bits 8..15: the distance range in texels, 1..64; 0 = 4 */
 FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height, const uint8_t* rgba8, uint32_t flags, int out_rect[4]);
 /* A glyph OUTLINE rasterised on the device into the atlas -- generateGlyph's job (common/fontglyphs.nim:61-106; the reference calls
@@ -265,7 +266,9 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  * (x + 0.5, y + 0.5), is stored as floor(255 * clamp(0.5 + d / R, 0, 1) + 0.5).  Nothing is premultiplied; the image is packed and its
  * level chain built like any other (a field 1 texel wide or high, of which that chain stores nothing, gets level 0: all a field is sampled
  * at). FDH_GLYPH_MTSDF with an LCD flag, a range without FDH_GLYPH_MTSDF or above 64, more than 65535 segments and an open contour are
- * FDH_ERR_INVALID; a record-only context packs the rectangle and makes no texels.
+ * FDH_ERR_INVALID; a record-only context packs the rectangle and makes no texels.  FDH_GLYPH_MTSDF_CORRECT adds step 5; it is valid only
+ * together with FDH_GLYPH_MTSDF on this call (alone, with an LCD flag or on fdh_put_glyph_image: FDH_ERR_INVALID), and without it
+ * nothing changes.
  * The construction is Chlumsky's multi-channel distance field (V. Chlumsky, "Shape Decomposition for Multi-channel Distance Fields",
  * 2015; the "simple" edge colouring of his msdfgen), restated here; this comment is the specification, tests/msdf_ref.py implements it
  * in float64 and the device (figdraw_amd/csrc/fdh_msdf_host.h, k_msdf.hip) is held to that within 1 LSB.  All host decisions (steps 1 - 3)
@@ -299,8 +302,30 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  *    o * sign(cross(T, p - N)) * |p - N|, sign(0) = +1.  If t is 0 or 1 it is replaced by the pseudo-distance o * cross(U, p - N), U the
  *    unit tangent of step 3 at that end, when that is not larger in magnitude.  A takes all edges and no pseudo-distance.  An outline
  *    without edges -- n_segs = 0, or every segment dropped by step 1 -- is no error: it gives an all-zero image.
- * Out of scope: msdfgen's error-correction pass (thin features and near-tangent corners keep the artefacts it would mend), overlapping
- * contours, cubic segments (the outline format has none), a batched multi-glyph call (it would be a new entry point). */
+ * 5. Correction, with FDH_GLYPH_MTSDF_CORRECT only.  Input: the image F of step 4, already quantised; output: the image G.  A is never
+ *    touched.  m(p) = median(R, G, B) of texel p of F.  Everything is exact integer arithmetic except d(q) below, and every decision
+ *    reads F, never G, so the order of evaluation does not matter.
+ *    Pairs: every two texels adjacent in x or in y form a pair (a, b), a the left texel of a horizontal pair, the upper texel of a
+ *    vertical one; diagonal neighbours form no pair.
+ *    Crossings: for the channels i < j, in the order (R, G), (G, B), (R, B): N = a_i - a_j, D = N - (b_i - b_j); if D < 0 both are negated.
+ *    The two channels cross inside the pair when D > 0 and 0 < N < D, at t = N / D of the way from a's centre to b's.  D times the
+ *    (linearly interpolated) value of channel k there is V_k = a_k D + N (b_k - a_k), and X = median(V_R, V_G, V_B).
+ *    Candidates: a crossing is a candidate when 2 m(a) > 255 and 2 m(b) > 255 and 2 X < 255 D (both texels inside, the interpolated
+ *    median outside), or when 2 m(a) < 255 and 2 m(b) < 255 and 2 X > 255 D (both outside, the interpolated median inside).
+ *    Verdict: t is the float32 quotient of the integers N and D; q is the float32 point (x_a + 0.5 + t, y_a + 0.5) for a horizontal pair
+ *    and (x_a + 0.5, y_a + 0.5 + t) for a vertical one, (x_a, y_a) the texel a and the sum rounded to float32 once, after t is added.
+ *    d(q) is the true signed distance of step 4 at q, by A's rule: all edges, ties to the larger orthogonality, no pseudo-distance, times
+ *    o.  The candidate is an artefact when the interpolated median is inside and d(q) < -R / 255, or outside and d(q) > R / 255: a point
+ *    within one quantisation step of the outline convicts nobody.  An outline without edges has no artefacts.
+ *    Marking: an artefact marks the texel of its pair whose |2 m - 255| is larger, and both when they are equal.  A texel marked by any
+ *    of its up to four pairs has R = G = B = m in G; every other texel of G is F's.
+ *    So m and A of every texel are unchanged, a marked texel interpolates its median linearly towards every neighbour, a field whose
+ *    channels all agree is unchanged, and a field 1 texel wide has no horizontal pairs.  tests/msdf_correct_ref.py implements this step in
+ *    float64; an implementation in float32 can differ from it only where |d(q)| is within rounding of R / 255.
+ * Out of scope: the rest of msdfgen's error correction -- artefacts that need all four texels of a bilinear cell to show (the median
+ *    inverting on a diagonal while no pair along x or y inverts), and corner protection (step 5 does not look for corners: near one, where
+ *    the channels must disagree, it relies on the verdict alone) --, overlapping contours, cubic segments (the outline format has
+ *    none), a batched multi-glyph call (it would be a new entry point). */
 FDH_API int fdh_put_glyph_outline(FdhContext*, int64_t key, int width, int height, const float* segs, int n_segs, uint32_t flags, int out_rect[4]);
 /* putFlippy (glcontext.nim:610-620): `bytes` is a whole .flippy file (common/formatflippy.nim:77-149: "flip", version 1, then per
  * mip "mip!", w, h, zlen, raw-snappy straight RGBA8); every stored level is uploaded as is at (x >> l, y >> l). */

@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
-"""What a distance-field put costs (fdh_put_glyph_outline with FDH_GLYPH_MTSDF, k_msdf_generate), on an MI355X -> profiles/msdf.txt.
+"""What a distance-field put costs (fdh_put_glyph_outline with FDH_GLYPH_MTSDF, k_msdf_generate, and with FDH_GLYPH_MTSDF_CORRECT
+k_msdf_correct), on an MI355X -> profiles/msdf.txt.
 
-  msdf_bench.py --all OUT [--nocull-lib LIB]   every step as a child process under its own time limit, in turn, nothing started after a
-                                               failure; writes the report.  LIB: the library built with -DFDH_MSDF_NO_CULL=1
-                                               (make -C figdraw_amd/csrc variant NAME=msdf_nocull DEFS=-DFDH_MSDF_NO_CULL=1)
-  msdf_bench.py --time CASE                    the whole call on the host clock, profiler off: 200 timed calls after 20; one JSON line
-  msdf_bench.py --trace CASE [--calls N]       N calls (run it under rocprofv3 --kernel-trace --stats -f csv); one JSON line
+  msdf_bench.py --all OUT [--nocull-lib LIB] [--parent-lib LIB] [--passes N]
+                                               every step as a child process under its own time limit, in turn, nothing started after a
+                                               failure; writes the report: per case the call without and with the correction pass, then
+                                               the other libraries without it, N times over in that order (libraries alternate).
+                                               --nocull-lib: the library built with -DFDH_MSDF_NO_CULL=1
+                                               (make -C figdraw_amd/csrc variant NAME=msdf_nocull DEFS=-DFDH_MSDF_NO_CULL=1);
+                                               --parent-lib: the parent commit's library, for "the flag-off call is unchanged"
+  msdf_bench.py --time CASE [--correct]        the whole call on the host clock, profiler off: 200 timed calls after 20; one JSON line
+  msdf_bench.py --trace CASE [--correct] [--calls N]   N calls (run it under rocprofv3 --kernel-trace --stats -f csv); one JSON line
 
 Cases: small = one glyph outline ('g' of the fixture, scaled to a 32 x 32 field, range 4); large = six glyph outlines scaled and laid side by
 side in a 256 x 256 field (about 200 segments)."""
@@ -45,13 +50,16 @@ def outline(case):
     return np.concatenate(parts).astype(np.float32), 256, 256
 
 
+CORRECT = {False: {}, True: {"correct": True}}  # (a library from before the flag is driven without the keyword's bit)
+
+
 def _context():
     from figdraw_amd.context import HipContext
 
     return HipContext(atlas_size=4096, device=0)
 
 
-def time_case(case, timed=200, warm=20):
+def time_case(case, correct=False, timed=200, warm=20):
     segs, w, h = outline(case)
     ctx = _context()
     us = []
@@ -59,62 +67,73 @@ def time_case(case, timed=200, warm=20):
         if k % 100 == 0:
             ctx.reset_atlas()  # (the packer's search grows with what is packed; every call packs a new rectangle)
         t1 = time.perf_counter()
-        ctx.put_glyph_outline(1 + k, segs, w, h, mtsdf=True, sdf_range=4)
+        ctx.put_glyph_outline(1 + k, segs, w, h, mtsdf=True, sdf_range=4, **CORRECT[correct])
         t2 = time.perf_counter()
         if k >= warm:
             us.append((t2 - t1) * 1e6)
     ctx.close()
-    print(json.dumps({"case": case, "segments": len(segs), "calls": timed, "median_us": statistics.median(us), "p10_us": sorted(us)[len(us) // 10],
+    print(json.dumps({"case": case, "correct": correct, "segments": len(segs), "calls": timed, "median_us": statistics.median(us), "p10_us": sorted(us)[len(us) // 10],
                       "p90_us": sorted(us)[9 * len(us) // 10]}))
 
 
-def trace_case(case, calls):
+def trace_case(case, calls, correct=False):
     segs, w, h = outline(case)
     ctx = _context()
     for k in range(calls):
-        ctx.put_glyph_outline(1 + k, segs, w, h, mtsdf=True, sdf_range=4)
+        ctx.put_glyph_outline(1 + k, segs, w, h, mtsdf=True, sdf_range=4, **CORRECT[correct])
     ctx.close()
-    print(json.dumps({"case": case, "segments": len(segs), "calls": calls}))
+    print(json.dumps({"case": case, "correct": correct, "segments": len(segs), "calls": calls}))
 
 
 HEAD = """tools/msdf_bench.py -- a distance-field put (fdh_put_glyph_outline with FDH_GLYPH_MTSDF), MI355X.
 whole call = host clock around the call, profiler off, 200 timed calls after 20 (it packs, builds the edge records, copies them, launches
-k_msdf_generate and the level chain's blits and minifies, and synchronises); kernel = k_msdf_generate alone from a
-rocprofv3 --kernel-trace --stats run of its own, 60 calls.  cull / no cull: the product library / the -DFDH_MSDF_NO_CULL=1 build.
+k_msdf_generate, with FDH_GLYPH_MTSDF_CORRECT k_msdf_correct, and the level chain's blits and minifies, and synchronises); kernel =
+k_msdf_generate and k_msdf_correct alone from a rocprofv3 --kernel-trace --stats run of its own, 60 calls.  this / corrected: the product
+library without / with FDH_GLYPH_MTSDF_CORRECT; no cull: the -DFDH_MSDF_NO_CULL=1 build; parent: the parent commit's library.
 
 Hypotheses, stated before the numbers (nothing had been timed when they were written):
   1. small (32 x 32, one glyph): the whole call is launch plus synchronise latency -- the kernel is a few microseconds of a call of
      many tens, and culling changes nothing that can be seen in the call.
   2. large (256 x 256, about 200 segments): the kernel is VALU-bound on the cubic solve (1024 waves x 200 edges x ~300 VALU
      instructions per quadratic without culling); culling removes most edges per 8 x 8 tile and the kernel's time with it.
+  3. the flag-off call is what the parent commit's was: same launches, and k_msdf_generate's arithmetic is the parent's instruction for
+     instruction (its per-edge body moved into an inline function; 53 VGPRs before and after).
+  4. the corrected call costs one more launch: on small that is launch latency plus one wave's walk over the 34 edges for each round of
+     the few tiles that hold a candidate (no culling there), a fraction of the generator's 50 us; on large, where most of the 1024 tiles
+     leave after phase 1, it is the phase-2 rounds of the few tiles with candidates, each walking all 254 edges: a latency chain of one
+     wave, tens of microseconds, beside the generator's 190.
 """
 
 
-def run_all(out_path, nocull_lib, trace_dir):
+def run_all(out_path, nocull_lib, trace_dir, parent_lib=None, passes=1):
     me = [sys.executable, os.path.abspath(__file__)]
     lines = HEAD.splitlines() + [""]
-    libs = [("cull", None)] + ([("no cull", os.path.abspath(nocull_lib))] if nocull_lib else [])
+    libs = [("this", None, False), ("corrected", None, True)] + ([("no cull", os.path.abspath(nocull_lib), False)] if nocull_lib else [])
+    libs += [("parent", os.path.abspath(parent_lib), False)] if parent_lib else []
     ok = True
     for case in CASES:
-        for tag, lib in libs:
+        for turn, (tag, lib, correct) in enumerate(libs * passes):
             env = dict(os.environ)
             if lib:
                 env["FIGDRAW_HIP_LIB"] = lib
-            got = _step(me + ["--time", case], 300, env)
+            flag = ["--correct"] if correct else []
+            got = _step(me + ["--time", case] + flag, 300, env)
             if got is None:
                 ok = False
                 break
             r = json.loads([ln for ln in got.strip().splitlines() if ln.startswith("{")][-1])
-            d = os.path.join(trace_dir, case + "_" + tag.replace(" ", ""))
-            got = _step(["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "-o", "t", "--"] + me + ["--trace", case, "--calls", "60"], 300, env)
+            d = os.path.join(trace_dir, f"{case}_{tag.replace(' ', '')}_{turn}")
+            got = _step(["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "-o", "t", "--"] + me + ["--trace", case, "--calls", "60"] + flag, 300, env)
             if got is None:
                 ok = False
                 break
             kern = _stats(d, "*kernel_stats.csv")
             calls, us, longest = kern.get("k_msdf_generate", (0, 0.0, 0.0))
-            others = ", ".join(f"{k} {v[1] / 60:.1f}" for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1]) if k != "k_msdf_generate")
+            ccalls, cus, clongest = kern.get("k_msdf_correct", (0, 0.0, 0.0))
+            others = ", ".join(f"{k} {v[1] / 60:.1f}" for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1]) if k not in ("k_msdf_generate", "k_msdf_correct"))
             lines.append(f"{case} ({CASES[case]}, {r['segments']} segments), {tag}: whole call median {r['median_us']:.1f} us (p10 {r['p10_us']:.1f}, p90 {r['p90_us']:.1f}); "
-                         f"kernel {us / max(calls, 1):.2f} us per launch over {calls} launches, the longest {longest:.1f}")
+                         f"k_msdf_generate {us / max(calls, 1):.2f} us per launch over {calls} launches, the longest {longest:.1f}"
+                         + (f"; k_msdf_correct {cus / ccalls:.2f} us per launch over {ccalls} launches, the longest {clongest:.1f}" if ccalls else ""))
             lines.append(f"    other kernels of the call, us per call: {others}")
             print(lines[-2], flush=True)
         if not ok:
@@ -129,16 +148,19 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--all", metavar="OUT")
     ap.add_argument("--nocull-lib")
+    ap.add_argument("--parent-lib")
+    ap.add_argument("--passes", type=int, default=1)
+    ap.add_argument("--correct", action="store_true", help="with --time / --trace: put with FDH_GLYPH_MTSDF_CORRECT")
     ap.add_argument("--trace-dir", default=os.path.join(ROOT, "build", "msdf_trace"))
     ap.add_argument("--time", choices=list(CASES))
     ap.add_argument("--trace", choices=list(CASES))
     ap.add_argument("--calls", type=int, default=60)
     a = ap.parse_args()
     if a.all:
-        sys.exit(run_all(a.all, a.nocull_lib, a.trace_dir))
+        sys.exit(run_all(a.all, a.nocull_lib, a.trace_dir, a.parent_lib, a.passes))
     elif a.time:
-        time_case(a.time)
+        time_case(a.time, a.correct)
     elif a.trace:
-        trace_case(a.trace, a.calls)
+        trace_case(a.trace, a.calls, a.correct)
     else:
         ap.error("nothing to do")
