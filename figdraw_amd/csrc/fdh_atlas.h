@@ -1,10 +1,13 @@
 // fdh_atlas.h -- the image atlas (fdh_atlas.cpp): the directory of entries, the skyline packer, the level chains in device memory and
 // the scratch buffers of the device glyph pipeline: one member of Context.  The context quiesces its stream (a frame in flight may sample
 // the atlas) and hands it over with every call; the atlas does not know the context.
-// A part of fdh_context.h, which includes it below Error, FDH_HIP and DeviceBuf: not a header to include on its own.
 #pragma once
+#include <cstdint>
 #include <unordered_map>
 #include <vector>
+
+#include "fdh_memory.h"  // DeviceBuf
+#include "fdh_types.h"   // AtlasView, kMaxMips
 
 namespace fdh {
 

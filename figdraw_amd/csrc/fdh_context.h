@@ -24,237 +24,14 @@
 #include "../../include/figdraw_hip_readback.h"
 #include "../../include/figdraw_hip_stream.h"
 #include "fdh_kernels.h"
+#include "fdh_plain.h"        // Error, Aff, PickTag, PhaseSum
+#include "fdh_memory.h"       // FDH_HIP, DeviceBuf, PinnedBuf, HostVec
+#include "fdh_frame.h"        // Phase, BlurJob, Lane, Piece, FrameLayout, LaunchJob
+#include "fdh_atlas.h"        // AtlasEntry, Atlas: one member of Context
+#include "fdh_damage_host.h"  // DamageTracker, DamageReadback: two members of Context
+#include "fdh_retained.h"     // RetainedScene: one member of Context
 
 namespace fdh {
-
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-void hip_check(hipError_t e, const char* what);
-#define FDH_HIP(x) ::fdh::hip_check((x), #x)
-
-// 2D affine part of the vmath Mat4 stack: [a c tx; b d ty]
-struct Aff {
-  float a = 1, b = 0, c = 0, d = 1, tx = 0, ty = 0;
-};
-
-// Fault-hunting builds (-DFDH_POISON=<byte>): every fresh device allocation is filled with that byte before its first use -- a kernel that
-// reads memory nothing has written yet then reads the same garbage every time, not what the allocation's previous owner left.
-void poison_fresh(void* p, size_t bytes);  // fdh_context.cpp
-template <typename T>
-struct DeviceBuf {
-  T* ptr = nullptr;
-  size_t cap = 0;
-  void reserve(size_t n) {
-    if (n <= cap) return;
-    size_t want = cap ? cap : 256;
-    while (want < n) want *= 2;
-    T* fresh = nullptr;  // allocate first: a failing hipMalloc (FDH_HIP throws) must leave ptr / cap describing a live block
-    FDH_HIP(hipMalloc((void**)&fresh, want * sizeof(T)));
-    poison_fresh(fresh, want * sizeof(T));
-    if (ptr) (void)hipFree(ptr);
-    ptr = fresh;
-    cap = want;
-  }
-  void reserve_exact(size_t n) {  // no doubling: a block of tens of megabytes is the size that was asked for
-    if (n <= cap) return;
-    T* fresh = nullptr;
-    FDH_HIP(hipMalloc((void**)&fresh, n * sizeof(T)));
-    poison_fresh(fresh, n * sizeof(T));
-    if (ptr) (void)hipFree(ptr);
-    ptr = fresh;
-    cap = n;
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-  }
-};
-
-template <typename T>
-struct PinnedBuf {
-  T *ptr = nullptr, *dev = nullptr;  // the block as the host addresses it, and as the device does (taken once, when the block is allocated)
-  size_t cap = 0;
-  void reserve(size_t n) {
-    if (n <= cap) return;
-    size_t want = cap ? cap : 256;
-    while (want < n) want *= 2;
-    reserve_exact(want);
-  }
-  void reserve_exact(size_t n) {  // no doubling: a block of tens of megabytes is the size that was asked for
-    if (n <= cap) return;
-    T *fresh = nullptr, *fresh_dev = nullptr;
-    FDH_HIP(hipHostMalloc((void**)&fresh, n * sizeof(T), hipHostMallocDefault));
-    if (hipError_t e = hipHostGetDevicePointer((void**)&fresh_dev, fresh, 0)) { (void)hipHostFree(fresh); FDH_HIP(e); }
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = fresh; dev = fresh_dev; cap = n;
-  }
-  void release() {
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = dev = nullptr;
-    cap = 0;
-  }
-};
-
-// A growable array of plain data, in ordinary memory or -- `pinned` -- in host memory the GPU fetches over PCIe (hipHostMalloc).
-// Pinned memory is written once, front to back, and never read by the CPU: on this platform the CPU's loads from it are not
-// served from its caches (a record read back from a pinned lane cost ~100 ns; round 4 measured 82 us for a 700-record frame that
-// took 4 us from ordinary memory).  Growth copies what the array holds (doubling: rare once a context has seen its scene).
-//
-// `vram` (with `pinned`): the same role in DEVICE memory the host writes through the PCIe BAR.  On the MI355X boxes all of HBM is
-// host-addressable (large BAR): the CPU's stores into a hipExtMallocWithFlags(hipDeviceMallocUncached) block are write-combined
-// posted writes (measured: 128 KB in 3.2 us = 41 GB/s, tools/microbench/bar_write.hip) and the GPU reads what they wrote from its
-// own memory instead of fetching it over the link with a round trip per lane: k_upload_frame 7.1 -> ~3 us.  Write-only for the
-// CPU -- a load from it crosses the link uncached -- so growth does NOT carry contents over (callers set n = 0 first, as the pinned
-// mirrors always did), and a store fence (store_fence()) precedes the hand-over to whoever launches the kernels.
-bool vram_staging(int device);  // large-BAR device and FDH_VRAM_STAGING != 0, decided per device ordinal (fdh_vram.cpp)
-// Device blocks for staging come from, and go back to, a process-wide store by size class (powers of two from 4 KB): they are
-// never handed back to the driver while the process lives.  A block the driver recycles may be memory another allocation's
-// kernels wrote through the L2s; the host's stores reach memory BESIDE those caches, and a line written back later lands on top
-// of them (tools/thread_churn.py: fresh contexts on four host threads, wrong first frames or a fault in ~5 % of runs).  Staging
-// blocks are only ever written by the host and read uncached by the device, so recycled among themselves they carry no such lines.
-// The store is keyed by DEVICE ORDINAL: a block allocated on GPU 0 never reaches a context on GPU 1.
-void* vram_block_acquire(int device, size_t bytes, size_t* size_class);  // throws Error on failure
-void vram_block_release(int device, void* p, size_t size_class);
-size_t vram_store_bytes(int device);   // bytes the store of a device holds (released blocks)
-int vram_contexts_alive(int device);   // device contexts alive on `device` (the deep strips' threshold goes by it: Context::schedule)
-void vram_context_born(int device);    // a device context exists on `device` ...
-void vram_context_gone(int device);    // ... and is gone: with the last one, the device's store is trimmed to kVramStoreKeep
-constexpr size_t kVramStoreKeep = (size_t)16 << 20;
-inline void store_fence() {
-#if defined(__x86_64__) || defined(__i386__)
-  __builtin_ia32_sfence();
-#else
-  __sync_synchronize();
-#endif
-}
-template <typename T>
-struct HostVec {
-  T* p = nullptr;
-  size_t n = 0, cap = 0;
-  bool pinned = false, vram = false;
-  int dev = 0;  // device ordinal of a vram block
-  HostVec() = default;
-  HostVec(const HostVec&) = delete;
-  HostVec& operator=(const HostVec&) = delete;
-  ~HostVec() { release(); }
-  void free_block(T* q) { if (!q) return; if (pinned && vram) vram_block_release(dev, q, vram_bytes_); else if (pinned) (void)hipHostFree(q); else std::free(q); }
-  size_t vram_bytes_ = 0;  // size class of the device block p (vram_block_acquire)
-  void release() {
-    free_block(p);
-    p = nullptr; n = cap = 0;
-  }
-  void reserve(size_t want) {
-    if (want <= cap) return;
-    size_t c = cap ? cap : 256;
-    while (c < want) c *= 2;
-    T* fresh = nullptr;
-    size_t fresh_bytes = 0;
-    if (pinned && vram) fresh = static_cast<T*>(vram_block_acquire(dev, c * sizeof(T), &fresh_bytes));
-    else if (pinned) FDH_HIP(hipHostMalloc((void**)&fresh, c * sizeof(T), hipHostMallocDefault));
-    else if (!(fresh = static_cast<T*>(std::aligned_alloc(64, (c * sizeof(T) + 63) & ~(size_t)63)))) throw std::bad_alloc();
-    if (n && !(pinned && vram)) std::memcpy(static_cast<void*>(fresh), static_cast<const void*>(p), n * sizeof(T));
-    free_block(p);
-    p = fresh; cap = c; vram_bytes_ = fresh_bytes;
-  }
-  // the block as the GPU addresses it
-  const uint8_t* device_view() const {
-    if (!p) return nullptr;
-    if (pinned && vram) return reinterpret_cast<const uint8_t*>(p);
-    void* d = nullptr;
-    FDH_HIP(hipHostGetDevicePointer(&d, const_cast<void*>(static_cast<const void*>(p)), 0));
-    return static_cast<const uint8_t*>(d);
-  }
-  T& operator[](size_t i) { return p[i]; }
-  const T& operator[](size_t i) const { return p[i]; }
-  T* slot() { if (n == cap) reserve(n + 1); return p + n; }  // the next element's place (not yet counted)
-  size_t size() const { return n; }
-  bool empty() const { return n == 0; }
-  T& back() { return p[n - 1]; }
-  void clear() { n = 0; }
-  void append(const T* src, size_t k) { if (!k) return; reserve(n + k); std::memcpy(static_cast<void*>(p + n), static_cast<const void*>(src), k * sizeof(T)); n += k; }
-};
-
-}  // namespace fdh
-#include "fdh_atlas.h"  // AtlasEntry, Atlas: one member of Context
-namespace fdh {
-
-struct Phase {
-  int first = 0, count = 0;
-  int blur = -1;  // index into blurs: executed before this phase's composite
-  int bin_x0 = 0, bin_y0 = 0, bin_x1 = 0, bin_y1 = 0;  // bins touched by the phase's draws
-  bool has_masks = false; // clip / rect-mask ops present
-  bool has_atlas = false; // axis-aligned atlas quads at >= 1:1 present (k_composite_tiles<2> unless has_slow)
-  bool has_slow = false;  // some draw needs k_composite_tiles<true> (atlas / rotated quad / bezier / rect-mask setup)
-  bool has_slow_atlas = false;  // ... and one of them is an atlas quad off the 4-wide path (rotated, or minified over mip levels): the 168-register form of that build
-  bool has_rot = false;   // rotated / skewed SDF quads whose edge functions fit 32 bits (F_EDGE32): the 4-wide path of builds <8> and <3>
-};
-struct BlurJob {
-  float radius;
-  int x0, y0, x1, y1;  // footprint: the mode-17 quad's pixel bounds
-  int fuse_draw;       // record index of the consuming mode-17 quad when k_blur_v composites it, else -1
-  BlurTaps taps;
-};
-
-// ------------------------------------------------------------------ the recorded frame
-// A frame's draw records are produced in their FINAL form while the calls arrive -- the 128-byte DrawRec the compositor reads,
-// the 24-byte BinRec the bin kernel reads (pixel bounds, saturated core, list-entry flags), the quad extensions: nothing is
-// built a second time at submit.  A LANE is what one thread records: lane 0 belongs to the thread that calls the context,
-// lanes 1.. to the walk pool's threads (fdh_frontend.cpp: large sibling groups of the scene tree are decomposed in parallel).
-// Picking (include/figdraw_hip_pick.h): each record's tag, kept beside the records of its lane while the frame has picking on.
-struct PickTag { int32_t z, id; };
-// The frame in painter's order is a list of PIECES, each a run of consecutive records of one lane.  A finished piece is
-// PUBLISHED -- copied, by the thread that recorded it, into the lane's pinned mirror arrays -- and the upload kernel gathers the
-// published pieces into the dense device arrays (k_upload_frame).
-struct Lane {
-  HostVec<DrawRec> recs;
-  HostVec<BinRec> bins;   // bins[i].box IS the bounds of record i (clip pushes: the union of their content, final at the pop)
-  HostVec<QuadExt> exts;  // DrawRec::ext of an F_GENERAL record indexes THIS array; the upload re-bases it
-  HostVec<uint32_t> boxes;  // the records' 4-byte bin boxes (what k_bin_draws scans; the device derives its own from the BinRecs):
-                            // kept here for the chunk boxes -- the union box of every 256 draws -- which Context::build_misc builds over the pieces
-  HostVec<DrawRec> up_recs;  // pinned mirrors (device contexts): what the GPU reads; element i = element i of the array above
-  HostVec<BinRec> up_bins;
-  HostVec<QuadExt> up_exts;
-  HostVec<PickTag> tags;    // picking frames only: tags[i] = the tag of record i (host memory, never uploaded)
-  bool device = false;
-  const uint8_t *d_recs = nullptr, *d_bins = nullptr, *d_exts = nullptr;  // the mirrors as the device sees them (taken when a mirror is allocated)
-  size_t pub_recs = 0, pub_exts = 0;  // elements below these may have been published this frame (kept across a mirror's growth)
-  // List stride (the largest number of list entries any bin of any phase can receive: it sizes the bin lists): a 2-D difference
-  // array over the bin grid, four updates per record when its bounds are final, evaluated per phase (count_close).
-  std::vector<int> diff;
-  int dw = 0, dh = 0;
-  int tx0 = 0, ty0 = 0, tx1 = 0, ty1 = 0;
-  bool touched = false;
-  uint64_t stamp = 0;  // the frame a pool thread's lane was last cleared for
-  void set_pinned(bool on, int dev) {
-    device = on;
-    up_recs.pinned = up_bins.pinned = up_exts.pinned = on;
-    up_recs.vram = up_bins.vram = up_exts.vram = on && vram_staging(dev);
-    up_recs.dev = up_bins.dev = up_exts.dev = dev;
-  }
-  void clear() { recs.clear(); bins.clear(); exts.clear(); boxes.clear(); tags.clear(); pub_recs = pub_exts = 0; }
-  void publish(uint32_t first, uint32_t n, uint32_t ext_first, uint32_t n_ext);  // records / extensions are final: copy them to the mirrors
-  void publish_bytes(int array, size_t at, size_t len);                          // ... a byte range of one array (0 recs, 1 bins, 2 exts)
-  void count_begin(int bins_x, int bins_y);
-  void count_add(const BBox& b);
-  int count_close();  // the largest count of any bin since the last close; leaves the array zeroed
-};
-
-// what a run of records adds to its phase (kept per parallel chunk by the walk pool's threads, merged by the calling thread)
-struct PhaseSum {
-  BBox u{0, 0, 0, 0};  // union of the records' final bounds
-  bool has_masks = false, has_atlas = false, has_slow = false, has_rot = false, has_slow_atlas = false;
-  int deepest = 0;     // deepest clip nesting reached, relative to the run's start
-  int64_t frag_mode[4] = {0, 0, 0, 0}, frag_ellip = 0, frag_other = 0;  // covered fragments by SdfMode 3 / 7 / 9 / 12
-};
-struct Piece {
-  int lane = 0;                     // (-1: the lane Context::consolidate_pieces copies a frame of too many pieces into)
-  uint32_t first = 0, n = 0;        // records [first, first + n) of the lane
-  uint32_t ext_first = 0, n_ext = 0;  // their quad extensions
-};
 
 struct RectMaskEntry { int kind; };  // 1 = fast analytic, 2 = real mask (glcontext.nim:36-44)
 class Context;
@@ -344,105 +121,6 @@ class Recorder {
   friend class Context;
 };
 
-// Retained scene (fdh_scene_*): the library-side half of the reference's RenderFragments (renderfragments.nim:426-544) --
-// a deep copy of the node tree plus, per root, the draw records its decomposition produced.  A frame re-decomposes only the
-// roots an update touched; every other root's records are spliced back from the cache.
-struct RetainedRoot {
-  std::vector<DrawRec> recs;     // in device form (Recorder::push_rec)
-  std::vector<BinRec> bins;      // bounds, cores, list-entry flags (the last record's LE_SHARE is decided again at every splice)
-  std::vector<QuadExt> exts;     // of this root's records, DrawRec::ext relative to exts.front()
-  std::vector<PickTag> tags;     // of this root's records, when it was walked in a picking frame (tagged)
-  bool tagged = false;
-  PhaseSum sum;
-  int64_t fragments = 0;
-  bool cacheable = false;        // no blur node inside (those split the frame into phases: re-walked every frame)
-  bool dirty = true;
-  uint64_t atlas_epoch = 0;      // image draws carry atlas positions: stale after the atlas was rebuilt
-  int cull_y0 = 0, cull_y1 = 0;  // the rows the records were culled to (Context::begin_frame)
-};
-struct RetainedLayer {
-  int32_t zlevel = 0;
-  std::vector<FdhFig> nodes;
-  std::vector<int32_t> roots;
-  std::vector<RetainedRoot> cache;  // parallel to `roots`
-};
-struct RetainedScene {
-  bool valid = false;
-  float fw = 0, fh = 0, rgba[4] = {1, 1, 1, 1};
-  bool clear = true;
-  float ui_scale = 1.0f, aa = 0.0f;
-  bool subpixel = false, variants = false;  // the text front-end settings the cached records were made under
-  uint32_t table_epoch = 0, table_epoch_seen = 0;  // bumped when a glyph-variant table first appears (rebase_side)
-  std::vector<RetainedLayer> layers;
-  std::vector<FdhGlyph> glyphs;
-  std::vector<int64_t> variant_ids;  // [glyphs][FDH_GLYPH_VARIANT_STEPS] or empty
-  std::vector<FdhDrawOp> ops;
-  std::vector<float> controls;
-  std::vector<FdhTextRect> text_rects;
-  int64_t roots_walked = 0, roots_reused = 0;  // of the last fdh_scene_render
-};
-
-// Where everything lies in a frame's device block: records | extensions | bin records | bin boxes | chunk boxes | phase table | blur
-// weight tables, byte offsets on 256-byte boundaries.  Laid out once per frame (Context::layout_frame_block) and kept with the frame.
-struct FrameLayout {
-  size_t recs = 0, exts = 0, binrecs = 0, boxes = 0, chunks = 0, phase_first = 0, tables = 0, total = 0;
-  size_t n = 0, n_ext = 0, n_chunks = 1;  // records, extensions, chunk boxes (one per 256 records)
-  std::vector<size_t> mx_h, mx_v;         // per blur node: its H / V weight table (0: none -- a filter too wide for the matrix-pipe passes)
-  size_t misc() const { return chunks; }  // "from the chunk boxes on": what a staging slot's misc buffer holds (Context::build_misc)
-  void lay_out(size_t n_recs, size_t n_exts, size_t n_phases, const std::vector<BlurJob>& blurs);  // fdh_prepare.cpp
-  // two frames put everything at the same place (`tables` and `n_chunks` follow from the fields compared)
-  bool operator==(const FrameLayout& o) const {
-    return total == o.total && recs == o.recs && exts == o.exts && binrecs == o.binrecs && boxes == o.boxes && chunks == o.chunks &&
-           phase_first == o.phase_first && n == o.n && n_ext == o.n_ext && mx_h == o.mx_h && mx_v == o.mx_v;
-  }
-};
-
-// What the launch side needs of one frame: filled by Context::prepare on the calling thread (which also fills the run table
-// the upload kernel works through), consumed by Context::issue / launch_frame on the context's submit thread, and kept
-// for fdh_replay / fdh_profile.
-struct LaunchJob {
-  struct View { DrawRec* recs = nullptr; QuadExt* exts = nullptr; BinRec* binrecs = nullptr; int* phase_first = nullptr; uint32_t* binbox = nullptr; uint32_t* chunkbox = nullptr; };
-  int W = 0, H = 0;
-  int rec_y0 = 0, rec_y1 = 0;  // rows the records were culled to (the frame, or a stripe + blur reach): a replay must stay inside
-  bool clear = true;
-  bool latency_routes = true;  // the frame was recorded for the one-kernel blur routes (Context::pick_routes)
-  uint32_t clear_rgba8 = 0xFFFFFFFFu;
-  bool opaque = false;     // the surface holds alpha 255 from the frame's first launch to its last (Context::decide_opaque)
-  std::vector<Phase> phases;
-  std::vector<BlurJob> blurs;
-  std::vector<const uint4*> mx_w_h, mx_w_v;  // per blur job: weight fragments of the matrix-pipe passes (in the frame block), or null
-  std::vector<char> blur_fused;              // per blur job: both passes run as ONE out-of-place kernel (full-frame nodes)
-  int n_fused = 0;
-  int n_recs = 0;
-  FrameLayout layout;      // of the device frame block, as this frame was prepared
-  View dv;                 // typed views into it
-  uint32_t* mask_spill = nullptr;  // clip levels beyond kMaskDepth, [level][strip][lane]; spill_stride dwords per level
-  size_t spill_stride = 0;
-  uint2* lists = nullptr;  // bin lists / counts (device)
-  uint32_t* counts = nullptr;
-  int bins_x = 0, bins_y = 0, list_stride = 0, binbox_shift = 0;
-  int big_blur = -1;       // index of the frame's largest blur job (its passes are timed on their own)
-  // the upload: the runs k_upload_frame gathers (records, bin records, extensions of every piece; phase table; blur tables)
-  std::vector<UploadRun> runs;
-  UploadTable table;       // (filled from `runs` when the frame is issued)
-  void* d_dst = nullptr;
-  int staging_slot = -1;
-  // damage tracking (fdh_set_damage_tracking): the frame is tracked; it is rendered in full whatever its key (no clear, a fused full-frame
-  // blur, more blur nodes than the resolve takes); the frame key (Context::damage_frame_key: everything outside the lists a bin's pixels depend on)
-  bool damage = false, damage_force = false;
-  uint64_t damage_key = 0;
-  int n_exts = 0;
-  // picking (include/figdraw_hip_pick.h): the frame was recorded with picking on; its records' tags in painter's order; its deepest clip
-  // nesting (what the pick kernels' clip stacks need)
-  bool pick = false;
-  std::vector<PickTag> pick_tags;
-  int pick_depth = 0;
-};
-
-}  // namespace fdh
-#include "fdh_damage_host.h"  // DamageTracker, DamageReadback: two members of Context
-namespace fdh {
-
 class Context : public Recorder {
  public:
   Context(int atlas_size, float pixel_scale, int device, uint32_t flags);
@@ -486,12 +164,12 @@ class Context : public Recorder {
   void set_ui_scale(float s) { ui_scale_ = s; }
   float ui_scale() const { return ui_scale_; }
   void render_frame(const FdhScene* scene, float fw, float fh, bool clear, const float rgba[4]);
-  // retained scenes (fdh_frontend.cpp)
-  void scene_retain(const FdhScene* scene, float fw, float fh, bool clear, const float rgba[4]);
-  void scene_update_nodes(int layer, int first, int count, const FdhFig* nodes, const FdhScene* side);
-  void scene_replace_root(int layer, int slot, const FdhFig* subtree, int n, const FdhScene* side, bool insert);
+  // retained scenes: the tree and its edits are retained_'s (fdh_retained.h); a frame of it is recorded here (fdh_frontend.cpp)
+  void scene_retain(const FdhScene* scene, float fw, float fh, bool clear, const float rgba[4]) { retained_.retain(scene, fw, fh, clear, rgba); scene_render(); }
+  void scene_update_nodes(int layer, int first, int count, const FdhFig* nodes, const FdhScene* side) { retained_.update_nodes(layer, first, count, nodes, side); }
+  void scene_replace_root(int layer, int slot, const FdhFig* subtree, int n, const FdhScene* side, bool insert) { retained_.replace_root(layer, slot, subtree, n, side, insert); }
   void scene_render();
-  void scene_stats(int64_t* walked, int64_t* reused) const { *walked = retained_.roots_walked; *reused = retained_.roots_reused; }
+  void scene_stats(int64_t* walked, int64_t* reused) const { retained_.stats(walked, reused); }
   int64_t uploaded_bytes() { drain(); return uploaded_bytes_; }
   // fault hunting (fdh_debug.cpp)
   void debug_verify_upload(uint32_t out[24]);  // fdh_debug_verify_upload
@@ -623,6 +301,9 @@ class Context : public Recorder {
   Lane& lane(int i) { return i < 0 ? *merge_lane_[(size_t)staging_i_] : *lanes_[(size_t)staging_i_][(size_t)i]; }  // (-1: consolidate_pieces' lane)
   Lane& ensure_lane(int i);
   void splice_cached(const RetainedRoot& C);
+  // render_frame's and scene_render's frame around walk(links): the frame of fw x fh UI units begun (culled, under a row stripe, by the
+  // blur reach of `scene`), the pixel scale on the transform stack, the frame ended -- or, when the walk throws, left unbegun
+  template <typename Walk> void walk_frame(float fw, float fh, bool clear, const float rgba[4], const FdhScene& scene, Walk walk);  // (fdh_frontend.cpp)
   void pick_routes();                       // begin_frame: the one-kernel blur routes (a frame alone) or the two-pass ones (frames in flight)
   void pool_slots(int slots);               // lanes 1 .. slots and their recorders, ready for a sibling group
 
@@ -703,9 +384,7 @@ class Context : public Recorder {
   uint32_t *backdrop_ = nullptr, *blur_tmp_ = nullptr;
   uint32_t* alt_ = nullptr;  // second frame surface: a fused full-frame blur renders out of place, phases alternate between fb_ and this
   uint32_t* dbg_snap_ = nullptr;
-  RetainedScene retained_;
-  void rebase_side(FdhFig* nodes, int n, const FdhScene* side);
-  void compact_side();
+  RetainedScene retained_;  // (fdh_retained.h)
   bool host_only_ = false;  // FDH_CREATE_RECORD_ONLY
   bool rec_on_ = false, rec_first_ = true, rec_mark_first_ = true;
   size_t rec_mark_ = 0;

@@ -1,9 +1,16 @@
 // fdh_damage_host.h -- the host side of damage tracking and damage readback (fdh_damage.cpp): two components of a device context, each one
 // member of Context.  The context hands them its stream, the frame's LaunchJob and surface, and profile mode's bracket around a launch
 // of the bin kind (span(true) before it, span(false) after); they do not know the context.
-// A part of fdh_context.h, which includes it below DeviceBuf, PinnedBuf and LaunchJob: not a header to include on its own.
 #pragma once
+#include <cstdint>
 #include <functional>
+#include <vector>
+
+#include "../../include/figdraw_hip_readback.h"  // FdhDamageTile
+#include "../../include/figdraw_hip_stream.h"    // FdhCodedTile
+#include "fdh_frame.h"    // LaunchJob
+#include "fdh_kernels.h"  // BinParams, CompositeParams
+#include "fdh_memory.h"   // DeviceBuf, PinnedBuf
 
 namespace fdh {
 

@@ -3,6 +3,11 @@
 // hipStream_t, so the host shim of tests/codec_emu compiles against this very file.
 #pragma once
 #include <stdint.h>
+#if defined(__HIP__)  // (the library's build; the host shim defines kBin, the vector types and hipStream_t itself before it includes this file)
+#include <hip/hip_runtime.h>
+
+#include "fdh_types.h"
+#endif
 
 namespace fdh {
 

@@ -803,25 +803,17 @@ static int scene_blur_reach(const FdhScene& scene, float ui) {
   return (int)std::min<long long>(reach, 1 << 20);
 }
 
-void Context::render_frame(const FdhScene* scene, float fw, float fh, bool clear, const float rgba[4]) {
-  if (!scene || (scene->n_layers > 0 && !scene->layers)) throw Error(FDH_ERR_INVALID, "render_frame: null scene");
+template <typename Walk> void Context::walk_frame(float fw, float fh, bool clear, const float rgba[4], const FdhScene& scene, Walk walk) {
   const float w = fw * ui_scale_, h = fh * ui_scale_;  // frameSize.scaled()
   if (w <= 0.0f || h <= 0.0f) return;
-  if (stripe_y1_ > stripe_y0_ && culling()) pending_reach_ = scene_blur_reach(*scene, ui_scale_);
+  if (stripe_y1_ > stripe_y0_ && culling()) pending_reach_ = scene_blur_reach(scene, ui_scale_);
   begin_frame((int)w, (int)h, clear, rgba);
   try {
     save_transform();
     scale(pixel_scale_, pixel_scale_);
     static thread_local LayerLinks links;  // (the arrays keep their capacity from frame to frame)
     links.layer = nullptr;
-    Walker wk{*this, *scene, ui_scale_, &links, true};
-    for (int l = 0; l < scene->n_layers; l++) {
-      const FdhLayer& L = scene->layers[l];
-      if ((L.n_nodes > 0 && !L.nodes) || (L.n_roots > 0 && !L.root_ids)) throw Error(FDH_ERR_INVALID, "render_frame: a layer's node or root array is null");
-      for (int r = 0; r < L.n_roots; r++)
-        if (L.root_ids[r] < 0 || L.root_ids[r] >= L.n_nodes) throw Error(FDH_ERR_INVALID, "render_frame: root index out of range");
-      wk.siblings(L, L.root_ids, L.n_roots);
-    }
+    walk(&links);
     restore_transform();
   } catch (...) {
     frame_begun_ = false;
@@ -830,308 +822,44 @@ void Context::render_frame(const FdhScene* scene, float fw, float fh, bool clear
   end_frame();
 }
 
-// ------------------------------------------------------------------ retained scenes (renderfragments.nim:426-544, common/transfer.nim)
-// The reference keeps a base `Renders` and lets the application insert / append / replace fragments of it between frames
-// (insertChildren, addChildren, insertRoot, updateFragment :523); its renderer still walks the whole tree every frame.  Here
-// the tree lives in the context: fdh_scene_retain copies it, fdh_scene_update_nodes / fdh_scene_replace_root / fdh_scene_insert_root
-// edit it, and fdh_scene_render re-decomposes only the roots an edit touched -- the draw records of every other root are
-// spliced back from the per-root cache (a memcpy), so a frame after a small edit costs the launches, not a tree walk.
-void Context::rebase_side(FdhFig* nodes, int n, const FdhScene* side) {
-  // the new nodes index glyph / op / control / text-rect arrays of `side`: append what they use to the retained arrays
-  RetainedScene& R = retained_;
-  for (int i = 0; i < n; i++) {
-    FdhFig& f = nodes[i];
-    if (f.glyph_count > 0) {
-      if (!side || !side->glyphs || f.glyph_first < 0 || f.glyph_first + f.glyph_count > side->n_glyphs) throw Error(FDH_ERR_INVALID, "scene update: glyph range outside the side arrays");
-      const int base = (int)R.glyphs.size();
-      R.glyphs.insert(R.glyphs.end(), side->glyphs + f.glyph_first, side->glyphs + f.glyph_first + f.glyph_count);
-      if (!R.variant_ids.empty() || side->glyph_variant_ids) {
-        // glyphs retained before any variant table existed fall back to their own image, as the new-glyph branch below does.
-        // (The table's mere presence changes how renderText treats EVERY glyph under variant positioning -- key lookup with
-        // shift 0 instead of the fractional shift -- so records cached without it are stale: table_epoch.)
-        if (R.variant_ids.empty()) R.table_epoch++;
-        for (size_t g0 = R.variant_ids.size() / FDH_GLYPH_VARIANT_STEPS; g0 < (size_t)base; g0++)
-          for (int st = 0; st < FDH_GLYPH_VARIANT_STEPS; st++) R.variant_ids.push_back(R.glyphs[g0].image_id);
-        for (int g = 0; g < f.glyph_count; g++)
-          for (int st = 0; st < FDH_GLYPH_VARIANT_STEPS; st++)
-            R.variant_ids.push_back(side->glyph_variant_ids ? side->glyph_variant_ids[(size_t)(f.glyph_first + g) * FDH_GLYPH_VARIANT_STEPS + st] : side->glyphs[f.glyph_first + g].image_id);
-      }
-      f.glyph_first = base;
+void Context::render_frame(const FdhScene* scene, float fw, float fh, bool clear, const float rgba[4]) {
+  if (!scene || (scene->n_layers > 0 && !scene->layers)) throw Error(FDH_ERR_INVALID, "render_frame: null scene");
+  walk_frame(fw, fh, clear, rgba, *scene, [&](LayerLinks* links) {
+    Walker wk{*this, *scene, ui_scale_, links, true};
+    for (int l = 0; l < scene->n_layers; l++) {
+      const FdhLayer& L = scene->layers[l];
+      if ((L.n_nodes > 0 && !L.nodes) || (L.n_roots > 0 && !L.root_ids)) throw Error(FDH_ERR_INVALID, "render_frame: a layer's node or root array is null");
+      for (int r = 0; r < L.n_roots; r++)
+        if (L.root_ids[r] < 0 || L.root_ids[r] >= L.n_nodes) throw Error(FDH_ERR_INVALID, "render_frame: root index out of range");
+      wk.siblings(L, L.root_ids, L.n_roots);
     }
-    if (f.text_rect_count > 0) {
-      if (!side || !side->text_rects || f.text_rect_first < 0 || f.text_rect_first + f.text_rect_count > side->n_text_rects) throw Error(FDH_ERR_INVALID, "scene update: text-rect range outside the side arrays");
-      const int base = (int)R.text_rects.size();
-      R.text_rects.insert(R.text_rects.end(), side->text_rects + f.text_rect_first, side->text_rects + f.text_rect_first + f.text_rect_count);
-      f.text_rect_first = base;
-    }
-    if (f.op_count > 0) {
-      if (!side || !side->ops || f.op_first < 0 || f.op_first + f.op_count > side->n_ops) throw Error(FDH_ERR_INVALID, "scene update: drawable-op range outside the side arrays");
-      const int base = (int)R.ops.size();
-      for (int k = 0; k < f.op_count; k++) {
-        FdhDrawOp op = side->ops[f.op_first + k];
-        if (op.ctrl_count > 0) {
-          if (!side->controls || op.ctrl_first < 0 || op.ctrl_first + op.ctrl_count > side->n_controls) throw Error(FDH_ERR_INVALID, "scene update: control-point range outside the side arrays");
-          const int cb = (int)(R.controls.size() / 2);
-          R.controls.insert(R.controls.end(), side->controls + 2 * op.ctrl_first, side->controls + 2 * (op.ctrl_first + op.ctrl_count));
-          op.ctrl_first = cb;
-        }
-        R.ops.push_back(op);
-      }
-      f.op_first = base;
-    }
-  }
+  });
 }
 
-// An edit either lands whole or not at all: rebase_side appends to the retained side arrays before it has seen every node of
-// the edit, so a bad range found late must take the appended entries back.
-namespace {
-struct SideMark {
-  RetainedScene& R;
-  const size_t g, v, o, c, t;
-  bool keep = false;
-  explicit SideMark(RetainedScene& r) : R(r), g(r.glyphs.size()), v(r.variant_ids.size()), o(r.ops.size()), c(r.controls.size()), t(r.text_rects.size()) {}
-  ~SideMark() {
-    if (keep) return;
-    R.glyphs.resize(g); R.variant_ids.resize(v); R.ops.resize(o); R.controls.resize(c); R.text_rects.resize(t);
-  }
-};
-}  // namespace
-
-// Every update_nodes / replace_root appends the side entries of the new nodes and orphans those of the old ones; an animated
-// text or drawable node would grow the arrays without bound (and n_glyphs past int32).  When the live entries are less than
-// half of an array that has grown past a few thousand, the arrays are rebuilt from the nodes that still reference them.  Node
-// ranges move, draw records do not depend on them: the per-root caches stay valid.
-void Context::compact_side() {
-  RetainedScene& R = retained_;
-  size_t live_g = 0, live_o = 0, live_t = 0;
-  for (const RetainedLayer& D : R.layers)
-    for (const FdhFig& f : D.nodes) { live_g += (size_t)std::max(f.glyph_count, 0); live_o += (size_t)std::max(f.op_count, 0); live_t += (size_t)std::max(f.text_rect_count, 0); }
-  auto bloated = [](size_t live, size_t have) { return have > 4096 && live * 2 < have; };
-  if (!bloated(live_g, R.glyphs.size()) && !bloated(live_o, R.ops.size()) && !bloated(live_t, R.text_rects.size())) return;
-  std::vector<FdhGlyph> glyphs;
-  std::vector<int64_t> variants;
-  std::vector<FdhDrawOp> ops;
-  std::vector<float> controls;
-  std::vector<FdhTextRect> rects;
-  const bool has_var = !R.variant_ids.empty();
-  for (RetainedLayer& D : R.layers)
-    for (FdhFig& f : D.nodes) {
-      if (f.glyph_count > 0 && f.glyph_first >= 0 && (size_t)f.glyph_first + (size_t)f.glyph_count <= R.glyphs.size()) {
-        const int base = (int)glyphs.size();
-        glyphs.insert(glyphs.end(), R.glyphs.begin() + f.glyph_first, R.glyphs.begin() + f.glyph_first + f.glyph_count);
-        if (has_var)
-          for (int g = f.glyph_first; g < f.glyph_first + f.glyph_count; g++)
-            for (int st = 0; st < FDH_GLYPH_VARIANT_STEPS; st++) {
-              const size_t at = (size_t)g * FDH_GLYPH_VARIANT_STEPS + st;
-              variants.push_back(at < R.variant_ids.size() ? R.variant_ids[at] : R.glyphs[(size_t)g].image_id);
-            }
-        f.glyph_first = base;
-      } else if (f.glyph_count > 0) f.glyph_count = 0;
-      if (f.text_rect_count > 0 && f.text_rect_first >= 0 && (size_t)f.text_rect_first + (size_t)f.text_rect_count <= R.text_rects.size()) {
-        const int base = (int)rects.size();
-        rects.insert(rects.end(), R.text_rects.begin() + f.text_rect_first, R.text_rects.begin() + f.text_rect_first + f.text_rect_count);
-        f.text_rect_first = base;
-      } else if (f.text_rect_count > 0) f.text_rect_count = 0;
-      if (f.op_count > 0 && f.op_first >= 0 && (size_t)f.op_first + (size_t)f.op_count <= R.ops.size()) {
-        const int base = (int)ops.size();
-        for (int k = 0; k < f.op_count; k++) {
-          FdhDrawOp op = R.ops[(size_t)(f.op_first + k)];
-          if (op.ctrl_count > 0 && op.ctrl_first >= 0 && 2 * ((size_t)op.ctrl_first + (size_t)op.ctrl_count) <= R.controls.size()) {
-            const int cb = (int)(controls.size() / 2);
-            controls.insert(controls.end(), R.controls.begin() + 2 * op.ctrl_first, R.controls.begin() + 2 * (op.ctrl_first + op.ctrl_count));
-            op.ctrl_first = cb;
-          } else op.ctrl_count = 0;
-          ops.push_back(op);
-        }
-        f.op_first = base;
-      } else if (f.op_count > 0) f.op_count = 0;
-    }
-  R.glyphs.swap(glyphs); R.variant_ids.swap(variants); R.ops.swap(ops); R.controls.swap(controls); R.text_rects.swap(rects);
-}
-
-// A retained layer is edited in place (subtrees compacted out, parents remapped): every parent index it holds must be -1 or
-// that of an EARLIER node (parents precede their children in a RenderList, fignodes.nim:119-163).
-static void check_parents(const FdhFig* nodes, int n, int first_index, const char* who) {
-  for (int k = 0; k < n; k++)
-    if (nodes[k].parent < -1 || nodes[k].parent >= first_index + k) throw Error(FDH_ERR_INVALID, std::string(who) + ": a node's parent must be -1 or an earlier node of the layer");
-}
-
-void Context::scene_retain(const FdhScene* scene, float fw, float fh, bool clear, const float rgba[4]) {
-  if (!scene || (scene->n_layers > 0 && !scene->layers)) throw Error(FDH_ERR_INVALID, "scene_retain: null scene");
-  for (int l = 0; l < scene->n_layers; l++) {
-    const FdhLayer& L = scene->layers[l];
-    if ((L.n_nodes > 0 && !L.nodes) || (L.n_roots > 0 && !L.root_ids)) throw Error(FDH_ERR_INVALID, "scene_retain: a layer's node or root array is null");
-    if (L.n_nodes > 32767) throw Error(FDH_ERR_INVALID, "scene_retain: more than 32767 nodes in a layer (FigIdx is int16, fignodes.nim:119)");
-    check_parents(L.nodes, L.n_nodes, 0, "scene_retain");
-  }
-  RetainedScene& R = retained_;
-  R = RetainedScene{};
-  R.fw = fw; R.fh = fh; R.clear = clear;
-  for (int i = 0; i < 4; i++) R.rgba[i] = rgba[i];
-  if (scene->glyphs && scene->n_glyphs > 0) R.glyphs.assign(scene->glyphs, scene->glyphs + scene->n_glyphs);
-  if (scene->glyph_variant_ids && scene->n_glyphs > 0) R.variant_ids.assign(scene->glyph_variant_ids, scene->glyph_variant_ids + (size_t)scene->n_glyphs * FDH_GLYPH_VARIANT_STEPS);
-  if (scene->ops && scene->n_ops > 0) R.ops.assign(scene->ops, scene->ops + scene->n_ops);
-  if (scene->controls && scene->n_controls > 0) R.controls.assign(scene->controls, scene->controls + 2 * (size_t)scene->n_controls);
-  if (scene->text_rects && scene->n_text_rects > 0) R.text_rects.assign(scene->text_rects, scene->text_rects + scene->n_text_rects);
-  R.layers.resize((size_t)std::max(scene->n_layers, 0));
-  for (int l = 0; l < scene->n_layers; l++) {
-    const FdhLayer& L = scene->layers[l];
-    RetainedLayer& D = R.layers[(size_t)l];
-    D.zlevel = L.zlevel;
-    if (L.n_nodes > 0) D.nodes.assign(L.nodes, L.nodes + L.n_nodes);
-    if (L.n_roots > 0) D.roots.assign(L.root_ids, L.root_ids + L.n_roots);
-    for (int r : D.roots) if (r < 0 || r >= L.n_nodes) throw Error(FDH_ERR_INVALID, "scene_retain: root index out of range");
-    D.cache.assign(D.roots.size(), RetainedRoot{});
-  }
-  R.valid = true;
-  scene_render();
-}
-
-// the root (index into the layer's nodes) each node hangs under; parents precede their children in a RenderList (fignodes.nim:119-163)
-static std::vector<int> roots_of(const RetainedLayer& D) {
-  std::vector<int> ro(D.nodes.size());
-  for (size_t i = 0; i < D.nodes.size(); i++) {
-    const int p = D.nodes[i].parent;
-    ro[i] = (p < 0 || (size_t)p >= i) ? (int)i : ro[(size_t)p];
-  }
-  return ro;
-}
-
-void Context::scene_update_nodes(int layer, int first, int count, const FdhFig* nodes, const FdhScene* side) {
-  RetainedScene& R = retained_;
-  if (!R.valid) throw Error(FDH_ERR_INVALID, "scene_update_nodes: no retained scene (fdh_scene_retain first)");
-  if (layer < 0 || (size_t)layer >= R.layers.size()) throw Error(FDH_ERR_INVALID, "scene_update_nodes: layer out of range");
-  RetainedLayer& D = R.layers[(size_t)layer];
-  if (count <= 0) return;
-  if (!nodes || first < 0 || (size_t)first + (size_t)count > D.nodes.size()) throw Error(FDH_ERR_INVALID, "scene_update_nodes: node range out of bounds");
-  check_parents(nodes, count, first, "scene_update_nodes");
-  // the roots above the range before the edit (a node may change its parent) ...
-  std::vector<int> before = roots_of(D);
-  std::vector<FdhFig> fresh(nodes, nodes + count);
-  {
-    SideMark mark(R);  // a bad side range throws out of rebase_side: the entries it had appended go with it
-    rebase_side(fresh.data(), count, side);
-    mark.keep = true;
-  }
-  std::copy(fresh.begin(), fresh.end(), D.nodes.begin() + first);
-  std::vector<int> after = roots_of(D);  // ... and after it
-  for (size_t s = 0; s < D.roots.size(); s++)
-    for (int i = first; i < first + count; i++)
-      if (before[(size_t)i] == D.roots[s] || after[(size_t)i] == D.roots[s]) { D.cache[s].dirty = true; break; }
-  compact_side();
-}
-
-void Context::scene_replace_root(int layer, int slot, const FdhFig* subtree, int n, const FdhScene* side, bool insert) {
-  RetainedScene& R = retained_;
-  if (!R.valid) throw Error(FDH_ERR_INVALID, "scene_replace_root: no retained scene (fdh_scene_retain first)");
-  if (layer < 0 || (size_t)layer >= R.layers.size()) throw Error(FDH_ERR_INVALID, "scene_replace_root: layer out of range");
-  RetainedLayer& D = R.layers[(size_t)layer];
-  if (slot < 0 || (size_t)slot > D.roots.size() || (!insert && (size_t)slot == D.roots.size())) throw Error(FDH_ERR_INVALID, "scene_replace_root: root slot out of range");
-  if (n < 0 || (n > 0 && !subtree)) throw Error(FDH_ERR_INVALID, "scene_replace_root: bad subtree");
-  if (n > 0 && subtree[0].parent >= 0) throw Error(FDH_ERR_INVALID, "scene_replace_root: the subtree's first node must be its root (parent -1)");
-  for (int i = 1; i < n; i++)
-    if (subtree[i].parent < 0 || subtree[i].parent >= i) throw Error(FDH_ERR_INVALID, "scene_replace_root: subtree parents must precede their children");
-  // Everything that can fail happens BEFORE the retained layer is touched: the node budget, and the re-basing of the new
-  // nodes' side ranges (into a copy; what it appended to the side arrays is taken back if it throws).  A failed call leaves
-  // the scene exactly as it was.
-  std::vector<int> ro;
-  size_t kept_count = D.nodes.size();
-  int old_root = -1;
-  if (!insert) {
-    ro = roots_of(D);
-    old_root = D.roots[(size_t)slot];
-    kept_count = 0;
-    for (size_t i = 0; i < D.nodes.size(); i++) if (ro[i] != old_root) kept_count++;
-  }
-  if (kept_count + (size_t)n > 32767u) throw Error(FDH_ERR_INVALID, "scene_replace_root: more than 32767 nodes in a layer (FigIdx is int16, fignodes.nim:119)");
-  std::vector<FdhFig> fresh;
-  if (n > 0) {
-    fresh.assign(subtree, subtree + n);
-    SideMark mark(R);
-    rebase_side(fresh.data(), n, side);
-    mark.keep = true;
-  }
-  // ---- commit (nothing below throws but std::bad_alloc)
-  if (!insert) {  // drop the old subtree, compacting the node array
-    std::vector<int> remap(D.nodes.size(), -1);
-    std::vector<FdhFig> kept;
-    kept.reserve(kept_count + (size_t)n);
-    for (size_t i = 0; i < D.nodes.size(); i++)
-      if (ro[i] != old_root) { remap[i] = (int)kept.size(); kept.push_back(D.nodes[i]); }
-    for (FdhFig& f : kept) if (f.parent >= 0) f.parent = remap[(size_t)f.parent];
-    // (the other roots' caches stay clean, and their records' tags name nodes by index: they move with the compaction)
-    for (size_t s = 0; s < D.cache.size(); s++)
-      if ((int)s != slot)
-        for (PickTag& g : D.cache[s].tags) if (g.id >= 0 && (size_t)g.id < remap.size()) g.id = remap[(size_t)g.id];
-    // (a root slot whose node hangs inside the removed subtree -- fdh_scene_update_nodes may have given a listed root a parent --
-    // goes with it: it would name a node that no longer exists)
-    for (size_t s = D.roots.size(); s-- > 0;) {
-      if ((int)s == slot) continue;
-      const int to = remap[(size_t)D.roots[s]];
-      if (to >= 0) { D.roots[s] = to; continue; }
-      D.roots.erase(D.roots.begin() + (std::ptrdiff_t)s);
-      D.cache.erase(D.cache.begin() + (std::ptrdiff_t)s);
-      if ((int)s < slot) slot--;
-    }
-    D.nodes.swap(kept);
-    if (n == 0) { D.roots.erase(D.roots.begin() + slot); D.cache.erase(D.cache.begin() + slot); compact_side(); return; }
-  } else {
-    if (n == 0) return;
-    D.roots.insert(D.roots.begin() + slot, 0);
-    D.cache.insert(D.cache.begin() + slot, RetainedRoot{});
-  }
-  const int base = (int)D.nodes.size();
-  for (int i = 1; i < n; i++) fresh[(size_t)i].parent += base;
-  D.nodes.insert(D.nodes.end(), fresh.begin(), fresh.end());
-  D.roots[(size_t)slot] = base;
-  D.cache[(size_t)slot] = RetainedRoot{};
-  compact_side();
-}
-
+// ------------------------------------------------------------------ retained scenes (fdh_retained.h)
+// A frame of the retained scene: the roots an edit touched are decomposed again, and their records kept; the records of every other
+// root are spliced back from its cache.
 void Context::scene_render() {
   RetainedScene& R = retained_;
-  if (!R.valid) throw Error(FDH_ERR_INVALID, "scene_render: no retained scene (fdh_scene_retain first)");
-  const float w = R.fw * ui_scale_, h = R.fh * ui_scale_;
-  if (w <= 0.0f || h <= 0.0f) return;
-  // every cached record depends on these front-end settings (the text path snaps glyph positions and picks shifts / variant
-  // images by the two sub-pixel switches, figrender.nim:464-476)
-  const bool config_changed = R.ui_scale != ui_scale_ || R.aa != aa_ || R.subpixel != subpixel_enabled_ || R.variants != subpixel_variants_ ||
-                              R.table_epoch != R.table_epoch_seen;
-  R.ui_scale = ui_scale_; R.aa = aa_; R.subpixel = subpixel_enabled_; R.variants = subpixel_variants_; R.table_epoch_seen = R.table_epoch;
-  for (const RetainedLayer& D : R.layers)
-    for (int r : D.roots) if (r < 0 || (size_t)r >= D.nodes.size()) throw Error(FDH_ERR_INVALID, "scene_render: root index out of range");
-  std::vector<FdhLayer> views(R.layers.size());
-  for (size_t l = 0; l < R.layers.size(); l++) {
-    RetainedLayer& D = R.layers[l];
-    views[l] = FdhLayer{D.zlevel, (int32_t)D.nodes.size(), (int32_t)D.roots.size(), 0, D.nodes.data(), D.roots.data()};
-  }
-  FdhScene view{};
-  view.layers = views.data(); view.n_layers = (int32_t)views.size();
-  view.glyphs = R.glyphs.data(); view.n_glyphs = (int32_t)R.glyphs.size();
-  view.glyph_variant_ids = R.variant_ids.empty() ? nullptr : R.variant_ids.data();
-  view.ops = R.ops.data(); view.n_ops = (int32_t)R.ops.size();
-  view.controls = R.controls.data(); view.n_controls = (int32_t)(R.controls.size() / 2);
-  view.text_rects = R.text_rects.data(); view.n_text_rects = (int32_t)R.text_rects.size();
-  R.roots_walked = R.roots_reused = 0;
-  if (stripe_y1_ > stripe_y0_ && culling()) pending_reach_ = scene_blur_reach(view, ui_scale_);
-  begin_frame((int)w, (int)h, R.clear, R.rgba);
-  rec_diff_upload_ = true;  // consecutive frames of a retained scene differ in a few records: Context::patch_runs uploads the difference
-  try {
-    save_transform();
-    scale(pixel_scale_, pixel_scale_);
-    static thread_local LayerLinks links;  // (the arrays keep their capacity from frame to frame)
-    links.layer = nullptr;
-    Walker wk{*this, view, ui_scale_, &links, false};  // (roots are walked one by one: each has its cache entry)
+  if (!R.valid()) throw Error(FDH_ERR_INVALID, "scene_render: no retained scene (fdh_scene_retain first)");
+  const RetainedScene::View V = R.view();
+  const FdhScene& view = V.scene;
+  walk_frame(R.fw(), R.fh(), R.clear(), R.rgba(), view, [&](LayerLinks* links) {
+    rec_diff_upload_ = true;  // consecutive frames of a retained scene differ in a few records: Context::patch_runs uploads the difference
+    const bool config_changed = R.latch_settings(ui_scale_, aa_, subpixel_enabled_, subpixel_variants_);
+    R.count_begin();
+    Walker wk{*this, view, ui_scale_, links, false};  // (roots are walked one by one: each has its cache entry)
     Lane& L0 = lane(0);
-    for (size_t l = 0; l < R.layers.size(); l++) {
-      RetainedLayer& D = R.layers[l];
+    for (size_t l = 0; l < R.n_layers(); l++) {
+      const RetainedLayer& D = R.layer(l);
+      RetainedRoot* const caches = D.roots.empty() ? nullptr : &R.cache(l, 0);  // (parallel to D.roots)
       for (size_t s = 0; s < D.roots.size(); s++) {
-        RetainedRoot& C = D.cache[s];
+        RetainedRoot& C = caches[s];
         // (cached records were culled to the rows in force when they were made: good for any frame that produces no row beyond them)
         if (!C.dirty && C.cacheable && !config_changed && C.cull_y0 <= cull_y0_ && C.cull_y1 >= cull_y1_ && C.atlas_epoch == atlas_.epoch() &&
             (C.tagged || !pick_frame_)) {
           splice_cached(C);
-          R.roots_reused++;
+          R.count_reused();
           continue;
         }
         const size_t r0 = L0.recs.n, e0 = L0.exts.n, p0 = phases_.size(), b0 = blurs_.size();
@@ -1139,8 +867,8 @@ void Context::scene_render() {
         const int d0 = depth_now_;
         add_sum(sum_, 0);  // (what the phase has so far goes to the phase: the root's own summary starts from nothing)
         sum_ = PhaseSum{};
-        wk.node(views[l], D.roots[s]);
-        R.roots_walked++;
+        wk.node(view.layers[l], D.roots[s]);
+        R.count_walked();
         C.dirty = false;
         C.atlas_epoch = atlas_.epoch();
         C.cull_y0 = cull_y0_; C.cull_y1 = cull_y1_;
@@ -1160,12 +888,7 @@ void Context::scene_render() {
         }
       }
     }
-    restore_transform();
-  } catch (...) {
-    frame_begun_ = false;
-    throw;
-  }
-  end_frame();
+  });
 }
 
 // A retained root's cached records take their place in lane 0 (fdh_scene_render): a memcpy per array, the extension indices
@@ -1182,16 +905,7 @@ void Context::splice_cached(const RetainedRoot& C) {
   L.boxes.reserve(L.bins.n);
   for (size_t i = r0; i < L.bins.n; i++) { L.count_add(L.bins[i].box); L.boxes[i] = bin_box_of(L.bins[i].box, 6 + binbox_shift_); }
   L.boxes.n = L.bins.n;
-  bbox_union(sum_.u, C.sum.u);
-  sum_.has_masks = sum_.has_masks || C.sum.has_masks;
-  sum_.has_atlas = sum_.has_atlas || C.sum.has_atlas;
-  sum_.has_slow = sum_.has_slow || C.sum.has_slow;
-  sum_.has_slow_atlas = sum_.has_slow_atlas || C.sum.has_slow_atlas;
-  sum_.has_rot = sum_.has_rot || C.sum.has_rot;
-  sum_.deepest = std::max(sum_.deepest, depth_now_ + C.sum.deepest);
-  for (int k = 0; k < 4; k++) sum_.frag_mode[k] += C.sum.frag_mode[k];
-  sum_.frag_ellip += C.sum.frag_ellip;
-  sum_.frag_other += C.sum.frag_other;
+  sum_.merge(C.sum, depth_now_);
   fragments_ += C.fragments;
   if (!C.recs.empty()) link_share(r0);  // the record in front of the splice may share its distance field with the first one here
 }

@@ -22,12 +22,6 @@ inline Aff aff_mul(const Aff& m, const Aff& n) {
   return r;
 }
 
-inline bool bbox_empty(const BBox& b) { return b.x1 <= b.x0 || b.y1 <= b.y0; }
-inline void bbox_union(BBox& a, const BBox& b) {
-  if (bbox_empty(b)) return;
-  if (bbox_empty(a)) { a = b; return; }
-  a.x0 = std::min(a.x0, b.x0); a.y0 = std::min(a.y0, b.y0); a.x1 = std::max(a.x1, b.x1); a.y1 = std::max(a.y1, b.y1);
-}
 BlurTaps make_taps(float blur_radius);
 uint32_t bin_box_of(const BBox& b, int shift);
 FdhColor sample_fill(const FdhFill& f, float t);

@@ -1121,12 +1121,7 @@ void Context::close_piece() {
   if (p.n == 0) pieces_.pop_back();
 }
 void Context::add_sum(const PhaseSum& s, int depth_base) {
-  Phase& ph = phases_.back();
-  ph.has_masks = ph.has_masks || s.has_masks;
-  ph.has_atlas = ph.has_atlas || s.has_atlas;
-  ph.has_slow = ph.has_slow || s.has_slow;
-  ph.has_slow_atlas = ph.has_slow_atlas || s.has_slow_atlas;
-  ph.has_rot = ph.has_rot || s.has_rot;
+  phases_.back().merge_flags(s);
   bbox_union(phase_u_, s.u);
   deepest_clip_ = std::max(deepest_clip_, depth_base + s.deepest);
   if (phases_.size() == 1) {  // the phase-0 composite launch's work units

@@ -323,6 +323,34 @@ def test_animated_text_node_does_not_grow_the_side_arrays():
     ctx.close()
 
 
+def test_failed_retain_leaves_the_retained_scene_untouched():
+    """fdh_scene_retain validates everything -- the root indices too -- before it touches the scene it holds: a retain that fails
+    leaves the previous scene retained, its per-root caches included"""
+    import ctypes as C
+    from figdraw_amd.context import _F4
+
+    w, h = 512, 384
+    sc = RS.random_scene(4, float(w), float(h), n=30, clips=True, blur=False)
+    lst = next(iter(sc.layers.values()))
+    ctx = HipContext(record_only=True)
+    ctx.scene_retain(sc, w, h)
+    want = ctx.record_digest()
+    assert want == _fresh_digest(sc, w, h) and ctx.scene_stats() == (len(lst.rootIds), 0)
+    other = RS.random_scene(9, float(w), float(h), n=12, clips=False, blur=False)
+    cs = other.to_c()
+    layer = cs.struct.layers[0]
+    roots = C.cast(layer.root_ids, C.POINTER(C.c_int32))
+    for bad in (layer.n_nodes, -1):
+        keep, roots[layer.n_roots - 1] = roots[layer.n_roots - 1], bad  # the LAST root of the last layer: found after everything else
+        assert ctx.L.fdh_scene_retain(ctx.h, cs.byref(), float(w), float(h), 1, _F4(1.0, 1.0, 1.0, 1.0)) == -1
+        assert b"root index out of range" in ctx.L.fdh_last_error()
+        roots[layer.n_roots - 1] = keep
+        ctx.scene_render()
+        assert ctx.record_digest() == want
+        assert ctx.scene_stats() == (0, len(lst.rootIds))  # every root is cacheable (no blur node): every one was reused
+    ctx.close()
+
+
 @pytest.mark.gpu
 def test_retained_scene_pixels_equal_full_render():
     """GPU: after each edit the retained context's frame equals a full fdh_render_frame of the edited tree, bit for bit, and
