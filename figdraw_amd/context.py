@@ -348,13 +348,14 @@ class HipContext:
         self._ck(self.L.fdh_put_image(self.h, int(key), rgba.shape[1], rgba.shape[0], rgba.ctypes.data, out))
         return tuple(out)
 
-    def put_glyph_outline(self, key, segs: np.ndarray, w: int, h: int, lcd_filter: bool = False, mtsdf: bool = False, sdf_range: int = 0, correct: bool = False):
+    def put_glyph_outline(self, key, segs: np.ndarray, w: int, h: int, lcd_filter: bool = False, mtsdf: bool = False, sdf_range: int = 0, correct: bool = False, overlap: bool = False):
         """a glyph outline (n x 6: x0, y0, cx, cy, x1, y1; cx = NaN for a line) into the atlas, made on the device: coverage, or with
         mtsdf=True a multi-channel + true signed distance field of `sdf_range` texels (0: 4) for draw_msdf (FDH_GLYPH_MTSDF); correct=True
-        adds the correction pass (FDH_GLYPH_MTSDF_CORRECT, with mtsdf only)"""
+        adds the correction pass (FDH_GLYPH_MTSDF_CORRECT, with mtsdf only); overlap=True combines contours that overlap as non-zero winding
+        fills them (FDH_GLYPH_MTSDF_OVERLAP, with mtsdf only)"""
         segs = np.ascontiguousarray(segs, dtype=np.float32).reshape(-1, 6)
         out = (C.c_int * 4)()
-        flags = (1 if lcd_filter else 0) | (4 if mtsdf else 0) | (8 if correct else 0) | (int(sdf_range) << 8)
+        flags = (1 if lcd_filter else 0) | (4 if mtsdf else 0) | (8 if correct else 0) | (32 if overlap else 0) | (int(sdf_range) << 8)
         self._ck(self.L.fdh_put_glyph_outline(self.h, int(key), int(w), int(h), segs.ctypes.data, len(segs), flags, out))
         return tuple(out)
 

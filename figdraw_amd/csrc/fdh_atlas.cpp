@@ -208,13 +208,14 @@ static int flatten_count(const float* q) {
 void Atlas::put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) {
   if (w <= 0 || h <= 0 || w > 4096 || h > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_outline: image size must be in 1..4096");
   if (n < 0 || (n > 0 && !segs)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: bad outline");
-  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT | FDH_GLYPH_MTSDF | FDH_GLYPH_MTSDF_CORRECT | 0xFF00u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: unknown flag");
+  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT | FDH_GLYPH_MTSDF | FDH_GLYPH_MTSDF_CORRECT | FDH_GLYPH_MTSDF_OVERLAP | 0xFF00u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: unknown flag");
   const uint32_t sdf_range = (flags >> 8) & 255u;
   if (sdf_range && (!(flags & FDH_GLYPH_MTSDF) || sdf_range > 64u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance range needs FDH_GLYPH_MTSDF and is at most 64");
   if ((flags & FDH_GLYPH_MTSDF_CORRECT) && !(flags & FDH_GLYPH_MTSDF)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: FDH_GLYPH_MTSDF_CORRECT needs FDH_GLYPH_MTSDF");
+  if ((flags & FDH_GLYPH_MTSDF_OVERLAP) && !(flags & FDH_GLYPH_MTSDF)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: FDH_GLYPH_MTSDF_OVERLAP needs FDH_GLYPH_MTSDF");
   if (flags & FDH_GLYPH_MTSDF) {
     if (flags & (FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field takes no LCD filter");
-    put_glyph_mtsdf(s, key, w, h, segs, n, sdf_range ? (float)sdf_range : 4.0f, (flags & FDH_GLYPH_MTSDF_CORRECT) != 0, out_rect);
+    put_glyph_mtsdf(s, key, w, h, segs, n, sdf_range ? (float)sdf_range : 4.0f, (flags & FDH_GLYPH_MTSDF_CORRECT) != 0, (flags & FDH_GLYPH_MTSDF_OVERLAP) != 0, out_rect);
     return;
   }
   std::vector<float> lines;
@@ -249,7 +250,8 @@ void Atlas::put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const fl
 // orientation and the coloured edges (fdh_msdf_host.h), the device the texels (k_msdf_generate): one copy, one launch, then the level
 // chain every glyph image takes.  Nothing is premultiplied and nothing filtered: the four bytes of a texel are four distances.
 // `correct` (FDH_GLYPH_MTSDF_CORRECT, step 5): one more launch on the same stream, k_msdf_correct from one glyph buffer into the other.
-void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, float range, bool correct, int out_rect[4]) {
+// `overlap` (FDH_GLYPH_MTSDF_OVERLAP, step 6): the same records and the same launches, by the kernels that combine the contours.
+void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, float range, bool correct, bool overlap, int out_rect[4]) {
   if (n > msdf::kMaxSegments) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field takes at most 65535 segments");
   msdf::Shape shape;
   if (!msdf::build_shape(segs, n, &shape)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: a distance field needs closed contours");
@@ -266,9 +268,9 @@ void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const floa
   const int x = e.x, y = e.y;
   if (!rec.empty()) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, s));
   uint32_t *field = glyph_a_.ptr, *spare = glyph_b_.ptr;
-  launch_msdf_generate(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, field);
+  (overlap ? launch_msdf_generate_union : launch_msdf_generate)(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, field);
   if (correct) {
-    launch_msdf_correct(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, field, spare);
+    (overlap ? launch_msdf_correct_union : launch_msdf_correct)(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, field, spare);
     std::swap(field, spare);
   }
   // The level chain (updateSubImage's, textures.nim:106-119) stores nothing of an image 1 texel wide or high, not even level 0.  A field is

@@ -64,7 +64,7 @@ class Atlas {
   void upload_rect(int level, int x, int y, int w, int h, const uint8_t* rgba);
   void put_levels(int x, int y, int w, int h, const uint8_t* rgba);
   void glyph_to_atlas(hipStream_t s, uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags);
-  void put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, float range, bool correct, int out_rect[4]);
+  void put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, float range, bool correct, bool overlap, int out_rect[4]);
 
   bool device_ = false;
   int size_ = 0, initial_size_ = 0, margin_ = 4, n_levels_ = 0;

@@ -133,6 +133,10 @@ void launch_msdf_generate(hipStream_t s, const float* edges, int n_edges, int w,
 // step 5 of the same specification, the correction pass of FDH_GLYPH_MTSDF_CORRECT (k_msdf_correct): the generated image `in` -> `out` (another
 // buffer: every decision reads `in`), same edge records; a texel convicted of carrying a false median between itself and a neighbour gets R = G = B = median
 void launch_msdf_correct(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out);
+// step 6, FDH_GLYPH_MTSDF_OVERLAP: the two launches above with the contours combined (k_msdf_generate_union, k_msdf_correct_union); the
+// records are the same, slot 15 of a contour's last one says where it ends and whether it is filled (+1) or a hole (-1)
+void launch_msdf_generate_union(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, uint32_t* out);
+void launch_msdf_correct_union(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out);
 // The frame upload (k_upload_frame): a table of runs, each `bytes` of pinned host memory (its device view) going to byte offset
 // dst_off of the frame block.  kind 0: 16-byte units; 1: BinRecs -- copied in 8-byte units, and the lane that carries a record's
 // pixel bounds also writes the draw's 4-byte bin box; 2: DrawRecs -- 16-byte units, and the `ext` of every F_GENERAL record gets

@@ -1,8 +1,8 @@
 // fdh_msdf_host.h -- the host half of distance-field generation (fdh_put_glyph_outline with FDH_GLYPH_MTSDF; the specification is the
-// comment at that flag in include/figdraw_hip.h, steps 1 to 3): an outline becomes contours, an orientation, coloured edges, and the
-// record k_msdf_generate reads per edge.  Plain C++, no HIP: tests/msdf_emu compiles it as it stands.  All decisions (corners, the
-// orientation, the split points) are taken in double on the float32 coordinates the caller passed, so that a second implementation in
-// double reproduces them exactly.
+// comment at that flag in include/figdraw_hip.h, steps 1 to 3, and of step 6 which contours are filled): an outline becomes contours, an
+// orientation, coloured edges, and the record k_msdf_generate reads per edge.  Plain C++, no HIP: tests/msdf_emu compiles it as it
+// stands.  All decisions (corners, the orientation, the split points) are taken in double on the float32 coordinates the caller
+// passed, so that a second implementation in double reproduces them exactly.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -15,7 +15,9 @@ namespace msdf {
 //   0..5   P0, P1, P2 (a line: P1 = P0)
 //   6      the colour mask as a number (R = 1, G = 2, B = 4)      7  kind: 0 line, 1 quadratic
 //   8..9   a = P1 - P0 (a line: e = P2 - P0)                      10..11  b = P0 - 2 P1 + P2 (a line: 0)
-//   12     1 / |b|^2 (a line: 1 / |e|^2)     13  kx = (a . b) / |b|^2     14  2 |a|^2     15  0
+//   12     1 / |b|^2 (a line: 1 / |e|^2)     13  kx = (a . b) / |b|^2     14  2 |a|^2
+//   15     0 inside a contour; on a contour's last edge +1 when the contour is filled, -1 when it is a hole (step 6 of the
+//          specification: FDH_GLYPH_MTSDF_OVERLAP; k_msdf_generate and k_msdf_correct do not read it)
 //   16..19 the unit tangents at t = 0 and at t = 1
 //   20..23 the box of the control points: x0, y0, x1, y1
 // 8..14 are what the cubic of the nearest point owes to the curve alone (sd_bezierN in fdh_device.h computes the same per draw), in
@@ -106,15 +108,17 @@ inline void colour_contour(std::vector<Edge>& c) {
 struct Shape {
   std::vector<Edge> edges;   // every contour's edges, contour after contour
   std::vector<int> contour;  // the contour of each edge
+  std::vector<bool> filled;  // per contour, step 6: orient * (its own area) >= 0; otherwise the contour is a hole
   double orient = 1.0;       // the sign of the total area
 };
 
 // steps 1 to 3.  false: an open contour
 inline bool build_shape(const float* segs, int n, Shape* out) {
-  out->edges.clear(); out->contour.clear(); out->orient = 1.0;
+  out->edges.clear(); out->contour.clear(); out->filled.clear(); out->orient = 1.0;
   std::vector<Edge> cur;
+  std::vector<double> areas;  // per contour: step 2's sum over its own edges
   int n_contours = 0;
-  double area = 0.0;
+  double area = 0.0, own = 0.0;
   for (int i = 0; i < n; i++) {
     const float* q = segs + 6 * (size_t)i;
     Edge e{};
@@ -132,17 +136,21 @@ inline bool build_shape(const float* segs, int n, Shape* out) {
     if (!cur.empty() && (cur.back().p[4] != e.p[0] || cur.back().p[5] != e.p[1])) return false;
     cur.push_back(e);
     const double x0 = e.p[0], y0 = e.p[1], x1 = e.p[4], y1 = e.p[5];
-    area += 0.5 * (x0 * y1 - x1 * y0);
-    if (!e.line) area += (((double)e.p[2] - x0) * (y1 - y0) - ((double)e.p[3] - y0) * (x1 - x0)) / 3.0;
+    const double chord = 0.5 * (x0 * y1 - x1 * y0), bow = e.line ? 0.0 : (((double)e.p[2] - x0) * (y1 - y0) - ((double)e.p[3] - y0) * (x1 - x0)) / 3.0;
+    area += chord; own += chord;
+    if (!e.line) { area += bow; own += bow; }
     if (e.p[4] == cur.front().p[0] && e.p[5] == cur.front().p[1]) {
       colour_contour(cur);
       for (const Edge& c : cur) { out->edges.push_back(c); out->contour.push_back(n_contours); }
+      areas.push_back(own);
+      own = 0.0;
       n_contours++;
       cur.clear();
     }
   }
   if (!cur.empty()) return false;
   out->orient = area >= 0.0 ? 1.0 : -1.0;
+  for (double a : areas) out->filled.push_back(out->orient * a >= 0.0);
   return true;
 }
 
@@ -172,6 +180,7 @@ inline void edge_records(const Shape& s, std::vector<float>* rec) {
     end_tangents(e, t0, t1);
     unit(t0[0], t0[1], &ux, &uy); r[16] = (float)ux; r[17] = (float)uy;
     unit(t1[0], t1[1], &ux, &uy); r[18] = (float)ux; r[19] = (float)uy;
+    if (i + 1 == s.edges.size() || s.contour[i + 1] != s.contour[i]) r[15] = s.filled[(size_t)s.contour[i]] ? 1.0f : -1.0f;
     r[20] = std::fmin(e.p[0], std::fmin(e.p[2], e.p[4])); r[21] = std::fmin(e.p[1], std::fmin(e.p[3], e.p[5]));
     r[22] = std::fmax(e.p[0], std::fmax(e.p[2], e.p[4])); r[23] = std::fmax(e.p[1], std::fmax(e.p[3], e.p[5]));
   }

@@ -6,6 +6,9 @@
 // pseudo-distances are made once, after the loop, from the winners.
 // k_msdf_correct is step 5, the correction pass behind FDH_GLYPH_MTSDF_CORRECT: the same mapping over the quantised image; integers find the
 // few places where interpolation between two texels carries the median across 0.5, and only a wave that holds one walks the edges again.
+// k_msdf_generate_union and k_msdf_correct_union are step 6, FDH_GLYPH_MTSDF_OVERLAP: the same walk, taken contour by contour -- a contour's
+// last record says so and whether it is filled or a hole --, each contour's result ranked into two lists of four, the texel's contour
+// selected after the loop.
 #include "fdh_device.h"
 #include "fdh_msdf_host.h"
 
@@ -289,6 +292,216 @@ __global__ __launch_bounds__(64) void k_msdf_correct(const float* __restrict__ e
 void launch_msdf_correct(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out) {
   if (w <= 0 || h <= 0) return;
   FDH_LAUNCH(k_msdf_correct, dim3((w + 7) / 8, (h + 7) / 8), dim3(64), 0, s, edges, n_edges, w, h, orient, range / 255.0f, in, out);
+}
+
+// ------------------------------------------------------------------ step 6 of the specification: overlapping contours
+// Two ranked lists of at most four contours: the filled ones by A descending, the holes by A ascending; ties keep contour order (a strict
+// compare finds the newcomer's place, so it never passes an equal earlier contour; what it displaces moves down without another compare, so
+// no displaced entry passes its equal either).  T: what travels with A -- the texel's encoded word in the generator;
+// the correction ranks A alone.  An absent filled entry is -3e38 (it never wins: an outline with edges has a filled contour), an absent
+// hole +3e38 (min leaves the filled one).  All in registers: every index below is a constant after unrolling.
+template <typename T> struct MsdfRank {
+  float fa[4], ga[4];
+  T fw[4], gw[4];
+  __device__ __forceinline__ void clear(T none) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) { fa[k] = -3.0e38f; ga[k] = 3.0e38f; fw[k] = none; gw[k] = none; }
+  }
+  // cls: slot 15 of the contour's last record (wave-uniform); negative: a hole
+  __device__ __forceinline__ void insert(float cls, float a, T word) {
+    if (!(cls < 0.0f)) {
+      bool up = false;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {  // the newcomer takes the first place whose holder it beats; from there on every entry moves down one
+        up = up || a > fa[k];
+        const float ta = fa[k]; const T tw = fw[k];
+        fa[k] = up ? a : ta; fw[k] = up ? word : tw;
+        a = up ? ta : a; word = up ? tw : word;
+      }
+    } else {
+      bool up = false;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        up = up || a < ga[k];
+        const float ta = ga[k]; const T tw = gw[k];
+        ga[k] = up ? a : ta; gw[k] = up ? word : tw;
+        a = up ? ta : a; word = up ? tw : word;
+      }
+    }
+  }
+  // the term f_k = min(a(F_k), a(G_k)) that is largest, ties to the lowest k -> its value, and the word of the contour it names
+  __device__ __forceinline__ float select(T& word) const {
+    float best = __builtin_fminf(fa[0], ga[0]);
+    word = ga[0] < fa[0] ? gw[0] : fw[0];
+#pragma unroll
+    for (int k = 1; k < 4; k++) {
+      const float f = __builtin_fminf(fa[k], ga[k]);
+      const T wk = ga[k] < fa[k] ? gw[k] : fw[k];
+      const bool up = f > best;
+      word = up ? wk : word; best = up ? f : best;
+    }
+    return best;
+  }
+};
+
+// k_msdf_generate's mapping and arithmetic, contour by contour: [first, last] is one contour (slot 15 of record `last` is not 0).  The cull
+// is k_msdf_generate's with its bound taken among this contour's edges alone -- every contour carries every channel after step 3 -- so
+// within a contour no edge that could win is skipped.  At the contour's end the tail that k_msdf_generate runs once makes the contour's
+// four distances and their word; A and the word go into the ranking.  The walk over the records is bounded by n_edges whatever slot 15 holds.
+__global__ __launch_bounds__(64) void k_msdf_generate_union(const float* __restrict__ edges, int n_edges, int w, int h, float orient, float inv_range,
+                                                            uint32_t* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int tx0 = blockIdx.x * 8, ty0 = blockIdx.y * 8;
+  const int x = tx0 + (threadIdx.x & 7), y = ty0 + (threadIdx.x >> 3);
+  if (x >= w || y >= h) return;
+  const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+#if !FDH_MSDF_NO_CULL
+  constexpr float kHalfDiag = 4.9497475f + 1.0e-3f;
+  const float mx = (float)tx0 + 4.0f, my = (float)ty0 + 4.0f;
+#endif
+  MsdfRank<uint32_t> rank;
+  rank.clear(0u);
+  int first = 0;
+  while (first < n_edges) {  // wave-uniform
+    int last = first;
+#if !FDH_MSDF_NO_CULL
+    float ub[3] = {3.0e38f, 3.0e38f, 3.0e38f};
+    for (;; last++) {  // the bound pass finds the contour's end as it goes
+      const float* __restrict__ r = edges + (size_t)last * msdf::kEdgeFloats;
+      const float ux = r[0] - mx, uy = r[1] - my, vx = r[4] - mx, vy = r[5] - my;
+      const float u = fsqrt(__builtin_fminf(ux * ux + uy * uy, vx * vx + vy * vy)) + kHalfDiag;
+      const int mask = (int)r[6];
+#pragma unroll
+      for (int c = 0; c < 3; c++) if ((mask >> c) & 1) ub[c] = __builtin_fminf(ub[c], u);
+      if (r[15] != 0.0f || last + 1 >= n_edges) break;
+    }
+#else
+    while (last + 1 < n_edges && edges[(size_t)last * msdf::kEdgeFloats + 15] == 0.0f) last++;
+#endif
+    float bd2[4], bo[4], bt[4];
+    int be[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) { bd2[c] = 3.0e38f; bo[c] = -1.0f; bt[c] = 0.0f; be[c] = -1; }
+    for (int i = first; i <= last; i++) {
+      const float* __restrict__ r = edges + (size_t)i * msdf::kEdgeFloats;
+      const int mask = (int)r[6];
+#if !FDH_MSDF_NO_CULL
+      {
+        const float gx = __builtin_fmaxf(__builtin_fmaxf(r[20] - mx, mx - r[22]), 0.0f), gy = __builtin_fmaxf(__builtin_fmaxf(r[21] - my, my - r[23]), 0.0f);
+        const float lb = fsqrt(gx * gx + gy * gy) - kHalfDiag;
+        float um = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; c++) if ((mask >> c) & 1) um = __builtin_fmaxf(um, ub[c]);
+        if (lb > um * 1.0001f) continue;  // wave-uniform
+      }
+#endif
+      float t, d2, ortho, side;
+      msdf_edge(r, px, py, t, d2, ortho, side);
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        if (c < 3 && !((mask >> c) & 1)) continue;  // wave-uniform
+        const bool better = d2 < bd2[c] || (d2 == bd2[c] && ortho > bo[c]);
+        bd2[c] = better ? d2 : bd2[c]; bo[c] = better ? ortho : bo[c]; bt[c] = better ? t : bt[c]; be[c] = better ? i : be[c];
+      }
+    }
+    uint32_t word = 0;
+    float a = -3.0e38f;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      float d = -3.0e38f;
+      if (be[c] >= 0) {
+        const float* __restrict__ r = edges + (size_t)be[c] * msdf::kEdgeFloats;
+        float Ex, Ey, Tx, Ty;
+        msdf_at(r, bt[c], px, py, Ex, Ey, Tx, Ty);
+        const float cr = Ty * Ex - Tx * Ey;
+        d = fsqrt(bd2[c]);
+        d = cr >= 0.0f ? d : -d;
+        if (c < 3 && (bt[c] <= 0.0f || bt[c] >= 1.0f)) {
+          const float ux = bt[c] <= 0.0f ? r[16] : r[18], uy = bt[c] <= 0.0f ? r[17] : r[19];
+          const float pd = uy * Ex - ux * Ey;
+          d = __builtin_fabsf(pd) <= __builtin_fabsf(d) ? pd : d;
+        }
+        d *= orient;
+      }
+      if (c == 3) a = d;
+      const float v = clamp01(0.5f + d * inv_range);
+      word |= (uint32_t)__builtin_floorf(255.0f * v + 0.5f) << (8 * c);
+    }
+    rank.insert(edges[(size_t)last * msdf::kEdgeFloats + 15], a, word);
+    first = last + 1;
+  }
+  uint32_t word;
+  rank.select(word);
+  out[(size_t)y * w + x] = word;
+}
+
+void launch_msdf_generate_union(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, uint32_t* out) {
+  if (w <= 0 || h <= 0) return;
+  FDH_LAUNCH(k_msdf_generate_union, dim3((w + 7) / 8, (h + 7) / 8), dim3(64), 0, s, edges, n_edges, w, h, orient, 1.0f / range, out);
+}
+
+// k_msdf_correct with step 6's verdict distance: phases as there, but phase 2's walk keeps (d2, ortho, side) per contour, makes the contour's
+// true distance at its end and ranks that scalar; d(q) is the largest term.
+__global__ __launch_bounds__(64) void k_msdf_correct_union(const float* __restrict__ edges, int n_edges, int w, int h, float orient, float step,
+                                                           const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int x = blockIdx.x * 8 + (threadIdx.x & 7), y = blockIdx.y * 8 + (threadIdx.x >> 3);
+  const bool live = x < w && y < h;
+  const int cx = x < w ? x : w - 1, cy = y < h ? y : h - 1;  // what is loaded lies inside the image whatever the lane
+  const int xl = cx > 0 ? cx - 1 : 0, xr = cx + 1 < w ? cx + 1 : w - 1, yu = cy > 0 ? cy - 1 : 0, yd = cy + 1 < h ? cy + 1 : h - 1;
+  const uint32_t c = in[(size_t)cy * w + cx];
+  const uint32_t nb[4] = {in[(size_t)cy * w + xl], in[(size_t)cy * w + xr], in[(size_t)yu * w + cx], in[(size_t)yd * w + cx]};
+  const bool has[4] = {live && x > 0, live && x + 1 < w, live && y > 0, live && y + 1 < h};
+  uint32_t todo = 0;
+#pragma unroll
+  for (int p = 0; p < 4; p++) {
+#pragma unroll
+    for (int cp = 0; cp < 3; cp++) {
+      int N, D;
+      bool inside;
+      const bool cand = msdf_candidate((p & 1) ? c : nb[p], (p & 1) ? nb[p] : c, cp, N, D, inside);
+      todo |= (uint32_t)(cand & has[p] & (n_edges > 0)) << (3 * p + cp);
+    }
+  }
+  const int depth = msdf_depth(c);
+  bool mark = false;
+  while (FDH_MSDF_ANY(todo != 0)) {  // wave-uniform
+    const int bit = todo ? __builtin_ctz(todo) : 0, p = bit / 3, cp = bit - 3 * p;
+    const uint32_t other = p == 0 ? nb[0] : (p == 1 ? nb[1] : (p == 2 ? nb[2] : nb[3]));
+    int N, D;
+    bool inside;
+    const bool cand = msdf_candidate((p & 1) ? c : other, (p & 1) ? other : c, cp, N, D, inside) & (todo != 0);
+    const float t = cand ? (float)N / (float)D : 0.0f;
+    const float ax = (float)(x - (p == 0 ? 1 : 0)) + 0.5f, ay = (float)(y - (p == 2 ? 1 : 0)) + 0.5f;
+    const float qx = p < 2 ? ax + t : ax, qy = p < 2 ? ay : ay + t;
+    MsdfRank<uint32_t> rank;  // (the words are never read here: the compiler drops them)
+    rank.clear(0u);
+    float bd2 = 3.0e38f, bo = -1.0f, bs = 0.0f;
+    for (int i = 0; i < n_edges; i++) {
+      const float* __restrict__ r = edges + (size_t)i * msdf::kEdgeFloats;
+      float te, d2, ortho, side;
+      msdf_edge(r, qx, qy, te, d2, ortho, side);
+      const bool better = d2 < bd2 || (d2 == bd2 && ortho > bo);
+      bd2 = better ? d2 : bd2; bo = better ? ortho : bo; bs = better ? side : bs;
+      if (r[15] != 0.0f || i + 1 == n_edges) {  // wave-uniform: the contour ends here
+        const float dc = fsqrt(bd2);
+        rank.insert(r[15], (bs >= 0.0f ? dc : -dc) * orient, 0u);
+        bd2 = 3.0e38f; bo = -1.0f; bs = 0.0f;
+      }
+    }
+    uint32_t none;
+    const float d = rank.select(none);
+    // a point within one quantisation step of the outline convicts nobody
+    const bool artefact = cand && (inside ? d < -step : d > step);
+    mark = mark | (artefact & (depth >= msdf_depth(other)));
+    todo &= todo - 1u;
+  }
+  if (live) out[(size_t)y * w + x] = mark ? ((c & 0xFF000000u) | (uint32_t)msdf_median(c) * 0x010101u) : c;
+}
+
+void launch_msdf_correct_union(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out) {
+  if (w <= 0 || h <= 0) return;
+  FDH_LAUNCH(k_msdf_correct_union, dim3((w + 7) / 8, (h + 7) / 8), dim3(64), 0, s, edges, n_edges, w, h, orient, range / 255.0f, in, out);
 }
 
 }  // namespace fdh

@@ -249,7 +249,8 @@ enum { FDH_GLYPH_LCD_FILTER = 1,
        FDH_GLYPH_LCD_CONTEXT = 2, /* filter iff fdh_set_text_lcd_filtering is on: what renderText's generateGlyph call does with
                                      ctx.textLcdFilteringEnabled() (figrender.nim:420) */
        FDH_GLYPH_MTSDF = 4,           /* fdh_put_glyph_outline: store a multi-channel + true signed distance field, not coverage */
-       FDH_GLYPH_MTSDF_CORRECT = 8    /* with FDH_GLYPH_MTSDF only: run the correction pass over the field (step 5 below) */ };
+       FDH_GLYPH_MTSDF_CORRECT = 8,   /* with FDH_GLYPH_MTSDF only: run the correction pass over the field (step 5 below) */
+       FDH_GLYPH_MTSDF_OVERLAP = 32   /* with FDH_GLYPH_MTSDF only: contours that overlap are combined as non-zero winding fills them (step 6 below) */ };
 #define FDH_GLYPH_SDF_RANGE(r) ((uint32_t)(r) << 8)   /* bits 8..15: the distance range in texels, 1..64; 0 = 4 */
 FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height, const uint8_t* rgba8, uint32_t flags, int out_rect[4]);
 /* A glyph OUTLINE rasterised on the device into the atlas -- generateGlyph's job (common/fontglyphs.nim:61-106; the reference calls
@@ -268,7 +269,11 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  * at). FDH_GLYPH_MTSDF with an LCD flag, a range without FDH_GLYPH_MTSDF or above 64, more than 65535 segments and an open contour are
  * FDH_ERR_INVALID; a record-only context packs the rectangle and makes no texels.  FDH_GLYPH_MTSDF_CORRECT adds step 5; it is valid only
  * together with FDH_GLYPH_MTSDF on this call (alone, with an LCD flag or on fdh_put_glyph_image: FDH_ERR_INVALID), and without it
- * nothing changes.
+ * nothing changes.  FDH_GLYPH_MTSDF_OVERLAP replaces step 4's choice among all edges by step 6's choice among contours, for outlines whose
+ * contours overlap (composite and variable-font glyphs: stem plus bowl, ring plus bar); the same rules hold for it -- valid only together
+ * with FDH_GLYPH_MTSDF, with or without FDH_GLYPH_MTSDF_CORRECT and a range; alone, with an LCD flag or on fdh_put_glyph_image:
+ * FDH_ERR_INVALID, refused before anything is packed; a record-only context packs the rectangle and makes no texels; without it nothing
+ * changes.
  * The construction is Chlumsky's multi-channel distance field (V. Chlumsky, "Shape Decomposition for Multi-channel Distance Fields",
  * 2015; the "simple" edge colouring of his msdfgen), restated here; this comment is the specification, tests/msdf_ref.py implements it
  * in float64 and the device (figdraw_amd/csrc/fdh_msdf_host.h, k_msdf.hip) is held to that within 1 LSB.  All host decisions (steps 1 - 3)
@@ -283,8 +288,8 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  *    start, and the next edge starts a new contour.  A contour left open: FDH_ERR_INVALID.
  * 2. Orientation.  o = +1 if the total signed area is >= 0, else -1: the sum over all edges of (x0 y1 - x1 y0) / 2 plus, for a
  *    quadratic, cross(P1 - P0, P2 - P0) / 3, with cross(u, v) = ux vy - uy vx.  Every signed distance is multiplied by o, so the field
- *    is positive inside whichever way the font winds, provided holes wind against their outer contour.  Overlapping contours are out
- *    of scope (msdfgen without its overlap mode).
+ *    is positive inside whichever way the font winds, provided holes wind against their outer contour.  Contours that overlap need
+ *    step 6 (FDH_GLYPH_MTSDF_OVERLAP): step 4 alone takes the nearest edge of the whole outline and turns negative inside an overlap.
  * 3. Colours (R = 1, G = 2, B = 4; magenta = R|B, yellow = R|G, cyan = G|B, white = all), per contour of m edges e_0 .. e_(m-1).  The
  *    tangent direction of an edge at its start is P1 - P0, at its end P2 - P1, and P2 - P0 for a line or where that vector is zero.
  *    Vertex i (where e_(i-1) ends and e_i starts, cyclically) is a corner when the unit tangents in and out have dot <= 0 or
@@ -322,10 +327,32 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  *    So m and A of every texel are unchanged, a marked texel interpolates its median linearly towards every neighbour, a field whose
  *    channels all agree is unchanged, and a field 1 texel wide has no horizontal pairs.  tests/msdf_correct_ref.py implements this step in
  *    float64; an implementation in float32 can differ from it only where |d(q)| is within rounding of R / 255.
+ * 6. Overlapping contours, with FDH_GLYPH_MTSDF_OVERLAP only; it takes the place of step 4's choice among all edges.  (Not msdfgen's
+ *    OverlappingContourCombiner, which depends on contour order and fails where a filled contour crosses a hole; this rule is
+ *    independent of the order in which the contours are passed, up to exact ties.)
+ *    Contours and winding: the contours are those of step 1, in order.  area_c is step 2's sum taken over the edges of contour c alone, in
+ *    their order, in double.  Contour c is filled when o * area_c >= 0 and a hole otherwise; o being the sign of the total, at least one
+ *    contour is filled.
+ *    Per-contour field: d_c(p) is step 4 evaluated over the edges of contour c only -- four values, each multiplied by o: pseudo-distances
+ *    for R, G and B, the true distance for A, the tie rules step 4's.  (After step 3 every contour carries every channel.)  a_c is its A,
+ *    before the encoding.  A hole's values are positive outside the hole.
+ *    Ranking: F_1, F_2, ... are the filled contours by a_c descending, G_1, G_2, ... the holes by a_c ascending; of two contours with equal
+ *    a_c the one earlier in contour order comes first.
+ *    Terms: for k = 1 .. 4, f_k = min(a(F_k), a(G_k)); where G_k is absent f_k = a(F_k); where F_k is absent there is no term k.
+ *    Selection: the k with the largest f_k, of equal ones the lowest k.  The texel's contour is G_k if a(G_k) < a(F_k), else F_k.
+ *    Output: all four channels of the texel are that contour's d_c, encoded as in step 4.  An outline without edges gives the all-zero
+ *    image, as before; an outline of one contour gives exactly step 4's image.
+ *    Meaning: a texel is inside when more filled contours than holes contain it (the k-th deepest filled contour around it is answered by
+ *    the k-th deepest hole); the magnitude is the lower bound max_k min(...) that the union and difference of the contours' distances give,
+ *    exact near every edge that is visible in the result.  The limit of 4 terms is exact unless four holes contain the same texel.
+ *    With FDH_GLYPH_MTSDF_CORRECT as well, step 5 is unchanged but for its verdict distance: d(q) is this step's A at q, max_k f_k, from
+ *    the contours' true distances at q (A's rule per contour, times o).
+ *    Not covered: a hole that reaches outside every filled contour (non-zero winding fills that part, winding -1, and this rule does
+ *    not), and a single contour that crosses itself (it has one area and one field: this step changes nothing about it).
  * Out of scope: the rest of msdfgen's error correction -- artefacts that need all four texels of a bilinear cell to show (the median
  *    inverting on a diagonal while no pair along x or y inverts), and corner protection (step 5 does not look for corners: near one, where
- *    the channels must disagree, it relies on the verdict alone) --, overlapping contours, cubic segments (the outline format has
- *    none), a batched multi-glyph call (it would be a new entry point). */
+ *    the channels must disagree, it relies on the verdict alone) --, a hole outside every filled contour and a contour that crosses
+ *    itself (see step 6), cubic segments (the outline format has none), a batched multi-glyph call (it would be a new entry point). */
 FDH_API int fdh_put_glyph_outline(FdhContext*, int64_t key, int width, int height, const float* segs, int n_segs, uint32_t flags, int out_rect[4]);
 /* putFlippy (glcontext.nim:610-620): `bytes` is a whole .flippy file (common/formatflippy.nim:77-149: "flip", version 1, then per
  * mip "mip!", w, h, zlen, raw-snappy straight RGBA8); every stored level is uploaded as is at (x >> l, y >> l). */

@@ -1,19 +1,21 @@
 #!/usr/bin/env python3
-"""What a distance-field put costs (fdh_put_glyph_outline with FDH_GLYPH_MTSDF, k_msdf_generate, and with FDH_GLYPH_MTSDF_CORRECT
-k_msdf_correct), on an MI355X -> profiles/msdf.txt.
+"""What a distance-field put costs (fdh_put_glyph_outline with FDH_GLYPH_MTSDF, k_msdf_generate, with FDH_GLYPH_MTSDF_CORRECT
+k_msdf_correct, and with FDH_GLYPH_MTSDF_OVERLAP k_msdf_generate_union), on an MI355X -> profiles/msdf.txt.
 
   msdf_bench.py --all OUT [--nocull-lib LIB] [--parent-lib LIB] [--passes N]
                                                every step as a child process under its own time limit, in turn, nothing started after a
-                                               failure; writes the report: per case the call without and with the correction pass, then
-                                               the other libraries without it, N times over in that order (libraries alternate).
+                                               failure; writes the report: per case the call without and with the correction pass, with
+                                               the overlap flag, then the other libraries without either, N times over in that order
+                                               (libraries alternate).
                                                --nocull-lib: the library built with -DFDH_MSDF_NO_CULL=1
                                                (make -C figdraw_amd/csrc variant NAME=msdf_nocull DEFS=-DFDH_MSDF_NO_CULL=1);
                                                --parent-lib: the parent commit's library, for "the flag-off call is unchanged"
-  msdf_bench.py --time CASE [--correct]        the whole call on the host clock, profiler off: 200 timed calls after 20; one JSON line
-  msdf_bench.py --trace CASE [--correct] [--calls N]   N calls (run it under rocprofv3 --kernel-trace --stats -f csv); one JSON line
+  msdf_bench.py --time CASE [--correct] [--overlap]    the whole call on the host clock, profiler off: 200 timed calls after 20; one JSON line
+  msdf_bench.py --trace CASE [--correct] [--overlap] [--calls N]   N calls (run it under rocprofv3 --kernel-trace --stats -f csv); one JSON line
 
 Cases: small = one glyph outline ('g' of the fixture, scaled to a 32 x 32 field, range 4); large = six glyph outlines scaled and laid side by
-side in a 256 x 256 field (about 200 segments)."""
+side in a 256 x 256 field (about 200 segments); font = the 106 inputs of tests/msdf_cases.py, one put each (a "call" is all 106); many =
+16 383 copies of one square, as many contours, in a 16 x 16 field (40 timed calls after 5)."""
 import argparse
 import json
 import os
@@ -27,7 +29,26 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from damage_readback_bench import _stats, _step  # noqa: E402
 
-CASES = {"small": "32 x 32, one glyph", "large": "256 x 256, six glyphs side by side"}
+CASES = {"small": "32 x 32, one glyph", "large": "256 x 256, six glyphs side by side", "font": "the 106 font inputs, one put each",
+         "many": "16 x 16, 16383 squares"}
+ROUNDS = {"many": (40, 5)}  # (timed, warm-up) where 200 after 20 would take too long
+
+
+def outlines(case):
+    """-> [(segs float32 (n, 6), w, h, range)]: the puts of one call"""
+    import numpy as np
+
+    if case == "font":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import msdf_cases
+
+        return [(segs, w, h, R) for _, segs, w, h, R in msdf_cases.inputs()]
+    if case == "many":
+        a, b, c, d = (2.0, 2.0), (10.0, 2.0), (10.0, 9.0), (2.0, 9.0)
+        nan = float("nan")
+        square = np.array([[p[0], p[1], nan, nan, q[0], q[1]] for p, q in ((a, b), (b, c), (c, d), (d, a))], np.float32)
+        return [(np.tile(square, (16383, 1)), 16, 16, 4)]
+    return [outline(case) + (4,)]
 
 
 def outline(case):
@@ -51,6 +72,7 @@ def outline(case):
 
 
 CORRECT = {False: {}, True: {"correct": True}}  # (a library from before the flag is driven without the keyword's bit)
+OVERLAP = {False: {}, True: {"overlap": True}}
 
 
 def _context():
@@ -59,37 +81,44 @@ def _context():
     return HipContext(atlas_size=4096, device=0)
 
 
-def time_case(case, correct=False, timed=200, warm=20):
-    segs, w, h = outline(case)
+def time_case(case, correct=False, overlap=False):
+    puts = outlines(case)
+    timed, warm = ROUNDS.get(case, (200, 20))
     ctx = _context()
     us = []
     for k in range(warm + timed):
-        if k % 100 == 0:
+        if k % (100 // len(puts) or 1) == 0:
             ctx.reset_atlas()  # (the packer's search grows with what is packed; every call packs a new rectangle)
         t1 = time.perf_counter()
-        ctx.put_glyph_outline(1 + k, segs, w, h, mtsdf=True, sdf_range=4, **CORRECT[correct])
+        for i, (segs, w, h, R) in enumerate(puts):
+            ctx.put_glyph_outline(1 + k * len(puts) + i, segs, w, h, mtsdf=True, sdf_range=R, **CORRECT[correct], **OVERLAP[overlap])
         t2 = time.perf_counter()
         if k >= warm:
             us.append((t2 - t1) * 1e6)
     ctx.close()
-    print(json.dumps({"case": case, "correct": correct, "segments": len(segs), "calls": timed, "median_us": statistics.median(us), "p10_us": sorted(us)[len(us) // 10],
-                      "p90_us": sorted(us)[9 * len(us) // 10]}))
+    print(json.dumps({"case": case, "correct": correct, "overlap": overlap, "segments": sum(len(p[0]) for p in puts), "calls": timed, "median_us": statistics.median(us),
+                      "p10_us": sorted(us)[len(us) // 10], "p90_us": sorted(us)[9 * len(us) // 10]}))
 
 
-def trace_case(case, calls, correct=False):
-    segs, w, h = outline(case)
+def trace_case(case, calls, correct=False, overlap=False):
+    puts = outlines(case)
     ctx = _context()
     for k in range(calls):
-        ctx.put_glyph_outline(1 + k, segs, w, h, mtsdf=True, sdf_range=4, **CORRECT[correct])
+        if k % (100 // len(puts) or 1) == 0:
+            ctx.reset_atlas()
+        for i, (segs, w, h, R) in enumerate(puts):
+            ctx.put_glyph_outline(1 + k * len(puts) + i, segs, w, h, mtsdf=True, sdf_range=R, **CORRECT[correct], **OVERLAP[overlap])
     ctx.close()
-    print(json.dumps({"case": case, "correct": correct, "segments": len(segs), "calls": calls}))
+    print(json.dumps({"case": case, "correct": correct, "overlap": overlap, "segments": sum(len(p[0]) for p in puts), "calls": calls}))
 
 
 HEAD = """tools/msdf_bench.py -- a distance-field put (fdh_put_glyph_outline with FDH_GLYPH_MTSDF), MI355X.
 whole call = host clock around the call, profiler off, 200 timed calls after 20 (it packs, builds the edge records, copies them, launches
 k_msdf_generate, with FDH_GLYPH_MTSDF_CORRECT k_msdf_correct, and the level chain's blits and minifies, and synchronises); kernel =
 k_msdf_generate and k_msdf_correct alone from a rocprofv3 --kernel-trace --stats run of its own, 60 calls.  this / corrected: the product
-library without / with FDH_GLYPH_MTSDF_CORRECT; no cull: the -DFDH_MSDF_NO_CULL=1 build; parent: the parent commit's library.
+library without / with FDH_GLYPH_MTSDF_CORRECT; overlap: the product library with FDH_GLYPH_MTSDF_OVERLAP (k_msdf_generate_union in
+k_msdf_generate's place); no cull: the -DFDH_MSDF_NO_CULL=1 build; parent: the parent commit's library.  font: a call is 106 puts, a
+launch one of them; many: 40 timed calls after 5, 12 traced.
 
 Hypotheses, stated before the numbers (nothing had been timed when they were written):
   1. small (32 x 32, one glyph): the whole call is launch plus synchronise latency -- the kernel is a few microseconds of a call of
@@ -102,37 +131,43 @@ Hypotheses, stated before the numbers (nothing had been timed when they were wri
      the few tiles that hold a candidate (no culling there), a fraction of the generator's 50 us; on large, where most of the 1024 tiles
      leave after phase 1, it is the phase-2 rounds of the few tiles with candidates, each walking all 254 edges: a latency chain of one
      wave, tens of microseconds, beside the generator's 190.
+  5. the union generator does k_msdf_generate's work per edge and adds one tail and one ranking per contour: on the font set, 1 to 3
+     contours a glyph, a few per cent of the kernel and nothing that shows in the call; on many (16 383 contours of 4 edges) the tail
+     is a quarter of the work and the cull's bound is taken per contour: the kernel may cost up to twice the plain one.
 """
 
 
-def run_all(out_path, nocull_lib, trace_dir, parent_lib=None, passes=1):
+def run_all(out_path, nocull_lib, trace_dir, parent_lib=None, passes=1, cases=tuple(CASES)):
     me = [sys.executable, os.path.abspath(__file__)]
     lines = HEAD.splitlines() + [""]
-    libs = [("this", None, False), ("corrected", None, True)] + ([("no cull", os.path.abspath(nocull_lib), False)] if nocull_lib else [])
-    libs += [("parent", os.path.abspath(parent_lib), False)] if parent_lib else []
+    libs = [("this", None, False, False), ("corrected", None, True, False), ("overlap", None, False, True)]
+    libs += [("no cull", os.path.abspath(nocull_lib), False, False)] if nocull_lib else []
+    libs += [("parent", os.path.abspath(parent_lib), False, False)] if parent_lib else []
     ok = True
-    for case in CASES:
-        for turn, (tag, lib, correct) in enumerate(libs * passes):
+    for case in cases:
+        for turn, (tag, lib, correct, overlap) in enumerate(libs * passes):
             env = dict(os.environ)
             if lib:
                 env["FIGDRAW_HIP_LIB"] = lib
-            flag = ["--correct"] if correct else []
+            flag = (["--correct"] if correct else []) + (["--overlap"] if overlap else [])
+            n_calls = 12 if case == "many" else 60
             got = _step(me + ["--time", case] + flag, 300, env)
             if got is None:
                 ok = False
                 break
             r = json.loads([ln for ln in got.strip().splitlines() if ln.startswith("{")][-1])
             d = os.path.join(trace_dir, f"{case}_{tag.replace(' ', '')}_{turn}")
-            got = _step(["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "-o", "t", "--"] + me + ["--trace", case, "--calls", "60"] + flag, 300, env)
+            got = _step(["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "-o", "t", "--"] + me + ["--trace", case, "--calls", str(n_calls)] + flag, 300, env)
             if got is None:
                 ok = False
                 break
             kern = _stats(d, "*kernel_stats.csv")
-            calls, us, longest = kern.get("k_msdf_generate", (0, 0.0, 0.0))
+            gen = "k_msdf_generate_union" if overlap else "k_msdf_generate"
+            calls, us, longest = kern.get(gen, (0, 0.0, 0.0))
             ccalls, cus, clongest = kern.get("k_msdf_correct", (0, 0.0, 0.0))
-            others = ", ".join(f"{k} {v[1] / 60:.1f}" for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1]) if k not in ("k_msdf_generate", "k_msdf_correct"))
+            others = ", ".join(f"{k} {v[1] / n_calls:.1f}" for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1]) if k not in (gen, "k_msdf_correct"))
             lines.append(f"{case} ({CASES[case]}, {r['segments']} segments), {tag}: whole call median {r['median_us']:.1f} us (p10 {r['p10_us']:.1f}, p90 {r['p90_us']:.1f}); "
-                         f"k_msdf_generate {us / max(calls, 1):.2f} us per launch over {calls} launches, the longest {longest:.1f}"
+                         f"{gen} {us / max(calls, 1):.2f} us per launch over {calls} launches, the longest {longest:.1f}"
                          + (f"; k_msdf_correct {cus / ccalls:.2f} us per launch over {ccalls} launches, the longest {clongest:.1f}" if ccalls else ""))
             lines.append(f"    other kernels of the call, us per call: {others}")
             print(lines[-2], flush=True)
@@ -151,16 +186,21 @@ if __name__ == "__main__":
     ap.add_argument("--parent-lib")
     ap.add_argument("--passes", type=int, default=1)
     ap.add_argument("--correct", action="store_true", help="with --time / --trace: put with FDH_GLYPH_MTSDF_CORRECT")
+    ap.add_argument("--overlap", action="store_true", help="with --time / --trace: put with FDH_GLYPH_MTSDF_OVERLAP")
+    ap.add_argument("--cases", default=",".join(CASES), help="with --all: the cases to run, comma-separated")
     ap.add_argument("--trace-dir", default=os.path.join(ROOT, "build", "msdf_trace"))
     ap.add_argument("--time", choices=list(CASES))
     ap.add_argument("--trace", choices=list(CASES))
     ap.add_argument("--calls", type=int, default=60)
     a = ap.parse_args()
+    unknown = [c for c in a.cases.split(",") if c not in CASES]
+    if unknown:
+        ap.error(f"--cases: unknown case(s) {', '.join(unknown)}; the cases are {', '.join(CASES)}")
     if a.all:
-        sys.exit(run_all(a.all, a.nocull_lib, a.trace_dir, a.parent_lib, a.passes))
+        sys.exit(run_all(a.all, a.nocull_lib, a.trace_dir, a.parent_lib, a.passes, a.cases.split(",")))
     elif a.time:
-        time_case(a.time, a.correct)
+        time_case(a.time, a.correct, a.overlap)
     elif a.trace:
-        trace_case(a.trace, a.calls, a.correct)
+        trace_case(a.trace, a.calls, a.correct, a.overlap)
     else:
         ap.error("nothing to do")
