@@ -43,6 +43,15 @@ class FrameStats(C.Structure):
                 ("bytes_blur_fused", C.c_int64), ("bytes_frame_implementation", C.c_int64)]
 
 
+class GlyphOutline(C.Structure):  # FdhGlyphOutline, include_glyphs/figdraw_hip_glyphs.h
+    _fields_ = [("key", C.c_int64), ("segs", C.c_void_p), ("n_segs", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("sdf_range", C.c_uint32)]
+
+
+class GlyphBatchStats(C.Structure):  # FdhGlyphBatchStats
+    _fields_ = [("glyphs", C.c_int32), ("written", C.c_int32), ("dropped_by_growth", C.c_int32), ("tiles", C.c_int32), ("edges", C.c_int32),
+                ("launches", C.c_int32), ("bytes_copied", C.c_int64)]
+
+
 def build(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 the C-ABI library in-tree (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -111,6 +120,10 @@ def load():
     L.fdh_atlas_packed_area.argtypes = [vp, C.POINTER(C.c_int64)]
     L.fdh_put_glyph_outline.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, C.c_uint32, C.c_int * 4]
     L.fdh_put_glyph_image.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_uint32, C.c_int * 4]
+    if hasattr(L, "fdh_put_glyph_outlines"):  # include_glyphs/figdraw_hip_glyphs.h (absent from libraries built before it, as below)
+        L.fdh_put_glyph_outlines.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
+        L.fdh_glyph_batch_stats.argtypes = [vp, C.POINTER(GlyphBatchStats)]
+        L.fdh_sizeof_glyph_outline.argtypes = []
     L.fdh_read_pixels.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.fdh_debug_read_surface.argtypes = [vp, C.c_int, vp]
     L.fdh_scene_retain.argtypes = [vp, vp, C.c_float, C.c_float, C.c_int, _F4]
@@ -358,6 +371,31 @@ class HipContext:
         flags = (1 if lcd_filter else 0) | (4 if mtsdf else 0) | (8 if correct else 0) | (32 if overlap else 0) | (int(sdf_range) << 8)
         self._ck(self.L.fdh_put_glyph_outline(self.h, int(key), int(w), int(h), segs.ctypes.data, len(segs), flags, out))
         return tuple(out)
+
+    def put_glyph_outlines(self, items, sdf_range: int = 0, correct: bool = False, overlap: bool = False):
+        """a batch of distance-field glyphs in one call (fdh_put_glyph_outlines, include_glyphs/figdraw_hip_glyphs.h): `items` is a sequence of
+        (key, segs, w, h) or (key, segs, w, h, range) -- a glyph's own range, 0 or absent: `sdf_range` (whose 0 is 4); correct and overlap as
+        in put_glyph_outline, for every glyph.  What the same put_glyph_outline(..., mtsdf=True) calls in order would leave, from a number of
+        launches that does not depend on len(items).  -> the rectangles, one (x, y, w, h) per item"""
+        items = list(items)
+        n = len(items)
+        arr = (GlyphOutline * max(n, 1))()
+        keep = []  # the outlines, alive until the call returns
+        for g, it in zip(arr, items):
+            segs = np.ascontiguousarray(it[1], dtype=np.float32).reshape(-1, 6)
+            keep.append(segs)
+            g.key, g.segs, g.n_segs, g.width, g.height = int(it[0]), segs.ctypes.data if len(segs) else None, len(segs), int(it[2]), int(it[3])
+            g.sdf_range = int(it[4]) if len(it) > 4 else 0
+        out = ((C.c_int * 4) * max(n, 1))()
+        flags = 4 | (8 if correct else 0) | (32 if overlap else 0) | (int(sdf_range) << 8)
+        self._ck(self.L.fdh_put_glyph_outlines(self.h, C.addressof(arr), n, flags, C.addressof(out)))
+        return [tuple(out[i]) for i in range(n)]
+
+    def glyph_batch_stats(self) -> dict:
+        """what the last put_glyph_outlines did: glyphs, written, dropped_by_growth, tiles, edges, launches, bytes_copied"""
+        st = GlyphBatchStats()
+        self._ck(self.L.fdh_glyph_batch_stats(self.h, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in GlyphBatchStats._fields_}
 
     def put_glyph_image(self, key, rgba: np.ndarray, lcd_filter=False):
         """a rasterised glyph, processed on the device on its way into the atlas (LCD filter, mip chain): pixie_raster.nim:12-95"""

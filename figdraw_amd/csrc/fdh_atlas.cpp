@@ -4,7 +4,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <climits>
 #include <cstring>
+#include <exception>
 
 namespace fdh {
 
@@ -48,7 +50,7 @@ void Atlas::release_levels() {
 }
 void Atlas::release() {
   release_levels();
-  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release();
+  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release();
 }
 void Atlas::reset(int minimum_size, hipStream_t s) {
   int sz = initial_size_;
@@ -277,6 +279,172 @@ void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const floa
   // sampled at level 0 alone, and these texels have no other home: such a field gets that level.
   if (w == 1 || h == 1) launch_atlas_blit(s, levels_[0], size_, x, y, field, w, h);
   glyph_to_atlas(s, field, spare, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
+}
+// fdh_put_glyph_outlines (the specification: include_glyphs/figdraw_hip_glyphs.h).  What n calls of put_glyph_mtsdf do, in three passes: every glyph is
+// validated and its shape built; every glyph is placed, in order, through place(); then the glyphs that are still in the atlas -- those
+// placed since the last growth -- get their texels from a number of launches that does not depend on n: the generator over the tiles of
+// all glyphs, the correction, and per atlas level one blit and one minify.
+// Single puts overwrite one another where two rectangles meet in a deep level (msdf::kOwnerLevel); one launch has no order, so the host
+// paints the rectangles of such a level in put order and gives every glyph the bits of the texels that are still its own.
+void Atlas::put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) {
+  // ---- pass 1: validation.  Nothing below this pass refuses a glyph.
+  if (flags & ~(uint32_t)(FDH_GLYPH_MTSDF | FDH_GLYPH_MTSDF_CORRECT | FDH_GLYPH_MTSDF_OVERLAP | 0xFF00u))
+    throw Error(FDH_ERR_INVALID, "put_glyph_outlines: unknown flag (coverage glyphs and the LCD flags are not batched)");
+  if (!(flags & FDH_GLYPH_MTSDF)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: needs FDH_GLYPH_MTSDF");
+  const uint32_t flag_range = (flags >> 8) & 255u;
+  if (flag_range > 64u) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: a distance range is at most 64");
+  if (n < 0 || (n > 0 && !glyphs)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: bad glyph array");
+  if (n > 65535) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: at most 65535 glyphs");
+  const bool correct = (flags & FDH_GLYPH_MTSDF_CORRECT) != 0, overlap = (flags & FDH_GLYPH_MTSDF_OVERLAP) != 0;
+  int64_t texels = 0, segments = 0;
+  for (int i = 0; i < n; i++) {
+    const FdhGlyphOutline& g = glyphs[i];
+    if (g.width <= 0 || g.height <= 0 || g.width > 4096 || g.height > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: image size must be in 1..4096");
+    if (g.n_segs < 0 || (g.n_segs > 0 && !g.segs)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: bad outline");
+    if (g.n_segs > msdf::kMaxSegments) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: a distance field takes at most 65535 segments");
+    if (g.sdf_range > 64u) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: a distance range is at most 64");
+    texels += (int64_t)g.width * g.height;
+    segments += g.n_segs;
+  }
+  if (texels > ((int64_t)1 << 24)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: at most 2^24 texels in a batch");
+  if (segments > ((int64_t)1 << 20)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: at most 2^20 segments in a batch");
+  std::vector<float> rec, one;           // the records of all glyphs, glyph after glyph (a device context only)
+  std::vector<msdf::BatchGlyph> tab((size_t)n);  // edge_off, n_edges, w, h, orient and the range now; the offsets and the place in pass 3
+  {
+    msdf::Shape shape;
+    for (int i = 0; i < n; i++) {
+      const FdhGlyphOutline& g = glyphs[i];
+      if (!msdf::build_shape(g.segs, g.n_segs, &shape)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines: a distance field needs closed contours");
+      const float range = g.sdf_range ? (float)g.sdf_range : (flag_range ? (float)flag_range : 4.0f);
+      msdf::BatchGlyph& t = tab[(size_t)i];
+      t = msdf::BatchGlyph{};
+      t.edge_off = (uint32_t)(rec.size() / msdf::kEdgeFloats); t.n_edges = (int32_t)shape.edges.size();
+      t.w = g.width; t.h = g.height;
+      t.orient = (float)shape.orient; t.inv_range = 1.0f / range; t.step = range / 255.0f;
+      if (device_) { msdf::edge_records(shape, &one); rec.insert(rec.end(), one.begin(), one.end()); }
+    }
+  }
+  batch_stats_ = FdhGlyphBatchStats{};
+  batch_stats_.glyphs = n;
+  if (n == 0) return;
+  // ---- the device buffers, for the whole batch (pass 3 takes a part of it), before any placement as every put does
+  auto level_size = [](int v, int l) { return (v + (1 << l) - 1) >> l; };
+  size_t all_tiles = 0, all_owner_words = 0;
+  for (const msdf::BatchGlyph& t : tab) {
+    all_tiles += (size_t)((t.w + 7) / 8) * ((t.h + 7) / 8);
+    size_t bits = 0;
+    for (int l = msdf::kOwnerLevel; l < kMaxMips && level_size(t.w, l) > 1 && level_size(t.h, l) > 1; l++) bits += (size_t)level_size(t.w, l) * level_size(t.h, l);
+    all_owner_words += (bits + 31) / 32;
+  }
+  constexpr size_t kGlyphWords = sizeof(msdf::BatchGlyph) / 4;
+  if (device_) {
+    glyph_a_.reserve((size_t)texels);
+    glyph_b_.reserve((size_t)texels);
+    glyph_edges_.reserve(std::max<size_t>(rec.size(), msdf::kEdgeFloats));
+    glyph_tab_.reserve((size_t)n * kGlyphWords + all_tiles + all_owner_words + 1);
+  }
+  // ---- pass 2: the places.  A placement that grows the atlas has dropped every entry before it: glyph i is then the first of the new atlas.
+  int first = 0, placed = 0;
+  std::exception_ptr failed;
+  for (; placed < n; placed++) {
+    const int before = size_;
+    try {
+      const AtlasEntry& e = place(s, glyphs[placed].key, glyphs[placed].width, glyphs[placed].height, out_rects ? out_rects[placed] : nullptr);
+      tab[(size_t)placed].x = e.x; tab[(size_t)placed].y = e.y;
+    } catch (...) {  // FDH_ERR_ATLAS_FULL (or no memory for a larger atlas): the glyphs before this one get their texels, as after single calls
+      failed = std::current_exception();
+    }
+    if (size_ != before) first = placed;
+    if (failed) break;
+  }
+  batch_stats_.written = placed - first;
+  batch_stats_.dropped_by_growth = first;
+  // ---- pass 3: the texels of glyphs first .. placed - 1
+  if (device_ && placed > first) {
+    const int m = placed - first;
+    const uint32_t edge_base = tab[(size_t)first].edge_off;
+    std::vector<uint32_t> words((size_t)m * kGlyphWords);
+    uint32_t field_off = 0, n_tiles = 0, owner_words = 0, n_edges = 0;
+    for (int k = 0; k < m; k++) {
+      msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+      t.edge_off -= edge_base; t.field_off = field_off; t.first_tile = n_tiles; t.owner_off = owner_words * 32u;
+      field_off += (uint32_t)(t.w * t.h);
+      n_tiles += (uint32_t)(((t.w + 7) / 8) * ((t.h + 7) / 8));
+      n_edges += (uint32_t)t.n_edges;
+      size_t bits = 0;
+      for (int l = msdf::kOwnerLevel; l < n_levels_ && level_size(t.w, l) > 1 && level_size(t.h, l) > 1; l++) bits += (size_t)level_size(t.w, l) * level_size(t.h, l);
+      owner_words += (uint32_t)((bits + 31) / 32);
+    }
+    words.resize((size_t)m * kGlyphWords + n_tiles + owner_words + 1, 0u);
+    std::memcpy(words.data(), &tab[(size_t)first], (size_t)m * sizeof(msdf::BatchGlyph));
+    uint32_t* tile_glyph = words.data() + (size_t)m * kGlyphWords;
+    uint32_t* owner = tile_glyph + n_tiles;
+    for (int k = 0; k < m; k++) {
+      const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+      const uint32_t end = k + 1 < m ? tab[(size_t)(first + k + 1)].first_tile : n_tiles;
+      for (uint32_t j = t.first_tile; j < end; j++) tile_glyph[j] = (uint32_t)k;
+    }
+    // the owner bits: level after level, the rectangles painted in put order into a map of the box they span
+    std::vector<int32_t> map;
+    for (int l = msdf::kOwnerLevel; l < n_levels_; l++) {
+      int bx0 = INT_MAX, by0 = INT_MAX, bx1 = 0, by1 = 0;
+      auto has_level = [&](const msdf::BatchGlyph& t) { return level_size(t.w, l) > 1 && level_size(t.h, l) > 1; };
+      for (int k = 0; k < m; k++) {
+        const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+        if (!has_level(t)) continue;
+        bx0 = std::min(bx0, t.x >> l); by0 = std::min(by0, t.y >> l);
+        bx1 = std::max(bx1, (t.x >> l) + level_size(t.w, l)); by1 = std::max(by1, (t.y >> l) + level_size(t.h, l));
+      }
+      if (bx1 <= bx0) break;  // no glyph reaches this level, nor a deeper one
+      const int bw = bx1 - bx0;
+      map.assign((size_t)bw * (by1 - by0), -1);
+      for (int k = 0; k < m; k++) {
+        const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+        if (!has_level(t)) continue;
+        for (int j = 0; j < level_size(t.h, l); j++)
+          for (int i = 0; i < level_size(t.w, l); i++) map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] = k;
+      }
+      for (int k = 0; k < m; k++) {
+        const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+        if (!has_level(t)) continue;
+        uint32_t bit = t.owner_off;
+        for (int d = msdf::kOwnerLevel; d < l; d++) bit += (uint32_t)(level_size(t.w, d) * level_size(t.h, d));
+        for (int j = 0; j < level_size(t.h, l); j++)
+          for (int i = 0; i < level_size(t.w, l); i++, bit++)
+            if (map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] == k) owner[bit >> 5] |= 1u << (bit & 31u);
+      }
+    }
+    const float* rec_first = rec.data() + (size_t)edge_base * msdf::kEdgeFloats;
+    const size_t rec_floats = rec.size() - (size_t)edge_base * msdf::kEdgeFloats;
+    if (rec_floats) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec_first, rec_floats * sizeof(float), hipMemcpyHostToDevice, s));
+    FDH_HIP(hipMemcpyAsync(glyph_tab_.ptr, words.data(), words.size() * 4, hipMemcpyHostToDevice, s));
+    const msdf::BatchGlyph* d_glyphs = reinterpret_cast<const msdf::BatchGlyph*>(glyph_tab_.ptr);
+    const uint32_t* d_tiles = glyph_tab_.ptr + (size_t)m * kGlyphWords;
+    const uint32_t* d_owner = d_tiles + n_tiles;
+    uint32_t *field = glyph_a_.ptr, *spare = glyph_b_.ptr;
+    int launches = 1;
+    launch_msdf_generate_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)n_tiles, field);
+    if (correct) {
+      launch_msdf_correct_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)n_tiles, field, spare);
+      std::swap(field, spare);
+      launches++;
+    }
+    for (int l = 0; l < n_levels_; l++) {  // every level, whatever the glyphs' sizes: the number of launches is the atlas's alone
+      launch_atlas_blit_batch(s, levels_[l], size_ >> l, l, d_glyphs, d_tiles, (int)n_tiles, d_owner, field);
+      launches++;
+      if (l + 1 == n_levels_) break;  // (a single put minifies once more, into a buffer nobody reads)
+      launch_minify2_batch(s, l, d_glyphs, d_tiles, (int)n_tiles, field, spare);
+      std::swap(field, spare);
+      launches++;
+    }
+    FDH_HIP(hipStreamSynchronize(s));  // (`rec` and `words` stay alive until here)
+    FDH_HIP(hipGetLastError());
+    batch_stats_.tiles = (int32_t)n_tiles;
+    batch_stats_.edges = (int32_t)n_edges;
+    batch_stats_.launches = launches;
+    batch_stats_.bytes_copied = (int64_t)(rec_floats * sizeof(float) + words.size() * 4);
+  }
+  if (failed) std::rethrow_exception(failed);
 }
 // Flippy: figdraw's mip-mapped image container (common/formatflippy.nim:77-149).  Layout: "flip", u32 version (1), then per
 // mip level "mip!", u32 width, u32 height, u32 zlen, and a raw-snappy block holding straight RGBA8.  The reference

@@ -6,6 +6,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../include_glyphs/figdraw_hip_glyphs.h"  // FdhGlyphOutline, FdhGlyphBatchStats
 #include "fdh_memory.h"  // DeviceBuf
 #include "fdh_types.h"   // AtlasView, kMaxMips
 
@@ -48,6 +49,9 @@ class Atlas {
   void put_image(hipStream_t s, int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]);
   void put_glyph_image(hipStream_t s, int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]);
   void put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]);
+  // fdh_put_glyph_outlines (the specification: include_glyphs/figdraw_hip_glyphs.h): n distance fields, validated as a whole, placed in order, made in one go
+  void put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
+  const FdhGlyphBatchStats& glyph_batch_stats() const { return batch_stats_; }
   void put_mips(hipStream_t s, int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]);
   void put_flippy(hipStream_t s, int64_t key, const uint8_t* data, size_t n, int out_rect[4]);
   void update_image(int64_t key, int w, int h, const uint8_t* rgba);
@@ -74,6 +78,8 @@ class Atlas {
   uint64_t epoch_ = 1;
   DeviceBuf<uint32_t> glyph_a_, glyph_b_;  // the device glyph pipeline: the raster and its filtered / minified successors
   DeviceBuf<float> glyph_lines_, glyph_acc_, glyph_edges_;  // flattened outline, area accumulators; the edge records of a distance field (fdh_msdf_host.h)
+  DeviceBuf<uint32_t> glyph_tab_;  // put_glyph_outlines: the glyph records (msdf::BatchGlyph), the tile -> glyph words, the owner bits of the deep levels
+  FdhGlyphBatchStats batch_stats_ = {};
 };
 
 }  // namespace fdh

@@ -9,6 +9,7 @@
 #include "../../include/figdraw_hip_readback.h"
 #include "../../include/figdraw_hip_stream.h"
 #include "../../include/figdraw_hip_exact.h"
+#include "../../include_glyphs/figdraw_hip_glyphs.h"
 
 using fdh::Context;
 
@@ -175,6 +176,16 @@ int fdh_update_image(FdhContext* c, int64_t key, int w, int h, const uint8_t* rg
   return guard([&] { C(c)->update_image(key, w, h, rgba); });
 }
 int fdh_remove_image(FdhContext* c, int64_t key) { return guard([&] { C(c)->remove_image(key); }); }
+int fdh_put_glyph_outlines(FdhContext* c, const FdhGlyphOutline* glyphs, int n_glyphs, uint32_t flags, int (*out_rects)[4]) {
+  return guard([&] { C(c)->put_glyph_outlines(glyphs, n_glyphs, flags, out_rects); });
+}
+int fdh_glyph_batch_stats(FdhContext* c, FdhGlyphBatchStats* out) {
+  return guard([&] {
+    if (!out) throw fdh::Error(FDH_ERR_INVALID, "fdh_glyph_batch_stats: null pointer");
+    *out = C(c)->glyph_batch_stats();
+  });
+}
+int fdh_sizeof_glyph_outline(void) { return (int)sizeof(FdhGlyphOutline); }
 int fdh_has_image(FdhContext* c, int64_t key, int* out) { return guard([&] { *out = C(c)->has_image(key) ? 1 : 0; }); }
 int fdh_reset_atlas(FdhContext* c, int minimum_size) { return guard([&] { C(c)->reset_atlas(minimum_size); }); }
 int fdh_atlas_size(FdhContext* c, int* out) { return guard([&] { *out = C(c)->atlas_size(); }); }

@@ -137,6 +137,18 @@ void launch_msdf_correct(hipStream_t s, const float* edges, int n_edges, int w, 
 // records are the same, slot 15 of a contour's last one says where it ends and whether it is filled (+1) or a hole (-1)
 void launch_msdf_generate_union(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, uint32_t* out);
 void launch_msdf_correct_union(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out);
+// fdh_put_glyph_outlines (include_glyphs/figdraw_hip_glyphs.h): the launches above and the level chain for a batch of glyphs at once.  `glyphs`: one
+// msdf::BatchGlyph each (fdh_msdf_host.h); `tile_glyph`: the glyph of each of the n_tiles 8 x 8 tiles, the 1-D grid of every launch here; the
+// edge records of all glyphs in `edges`, their fields one after the other in `out` / `in` / `src` / `dst`.  `overlap`: step 6's kernels.
+// Level l of the chain: the blit of every glyph that has that level (`owner`: one bit per texel from level msdf::kOwnerLevel on, set
+// where the glyph is the last of the batch to cover the texel), and its minify from `src` into `dst`.
+namespace msdf { struct BatchGlyph; }
+void launch_msdf_generate_batch(hipStream_t s, bool overlap, const float* edges, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, uint32_t* out);
+void launch_msdf_correct_batch(hipStream_t s, bool overlap, const float* edges, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* in,
+                               uint32_t* out);
+void launch_atlas_blit_batch(hipStream_t s, uint32_t* level, int LS, int l, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* owner,
+                             const uint32_t* src);
+void launch_minify2_batch(hipStream_t s, int l, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* src, uint32_t* dst);
 // The frame upload (k_upload_frame): a table of runs, each `bytes` of pinned host memory (its device view) going to byte offset
 // dst_off of the frame block.  kind 0: 16-byte units; 1: BinRecs -- copied in 8-byte units, and the lane that carries a record's
 // pixel bounds also writes the draw's 4-byte bin box; 2: DrawRecs -- 16-byte units, and the `ext` of every F_GENERAL record gets

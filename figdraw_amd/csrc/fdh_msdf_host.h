@@ -186,5 +186,27 @@ inline void edge_records(const Shape& s, std::vector<float>* rec) {
   }
 }
 
+// fdh_put_glyph_outlines (include_glyphs/figdraw_hip_glyphs.h): one glyph of a batch as the batched kernels read it, 16 words.  The glyphs' edge
+// records lie one after the other in one buffer, their w x h fields one after the other in another (and in its twin: the correction and the
+// level chain go from one to the other inside the glyph's own region); the 8 x 8 tiles of all glyphs are numbered through, row-major
+// inside a glyph, and a table of one word per tile names the tile's glyph.
+struct BatchGlyph {
+  uint32_t edge_off;   // the glyph's first record, in records
+  int32_t n_edges;
+  int32_t w, h;
+  float orient;        // the sign of the outline's area
+  float inv_range;     // 1 / range and range / 255 as the single launchers pass them
+  float step;
+  uint32_t field_off;  // the glyph's first texel in the field buffers
+  uint32_t first_tile;
+  int32_t x, y;        // where the field goes in level 0 of the atlas
+  uint32_t owner_off;  // the glyph's first bit in the table of owned texels (k_atlas_blit_batch), per level from kOwnerLevel on
+  uint32_t pad[4];
+};
+static_assert(sizeof(BatchGlyph) == 64, "BatchGlyph is 16 words");
+// Up to this level two glyphs' rectangles cannot meet: the packer keeps 8 texels between them, and level l places ceil(w / 2^l) texels at
+// x >> l, which ends at most at ceil((x + w) / 2^l) <= (x + w + 8) >> l while 2^l - 1 <= 8.  From this level on they can, and the later put wins.
+constexpr int kOwnerLevel = 4;
+
 }  // namespace msdf
 }  // namespace fdh

@@ -2,6 +2,7 @@
 // pixie's minifyBy2 for the mip chain (opengl/textures.nim:106-119), the blit into a level, the coverage rasteriser of glyph outlines,
 // and a fill.
 #include "fdh_device.h"
+#include "fdh_msdf_host.h"  // msdf::BatchGlyph: the batched blit and minify of fdh_put_glyph_outlines
 
 namespace fdh {
 // ------------------------------------------------------------------ glyph images on their way into the atlas
@@ -45,12 +46,69 @@ __global__ void k_minify2(const uint32_t* __restrict__ src, uint32_t* __restrict
   }
   dst[(size_t)y * nw + x] = o;
 }
+// (k_minify2 as a function of the texel, for k_minify2_batch; k_minify2 itself stays as it was compiled: profiles/msdf.txt section 6)
+__device__ __forceinline__ void minify2_texel(const uint32_t* src, uint32_t* dst, int sw, int sh, int x, int y) {
+  const int nw = (sw + 1) >> 1, nh = (sh + 1) >> 1;
+  if (x >= nw || y >= nh) return;
+  const bool col_pair = 2 * x + 1 < sw, row_pair = 2 * y + 1 < sh;
+  const int x0 = col_pair ? 2 * x : sw - 1, x1 = col_pair ? 2 * x + 1 : sw - 1, y0 = row_pair ? 2 * y : sh - 1, y1 = row_pair ? 2 * y + 1 : sh - 1;
+  const uint32_t a = src[(size_t)y0 * sw + x0], b = src[(size_t)y0 * sw + x1], c = src[(size_t)y1 * sw + x0], d = src[(size_t)y1 * sw + x1];
+  uint32_t o = 0;
+#pragma unroll
+  for (int k = 0; k < 32; k += 8) {
+    const uint32_t ca = (a >> k) & 255u, cb = (b >> k) & 255u, cc = (c >> k) & 255u, cd = (d >> k) & 255u;
+    uint32_t v;
+    if (col_pair && row_pair) v = (ca + cb + cc + cd) >> 2;
+    else if (row_pair) v = ((ca * 127u + cc * 128u) / 255u) * 128u / 255u;  // last column: rows 2y, 2y + 1
+    else if (col_pair) v = ((ca * 127u + cb * 128u) / 255u) * 128u / 255u;  // last row: columns 2x, 2x + 1
+    else v = ca * 64u / 255u;
+    o |= v << k;
+  }
+  dst[(size_t)y * nw + x] = o;
+}
 // a w x h image into the rectangle (x, y) of one atlas level (LS texels wide); texels outside the level are dropped
-__global__ void k_atlas_blit(uint32_t* __restrict__ level, int LS, int x, int y, const uint32_t* __restrict__ src, int w, int h) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+__device__ __forceinline__ void atlas_blit_texel(uint32_t* level, int LS, int x, int y, const uint32_t* src, int w, int h, int i, int j) {
   if (i >= w || j >= h) return;
   const int tx = x + i, ty = y + j;
   if (tx >= 0 && ty >= 0 && tx < LS && ty < LS) level[(size_t)ty * LS + tx] = src[(size_t)j * w + i];
+}
+__global__ void k_atlas_blit(uint32_t* __restrict__ level, int LS, int x, int y, const uint32_t* __restrict__ src, int w, int h) {
+  atlas_blit_texel(level, LS, x, y, src, w, h, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
+}
+// fdh_put_glyph_outlines (include_glyphs/figdraw_hip_glyphs.h): level `l` of the chain for every glyph of a batch at once, over the tile table of the
+// batched generator (k_msdf.hip): one workgroup per 8 x 8 tile of a glyph's LEVEL-0 tile grid -- the glyph minified l times has fewer, the
+// rest leave.  A glyph's image at level l is ceil(w / 2^l) x ceil(h / 2^l), stored densely at the start of the glyph's own region of the
+// two field buffers, which it goes back and forth between as a single put does between its two.  A glyph is in the chain while that image is
+// more than 1 texel wide and high (Atlas::each_level); at level 0 a narrower one is stored all the same (Atlas::put_glyph_mtsdf).
+// From msdf::kOwnerLevel on two glyphs' rectangles can meet, and single puts leave such a texel to the later one: the host has worked out
+// which texels a glyph owns, one bit each, level after level from the glyph's owner_off.
+struct BatchTile { msdf::BatchGlyph g; int cw, ch, i, j; };
+__device__ __forceinline__ BatchTile batch_tile(const msdf::BatchGlyph* __restrict__ glyphs, const uint32_t* __restrict__ tile_glyph, int l) {
+  BatchTile t;
+  t.g = glyphs[tile_glyph[blockIdx.x]];
+  const int tile = (int)(blockIdx.x - t.g.first_tile), tiles_x = (t.g.w + 7) / 8;
+  t.cw = (t.g.w + (1 << l) - 1) >> l; t.ch = (t.g.h + (1 << l) - 1) >> l;
+  t.j = tile / tiles_x * 8 + (int)(threadIdx.x >> 3); t.i = (tile - tile / tiles_x * tiles_x) * 8 + (int)(threadIdx.x & 7);
+  return t;
+}
+__global__ __launch_bounds__(64) void k_atlas_blit_batch(uint32_t* __restrict__ level, int LS, int l, const msdf::BatchGlyph* __restrict__ glyphs,
+                                                         const uint32_t* __restrict__ tile_glyph, const uint32_t* __restrict__ owner, const uint32_t* __restrict__ src) {
+  const BatchTile t = batch_tile(glyphs, tile_glyph, l);
+  if (!((t.cw > 1 && t.ch > 1) || l == 0)) return;
+  if (l >= msdf::kOwnerLevel) {
+    if (t.i >= t.cw || t.j >= t.ch) return;
+    uint32_t bit = t.g.owner_off;
+    for (int k = msdf::kOwnerLevel; k < l; k++) bit += (uint32_t)(((t.g.w + (1 << k) - 1) >> k) * ((t.g.h + (1 << k) - 1) >> k));
+    bit += (uint32_t)(t.j * t.cw + t.i);
+    if (!((owner[bit >> 5] >> (bit & 31u)) & 1u)) return;
+  }
+  atlas_blit_texel(level, LS, t.g.x >> l, t.g.y >> l, src + t.g.field_off, t.cw, t.ch, t.i, t.j);
+}
+__global__ __launch_bounds__(64) void k_minify2_batch(int l, const msdf::BatchGlyph* __restrict__ glyphs, const uint32_t* __restrict__ tile_glyph,
+                                                      const uint32_t* __restrict__ src, uint32_t* __restrict__ dst) {
+  const BatchTile t = batch_tile(glyphs, tile_glyph, l);
+  if (!(t.cw > 1 && t.ch > 1)) return;
+  minify2_texel(src + t.g.field_off, dst + t.g.field_off, t.cw, t.ch, t.i, t.j);
 }
 // Glyph outline -> coverage: exact-area scanline accumulation (oracle/figdraw_oracle.c, raster_row_line, operation for operation:
 // no FMA contraction here so that both produce the same floats).  One lane owns one pixel row: it walks every line segment in
@@ -129,6 +187,13 @@ void launch_minify2(hipStream_t s, const uint32_t* src, uint32_t* dst, int sw, i
 }
 void launch_atlas_blit(hipStream_t s, uint32_t* level, int LS, int x, int y, const uint32_t* src, int w, int h) {
   if (w > 0 && h > 0) hipLaunchKernelGGL(k_atlas_blit, dim3((w + 63) / 64, h), dim3(64), 0, s, level, LS, x, y, src, w, h);
+}
+void launch_atlas_blit_batch(hipStream_t s, uint32_t* level, int LS, int l, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* owner,
+                             const uint32_t* src) {
+  if (n_tiles > 0) hipLaunchKernelGGL(k_atlas_blit_batch, dim3(n_tiles), dim3(64), 0, s, level, LS, l, glyphs, tile_glyph, owner, src);
+}
+void launch_minify2_batch(hipStream_t s, int l, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* src, uint32_t* dst) {
+  if (n_tiles > 0) hipLaunchKernelGGL(k_minify2_batch, dim3(n_tiles), dim3(64), 0, s, l, glyphs, tile_glyph, src, dst);
 }
 
 __global__ void k_fill_u32(uint32_t* p, uint32_t v, size_t n) {

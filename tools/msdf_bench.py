@@ -10,8 +10,13 @@ k_msdf_correct, and with FDH_GLYPH_MTSDF_OVERLAP k_msdf_generate_union), on an M
                                                --nocull-lib: the library built with -DFDH_MSDF_NO_CULL=1
                                                (make -C figdraw_amd/csrc variant NAME=msdf_nocull DEFS=-DFDH_MSDF_NO_CULL=1);
                                                --parent-lib: the parent commit's library, for "the flag-off call is unchanged"
-  msdf_bench.py --time CASE [--correct] [--overlap]    the whole call on the host clock, profiler off: 200 timed calls after 20; one JSON line
-  msdf_bench.py --trace CASE [--correct] [--overlap] [--calls N]   N calls (run it under rocprofv3 --kernel-trace --stats -f csv); one JSON line
+  msdf_bench.py --batch OUT --parent-lib LIB [--passes N]
+                                               the font set as ONE fdh_put_glyph_outlines (include_glyphs/figdraw_hip_glyphs.h) against 106 single puts
+                                               of the parent commit's library, per flag combination, alternating, N passes each (default 2);
+                                               then the batch's kernels from a rocprofv3 run of its own; writes section 6's table
+  msdf_bench.py --time CASE [--correct] [--overlap] [--batched]    the whole call on the host clock, profiler off: 200 timed calls after 20; one JSON line
+  msdf_bench.py --trace CASE [--correct] [--overlap] [--batched] [--calls N]   N calls (run it under rocprofv3 --kernel-trace --stats -f csv); one JSON line
+                                               --batched: a call is one fdh_put_glyph_outlines of the case's puts
 
 Cases: small = one glyph outline ('g' of the fixture, scaled to a 32 x 32 field, range 4); large = six glyph outlines scaled and laid side by
 side in a 256 x 256 field (about 200 segments); font = the 106 inputs of tests/msdf_cases.py, one put each (a "call" is all 106); many =
@@ -81,7 +86,15 @@ def _context():
     return HipContext(atlas_size=4096, device=0)
 
 
-def time_case(case, correct=False, overlap=False):
+def put_all(ctx, puts, first_key, correct, overlap, batched):
+    if batched:
+        ctx.put_glyph_outlines([(first_key + i, segs, w, h, R) for i, (segs, w, h, R) in enumerate(puts)], correct=correct, overlap=overlap)
+        return
+    for i, (segs, w, h, R) in enumerate(puts):
+        ctx.put_glyph_outline(first_key + i, segs, w, h, mtsdf=True, sdf_range=R, **CORRECT[correct], **OVERLAP[overlap])
+
+
+def time_case(case, correct=False, overlap=False, batched=False):
     puts = outlines(case)
     timed, warm = ROUNDS.get(case, (200, 20))
     ctx = _context()
@@ -90,26 +103,25 @@ def time_case(case, correct=False, overlap=False):
         if k % (100 // len(puts) or 1) == 0:
             ctx.reset_atlas()  # (the packer's search grows with what is packed; every call packs a new rectangle)
         t1 = time.perf_counter()
-        for i, (segs, w, h, R) in enumerate(puts):
-            ctx.put_glyph_outline(1 + k * len(puts) + i, segs, w, h, mtsdf=True, sdf_range=R, **CORRECT[correct], **OVERLAP[overlap])
+        put_all(ctx, puts, 1 + k * len(puts), correct, overlap, batched)
         t2 = time.perf_counter()
         if k >= warm:
             us.append((t2 - t1) * 1e6)
+    stats = ctx.glyph_batch_stats() if batched else None
     ctx.close()
-    print(json.dumps({"case": case, "correct": correct, "overlap": overlap, "segments": sum(len(p[0]) for p in puts), "calls": timed, "median_us": statistics.median(us),
+    print(json.dumps({"case": case, "correct": correct, "overlap": overlap, "batched": batched, "batch_stats": stats, "segments": sum(len(p[0]) for p in puts), "calls": timed, "median_us": statistics.median(us),
                       "p10_us": sorted(us)[len(us) // 10], "p90_us": sorted(us)[9 * len(us) // 10]}))
 
 
-def trace_case(case, calls, correct=False, overlap=False):
+def trace_case(case, calls, correct=False, overlap=False, batched=False):
     puts = outlines(case)
     ctx = _context()
     for k in range(calls):
         if k % (100 // len(puts) or 1) == 0:
             ctx.reset_atlas()
-        for i, (segs, w, h, R) in enumerate(puts):
-            ctx.put_glyph_outline(1 + k * len(puts) + i, segs, w, h, mtsdf=True, sdf_range=R, **CORRECT[correct], **OVERLAP[overlap])
+        put_all(ctx, puts, 1 + k * len(puts), correct, overlap, batched)
     ctx.close()
-    print(json.dumps({"case": case, "correct": correct, "overlap": overlap, "segments": sum(len(p[0]) for p in puts), "calls": calls}))
+    print(json.dumps({"case": case, "correct": correct, "overlap": overlap, "batched": batched, "segments": sum(len(p[0]) for p in puts), "calls": calls}))
 
 
 HEAD = """tools/msdf_bench.py -- a distance-field put (fdh_put_glyph_outline with FDH_GLYPH_MTSDF), MI355X.
@@ -179,9 +191,68 @@ def run_all(out_path, nocull_lib, trace_dir, parent_lib=None, passes=1, cases=tu
     return 0 if ok else 1
 
 
+BATCH_HEAD = """tools/msdf_bench.py --batch -- the 106 font inputs as ONE fdh_put_glyph_outlines against 106 single fdh_put_glyph_outline calls of the
+parent commit's library, MI355X.  Host clock around the 106 glyphs, profiler off, 200 timed after 20 per leg; the two legs alternate, each
+leg a process of its own, `passes` times per flag combination.  Kernels: a rocprofv3 --kernel-trace --stats run of its own, 60 batches.
+
+Hypotheses, stated before the numbers (nothing had been timed when they were written):
+  1. the batched generate launch (about 2 100 waves) takes about as long as the single launch of its slowest glyph: tens of microseconds,
+     where the 106 single launches add up to milliseconds.
+  2. the call is then dominated by the host -- build_shape and the edge records of 106 outlines, the packer -- and by the level chain's
+     launches: 2 x 12 - 1 of them on a 4096 atlas, most with nothing to do below level 5.
+"""
+
+
+def run_batch(out_path, parent_lib, trace_dir, passes=2):
+    me = [sys.executable, os.path.abspath(__file__)]
+    lines = BATCH_HEAD.splitlines() + [""]
+    parent_env = dict(os.environ, FIGDRAW_HIP_LIB=os.path.abspath(parent_lib))
+    ok = True
+    for correct in (False, True):
+        for overlap in (False, True):
+            flag = (["--correct"] if correct else []) + (["--overlap"] if overlap else [])
+            name = " | ".join(["MTSDF"] + (["CORRECT"] if correct else []) + (["OVERLAP"] if overlap else []))
+            med = {"batch": [], "singles": []}
+            stats = None
+            for _ in range(passes):
+                for leg, cmd, env in (("batch", ["--batched"], None), ("singles", [], parent_env)):
+                    got = _step(me + ["--time", "font"] + flag + cmd, 300, env) if ok else None
+                    if got is None:
+                        ok = False
+                        break
+                    r = json.loads([ln for ln in got.strip().splitlines() if ln.startswith("{")][-1])
+                    med[leg].append((r["median_us"], r["p10_us"], r["p90_us"]))
+                    stats = r.get("batch_stats") or stats
+            if not ok:
+                break
+            d = os.path.join(trace_dir, "batch_" + "_".join(["font"] + [f.strip("-") for f in flag]))
+            got = _step(["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "-o", "t", "--"] + me + ["--trace", "font", "--batched", "--calls", "60"] + flag, 300)
+            if got is None:
+                ok = False
+                break
+            kern = _stats(d, "*kernel_stats.csv")
+            b, s1 = [m[0] for m in med["batch"]], [m[0] for m in med["singles"]]
+            spread = max(max(b) - min(b), max(s1) - min(s1))
+            lines.append(f"{name}: batch, median us per pass {', '.join(f'{m[0]:.1f} (p10 {m[1]:.1f}, p90 {m[2]:.1f})' for m in med['batch'])}; "
+                         f"106 single calls of the parent, {', '.join(f'{m[0]:.1f} (p10 {m[1]:.1f}, p90 {m[2]:.1f})' for m in med['singles'])}")
+            lines.append(f"    ratio of the means of the passes' medians {sum(s1) / sum(b):.1f} x; singles - batch {sum(s1) / len(s1) - sum(b) / len(b):.1f} us, "
+                         f"the larger spread between a leg's own passes {spread:.1f} us: {'the batch wins by more than the spread' if min(s1) - max(b) > spread else 'NOT beyond the spread'}")
+            lines.append(f"    the batch: {stats}")
+            lines.append("    kernels, us per launch (launches per batch): " + ", ".join(f"{k} {v[1] / max(v[0], 1):.2f} ({v[0] / 60:.0f}), the longest {v[2]:.1f}"
+                                                                                       for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1])))
+            lines.append(f"    kernels, us per batch in all: {sum(v[1] for v in kern.values()) / 60:.1f}")
+            print("\n".join(lines[-5:]), flush=True)
+    if not ok:
+        lines += ["", "INCOMPLETE: a step failed; nothing was started after it"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    return 0 if ok else 1
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--all", metavar="OUT")
+    ap.add_argument("--batch", metavar="OUT", help="the font set as one batch against single calls of --parent-lib")
+    ap.add_argument("--batched", action="store_true", help="with --time / --trace: one fdh_put_glyph_outlines per call")
     ap.add_argument("--nocull-lib")
     ap.add_argument("--parent-lib")
     ap.add_argument("--passes", type=int, default=1)
@@ -196,11 +267,15 @@ if __name__ == "__main__":
     unknown = [c for c in a.cases.split(",") if c not in CASES]
     if unknown:
         ap.error(f"--cases: unknown case(s) {', '.join(unknown)}; the cases are {', '.join(CASES)}")
-    if a.all:
+    if a.batch:
+        if not a.parent_lib:
+            ap.error("--batch needs --parent-lib")
+        sys.exit(run_batch(a.batch, a.parent_lib, a.trace_dir, max(a.passes, 2)))
+    elif a.all:
         sys.exit(run_all(a.all, a.nocull_lib, a.trace_dir, a.parent_lib, a.passes, a.cases.split(",")))
     elif a.time:
-        time_case(a.time, a.correct, a.overlap)
+        time_case(a.time, a.correct, a.overlap, a.batched)
     elif a.trace:
-        trace_case(a.trace, a.calls, a.correct, a.overlap)
+        trace_case(a.trace, a.calls, a.correct, a.overlap, a.batched)
     else:
         ap.error("nothing to do")
