@@ -124,6 +124,9 @@ def load():
         L.fdh_put_glyph_outlines.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
         L.fdh_glyph_batch_stats.argtypes = [vp, C.POINTER(GlyphBatchStats)]
         L.fdh_sizeof_glyph_outline.argtypes = []
+    if hasattr(L, "fdh_put_glyph_coverage_batch"):  # include_glyphs/figdraw_hip_coverage.h
+        L.fdh_put_glyph_coverage_batch.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
+        L.fdh_glyph_coverage_batch_stats.argtypes = [vp, C.POINTER(GlyphBatchStats)]
     L.fdh_read_pixels.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.fdh_debug_read_surface.argtypes = [vp, C.c_int, vp]
     L.fdh_scene_retain.argtypes = [vp, vp, C.c_float, C.c_float, C.c_int, _F4]
@@ -395,6 +398,29 @@ class HipContext:
         """what the last put_glyph_outlines did: glyphs, written, dropped_by_growth, tiles, edges, launches, bytes_copied"""
         st = GlyphBatchStats()
         self._ck(self.L.fdh_glyph_batch_stats(self.h, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in GlyphBatchStats._fields_}
+
+    def put_glyph_coverage_batch(self, items, lcd_filter=False):
+        """a batch of coverage glyphs in one call (fdh_put_glyph_coverage_batch, include_glyphs/figdraw_hip_coverage.h): `items` is a sequence of
+        (key, segs, w, h); lcd_filter as in put_glyph_image (True, False or "context"), for every glyph.  What the same put_glyph_outline
+        calls in order would leave, from a number of launches that does not depend on len(items).  -> the rectangles, one (x, y, w, h) per item"""
+        items = list(items)
+        n = len(items)
+        arr = (GlyphOutline * max(n, 1))()
+        keep = []  # the outlines, alive until the call returns
+        for g, it in zip(arr, items):
+            segs = np.ascontiguousarray(it[1], dtype=np.float32).reshape(-1, 6)
+            keep.append(segs)
+            g.key, g.segs, g.n_segs, g.width, g.height, g.sdf_range = int(it[0]), segs.ctypes.data if len(segs) else None, len(segs), int(it[2]), int(it[3]), 0
+        out = ((C.c_int * 4) * max(n, 1))()
+        flags = 2 if lcd_filter == "context" else (1 if lcd_filter else 0)
+        self._ck(self.L.fdh_put_glyph_coverage_batch(self.h, C.addressof(arr), n, flags, C.addressof(out)))
+        return [tuple(out[i]) for i in range(n)]
+
+    def glyph_coverage_batch_stats(self) -> dict:
+        """what the last put_glyph_coverage_batch did: glyphs, written, dropped_by_growth, tiles, edges (flattened lines), launches, bytes_copied"""
+        st = GlyphBatchStats()
+        self._ck(self.L.fdh_glyph_coverage_batch_stats(self.h, C.byref(st)))
         return {name: int(getattr(st, name)) for name, _ in GlyphBatchStats._fields_}
 
     def put_glyph_image(self, key, rgba: np.ndarray, lcd_filter=False):

@@ -207,6 +207,22 @@ static int flatten_count(const float* q) {
   const int n = (int)std::ceil(std::sqrt(dev * 10.0f));  // error of n chords = dev / (4 n^2) <= 0.025 px
   return n < 1 ? 1 : (n > 64 ? 64 : n);
 }
+// the lines (x0, y0, x1, y1) of an outline's n segments, appended: the single put's and the coverage batch's
+static void flatten_outline(const float* segs, int n, std::vector<float>* lines) {
+  for (int i = 0; i < n; i++) {
+    const float* q = segs + 6 * (size_t)i;
+    if (q[2] != q[2]) { lines->insert(lines->end(), {q[0], q[1], q[4], q[5]}); continue; }
+    const int k = flatten_count(q);
+    float px = q[0], py = q[1];
+    for (int j = 1; j <= k; j++) {
+      const float t = (float)j / (float)k, u = 1.0f - t;
+      const float x = j == k ? q[4] : (u * u) * q[0] + (2.0f * u * t) * q[2] + (t * t) * q[4];
+      const float y = j == k ? q[5] : (u * u) * q[1] + (2.0f * u * t) * q[3] + (t * t) * q[5];
+      lines->insert(lines->end(), {px, py, x, y});
+      px = x; py = y;
+    }
+  }
+}
 void Atlas::put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) {
   if (w <= 0 || h <= 0 || w > 4096 || h > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_outline: image size must be in 1..4096");
   if (n < 0 || (n > 0 && !segs)) throw Error(FDH_ERR_INVALID, "put_glyph_outline: bad outline");
@@ -222,19 +238,7 @@ void Atlas::put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const fl
   }
   std::vector<float> lines;
   lines.reserve((size_t)n * 16);
-  for (int i = 0; i < n; i++) {
-    const float* q = segs + 6 * (size_t)i;
-    if (q[2] != q[2]) { lines.insert(lines.end(), {q[0], q[1], q[4], q[5]}); continue; }
-    const int k = flatten_count(q);
-    float px = q[0], py = q[1];
-    for (int j = 1; j <= k; j++) {
-      const float t = (float)j / (float)k, u = 1.0f - t;
-      const float x = j == k ? q[4] : (u * u) * q[0] + (2.0f * u * t) * q[2] + (t * t) * q[4];
-      const float y = j == k ? q[5] : (u * u) * q[1] + (2.0f * u * t) * q[3] + (t * t) * q[5];
-      lines.insert(lines.end(), {px, py, x, y});
-      px = x; py = y;
-    }
-  }
+  flatten_outline(segs, n, &lines);
   const size_t npx = (size_t)w * h, m = lines.size() / 4;
   if (device_) {
     glyph_a_.reserve(npx);
@@ -279,6 +283,120 @@ void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const floa
   // sampled at level 0 alone, and these texels have no other home: such a field gets that level.
   if (w == 1 || h == 1) launch_atlas_blit(s, levels_[0], size_, x, y, field, w, h);
   glyph_to_atlas(s, field, spare, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
+}
+// ---- what the two batch calls share (put_glyph_outlines and put_glyph_coverage_batch below)
+constexpr size_t kBatchGlyphWords = sizeof(msdf::BatchGlyph) / 4;
+static int level_size(int v, int l) { return (v + (1 << l) - 1) >> l; }
+// The 8 x 8 tiles of a glyph.  `thin_tiles`: a glyph 1 texel wide or high has tiles too (a distance field: put_glyph_mtsdf stores its level 0);
+// without it such a glyph has none and gets no texel from any launch (a coverage glyph: each_level stores nothing of it).
+static size_t batch_tiles(const msdf::BatchGlyph& t, bool thin_tiles) {
+  return thin_tiles || (t.w > 1 && t.h > 1) ? (size_t)((t.w + 7) / 8) * ((t.h + 7) / 8) : 0;
+}
+static size_t owner_bits(const msdf::BatchGlyph& t, int n_levels) {
+  size_t bits = 0;
+  for (int l = msdf::kOwnerLevel; l < n_levels && level_size(t.w, l) > 1 && level_size(t.h, l) > 1; l++) bits += (size_t)level_size(t.w, l) * level_size(t.h, l);
+  return bits;
+}
+// the words of the tables of a whole batch, whatever atlas it ends in: what glyph_tab_ is reserved for before the first placement
+size_t Atlas::batch_table_words(const std::vector<msdf::BatchGlyph>& tab, bool thin_tiles) {
+  size_t all_tiles = 0, all_owner_words = 0;
+  for (const msdf::BatchGlyph& t : tab) {
+    all_tiles += batch_tiles(t, thin_tiles);
+    all_owner_words += (owner_bits(t, kMaxMips) + 31) / 32;
+  }
+  return tab.size() * kBatchGlyphWords + all_tiles + all_owner_words + 1;
+}
+// Pass 2 of a batch: every glyph through place(), in order; tab[i] takes its place.  A placement that grows the atlas has dropped every entry
+// before it: glyph i is then the first of the new atlas (*first).  *placed: the glyphs that got a place; the exception that ended the loop
+// (FDH_ERR_ATLAS_FULL, or no memory for a larger atlas) is returned: the glyphs before that one get their texels, as after single calls.
+std::exception_ptr Atlas::place_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, int (*out_rects)[4], std::vector<msdf::BatchGlyph>& tab, int* first, int* placed) {
+  std::exception_ptr failed;
+  int f = 0, p = 0;
+  for (; p < n; p++) {
+    const int before = size_;
+    try {
+      const AtlasEntry& e = place(s, glyphs[p].key, glyphs[p].width, glyphs[p].height, out_rects ? out_rects[p] : nullptr);
+      tab[(size_t)p].x = e.x; tab[(size_t)p].y = e.y;
+    } catch (...) {
+      failed = std::current_exception();
+    }
+    if (size_ != before) f = p;
+    if (failed) break;
+  }
+  *first = f; *placed = p;
+  return failed;
+}
+// The tables of glyphs first .. first + m - 1 as the batched kernels read them: the glyph records (their offsets filled in here, edge_off
+// made relative to the first glyph's), one word per tile naming its glyph, and the owner bits: level after level from msdf::kOwnerLevel
+// on, the rectangles painted in put order into a map of the box they span.
+void Atlas::batch_tables(std::vector<msdf::BatchGlyph>& tab, int first, int m, bool thin_tiles, BatchTables* T) const {
+  const uint32_t edge_base = tab[(size_t)first].edge_off;
+  uint32_t field_off = 0, n_tiles = 0, owner_words = 0, n_edges = 0;
+  for (int k = 0; k < m; k++) {
+    msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+    t.edge_off -= edge_base; t.field_off = field_off; t.first_tile = n_tiles; t.owner_off = owner_words * 32u;
+    field_off += (uint32_t)(t.w * t.h);
+    n_tiles += (uint32_t)batch_tiles(t, thin_tiles);
+    n_edges += (uint32_t)t.n_edges;
+    owner_words += (uint32_t)((owner_bits(t, n_levels_) + 31) / 32);
+  }
+  std::vector<uint32_t>& words = T->words;
+  words.assign((size_t)m * kBatchGlyphWords + n_tiles + owner_words + 1, 0u);
+  std::memcpy(words.data(), &tab[(size_t)first], (size_t)m * sizeof(msdf::BatchGlyph));
+  uint32_t* tile_glyph = words.data() + (size_t)m * kBatchGlyphWords;
+  uint32_t* owner = tile_glyph + n_tiles;
+  for (int k = 0; k < m; k++) {
+    const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+    const uint32_t end = k + 1 < m ? tab[(size_t)(first + k + 1)].first_tile : n_tiles;
+    for (uint32_t j = t.first_tile; j < end; j++) tile_glyph[j] = (uint32_t)k;
+  }
+  std::vector<int32_t> map;
+  for (int l = msdf::kOwnerLevel; l < n_levels_; l++) {
+    int bx0 = INT_MAX, by0 = INT_MAX, bx1 = 0, by1 = 0;
+    auto has_level = [&](const msdf::BatchGlyph& t) { return level_size(t.w, l) > 1 && level_size(t.h, l) > 1; };
+    for (int k = 0; k < m; k++) {
+      const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+      if (!has_level(t)) continue;
+      bx0 = std::min(bx0, t.x >> l); by0 = std::min(by0, t.y >> l);
+      bx1 = std::max(bx1, (t.x >> l) + level_size(t.w, l)); by1 = std::max(by1, (t.y >> l) + level_size(t.h, l));
+    }
+    if (bx1 <= bx0) break;  // no glyph reaches this level, nor a deeper one
+    const int bw = bx1 - bx0;
+    map.assign((size_t)bw * (by1 - by0), -1);
+    for (int k = 0; k < m; k++) {
+      const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+      if (!has_level(t)) continue;
+      for (int j = 0; j < level_size(t.h, l); j++)
+        for (int i = 0; i < level_size(t.w, l); i++) map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] = k;
+    }
+    for (int k = 0; k < m; k++) {
+      const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
+      if (!has_level(t)) continue;
+      uint32_t bit = t.owner_off;
+      for (int d = msdf::kOwnerLevel; d < l; d++) bit += (uint32_t)(level_size(t.w, d) * level_size(t.h, d));
+      for (int j = 0; j < level_size(t.h, l); j++)
+        for (int i = 0; i < level_size(t.w, l); i++, bit++)
+          if (map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] == k) owner[bit >> 5] |= 1u << (bit & 31u);
+    }
+  }
+  T->n_tiles = n_tiles; T->n_edges = n_edges;
+}
+// The level chain of a batch whose tables (T, of m glyphs) are in glyph_tab_ and whose images are in `field`: one blit and one minify per
+// level, whatever the glyphs' sizes -- the number of launches, which is returned, is the atlas's alone.
+int Atlas::batch_level_chain(hipStream_t s, int m, const BatchTables& T, uint32_t* field, uint32_t* spare) {
+  const msdf::BatchGlyph* d_glyphs = reinterpret_cast<const msdf::BatchGlyph*>(glyph_tab_.ptr);
+  const uint32_t* d_tiles = glyph_tab_.ptr + (size_t)m * kBatchGlyphWords;
+  const uint32_t* d_owner = d_tiles + T.n_tiles;
+  int launches = 0;
+  for (int l = 0; l < n_levels_; l++) {
+    launch_atlas_blit_batch(s, levels_[l], size_ >> l, l, d_glyphs, d_tiles, (int)T.n_tiles, d_owner, field);
+    launches++;
+    if (l + 1 == n_levels_) break;  // (a single put minifies once more, into a buffer nobody reads)
+    launch_minify2_batch(s, l, d_glyphs, d_tiles, (int)T.n_tiles, field, spare);
+    std::swap(field, spare);
+    launches++;
+  }
+  return launches;
 }
 // fdh_put_glyph_outlines (the specification: include_glyphs/figdraw_hip_glyphs.h).  What n calls of put_glyph_mtsdf do, in three passes: every glyph is
 // validated and its shape built; every glyph is placed, in order, through place(); then the glyphs that are still in the atlas -- those
@@ -328,121 +446,129 @@ void Atlas::put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int
   batch_stats_.glyphs = n;
   if (n == 0) return;
   // ---- the device buffers, for the whole batch (pass 3 takes a part of it), before any placement as every put does
-  auto level_size = [](int v, int l) { return (v + (1 << l) - 1) >> l; };
-  size_t all_tiles = 0, all_owner_words = 0;
-  for (const msdf::BatchGlyph& t : tab) {
-    all_tiles += (size_t)((t.w + 7) / 8) * ((t.h + 7) / 8);
-    size_t bits = 0;
-    for (int l = msdf::kOwnerLevel; l < kMaxMips && level_size(t.w, l) > 1 && level_size(t.h, l) > 1; l++) bits += (size_t)level_size(t.w, l) * level_size(t.h, l);
-    all_owner_words += (bits + 31) / 32;
-  }
-  constexpr size_t kGlyphWords = sizeof(msdf::BatchGlyph) / 4;
   if (device_) {
     glyph_a_.reserve((size_t)texels);
     glyph_b_.reserve((size_t)texels);
     glyph_edges_.reserve(std::max<size_t>(rec.size(), msdf::kEdgeFloats));
-    glyph_tab_.reserve((size_t)n * kGlyphWords + all_tiles + all_owner_words + 1);
+    glyph_tab_.reserve(batch_table_words(tab, true));
   }
-  // ---- pass 2: the places.  A placement that grows the atlas has dropped every entry before it: glyph i is then the first of the new atlas.
+  // ---- pass 2: the places
   int first = 0, placed = 0;
-  std::exception_ptr failed;
-  for (; placed < n; placed++) {
-    const int before = size_;
-    try {
-      const AtlasEntry& e = place(s, glyphs[placed].key, glyphs[placed].width, glyphs[placed].height, out_rects ? out_rects[placed] : nullptr);
-      tab[(size_t)placed].x = e.x; tab[(size_t)placed].y = e.y;
-    } catch (...) {  // FDH_ERR_ATLAS_FULL (or no memory for a larger atlas): the glyphs before this one get their texels, as after single calls
-      failed = std::current_exception();
-    }
-    if (size_ != before) first = placed;
-    if (failed) break;
-  }
+  std::exception_ptr failed = place_batch(s, glyphs, n, out_rects, tab, &first, &placed);
   batch_stats_.written = placed - first;
   batch_stats_.dropped_by_growth = first;
   // ---- pass 3: the texels of glyphs first .. placed - 1
   if (device_ && placed > first) {
     const int m = placed - first;
     const uint32_t edge_base = tab[(size_t)first].edge_off;
-    std::vector<uint32_t> words((size_t)m * kGlyphWords);
-    uint32_t field_off = 0, n_tiles = 0, owner_words = 0, n_edges = 0;
-    for (int k = 0; k < m; k++) {
-      msdf::BatchGlyph& t = tab[(size_t)(first + k)];
-      t.edge_off -= edge_base; t.field_off = field_off; t.first_tile = n_tiles; t.owner_off = owner_words * 32u;
-      field_off += (uint32_t)(t.w * t.h);
-      n_tiles += (uint32_t)(((t.w + 7) / 8) * ((t.h + 7) / 8));
-      n_edges += (uint32_t)t.n_edges;
-      size_t bits = 0;
-      for (int l = msdf::kOwnerLevel; l < n_levels_ && level_size(t.w, l) > 1 && level_size(t.h, l) > 1; l++) bits += (size_t)level_size(t.w, l) * level_size(t.h, l);
-      owner_words += (uint32_t)((bits + 31) / 32);
-    }
-    words.resize((size_t)m * kGlyphWords + n_tiles + owner_words + 1, 0u);
-    std::memcpy(words.data(), &tab[(size_t)first], (size_t)m * sizeof(msdf::BatchGlyph));
-    uint32_t* tile_glyph = words.data() + (size_t)m * kGlyphWords;
-    uint32_t* owner = tile_glyph + n_tiles;
-    for (int k = 0; k < m; k++) {
-      const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
-      const uint32_t end = k + 1 < m ? tab[(size_t)(first + k + 1)].first_tile : n_tiles;
-      for (uint32_t j = t.first_tile; j < end; j++) tile_glyph[j] = (uint32_t)k;
-    }
-    // the owner bits: level after level, the rectangles painted in put order into a map of the box they span
-    std::vector<int32_t> map;
-    for (int l = msdf::kOwnerLevel; l < n_levels_; l++) {
-      int bx0 = INT_MAX, by0 = INT_MAX, bx1 = 0, by1 = 0;
-      auto has_level = [&](const msdf::BatchGlyph& t) { return level_size(t.w, l) > 1 && level_size(t.h, l) > 1; };
-      for (int k = 0; k < m; k++) {
-        const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
-        if (!has_level(t)) continue;
-        bx0 = std::min(bx0, t.x >> l); by0 = std::min(by0, t.y >> l);
-        bx1 = std::max(bx1, (t.x >> l) + level_size(t.w, l)); by1 = std::max(by1, (t.y >> l) + level_size(t.h, l));
-      }
-      if (bx1 <= bx0) break;  // no glyph reaches this level, nor a deeper one
-      const int bw = bx1 - bx0;
-      map.assign((size_t)bw * (by1 - by0), -1);
-      for (int k = 0; k < m; k++) {
-        const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
-        if (!has_level(t)) continue;
-        for (int j = 0; j < level_size(t.h, l); j++)
-          for (int i = 0; i < level_size(t.w, l); i++) map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] = k;
-      }
-      for (int k = 0; k < m; k++) {
-        const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
-        if (!has_level(t)) continue;
-        uint32_t bit = t.owner_off;
-        for (int d = msdf::kOwnerLevel; d < l; d++) bit += (uint32_t)(level_size(t.w, d) * level_size(t.h, d));
-        for (int j = 0; j < level_size(t.h, l); j++)
-          for (int i = 0; i < level_size(t.w, l); i++, bit++)
-            if (map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] == k) owner[bit >> 5] |= 1u << (bit & 31u);
-      }
-    }
+    BatchTables T;
+    batch_tables(tab, first, m, true, &T);
     const float* rec_first = rec.data() + (size_t)edge_base * msdf::kEdgeFloats;
     const size_t rec_floats = rec.size() - (size_t)edge_base * msdf::kEdgeFloats;
     if (rec_floats) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec_first, rec_floats * sizeof(float), hipMemcpyHostToDevice, s));
-    FDH_HIP(hipMemcpyAsync(glyph_tab_.ptr, words.data(), words.size() * 4, hipMemcpyHostToDevice, s));
+    FDH_HIP(hipMemcpyAsync(glyph_tab_.ptr, T.words.data(), T.words.size() * 4, hipMemcpyHostToDevice, s));
     const msdf::BatchGlyph* d_glyphs = reinterpret_cast<const msdf::BatchGlyph*>(glyph_tab_.ptr);
-    const uint32_t* d_tiles = glyph_tab_.ptr + (size_t)m * kGlyphWords;
-    const uint32_t* d_owner = d_tiles + n_tiles;
+    const uint32_t* d_tiles = glyph_tab_.ptr + (size_t)m * kBatchGlyphWords;
     uint32_t *field = glyph_a_.ptr, *spare = glyph_b_.ptr;
     int launches = 1;
-    launch_msdf_generate_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)n_tiles, field);
+    launch_msdf_generate_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)T.n_tiles, field);
     if (correct) {
-      launch_msdf_correct_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)n_tiles, field, spare);
+      launch_msdf_correct_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)T.n_tiles, field, spare);
       std::swap(field, spare);
       launches++;
     }
-    for (int l = 0; l < n_levels_; l++) {  // every level, whatever the glyphs' sizes: the number of launches is the atlas's alone
-      launch_atlas_blit_batch(s, levels_[l], size_ >> l, l, d_glyphs, d_tiles, (int)n_tiles, d_owner, field);
-      launches++;
-      if (l + 1 == n_levels_) break;  // (a single put minifies once more, into a buffer nobody reads)
-      launch_minify2_batch(s, l, d_glyphs, d_tiles, (int)n_tiles, field, spare);
-      std::swap(field, spare);
-      launches++;
-    }
-    FDH_HIP(hipStreamSynchronize(s));  // (`rec` and `words` stay alive until here)
+    launches += batch_level_chain(s, m, T, field, spare);
+    FDH_HIP(hipStreamSynchronize(s));  // (`rec` and `T` stay alive until here)
     FDH_HIP(hipGetLastError());
-    batch_stats_.tiles = (int32_t)n_tiles;
-    batch_stats_.edges = (int32_t)n_edges;
+    batch_stats_.tiles = (int32_t)T.n_tiles;
+    batch_stats_.edges = (int32_t)T.n_edges;
     batch_stats_.launches = launches;
-    batch_stats_.bytes_copied = (int64_t)(rec_floats * sizeof(float) + words.size() * 4);
+    batch_stats_.bytes_copied = (int64_t)(rec_floats * sizeof(float) + T.words.size() * 4);
+  }
+  if (failed) std::rethrow_exception(failed);
+}
+// fdh_put_glyph_coverage_batch (the specification: include_glyphs/figdraw_hip_coverage.h).  What n coverage calls of put_glyph_outline do, in the three
+// passes of put_glyph_outlines: every glyph validated and its outline flattened into one array of lines; every glyph placed, in order; then
+// the glyphs still in the atlas get their texels: two launches make the coverage of all of them (k_coverage_cells_batch, k_coverage_sum_batch),
+// one filters it (k_lcd_filter_batch), and every atlas level takes one blit and one minify.  A glyph 1 texel wide or high is placed
+// and has no tiles: a single put stores nothing of it.
+void Atlas::put_glyph_coverage_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) {
+  // ---- pass 1: validation.  Nothing below this pass refuses a glyph.  (FDH_GLYPH_LCD_CONTEXT is resolved by the context.)
+  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT))
+    throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: the LCD flags only (distance fields are fdh_put_glyph_outlines')");
+  if (n < 0 || (n > 0 && !glyphs)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: bad glyph array");
+  if (n > 65535) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: at most 65535 glyphs");
+  std::vector<msdf::BatchGlyph> tab((size_t)n);  // edge_off, n_edges: the glyph's first line and its line count; orient, inv_range, step: unused
+  int64_t texels = 0, segments = 0, n_lines = 0;
+  for (int i = 0; i < n; i++) {
+    const FdhGlyphOutline& g = glyphs[i];
+    if (g.width <= 0 || g.height <= 0 || g.width > 4096 || g.height > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: image size must be in 1..4096");
+    if (g.n_segs < 0 || (g.n_segs > 0 && !g.segs)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: bad outline");
+    if (g.sdf_range) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: a coverage glyph has no distance range");
+    texels += (int64_t)g.width * g.height;
+    segments += g.n_segs;
+    if (segments > ((int64_t)1 << 20)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: at most 2^20 segments in a batch");
+    msdf::BatchGlyph& t = tab[(size_t)i];
+    t = msdf::BatchGlyph{};
+    t.w = g.width; t.h = g.height;
+    t.edge_off = (uint32_t)n_lines;
+    for (int k = 0; k < g.n_segs; k++) {
+      const float* q = g.segs + 6 * (size_t)k;
+      t.n_edges += q[2] != q[2] ? 1 : flatten_count(q);
+    }
+    n_lines += t.n_edges;
+  }
+  if (texels > ((int64_t)1 << 24)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: at most 2^24 texels in a batch");
+  if (n_lines > ((int64_t)1 << 22)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: at most 2^22 flattened lines in a batch");
+  std::vector<float> lines;  // of all glyphs, glyph after glyph (a device context only)
+  if (device_) {
+    lines.reserve((size_t)n_lines * 4);
+    for (int i = 0; i < n; i++) flatten_outline(glyphs[i].segs, glyphs[i].n_segs, &lines);
+  }
+  coverage_stats_ = FdhGlyphBatchStats{};
+  coverage_stats_.glyphs = n;
+  if (n == 0) return;
+  // ---- the device buffers, for the whole batch, before any placement as every put does
+  if (device_) {
+    glyph_a_.reserve((size_t)texels);
+    glyph_b_.reserve((size_t)texels);
+    glyph_lines_.reserve(std::max<size_t>(lines.size(), 4));
+    glyph_tab_.reserve(batch_table_words(tab, false));
+  }
+  // ---- pass 2: the places
+  int first = 0, placed = 0;
+  std::exception_ptr failed = place_batch(s, glyphs, n, out_rects, tab, &first, &placed);
+  coverage_stats_.written = placed - first;
+  coverage_stats_.dropped_by_growth = first;
+  // ---- pass 3: the texels of glyphs first .. placed - 1
+  if (device_ && placed > first) {
+    const int m = placed - first;
+    const size_t line_base = (size_t)tab[(size_t)first].edge_off * 4;
+    BatchTables T;
+    batch_tables(tab, first, m, false, &T);
+    const size_t line_floats = (size_t)T.n_edges * 4;
+    if (line_floats) FDH_HIP(hipMemcpyAsync(glyph_lines_.ptr, lines.data() + line_base, line_floats * sizeof(float), hipMemcpyHostToDevice, s));
+    FDH_HIP(hipMemcpyAsync(glyph_tab_.ptr, T.words.data(), T.words.size() * 4, hipMemcpyHostToDevice, s));
+    const msdf::BatchGlyph* d_glyphs = reinterpret_cast<const msdf::BatchGlyph*>(glyph_tab_.ptr);
+    const uint32_t* d_tiles = glyph_tab_.ptr + (size_t)m * kBatchGlyphWords;
+    uint32_t *field = glyph_a_.ptr, *spare = glyph_b_.ptr;
+    int launches = 0;
+    if (T.n_tiles) {
+      launch_coverage_batch(s, reinterpret_cast<const float4*>(glyph_lines_.ptr), d_glyphs, d_tiles, (int)T.n_tiles, reinterpret_cast<float*>(spare), field);
+      launches += 2;
+      if (flags & FDH_GLYPH_LCD_FILTER) {
+        launch_lcd_filter_batch(s, d_glyphs, d_tiles, (int)T.n_tiles, field, spare);
+        std::swap(field, spare);
+        launches++;
+      }
+      launches += batch_level_chain(s, m, T, field, spare);
+    }
+    FDH_HIP(hipStreamSynchronize(s));  // (`lines` and `T` stay alive until here)
+    FDH_HIP(hipGetLastError());
+    coverage_stats_.tiles = (int32_t)T.n_tiles;
+    coverage_stats_.edges = (int32_t)T.n_edges;
+    coverage_stats_.launches = launches;
+    coverage_stats_.bytes_copied = (int64_t)(line_floats * sizeof(float) + T.words.size() * 4);
   }
   if (failed) std::rethrow_exception(failed);
 }

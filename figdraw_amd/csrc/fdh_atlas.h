@@ -3,14 +3,16 @@
 // the atlas) and hands it over with every call; the atlas does not know the context.
 #pragma once
 #include <cstdint>
+#include <exception>
 #include <unordered_map>
 #include <vector>
 
-#include "../../include_glyphs/figdraw_hip_glyphs.h"  // FdhGlyphOutline, FdhGlyphBatchStats
+#include "../../include_glyphs/figdraw_hip_coverage.h"  // FdhGlyphOutline, FdhGlyphBatchStats (figdraw_hip_glyphs.h) and the coverage batch
 #include "fdh_memory.h"  // DeviceBuf
 #include "fdh_types.h"   // AtlasView, kMaxMips
 
 namespace fdh {
+namespace msdf { struct BatchGlyph; }  // fdh_msdf_host.h: one glyph of a batch as the batched kernels read it
 
 // An atlas entry and, when its level-0 texels were seen on the host (fdh_put_image), the bounds of what is IN it: for eight
 // levels t = 0, 16, .. 112 the box (entry-relative texels, x1 / y1 exclusive) of texels whose alpha, and whose largest colour
@@ -52,6 +54,9 @@ class Atlas {
   // fdh_put_glyph_outlines (the specification: include_glyphs/figdraw_hip_glyphs.h): n distance fields, validated as a whole, placed in order, made in one go
   void put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
   const FdhGlyphBatchStats& glyph_batch_stats() const { return batch_stats_; }
+  // fdh_put_glyph_coverage_batch (the specification: include_glyphs/figdraw_hip_coverage.h): n coverage glyphs, validated as a whole, placed in order, made in one go
+  void put_glyph_coverage_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
+  const FdhGlyphBatchStats& glyph_coverage_batch_stats() const { return coverage_stats_; }
   void put_mips(hipStream_t s, int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]);
   void put_flippy(hipStream_t s, int64_t key, const uint8_t* data, size_t n, int out_rect[4]);
   void update_image(int64_t key, int w, int h, const uint8_t* rgba);
@@ -69,6 +74,12 @@ class Atlas {
   void put_levels(int x, int y, int w, int h, const uint8_t* rgba);
   void glyph_to_atlas(hipStream_t s, uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags);
   void put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, float range, bool correct, bool overlap, int out_rect[4]);
+  // what the two batch calls share (fdh_atlas.cpp): the size of the tables, the placement pass, the tables, the level chain
+  struct BatchTables { std::vector<uint32_t> words; uint32_t n_tiles = 0, n_edges = 0; };  // words: glyph records, tile -> glyph, owner bits
+  static size_t batch_table_words(const std::vector<msdf::BatchGlyph>& tab, bool thin_tiles);
+  std::exception_ptr place_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, int (*out_rects)[4], std::vector<msdf::BatchGlyph>& tab, int* first, int* placed);
+  void batch_tables(std::vector<msdf::BatchGlyph>& tab, int first, int m, bool thin_tiles, BatchTables* T) const;
+  int batch_level_chain(hipStream_t s, int m, const BatchTables& T, uint32_t* field, uint32_t* spare);
 
   bool device_ = false;
   int size_ = 0, initial_size_ = 0, margin_ = 4, n_levels_ = 0;
@@ -79,7 +90,7 @@ class Atlas {
   DeviceBuf<uint32_t> glyph_a_, glyph_b_;  // the device glyph pipeline: the raster and its filtered / minified successors
   DeviceBuf<float> glyph_lines_, glyph_acc_, glyph_edges_;  // flattened outline, area accumulators; the edge records of a distance field (fdh_msdf_host.h)
   DeviceBuf<uint32_t> glyph_tab_;  // put_glyph_outlines: the glyph records (msdf::BatchGlyph), the tile -> glyph words, the owner bits of the deep levels
-  FdhGlyphBatchStats batch_stats_ = {};
+  FdhGlyphBatchStats batch_stats_ = {}, coverage_stats_ = {};  // of the last put_glyph_outlines, of the last put_glyph_coverage_batch
 };
 
 }  // namespace fdh

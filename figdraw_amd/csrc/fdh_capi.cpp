@@ -10,6 +10,7 @@
 #include "../../include/figdraw_hip_stream.h"
 #include "../../include/figdraw_hip_exact.h"
 #include "../../include_glyphs/figdraw_hip_glyphs.h"
+#include "../../include_glyphs/figdraw_hip_coverage.h"
 
 using fdh::Context;
 
@@ -186,6 +187,15 @@ int fdh_glyph_batch_stats(FdhContext* c, FdhGlyphBatchStats* out) {
   });
 }
 int fdh_sizeof_glyph_outline(void) { return (int)sizeof(FdhGlyphOutline); }
+int fdh_put_glyph_coverage_batch(FdhContext* c, const FdhGlyphOutline* glyphs, int n_glyphs, uint32_t flags, int (*out_rects)[4]) {
+  return guard([&] { C(c)->put_glyph_coverage_batch(glyphs, n_glyphs, flags, out_rects); });
+}
+int fdh_glyph_coverage_batch_stats(FdhContext* c, FdhGlyphBatchStats* out) {
+  return guard([&] {
+    if (!out) throw fdh::Error(FDH_ERR_INVALID, "fdh_glyph_coverage_batch_stats: null pointer");
+    *out = C(c)->glyph_coverage_batch_stats();
+  });
+}
 int fdh_has_image(FdhContext* c, int64_t key, int* out) { return guard([&] { *out = C(c)->has_image(key) ? 1 : 0; }); }
 int fdh_reset_atlas(FdhContext* c, int minimum_size) { return guard([&] { C(c)->reset_atlas(minimum_size); }); }
 int fdh_atlas_size(FdhContext* c, int* out) { return guard([&] { *out = C(c)->atlas_size(); }); }

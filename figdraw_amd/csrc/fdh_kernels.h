@@ -149,6 +149,12 @@ void launch_msdf_correct_batch(hipStream_t s, bool overlap, const float* edges, 
 void launch_atlas_blit_batch(hipStream_t s, uint32_t* level, int LS, int l, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* owner,
                              const uint32_t* src);
 void launch_minify2_batch(hipStream_t s, int l, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* src, uint32_t* dst);
+// fdh_put_glyph_coverage_batch (include_glyphs/figdraw_hip_coverage.h): the coverage of every glyph of a batch, over the same tables -- a glyph's edge_off /
+// n_edges are its first flattened line (x0, y0, x1, y1) in `lines` and its line count.  Two launches: the area cells of all tiles into
+// `acc` (floats, laid out like the fields: the spare field buffer), then each row's running sum and the texels into `out`.  The LCD filter
+// of every glyph, from `src` into `dst`.  Bit for bit what launch_rasterize_lines and launch_lcd_filter make of each glyph.
+void launch_coverage_batch(hipStream_t s, const float4* lines, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, float* acc, uint32_t* out);
+void launch_lcd_filter_batch(hipStream_t s, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* src, uint32_t* dst);
 // The frame upload (k_upload_frame): a table of runs, each `bytes` of pinned host memory (its device view) going to byte offset
 // dst_off of the frame block.  kind 0: 16-byte units; 1: BinRecs -- copied in 8-byte units, and the lane that carries a record's
 // pixel bounds also writes the draw's 4-byte bin box; 2: DrawRecs -- 16-byte units, and the `ext` of every F_GENERAL record gets

@@ -196,6 +196,155 @@ void launch_minify2_batch(hipStream_t s, int l, const msdf::BatchGlyph* glyphs, 
   if (n_tiles > 0) hipLaunchKernelGGL(k_minify2_batch, dim3(n_tiles), dim3(64), 0, s, l, glyphs, tile_glyph, src, dst);
 }
 
+// ------------------------------------------------------------------ fdh_put_glyph_coverage_batch: the coverage glyphs of a batch at once
+// (the specification: include_glyphs/figdraw_hip_coverage.h).  The tables are the distance-field batch's: one msdf::BatchGlyph per glyph -- edge_off and
+// n_edges are the glyph's first flattened line and its line count in `lines` --, one word per 8 x 8 tile naming the tile's glyph, the
+// glyphs' w x h images one after the other in the two field buffers.  k_rasterize_lines SCATTERS: a lane owns a row and every line adds to
+// the cells x0i .. x1i of that row.  Here a lane owns one accumulator cell (x, y) and GATHERS: it walks the glyph's lines in the same order
+// and adds what raster_row_line would add to acc[x] of row y -- the same expressions, picked by where x lies in [x0i, x1i].  A line adds
+// to a cell at most once, so the cell's value is the same sequence of float additions and the same bits; it lives in a register and is
+// stored once (as a float, into the glyph's region of the spare field buffer).  Cells x >= w are never read by the running sum: they do
+// not exist here.  The line index is the loop counter, the tile and the glyph depend on blockIdx alone: scalar loads, wave-uniform culls.
+__device__ __forceinline__ void coverage_cell_line(float& acc, int w, int x, int y, float x0, float y0, float x1, float y1) {
+#pragma clang fp contract(off)
+  if (y0 == y1) return;
+  float dir = 1.0f;
+  if (y0 > y1) { float t = x0; x0 = x1; x1 = t; t = y0; y0 = y1; y1 = t; dir = -1.0f; }
+  const float ya = y0 > (float)y ? y0 : (float)y, yb = y1 < (float)(y + 1) ? y1 : (float)(y + 1);
+  if (!(yb > ya)) return;
+  const float dxdy = (x1 - x0) / (y1 - y0);
+  const float xa = x0 + (ya - y0) * dxdy, xb = x0 + (yb - y0) * dxdy;
+  const float d = (yb - ya) * dir;
+  float xl = xa < xb ? xa : xb, xr = xa < xb ? xb : xa;
+  if (xl < 0.0f) xl = 0.0f;
+  if (xr < 0.0f) xr = 0.0f;
+  if (xl > (float)w) xl = (float)w;
+  if (xr > (float)w) xr = (float)w;
+  const float x0floor = __builtin_floorf(xl);
+  const int x0i = (int)x0floor;
+  const float x1ceil = __builtin_ceilf(xr);
+  const int x1i = (int)x1ceil;
+  if (x < x0i) return;
+  if (x1i <= x0i + 1) {  // narrow: cells x0i and x0i + 1
+    if (x > x0i + 1) return;
+    const float xmf = 0.5f * (xl + xr) - x0floor;
+    if (x == x0i) acc += d - d * xmf;
+    else acc += d * xmf;
+  } else {               // wide: cells x0i .. x1i
+    if (x > x1i) return;
+    const float s = 1.0f / (xr - xl);
+    const float x0f = xl - x0floor;
+    const float a0 = 0.5f * s * (1.0f - x0f) * (1.0f - x0f);
+    const float x1f = xr - x1ceil + 1.0f;
+    const float am = 0.5f * s * x1f * x1f;
+    if (x == x0i) acc += d * a0;
+    else if (x == x1i) acc += d * am;
+    else if (x1i == x0i + 2) acc += d * (1.0f - a0 - am);
+    else {
+      const float a1 = s * (1.5f - x0f);
+      if (x == x0i + 1) acc += d * (a1 - a0);
+      else if (x == x1i - 1) {
+        const float a2 = a1 + (float)(x1i - x0i - 3) * s;
+        acc += d * (1.0f - a2 - am);
+      } else acc += d * s;
+    }
+  }
+}
+// One workgroup per tile, one lane per cell.  A line is skipped for the whole tile where no row of the tile can take anything from it:
+// its y-range misses the tile's 8 rows (yb > ya fails in every row), or -- coordinates up to 2^16 in size -- its x-range, clamped to
+// [0, w] as raster_row_line clamps, ends more than 2 cells left of the tile or starts 9 or more cells right of its first column.  (A row's xa and
+// xb are x0 + (y - y0) * dxdy with 0 <= y - y0 <= y1 - y0: within [min(x0, x1), max(x0, x1)] but for rounding, which at that size stays below
+// 0.06; the cells a row touches end at ceil(xr) or x0i + 1 and start at floor(xl): a whole cell of slack on either side.)  Lines left
+// of a tile reach it through the running sum, not through its cells.
+__global__ __launch_bounds__(64) void k_coverage_cells_batch(const float4* __restrict__ lines, const msdf::BatchGlyph* __restrict__ glyphs,
+                                                             const uint32_t* __restrict__ tile_glyph, float* __restrict__ acc) {
+#pragma clang fp contract(off)
+  const msdf::BatchGlyph g = glyphs[tile_glyph[blockIdx.x]];
+  const int tile = (int)(blockIdx.x - g.first_tile), tiles_x = (g.w + 7) / 8;
+  const int ty0 = tile / tiles_x * 8, tx0 = (tile - tile / tiles_x * tiles_x) * 8;
+  const int x = tx0 + (int)(threadIdx.x & 7), y = ty0 + (int)(threadIdx.x >> 3);
+  if (x >= g.w || y >= g.h) return;
+  const float4* __restrict__ ln = lines + g.edge_off;
+  const float fw = (float)g.w, left = (float)(tx0 - 2), right = (float)(tx0 + 9), top = (float)ty0, bottom = (float)(ty0 + 8);
+  float a = 0.0f;
+  for (int i = 0; i < g.n_edges; i++) {
+    const float4 l = ln[i];
+    const float ylo = l.y < l.w ? l.y : l.w, yhi = l.y < l.w ? l.w : l.y;
+    if (!(yhi > top) || !(ylo < bottom)) continue;
+    float xlo = l.x < l.z ? l.x : l.z, xhi = l.x < l.z ? l.z : l.x;
+    if (xlo >= -65536.0f && xhi <= 65536.0f) {
+      if (xlo < 0.0f) xlo = 0.0f;
+      if (xhi < 0.0f) xhi = 0.0f;
+      if (xlo > fw) xlo = fw;
+      if (xhi > fw) xhi = fw;
+      if (xhi < left || xlo >= right) continue;
+    }
+    coverage_cell_line(a, g.w, x, y, l.x, l.y, l.z, l.w);
+  }
+  acc[g.field_off + (size_t)y * g.w + x] = a;
+}
+// The second half of k_rasterize_lines, `sum += acc[x]` from left to right: a float recurrence that keeps its order.  The first tile of
+// every 8-row band of a glyph does the band (the other workgroups leave at once): lane (row, column) walks the tiles from left to right
+// and carries its row's sum across them; inside a tile every lane of a row makes the same 8 additions and keeps the sum as it stood after
+// its own column -- cell x's coverage is (((a0 + a1) + a2) .. + ax), as in the single kernel, and a store covers 8 neighbouring texels.
+__global__ __launch_bounds__(64) void k_coverage_sum_batch(const msdf::BatchGlyph* __restrict__ glyphs, const uint32_t* __restrict__ tile_glyph,
+                                                           const float* __restrict__ acc, uint32_t* __restrict__ out) {
+#pragma clang fp contract(off)
+  const msdf::BatchGlyph g = glyphs[tile_glyph[blockIdx.x]];
+  const int tile = (int)(blockIdx.x - g.first_tile), tiles_x = (g.w + 7) / 8;
+  const int band = tile / tiles_x;
+  if (tile != band * tiles_x) return;
+  const int c = (int)(threadIdx.x & 7), y = band * 8 + (int)(threadIdx.x >> 3);
+  if (y >= g.h) return;
+  const float* __restrict__ row = acc + g.field_off + (size_t)y * g.w;
+  uint32_t* __restrict__ orow = out + g.field_off + (size_t)y * g.w;
+  float sum = 0.0f;
+  for (int x0 = 0; x0 < g.w; x0 += 8) {
+    float mine = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      if (x0 + k < g.w) {
+        sum += row[x0 + k];
+        if (k == c) mine = sum;
+      }
+    }
+    if (x0 + c < g.w) {
+      float cov = __builtin_fabsf(mine);
+      if (cov > 1.0f) cov = 1.0f;
+      const uint32_t v = (uint32_t)(cov * 255.0f + 0.5f);
+      orow[x0 + c] = v * 0x01010101u;
+    }
+  }
+}
+// (k_lcd_filter as a function of the texel, for k_lcd_filter_batch; k_lcd_filter itself stays as it was compiled)
+__device__ __forceinline__ void lcd_filter_texel(const uint32_t* src, uint32_t* dst, int w, int x, int y) {
+  const int wt[5] = {8, 77, 86, 77, 8};
+  int sr = 0, sg = 0, sb = 0, sa = 0;
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    const int sx = min(max(x + i - 2, 0), w - 1);
+    const uint32_t p = src[(size_t)y * w + sx];
+    sr += (int)(p & 255u) * wt[i]; sg += (int)((p >> 8) & 255u) * wt[i]; sb += (int)((p >> 16) & 255u) * wt[i]; sa += (int)(p >> 24) * wt[i];
+  }
+  dst[(size_t)y * w + x] = (uint32_t)(((sr + 128) >> 8) & 255) | ((uint32_t)(((sg + 128) >> 8) & 255) << 8) |
+                           ((uint32_t)(((sb + 128) >> 8) & 255) << 16) | ((uint32_t)(((sa + 128) >> 8) & 255) << 24);
+}
+// every glyph of the batch from one field buffer into the other, columns clamped to the glyph's own width
+__global__ __launch_bounds__(64) void k_lcd_filter_batch(const msdf::BatchGlyph* __restrict__ glyphs, const uint32_t* __restrict__ tile_glyph,
+                                                         const uint32_t* __restrict__ src, uint32_t* __restrict__ dst) {
+  const BatchTile t = batch_tile(glyphs, tile_glyph, 0);
+  if (t.i >= t.g.w || t.j >= t.g.h) return;
+  lcd_filter_texel(src + t.g.field_off, dst + t.g.field_off, t.g.w, t.i, t.j);
+}
+void launch_coverage_batch(hipStream_t s, const float4* lines, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, float* acc, uint32_t* out) {
+  if (n_tiles <= 0) return;
+  hipLaunchKernelGGL(k_coverage_cells_batch, dim3(n_tiles), dim3(64), 0, s, lines, glyphs, tile_glyph, acc);
+  hipLaunchKernelGGL(k_coverage_sum_batch, dim3(n_tiles), dim3(64), 0, s, glyphs, tile_glyph, acc, out);
+}
+void launch_lcd_filter_batch(hipStream_t s, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* src, uint32_t* dst) {
+  if (n_tiles > 0) hipLaunchKernelGGL(k_lcd_filter_batch, dim3(n_tiles), dim3(64), 0, s, glyphs, tile_glyph, src, dst);
+}
+
 __global__ void k_fill_u32(uint32_t* p, uint32_t v, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;

@@ -259,7 +259,8 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  * NaN; contours closed, non-zero winding.  Sub-pixel variants are the same outline shifted by variant / steps in x
  * (pixie_raster.nim:69-72).  Coverage = exact-area scanline accumulation (curves flattened to <= 0.025 px chord error), stored
  * premultiplied white like pixie's white paint; flags as for fdh_put_glyph_image.  pixie's own texels are third-party and
- * unpinned: the oracle restates the same published algorithm and the two agree bit for bit. */
+ * unpinned: the oracle restates the same published algorithm and the two agree bit for bit.
+ * Many coverage glyphs in one call, the same texels from launches whose number does not depend on theirs: include_glyphs/figdraw_hip_coverage.h. */
 /* DISTANCE FIELDS.  With flags = FDH_GLYPH_MTSDF | FDH_GLYPH_SDF_RANGE(R) the same call stores, instead of coverage, the width x height
  * RGBA8 image that fdh_draw_msdf(key, ..., px_range = R, sd_threshold = 0.5, mtsdf = 0 or 1) expects -- what the reference gets at run time
  * from the third-party sdfy (generateMsdfPath / generateMtsdfPath, examples/windy_msdf_star.nim:279-286).  R, G, B hold the three channels'
