@@ -124,6 +124,8 @@ def load():
         L.fdh_put_glyph_outlines.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
         L.fdh_glyph_batch_stats.argtypes = [vp, C.POINTER(GlyphBatchStats)]
         L.fdh_sizeof_glyph_outline.argtypes = []
+    if hasattr(L, "fdh_put_glyph_outline_cubic"):  # include_glyphs/figdraw_hip_cubic.h
+        L.fdh_put_glyph_outline_cubic.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, C.c_uint32, C.c_int * 4]
     if hasattr(L, "fdh_put_glyph_coverage_batch"):  # include_glyphs/figdraw_hip_coverage.h
         L.fdh_put_glyph_coverage_batch.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
         L.fdh_glyph_coverage_batch_stats.argtypes = [vp, C.POINTER(GlyphBatchStats)]
@@ -373,6 +375,16 @@ class HipContext:
         out = (C.c_int * 4)()
         flags = (1 if lcd_filter else 0) | (4 if mtsdf else 0) | (8 if correct else 0) | (32 if overlap else 0) | (int(sdf_range) << 8)
         self._ck(self.L.fdh_put_glyph_outline(self.h, int(key), int(w), int(h), segs.ctypes.data, len(segs), flags, out))
+        return tuple(out)
+
+    def put_glyph_outline_cubic(self, key, segs8: np.ndarray, w: int, h: int, lcd_filter=False, mtsdf: bool = False, sdf_range: int = 0, correct: bool = False):
+        """a glyph outline with cubic segments (fdh_put_glyph_outline_cubic, include_glyphs/figdraw_hip_cubic.h): n x 8 floats x0, y0, c1x, c1y,
+        c2x, c2y, x1, y1; c2x = NaN: a quadratic with control point (c1x, c1y); c1x = NaN: a line.  lcd_filter as in put_glyph_image (True,
+        False or "context"); mtsdf, sdf_range and correct as in put_glyph_outline.  -> the rectangle (x, y, w, h)"""
+        segs = np.ascontiguousarray(segs8, dtype=np.float32).reshape(-1, 8)
+        out = (C.c_int * 4)()
+        flags = (2 if lcd_filter == "context" else (1 if lcd_filter else 0)) | (4 if mtsdf else 0) | (8 if correct else 0) | (int(sdf_range) << 8)
+        self._ck(self.L.fdh_put_glyph_outline_cubic(self.h, int(key), int(w), int(h), segs.ctypes.data if len(segs) else None, len(segs), flags, out))
         return tuple(out)
 
     def put_glyph_outlines(self, items, sdf_range: int = 0, correct: bool = False, overlap: bool = False):

@@ -1,6 +1,7 @@
 // fdh_atlas.cpp -- class Atlas (fdh_atlas.h), the image atlas: directory and skyline packer, level chains, glyph images and outlines, the Flippy container.
 #include "fdh_context.h"
 #include "fdh_msdf_host.h"
+#include "fdh_msdf_cubic_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -239,6 +240,10 @@ void Atlas::put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const fl
   std::vector<float> lines;
   lines.reserve((size_t)n * 16);
   flatten_outline(segs, n, &lines);
+  put_glyph_lines(s, key, w, h, lines, flags, out_rect);
+}
+// a coverage glyph from its flattened outline: packed, rasterised, filtered, its level chain built
+void Atlas::put_glyph_lines(hipStream_t s, int64_t key, int w, int h, const std::vector<float>& lines, uint32_t flags, int out_rect[4]) {
   const size_t npx = (size_t)w * h, m = lines.size() / 4;
   if (device_) {
     glyph_a_.reserve(npx);
@@ -282,6 +287,59 @@ void Atlas::put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const floa
   // The level chain (updateSubImage's, textures.nim:106-119) stores nothing of an image 1 texel wide or high, not even level 0.  A field is
   // sampled at level 0 alone, and these texels have no other home: such a field gets that level.
   if (w == 1 || h == 1) launch_atlas_blit(s, levels_[0], size_, x, y, field, w, h);
+  glyph_to_atlas(s, field, spare, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
+}
+// fdh_put_glyph_outline_cubic (the specification: include_glyphs/figdraw_hip_cubic.h): put_glyph_outline for segments of 8 floats.  Without a cubic
+// among them it IS that call, on the same segments in its format.  With one: coverage flattens the cubics on the host too and goes the
+// coverage put's way; a distance field goes put_glyph_mtsdf's way with the records and the kernels that know cubics (fdh_msdf_cubic_host.h,
+// k_msdf_cubic.hip).  Everything is validated before anything is packed.
+void Atlas::put_glyph_outline_cubic(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) {
+  namespace mc = msdf::cubic;
+  if (n < 0 || (n > 0 && !segs)) throw Error(FDH_ERR_INVALID, "put_glyph_outline_cubic: bad outline");
+  if (!mc::holds_cubic(segs, n)) {
+    std::vector<float> six;
+    mc::to_quadratic_format(segs, n, &six);
+    static const float none[6] = {};
+    put_glyph_outline(s, key, w, h, n > 0 ? six.data() : none, n, flags, out_rect);
+    return;
+  }
+  if (w <= 0 || h <= 0 || w > 4096 || h > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_outline_cubic: image size must be in 1..4096");
+  if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT | FDH_GLYPH_MTSDF | FDH_GLYPH_MTSDF_CORRECT | FDH_GLYPH_MTSDF_OVERLAP | 0xFF00u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline_cubic: unknown flag");
+  const uint32_t sdf_range = (flags >> 8) & 255u;
+  if (sdf_range && (!(flags & FDH_GLYPH_MTSDF) || sdf_range > 64u)) throw Error(FDH_ERR_INVALID, "put_glyph_outline_cubic: a distance range needs FDH_GLYPH_MTSDF and is at most 64");
+  if ((flags & FDH_GLYPH_MTSDF_CORRECT) && !(flags & FDH_GLYPH_MTSDF)) throw Error(FDH_ERR_INVALID, "put_glyph_outline_cubic: FDH_GLYPH_MTSDF_CORRECT needs FDH_GLYPH_MTSDF");
+  if (flags & FDH_GLYPH_MTSDF_OVERLAP) throw Error(FDH_ERR_INVALID, "put_glyph_outline_cubic: FDH_GLYPH_MTSDF_OVERLAP takes no cubic segment");
+  const size_t npx = (size_t)w * h;
+  if (!(flags & FDH_GLYPH_MTSDF)) {  // coverage: put_glyph_outline's path on the lines of this outline
+    std::vector<float> lines;
+    lines.reserve((size_t)n * 16);
+    mc::flatten_outline(segs, n, &lines);
+    put_glyph_lines(s, key, w, h, lines, flags, out_rect);
+    return;
+  }
+  if (flags & (FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT)) throw Error(FDH_ERR_INVALID, "put_glyph_outline_cubic: a distance field takes no LCD filter");
+  if (n > msdf::kMaxSegments) throw Error(FDH_ERR_INVALID, "put_glyph_outline_cubic: a distance field takes at most 65535 segments");
+  const float range = sdf_range ? (float)sdf_range : 4.0f;
+  mc::Shape shape;
+  if (!mc::build_shape(segs, n, &shape)) throw Error(FDH_ERR_INVALID, "put_glyph_outline_cubic: a distance field needs closed contours");
+  std::vector<float> rec;
+  if (device_) {
+    mc::edge_records(shape, &rec);
+    glyph_a_.reserve(npx);
+    glyph_b_.reserve(npx);
+    glyph_edges_.reserve(std::max<size_t>(rec.size(), mc::kCubicEdgeFloats));
+  }
+  const AtlasEntry& e = place(s, key, w, h, out_rect);
+  if (!device_) return;
+  const int x = e.x, y = e.y;
+  if (!rec.empty()) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  uint32_t *field = glyph_a_.ptr, *spare = glyph_b_.ptr;
+  launch_msdf_generate_cubic(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, field);
+  if (flags & FDH_GLYPH_MTSDF_CORRECT) {
+    launch_msdf_correct_cubic(s, glyph_edges_.ptr, (int)shape.edges.size(), w, h, (float)shape.orient, range, field, spare);
+    std::swap(field, spare);
+  }
+  if (w == 1 || h == 1) launch_atlas_blit(s, levels_[0], size_, x, y, field, w, h);  // (as in put_glyph_mtsdf: such a field gets level 0)
   glyph_to_atlas(s, field, spare, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
 }
 // ---- what the two batch calls share (put_glyph_outlines and put_glyph_coverage_batch below)

@@ -7,6 +7,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../include_glyphs/figdraw_hip_cubic.h"  // fdh_put_glyph_outline_cubic
 #include "../../include_glyphs/figdraw_hip_coverage.h"  // FdhGlyphOutline, FdhGlyphBatchStats (figdraw_hip_glyphs.h) and the coverage batch
 #include "fdh_memory.h"  // DeviceBuf
 #include "fdh_types.h"   // AtlasView, kMaxMips
@@ -51,6 +52,8 @@ class Atlas {
   void put_image(hipStream_t s, int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]);
   void put_glyph_image(hipStream_t s, int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]);
   void put_glyph_outline(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]);
+  // fdh_put_glyph_outline_cubic (the specification: include_glyphs/figdraw_hip_cubic.h): put_glyph_outline for segments of 8 floats, cubics among them
+  void put_glyph_outline_cubic(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]);
   // fdh_put_glyph_outlines (the specification: include_glyphs/figdraw_hip_glyphs.h): n distance fields, validated as a whole, placed in order, made in one go
   void put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
   const FdhGlyphBatchStats& glyph_batch_stats() const { return batch_stats_; }
@@ -73,6 +76,7 @@ class Atlas {
   void upload_rect(int level, int x, int y, int w, int h, const uint8_t* rgba);
   void put_levels(int x, int y, int w, int h, const uint8_t* rgba);
   void glyph_to_atlas(hipStream_t s, uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags);
+  void put_glyph_lines(hipStream_t s, int64_t key, int w, int h, const std::vector<float>& lines, uint32_t flags, int out_rect[4]);
   void put_glyph_mtsdf(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, float range, bool correct, bool overlap, int out_rect[4]);
   // what the two batch calls share (fdh_atlas.cpp): the size of the tables, the placement pass, the tables, the level chain
   struct BatchTables { std::vector<uint32_t> words; uint32_t n_tiles = 0, n_edges = 0; };  // words: glyph records, tile -> glyph, owner bits

@@ -11,6 +11,7 @@
 #include "../../include/figdraw_hip_exact.h"
 #include "../../include_glyphs/figdraw_hip_glyphs.h"
 #include "../../include_glyphs/figdraw_hip_coverage.h"
+#include "../../include_glyphs/figdraw_hip_cubic.h"
 
 using fdh::Context;
 
@@ -177,6 +178,9 @@ int fdh_update_image(FdhContext* c, int64_t key, int w, int h, const uint8_t* rg
   return guard([&] { C(c)->update_image(key, w, h, rgba); });
 }
 int fdh_remove_image(FdhContext* c, int64_t key) { return guard([&] { C(c)->remove_image(key); }); }
+int fdh_put_glyph_outline_cubic(FdhContext* c, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) {
+  return guard([&] { C(c)->put_glyph_outline_cubic(key, w, h, segs, n, flags, out_rect); });
+}
 int fdh_put_glyph_outlines(FdhContext* c, const FdhGlyphOutline* glyphs, int n_glyphs, uint32_t flags, int (*out_rects)[4]) {
   return guard([&] { C(c)->put_glyph_outlines(glyphs, n_glyphs, flags, out_rects); });
 }

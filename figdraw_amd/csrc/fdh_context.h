@@ -145,6 +145,7 @@ class Context : public Recorder {
   void put_mips(int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]) { sync(); atlas_.put_mips(stream_, key, n, ws, hs, premul_rgba, out_rect); }
   void put_flippy(int64_t key, const uint8_t* data, size_t n, int out_rect[4]) { sync(); atlas_.put_flippy(stream_, key, data, n, out_rect); }
   void remove_image(int64_t key) { atlas_.remove(key); }
+  void put_glyph_outline_cubic(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) { sync(); atlas_.put_glyph_outline_cubic(stream_, key, w, h, segs, n, resolve_lcd(flags), out_rect); }
   void put_glyph_outlines(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_outlines(stream_, glyphs, n, flags, out_rects); }
   const FdhGlyphBatchStats& glyph_batch_stats() const { return atlas_.glyph_batch_stats(); }
   void put_glyph_coverage_batch(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_coverage_batch(stream_, glyphs, n, resolve_lcd(flags), out_rects); }

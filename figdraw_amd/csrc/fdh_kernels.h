@@ -137,6 +137,10 @@ void launch_msdf_correct(hipStream_t s, const float* edges, int n_edges, int w, 
 // records are the same, slot 15 of a contour's last one says where it ends and whether it is filled (+1) or a hole (-1)
 void launch_msdf_generate_union(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, uint32_t* out);
 void launch_msdf_correct_union(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out);
+// fdh_put_glyph_outline_cubic (include_glyphs/figdraw_hip_cubic.h; k_msdf_cubic.hip): launch_msdf_generate and launch_msdf_correct for an outline
+// that holds cubic segments -- n_edges records of msdf::cubic::kCubicEdgeFloats floats (fdh_msdf_cubic_host.h): lines, quadratics and cubics
+void launch_msdf_generate_cubic(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, uint32_t* out);
+void launch_msdf_correct_cubic(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out);
 // fdh_put_glyph_outlines (include_glyphs/figdraw_hip_glyphs.h): the launches above and the level chain for a batch of glyphs at once.  `glyphs`: one
 // msdf::BatchGlyph each (fdh_msdf_host.h); `tile_glyph`: the glyph of each of the n_tiles 8 x 8 tiles, the 1-D grid of every launch here; the
 // edge records of all glyphs in `edges`, their fields one after the other in `out` / `in` / `src` / `dst`.  `overlap`: step 6's kernels.

@@ -10,3 +10,4 @@
 #include "k_damage_codec.hip"
 #include "k_damage_filter.hip"
 #include "k_msdf.hip"
+#include "k_msdf_cubic.hip"

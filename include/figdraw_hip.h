@@ -353,7 +353,7 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  * Out of scope: the rest of msdfgen's error correction -- artefacts that need all four texels of a bilinear cell to show (the median
  *    inverting on a diagonal while no pair along x or y inverts), and corner protection (step 5 does not look for corners: near one, where
  *    the channels must disagree, it relies on the verdict alone) --, a hole outside every filled contour and a contour that crosses
- *    itself (see step 6), cubic segments (the outline format has none).
+ *    itself (see step 6), cubic segments (this call's outline format has none: ../include_glyphs/figdraw_hip_cubic.h is the call that takes them).
  * Many glyphs at once: ../include_glyphs/figdraw_hip_glyphs.h -- a batch of these calls from a number of launches that does not depend on the number of glyphs. */
 FDH_API int fdh_put_glyph_outline(FdhContext*, int64_t key, int width, int height, const float* segs, int n_segs, uint32_t flags, int out_rect[4]);
 /* putFlippy (glcontext.nim:610-620): `bytes` is a whole .flippy file (common/formatflippy.nim:77-149: "flip", version 1, then per

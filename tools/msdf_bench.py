@@ -14,6 +14,12 @@ k_msdf_correct, and with FDH_GLYPH_MTSDF_OVERLAP k_msdf_generate_union), on an M
                                                the font set as ONE fdh_put_glyph_outlines (include_glyphs/figdraw_hip_glyphs.h) against 106 single puts
                                                of the parent commit's library, per flag combination, alternating, N passes each (default 2);
                                                then the batch's kernels from a rocprofv3 run of its own; writes section 6's table
+  msdf_bench.py --cubic OUT [--passes N]      the font set with every quadratic skewed into a cubic (tests/msdf_cubic_cases.py), three ways: native
+                                               through fdh_put_glyph_outline_cubic; (a) each cubic cut into four quadratics; (b) each cubic
+                                               flattened to lines at 0.025 px, both through fdh_put_glyph_outline.  Per leg the host clock around
+                                               the set, the generator's device time from a rocprofv3 run of its own, and the largest texel
+                                               difference from the float64 cubic reference; writes section 7's table
+  msdf_bench.py --time-cubic LEG | --trace-cubic LEG | --error-cubic LEG     one step of --cubic (LEG: native, quadratics, lines); one JSON line
   msdf_bench.py --time CASE [--correct] [--overlap] [--batched]    the whole call on the host clock, profiler off: 200 timed calls after 20; one JSON line
   msdf_bench.py --trace CASE [--correct] [--overlap] [--batched] [--calls N]   N calls (run it under rocprofv3 --kernel-trace --stats -f csv); one JSON line
                                                --batched: a call is one fdh_put_glyph_outlines of the case's puts
@@ -191,6 +197,162 @@ def run_all(out_path, nocull_lib, trace_dir, parent_lib=None, passes=1, cases=tu
     return 0 if ok else 1
 
 
+# ---------------------------------------------------------------------------------------------------- cubic outlines
+CUBIC_LEGS = ("native", "quadratics", "lines")
+
+
+def _split_cubic(P, t):
+    """de Casteljau at t -> the two halves, (4, 2) each"""
+    a, b, c = P[0] + (P[1] - P[0]) * t, P[1] + (P[2] - P[1]) * t, P[2] + (P[3] - P[2]) * t
+    d, e = a + (b - a) * t, b + (c - b) * t
+    m = d + (e - d) * t
+    return [P[0], a, d, m], [m, e, c, P[3]]
+
+
+def cubic_puts(leg):
+    """-> [(segs, w, h, R)] of the skewed font set: 8-float outlines for `native`; 6-float outlines for `quadratics` (each cubic cut at 1/4,
+    1/2, 3/4 and each part replaced by the quadratic with control point (3 (Q1 + Q2) - (Q0 + Q3)) / 4, the midpoint approximation) and for
+    `lines` (each cubic in the coverage path's chords of 0.025 px)"""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import msdf_cubic_cases as CC
+
+    out = []
+    nan = float("nan")
+    for _, segs, w, h, R in CC.skewed():
+        if leg == "native":
+            out.append((segs, w, h, R))
+            continue
+        rows = []
+        for q in segs.astype(np.float64):
+            if np.isnan(q[2]) or np.isnan(q[4]):
+                rows.append([q[0], q[1], q[2], q[3], q[6], q[7]])
+            elif leg == "lines":
+                rows += [[x0, y0, nan, nan, x1, y1] for x0, y0, x1, y1 in CC.flatten_lines(q.astype(np.float32)[None])]
+            else:
+                P = [np.array(q[2 * k:2 * k + 2]) for k in range(4)]
+                left, right = _split_cubic(P, 0.5)
+                parts = _split_cubic(left, 0.5) + _split_cubic(right, 0.5)
+                ends = [np.float32(parts[0][0])] + [np.float32(Q[3]) for Q in parts]  # rounded once, so that the parts meet
+                ends[-1] = np.float32(P[3])
+                for k, Q in enumerate(parts):
+                    c = (3.0 * (Q[1] + Q[2]) - (Q[0] + Q[3])) / 4.0
+                    rows.append([ends[k][0], ends[k][1], c[0], c[1], ends[k + 1][0], ends[k + 1][1]])
+        out.append((np.array(rows, np.float32), w, h, R))
+    return out
+
+
+def _put_cubic_set(ctx, leg, puts, first_key):
+    rects = []
+    for i, (segs, w, h, R) in enumerate(puts):
+        if leg == "native":
+            rects.append(ctx.put_glyph_outline_cubic(first_key + i, segs, w, h, mtsdf=True, sdf_range=R))
+        else:
+            rects.append(ctx.put_glyph_outline(first_key + i, segs, w, h, mtsdf=True, sdf_range=R))
+    return rects
+
+
+def time_cubic(leg, timed=100, warm=10):
+    puts = cubic_puts(leg)
+    ctx = _context()
+    us = []
+    for k in range(warm + timed):
+        ctx.reset_atlas()
+        t1 = time.perf_counter()
+        _put_cubic_set(ctx, leg, puts, 1)
+        t2 = time.perf_counter()
+        if k >= warm:
+            us.append((t2 - t1) * 1e6)
+    ctx.close()
+    print(json.dumps({"leg": leg, "segments": sum(len(p[0]) for p in puts), "calls": timed, "median_us": statistics.median(us),
+                      "p10_us": sorted(us)[len(us) // 10], "p90_us": sorted(us)[9 * len(us) // 10]}))
+
+
+def trace_cubic(leg, calls):
+    puts = cubic_puts(leg)
+    ctx = _context()
+    for _ in range(calls):
+        ctx.reset_atlas()
+        _put_cubic_set(ctx, leg, puts, 1)
+    ctx.close()
+    print(json.dumps({"leg": leg, "calls": calls}))
+
+
+def error_cubic(leg):
+    """the device's texels of the leg against the float64 reference of the cubic outlines"""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import msdf_cubic_cases as CC
+    import msdf_cubic_ref as R
+
+    puts = cubic_puts(leg)
+    ctx = _context()
+    rects = _put_cubic_set(ctx, leg, puts, 1)
+    atlas = ctx.debug_read_surface(4)
+    ctx.close()
+    worst, beyond, images = 0, 0, 0
+    for (x, y, w, h), (_, segs, _, _, Rr) in zip(rects, CC.skewed()):
+        d = np.abs(atlas[y:y + h, x:x + w].astype(int) - R.generate(segs, w, h, Rr).astype(int)).max(axis=2)
+        worst, beyond, images = max(worst, int(d.max())), beyond + int((d > 1).sum()), images + int((d > 1).sum() > 2)
+    print(json.dumps({"leg": leg, "max_lsb": worst, "texels_beyond_1_lsb": beyond, "images_beyond_the_cap": images}))
+
+
+CUBIC_HEAD = """tools/msdf_bench.py --cubic -- the 106 font inputs with every quadratic skewed into a genuine cubic (tests/msdf_cubic_cases.py skewed()),
+as distance fields, three ways, MI355X: native = fdh_put_glyph_outline_cubic on the cubics; quadratics = each cubic cut into four quadratics
+on the host (midpoint approximation), fdh_put_glyph_outline; lines = each cubic flattened to lines at 0.025 px, fdh_put_glyph_outline.  Host
+clock around the 106 puts, profiler off, 100 timed sets after 10, the legs alternating, each a process of its own; the generator's device
+time from a rocprofv3 --kernel-trace --stats run of its own, 20 sets; the field error is the device's texels against the float64 reference
+of the CUBIC outlines (tests/msdf_cubic_ref.py), over all 106 images.
+
+Hypothesis, stated before the numbers (nothing had been timed when it was written): a native cubic costs several times a quadratic per
+edge and texel (K + 1 = 9 to 33 evaluations of g and four refinements of six Newton steps against one closed-form solve and four Newton
+steps), but the native call walks a quarter of leg (a)'s curved edges and a smaller fraction still of leg (b)'s lines, which are cheap per
+edge; the three generators come out within a small factor of one another, native the slowest per launch or close to it, and the whole
+call, which is launch latency and the level chain, shows no difference beyond its spread.  What the native call buys is the field error:
+legs (a) and (b) leave texels several LSB from the cubic reference, the native call none beyond the tolerance.
+"""
+
+
+def run_cubic(out_path, trace_dir, passes=2):
+    me = [sys.executable, os.path.abspath(__file__)]
+    lines = CUBIC_HEAD.splitlines() + [""]
+    med = {leg: [] for leg in CUBIC_LEGS}
+    seg = {}
+    ok = True
+    for _ in range(passes):
+        for leg in CUBIC_LEGS:
+            got = _step(me + ["--time-cubic", leg], 300) if ok else None
+            if got is None:
+                ok = False
+                break
+            r = json.loads([ln for ln in got.strip().splitlines() if ln.startswith("{")][-1])
+            med[leg].append((r["median_us"], r["p10_us"], r["p90_us"]))
+            seg[leg] = r["segments"]
+    for leg in CUBIC_LEGS:
+        if not ok:
+            break
+        d = os.path.join(trace_dir, "cubic_" + leg)
+        got = _step(["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "-o", "t", "--"] + me + ["--trace-cubic", leg, "--calls", "20"], 300)
+        err = _step(me + ["--error-cubic", leg], 300) if got is not None else None
+        if got is None or err is None:
+            ok = False
+            break
+        kern = _stats(d, "*kernel_stats.csv")
+        gen = "k_msdf_generate_cubic" if leg == "native" else "k_msdf_generate"
+        calls, us, longest = kern.get(gen, (0, 0.0, 0.0))
+        e = json.loads([ln for ln in err.strip().splitlines() if ln.startswith("{")][-1])
+        lines.append(f"{leg} ({seg[leg]} segments): the 106 puts, median us per pass {', '.join(f'{m[0]:.1f} (p10 {m[1]:.1f}, p90 {m[2]:.1f})' for m in med[leg])}; "
+                     f"{gen} {us / max(calls, 1):.2f} us per launch over {calls} launches, {us / 20:.1f} us per set, the longest {longest:.1f}")
+        lines.append(f"    against the cubic reference: largest difference {e['max_lsb']} LSB, {e['texels_beyond_1_lsb']} texels beyond 1 LSB, {e['images_beyond_the_cap']} images beyond the cap of 2 texels")
+        print("\n".join(lines[-2:]), flush=True)
+    if not ok:
+        lines += ["", "INCOMPLETE: a step failed; nothing was started after it"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    return 0 if ok else 1
+
+
 BATCH_HEAD = """tools/msdf_bench.py --batch -- the 106 font inputs as ONE fdh_put_glyph_outlines against 106 single fdh_put_glyph_outline calls of the
 parent commit's library, MI355X.  Host clock around the 106 glyphs, profiler off, 200 timed after 20 per leg; the two legs alternate, each
 leg a process of its own, `passes` times per flag combination.  Kernels: a rocprofv3 --kernel-trace --stats run of its own, 60 batches.
@@ -252,6 +414,10 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--all", metavar="OUT")
     ap.add_argument("--batch", metavar="OUT", help="the font set as one batch against single calls of --parent-lib")
+    ap.add_argument("--cubic", metavar="OUT", help="cubic outlines natively against four quadratics per cubic and against lines")
+    ap.add_argument("--time-cubic", choices=list(CUBIC_LEGS))
+    ap.add_argument("--trace-cubic", choices=list(CUBIC_LEGS))
+    ap.add_argument("--error-cubic", choices=list(CUBIC_LEGS))
     ap.add_argument("--batched", action="store_true", help="with --time / --trace: one fdh_put_glyph_outlines per call")
     ap.add_argument("--nocull-lib")
     ap.add_argument("--parent-lib")
@@ -267,7 +433,15 @@ if __name__ == "__main__":
     unknown = [c for c in a.cases.split(",") if c not in CASES]
     if unknown:
         ap.error(f"--cases: unknown case(s) {', '.join(unknown)}; the cases are {', '.join(CASES)}")
-    if a.batch:
+    if a.cubic:
+        sys.exit(run_cubic(a.cubic, a.trace_dir, max(a.passes, 2)))
+    elif a.time_cubic:
+        time_cubic(a.time_cubic)
+    elif a.trace_cubic:
+        trace_cubic(a.trace_cubic, a.calls if a.calls != 60 else 20)
+    elif a.error_cubic:
+        error_cubic(a.error_cubic)
+    elif a.batch:
         if not a.parent_lib:
             ap.error("--batch needs --parent-lib")
         sys.exit(run_batch(a.batch, a.parent_lib, a.trace_dir, max(a.passes, 2)))
