@@ -52,6 +52,17 @@ int fdh_saturated_core(const float rect[4], const float rx[4], const float ry[4]
                        const float shape[2], float aa, int out_px[4]) {
   return guard([&] { fdh::saturated_core_of(rect, rx, ry, mode, factor, spread, shape, aa, out_px); });
 }
+/* Diagnostic, host-only, for the test-suite (not part of the installed header): fdh_saturated_core for the whole core as the bin launch
+ * sees it -- a union of up to three rectangles, DrawRec's own, the full-width band and the full-height band between the corner cells --,
+ * 3 x {x0, y0, x1, y1} in out_px as decoded from the draw's BinRec, empty ones as zeros; *n_out = how many are not empty.  push != 0: the
+ * record is a clip push (fdh_begin_mask) of that rounded rectangle instead of a draw.  FDH_CORE_UNION=0 leaves the first rectangle alone. */
+__attribute__((visibility("default"))) int fdh_saturated_core_union(const float rect[4], const float rx[4], const float ry[4], int mode, float factor, float spread,
+                             const float shape[2], float aa, int push, int out_px[12], int* n_out) {
+  return guard([&] {
+    if (!out_px || !n_out) throw fdh::Error(FDH_ERR_INVALID, "fdh_saturated_core_union: null pointer");
+    *n_out = fdh::saturated_core_union_of(rect, rx, ry, mode, factor, spread, shape, aa, push, out_px);
+  });
+}
 int fdh_blur_weight_fragments(float blur_radius, int vertical, float* dense, uint16_t* frag_bits, int* reach, int* k_steps) {
   return guard([&] {
     if (!dense || !frag_bits || !reach || !k_steps) throw fdh::Error(FDH_ERR_INVALID, "fdh_blur_weight_fragments: null pointer");

@@ -41,6 +41,9 @@ struct SerialOnly {};  // thrown by a pool thread's recorder at a call only the 
 // The BackendContext state machine (glcontext.nim): transform stack, clip / rect-mask stacks, and the draw calls, each turning
 // into records of ONE lane.  Context derives from it (lane 0: the C entry points and the serial walk); the walk pool's threads
 // each own one more (fdh_frontend.cpp).
+// the two bands of an upright draw's saturated core in BinRec's form (fdh_types.h; all zero: none)
+struct CoreBands { uint32_t grow = 0; uint16_t hy0 = 0, hy1 = 0, vx0 = 0, vx1 = 0; };
+
 class Recorder {
  public:
   Recorder(Context* cx, bool is_main) : cx_(cx), is_main_(is_main) {}
@@ -108,6 +111,7 @@ class Recorder {
   void quad_corners(const float vx[4], const float vy[4], QuadPx& q) const;
   bool emit_corners(DrawRec& r, const QuadPx& q, bool count_fragments);
   void push_rec(BBox b);  // count the slot next_rec() handed out
+  CoreBands bands_;       // emit_corners -> push_rec: the core bands of the record being emitted
   void commit_bins(uint32_t idx);  // the record's bounds are final: list-entry flags, list-stride count, phase summary
   void link_share(uint32_t idx);   // LE_SHARE on idx - 1 when record idx is drawn over the same quad with the same shape
   bool bbox_visible(const BBox& b) const;
@@ -471,5 +475,8 @@ void comm_unique_id(uint8_t out[FDH_COMM_ID_BYTES]);
 void blur_weight_fragments(float blur_radius, bool vertical, float* dense, uint16_t* frag_bits, int* reach, int* k_steps);
 void saturated_core_of(const float rect[4], const float rx[4], const float ry[4], int mode, float factor, float spread,
                        const float shape[2], float aa, int out[4]);
+int saturated_core_union_of(const float rect[4], const float rx[4], const float ry[4], int mode, float factor, float spread,
+                            const float shape[2], float aa, int push, int out[12]);
+int binrec_core_rects(const BinRec& br, int out[12]);
 
 }  // namespace fdh

@@ -391,16 +391,24 @@ __device__ __forceinline__ uint32_t strip_mask_inside(int x0, int y0, int x1, in
 // x0 <= bx, y0 <= by, bx <= x1, by <= y1: one subtract, one and, one compare per draw.
 // The two ends of an entry's making that every draw goes through -- both translation units hold them: the compositor of a frame with at
 // most 64 draws per phase makes its entries itself (round 6: "direct" launches, k_composite_tiles).
-// (the 24-byte BinRec in ONE round trip -- a 16- and an 8-byte load issued together, pinned: read field by field the compiler sank
+// (the 32-byte BinRec in ONE round trip -- its loads issued together, pinned: read field by field the compiler sank
 // each field's load behind the test before it, three to four dependent L2 latencies per batch of hits)
+// (kUnion = false, for bin_entry_tail<false>: the bands are not fetched)
+template <bool kUnion = true>
 __device__ __forceinline__ bool bin_entry_head(const BinRec* __restrict__ binrec, int i, int x0, int y0, BinRec& r, uint32_t& word, uint32_t& strips) {
   {
     const uint2* __restrict__ src = reinterpret_cast<const uint2*>(binrec + i);
-    uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-    asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2));
+    uint2 q0 = src[0], q1 = src[1], q2 = src[2], q3 = make_uint2(0u, 0u);
+    if (kUnion) {
+      q3 = src[3];
+      asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3));
+    } else {
+      asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2));
+    }
     r.box.x0 = (int16_t)(q0.x & 0xffffu); r.box.y0 = (int16_t)(q0.x >> 16); r.box.x1 = (int16_t)(q0.y & 0xffffu); r.box.y1 = (int16_t)(q0.y >> 16);
     r.ix0 = (int16_t)(q1.x & 0xffffu); r.iy0 = (int16_t)(q1.x >> 16); r.ix1 = (int16_t)(q1.y & 0xffffu); r.iy1 = (int16_t)(q1.y >> 16);
-    r.flags = q2.x; r.pad = q2.y;
+    r.flags = q2.x; r.grow = q2.y;
+    r.hy0 = (uint16_t)(q3.x & 0xffffu); r.hy1 = (uint16_t)(q3.x >> 16); r.vx0 = (uint16_t)(q3.y & 0xffffu); r.vx1 = (uint16_t)(q3.y >> 16);
   }
   const BBox b = r.box;
   strips = strip_mask(b.x0 - x0, b.y0 - y0, b.x1 - x0, b.y1 - y0);
@@ -409,10 +417,18 @@ __device__ __forceinline__ bool bin_entry_head(const BinRec* __restrict__ binrec
 }
 // (written without branches, for the same reason -- and without `?:` on anything but flags: the compiler turned selects between
 // computed masks back into branches in one build of the compositor; bit masks it cannot)
+// (kUnion = false: DrawRec's rectangle alone -- the compositor's direct launches, whose draw loop paid for the two bands' masks with
+// spilled scalar registers; their frames hold at most 64 draws)
+template <bool kUnion = true>
 __device__ __forceinline__ void bin_entry_tail(const BinRec& r, int x0, int y0, bool& hit, uint32_t& strips) {
   const uint32_t m_core = 0u - (uint32_t)((r.flags & BR_HAS_CORE) != 0u), m_removed = 0u - (uint32_t)((r.flags & BR_CORE_REMOVED) != 0u),
                  m_exact = 0u - (uint32_t)((r.flags & BR_BOX_EXACT) != 0u);  // all ones / zero
-  const uint32_t core = strip_mask_inside(r.ix0 - x0, r.iy0 - y0, r.ix1 - x0, r.iy1 - y0) & strips & m_core;
+  // the core is a union: DrawRec's rectangle, the full-width band H and the full-height band V between the corner cells (BinRec)
+  const int cx0 = r.ix0 - x0, cy0 = r.iy0 - y0, cx1 = r.ix1 - x0, cy1 = r.iy1 - y0;
+  const int gx0 = (int)(r.grow & 255u), gx1 = (int)((r.grow >> 8) & 255u), gy0 = (int)((r.grow >> 16) & 255u), gy1 = (int)(r.grow >> 24);
+  uint32_t in_core = strip_mask_inside(cx0, cy0, cx1, cy1);
+  if (kUnion) in_core |= strip_mask_inside(cx0 - gx0, cy0 + (int)r.hy0, cx1 + gx1, cy1 - (int)r.hy1) | strip_mask_inside(cx0 + (int)r.vx0, cy0 - gy0, cx1 - (int)r.vx1, cy1 + gy1);
+  const uint32_t core = in_core & strips & m_core;
   // alpha == 0 on the core (stroke interior) or too small to change an 8-bit channel (deep inside an inner shadow): those strips leave
   // the entry, and the entry goes with them if none is left; any other core is marked in the high half
   const uint32_t s1 = (strips & ~(core & m_removed)) | ((core & ~m_removed) << 16);

@@ -23,7 +23,7 @@ struct BlurJob {
 
 // ------------------------------------------------------------------ the recorded frame
 // A frame's draw records are produced in their FINAL form while the calls arrive -- the 128-byte DrawRec the compositor reads,
-// the 24-byte BinRec the bin kernel reads (pixel bounds, saturated core, list-entry flags), the quad extensions: nothing is
+// the 32-byte BinRec the bin kernel reads (pixel bounds, saturated core, list-entry flags), the quad extensions: nothing is
 // built a second time at submit.  A LANE is what one thread records: lane 0 belongs to the thread that calls the context,
 // lanes 1.. to the walk pool's threads (fdh_frontend.cpp: large sibling groups of the scene tree are decomposed in parallel).
 // (PickTag, a record's tag in a picking frame: fdh_plain.h)

@@ -143,7 +143,8 @@ DrawRec& Recorder::next_rec() {
 // counts the slot next_rec() handed out; its BinRec starts as bare bounds (flags follow when the bounds are final: commit_bins)
 void Recorder::push_rec(BBox b) {  // (by value: callers pass bounds that live in the very array slot() may move)
   BinRec* br = lane_->bins.slot();
-  *br = BinRec{b, 0, 0, 0, 0, 0u, 0u};
+  *br = BinRec{b, 0, 0, 0, 0, 0u, bands_.grow, bands_.hy0, bands_.hy1, bands_.vx0, bands_.vx1};
+  bands_ = CoreBands{};  // (they belong to the record emit_corners just made)
   *lane_->boxes.slot() = 0x7f7f7f7fu;
   lane_->recs.n++;
   lane_->bins.n++;
@@ -353,8 +354,16 @@ int Lane::count_close() {
 // corners are pulled in by (1 - 1/sqrt 2) r per corner lies inside it.  Elliptical corners use an approximate
 // distance (atlas.frag:71-79), so there the core stays out of the corner cells, where the distance is the plain
 // box distance max(|p| - b).  One pixel of slack on every side absorbs all float rounding.
-// (first half: the rectangle {xl..xr} x {yb..yt} of the local frame, y up; false = no core)
-static bool local_core(const DrawRec& r, double& xl, double& xr, double& yb, double& yt) {
+// Between the corner cells the distance IS the plain box distance max(|p| - b), whatever the corners are, so two more rectangles are
+// saturated: the band H, full width (|x| <= bx - e) between the corner cells of the e-inset shape above and below, and the band
+// V, full height between the ones left and right.  The core is the union of the three (BinRec; DrawRec keeps the first).
+// (first half: rectangles of the local frame, y up.  out[0]: the one DrawRec::ix0..iy1 holds -- inscribed for circular corners,
+// the larger band for elliptical ones --, out[1]: H, out[2]: V; any of them may be empty.  false = no core)
+struct LocalRect {
+  double xl, xr, yb, yt;
+  bool ok() const { return xr > xl && yt > yb; }
+};
+static bool local_core(const DrawRec& r, LocalRect out[3]) {
   const uint32_t mode = r.op_mode & 255u, op = (r.op_mode >> 12) & 15u;
   const uint32_t fill_mode = (r.op_mode >> 9) & 7u;
   if (!(op == OP_DRAW || op == OP_MASK_PUSH) || !(r.aa > 0.0f)) return false;
@@ -382,29 +391,33 @@ static bool local_core(const DrawRec& r, double& xl, double& xr, double& yb, dou
     cry[k] = hi * by / 4095.0;
   }
   enum { TR = 0, BR = 1, TL = 2, BL = 3 };
+  LocalRect &H = out[1], &V = out[2];
+  H.xl = -(bx - e); H.xr = bx - e;
+  V.yb = -(by - e); V.yt = by - e;
   if (!(r.op_mode & F_ELLIP)) {
     const double k = 0.2929;
     auto rr = [&](int i) { return std::max(crx[i] - e, 0.0); };
-    xr = (bx - e) - k * std::max(rr(TR), rr(BR));
-    xl = -(bx - e) + k * std::max(rr(TL), rr(BL));
-    yt = (by - e) - k * std::max(rr(TR), rr(TL));
-    yb = -(by - e) + k * std::max(rr(BR), rr(BL));
+    const double mr = std::max(rr(TR), rr(BR)), ml = std::max(rr(TL), rr(BL)), mt = std::max(rr(TR), rr(TL)), mb = std::max(rr(BR), rr(BL));
+    out[0].xr = (bx - e) - k * mr;
+    out[0].xl = -(bx - e) + k * ml;
+    out[0].yt = (by - e) - k * mt;
+    out[0].yb = -(by - e) + k * mb;
+    H.yt = (by - e) - mt; H.yb = -(by - e) + mb;
+    V.xr = (bx - e) - mr; V.xl = -(bx - e) + ml;
   } else {
     // horizontal band (full width, between the corner cells) or vertical band, whichever is larger
-    const double hx0 = -(bx - e), hx1 = bx - e;
-    const double hy1 = std::min(by - e, by - std::max(cry[TR], cry[TL])), hy0 = -std::min(by - e, by - std::max(cry[BR], cry[BL]));
-    const double vy0 = -(by - e), vy1 = by - e;
-    const double vx1 = std::min(bx - e, bx - std::max(crx[TR], crx[BR])), vx0 = -std::min(bx - e, bx - std::max(crx[TL], crx[BL]));
-    const double ah = std::max(hx1 - hx0, 0.0) * std::max(hy1 - hy0, 0.0), av = std::max(vx1 - vx0, 0.0) * std::max(vy1 - vy0, 0.0);
-    if (ah >= av) { xl = hx0; xr = hx1; yb = hy0; yt = hy1; } else { xl = vx0; xr = vx1; yb = vy0; yt = vy1; }
+    H.yt = std::min(by - e, by - std::max(cry[TR], cry[TL])); H.yb = -std::min(by - e, by - std::max(cry[BR], cry[BL]));
+    V.xr = std::min(bx - e, bx - std::max(crx[TR], crx[BR])); V.xl = -std::min(bx - e, bx - std::max(crx[TL], crx[BL]));
+    const double ah = std::max(H.xr - H.xl, 0.0) * std::max(H.yt - H.yb, 0.0), av = std::max(V.xr - V.xl, 0.0) * std::max(V.yt - V.yb, 0.0);
+    out[0] = ah >= av ? H : V;
   }
-  if (inset) { xl += r.p2; xr += r.p2; yb -= r.p3; yt -= r.p3; }  // the shadow shape sits at (p2, -p3) in the quad's frame
-  return xr > xl && yt > yb;
+  if (inset)  // the shadow shape sits at (p2, -p3) in the quad's frame
+    for (int k = 0; k < 3; k++) { out[k].xl += r.p2; out[k].xr += r.p2; out[k].yb -= r.p3; out[k].yt -= r.p3; }
+  return true;
 }
-static void set_saturated_core(DrawRec& r, float w_px, float h_px) {
-  r.ix0 = r.iy0 = r.ix1 = r.iy1 = 0;
-  double xl, xr, yb, yt;
-  if (!local_core(r, xl, xr, yb, yt)) return;
+// (second half: a local rectangle's pixel centres; false = none)
+static bool core_pixels(const DrawRec& r, float w_px, float h_px, const LocalRect& c, int16_t px[4]) {
+  if (!c.ok()) return false;
   const double qhx = r.p0, qhy = r.p1;
   // local -> pixel centres: cx = ox + w_px * (x / (2 qhx) + 0.5), cy = oy + h_px * (0.5 - y / (2 qhy))
   // slack: what float rounding in the kernels' coordinate arithmetic can move a pixel centre against the level set (~2e-3 px at
@@ -415,14 +428,62 @@ static void set_saturated_core(DrawRec& r, float w_px, float h_px) {
 #define FDH_CORE_SLACK (1.0 / 16.0)
 #endif
   const double slack = FDH_CORE_SLACK;
-  const double cxl = r.ox + w_px * (xl / (2.0 * qhx) + 0.5) + slack, cxr = r.ox + w_px * (xr / (2.0 * qhx) + 0.5) - slack;
-  const double cyt = r.oy + h_px * (0.5 - yt / (2.0 * qhy)) + slack, cyb = r.oy + h_px * (0.5 - yb / (2.0 * qhy)) - slack;
+  const double cxl = r.ox + w_px * (c.xl / (2.0 * qhx) + 0.5) + slack, cxr = r.ox + w_px * (c.xr / (2.0 * qhx) + 0.5) - slack;
+  const double cyt = r.oy + h_px * (0.5 - c.yt / (2.0 * qhy)) + slack, cyb = r.oy + h_px * (0.5 - c.yb / (2.0 * qhy)) - slack;
   double ix0 = std::ceil(cxl - 0.5), ix1 = std::floor(cxr - 0.5) + 1.0, iy0 = std::ceil(cyt - 0.5), iy1 = std::floor(cyb - 0.5) + 1.0;
   ix0 = std::max(ix0, (double)r.ox); ix1 = std::min(ix1, (double)r.ox + w_px);  // stay inside the quad (coverage)
   iy0 = std::max(iy0, (double)r.oy); iy1 = std::min(iy1, (double)r.oy + h_px);
   auto c16 = [](double v) { return (int16_t)std::min(std::max(v, -32768.0), 32767.0); };
-  if (!(ix1 > ix0 && iy1 > iy0)) return;
-  r.ix0 = c16(ix0); r.iy0 = c16(iy0); r.ix1 = c16(ix1); r.iy1 = c16(iy1);
+  if (!(ix1 > ix0 && iy1 > iy0)) return false;
+  px[0] = c16(ix0); px[1] = c16(iy0); px[2] = c16(ix1); px[3] = c16(iy1);
+  return true;
+}
+static bool core_union_on() {
+  static const bool enabled = [] { const char* v = std::getenv("FDH_CORE_UNION"); return !v || std::atoi(v) != 0; }();
+  return enabled;
+}
+// The bands in BinRec's form, relative to the first rectangle `c`, which each crosses: H is at least as wide and no taller, V at least
+// as tall and no wider (a band that is not -- none should be -- stays out).  What does not fit its field is cut towards the smaller band.
+static CoreBands pack_bands(const int16_t c[4], const int16_t* h, const int16_t* v) {
+  CoreBands b;
+  auto u8 = [](int d) { return (uint32_t)std::min(d, 255); };
+  auto u16 = [](int d) { return (uint16_t)std::min(d, 65535); };
+  if (h && h[0] <= c[0] && h[2] >= c[2] && h[1] >= c[1] && h[3] <= c[3]) {
+    b.grow |= u8(c[0] - h[0]) | (u8(h[2] - c[2]) << 8);
+    b.hy0 = u16(h[1] - c[1]); b.hy1 = u16(c[3] - h[3]);
+  }
+  if (v && v[1] <= c[1] && v[3] >= c[3] && v[0] >= c[0] && v[2] <= c[2]) {
+    b.grow |= (u8(c[1] - v[1]) << 16) | (u8(v[3] - c[3]) << 24);
+    b.vx0 = u16(v[0] - c[0]); b.vx1 = u16(c[2] - v[2]);
+  }
+  return b;
+}
+// The rectangles the bin launch tests for record `br` (bin_entry_tail does the same arithmetic): out = 3 x {x0, y0, x1, y1}, empty
+// ones as zeros; returns how many are not empty.
+int binrec_core_rects(const BinRec& br, int out[12]) {
+  const int g[4] = {(int)(br.grow & 255u), (int)((br.grow >> 8) & 255u), (int)((br.grow >> 16) & 255u), (int)(br.grow >> 24)};
+  const int q[3][4] = {{br.ix0, br.iy0, br.ix1, br.iy1},
+                       {br.ix0 - g[0], br.iy0 + (int)br.hy0, br.ix1 + g[1], br.iy1 - (int)br.hy1},
+                       {br.ix0 + (int)br.vx0, br.iy0 - g[2], br.ix1 - (int)br.vx1, br.iy1 + g[3]}};
+  int n = 0;
+  for (int k = 0; k < 3; k++) {
+    const bool ok = q[k][2] > q[k][0] && q[k][3] > q[k][1];
+    for (int j = 0; j < 4; j++) out[4 * k + j] = ok ? q[k][j] : 0;
+    n += ok ? 1 : 0;
+  }
+  return n;
+}
+// DrawRec's core, and the bands for the record's BinRec (all zero: none)
+static CoreBands set_saturated_core(DrawRec& r, float w_px, float h_px) {
+  r.ix0 = r.iy0 = r.ix1 = r.iy1 = 0;
+  LocalRect lc[3];
+  if (!local_core(r, lc)) return CoreBands{};
+  int16_t c[4], h[4], v[4];
+  if (!core_pixels(r, w_px, h_px, lc[0], c)) return CoreBands{};
+  r.ix0 = c[0]; r.iy0 = c[1]; r.ix1 = c[2]; r.iy1 = c[3];
+  if (!core_union_on()) return CoreBands{};
+  const bool hok = core_pixels(r, w_px, h_px, lc[1], h), vok = core_pixels(r, w_px, h_px, lc[2], v);
+  return pack_bands(c, hok ? h : nullptr, vok ? v : nullptr);
 }
 
 // Quad emission: ceil(ctx.mat * corner) per vertex, order BL,BR,TR,TL (glcontext.nim:1498-1509), then either the
@@ -482,6 +543,7 @@ bool Recorder::emit_corners(DrawRec& r, const QuadPx& q, bool count_fragments) {
   const float* px = q.px;
   const float* py = q.py;
   BBox b = q.b;
+  bands_ = CoreBands{};
   // A draw that reaches no pixel the frame will produce leaves no trace (it would never be binned).  Clip pushes stay: their
   // bounds grow to their content's, and a push that is not there would let that content through.
   const bool cullable = ((r.op_mode >> 12) & 15u) == OP_DRAW && culling();
@@ -510,7 +572,7 @@ bool Recorder::emit_corners(DrawRec& r, const QuadPx& q, bool count_fragments) {
     r.inv_h = 1.0f / (py[0] - py[3]);
     r.kx = 2.0f * r.p0 * r.inv_w;  // (meaningful for SDF quads, where p0, p1 are the quad's half extents)
     r.ky = 2.0f * r.p1 * r.inv_h;
-    if (!bezier) set_saturated_core(r, px[1] - px[0], py[0] - py[3]);
+    if (!bezier) bands_ = set_saturated_core(r, px[1] - px[0], py[0] - py[3]);
   }
   if (!aligned || bezier) {
     QuadExt& q = *lane_->exts.slot();
@@ -571,8 +633,9 @@ bool Recorder::emit_corners(DrawRec& r, const QuadPx& q, bool count_fragments) {
     if (edge32) r.op_mode |= F_EDGE32;
     // the saturated core of a rotated SDF draw, in the local frame, and the two triangles' maps into that frame (QuadExt::core, lm)
     q.core[0] = q.core[1] = q.core[2] = q.core[3] = 0.0f;
-    double xl, xr, yb, yt;
-    if (edge32 && !atlas_mode && mode < 18u && ((r.op_mode >> 12) & 15u) == OP_DRAW && q.inv_sum[0] != 0.0f && q.inv_sum[1] != 0.0f && local_core(r, xl, xr, yb, yt)) {
+    LocalRect lc[3];
+    if (edge32 && !atlas_mode && mode < 18u && ((r.op_mode >> 12) & 15u) == OP_DRAW && q.inv_sum[0] != 0.0f && q.inv_sum[1] != 0.0f && local_core(r, lc) && lc[0].ok()) {
+      double xl = lc[0].xl, xr = lc[0].xr, yb = lc[0].yb, yt = lc[0].yt;
       // tri 0 = (TL, BL, BR): u = E2 is, v = (E1 + E2) is;  tri 1 = (TR, TL, BR): u = (E0 + E2) is, v = E2 is;  local x = (u - 0.5) 2 qhx,
       // local y (up) = -(v - 0.5) 2 qhy (atlas.frag:252-262)
       const double qhx = r.p0, qhy = r.p1;
@@ -669,6 +732,25 @@ void saturated_core_of(const float rect[4], const float rx[4], const float ry[4]
   r.inv_w = 1.0f / (x1 - x0); r.inv_h = 1.0f / (y1 - y0);
   set_saturated_core(r, x1 - x0, y1 - y0);
   out[0] = r.ix0; out[1] = r.iy0; out[2] = r.ix1; out[3] = r.iy1;
+}
+// The same for the whole union, as the bin launch decodes it from the draw's BinRec (binrec_core_rects); `push`: the record is a clip
+// push (begin_mask) instead of a draw.  Returns the number of rectangles that are not empty.
+int saturated_core_union_of(const float rect[4], const float rx[4], const float ry[4], int mode, float factor, float spread,
+                            const float shape[2], float aa, int push, int out[12]) {
+  const FdhColor white{255, 255, 255, 255}, zero{0, 0, 0, 0};
+  const FdhColor cols[4] = {white, white, white, white};
+  DrawRec r;
+  std::memset(static_cast<void*>(&r), 0, sizeof r);
+  fill_sdf_rec(r, rect, cols, rx, ry, mode, factor, spread, shape, 0, zero, zero, 0.5f, aa);
+  if (push) r.op_mode |= OP_MASK_PUSH << 12;
+  const float x0 = std::ceil(rect[0]), y0 = std::ceil(rect[1]), x1 = std::ceil(rect[0] + rect[2]), y1 = std::ceil(rect[1] + rect[3]);
+  for (int k = 0; k < 12; k++) out[k] = 0;
+  if (!(x1 > x0 && y1 > y0)) return 0;
+  r.ox = x0; r.oy = y0;
+  r.inv_w = 1.0f / (x1 - x0); r.inv_h = 1.0f / (y1 - y0);
+  const CoreBands b = set_saturated_core(r, x1 - x0, y1 - y0);
+  const BinRec br{BBox{0, 0, 0, 0}, r.ix0, r.iy0, r.ix1, r.iy1, 0u, b.grow, b.hy0, b.hy1, b.vx0, b.vx1};
+  return binrec_core_rects(br, out);
 }
 
 // drawRoundedRectSdfOpenGl: glcontext.nim:1449-1559

@@ -78,7 +78,8 @@ struct alignas(16) DrawRec {
   // Saturated core of an axis-aligned SDF draw, in (unclipped) pixel bounds, empty when unknown: every pixel centre in
   // [ix0,ix1) x [iy0,iy1) has coverage alpha == 1 (fills, clip pushes, drop-shadow bodies, blur composites) or, for
   // the annular stroke modes 11/12, alpha == 0 -- or, for an inner shadow (mode 9), alpha too small to change any 8-bit
-  // channel.  Conservative by a pixel; lets a strip be classified by a bit test.
+  // channel.  Conservative by a pixel; lets a strip be classified by a bit test.  (One rectangle of the saturated region: the bin
+  // launch tests a union of three, BinRec below; every other reader of a core -- the blur kernels, clear folding -- reads this one.)
   int16_t ix0, iy0, ix1, iy1;
   // axis-aligned SDF quads: local-frame steps per pixel, kx = 2 p0 inv_w, ky = 2 p1 inv_h (atlas.frag:252-262: p = (uv - 0.5) * 2 *
   // quadHalfExtents): a lane's pixels 1..3 are pixel 0's local x plus multiples of kx
@@ -111,13 +112,19 @@ static_assert(sizeof(QuadExt) == 208 && offsetof(QuadExt, core) == 144 && offset
 
 struct alignas(8) BBox { int16_t x0, y0, x1, y1; };
 
-// What k_bin_draws needs of a draw, in one 24-byte piece (built on the host at submit): the clipped pixel bounds, the
+// What k_bin_draws needs of a draw, in one 32-byte piece (built on the host at submit): the clipped pixel bounds, the
 // saturated core, and the parts of a list entry that do not depend on the bin -- flags and path code in their entry
 // positions (bits 25..31: LE_SHARE, LE_PATH, LE_OPAQUE, LE_PLAIN), bit 0: the draw has a core worth testing (axis-aligned SDF draw or
 // clip push), bit 1: its core strips are REMOVED from the entry (stroke interiors, deep inside an inner shadow).  Before, a
 // hit walked bounds -> mode word -> core -> colours: three dependent round trips per batch of hits.
-struct alignas(8) BinRec { BBox box; int16_t ix0, iy0, ix1, iy1; uint32_t flags; uint32_t pad; };
-static_assert(sizeof(BinRec) == 24, "BinRec must be 24 bytes");
+// The core of an upright draw is a UNION of up to three rectangles: [ix0,ix1) x [iy0,iy1) -- DrawRec's own, the one every other reader
+// of a core sees -- and the two bands between the corner cells, where the rounded-box distance is the plain box distance: H, full
+// width, and V, full height.  Each band is held relative to the first rectangle, which it crosses:
+//   H = [ix0 - gx0, ix1 + gx1) x [iy0 + hy0, iy1 - hy1)      V = [ix0 + vx0, ix1 - vx1) x [iy0 - gy0, iy1 + gy1)
+// grow = gx0 | gx1 << 8 | gy0 << 16 | gy1 << 24 (bytes: a band that reaches farther is cut short, which keeps it conservative).  All
+// zero: both bands are the first rectangle again (FDH_CORE_UNION=0, rotated quads, draws without a core).
+struct alignas(8) BinRec { BBox box; int16_t ix0, iy0, ix1, iy1; uint32_t flags; uint32_t grow; uint16_t hy0, hy1, vx0, vx1; };
+static_assert(sizeof(BinRec) == 32, "BinRec must be 32 bytes");
 constexpr uint32_t BR_HAS_CORE = 1u, BR_CORE_REMOVED = 2u;
 // bit 2: a rotated / skewed SDF draw (F_GENERAL | F_EDGE32, OP_DRAW): its pixel bounds are the quad's bounding box; k_bin_draws drops the
 // strips that lie outside one of the quad's four outer edges (half of the box of a quad rotated by 30 degrees)

@@ -294,7 +294,7 @@ __global__ __launch_bounds__(64) void k_upload_frame(uint8_t* __restrict__ dst, 
   const UploadRun R = T.run[blockIdx.y];
   const uint32_t at = blockIdx.x * 1024u;
   if (at >= R.bytes) return;
-  if (R.kind == 1u) {  // BinRecs in 8-byte units (24 bytes each: a piece starts 8-byte aligned)
+  if (R.kind == 1u) {  // BinRecs in 8-byte units (32 bytes each: a piece starts 8-byte aligned)
     const uint32_t ush = 6u + T.binbox_shift;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
@@ -303,8 +303,8 @@ __global__ __launch_bounds__(64) void k_upload_frame(uint8_t* __restrict__ dst, 
       const uint2 v = *reinterpret_cast<const uint2*>(static_cast<const uint8_t*>(R.src) + o);
       *reinterpret_cast<uint2*>(dst + R.dst_off + o) = v;
       const uint32_t rel = R.dst_off - T.bins_off + o;  // byte offset in the BinRec array
-      if (rel % 24u != 0u) continue;
-      const uint32_t draw = rel / 24u;
+      if (rel % (uint32_t)sizeof(BinRec) != 0u) continue;
+      const uint32_t draw = rel / (uint32_t)sizeof(BinRec);
       const int x0 = (int)(int16_t)(v.x & 0xffffu), y0 = (int)(int16_t)(v.x >> 16), x1 = (int)(int16_t)(v.y & 0xffffu), y1 = (int)(int16_t)(v.y >> 16);
       uint32_t q = 0x7f7f7f7fu;  // x0 = y0 = 127, x1 = y1 = 0: never hits
       if (x1 > x0 && y1 > y0)

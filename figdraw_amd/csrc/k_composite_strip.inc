@@ -154,8 +154,8 @@
       const int by = bin / P.bins_x, bx = bin - by * P.bins_x;
       BinRec br;
       uint32_t word = 0, strips = 0;
-      bool hit = bin_entry_head(P.binrec, P.direct_first + (int)min(i, cnt - 1u), bx * kBin, by * kBin, br, word, strips);
-      bin_entry_tail(br, bx * kBin, by * kBin, hit, strips);
+      bool hit = bin_entry_head<false>(P.binrec, P.direct_first + (int)min(i, cnt - 1u), bx * kBin, by * kBin, br, word, strips);
+      bin_entry_tail<false>(br, bx * kBin, by * kBin, hit, strips);  // (the one-rectangle core: see there)
       e = make_uint2(word, hit ? strips : 0u);
     } else {
       e = list[min(i, cnt - 1u)];  // {draw index | flags, strips touched | strips inside the saturated core << 16}
