@@ -129,6 +129,9 @@ def load():
     if hasattr(L, "fdh_put_glyph_coverage_batch"):  # include_glyphs/figdraw_hip_coverage.h
         L.fdh_put_glyph_coverage_batch.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
         L.fdh_glyph_coverage_batch_stats.argtypes = [vp, C.POINTER(GlyphBatchStats)]
+    if hasattr(L, "fdh_put_glyph_outlines_cubic"):  # include_glyphs/figdraw_hip_cubic_batch.h
+        L.fdh_put_glyph_outlines_cubic.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
+        L.fdh_put_glyph_coverage_batch_cubic.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
     L.fdh_read_pixels.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.fdh_debug_read_surface.argtypes = [vp, C.c_int, vp]
     L.fdh_scene_retain.argtypes = [vp, vp, C.c_float, C.c_float, C.c_int, _F4]
@@ -387,27 +390,50 @@ class HipContext:
         self._ck(self.L.fdh_put_glyph_outline_cubic(self.h, int(key), int(w), int(h), segs.ctypes.data if len(segs) else None, len(segs), flags, out))
         return tuple(out)
 
+    def _glyph_outline_array(self, items, floats: int):
+        """what the four batch calls take: items (key, segs, w, h[, range]), segs n x `floats` -> (n, the FdhGlyphOutline array, the rectangles to fill,
+        the outlines, which must stay alive until the call returns)"""
+        items = list(items)
+        n = len(items)
+        arr = (GlyphOutline * max(n, 1))()
+        keep = []
+        for g, it in zip(arr, items):
+            segs = np.ascontiguousarray(it[1], dtype=np.float32).reshape(-1, floats)
+            keep.append(segs)
+            g.key, g.segs, g.n_segs, g.width, g.height = int(it[0]), segs.ctypes.data if len(segs) else None, len(segs), int(it[2]), int(it[3])
+            g.sdf_range = int(it[4]) if len(it) > 4 else 0
+        return n, arr, ((C.c_int * 4) * max(n, 1))(), keep
+
     def put_glyph_outlines(self, items, sdf_range: int = 0, correct: bool = False, overlap: bool = False):
         """a batch of distance-field glyphs in one call (fdh_put_glyph_outlines, include_glyphs/figdraw_hip_glyphs.h): `items` is a sequence of
         (key, segs, w, h) or (key, segs, w, h, range) -- a glyph's own range, 0 or absent: `sdf_range` (whose 0 is 4); correct and overlap as
         in put_glyph_outline, for every glyph.  What the same put_glyph_outline(..., mtsdf=True) calls in order would leave, from a number of
         launches that does not depend on len(items).  -> the rectangles, one (x, y, w, h) per item"""
-        items = list(items)
-        n = len(items)
-        arr = (GlyphOutline * max(n, 1))()
-        keep = []  # the outlines, alive until the call returns
-        for g, it in zip(arr, items):
-            segs = np.ascontiguousarray(it[1], dtype=np.float32).reshape(-1, 6)
-            keep.append(segs)
-            g.key, g.segs, g.n_segs, g.width, g.height = int(it[0]), segs.ctypes.data if len(segs) else None, len(segs), int(it[2]), int(it[3])
-            g.sdf_range = int(it[4]) if len(it) > 4 else 0
-        out = ((C.c_int * 4) * max(n, 1))()
+        n, arr, out, keep = self._glyph_outline_array(items, 6)
         flags = 4 | (8 if correct else 0) | (32 if overlap else 0) | (int(sdf_range) << 8)
         self._ck(self.L.fdh_put_glyph_outlines(self.h, C.addressof(arr), n, flags, C.addressof(out)))
         return [tuple(out[i]) for i in range(n)]
 
+    def put_glyph_outlines_cubic(self, items, sdf_range: int = 0, correct: bool = False, overlap: bool = False):
+        """put_glyph_outlines for outlines with cubic segments (fdh_put_glyph_outlines_cubic, include_glyphs/figdraw_hip_cubic_batch.h): `items` as
+        there, each `segs` n x 8 in the format of put_glyph_outline_cubic.  What the same put_glyph_outline_cubic(..., mtsdf=True) calls in order
+        would leave; overlap only where no glyph holds a cubic.  -> the rectangles, one (x, y, w, h) per item"""
+        n, arr, out, keep = self._glyph_outline_array(items, 8)
+        flags = 4 | (8 if correct else 0) | (32 if overlap else 0) | (int(sdf_range) << 8)
+        self._ck(self.L.fdh_put_glyph_outlines_cubic(self.h, C.addressof(arr), n, flags, C.addressof(out)))
+        return [tuple(out[i]) for i in range(n)]
+
+    def put_glyph_coverage_batch_cubic(self, items, lcd_filter=False):
+        """put_glyph_coverage_batch for outlines with cubic segments (fdh_put_glyph_coverage_batch_cubic, include_glyphs/figdraw_hip_cubic_batch.h):
+        `items` is a sequence of (key, segs, w, h), each `segs` n x 8; lcd_filter as in put_glyph_image, for every glyph.  What the same
+        put_glyph_outline_cubic calls in order would leave.  -> the rectangles, one (x, y, w, h) per item"""
+        n, arr, out, keep = self._glyph_outline_array([it[:4] for it in items], 8)
+        flags = 2 if lcd_filter == "context" else (1 if lcd_filter else 0)
+        self._ck(self.L.fdh_put_glyph_coverage_batch_cubic(self.h, C.addressof(arr), n, flags, C.addressof(out)))
+        return [tuple(out[i]) for i in range(n)]
+
     def glyph_batch_stats(self) -> dict:
-        """what the last put_glyph_outlines did: glyphs, written, dropped_by_growth, tiles, edges, launches, bytes_copied"""
+        """what the last put_glyph_outlines or put_glyph_outlines_cubic did: glyphs, written, dropped_by_growth, tiles, edges, launches, bytes_copied"""
         st = GlyphBatchStats()
         self._ck(self.L.fdh_glyph_batch_stats(self.h, C.byref(st)))
         return {name: int(getattr(st, name)) for name, _ in GlyphBatchStats._fields_}
@@ -416,21 +442,13 @@ class HipContext:
         """a batch of coverage glyphs in one call (fdh_put_glyph_coverage_batch, include_glyphs/figdraw_hip_coverage.h): `items` is a sequence of
         (key, segs, w, h); lcd_filter as in put_glyph_image (True, False or "context"), for every glyph.  What the same put_glyph_outline
         calls in order would leave, from a number of launches that does not depend on len(items).  -> the rectangles, one (x, y, w, h) per item"""
-        items = list(items)
-        n = len(items)
-        arr = (GlyphOutline * max(n, 1))()
-        keep = []  # the outlines, alive until the call returns
-        for g, it in zip(arr, items):
-            segs = np.ascontiguousarray(it[1], dtype=np.float32).reshape(-1, 6)
-            keep.append(segs)
-            g.key, g.segs, g.n_segs, g.width, g.height, g.sdf_range = int(it[0]), segs.ctypes.data if len(segs) else None, len(segs), int(it[2]), int(it[3]), 0
-        out = ((C.c_int * 4) * max(n, 1))()
+        n, arr, out, keep = self._glyph_outline_array([it[:4] for it in items], 6)
         flags = 2 if lcd_filter == "context" else (1 if lcd_filter else 0)
         self._ck(self.L.fdh_put_glyph_coverage_batch(self.h, C.addressof(arr), n, flags, C.addressof(out)))
         return [tuple(out[i]) for i in range(n)]
 
     def glyph_coverage_batch_stats(self) -> dict:
-        """what the last put_glyph_coverage_batch did: glyphs, written, dropped_by_growth, tiles, edges (flattened lines), launches, bytes_copied"""
+        """what the last put_glyph_coverage_batch or put_glyph_coverage_batch_cubic did: glyphs, written, dropped_by_growth, tiles, edges (flattened lines), launches, bytes_copied"""
         st = GlyphBatchStats()
         self._ck(self.L.fdh_glyph_coverage_batch_stats(self.h, C.byref(st)))
         return {name: int(getattr(st, name)) for name, _ in GlyphBatchStats._fields_}

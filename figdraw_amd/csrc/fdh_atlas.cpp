@@ -8,6 +8,7 @@
 #include <climits>
 #include <cstring>
 #include <exception>
+#include <string>
 
 namespace fdh {
 
@@ -500,6 +501,13 @@ void Atlas::put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int
       if (device_) { msdf::edge_records(shape, &one); rec.insert(rec.end(), one.begin(), one.end()); }
     }
   }
+  field_batch(s, glyphs, n, out_rects, tab, rec, msdf::kEdgeFloats, texels, correct, overlap ? FieldKernels::overlap : FieldKernels::plain);
+}
+// Passes 2 and 3 of a batch of distance fields, whose pass 1 (the caller's) left `tab` (edge_off in records of `stride` floats, n_edges, w, h,
+// orient and the range) and `rec`, the records of all glyphs; `texels`: the sum of w * h.  put_glyph_outlines' and put_glyph_outlines_cubic's:
+// the record stride and the two kernels are what differs.
+void Atlas::field_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, int (*out_rects)[4], std::vector<msdf::BatchGlyph>& tab, const std::vector<float>& rec,
+                        size_t stride, int64_t texels, bool correct, FieldKernels kernels) {
   batch_stats_ = FdhGlyphBatchStats{};
   batch_stats_.glyphs = n;
   if (n == 0) return;
@@ -507,7 +515,7 @@ void Atlas::put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int
   if (device_) {
     glyph_a_.reserve((size_t)texels);
     glyph_b_.reserve((size_t)texels);
-    glyph_edges_.reserve(std::max<size_t>(rec.size(), msdf::kEdgeFloats));
+    glyph_edges_.reserve(std::max<size_t>(rec.size(), stride));
     glyph_tab_.reserve(batch_table_words(tab, true));
   }
   // ---- pass 2: the places
@@ -521,17 +529,20 @@ void Atlas::put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int
     const uint32_t edge_base = tab[(size_t)first].edge_off;
     BatchTables T;
     batch_tables(tab, first, m, true, &T);
-    const float* rec_first = rec.data() + (size_t)edge_base * msdf::kEdgeFloats;
-    const size_t rec_floats = rec.size() - (size_t)edge_base * msdf::kEdgeFloats;
+    const float* rec_first = rec.data() + (size_t)edge_base * stride;
+    const size_t rec_floats = rec.size() - (size_t)edge_base * stride;
     if (rec_floats) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec_first, rec_floats * sizeof(float), hipMemcpyHostToDevice, s));
     FDH_HIP(hipMemcpyAsync(glyph_tab_.ptr, T.words.data(), T.words.size() * 4, hipMemcpyHostToDevice, s));
     const msdf::BatchGlyph* d_glyphs = reinterpret_cast<const msdf::BatchGlyph*>(glyph_tab_.ptr);
     const uint32_t* d_tiles = glyph_tab_.ptr + (size_t)m * kBatchGlyphWords;
     uint32_t *field = glyph_a_.ptr, *spare = glyph_b_.ptr;
+    const bool overlap = kernels == FieldKernels::overlap;
     int launches = 1;
-    launch_msdf_generate_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)T.n_tiles, field);
+    if (kernels == FieldKernels::cubic) launch_msdf_generate_cubic_batch(s, glyph_edges_.ptr, d_glyphs, d_tiles, (int)T.n_tiles, field);
+    else launch_msdf_generate_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)T.n_tiles, field);
     if (correct) {
-      launch_msdf_correct_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)T.n_tiles, field, spare);
+      if (kernels == FieldKernels::cubic) launch_msdf_correct_cubic_batch(s, glyph_edges_.ptr, d_glyphs, d_tiles, (int)T.n_tiles, field, spare);
+      else launch_msdf_correct_batch(s, overlap, glyph_edges_.ptr, d_glyphs, d_tiles, (int)T.n_tiles, field, spare);
       std::swap(field, spare);
       launches++;
     }
@@ -545,43 +556,124 @@ void Atlas::put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int
   }
   if (failed) std::rethrow_exception(failed);
 }
-// fdh_put_glyph_coverage_batch (the specification: include_glyphs/figdraw_hip_coverage.h).  What n coverage calls of put_glyph_outline do, in the three
+// fdh_put_glyph_outlines_cubic (the specification: include_glyphs/figdraw_hip_cubic_batch.h): put_glyph_outlines for segments of 8 floats.  Without a
+// cubic in any glyph it IS that call, on six-float copies of the segments.  With one, every glyph -- those without a cubic too -- goes the cubic
+// call's way: mc::build_shape, records of mc::kCubicEdgeFloats floats, and the batched kernels of k_msdf_cubic.hip, in which a line or a
+// quadratic runs k_msdf.hip's expressions: such a glyph gets the bytes its single call (put_glyph_mtsdf) gives it.
+void Atlas::put_glyph_outlines_cubic(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) {
+  namespace mc = msdf::cubic;
+  // ---- pass 1: validation.  Nothing below this pass refuses a glyph.
+  if (flags & ~(uint32_t)(FDH_GLYPH_MTSDF | FDH_GLYPH_MTSDF_CORRECT | FDH_GLYPH_MTSDF_OVERLAP | 0xFF00u))
+    throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: unknown flag (coverage glyphs are fdh_put_glyph_coverage_batch_cubic's)");
+  if (!(flags & FDH_GLYPH_MTSDF)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: needs FDH_GLYPH_MTSDF");
+  const uint32_t flag_range = (flags >> 8) & 255u;
+  if (flag_range > 64u) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: a distance range is at most 64");
+  if (n < 0 || (n > 0 && !glyphs)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: bad glyph array");
+  if (n > 65535) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: at most 65535 glyphs");
+  int64_t texels = 0, segments = 0;
+  bool any_cubic = false;
+  for (int i = 0; i < n; i++) {
+    const FdhGlyphOutline& g = glyphs[i];
+    if (g.width <= 0 || g.height <= 0 || g.width > 4096 || g.height > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: image size must be in 1..4096");
+    if (g.n_segs < 0 || (g.n_segs > 0 && !g.segs)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: bad outline");
+    if (g.n_segs > msdf::kMaxSegments) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: a distance field takes at most 65535 segments");
+    if (g.sdf_range > 64u) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: a distance range is at most 64");
+    texels += (int64_t)g.width * g.height;
+    segments += g.n_segs;
+    any_cubic = any_cubic || mc::holds_cubic(g.segs, g.n_segs);
+  }
+  if (texels > ((int64_t)1 << 24)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: at most 2^24 texels in a batch");
+  if (segments > ((int64_t)1 << 20)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: at most 2^20 segments in a batch");
+  if (!any_cubic) {  // the six-float batch, on copies
+    std::vector<std::vector<float>> six((size_t)n);
+    std::vector<FdhGlyphOutline> plain(glyphs, glyphs + n);
+    for (int i = 0; i < n; i++) {
+      mc::to_quadratic_format(glyphs[i].segs, glyphs[i].n_segs, &six[(size_t)i]);
+      plain[(size_t)i].segs = six[(size_t)i].data();
+    }
+    put_glyph_outlines(s, plain.data(), n, flags, out_rects);
+    return;
+  }
+  if (flags & FDH_GLYPH_MTSDF_OVERLAP) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: FDH_GLYPH_MTSDF_OVERLAP takes no cubic segment");
+  std::vector<float> rec, one;                   // the records of all glyphs, glyph after glyph (a device context only)
+  std::vector<msdf::BatchGlyph> tab((size_t)n);  // edge_off (in records of mc::kCubicEdgeFloats floats), n_edges, w, h, orient and the range now
+  {
+    mc::Shape shape;
+    for (int i = 0; i < n; i++) {
+      const FdhGlyphOutline& g = glyphs[i];
+      if (!mc::build_shape(g.segs, g.n_segs, &shape)) throw Error(FDH_ERR_INVALID, "put_glyph_outlines_cubic: a distance field needs closed contours");
+      const float range = g.sdf_range ? (float)g.sdf_range : (flag_range ? (float)flag_range : 4.0f);
+      msdf::BatchGlyph& t = tab[(size_t)i];
+      t = msdf::BatchGlyph{};
+      t.edge_off = (uint32_t)(rec.size() / mc::kCubicEdgeFloats); t.n_edges = (int32_t)shape.edges.size();
+      t.w = g.width; t.h = g.height;
+      t.orient = (float)shape.orient; t.inv_range = 1.0f / range; t.step = range / 255.0f;
+      if (device_) { mc::edge_records(shape, &one); rec.insert(rec.end(), one.begin(), one.end()); }
+    }
+  }
+  field_batch(s, glyphs, n, out_rects, tab, rec, mc::kCubicEdgeFloats, texels, (flags & FDH_GLYPH_MTSDF_CORRECT) != 0, FieldKernels::cubic);
+}
+// the two segment formats of a coverage batch: the floats of a segment, its line count, and the flattening of an outline
+struct Atlas::OutlineFormat {
+  const char* who;          // the call's name in its error messages
+  const char* fields_call;  // the batch that takes distance fields of this format: what a refused flag points to
+  int floats;
+  int (*lines_of)(const float* seg);
+  void (*flatten)(const float* segs, int n, std::vector<float>* lines);
+};
+// fdh_put_glyph_coverage_batch: coverage_batch below on segments of 6 floats
+void Atlas::put_glyph_coverage_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) {
+  static const OutlineFormat six = {"put_glyph_coverage_batch", "fdh_put_glyph_outlines'", 6, [](const float* q) { return q[2] != q[2] ? 1 : flatten_count(q); }, flatten_outline};
+  coverage_batch(s, six, glyphs, n, flags, out_rects);
+}
+// fdh_put_glyph_coverage_batch_cubic (the specification: include_glyphs/figdraw_hip_cubic_batch.h): the same passes and the same launches on the lines
+// the single cubic call makes of each outline (msdf::cubic::flatten_outline)
+void Atlas::put_glyph_coverage_batch_cubic(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) {
+  static const OutlineFormat eight = {"put_glyph_coverage_batch_cubic", "fdh_put_glyph_outlines_cubic's", 8,
+                                      [](const float* q) {
+                                        if (q[2] != q[2]) return 1;
+                                        if (q[4] == q[4]) return msdf::cubic::cubic_flatten_count(q);
+                                        const float six[6] = {q[0], q[1], q[2], q[3], q[6], q[7]};
+                                        return flatten_count(six);
+                                      },
+                                      msdf::cubic::flatten_outline};
+  coverage_batch(s, eight, glyphs, n, flags, out_rects);
+}
+// The coverage batch in either format (the specifications: include_glyphs/figdraw_hip_coverage.h and figdraw_hip_cubic_batch.h).  What n coverage calls of put_glyph_outline do, in the three
 // passes of put_glyph_outlines: every glyph validated and its outline flattened into one array of lines; every glyph placed, in order; then
 // the glyphs still in the atlas get their texels: two launches make the coverage of all of them (k_coverage_cells_batch, k_coverage_sum_batch),
 // one filters it (k_lcd_filter_batch), and every atlas level takes one blit and one minify.  A glyph 1 texel wide or high is placed
 // and has no tiles: a single put stores nothing of it.
-void Atlas::put_glyph_coverage_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) {
+void Atlas::coverage_batch(hipStream_t s, const OutlineFormat& fmt, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) {
+  auto bad = [&fmt](const std::string& what) { return Error(FDH_ERR_INVALID, std::string(fmt.who) + ": " + what); };
   // ---- pass 1: validation.  Nothing below this pass refuses a glyph.  (FDH_GLYPH_LCD_CONTEXT is resolved by the context.)
   if (flags & ~(uint32_t)(FDH_GLYPH_LCD_FILTER | FDH_GLYPH_LCD_CONTEXT))
-    throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: the LCD flags only (distance fields are fdh_put_glyph_outlines')");
-  if (n < 0 || (n > 0 && !glyphs)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: bad glyph array");
-  if (n > 65535) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: at most 65535 glyphs");
+    throw bad(std::string("the LCD flags only (distance fields are ") + fmt.fields_call + ")");
+  if (n < 0 || (n > 0 && !glyphs)) throw bad("bad glyph array");
+  if (n > 65535) throw bad("at most 65535 glyphs");
   std::vector<msdf::BatchGlyph> tab((size_t)n);  // edge_off, n_edges: the glyph's first line and its line count; orient, inv_range, step: unused
   int64_t texels = 0, segments = 0, n_lines = 0;
   for (int i = 0; i < n; i++) {
     const FdhGlyphOutline& g = glyphs[i];
-    if (g.width <= 0 || g.height <= 0 || g.width > 4096 || g.height > 4096) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: image size must be in 1..4096");
-    if (g.n_segs < 0 || (g.n_segs > 0 && !g.segs)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: bad outline");
-    if (g.sdf_range) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: a coverage glyph has no distance range");
+    if (g.width <= 0 || g.height <= 0 || g.width > 4096 || g.height > 4096) throw bad("image size must be in 1..4096");
+    if (g.n_segs < 0 || (g.n_segs > 0 && !g.segs)) throw bad("bad outline");
+    if (g.sdf_range) throw bad("a coverage glyph has no distance range");
     texels += (int64_t)g.width * g.height;
     segments += g.n_segs;
-    if (segments > ((int64_t)1 << 20)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: at most 2^20 segments in a batch");
+    if (segments > ((int64_t)1 << 20)) throw bad("at most 2^20 segments in a batch");
     msdf::BatchGlyph& t = tab[(size_t)i];
     t = msdf::BatchGlyph{};
     t.w = g.width; t.h = g.height;
     t.edge_off = (uint32_t)n_lines;
-    for (int k = 0; k < g.n_segs; k++) {
-      const float* q = g.segs + 6 * (size_t)k;
-      t.n_edges += q[2] != q[2] ? 1 : flatten_count(q);
-    }
+    for (int k = 0; k < g.n_segs; k++) t.n_edges += fmt.lines_of(g.segs + (size_t)fmt.floats * k);
     n_lines += t.n_edges;
   }
-  if (texels > ((int64_t)1 << 24)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: at most 2^24 texels in a batch");
-  if (n_lines > ((int64_t)1 << 22)) throw Error(FDH_ERR_INVALID, "put_glyph_coverage_batch: at most 2^22 flattened lines in a batch");
+  if (texels > ((int64_t)1 << 24)) throw bad("at most 2^24 texels in a batch");
+  if (n_lines > ((int64_t)1 << 22)) throw bad("at most 2^22 flattened lines in a batch");
   std::vector<float> lines;  // of all glyphs, glyph after glyph (a device context only)
   if (device_) {
     lines.reserve((size_t)n_lines * 4);
-    for (int i = 0; i < n; i++) flatten_outline(glyphs[i].segs, glyphs[i].n_segs, &lines);
+    for (int i = 0; i < n; i++) fmt.flatten(glyphs[i].segs, glyphs[i].n_segs, &lines);
   }
   coverage_stats_ = FdhGlyphBatchStats{};
   coverage_stats_.glyphs = n;

@@ -7,8 +7,8 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include_glyphs/figdraw_hip_cubic.h"  // fdh_put_glyph_outline_cubic
-#include "../../include_glyphs/figdraw_hip_coverage.h"  // FdhGlyphOutline, FdhGlyphBatchStats (figdraw_hip_glyphs.h) and the coverage batch
+#include "../../include_glyphs/figdraw_hip_cubic_batch.h"  // the two cubic batches; and through it figdraw_hip_cubic.h (fdh_put_glyph_outline_cubic),
+                                                            // figdraw_hip_coverage.h (the coverage batch), figdraw_hip_glyphs.h (FdhGlyphOutline, FdhGlyphBatchStats)
 #include "fdh_memory.h"  // DeviceBuf
 #include "fdh_types.h"   // AtlasView, kMaxMips
 
@@ -56,9 +56,13 @@ class Atlas {
   void put_glyph_outline_cubic(hipStream_t s, int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]);
   // fdh_put_glyph_outlines (the specification: include_glyphs/figdraw_hip_glyphs.h): n distance fields, validated as a whole, placed in order, made in one go
   void put_glyph_outlines(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
+  // fdh_put_glyph_outlines_cubic (the specification: include_glyphs/figdraw_hip_cubic_batch.h): put_glyph_outlines for segments of 8 floats
+  void put_glyph_outlines_cubic(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
   const FdhGlyphBatchStats& glyph_batch_stats() const { return batch_stats_; }
   // fdh_put_glyph_coverage_batch (the specification: include_glyphs/figdraw_hip_coverage.h): n coverage glyphs, validated as a whole, placed in order, made in one go
   void put_glyph_coverage_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
+  // fdh_put_glyph_coverage_batch_cubic (the specification: include_glyphs/figdraw_hip_cubic_batch.h): put_glyph_coverage_batch for segments of 8 floats
+  void put_glyph_coverage_batch_cubic(hipStream_t s, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
   const FdhGlyphBatchStats& glyph_coverage_batch_stats() const { return coverage_stats_; }
   void put_mips(hipStream_t s, int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]);
   void put_flippy(hipStream_t s, int64_t key, const uint8_t* data, size_t n, int out_rect[4]);
@@ -84,6 +88,12 @@ class Atlas {
   std::exception_ptr place_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, int (*out_rects)[4], std::vector<msdf::BatchGlyph>& tab, int* first, int* placed);
   void batch_tables(std::vector<msdf::BatchGlyph>& tab, int first, int m, bool thin_tiles, BatchTables* T) const;
   int batch_level_chain(hipStream_t s, int m, const BatchTables& T, uint32_t* field, uint32_t* spare);
+  // passes 2 and 3 of the two batches of distance fields (the record stride and the kernels differ); the coverage batch in its two segment formats
+  enum class FieldKernels { plain, overlap, cubic };
+  void field_batch(hipStream_t s, const FdhGlyphOutline* glyphs, int n, int (*out_rects)[4], std::vector<msdf::BatchGlyph>& tab, const std::vector<float>& rec, size_t stride,
+                   int64_t texels, bool correct, FieldKernels kernels);
+  struct OutlineFormat;
+  void coverage_batch(hipStream_t s, const OutlineFormat& fmt, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
 
   bool device_ = false;
   int size_ = 0, initial_size_ = 0, margin_ = 4, n_levels_ = 0;
@@ -94,7 +104,7 @@ class Atlas {
   DeviceBuf<uint32_t> glyph_a_, glyph_b_;  // the device glyph pipeline: the raster and its filtered / minified successors
   DeviceBuf<float> glyph_lines_, glyph_acc_, glyph_edges_;  // flattened outline, area accumulators; the edge records of a distance field (fdh_msdf_host.h)
   DeviceBuf<uint32_t> glyph_tab_;  // put_glyph_outlines: the glyph records (msdf::BatchGlyph), the tile -> glyph words, the owner bits of the deep levels
-  FdhGlyphBatchStats batch_stats_ = {}, coverage_stats_ = {};  // of the last put_glyph_outlines, of the last put_glyph_coverage_batch
+  FdhGlyphBatchStats batch_stats_ = {}, coverage_stats_ = {};  // of the last put_glyph_outlines, of the last put_glyph_coverage_batch (either in either segment format)
 };
 
 }  // namespace fdh

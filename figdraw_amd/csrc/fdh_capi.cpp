@@ -195,6 +195,9 @@ int fdh_put_glyph_outline_cubic(FdhContext* c, int64_t key, int w, int h, const 
 int fdh_put_glyph_outlines(FdhContext* c, const FdhGlyphOutline* glyphs, int n_glyphs, uint32_t flags, int (*out_rects)[4]) {
   return guard([&] { C(c)->put_glyph_outlines(glyphs, n_glyphs, flags, out_rects); });
 }
+int fdh_put_glyph_outlines_cubic(FdhContext* c, const FdhGlyphOutline* glyphs, int n_glyphs, uint32_t flags, int (*out_rects)[4]) {
+  return guard([&] { C(c)->put_glyph_outlines_cubic(glyphs, n_glyphs, flags, out_rects); });
+}
 int fdh_glyph_batch_stats(FdhContext* c, FdhGlyphBatchStats* out) {
   return guard([&] {
     if (!out) throw fdh::Error(FDH_ERR_INVALID, "fdh_glyph_batch_stats: null pointer");
@@ -204,6 +207,9 @@ int fdh_glyph_batch_stats(FdhContext* c, FdhGlyphBatchStats* out) {
 int fdh_sizeof_glyph_outline(void) { return (int)sizeof(FdhGlyphOutline); }
 int fdh_put_glyph_coverage_batch(FdhContext* c, const FdhGlyphOutline* glyphs, int n_glyphs, uint32_t flags, int (*out_rects)[4]) {
   return guard([&] { C(c)->put_glyph_coverage_batch(glyphs, n_glyphs, flags, out_rects); });
+}
+int fdh_put_glyph_coverage_batch_cubic(FdhContext* c, const FdhGlyphOutline* glyphs, int n_glyphs, uint32_t flags, int (*out_rects)[4]) {
+  return guard([&] { C(c)->put_glyph_coverage_batch_cubic(glyphs, n_glyphs, flags, out_rects); });
 }
 int fdh_glyph_coverage_batch_stats(FdhContext* c, FdhGlyphBatchStats* out) {
   return guard([&] {

@@ -151,8 +151,10 @@ class Context : public Recorder {
   void remove_image(int64_t key) { atlas_.remove(key); }
   void put_glyph_outline_cubic(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) { sync(); atlas_.put_glyph_outline_cubic(stream_, key, w, h, segs, n, resolve_lcd(flags), out_rect); }
   void put_glyph_outlines(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_outlines(stream_, glyphs, n, flags, out_rects); }
+  void put_glyph_outlines_cubic(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_outlines_cubic(stream_, glyphs, n, flags, out_rects); }
   const FdhGlyphBatchStats& glyph_batch_stats() const { return atlas_.glyph_batch_stats(); }
   void put_glyph_coverage_batch(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_coverage_batch(stream_, glyphs, n, resolve_lcd(flags), out_rects); }
+  void put_glyph_coverage_batch_cubic(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_coverage_batch_cubic(stream_, glyphs, n, resolve_lcd(flags), out_rects); }
   const FdhGlyphBatchStats& glyph_coverage_batch_stats() const { return atlas_.glyph_coverage_batch_stats(); }
   bool has_image(int64_t key) const { return atlas_.has(key); }
   void reset_atlas(int minimum_size) { sync(); atlas_.reset(minimum_size, stream_); }

@@ -150,6 +150,11 @@ namespace msdf { struct BatchGlyph; }
 void launch_msdf_generate_batch(hipStream_t s, bool overlap, const float* edges, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, uint32_t* out);
 void launch_msdf_correct_batch(hipStream_t s, bool overlap, const float* edges, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* in,
                                uint32_t* out);
+// fdh_put_glyph_outlines_cubic (include_glyphs/figdraw_hip_cubic_batch.h; k_msdf_cubic.hip): the two launches above over records of
+// msdf::cubic::kCubicEdgeFloats floats, in which a glyph's edge_off counts.  (No `overlap`: step 6 takes no cubic.)
+void launch_msdf_generate_cubic_batch(hipStream_t s, const float* edges, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, uint32_t* out);
+void launch_msdf_correct_cubic_batch(hipStream_t s, const float* edges, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* in,
+                                     uint32_t* out);
 void launch_atlas_blit_batch(hipStream_t s, uint32_t* level, int LS, int l, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* owner,
                              const uint32_t* src);
 void launch_minify2_batch(hipStream_t s, int l, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* src, uint32_t* dst);

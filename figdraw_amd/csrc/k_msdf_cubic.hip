@@ -371,6 +371,154 @@ __global__ __launch_bounds__(64) void k_msdf_correct_cubic(const float* __restri
   if (live) out[(size_t)y * w + x] = mark ? ((c & 0xFF000000u) | (uint32_t)msdf_median(c) * 0x010101u) : c;
 }
 
+// ------------------------------------------------------------------ the two kernel bodies as functions of the tile origin
+// k_msdf_generate_cubic and k_msdf_correct_cubic once more, statement for statement, with the tile's origin (tx0, ty0) a parameter where the
+// kernels take it from blockIdx: what the batched kernels below run on one glyph's slice of a concatenated buffer (k_msdf.hip's pattern,
+// for its reason: the kernels above do not call these, so they keep their instruction streams -- profiles/msdf.txt sections 6 and 8).
+// tests/msdf_cubic_batch_emu holds the two forms to the same bytes, glyph by glyph.
+__device__ __forceinline__ void cubic_generate_tile(const float* edges, int n_edges, int w, int h, float orient, float inv_range, uint32_t* out, int tx0, int ty0) {
+#pragma clang fp contract(off)
+  const int x = tx0 + (threadIdx.x & 7), y = ty0 + (threadIdx.x >> 3);
+  if (x >= w || y >= h) return;
+  const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+#if !FDH_MSDF_NO_CULL
+  // k_msdf_generate's cull: an end point bounds every carried channel from above, the control box (of all four points, for a cubic:
+  // it holds the curve) bounds the edge from below
+  constexpr float kHalfDiag = 4.9497475f + 1.0e-3f;
+  const float mx = (float)tx0 + 4.0f, my = (float)ty0 + 4.0f;
+  float ub[3] = {3.0e38f, 3.0e38f, 3.0e38f};
+  for (int i = 0; i < n_edges; i++) {
+    const float* __restrict__ r = edges + (size_t)i * kRec;
+    const float ux = r[0] - mx, uy = r[1] - my, vx = r[4] - mx, vy = r[5] - my;
+    const float u = fsqrt(__builtin_fminf(ux * ux + uy * uy, vx * vx + vy * vy)) + kHalfDiag;
+    const int mask = (int)r[6];
+#pragma unroll
+    for (int c = 0; c < 3; c++) if ((mask >> c) & 1) ub[c] = __builtin_fminf(ub[c], u);
+  }
+#endif
+  float bd2[4], bo[4], bt[4];
+  int be[4];
+#pragma unroll
+  for (int c = 0; c < 4; c++) { bd2[c] = 3.0e38f; bo[c] = -1.0f; bt[c] = 0.0f; be[c] = -1; }
+  for (int i = 0; i < n_edges; i++) {
+    const float* __restrict__ r = edges + (size_t)i * kRec;
+    const int mask = (int)r[6];
+#if !FDH_MSDF_NO_CULL
+    {
+      const float gx = __builtin_fmaxf(__builtin_fmaxf(r[20] - mx, mx - r[22]), 0.0f), gy = __builtin_fmaxf(__builtin_fmaxf(r[21] - my, my - r[23]), 0.0f);
+      const float lb = fsqrt(gx * gx + gy * gy) - kHalfDiag;
+      float um = 0.0f;
+#pragma unroll
+      for (int c = 0; c < 3; c++) if ((mask >> c) & 1) um = __builtin_fmaxf(um, ub[c]);
+      if (lb > um * 1.0001f) continue;  // wave-uniform
+    }
+#endif
+    float t, d2, ortho, side;
+    edge_offer(r, px, py, t, d2, ortho, side);
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      if (c < 3 && !((mask >> c) & 1)) continue;  // wave-uniform
+      const bool better = d2 < bd2[c] || (d2 == bd2[c] && ortho > bo[c]);
+      bd2[c] = better ? d2 : bd2[c]; bo[c] = better ? ortho : bo[c]; bt[c] = better ? t : bt[c]; be[c] = better ? i : be[c];
+    }
+  }
+  uint32_t word = 0;
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    float d = -3.0e38f;  // no edge: outside
+    if (be[c] >= 0) {
+      const float* __restrict__ r = edges + (size_t)be[c] * kRec;
+      float Ex, Ey, Tx, Ty;
+      edge_at(r, bt[c], px, py, Ex, Ey, Tx, Ty);
+      // the vector to the texel is -E: cross(T, p - N) = Ty Ex - Tx Ey
+      const float cr = Ty * Ex - Tx * Ey;
+      d = fsqrt(bd2[c]);
+      d = cr >= 0.0f ? d : -d;
+      if (c < 3 && (bt[c] <= 0.0f || bt[c] >= 1.0f)) {  // the nearest point is an end: the distance to the tangent line there
+        const float ux = bt[c] <= 0.0f ? r[16] : r[18], uy = bt[c] <= 0.0f ? r[17] : r[19];
+        const float pd = uy * Ex - ux * Ey;
+        d = __builtin_fabsf(pd) <= __builtin_fabsf(d) ? pd : d;
+      }
+      d *= orient;
+    }
+    const float v = clamp01(0.5f + d * inv_range);
+    word |= (uint32_t)__builtin_floorf(255.0f * v + 0.5f) << (8 * c);
+  }
+  out[(size_t)y * w + x] = word;
+}
+__device__ __forceinline__ void cubic_correct_tile(const float* edges, int n_edges, int w, int h, float orient, float step, const uint32_t* in, uint32_t* out,
+                                                   int tx0, int ty0) {
+#pragma clang fp contract(off)
+  const int x = tx0 + (threadIdx.x & 7), y = ty0 + (threadIdx.x >> 3);
+  const bool live = x < w && y < h;
+  const int cx = x < w ? x : w - 1, cy = y < h ? y : h - 1;  // what is loaded lies inside the image whatever the lane
+  const int xl = cx > 0 ? cx - 1 : 0, xr = cx + 1 < w ? cx + 1 : w - 1, yu = cy > 0 ? cy - 1 : 0, yd = cy + 1 < h ? cy + 1 : h - 1;
+  const uint32_t c = in[(size_t)cy * w + cx];
+  const uint32_t nb[4] = {in[(size_t)cy * w + xl], in[(size_t)cy * w + xr], in[(size_t)yu * w + cx], in[(size_t)yd * w + cx]};
+  const bool has[4] = {live && x > 0, live && x + 1 < w, live && y > 0, live && y + 1 < h};
+  uint32_t todo = 0;
+#pragma unroll
+  for (int p = 0; p < 4; p++) {
+#pragma unroll
+    for (int cp = 0; cp < 3; cp++) {
+      int N, D;
+      bool inside;
+      const bool cand = msdf_candidate((p & 1) ? c : nb[p], (p & 1) ? nb[p] : c, cp, N, D, inside);
+      todo |= (uint32_t)(cand & has[p] & (n_edges > 0)) << (3 * p + cp);
+    }
+  }
+  const int depth = msdf_depth(c);
+  bool mark = false;
+  while (FDH_MSDF_ANY(todo != 0)) {  // wave-uniform
+    const int bit = todo ? __builtin_ctz(todo) : 0, p = bit / 3, cp = bit - 3 * p;
+    const uint32_t other = p == 0 ? nb[0] : (p == 1 ? nb[1] : (p == 2 ? nb[2] : nb[3]));
+    int N, D;
+    bool inside;
+    const bool cand = msdf_candidate((p & 1) ? c : other, (p & 1) ? other : c, cp, N, D, inside) & (todo != 0);
+    const float t = cand ? (float)N / (float)D : 0.0f;
+    const float ax = (float)(x - (p == 0 ? 1 : 0)) + 0.5f, ay = (float)(y - (p == 2 ? 1 : 0)) + 0.5f;
+    const float qx = p < 2 ? ax + t : ax, qy = p < 2 ? ay : ay + t;
+    float bd2 = 3.0e38f, bo = -1.0f, bs = 0.0f;
+    for (int i = 0; i < n_edges; i++) {
+      const float* __restrict__ r = edges + (size_t)i * kRec;
+      float te, d2, ortho, side;
+      edge_offer(r, qx, qy, te, d2, ortho, side);
+      const bool better = d2 < bd2 || (d2 == bd2 && ortho > bo);
+      bd2 = better ? d2 : bd2; bo = better ? ortho : bo; bs = better ? side : bs;
+    }
+    float d = fsqrt(bd2);
+    d = (bs >= 0.0f ? d : -d) * orient;
+    // a point within one quantisation step of the outline convicts nobody
+    const bool artefact = cand && (inside ? d < -step : d > step);
+    mark = mark | (artefact & (depth >= msdf_depth(other)));
+    todo &= todo - 1u;
+  }
+  if (live) out[(size_t)y * w + x] = mark ? ((c & 0xFF000000u) | (uint32_t)msdf_median(c) * 0x010101u) : c;
+}
+
+// ------------------------------------------------------------------ fdh_put_glyph_outlines_cubic: a batch of fields in one launch
+// (the specification: include_glyphs/figdraw_hip_cubic_batch.h).  k_msdf_generate_batch and k_msdf_correct_batch of k_msdf.hip over the wider records:
+// a 1-D grid over all 8 x 8 tiles of all glyphs, the tile's glyph (tile_glyph) and the glyph's record (msdf::BatchGlyph, fdh_msdf_host.h;
+// edge_off counts records of kRec floats) read from blockIdx alone -- scalar loads, as the edge records behind them.  A tile lies inside
+// its glyph's tile grid, so a store goes to the glyph's own w x h texels and nowhere else.  A glyph without a cubic has records of lines
+// and quadratics only and runs k_msdf.hip's statements on them: its bytes are k_msdf_generate's and k_msdf_correct's.
+#define FDH_CUBIC_BATCH_TILE                                                                     \
+  const msdf::BatchGlyph g = glyphs[tile_glyph[blockIdx.x]];                                     \
+  const int tile = (int)(blockIdx.x - g.first_tile), tiles_x = (g.w + 7) / 8;                    \
+  const int ty0 = tile / tiles_x * 8, tx0 = (tile - tile / tiles_x * tiles_x) * 8;               \
+  const float* __restrict__ rec = edges + (size_t)g.edge_off * kRec
+__global__ __launch_bounds__(64) void k_msdf_generate_cubic_batch(const float* __restrict__ edges, const msdf::BatchGlyph* __restrict__ glyphs,
+                                                                  const uint32_t* __restrict__ tile_glyph, uint32_t* __restrict__ out) {
+  FDH_CUBIC_BATCH_TILE;
+  cubic_generate_tile(rec, g.n_edges, g.w, g.h, g.orient, g.inv_range, out + g.field_off, tx0, ty0);
+}
+__global__ __launch_bounds__(64) void k_msdf_correct_cubic_batch(const float* __restrict__ edges, const msdf::BatchGlyph* __restrict__ glyphs,
+                                                                 const uint32_t* __restrict__ tile_glyph, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  FDH_CUBIC_BATCH_TILE;
+  cubic_correct_tile(rec, g.n_edges, g.w, g.h, g.orient, g.step, in + g.field_off, out + g.field_off, tx0, ty0);
+}
+#undef FDH_CUBIC_BATCH_TILE
+
 }  // namespace cubic
 
 void launch_msdf_generate_cubic(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, uint32_t* out) {
@@ -380,6 +528,15 @@ void launch_msdf_generate_cubic(hipStream_t s, const float* edges, int n_edges, 
 void launch_msdf_correct_cubic(hipStream_t s, const float* edges, int n_edges, int w, int h, float orient, float range, const uint32_t* in, uint32_t* out) {
   if (w <= 0 || h <= 0) return;
   FDH_LAUNCH(cubic::k_msdf_correct_cubic, dim3((w + 7) / 8, (h + 7) / 8), dim3(64), 0, s, edges, n_edges, w, h, orient, range / 255.0f, in, out);
+}
+void launch_msdf_generate_cubic_batch(hipStream_t s, const float* edges, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, uint32_t* out) {
+  if (n_tiles <= 0) return;
+  FDH_LAUNCH(cubic::k_msdf_generate_cubic_batch, dim3(n_tiles), dim3(64), 0, s, edges, glyphs, tile_glyph, out);
+}
+void launch_msdf_correct_cubic_batch(hipStream_t s, const float* edges, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* in,
+                                     uint32_t* out) {
+  if (n_tiles <= 0) return;
+  FDH_LAUNCH(cubic::k_msdf_correct_cubic_batch, dim3(n_tiles), dim3(64), 0, s, edges, glyphs, tile_glyph, in, out);
 }
 
 }  // namespace fdh

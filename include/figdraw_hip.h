@@ -260,7 +260,8 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  * (pixie_raster.nim:69-72).  Coverage = exact-area scanline accumulation (curves flattened to <= 0.025 px chord error), stored
  * premultiplied white like pixie's white paint; flags as for fdh_put_glyph_image.  pixie's own texels are third-party and
  * unpinned: the oracle restates the same published algorithm and the two agree bit for bit.
- * Many coverage glyphs in one call, the same texels from launches whose number does not depend on theirs: include_glyphs/figdraw_hip_coverage.h. */
+ * Many coverage glyphs in one call, the same texels from launches whose number does not depend on theirs: include_glyphs/figdraw_hip_coverage.h
+ * (outlines with cubic segments: include_glyphs/figdraw_hip_cubic_batch.h). */
 /* DISTANCE FIELDS.  With flags = FDH_GLYPH_MTSDF | FDH_GLYPH_SDF_RANGE(R) the same call stores, instead of coverage, the width x height
  * RGBA8 image that fdh_draw_msdf(key, ..., px_range = R, sd_threshold = 0.5, mtsdf = 0 or 1) expects -- what the reference gets at run time
  * from the third-party sdfy (generateMsdfPath / generateMtsdfPath, examples/windy_msdf_star.nim:279-286).  R, G, B hold the three channels'
@@ -354,7 +355,8 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  *    inverting on a diagonal while no pair along x or y inverts), and corner protection (step 5 does not look for corners: near one, where
  *    the channels must disagree, it relies on the verdict alone) --, a hole outside every filled contour and a contour that crosses
  *    itself (see step 6), cubic segments (this call's outline format has none: ../include_glyphs/figdraw_hip_cubic.h is the call that takes them).
- * Many glyphs at once: ../include_glyphs/figdraw_hip_glyphs.h -- a batch of these calls from a number of launches that does not depend on the number of glyphs. */
+ * Many glyphs at once: ../include_glyphs/figdraw_hip_glyphs.h -- a batch of these calls from a number of launches that does not depend on the number of glyphs;
+ * ../include_glyphs/figdraw_hip_cubic_batch.h -- the same batch, and the coverage batch, for outlines with cubic segments. */
 FDH_API int fdh_put_glyph_outline(FdhContext*, int64_t key, int width, int height, const float* segs, int n_segs, uint32_t flags, int out_rect[4]);
 /* putFlippy (glcontext.nim:610-620): `bytes` is a whole .flippy file (common/formatflippy.nim:77-149: "flip", version 1, then per
  * mip "mip!", w, h, zlen, raw-snappy straight RGBA8); every stored level is uploaded as is at (x >> l, y >> l). */

@@ -1,7 +1,7 @@
 /* figdraw_hip_cubic.h -- glyph outlines with CUBIC Bezier segments for libfigdraw_hip.so: fdh_put_glyph_outline (figdraw_hip.h) for the
  * outlines of OpenType/CFF fonts, which are cubics where TrueType's are quadratics.  Same conventions as figdraw_hip.h (plain C, every
- * call returns 0 or a negative FdhStatus, fdh_last_error() says why).  The header lives in include_glyphs/ beside figdraw_hip_glyphs.h and
- * figdraw_hip_coverage.h and reaches figdraw_hip.h by its relative path: -I include_glyphs is all a caller adds.
+ * call returns 0 or a negative FdhStatus, fdh_last_error() says why).  The header lives in include_glyphs/ beside figdraw_hip_glyphs.h,
+ * figdraw_hip_coverage.h and figdraw_hip_cubic_batch.h and reaches figdraw_hip.h by its relative path: -I include_glyphs is all a caller adds.
  *
  * Why.  fdh_put_glyph_outline takes lines and quadratics.  A caller with cubics had to flatten them, which multiplies the edges a
  * distance field walks per texel (and the call refuses more than 65535), or to approximate them by quadratics, which puts the
@@ -53,8 +53,9 @@
  *    nearest point (a cusp), the orthogonality is 0 and the sign is +.
  * 5. Correction.  Unchanged; d(q) takes the cubic edges by rule 4.
  * Not covered: a cubic that crosses itself, which joins "a contour that crosses itself" of figdraw_hip.h.
- * Out of scope: a cubic segment inside fdh_put_glyph_outlines (figdraw_hip_glyphs.h) or fdh_put_glyph_coverage_batch
- * (figdraw_hip_coverage.h) -- both batches take the 6-float format only --, and FDH_GLYPH_MTSDF_OVERLAP together with a cubic.
+ * Many such outlines at once: figdraw_hip_cubic_batch.h -- fdh_put_glyph_outlines_cubic and fdh_put_glyph_coverage_batch_cubic, the two batches
+ * (figdraw_hip_glyphs.h, figdraw_hip_coverage.h) for segments of 8 floats.
+ * Out of scope: FDH_GLYPH_MTSDF_OVERLAP together with a cubic.
  *
  * On the device.  The host makes contours, orientation, colours and one record of 36 floats per edge; k_msdf_generate_cubic is
  * k_msdf_generate over those records (a lane per texel, a wave per 8 x 8 tile, records by scalar loads, the per-tile cull with the box of

@@ -14,6 +14,10 @@ k_msdf_correct, and with FDH_GLYPH_MTSDF_OVERLAP k_msdf_generate_union), on an M
                                                the font set as ONE fdh_put_glyph_outlines (include_glyphs/figdraw_hip_glyphs.h) against 106 single puts
                                                of the parent commit's library, per flag combination, alternating, N passes each (default 2);
                                                then the batch's kernels from a rocprofv3 run of its own; writes section 6's table
+  msdf_bench.py --cubic-batch OUT --parent-lib LIB [--passes N]
+                                               the 106 skewed font outlines (tests/msdf_cubic_cases.py skewed()) as ONE fdh_put_glyph_outlines_cubic
+                                               (include_glyphs/figdraw_hip_cubic_batch.h) against 106 fdh_put_glyph_outline_cubic calls of the parent
+                                               commit's library, plain and with the correction, --batch's protocol; writes section 8's table
   msdf_bench.py --cubic OUT [--passes N]      the font set with every quadratic skewed into a cubic (tests/msdf_cubic_cases.py), three ways: native
                                                through fdh_put_glyph_outline_cubic; (a) each cubic cut into four quadratics; (b) each cubic
                                                flattened to lines at 0.025 px, both through fdh_put_glyph_outline.  Per leg the host clock around
@@ -26,7 +30,8 @@ k_msdf_correct, and with FDH_GLYPH_MTSDF_OVERLAP k_msdf_generate_union), on an M
 
 Cases: small = one glyph outline ('g' of the fixture, scaled to a 32 x 32 field, range 4); large = six glyph outlines scaled and laid side by
 side in a 256 x 256 field (about 200 segments); font = the 106 inputs of tests/msdf_cases.py, one put each (a "call" is all 106); many =
-16 383 copies of one square, as many contours, in a 16 x 16 field (40 timed calls after 5)."""
+16 383 copies of one square, as many contours, in a 16 x 16 field (40 timed calls after 5); cubicfont (--time / --trace only) = the 106 skewed
+font outlines, segments of 8 floats, one fdh_put_glyph_outline_cubic each or with --batched one fdh_put_glyph_outlines_cubic."""
 import argparse
 import json
 import os
@@ -42,6 +47,7 @@ from damage_readback_bench import _stats, _step  # noqa: E402
 
 CASES = {"small": "32 x 32, one glyph", "large": "256 x 256, six glyphs side by side", "font": "the 106 font inputs, one put each",
          "many": "16 x 16, 16383 squares"}
+TIMED_CASES = dict(CASES, cubicfont="the 106 skewed font outlines (cubic segments), one put each")  # --time / --trace; --all runs CASES
 ROUNDS = {"many": (40, 5)}  # (timed, warm-up) where 200 after 20 would take too long
 
 
@@ -54,6 +60,11 @@ def outlines(case):
         import msdf_cases
 
         return [(segs, w, h, R) for _, segs, w, h, R in msdf_cases.inputs()]
+    if case == "cubicfont":  # segments of 8 floats: put_all takes the cubic calls
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import msdf_cubic_cases
+
+        return [(segs, w, h, R) for _, segs, w, h, R in msdf_cubic_cases.skewed()]
     if case == "many":
         a, b, c, d = (2.0, 2.0), (10.0, 2.0), (10.0, 9.0), (2.0, 9.0)
         nan = float("nan")
@@ -93,6 +104,13 @@ def _context():
 
 
 def put_all(ctx, puts, first_key, correct, overlap, batched):
+    if puts[0][0].shape[1] == 8:  # cubic outlines (no overlap flag there)
+        if batched:
+            ctx.put_glyph_outlines_cubic([(first_key + i, segs, w, h, R) for i, (segs, w, h, R) in enumerate(puts)], correct=correct)
+            return
+        for i, (segs, w, h, R) in enumerate(puts):
+            ctx.put_glyph_outline_cubic(first_key + i, segs, w, h, mtsdf=True, sdf_range=R, **CORRECT[correct])
+        return
     if batched:
         ctx.put_glyph_outlines([(first_key + i, segs, w, h, R) for i, (segs, w, h, R) in enumerate(puts)], correct=correct, overlap=overlap)
         return
@@ -365,45 +383,61 @@ Hypotheses, stated before the numbers (nothing had been timed when they were wri
 """
 
 
-def run_batch(out_path, parent_lib, trace_dir, passes=2):
+CUBIC_BATCH_HEAD = """tools/msdf_bench.py --cubic-batch -- the 106 skewed font outlines (tests/msdf_cubic_cases.py skewed(): 2 335 segments of 8 floats, 1 782 of them
+cubics) as ONE fdh_put_glyph_outlines_cubic of this library against 106 fdh_put_glyph_outline_cubic calls of the parent commit's library,
+MI355X, 4096 atlas reset before every call outside the clock.  Section 6's protocol: host clock around the 106 glyphs, profiler off, 200 timed
+after 20 per leg; the legs alternate, each a process of its own, two passes per flag combination; kernels from a rocprofv3 --kernel-trace
+--stats run of its own, 60 batches.
+
+Hypotheses, stated before the numbers (nothing about the cubic path had been timed when they were written):
+  1. the batched cubic generator is several times section 6's 85 us -- a cubic edge costs 9 to 33 evaluations of the quintic and four
+     refinements of six Newton steps where a quadratic costs one closed-form solve -- but stays well under a millisecond: about 2 500 waves
+     with culling, over 256 CUs.
+  2. the 106 single cubic calls cost what section 6's single calls cost plus the heavier launches, 8 ms or more, because the idle device
+     between puts is the same; so the batch wins by about the same difference, and by a smaller ratio than 11.9 x only in so far as the
+     host's share (cubic build_shape, 36-float records: 336 KB instead of 224 KB) and the generator grew.
+  3. the correction is one more launch of the generator's order (no culling, but only the tiles with candidates walk the edges).
+"""
+
+
+def run_batch(out_path, parent_lib, trace_dir, passes=2, case="font", head=None, combos=((False, False), (False, True), (True, False), (True, True))):
     me = [sys.executable, os.path.abspath(__file__)]
-    lines = BATCH_HEAD.splitlines() + [""]
+    lines = (head or BATCH_HEAD).splitlines() + [""]
     parent_env = dict(os.environ, FIGDRAW_HIP_LIB=os.path.abspath(parent_lib))
     ok = True
-    for correct in (False, True):
-        for overlap in (False, True):
-            flag = (["--correct"] if correct else []) + (["--overlap"] if overlap else [])
-            name = " | ".join(["MTSDF"] + (["CORRECT"] if correct else []) + (["OVERLAP"] if overlap else []))
-            med = {"batch": [], "singles": []}
-            stats = None
-            for _ in range(passes):
-                for leg, cmd, env in (("batch", ["--batched"], None), ("singles", [], parent_env)):
-                    got = _step(me + ["--time", "font"] + flag + cmd, 300, env) if ok else None
-                    if got is None:
-                        ok = False
-                        break
-                    r = json.loads([ln for ln in got.strip().splitlines() if ln.startswith("{")][-1])
-                    med[leg].append((r["median_us"], r["p10_us"], r["p90_us"]))
-                    stats = r.get("batch_stats") or stats
-            if not ok:
-                break
-            d = os.path.join(trace_dir, "batch_" + "_".join(["font"] + [f.strip("-") for f in flag]))
-            got = _step(["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "-o", "t", "--"] + me + ["--trace", "font", "--batched", "--calls", "60"] + flag, 300)
-            if got is None:
-                ok = False
-                break
-            kern = _stats(d, "*kernel_stats.csv")
-            b, s1 = [m[0] for m in med["batch"]], [m[0] for m in med["singles"]]
-            spread = max(max(b) - min(b), max(s1) - min(s1))
-            lines.append(f"{name}: batch, median us per pass {', '.join(f'{m[0]:.1f} (p10 {m[1]:.1f}, p90 {m[2]:.1f})' for m in med['batch'])}; "
-                         f"106 single calls of the parent, {', '.join(f'{m[0]:.1f} (p10 {m[1]:.1f}, p90 {m[2]:.1f})' for m in med['singles'])}")
-            lines.append(f"    ratio of the means of the passes' medians {sum(s1) / sum(b):.1f} x; singles - batch {sum(s1) / len(s1) - sum(b) / len(b):.1f} us, "
-                         f"the larger spread between a leg's own passes {spread:.1f} us: {'the batch wins by more than the spread' if min(s1) - max(b) > spread else 'NOT beyond the spread'}")
-            lines.append(f"    the batch: {stats}")
-            lines.append("    kernels, us per launch (launches per batch): " + ", ".join(f"{k} {v[1] / max(v[0], 1):.2f} ({v[0] / 60:.0f}), the longest {v[2]:.1f}"
-                                                                                       for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1])))
-            lines.append(f"    kernels, us per batch in all: {sum(v[1] for v in kern.values()) / 60:.1f}")
-            print("\n".join(lines[-5:]), flush=True)
+    for correct, overlap in combos:
+        flag = (["--correct"] if correct else []) + (["--overlap"] if overlap else [])
+        name = " | ".join(["MTSDF"] + (["CORRECT"] if correct else []) + (["OVERLAP"] if overlap else []))
+        med = {"batch": [], "singles": []}
+        stats = None
+        for _ in range(passes):
+            for leg, cmd, env in (("batch", ["--batched"], None), ("singles", [], parent_env)):
+                got = _step(me + ["--time", case] + flag + cmd, 300, env) if ok else None
+                if got is None:
+                    ok = False
+                    break
+                r = json.loads([ln for ln in got.strip().splitlines() if ln.startswith("{")][-1])
+                med[leg].append((r["median_us"], r["p10_us"], r["p90_us"]))
+                stats = r.get("batch_stats") or stats
+        if not ok:
+            break
+        d = os.path.join(trace_dir, "batch_" + "_".join([case] + [f.strip("-") for f in flag]))
+        got = _step(["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "-o", "t", "--"] + me + ["--trace", case, "--batched", "--calls", "60"] + flag, 300)
+        if got is None:
+            ok = False
+            break
+        kern = _stats(d, "*kernel_stats.csv")
+        b, s1 = [m[0] for m in med["batch"]], [m[0] for m in med["singles"]]
+        spread = max(max(b) - min(b), max(s1) - min(s1))
+        lines.append(f"{name}: batch, median us per pass {', '.join(f'{m[0]:.1f} (p10 {m[1]:.1f}, p90 {m[2]:.1f})' for m in med['batch'])}; "
+                     f"106 single calls of the parent, {', '.join(f'{m[0]:.1f} (p10 {m[1]:.1f}, p90 {m[2]:.1f})' for m in med['singles'])}")
+        lines.append(f"    ratio of the means of the passes' medians {sum(s1) / sum(b):.1f} x; singles - batch {sum(s1) / len(s1) - sum(b) / len(b):.1f} us, "
+                     f"the larger spread between a leg's own passes {spread:.1f} us: {'the batch wins by more than the spread' if min(s1) - max(b) > spread else 'NOT beyond the spread'}")
+        lines.append(f"    the batch: {stats}")
+        lines.append("    kernels, us per launch (launches per batch): " + ", ".join(f"{k} {v[1] / max(v[0], 1):.2f} ({v[0] / 60:.0f}), the longest {v[2]:.1f}"
+                                                                                   for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1])))
+        lines.append(f"    kernels, us per batch in all: {sum(v[1] for v in kern.values()) / 60:.1f}")
+        print("\n".join(lines[-5:]), flush=True)
     if not ok:
         lines += ["", "INCOMPLETE: a step failed; nothing was started after it"]
     open(out_path, "w").write("\n".join(lines) + "\n")
@@ -414,6 +448,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--all", metavar="OUT")
     ap.add_argument("--batch", metavar="OUT", help="the font set as one batch against single calls of --parent-lib")
+    ap.add_argument("--cubic-batch", metavar="OUT", help="the skewed font set as one cubic batch against single cubic calls of --parent-lib")
     ap.add_argument("--cubic", metavar="OUT", help="cubic outlines natively against four quadratics per cubic and against lines")
     ap.add_argument("--time-cubic", choices=list(CUBIC_LEGS))
     ap.add_argument("--trace-cubic", choices=list(CUBIC_LEGS))
@@ -426,8 +461,8 @@ if __name__ == "__main__":
     ap.add_argument("--overlap", action="store_true", help="with --time / --trace: put with FDH_GLYPH_MTSDF_OVERLAP")
     ap.add_argument("--cases", default=",".join(CASES), help="with --all: the cases to run, comma-separated")
     ap.add_argument("--trace-dir", default=os.path.join(ROOT, "build", "msdf_trace"))
-    ap.add_argument("--time", choices=list(CASES))
-    ap.add_argument("--trace", choices=list(CASES))
+    ap.add_argument("--time", choices=list(TIMED_CASES))
+    ap.add_argument("--trace", choices=list(TIMED_CASES))
     ap.add_argument("--calls", type=int, default=60)
     a = ap.parse_args()
     unknown = [c for c in a.cases.split(",") if c not in CASES]
@@ -441,6 +476,10 @@ if __name__ == "__main__":
         trace_cubic(a.trace_cubic, a.calls if a.calls != 60 else 20)
     elif a.error_cubic:
         error_cubic(a.error_cubic)
+    elif a.cubic_batch:
+        if not a.parent_lib:
+            ap.error("--cubic-batch needs --parent-lib")
+        sys.exit(run_batch(a.cubic_batch, a.parent_lib, a.trace_dir, max(a.passes, 2), "cubicfont", CUBIC_BATCH_HEAD, ((False, False), (True, False))))
     elif a.batch:
         if not a.parent_lib:
             ap.error("--batch needs --parent-lib")
