@@ -82,6 +82,7 @@ void Context::release_device_state() {
   for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
   for (auto& e : ev_pool_) (void)hipEventDestroy(e);
   atlas_.release();
+  glyphs_.release();
   if (fb_) (void)hipFree(fb_);
   if (backdrop_) (void)hipFree(backdrop_);
   if (blur_tmp_) (void)hipFree(blur_tmp_);

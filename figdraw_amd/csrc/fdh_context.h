@@ -28,6 +28,7 @@
 #include "fdh_memory.h"       // FDH_HIP, DeviceBuf, PinnedBuf, HostVec
 #include "fdh_frame.h"        // Phase, BlurJob, Lane, Piece, FrameLayout, LaunchJob
 #include "fdh_atlas.h"        // AtlasEntry, Atlas: one member of Context
+#include "fdh_glyphs.h"       // GlyphMaker, beside it: glyphs made on the device
 #include "fdh_damage_host.h"  // DamageTracker, DamageReadback: two members of Context
 #include "fdh_retained.h"     // RetainedScene: one member of Context
 
@@ -141,21 +142,21 @@ class Context : public Recorder {
   void comm_info(int* rank, int* world) const { *rank = comm_ ? comm_rank_ : 0; *world = comm_ ? comm_world_ : 1; }
 
   // atlas (fdh_atlas.h): the context's part of a call that changes texels is sync() -- a frame in flight may still sample the atlas -- and
-  // what FDH_GLYPH_LCD_CONTEXT means here; the rest is atlas_'s
+  // what FDH_GLYPH_LCD_CONTEXT means here; the rest is atlas_'s, and for glyphs made on the device glyphs_' (fdh_glyphs.h), which places them in atlas_
   void put_image(int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]) { sync(); atlas_.put_image(stream_, key, w, h, rgba, out_rect); }
-  void put_glyph_image(int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]) { sync(); atlas_.put_glyph_image(stream_, key, w, h, rgba, resolve_lcd(flags), out_rect); }
-  void put_glyph_outline(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) { sync(); atlas_.put_glyph_outline(stream_, key, w, h, segs, n, resolve_lcd(flags), out_rect); }
+  void put_glyph_image(int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]) { sync(); glyphs_.put_glyph_image(stream_, atlas_, key, w, h, rgba, resolve_lcd(flags), out_rect); }
+  void put_glyph_outline(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) { sync(); glyphs_.put_glyph_outline(stream_, atlas_, key, w, h, segs, n, resolve_lcd(flags), out_rect); }
   void update_image(int64_t key, int w, int h, const uint8_t* rgba) { sync(); atlas_.update_image(key, w, h, rgba); }
   void put_mips(int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]) { sync(); atlas_.put_mips(stream_, key, n, ws, hs, premul_rgba, out_rect); }
   void put_flippy(int64_t key, const uint8_t* data, size_t n, int out_rect[4]) { sync(); atlas_.put_flippy(stream_, key, data, n, out_rect); }
   void remove_image(int64_t key) { atlas_.remove(key); }
-  void put_glyph_outline_cubic(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) { sync(); atlas_.put_glyph_outline_cubic(stream_, key, w, h, segs, n, resolve_lcd(flags), out_rect); }
-  void put_glyph_outlines(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_outlines(stream_, glyphs, n, flags, out_rects); }
-  void put_glyph_outlines_cubic(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_outlines_cubic(stream_, glyphs, n, flags, out_rects); }
-  const FdhGlyphBatchStats& glyph_batch_stats() const { return atlas_.glyph_batch_stats(); }
-  void put_glyph_coverage_batch(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_coverage_batch(stream_, glyphs, n, resolve_lcd(flags), out_rects); }
-  void put_glyph_coverage_batch_cubic(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); atlas_.put_glyph_coverage_batch_cubic(stream_, glyphs, n, resolve_lcd(flags), out_rects); }
-  const FdhGlyphBatchStats& glyph_coverage_batch_stats() const { return atlas_.glyph_coverage_batch_stats(); }
+  void put_glyph_outline_cubic(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) { sync(); glyphs_.put_glyph_outline_cubic(stream_, atlas_, key, w, h, segs, n, resolve_lcd(flags), out_rect); }
+  void put_glyph_outlines(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); glyphs_.put_glyph_outlines(stream_, atlas_, glyphs, n, flags, out_rects); }
+  void put_glyph_outlines_cubic(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); glyphs_.put_glyph_outlines_cubic(stream_, atlas_, glyphs, n, flags, out_rects); }
+  const FdhGlyphBatchStats& glyph_batch_stats() const { return glyphs_.glyph_batch_stats(); }
+  void put_glyph_coverage_batch(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); glyphs_.put_glyph_coverage_batch(stream_, atlas_, glyphs, n, resolve_lcd(flags), out_rects); }
+  void put_glyph_coverage_batch_cubic(const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]) { sync(); glyphs_.put_glyph_coverage_batch_cubic(stream_, atlas_, glyphs, n, resolve_lcd(flags), out_rects); }
+  const FdhGlyphBatchStats& glyph_coverage_batch_stats() const { return glyphs_.glyph_coverage_batch_stats(); }
   bool has_image(int64_t key) const { return atlas_.has(key); }
   void reset_atlas(int minimum_size) { sync(); atlas_.reset(minimum_size, stream_); }
   int atlas_size() const { return atlas_.size(); }
@@ -446,6 +447,7 @@ class Context : public Recorder {
   int staging_i_ = 0;
 
   Atlas atlas_;  // (fdh_atlas.h)
+  GlyphMaker glyphs_;  // (fdh_glyphs.h)
 
   FdhFrameStats stats_ = {};
  public:

@@ -77,44 +77,6 @@ inline Edge third(const Edge& e, int k) {
   return o;
 }
 
-// step 3 for one closed contour (edges in order); may replace it by its split form.  msdf::colour_contour, on these edges.
-inline void colour_contour(std::vector<Edge>& c) {
-  const int m = (int)c.size();
-  std::vector<int> corners;
-  const double kSin3 = std::sin(3.0);
-  for (int i = 0; i < m; i++) {  // vertex i: where edge i - 1 ends and edge i starts
-    double a0[2], a1[2], b0[2], b1[2], ix, iy, ox, oy;
-    end_tangents(c[(i + m - 1) % m], a0, a1);
-    end_tangents(c[i], b0, b1);
-    unit(a1[0], a1[1], &ix, &iy);
-    unit(b0[0], b0[1], &ox, &oy);
-    const double dot = ix * ox + iy * oy, cross = ix * oy - iy * ox;
-    if (dot <= 0.0 || std::fabs(cross) > kSin3) corners.push_back(i);
-  }
-  static const int cycle[3] = {kMagenta, kYellow, kCyan};
-  const int n = (int)corners.size();
-  if (n == 0) {
-    for (Edge& e : c) e.colour = kWhite;
-  } else if (n == 1) {
-    std::vector<Edge> r;  // from the corner round
-    for (int j = 0; j < m; j++) {
-      const Edge& e = c[(corners[0] + j) % m];
-      if (m >= 3) r.push_back(e);
-      else for (int k = 0; k < 3; k++) r.push_back(third(e, k));
-    }
-    const int mm = (int)r.size();
-    for (int j = 0; j < mm; j++) r[j].colour = cycle[3 * j / mm];
-    c.swap(r);
-  } else {
-    int run = -1, next = 0;  // walk from the first corner; `next`: index into corners of the corner ahead
-    for (int j = 0; j < m; j++) {
-      const int i = (corners[0] + j) % m;
-      if (next < n && corners[next] == i) { run++; next++; }
-      c[i].colour = (run == n - 1 && n % 3 == 1) ? (int)kYellow : cycle[run % 3];
-    }
-  }
-}
-
 struct Shape {
   std::vector<Edge> edges;   // every contour's edges, contour after contour
   std::vector<int> contour;  // the contour of each edge
@@ -195,7 +157,7 @@ inline bool build_shape(const float* segs, int n, Shape* out) {
     area += chord; own += chord;
     if (e.kind != kLine) { area += bow; own += bow; }
     if (e.p[6] == cur.front().p[0] && e.p[7] == cur.front().p[1]) {
-      colour_contour(cur);
+      colour_contour(cur);  // (msdf::colour_contour, on these edges)
       for (const Edge& c : cur) { out->edges.push_back(c); out->contour.push_back(n_contours); }
       areas.push_back(own);
       own = 0.0;
@@ -281,7 +243,7 @@ inline void edge_records(const Shape& s, std::vector<float>* rec) {
   }
 }
 
-// The coverage path: the lines (x0, y0, x1, y1) of an outline's n segments of 8 floats, appended.  Lines and quadratics: Atlas's
+// The coverage path: the lines (x0, y0, x1, y1) of an outline's n segments of 8 floats, appended.  Lines and quadratics: fdh_glyphs.cpp's
 // flatten_outline, formula for formula.  A cubic: k uniform chords; the error of a chord over an interval h of t is at most
 // h^2 / 8 max |B''|, and max |B''| = 6 max(|P0 - 2 P1 + P2|, |P1 - 2 P2 + P3|): k = ceil(sqrt(0.75 dev / 0.025)), at most 256.
 inline int cubic_flatten_count(const float* q) {

@@ -67,8 +67,10 @@ inline Edge third(const Edge& e, int k) {
   return o;
 }
 
-// step 3 for one closed contour (edges in order); may replace it by its split form
-inline void colour_contour(std::vector<Edge>& c) {
+// step 3 for one closed contour (edges in order); may replace it by its split form.  Written once for both edge types (this file's and
+// fdh_msdf_cubic_host.h's): end_tangents and third are the overloads of the edge's own namespace.
+template <typename E>
+inline void colour_contour(std::vector<E>& c) {
   const int m = (int)c.size();
   std::vector<int> corners;
   const double kSin3 = std::sin(3.0);
@@ -84,11 +86,11 @@ inline void colour_contour(std::vector<Edge>& c) {
   static const int cycle[3] = {kMagenta, kYellow, kCyan};
   const int n = (int)corners.size();
   if (n == 0) {
-    for (Edge& e : c) e.colour = kWhite;
+    for (E& e : c) e.colour = kWhite;
   } else if (n == 1) {
-    std::vector<Edge> r;  // from the corner round
+    std::vector<E> r;  // from the corner round
     for (int j = 0; j < m; j++) {
-      const Edge& e = c[(corners[0] + j) % m];
+      const E& e = c[(corners[0] + j) % m];
       if (m >= 3) r.push_back(e);
       else for (int k = 0; k < 3; k++) r.push_back(third(e, k));
     }

@@ -4,7 +4,7 @@
 // scratch directory together with k_atlas_upload.hip and fdh_msdf_host.h from csrc, unmodified.
 // usage: emu batch.raw out.raw     batch.raw: int32 n, then per glyph int32 w, h, n_lines and n_lines x 4 float32 (x0, y0, x1, y1)
 // The images of all glyphs lie in one buffer (and its twin) with 64 words of 0xEE before the first, between two and behind the last; the
-// lines and the tables are sized exactly.  The tables are built as Atlas::put_glyph_coverage_batch builds them: a glyph 1 texel wide or
+// lines and the tables are sized exactly.  The tables are built as batch_tables (fdh_glyph_tables.h) builds them for put_glyph_coverage_batch: a glyph 1 texel wide or
 // high has no tiles, and its region must stay as it was.  Every other glyph's bytes must be the single launcher's, unfiltered and
 // filtered; no pad may be written, nor the lines, the tables or the filter's input.
 // -> out.raw: per glyph w x h words unfiltered, then w x h words filtered (a glyph without tiles: 0xEE), for the caller to compare with the

@@ -51,7 +51,7 @@ int main(int argc, char** argv) {
     n_edges += (size_t)g.n_edges;
   }
   fclose(f);
-  // the batch's tables, as Atlas::put_glyph_outlines builds them (the field offsets here step over the pads)
+  // the batch's tables, as batch_tables (fdh_glyph_tables.h) builds them for put_glyph_outlines (the field offsets here step over the pads)
   std::vector<float> rec;
   std::vector<fdh::msdf::BatchGlyph> tab((size_t)n);
   std::vector<uint32_t> tile_glyph;

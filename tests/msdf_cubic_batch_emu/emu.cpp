@@ -5,7 +5,7 @@
 // fdh_msdf_host.h from csrc, unmodified.
 // usage: emu batch.raw [FIRST]   batch.raw: int32 n, then per glyph int32 w, h, range, n_segs and n_segs x 8 float32 (c2x = NaN: a
 //                                quadratic, c1x = NaN: a line).  FIRST (default 0): the batch is cut there as after a growth of the atlas --
-//                                the tables are those of glyphs FIRST .. n - 1, edge_off rebased to the first of them (Atlas::batch_tables),
+//                                the tables are those of glyphs FIRST .. n - 1, edge_off rebased to the first of them (batch_tables, fdh_glyph_tables.h),
 //                                and the records are that slice alone.
 // The fields of the glyphs lie in one buffer with 64 words of 0xEE before the first, between two and behind the last; the tables and the
 // records are sized exactly.  Every glyph's bytes must be the single launchers' (k_msdf_generate_cubic, then k_msdf_correct_cubic on what
@@ -69,7 +69,7 @@ int main(int argc, char** argv) {
     all_rec.insert(all_rec.end(), g.rec.begin(), g.rec.end());
   }
   fclose(f);
-  // the tables of glyphs first .. n - 1, as Atlas::batch_tables builds them (the field offsets here step over the pads)
+  // the tables of glyphs first .. n - 1, as batch_tables (fdh_glyph_tables.h) builds them (the field offsets here step over the pads)
   const uint32_t edge_base = tab[(size_t)first].edge_off;
   std::vector<float> rec(all_rec.begin() + (size_t)edge_base * mc::kCubicEdgeFloats, all_rec.end());
   std::vector<fdh::msdf::BatchGlyph> sub;

@@ -1,4 +1,4 @@
-"""The image atlas (figdraw_amd/csrc/fdh_atlas.h, class Atlas) as a record-only context shows it: one packer behind every put kind, placed
+"""The image atlas (figdraw_amd/csrc/fdh_atlas.h, class Atlas; the glyph puts: fdh_glyphs.h, class GlyphMaker) as a record-only context shows it: one packer behind every put kind, placed
 where the oracle places; growth through the put kinds; a refused put leaves nothing behind; and the draw records that read the
 directory (Recorder's entry lookup and axis-aligned LOD), pinned by digests made with the library of the commit before the atlas moved
 out of Context (tests/golden/atlas_record_digests.json)."""
