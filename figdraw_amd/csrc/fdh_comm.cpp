@@ -164,11 +164,11 @@ void Context::gather_stripes(int dst_rank, void* dst_image) {
   if (dst_rank < 0 || dst_rank >= world) throw Error(FDH_ERR_INVALID, "gather_stripes: destination rank out of range");
   drain();  // the frame's launches are on the stream: the transfers queue behind them
   FDH_HIP(hipSetDevice(device_));
-  const size_t row_bytes = (size_t)W_ * 4;
+  const size_t row_bytes = (size_t)env_.W * 4;
   int my0, my1;
-  stripe_rows(H_, world, rank, &my0, &my1);
+  stripe_rows(env_.H, world, rank, &my0, &my1);
   // what travels is the rule's stripe: a context that rendered another one (fdh_set_stripe) would send rows it never produced
-  if (stripe_y1_ > stripe_y0_ && (std::max(0, stripe_y0_) != my0 || std::min(H_, stripe_y1_) != my1))
+  if (stripe_y1_ > stripe_y0_ && (std::max(0, stripe_y0_) != my0 || std::min(env_.H, stripe_y1_) != my1))
     throw Error(FDH_ERR_INVALID, "gather_stripes: the stripe set with fdh_set_stripe is not this rank's fdh_stripe_rows(height, world, rank)");
   uint8_t* own = reinterpret_cast<uint8_t*>(fb_);
   uint8_t* dst = dst_image ? static_cast<uint8_t*>(dst_image) : own;
@@ -183,7 +183,7 @@ void Context::gather_stripes(int dst_rank, void* dst_image) {
   if (rank == dst_rank) {
     for (int r = 0; r < world; r++) {
       int y0, y1;
-      stripe_rows(H_, world, r, &y0, &y1);
+      stripe_rows(env_.H, world, r, &y0, &y1);
       if (r != rank && y1 > y0) FDH_NCCL(R.Recv(dst + (size_t)y0 * row_bytes, (size_t)(y1 - y0) * row_bytes, ncclUint8, r, comm, stream_));
     }
   } else if (my1 > my0) {
@@ -204,7 +204,7 @@ void Context::gather_frames(int dst_rank, void* const* dst_images) {
       if (r != rank && !dst_images[r]) throw Error(FDH_ERR_INVALID, "gather_frames: null destination image");
   drain();
   FDH_HIP(hipSetDevice(device_));
-  const size_t bytes = (size_t)W_ * H_ * 4;
+  const size_t bytes = (size_t)env_.W * env_.H * 4;
   if (rank == dst_rank && dst_images[rank] && dst_images[rank] != fb_)
     FDH_HIP(hipMemcpyAsync(dst_images[rank], fb_, bytes, hipMemcpyDeviceToDevice, stream_));
   if (world == 1) return;

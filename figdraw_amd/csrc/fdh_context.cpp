@@ -30,8 +30,10 @@ void poison_fresh(void* p, size_t bytes) {
 }
 
 // ------------------------------------------------------------------ lifetime
-Context::Context(int atlas_size, float pixel_scale, int device, uint32_t flags) : Recorder(this, true), device_(device), flags_(flags), pixel_scale_(pixel_scale) {
-  host_only_ = (flags & FDH_CREATE_RECORD_ONLY) != 0;
+Context::Context(int atlas_size, float pixel_scale, int device, uint32_t flags)
+    : Recorder(frame_env_, &call_log_), device_(device), flags_(flags), pixel_scale_(pixel_scale),
+      frame_((flags & FDH_CREATE_RECORD_ONLY) != 0, device), host_only_((flags & FDH_CREATE_RECORD_ONLY) != 0) {
+  frame_env_.atlas = &atlas_;
   if (host_only_) {  // a call recorder: the front-end and the atlas packer run, nothing is drawn, no device is touched
     atlas_.init(atlas_size, false, nullptr);
     return;
@@ -92,13 +94,13 @@ void Context::release_device_state() {
   damage_.release(); readback_.release();
   d_mask_spill_.release();
   d_pick_.release(); d_pick_spill_.release(); h_pick_.release();
-  for (auto& set : lanes_) set.clear();  // (pinned arrays: freed while the device is still this thread's)
+  frame_.release_lanes();  // (pinned arrays: freed while the device is still this thread's)
   for (auto& m : misc_) m.release();
   for (auto& e : staging_ev_) if (e) (void)hipEventDestroy(e);
   if (seq_host_) (void)hipHostFree((void*)seq_host_);
   if (deep_host_) (void)hipHostFree((void*)deep_host_);
   if (own_stream_) (void)hipStreamDestroy(own_stream_);
-  for (auto& l : merge_lane_) l.reset();  // (their staging blocks go to the store before the store is looked at)
+  frame_.release_merge_lanes();  // (their staging blocks go to the store before the store is looked at)
   vram_context_gone(device_);
 }
 
@@ -187,7 +189,7 @@ void Context::sync() {
 
 // ------------------------------------------------------------------ frame
 void Context::ensure_surfaces() {
-  if (host_only_ || (surf_w_ == W_ && surf_h_ == H_ && fb_)) return;
+  if (host_only_ || (surf_w_ == env_.W && surf_h_ == env_.H && fb_)) return;
   drain();  // the frame in submission still renders into the old surfaces
   FDH_HIP(hipStreamSynchronize(stream_));
   if (fb_) FDH_HIP(hipFree(fb_));
@@ -195,7 +197,7 @@ void Context::ensure_surfaces() {
   if (blur_tmp_) FDH_HIP(hipFree(blur_tmp_));
   if (alt_) { FDH_HIP(hipFree(alt_)); alt_ = nullptr; }
   if (dbg_snap_) { FDH_HIP(hipFree(dbg_snap_)); dbg_snap_ = nullptr; }
-  const size_t n = (size_t)W_ * H_;
+  const size_t n = (size_t)env_.W * env_.H;
   FDH_HIP(hipMalloc((void**)&fb_, n * 4));
   FDH_HIP(hipMalloc((void**)&backdrop_, n * 4));
   FDH_HIP(hipMalloc((void**)&blur_tmp_, n * 4));
@@ -205,19 +207,19 @@ void Context::ensure_surfaces() {
 #else
   FDH_HIP(hipMemsetAsync(fb_, 0, n * 4, stream_));
 #endif
-  surf_w_ = W_;
-  surf_h_ = H_;
+  surf_w_ = env_.W;
+  surf_h_ = env_.H;
 }
 
 void Context::begin_frame(int w, int h, bool clear, const float rgba[4]) {  // glcontext.nim:2080-2092, 1951-1980
-  rec_begin_frame(clear, rgba);
-  if (frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has already been called.");
+  log_begin_frame(clear, rgba);
+  if (env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has already been called.");
   if (w <= 0 || h <= 0 || w > 16384 || h > 16384) throw Error(FDH_ERR_INVALID, "beginFrame: frame size must be in 1..16384");
   t_begin_frame_ = std::chrono::steady_clock::now();
   for (auto& v : host_ns_) v = 0;
   if (!host_only_) FDH_HIP(hipSetDevice(device_));
-  W_ = w;
-  H_ = h;
+  frame_env_.W = w;
+  frame_env_.H = h;
   ensure_surfaces();
   clear_ = clear;
   if (clear) {
@@ -226,50 +228,20 @@ void Context::begin_frame(int w, int h, bool clear, const float rgba[4]) {  // g
   }
   // The records of this frame go into the next set of lanes: the set's last user was the frame kStaging frames ago, whose upload
   // kernel has run by now (that frame's issue was waited for by the end_frame after it: the event is recorded).
-  staging_i_ = (staging_i_ + 1) % kStaging;
-  frame_no_++;
-  if (!host_only_ && staging_busy_[staging_i_]) { HostTimer t(host_ns_[1]); wait_staging(staging_i_); }
-  Lane& L0 = ensure_lane(0);
-  L0.clear();
-  L0.count_begin((w + kBin - 1) / kBin, (h + kBin - 1) / kBin);
-  binbox_shift_ = ((w + kBin - 1) / kBin > 128 || (h + kBin - 1) / kBin > 128) ? 1 : 0;
-  lane_ = &L0;
-  frame_begun_ = true;
-  mask_begun_ = false;
-  mask_depth_ = 0;
-  pick_frame_ = pick_on_;
-  tag_ = PickTag{-1, -1};
-  rect_masks_.clear();
-  open_ops_.clear();
-  outer_rect_masks_ = 0;
-  outer_open_ = false;
-  outer_union_ = BBox{0, 0, 0, 0};
-  depth_now_ = 0;
-  sum_ = PhaseSum{};
-  fragments_ = 0;
-  culled_draws_ = 0;
-  pieces_.clear();
-  n_total_ = n_ext_total_ = 0;
-  piece_open_ = false;
-  phases_.clear();
-  phases_.push_back(Phase{});
-  blurs_.clear();
-  phase_u_ = BBox{0, 0, 0, 0};
-  stride_max_ = 1;
-  phase_extra_ = 0;
-  deepest_clip_ = 0;
-  for (auto& f : frag_mode_) f = 0;
-  frag_ellip_ = frag_other_ = 0;
+  if (!host_only_ && staging_busy_[frame_.next_set()]) { HostTimer t(host_ns_[1]); wait_staging(frame_.next_set()); }
+  reset(frame_.begin(w, h));
+  frame_env_.binbox_shift = ((w + kBin - 1) / kBin > 128 || (h + kBin - 1) / kBin > 128) ? 1 : 0;
+  frame_env_.frame_begun = true;
+  frame_env_.pick_frame = pick_on_;
   parallel_groups_ = 0;
   rec_diff_upload_ = false;
-  open_piece();
   pick_routes();
   // rows a draw has to reach: the frame's, or -- under fdh_set_stripe, when the front-end has told how far the scene's blur nodes
   // reach (render_frame: the per-call path cannot know what is still to come) -- the stripe's, widened by that reach
-  cull_y0_ = 0; cull_y1_ = H_;
+  frame_env_.cull_y0 = 0; frame_env_.cull_y1 = env_.H;
   if (stripe_y1_ > stripe_y0_ && pending_reach_ >= 0) {
-    cull_y0_ = std::max(0, std::min(H_, stripe_y0_) - pending_reach_);
-    cull_y1_ = std::min(H_, std::max(0, stripe_y1_) + pending_reach_);
+    frame_env_.cull_y0 = std::max(0, std::min(env_.H, stripe_y0_) - pending_reach_);
+    frame_env_.cull_y1 = std::min(env_.H, std::max(0, stripe_y1_) + pending_reach_);
   }
   pending_reach_ = -1;
   t_walk_begin_ = std::chrono::steady_clock::now();
@@ -282,32 +254,32 @@ void Context::begin_frame(int w, int h, bool clear, const float rgba[4]) {  // g
 //   issue    launches the upload kernel and the frame's kernels (~20 us of HIP runtime calls) from the submit thread, so the
 //            caller is already walking the next frame's tree.  FDH_CREATE_SYNC_SUBMIT contexts run it inline.
 void Context::end_frame() {  // glcontext.nim:1982-1989
-  rec_end_frame();
-  if (!frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame was not called first.");
+  log_end_frame();
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame was not called first.");
   if (mask_depth_ != 0) throw Error(FDH_ERR_INVALID, "Not all masks have been popped.");
   if (!rect_masks_.empty()) throw Error(FDH_ERR_INVALID, "Not all rect masks have been popped.");
-  frame_begun_ = false;
+  frame_env_.frame_begun = false;
   const auto t0 = std::chrono::steady_clock::now();
   host_ns_[2] = std::chrono::duration_cast<std::chrono::nanoseconds>(t0 - t_walk_begin_).count();
-  close_phase();
-  close_piece();
+  frame_.close_phase(take_sum());
+  frame_.close_piece();
   culled_total_ = culled_draws_;
   const auto t1 = std::chrono::steady_clock::now();
   host_ns_[3] = std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
   // (without what begin_frame waited for the GPU -- the lane set's previous upload: back-pressure, not work)
   host_record_ms_ = std::chrono::duration<float, std::milli>(t1 - t_begin_frame_).count() - (float)host_ns_[1] * 1e-6f;
   // a list entry carries the draw index in 25 bits beside its path code and flags (k_bin_draws, LE_INDEX)
-  if (n_total_ >= LE_INDEX) throw Error(FDH_ERR_INVALID, "more than 33 554 430 draw records in one frame");
+  if (frame_.n_records() >= LE_INDEX) throw Error(FDH_ERR_INVALID, "more than 33 554 430 draw records in one frame");
   {  // picking: the frame's tag table, in painter's order, goes with the frame (a record-only context keeps it as its last frame)
     LaunchJob& T = host_only_ ? job_ : next_;
-    T.pick = pick_frame_;
-    T.pick_depth = deepest_clip_;
+    T.pick = env_.pick_frame;
+    T.pick_depth = frame_.deepest_clip();
     T.pick_tags.clear();
-    if (pick_frame_) {
-      T.pick_tags.resize(n_total_);
+    if (env_.pick_frame) {
+      T.pick_tags.resize(frame_.n_records());
       size_t o = 0;
-      for (const Piece& p : pieces_) {
-        if (p.n) std::memcpy(static_cast<void*>(T.pick_tags.data() + o), lane(p.lane).tags.p + p.first, p.n * sizeof(PickTag));
+      for (const Piece& p : frame_.pieces()) {
+        if (p.n) std::memcpy(static_cast<void*>(T.pick_tags.data() + o), frame_.lane(p.lane).tags.p + p.first, p.n * sizeof(PickTag));
         o += p.n;
       }
     }
@@ -333,16 +305,42 @@ void Context::end_frame() {  // glcontext.nim:1982-1989
   cv_job_.notify_one();
 }
 
-void Context::pool_slots(int slots) {
-  while ((int)pool_recs_.size() < slots) pool_recs_.emplace_back(new Recorder(this, false));
-  for (int s = 0; s < slots; s++) {
-    Lane& Ln = ensure_lane(s + 1);
-    if (Ln.stamp != frame_no_) {  // first use in this frame
-      Ln.clear();
-      Ln.count_begin((W_ + kBin - 1) / kBin, (H_ + kBin - 1) / kBin);
-      Ln.stamp = frame_no_;
-    }
+Recorder& Context::pool_recorder(int slot) {
+  while ((int)pool_recs_.size() <= slot) pool_recs_.emplace_back(new Recorder(frame_env_, nullptr));
+  return *pool_recs_[(size_t)slot];
+}
+void Context::use_device_here() const {
+  thread_local int t_dev = -1;
+  if (!host_only_ && t_dev != device_) { (void)hipSetDevice(device_); t_dev = device_; }
+}
+// The 4x4 white "rect" atlas image drawRect / drawFilledQuad sample (glcontext.nim:966-970, 1411-1415); it takes atlas space on first
+// use exactly like the reference's -- on the calling thread.
+void Context::make_rect_image() {
+  uint8_t white[4 * 4 * 4];
+  std::memset(white, 255, sizeof white);
+  put_image(kRectImageKey, 4, 4, white, nullptr);
+}
+// A blurred snapshot is a barrier in painter's order: close the phase, blur, continue in a new phase.
+void Context::blur_node(const DrawRec& quad, const float rect[4], float blur_radius) {
+  const std::vector<DrawRec> reopen = close_open_clips();
+  frame_.split_phase(take_sum(), (int)frame_.blurs().size());
+  set_phase_floor(lane_->recs.n);
+  // no clip state to carry: the V pass can composite the quad itself -- unless the region is small enough for the one-kernel
+  // route, whose snapshot goes to the backdrop surface and is sampled by the phase's compositor launch (k_blur_small)
+  const uint32_t idx = reopen_clips_and_emit(reopen, quad, rect);
+  const BBox fb = lane_->bins[idx].box;
+  BlurJob job;
+  job.taps = make_taps(blur_radius);
+  const bool fuse = clip_free() && !(env_.latency_routes && blur_one_kernel_ok(fb.x1 - fb.x0, fb.y1 - fb.y0, job.taps.reach));
+  job.fuse_draw = -1;
+  if (fuse) {
+    job.fuse_draw = (int)frame_.global_index(idx);
+    lane_->bins[idx].box = BBox{0, 0, 0, 0};  // never binned: k_blur_v blends it
   }
+  commit_bins(idx);
+  job.radius = blur_radius;
+  job.x0 = fb.x0; job.y0 = fb.y0; job.x1 = fb.x1; job.y1 = fb.y1;
+  frame_.add_blur(job);
 }
 int Context::walk_threads() const { return walk_threads_ >= 0 ? walk_threads_ : WalkPool::default_helpers(); }
 
@@ -702,10 +700,10 @@ void Context::read_pixels(int x, int y, int w, int h, uint8_t* out) {
   drain();
   if (!fb_) throw Error(FDH_ERR_INVALID, "readPixels before the first frame");
   FDH_HIP(hipSetDevice(device_));
-  if (w <= 0 || h <= 0) { x = 0; y = 0; w = W_; h = H_; }
-  if (x < 0 || y < 0 || x + w > W_ || y + h > H_) throw Error(FDH_ERR_INVALID, "readPixels: rectangle outside the frame");
+  if (w <= 0 || h <= 0) { x = 0; y = 0; w = env_.W; h = env_.H; }
+  if (x < 0 || y < 0 || x + w > env_.W || y + h > env_.H) throw Error(FDH_ERR_INVALID, "readPixels: rectangle outside the frame");
   FDH_HIP(hipStreamSynchronize(stream_));
-  FDH_HIP(hipMemcpy2D(out, (size_t)w * 4, fb_ + (size_t)y * W_ + x, (size_t)W_ * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost));
+  FDH_HIP(hipMemcpy2D(out, (size_t)w * 4, fb_ + (size_t)y * env_.W + x, (size_t)env_.W * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost));
 }
 // ------------------------------------------------------------------ damage tracking, damage readback: the context's part (fdh_damage.cpp)
 void Context::set_damage_tracking(bool on) {
@@ -772,7 +770,7 @@ void Context::frame_device_ptr(void** p, int* w, int* h, int64_t* pitch_bytes) {
   need_device("frame_device_ptr");
   drain();
   if (!fb_) throw Error(FDH_ERR_INVALID, "no frame surface yet");
-  *p = fb_; *w = W_; *h = H_; *pitch_bytes = (int64_t)W_ * 4;
+  *p = fb_; *w = env_.W; *h = env_.H; *pitch_bytes = (int64_t)env_.W * 4;
 }
 
 }  // namespace fdh

@@ -26,105 +26,14 @@
 #include "fdh_kernels.h"
 #include "fdh_plain.h"        // Error, Aff, PickTag, PhaseSum
 #include "fdh_memory.h"       // FDH_HIP, DeviceBuf, PinnedBuf, HostVec
-#include "fdh_frame.h"        // Phase, BlurJob, Lane, Piece, FrameLayout, LaunchJob
+#include "fdh_frame.h"        // Phase, BlurJob, Lane, Piece, RecordedFrame (one member of Context), FrameLayout, LaunchJob
 #include "fdh_atlas.h"        // AtlasEntry, Atlas: one member of Context
+#include "fdh_recorder.h"     // Recorder (Context is lane 0's), FrameEnv, CallLog
 #include "fdh_glyphs.h"       // GlyphMaker, beside it: glyphs made on the device
 #include "fdh_damage_host.h"  // DamageTracker, DamageReadback: two members of Context
 #include "fdh_retained.h"     // RetainedScene: one member of Context
 
 namespace fdh {
-
-struct RectMaskEntry { int kind; };  // 1 = fast analytic, 2 = real mask (glcontext.nim:36-44)
-class Context;
-struct SerialOnly {};  // thrown by a pool thread's recorder at a call only the calling thread can serve (a blur node, the lazily
-                       // created 4x4 "rect" atlas image): the calling thread then walks that sibling group itself
-
-// The BackendContext state machine (glcontext.nim): transform stack, clip / rect-mask stacks, and the draw calls, each turning
-// into records of ONE lane.  Context derives from it (lane 0: the C entry points and the serial walk); the walk pool's threads
-// each own one more (fdh_frontend.cpp).
-// the two bands of an upright draw's saturated core in BinRec's form (fdh_types.h; all zero: none)
-struct CoreBands { uint32_t grow = 0; uint16_t hy0 = 0, hy1 = 0, vx0 = 0, vx1 = 0; };
-
-class Recorder {
- public:
-  Recorder(Context* cx, bool is_main) : cx_(cx), is_main_(is_main) {}
-  void save_transform();
-  void restore_transform();
-  void translate(float x, float y);
-  void rotate(float a);
-  void scale(float sx, float sy);
-  void apply_transform(const float m[16]);
-  bool transform_mirrors_y() const;
-  void set_aa(float aa);
-  float aa() const { return aa_; }
-  void draw_rounded_rect_sdf(const float rect[4], const FdhColor colors[4], const float rx[4], const float ry[4], int mode,
-                             float factor, float spread, const float shape[2], int fill_mode, FdhColor mid, FdhColor stop,
-                             float mid_pos);
-  void draw_rounded_rect_fill(const float rect[4], const FdhFill& fill, const float rx[4], const float ry[4], int mode,
-                              float factor, float spread, const float shape[2]);
-  void draw_image(int64_t key, const float pos[2], const FdhColor colors[4], const float size[2], bool flip_y);
-  void draw_image_adj(int64_t key, const float pos[2], FdhColor color, const float size[2]);
-  void draw_msdf(int64_t key, const float pos[2], FdhColor color, const float size[2], float px_range, float sd_threshold,
-                 float stroke_weight, bool mtsdf, bool flip_y);
-  void draw_quadratic_bezier_sdf(const float rect[4], const FdhFill& fill, const float p0[2], const float p1[2], const float p2[2],
-                                 float stroke_weight, int cap);
-  void draw_filled_quad(const float verts[8], const FdhColor colors[4]);
-  void draw_rect(const float rect[4], FdhColor color);
-  void draw_backdrop_blur(const float rect[4], const float rx[4], const float ry[4], float blur_radius);
-  void begin_mask(const float rect[4], const float rx[4], const float ry[4]);
-  void end_mask();
-  void pop_mask();
-  void begin_rect_mask(const float rect[4], const float rx[4], const float ry[4]);
-  void pop_rect_mask();
-  void set_subpixel_shift(float s);
-  bool subpixel_enabled() const;
-  bool subpixel_variants() const;
-  bool culling() const;
-  // would a quad over `rect` (pre-transform units), grown by `pad` pixels on every side, reach a pixel the frame will produce?
-  bool rect_visible(const float rect[4], float pad) const;
-
-  // ---- state (the calling thread's recorder is reset by begin_frame; a pool thread's by adopt())
-  Context* const cx_;
-  const bool is_main_;
-  Lane* lane_ = nullptr;
-  Aff mat_;
-  std::vector<Aff> mats_;
-  float aa_ = 1.2f;
-  float subpixel_shift_ = 0.0f;
-  bool mask_begun_ = false;
-  int mask_depth_ = 0;
-  std::vector<RectMaskEntry> rect_masks_;
-  int outer_rect_masks_ = 0;        // pool threads: rect masks open around the sibling group (begin_rect_mask nests differently inside one)
-  std::vector<uint32_t> open_ops_;  // lane indices of the open MASK_PUSH / RMASK_BEGIN records (their bounds grow with their content)
-  bool outer_open_ = false;         // pool threads: clips are open around the sibling group; their bounds take ...
-  BBox outer_union_{0, 0, 0, 0};    // ... the union of everything emitted here (merged by the calling thread)
-  int depth_now_ = 0;               // clip nesting inside the current phase (open pushes are re-emitted at a phase's start)
-  PhaseSum sum_;                    // of the records committed since the last take_sum()
-  int64_t fragments_ = 0, culled_draws_ = 0;
-  int phase_floor_ = 0;             // lane index of the first record of the current phase in this lane (LE_SHARE never crosses it)
-  PickTag tag_{-1, -1};             // the tag of the records this recorder makes next (picking frames: fdh_set_pick_tag, the front-end)
-
- protected:
-  DrawRec& next_rec();  // the lane's next record slot, zeroed (counted by emit_* when the draw survives culling)
-  bool emit_quad(DrawRec& r, float x0, float y0, float x1, float y1, bool count_fragments);  // false: culled, nothing was recorded
-  bool emit_quad_pts(DrawRec& r, const float vx[4], const float vy[4], bool count_fragments);
-  struct QuadPx { float px[4], py[4]; BBox b; bool finite; };
-  void quad_corners(const float vx[4], const float vy[4], QuadPx& q) const;
-  bool emit_corners(DrawRec& r, const QuadPx& q, bool count_fragments);
-  void push_rec(BBox b);  // count the slot next_rec() handed out
-  CoreBands bands_;       // emit_corners -> push_rec: the core bands of the record being emitted
-  void commit_bins(uint32_t idx);  // the record's bounds are final: list-entry flags, list-stride count, phase summary
-  void link_share(uint32_t idx);   // LE_SHARE on idx - 1 when record idx is drawn over the same quad with the same shape
-  bool bbox_visible(const BBox& b) const;
-  struct EntryUV { const AtlasEntry* e; float S, x, y, w, h; };  // an atlas entry, the atlas size, the entry's rect / size
-  EntryUV entry_uv(int64_t key) const;
-  struct PixelQuad { float x0, y0, x1, y1, w, h; };
-  PixelQuad axis_lod(DrawRec& r, float S, float x0, float y0, float x1, float y1) const;
-  void rect_entry();  // the 4x4 white image exists from here on (SerialOnly on a pool thread that finds it missing)
-  void white_texel_uv(DrawRec& r) const;
-  void shrink_to_ink(const AtlasEntry& e, bool use_alpha, int level_t);
-  friend class Context;
-};
 
 class Context : public Recorder {
  public:
@@ -135,8 +44,8 @@ class Context : public Recorder {
   void begin_frame(int w, int h, bool clear, const float rgba[4]);
   void end_frame();
   float pixel_scale() const { return pixel_scale_; }
-  void set_subpixel_enabled(bool e) { subpixel_enabled_ = e; }
-  void set_subpixel_variants(bool e) { subpixel_variants_ = e; }
+  void set_subpixel_enabled(bool e) { frame_env_.subpixel_enabled = e; }
+  void set_subpixel_variants(bool e) { frame_env_.subpixel_variants = e; }
   void set_text_lcd_filtering(bool e) { text_lcd_filtering_ = e; }
   bool text_lcd_filtering() const { return text_lcd_filtering_; }
   void comm_info(int* rank, int* world) const { *rank = comm_ ? comm_rank_ : 0; *world = comm_ ? comm_world_ : 1; }
@@ -167,8 +76,8 @@ class Context : public Recorder {
   void frame_device_ptr(void** p, int* w, int* h, int64_t* pitch_bytes);
   void debug_read_surface(int which, uint8_t* out);
   // call recorder (fdh_record_begin / fdh_record_json): the backend-level calls the scene front-end makes, as JSON
-  void record_begin();
-  const char* record_json();
+  void record_begin() { call_log_.begin(); }
+  const char* record_json() { return call_log_.json(); }
   void sync();
   void set_stream(void* s);
 
@@ -214,7 +123,7 @@ class Context : public Recorder {
   void damage_exact_stats(int* n_pending, int* n_changed, int* fresh);
   // picking (include/figdraw_hip_pick.h; fdh_pick.cpp)
   void set_pick(bool on) { pick_on_ = on; }
-  void set_pick_tag(int32_t z, int32_t id) { tag_ = PickTag{z, id}; }
+  void set_pick_tag(int32_t z, int32_t id) { set_tag(PickTag{z, id}); }
   void pick_points(const float* xy, int n, int threshold, uint32_t flags, int max_hits, FdhPickHit* out, int* counts);
   void pick_region(int x, int y, int w, int h, int threshold, uint32_t flags, int32_t* out_draw);
   void pick_draw_tags(int32_t* zlevels, int32_t* ids, int cap, int* n);
@@ -222,13 +131,25 @@ class Context : public Recorder {
   // reach of the scene's blur nodes -- are not recorded, and the scene front-end skips the content of a clipping node whose mask
   // lies outside.  0 off, 1 on (default; off while the call recorder runs, so that recorded streams stay the reference's), 2 on
   // even while recording (tests).  The pixels are the same either way.
-  void set_cull(int mode) { cull_mode_ = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
+  void set_cull(int mode) { frame_env_.cull_mode = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
   int64_t culled_draws() const { return culled_total_; }
   // The scene front-end decomposes large sibling groups on `n` pool threads beside the calling one (0: serial; default:
   // FDH_WALK_THREADS or a few, by the host's core count).  Same records either way (fdh_debug_record_digest).
   void set_walk_threads(int n) { walk_threads_ = n < 0 ? -1 : (n > 64 ? 64 : n); }
   int walk_threads() const;
   int64_t parallel_groups() const { return parallel_groups_; }
+  // What a sibling group on the pool needs of the context (ParallelWalk::group, fdh_frontend.cpp).
+  // GroupCuts: where the last frames cut their forked sibling groups into chunks, and what each chunk cost (records made + a share per
+  // item visited): a group that comes again -- same first item, same length -- is cut where that cost says the work is, not into equal
+  // item counts (a viewport's visible rows are a fifth of its cells).  Boundaries change nothing a frame records.
+  struct GroupCuts { int first_item = -1, n = 0; std::vector<int> cut; std::vector<float> cost; uint64_t used = 0; };
+  std::vector<GroupCuts>& group_cuts() { return group_cuts_; }
+  void count_parallel_group() { parallel_groups_++; }
+  bool may_fork() const { return env_.frame_begun && !call_log_.on(); }  // (not while the call recorder runs)
+  RecordedFrame& frame() { return frame_; }
+  void reopen_piece() { set_phase_floor(frame_.open_piece()); }  // lane 0 goes on after a group (LE_SHARE never looks across a piece boundary)
+  Recorder& pool_recorder(int slot);  // the pool threads' recorders (slot s records into lane s + 1)
+  void use_device_here() const;       // a pool thread before it publishes: a lane's pinned mirror is allocated by the thread that publishes into it
   void set_blur_route(int route) { blur_route_ = route < 0 ? -1 : (route ? 1 : 0); }
   void replay(int times);
   void replay_timed(int times, float* ms_out);
@@ -241,11 +162,10 @@ class Context : public Recorder {
   void flush() { drain(); }
 
  private:
-  friend class Recorder;
-  friend struct ParallelWalk;
   void release_device_state();  // the destructor's device half (also a constructor that fails half way)
-  void rec_begin_frame(bool clear, const float rgba[4]);  // begin_frame / end_frame as the call recorder sees them (fdh_record.cpp)
-  void rec_end_frame();
+  // Recorder's calling-thread-only work (fdh_context.cpp)
+  void make_rect_image() override;
+  void blur_node(const DrawRec& quad, const float rect[4], float blur_radius) override;
   // FDH_GLYPH_LCD_CONTEXT: the LCD filter as setTextLcdFilteringEnabled said.  (With FDH_GLYPH_MTSDF the flags pass as they are: a distance
   // field takes neither LCD flag, and the atlas refuses them.)
   uint32_t resolve_lcd(uint32_t flags) const {
@@ -301,28 +221,14 @@ class Context : public Recorder {
   hipEvent_t next_event();
   void ensure_surfaces();
   void need_device(const char* what) const;
-  // pieces / phases (calling thread)
-  void split_phase(int blur);               // a blurred snapshot is a barrier in painter's order
-  void open_piece();                        // lane 0's records from here on form a new piece
-  void close_piece();
-  void add_piece(const Piece& p, const PhaseSum& s, const BBox& outer_union, int64_t fragments, int64_t culled);  // a pool thread's chunk, in order
-  void add_sum(const PhaseSum& s, int depth_base);
-  void close_phase();                       // the phase ends here: summary, bins reached, its share of the list stride
-  uint32_t global_index(uint32_t lane0_index) const { return lane0_index + g0_delta_; }
-  uint32_t global_count() const;            // records of the frame so far
-  Lane& lane(int i) { return i < 0 ? *merge_lane_[(size_t)staging_i_] : *lanes_[(size_t)staging_i_][(size_t)i]; }  // (-1: consolidate_pieces' lane)
-  Lane& ensure_lane(int i);
-  void splice_cached(const RetainedRoot& C);
   // render_frame's and scene_render's frame around walk(links): the frame of fw x fh UI units begun (culled, under a row stripe, by the
   // blur reach of `scene`), the pixel scale on the transform stack, the frame ended -- or, when the walk throws, left unbegun
   template <typename Walk> void walk_frame(float fw, float fh, bool clear, const float rgba[4], const FdhScene& scene, Walk walk);  // (fdh_frontend.cpp)
   void pick_routes();                       // begin_frame: the one-kernel blur routes (a frame alone) or the two-pass ones (frames in flight)
-  void pool_slots(int slots);               // lanes 1 .. slots and their recorders, ready for a sibling group
 
   int device_ = 0;
   uint32_t flags_ = 0;
   int blur_route_ = -1;   // fdh_set_blur_route: -1 per-frame decision, 0 two passes, 1 fused
-  bool latency_routes_ = true;  // this frame takes the one-kernel blur routes (pick_routes)
   std::shared_ptr<void> comm_;  // shared communicator object (fdh_comm.cpp), shared with the contexts that borrowed it: destroyed with its last holder
   int comm_rank_ = 0, comm_world_ = 1;
   hipStream_t own_stream_ = nullptr, stream_ = nullptr;
@@ -339,25 +245,17 @@ class Context : public Recorder {
   void span_begin(SpanKind kind); void span_end();
 
   // frame state
-  int W_ = 0, H_ = 0;
-  bool frame_begun_ = false;
+  FrameEnv frame_env_;  // what the recorders read of the frame (Recorder::env_ is this, const): size, cull rows, settings latched at begin_frame
   bool clear_ = true;
   uint32_t clear_rgba8_ = 0xFFFFFFFFu;
   float pixel_scale_ = 1.0f, ui_scale_ = 1.0f;
   float ctx_aa_ = 1.2f;   // (Recorder::aa_ of lane 0 is the live value; kept across frames)
-  bool subpixel_enabled_ = false, subpixel_variants_ = false, text_lcd_filtering_ = false;
+  bool text_lcd_filtering_ = false;
   int stripe_y0_ = 0, stripe_y1_ = 0;
-  int cull_mode_ = 1;
-  int binbox_shift_ = 0;           // bin boxes in 64 << shift px units (frames of more than 128 bins along an axis)
-  int cull_y0_ = 0, cull_y1_ = 0;  // rows a draw must reach to be recorded (begin_frame: the frame, or the stripe + blur reach)
   int pending_reach_ = -1;         // render_frame / scene_render: summed vertical reach of the scene's blur nodes (-1: unknown)
   int64_t culled_total_ = 0;       // of the last recorded frame
   int walk_threads_ = -1;
   int64_t parallel_groups_ = 0;    // sibling groups of the last frame that were decomposed on the pool
-  // Where the last frames cut their forked sibling groups into chunks, and what each chunk cost (records made + a share per item
-  // visited): a group that comes again -- same first item, same length -- is cut where that cost says the work is, not into equal
-  // item counts (a viewport's visible rows are a fifth of its cells).  Boundaries change nothing a frame records.
-  struct GroupCuts { int first_item = -1, n = 0; std::vector<int> cut; std::vector<float> cost; uint64_t used = 0; };
   std::vector<GroupCuts> group_cuts_;
 
   // submit thread (device contexts, unless FDH_CREATE_SYNC_SUBMIT): one job in flight at most.  The flag both sides poll
@@ -378,17 +276,7 @@ class Context : public Recorder {
 
   // recorded frame (calling thread)
   alignas(128) bool rec_diff_upload_ = false;
-  std::vector<Piece> pieces_;      // the frame in painter's order
-  bool piece_open_ = false;        // the last piece is lane 0's and still growing
-  uint32_t n_total_ = 0, n_ext_total_ = 0;  // records / extensions in closed pieces
-  uint32_t g0_delta_ = 0;          // global index of a record of lane 0's open piece = its lane index + this
-  std::vector<Phase> phases_;
-  std::vector<BlurJob> blurs_;
-  BBox phase_u_{0, 0, 0, 0};       // union of the current phase's record bounds
-  int stride_max_ = 1;             // list stride so far: max over the closed phases
-  int phase_extra_ = 0;            // the current phase: bound contributed by pool threads' lanes (sum of their own maxima)
-  int deepest_clip_ = 0;
-  int64_t frag_mode_[4] = {0, 0, 0, 0}, frag_ellip_ = 0, frag_other_ = 0;  // phase 0
+  RecordedFrame frame_;            // (fdh_frame.h)
   bool have_frame_ = false;
 
   // device state (submission side)
@@ -398,9 +286,7 @@ class Context : public Recorder {
   uint32_t* dbg_snap_ = nullptr;
   RetainedScene retained_;  // (fdh_retained.h)
   bool host_only_ = false;  // FDH_CREATE_RECORD_ONLY
-  bool rec_on_ = false, rec_first_ = true, rec_mark_first_ = true;
-  size_t rec_mark_ = 0;
-  std::string rec_;
+  CallLog call_log_;        // fdh_record_begin / fdh_record_json (fdh_calllog.h)
   int surf_w_ = 0, surf_h_ = 0;
   // records, quad extensions, bin records and phase offsets of a frame live in ONE device block; the typed views point into it
   DeviceBuf<uint8_t> d_frame_;
@@ -411,23 +297,20 @@ class Context : public Recorder {
   DamageTracker damage_;
   DamageReadback readback_;
   ReadFrame read_frame(const char* who);  // a read's first steps: the last frame is complete; what the read needs of it
-  // picking: fdh_set_pick (calling thread), latched per frame at begin_frame (pick_frame_: the lanes keep tags); the pick launches' buffers
-  bool pick_on_ = false, pick_frame_ = false;
+  // picking: fdh_set_pick (calling thread), latched per frame at begin_frame (FrameEnv::pick_frame: the lanes keep tags); the pick launches' buffers
+  bool pick_on_ = false;
   void pick_check(const char* who, int threshold, uint32_t flags);
   DeviceBuf<uint8_t> d_pick_, d_pick_spill_;
   PinnedBuf<uint8_t> h_pick_;
   int order_read_ = 0, order_nb_ = 0;
   bool order_valid_ = false;
-  // kStaging sets of lanes in rotation, each released when the upload that reads it has run (the bin launch behind it says so
+  // the frame's kStaging sets of lanes in rotation (RecordedFrame), each released when the upload that reads it has run (the bin launch behind it says so
   // through *seq_host_, Context::issue; an event where a frame has no bin launch): the host records
   // frames N + 1 .. while frame N's upload has not run yet (one set forced a stream sync per frame)
   struct MxTables { int reach; std::vector<float> dense; std::vector<uint8_t> h, v; bool keeps_opaque = false; };  // k_blur_mx weight fragments of one filter
   std::vector<MxTables> mx_cache_;
-  static constexpr int kStaging = 4;
-  std::vector<std::unique_ptr<Lane>> lanes_[kStaging];
-  std::unique_ptr<Lane> merge_lane_[kStaging];
+  static constexpr int kStaging = RecordedFrame::kStaging;
   std::vector<std::unique_ptr<Recorder>> pool_recs_;  // the pool threads' recorders (slot s records into lane s + 1)
-  uint64_t frame_no_ = 0;
   HostVec<uint8_t> misc_[kStaging];   // per slot (pinned): phase table, blur weight tables
   std::vector<uint8_t> misc_host_;    // ... as build_misc builds them
   const uint8_t* misc_dev_[kStaging] = {};   // the pinned buffers' device views (hipHostGetDevicePointer costs a third of a microsecond)
@@ -444,7 +327,6 @@ class Context : public Recorder {
   volatile uint32_t* seq_host_ = nullptr;  // pinned: the sequence number of the last frame whose bin launch has started (k_bin_draws)
   uint32_t upload_seq_ = 0;
   void wait_staging(int slot);             // calling thread: until the set's last upload has run
-  int staging_i_ = 0;
 
   Atlas atlas_;  // (fdh_atlas.h)
   GlyphMaker glyphs_;  // (fdh_glyphs.h)

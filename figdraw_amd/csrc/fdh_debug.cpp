@@ -12,11 +12,11 @@ uint64_t Context::record_digest() {
   drain();
   uint64_t h = 1469598103934665603ull;
   auto mix = [&](const void* p, size_t n) { const uint8_t* b = static_cast<const uint8_t*>(p); for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } };
-  const uint64_t n = n_total_;
+  const uint64_t n = frame_.n_records();
   mix(&n, sizeof n);
   uint32_t ext_base = 0;
-  for (const Piece& p : pieces_) {
-    const Lane& L = lane(p.lane);
+  for (const Piece& p : frame_.pieces()) {
+    const Lane& L = frame_.lane(p.lane);
     for (uint32_t i = 0; i < p.n; i++) {
       DrawRec r = L.recs[p.first + i];
       record_host_form(r);
@@ -25,9 +25,9 @@ uint64_t Context::record_digest() {
     }
     ext_base += p.n_ext;
   }
-  for (const Piece& p : pieces_) { const Lane& L = lane(p.lane); for (uint32_t i = 0; i < p.n; i++) mix(&L.bins[p.first + i].box, sizeof(BBox)); }
-  for (const Piece& p : pieces_) { const Lane& L = lane(p.lane); for (uint32_t i = 0; i < p.n_ext; i++) mix(&L.exts[p.ext_first + i], sizeof(QuadExt)); }
-  for (const Phase& ph : phases_) { mix(&ph.first, sizeof ph.first); mix(&ph.count, sizeof ph.count); mix(&ph.blur, sizeof ph.blur); }
+  for (const Piece& p : frame_.pieces()) { const Lane& L = frame_.lane(p.lane); for (uint32_t i = 0; i < p.n; i++) mix(&L.bins[p.first + i].box, sizeof(BBox)); }
+  for (const Piece& p : frame_.pieces()) { const Lane& L = frame_.lane(p.lane); for (uint32_t i = 0; i < p.n_ext; i++) mix(&L.exts[p.ext_first + i], sizeof(QuadExt)); }
+  for (const Phase& ph : frame_.phases()) { mix(&ph.first, sizeof ph.first); mix(&ph.count, sizeof ph.count); mix(&ph.blur, sizeof ph.blur); }
   return h;
 }
 
@@ -43,11 +43,11 @@ void Context::debug_verify_upload(uint32_t out[24]) {
   FDH_HIP(hipStreamSynchronize(stream_));
   for (int i = 0; i < 24; i++) out[i] = 0;
   const LaunchJob& J = job_;
-  out[10] = (uint32_t)pieces_.size(); out[11] = n_total_;
-  if (!J.dv.recs || n_total_ == 0) return;
-  std::vector<DrawRec> recs(n_total_);
-  std::vector<BinRec> bins(n_total_);
-  std::vector<QuadExt> exts(n_ext_total_);
+  out[10] = (uint32_t)frame_.pieces().size(); out[11] = frame_.n_records();
+  if (!J.dv.recs || frame_.n_records() == 0) return;
+  std::vector<DrawRec> recs(frame_.n_records());
+  std::vector<BinRec> bins(frame_.n_records());
+  std::vector<QuadExt> exts(frame_.n_extensions());
   FDH_HIP(hipMemcpy(recs.data(), J.dv.recs, recs.size() * sizeof(DrawRec), hipMemcpyDeviceToHost));
   FDH_HIP(hipMemcpy(bins.data(), J.dv.binrecs, bins.size() * sizeof(BinRec), hipMemcpyDeviceToHost));
   if (!exts.empty()) FDH_HIP(hipMemcpy(exts.data(), J.dv.exts, exts.size() * sizeof(QuadExt), hipMemcpyDeviceToHost));
@@ -69,8 +69,8 @@ void Context::debug_verify_upload(uint32_t out[24]) {
     }
   };
   uint32_t r0 = 0, e0 = 0;
-  for (const Piece& p : pieces_) {
-    const Lane& L = lane(p.lane);
+  for (const Piece& p : frame_.pieces()) {
+    const Lane& L = frame_.lane(p.lane);
     std::vector<DrawRec> want(L.recs.p + p.first, L.recs.p + p.first + p.n);
     for (DrawRec& r : want) if (r.op_mode & F_GENERAL) r.ext = r.ext - p.ext_first + e0;
     cmp(0, p.lane, recs.data() + r0, want.data(), (size_t)p.n * sizeof(DrawRec), (size_t)r0 * sizeof(DrawRec));
@@ -96,11 +96,11 @@ void Context::debug_verify_upload(uint32_t out[24]) {
   // the bin boxes the upload kernel derives from the bin records: out[17] boxes that differ from the host's, out[18] first index,
   // out[19] device value, out[20] host value
   {
-    std::vector<uint32_t> box(n_total_);
+    std::vector<uint32_t> box(frame_.n_records());
     FDH_HIP(hipMemcpy(box.data(), J.dv.binbox, box.size() * 4, hipMemcpyDeviceToHost));
     uint32_t g0 = 0;
-    for (const Piece& p : pieces_) {
-      const Lane& L = lane(p.lane);
+    for (const Piece& p : frame_.pieces()) {
+      const Lane& L = frame_.lane(p.lane);
       for (uint32_t i = 0; i < p.n; i++, g0++) {
         if (g0 == 0 && out[1]) continue;  // (a folded clear emptied record 0's box on the device side)
         if (box[g0] == L.boxes.p[p.first + i]) continue;
@@ -160,7 +160,7 @@ void Context::debug_read_surface(int which, uint8_t* out) {
   if (!src) throw Error(FDH_ERR_INVALID, "debug_read_surface: no such surface (or no frame yet)");
   FDH_HIP(hipSetDevice(device_));
   FDH_HIP(hipStreamSynchronize(stream_));
-  FDH_HIP(hipMemcpy(out, src, (size_t)W_ * H_ * 4, hipMemcpyDeviceToHost));
+  FDH_HIP(hipMemcpy(out, src, (size_t)env_.W * env_.H * 4, hipMemcpyDeviceToHost));
 }
 
 }  // namespace fdh

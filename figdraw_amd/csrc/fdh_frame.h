@@ -1,10 +1,13 @@
 // fdh_frame.h -- the recorded frame and its launch description: a phase and its blur node, the lane one thread records into, the pieces
 // that put the lanes' records into painter's order, the layout of the frame's device block, and the LaunchJob the submit side works from.
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "fdh_kernels.h"
+#include "fdh_plain.h"   // PhaseFlags, PhaseSum, PickTag
 #include "fdh_memory.h"
 
 namespace fdh {
@@ -64,10 +67,93 @@ struct Lane {
   int count_close();  // the largest count of any bin since the last close; leaves the array zeroed
 };
 
+// (in the header: once per record on the record path, inlined into Recorder::commit_bins)
+inline void Lane::count_add(const BBox& b) {
+  if (bbox_empty(b)) return;
+  constexpr int kBinShift = 6;
+  static_assert((1 << kBinShift) == kBin, "bins are 64 px");
+  const int bx0 = b.x0 >> kBinShift, by0 = b.y0 >> kBinShift, bx1 = ((b.x1 - 1) >> kBinShift) + 1, by1 = ((b.y1 - 1) >> kBinShift) + 1;  // [bx0,bx1) x [by0,by1)
+  if (bx1 >= dw || by1 >= dh) return;  // (bounds are clipped to the frame: cannot happen)
+  int* d = diff.data();
+  d[(size_t)by0 * dw + bx0]++; d[(size_t)by0 * dw + bx1]--; d[(size_t)by1 * dw + bx0]--; d[(size_t)by1 * dw + bx1]++;
+  if (!touched) { tx0 = bx0; ty0 = by0; tx1 = bx1; ty1 = by1; touched = true; }
+  else { tx0 = std::min(tx0, bx0); ty0 = std::min(ty0, by0); tx1 = std::max(tx1, bx1); ty1 = std::max(ty1, by1); }
+}
+
 struct Piece {
   int lane = 0;                     // (-1: the lane Context::consolidate_pieces copies a frame of too many pieces into)
   uint32_t first = 0, n = 0;        // records [first, first + n) of the lane
   uint32_t ext_first = 0, n_ext = 0;  // their quad extensions
+};
+
+// The frame as it is being recorded (calling thread): kStaging sets of lanes in rotation, the pieces that put the current set's records
+// into painter's order, the phases and their blur nodes, and what a frame's launch is sized by (list stride, deepest clip, phase 0's
+// fragment counts).  Written by the calling thread's recorder (Context), the join of a sibling group (ParallelWalk::group) and
+// Context::consolidate_pieces; read by prepare's stages and the debug digests.  WHEN a set may be used again is submission's business
+// (Context::wait_staging): the frame only says which set is current.
+class RecordedFrame {
+ public:
+  static constexpr int kStaging = 4;
+  RecordedFrame(bool host_only, int device) : host_only_(host_only), device_(device) {}
+  int next_set() const { return (set_ + 1) % kStaging; }  // the set begin() turns to (its last upload must have run by then)
+  // The records of this frame go into the next set of lanes: the set's last user was the frame kStaging frames ago.  Lane 0 cleared,
+  // one empty phase, lane 0's first piece open.
+  Lane& begin(int w, int h);
+
+  // ---- readers
+  const std::vector<Piece>& pieces() const { return pieces_; }
+  const std::vector<Phase>& phases() const { return phases_; }
+  const std::vector<BlurJob>& blurs() const { return blurs_; }
+  uint32_t n_records() const { return n_total_; }      // in closed pieces (the whole frame once it has ended)
+  uint32_t n_extensions() const { return n_ext_total_; }
+  int list_stride() const { return stride_max_; }      // max over the closed phases
+  int deepest_clip() const { return deepest_clip_; }
+  const int64_t* frag_mode() const { return frag_mode_; }  // phase 0: covered fragments by mode [4], elliptical, other
+  int64_t frag_ellip() const { return frag_ellip_; }
+  int64_t frag_other() const { return frag_other_; }
+  int set() const { return set_; }
+  uint64_t frame_no() const { return frame_no_; }
+  const Lane& lane(int i) const { return i < 0 ? *merge_lane_[(size_t)set_] : *lanes_[(size_t)set_][(size_t)i]; }  // (-1: consolidate_pieces' lane)
+  Lane& lane(int i) { return const_cast<Lane&>(static_cast<const RecordedFrame*>(this)->lane(i)); }
+  uint32_t global_index(uint32_t lane0_index) const { return lane0_index + g0_delta_; }
+  uint32_t global_count() const;  // records of the frame so far
+
+  // ---- writers: pieces / phases
+  uint32_t open_piece();   // lane 0's records from here on form a new piece; returns its first lane index
+  void close_piece();
+  void add_piece(const Piece& p);  // a pool thread's chunk, in order (the caller closed lane 0's piece before the group)
+  void add_sum(const PhaseSum& s, int depth_base);
+  void add_stride(int extra) { phase_extra_ += extra; }  // the current phase: bound contributed by pool threads' lanes
+  void close_phase(const PhaseSum& rest);  // the phase ends here: summary, bins reached, its share of the list stride
+  void split_phase(const PhaseSum& rest, int blur);  // a blurred snapshot is a barrier in painter's order
+  void add_blur(const BlurJob& j) { blurs_.push_back(j); }
+  void pool_slots(int slots);      // lanes 1 .. slots, ready for a sibling group
+  void rewind_lane(int i, size_t recs, size_t exts);  // ... and back to where it stood before a group that failed
+  Lane& merge_lane();              // consolidate_pieces: the current set's spare lane, cleared ...
+  void replace_pieces(const Piece& all) { pieces_.assign(1, all); }  // ... and the frame as one piece of it
+  void release_lanes() { for (auto& set : lanes_) set.clear(); }
+  void release_merge_lanes() { for (auto& l : merge_lane_) l.reset(); }
+
+ private:
+  Lane& ensure_lane(int i);
+  const bool host_only_;
+  const int device_;
+  int bins_x_ = 0, bins_y_ = 0;
+  std::vector<Piece> pieces_;      // the frame in painter's order
+  bool piece_open_ = false;        // the last piece is lane 0's and still growing
+  uint32_t n_total_ = 0, n_ext_total_ = 0;  // records / extensions in closed pieces
+  uint32_t g0_delta_ = 0;          // global index of a record of lane 0's open piece = its lane index + this
+  std::vector<Phase> phases_;
+  std::vector<BlurJob> blurs_;
+  BBox phase_u_{0, 0, 0, 0};       // union of the current phase's record bounds
+  int stride_max_ = 1;             // list stride so far: max over the closed phases
+  int phase_extra_ = 0;            // the current phase: bound contributed by pool threads' lanes (sum of their own maxima)
+  int deepest_clip_ = 0;
+  int64_t frag_mode_[4] = {0, 0, 0, 0}, frag_ellip_ = 0, frag_other_ = 0;  // phase 0
+  std::vector<std::unique_ptr<Lane>> lanes_[kStaging];
+  std::unique_ptr<Lane> merge_lane_[kStaging];
+  int set_ = 0;
+  uint64_t frame_no_ = 0;
 };
 
 // Where everything lies in a frame's device block: records | extensions | bin records | bin boxes | chunk boxes | phase table | blur

@@ -44,7 +44,7 @@ struct LayerLinks {
 };
 
 struct Walker;
-struct ParallelWalk {  // (a friend of Context: the pool threads' recorders and lanes are the context's)
+struct ParallelWalk {  // (the pool threads' recorders and lanes are the context's: Context::pool_recorder, Context::frame)
   static bool group(Walker& main, const FdhLayer& L, const int* items, int n);
 };
 
@@ -53,7 +53,7 @@ struct Walker {
   const FdhScene& scene;
   float ui;
   LayerLinks* links;       // shared by the calling thread's walker and the pool threads' (built by the former, before a group starts)
-  bool can_fork = false;   // the calling thread's walker outside any group: large sibling groups go to the pool
+  Context* fork_cx = nullptr;  // the calling thread's walker outside any group: its context, whose pool large sibling groups go to
 
   float scaled(float v) const { return v * ui; }  // common/shared.nim:94-95
 
@@ -523,7 +523,7 @@ struct Walker {
     for (size_t o = 0; o < sizeof(FdhFig); o += 64) __builtin_prefetch(p + o, 0, 3);
   }
   void siblings(const FdhLayer& L, const int* items, int n) {
-    if (!can_fork || n < kForkMin) { for (int k = 0; k < n; k++) { if (k + 1 < n) prefetch_node(L, items[k + 1]); node(L, items[k]); } return; }
+    if (!fork_cx || n < kForkMin) { for (int k = 0; k < n; k++) { if (k + 1 < n) prefetch_node(L, items[k + 1]); node(L, items[k]); } return; }
     int i = 0;
     while (i < n) {
       if (has_blur(L, items[i])) { node(L, items[i]); i++; continue; }
@@ -543,7 +543,7 @@ struct Walker {
     // picking: this node owns every record its stage makes -- shadows, fill, stroke, glyph / image quads, curve spans, the blur
     // composite, its clip and rect-mask records (its children's records carry their own tags)
     const PickTag own{L.zlevel, idx};
-    ctx.tag_ = own;
+    ctx.set_tag(own);
     float box[4], rx[4], ry[4];
     box_of(n, box);
     radii(n, rx, ry);
@@ -616,7 +616,7 @@ struct Walker {
     // children -- a table's viewport -- otherwise strides over all its grandchildren to find them, a few MB of node structs.
     if (n.child_count > 0) {
       links->build(L);
-      if (can_fork && n.child_count >= kForkMin) {
+      if (fork_cx && n.child_count >= kForkMin) {
         std::vector<int> kids;
         kids.reserve((size_t)n.child_count);
         for (int i = links->first_child[(size_t)idx]; i >= 0 && (int)kids.size() < n.child_count; i = links->next_sibling[(size_t)i]) kids.push_back(i);
@@ -631,7 +631,7 @@ struct Walker {
         }
       }
     }
-    ctx.tag_ = own;
+    ctx.set_tag(own);
     if (rmask) ctx.pop_rect_mask();
     if (clip) ctx.pop_mask();
     if (xf) ctx.restore_transform();
@@ -649,9 +649,10 @@ struct Walker {
 // around the group grow by each chunk's union, the phase takes each chunk's summary, the list stride each thread's maximum.
 // Subtrees holding a backdrop-blur node never get here (Walker::siblings): a blur splits the frame into phases.
 bool ParallelWalk::group(Walker& mw, const FdhLayer& L, const int* items, int n) {
-  Context& C = *mw.ctx.cx_;
+  Context& C = *mw.fork_cx;
+  RecordedFrame& F = C.frame();
   const int helpers = C.walk_threads();
-  if (helpers <= 0 || C.rec_on_ || !C.frame_begun_) return false;
+  if (helpers <= 0 || !C.may_fork()) return false;
   Context::HostTimer t_group(C.host_ns_[7]);
   const int slots = helpers + 1;
   // (every chunk is a piece of the frame -- three upload runs, a merge step --, and a frame's run table holds 31 pieces; three chunks per
@@ -660,9 +661,7 @@ bool ParallelWalk::group(Walker& mw, const FdhLayer& L, const int* items, int n)
   if (n_chunks < 2) return false;
   struct alignas(128) Out {
     Piece p;
-    PhaseSum s;
-    BBox outer{0, 0, 0, 0};
-    int64_t frags = 0, culled = 0;
+    ChunkResult r;
     bool serial_only = false;
     std::exception_ptr err;
     int slot = -1;
@@ -671,15 +670,15 @@ bool ParallelWalk::group(Walker& mw, const FdhLayer& L, const int* items, int n)
   // chunk c covers items [cut[c], cut[c + 1]): equal counts the first time a group is seen, then by what the chunks cost last time
   // (cost spread evenly over a chunk's items; the new cuts are the quantiles of that piecewise-constant density)
   Context::GroupCuts* gc = nullptr;
-  for (auto& g : C.group_cuts_) if (g.first_item == items[0] && g.n == n && (int)g.cut.size() == n_chunks + 1) { gc = &g; break; }
+  for (auto& g : C.group_cuts()) if (g.first_item == items[0] && g.n == n && (int)g.cut.size() == n_chunks + 1) { gc = &g; break; }
   if (!gc) {
-    if (C.group_cuts_.size() >= 16) {  // (forget the one that has not come for the longest)
+    if (C.group_cuts().size() >= 16) {  // (forget the one that has not come for the longest)
       size_t old = 0;
-      for (size_t i = 1; i < C.group_cuts_.size(); i++) if (C.group_cuts_[i].used < C.group_cuts_[old].used) old = i;
-      C.group_cuts_.erase(C.group_cuts_.begin() + (long)old);
+      for (size_t i = 1; i < C.group_cuts().size(); i++) if (C.group_cuts()[i].used < C.group_cuts()[old].used) old = i;
+      C.group_cuts().erase(C.group_cuts().begin() + (long)old);
     }
-    C.group_cuts_.emplace_back();
-    gc = &C.group_cuts_.back();
+    C.group_cuts().emplace_back();
+    gc = &C.group_cuts().back();
     gc->first_item = items[0]; gc->n = n;
     gc->cut.resize((size_t)n_chunks + 1);
     for (int c = 0; c <= n_chunks; c++) gc->cut[(size_t)c] = (int)((int64_t)c * n / n_chunks);
@@ -704,39 +703,29 @@ bool ParallelWalk::group(Walker& mw, const FdhLayer& L, const int* items, int n)
       gc->cut = cut;
     }
   }
-  gc->used = C.frame_no_;
+  gc->used = F.frame_no();
   const std::vector<int> cut = gc->cut;  // (a copy: the pool threads read it while nothing else may touch the cache)
   mw.links->build(L);  // (the pool threads read the links: built before they start)
-  C.pool_slots(slots);
+  F.pool_slots(slots);
+  for (int s = 0; s < slots; s++) C.pool_recorder(s);  // (made here: the pool's threads only look them up)
   struct Mark { size_t recs, exts; };
   std::vector<Mark> marks((size_t)slots);
-  for (int s = 0; s < slots; s++) { Lane& Ln = C.lane(s + 1); marks[(size_t)s] = Mark{Ln.recs.n, Ln.exts.n}; }
+  for (int s = 0; s < slots; s++) { Lane& Ln = F.lane(s + 1); marks[(size_t)s] = Mark{Ln.recs.n, Ln.exts.n}; }
   std::vector<int> slot_max((size_t)slots, 0);
   const Recorder& base = mw.ctx;
-  const int outer_rmasks = (int)base.rect_masks_.size() + base.outer_rect_masks_;
-  const bool outer_open = !base.open_ops_.empty() || base.outer_open_;
-  C.close_piece();
+  const int outer_rmasks = base.rect_masks_around();
+  const bool outer_open = base.clips_open();
+  F.close_piece();
   auto fn = [&](int slot, int c) {
-    Recorder& R = *C.pool_recs_[(size_t)slot];
-    Lane& Ln = C.lane(slot + 1);
+    Recorder& R = C.pool_recorder(slot);
+    Lane& Ln = F.lane(slot + 1);
     if (c < 0) { slot_max[(size_t)slot] = Ln.count_close(); return; }
     Out& o = outs[(size_t)c];
-    thread_local int t_dev = -1;
-    if (!C.host_only_ && t_dev != C.device_) { (void)hipSetDevice(C.device_); t_dev = C.device_; }  // (a lane's pinned mirror is allocated by the thread that publishes into it)
-    R.lane_ = &Ln;
-    R.mat_ = base.mat_; R.mats_.clear();
-    R.aa_ = base.aa_; R.subpixel_shift_ = base.subpixel_shift_;
-    R.mask_begun_ = false; R.mask_depth_ = 0;
-    R.rect_masks_.clear(); R.outer_rect_masks_ = outer_rmasks;
-    R.open_ops_.clear(); R.outer_open_ = outer_open; R.outer_union_ = BBox{0, 0, 0, 0};
-    R.depth_now_ = 0;
-    R.sum_ = PhaseSum{};
-    R.fragments_ = 0; R.culled_draws_ = 0;
-    R.phase_floor_ = (int)Ln.recs.n;
-    R.tag_ = base.tag_;
+    C.use_device_here();
+    R.adopt(base, Ln, outer_rmasks, outer_open);
     o.p.lane = slot + 1; o.p.first = (uint32_t)Ln.recs.n; o.p.ext_first = (uint32_t)Ln.exts.n;
     try {
-      Walker w{R, mw.scene, mw.ui, mw.links, false};
+      Walker w{R, mw.scene, mw.ui, mw.links, nullptr};
       w.depth = mw.depth;
       const int i0 = cut[(size_t)c], i1 = cut[(size_t)c + 1];
       for (int k = i0; k < i1; k++) { if (k + 1 < i1) Walker::prefetch_node(L, items[k + 1]); w.node(L, items[k]); }
@@ -750,7 +739,7 @@ bool ParallelWalk::group(Walker& mw, const FdhLayer& L, const int* items, int n)
       try { Ln.publish(o.p.first, o.p.n, o.p.ext_first, o.p.n_ext); }  // (final: every clip the chunk opened it closed)
       catch (...) { o.err = std::current_exception(); }
     }
-    o.s = R.sum_; o.outer = R.outer_union_; o.frags = R.fragments_; o.culled = R.culled_draws_;
+    o.r = R.finish_chunk();
   };
   bool ran;
   { Context::HostTimer t(C.host_ns_[8]); ran = WalkPool::get().run(helpers, n_chunks, fn); }
@@ -758,12 +747,8 @@ bool ParallelWalk::group(Walker& mw, const FdhLayer& L, const int* items, int n)
   std::exception_ptr err;
   for (const Out& o : outs) { if (o.serial_only || o.err) failed = true; if (o.err && !err) err = o.err; }
   if (failed) {  // nothing of the group stays: the calling thread walks it itself (or the frame ends with the error)
-    for (int s = 0; s < slots; s++) {
-      Lane& Ln = C.lane(s + 1);
-      Ln.recs.n = Ln.bins.n = Ln.boxes.n = marks[(size_t)s].recs; Ln.exts.n = marks[(size_t)s].exts;
-      if (C.pick_frame_) Ln.tags.n = marks[(size_t)s].recs;
-    }
-    C.open_piece();
+    for (int s = 0; s < slots; s++) F.rewind_lane(s + 1, marks[(size_t)s].recs, marks[(size_t)s].exts);
+    C.reopen_piece();
     if (err) std::rethrow_exception(err);
     return false;
   }
@@ -771,18 +756,16 @@ bool ParallelWalk::group(Walker& mw, const FdhLayer& L, const int* items, int n)
   gc->cost.resize((size_t)n_chunks);
   for (int c = 0; c < n_chunks; c++) gc->cost[(size_t)c] = (float)outs[(size_t)c].p.n + 0.25f * (float)(cut[(size_t)c + 1] - cut[(size_t)c]);
   Piece run{};
-  PhaseSum none{};
   for (const Out& o : outs) {
     // (chunks one thread took back to back lie back to back in its lane: one piece)
     if (run.n && run.lane == o.p.lane && run.first + run.n == o.p.first && run.ext_first + run.n_ext == o.p.ext_first) { run.n += o.p.n; run.n_ext += o.p.n_ext; }
-    else { if (run.n) C.add_piece(run, none, BBox{0, 0, 0, 0}, 0, 0); run = o.p; }
-    Piece nothing{};
-    C.add_piece(nothing, o.s, o.outer, o.frags, o.culled);
+    else { F.add_piece(run); run = o.p; }
+    F.add_sum(o.r.sum, C.absorb(o.r));
   }
-  if (run.n) C.add_piece(run, none, BBox{0, 0, 0, 0}, 0, 0);
-  for (int s = 0; s < slots; s++) C.phase_extra_ += slot_max[(size_t)s];
-  C.open_piece();
-  C.parallel_groups_++;
+  F.add_piece(run);
+  for (int s = 0; s < slots; s++) F.add_stride(slot_max[(size_t)s]);
+  C.reopen_piece();
+  C.count_parallel_group();
   return true;
 }
 
@@ -816,7 +799,7 @@ template <typename Walk> void Context::walk_frame(float fw, float fh, bool clear
     walk(&links);
     restore_transform();
   } catch (...) {
-    frame_begun_ = false;
+    frame_env_.frame_begun = false;
     throw;
   }
   end_frame();
@@ -825,7 +808,7 @@ template <typename Walk> void Context::walk_frame(float fw, float fh, bool clear
 void Context::render_frame(const FdhScene* scene, float fw, float fh, bool clear, const float rgba[4]) {
   if (!scene || (scene->n_layers > 0 && !scene->layers)) throw Error(FDH_ERR_INVALID, "render_frame: null scene");
   walk_frame(fw, fh, clear, rgba, *scene, [&](LayerLinks* links) {
-    Walker wk{*this, *scene, ui_scale_, links, true};
+    Walker wk{*this, *scene, ui_scale_, links, this};
     for (int l = 0; l < scene->n_layers; l++) {
       const FdhLayer& L = scene->layers[l];
       if ((L.n_nodes > 0 && !L.nodes) || (L.n_roots > 0 && !L.root_ids)) throw Error(FDH_ERR_INVALID, "render_frame: a layer's node or root array is null");
@@ -846,68 +829,47 @@ void Context::scene_render() {
   const FdhScene& view = V.scene;
   walk_frame(R.fw(), R.fh(), R.clear(), R.rgba(), view, [&](LayerLinks* links) {
     rec_diff_upload_ = true;  // consecutive frames of a retained scene differ in a few records: Context::patch_runs uploads the difference
-    const bool config_changed = R.latch_settings(ui_scale_, aa_, subpixel_enabled_, subpixel_variants_);
+    const bool config_changed = R.latch_settings(ui_scale_, aa_, env_.subpixel_enabled, env_.subpixel_variants);
     R.count_begin();
-    Walker wk{*this, view, ui_scale_, links, false};  // (roots are walked one by one: each has its cache entry)
-    Lane& L0 = lane(0);
+    Walker wk{*this, view, ui_scale_, links, nullptr};  // (roots are walked one by one: each has its cache entry)
+    const Lane& L0 = frame_.lane(0);
     for (size_t l = 0; l < R.n_layers(); l++) {
       const RetainedLayer& D = R.layer(l);
       RetainedRoot* const caches = D.roots.empty() ? nullptr : &R.cache(l, 0);  // (parallel to D.roots)
       for (size_t s = 0; s < D.roots.size(); s++) {
         RetainedRoot& C = caches[s];
         // (cached records were culled to the rows in force when they were made: good for any frame that produces no row beyond them)
-        if (!C.dirty && C.cacheable && !config_changed && C.cull_y0 <= cull_y0_ && C.cull_y1 >= cull_y1_ && C.atlas_epoch == atlas_.epoch() &&
-            (C.tagged || !pick_frame_)) {
-          splice_cached(C);
+        if (!C.dirty && C.cacheable && !config_changed && C.cull_y0 <= env_.cull_y0 && C.cull_y1 >= env_.cull_y1 && C.atlas_epoch == atlas_.epoch() &&
+            (C.tagged || !env_.pick_frame)) {
+          splice(C);
           R.count_reused();
           continue;
         }
-        const size_t r0 = L0.recs.n, e0 = L0.exts.n, p0 = phases_.size(), b0 = blurs_.size();
-        const int64_t f0 = fragments_;
-        const int d0 = depth_now_;
-        add_sum(sum_, 0);  // (what the phase has so far goes to the phase: the root's own summary starts from nothing)
-        sum_ = PhaseSum{};
+        const size_t r0 = L0.recs.n, e0 = L0.exts.n, p0 = frame_.phases().size(), b0 = frame_.blurs().size();
+        frame_.add_sum(take_sum(), 0);  // (what the phase has so far goes to the phase: the root's own summary starts from nothing)
+        const RootMark m0 = mark();
         wk.node(view.layers[l], D.roots[s]);
         R.count_walked();
         C.dirty = false;
         C.atlas_epoch = atlas_.epoch();
-        C.cull_y0 = cull_y0_; C.cull_y1 = cull_y1_;
-        C.cacheable = phases_.size() == p0 && blurs_.size() == b0;
+        C.cull_y0 = env_.cull_y0; C.cull_y1 = env_.cull_y1;
+        C.cacheable = frame_.phases().size() == p0 && frame_.blurs().size() == b0;
         C.recs.clear(); C.bins.clear(); C.exts.clear(); C.tags.clear();
-        C.tagged = pick_frame_;
+        C.tagged = env_.pick_frame;
         if (C.cacheable) {
-          if (pick_frame_) C.tags.assign(L0.tags.p + r0, L0.tags.p + L0.tags.n);
+          if (env_.pick_frame) C.tags.assign(L0.tags.p + r0, L0.tags.p + L0.tags.n);
           C.recs.assign(L0.recs.p + r0, L0.recs.p + L0.recs.n);
           C.bins.assign(L0.bins.p + r0, L0.bins.p + L0.bins.n);
           C.exts.assign(L0.exts.p + e0, L0.exts.p + L0.exts.n);
           for (DrawRec& r : C.recs) if (r.op_mode & F_GENERAL) r.ext -= (uint32_t)e0;
-          if (!C.bins.empty()) C.bins.back().flags &= ~LE_SHARE;  // (what follows the root is decided at every splice: Context::splice_cached)
-          C.fragments = fragments_ - f0;
-          C.sum = sum_;
-          C.sum.deepest = std::max(0, sum_.deepest - d0);
+          if (!C.bins.empty()) C.bins.back().flags &= ~LE_SHARE;  // (what follows the root is decided at every splice: Recorder::splice)
+          const RootSince added = since(m0);
+          C.fragments = added.fragments;
+          C.sum = added.sum;
         }
       }
     }
   });
-}
-
-// A retained root's cached records take their place in lane 0 (fdh_scene_render): a memcpy per array, the extension indices
-// moved to where the extensions landed, the list-stride count and the phase summary brought up to date.
-void Context::splice_cached(const RetainedRoot& C) {
-  Lane& L = lane(0);
-  const uint32_t r0 = (uint32_t)L.recs.n, e0 = (uint32_t)L.exts.n;
-  L.recs.append(C.recs.data(), C.recs.size());
-  L.bins.append(C.bins.data(), C.bins.size());
-  L.exts.append(C.exts.data(), C.exts.size());
-  if (pick_frame_) L.tags.append(C.tags.data(), C.tags.size());  // (scene_render splices only tagged roots into a picking frame)
-  if (!C.exts.empty())
-    for (size_t i = r0; i < L.recs.n; i++) if (L.recs[i].op_mode & F_GENERAL) L.recs[i].ext += e0;
-  L.boxes.reserve(L.bins.n);
-  for (size_t i = r0; i < L.bins.n; i++) { L.count_add(L.bins[i].box); L.boxes[i] = bin_box_of(L.bins[i].box, 6 + binbox_shift_); }
-  L.boxes.n = L.bins.n;
-  sum_.merge(C.sum, depth_now_);
-  fragments_ += C.fragments;
-  if (!C.recs.empty()) link_share(r0);  // the record in front of the splice may share its distance field with the first one here
 }
 
 }  // namespace fdh

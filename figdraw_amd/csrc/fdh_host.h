@@ -2,7 +2,7 @@
 #pragma once
 #include <cmath>
 
-#include "fdh_context.h"
+#include "fdh_recorder.h"
 
 namespace fdh {
 

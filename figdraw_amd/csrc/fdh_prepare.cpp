@@ -128,7 +128,7 @@ void Context::prepare(LaunchJob& J) {
   size_bin_buffers(J);
   layout_frame_block(J);
   choose_fused_blurs(J);
-  if (pieces_.size() * 3 + 2 > (size_t)kMaxUploadRuns) consolidate_pieces();  // more pieces than the upload's kernel-argument table holds
+  if (frame_.pieces().size() * 3 + 2 > (size_t)kMaxUploadRuns) consolidate_pieces();  // more pieces than the upload's kernel-argument table holds
   const FoldGuard fold = fold_clear(J);
   decide_opaque(J);
   damage_frame_key(J);
@@ -144,32 +144,32 @@ void Context::prepare(LaunchJob& J) {
 
 // what the launch side reads of the recorded frame, copied: the recording side moves on to the next frame
 void Context::describe_frame(LaunchJob& J) {
-  J.W = W_; J.H = H_; J.clear = clear_; J.clear_rgba8 = clear_rgba8_;
-  J.rec_y0 = culling() ? cull_y0_ : 0; J.rec_y1 = culling() ? cull_y1_ : H_;
-  J.latency_routes = latency_routes_;
-  J.phases = phases_;  // (copies: the recording side keeps its own for fdh_debug_record_digest)
-  J.blurs = blurs_;
-  J.n_recs = (int)n_total_;
-  J.n_exts = (int)n_ext_total_;
-  J.bins_x = (W_ + kBin - 1) / kBin;
-  J.bins_y = (H_ + kBin - 1) / kBin;
-  J.binbox_shift = binbox_shift_;
-  J.staging_slot = staging_i_;
+  J.W = env_.W; J.H = env_.H; J.clear = clear_; J.clear_rgba8 = clear_rgba8_;
+  J.rec_y0 = culling() ? env_.cull_y0 : 0; J.rec_y1 = culling() ? env_.cull_y1 : env_.H;
+  J.latency_routes = env_.latency_routes;
+  J.phases = frame_.phases();  // (copies: the recording side keeps its own for fdh_debug_record_digest)
+  J.blurs = frame_.blurs();
+  J.n_recs = (int)frame_.n_records();
+  J.n_exts = (int)frame_.n_extensions();
+  J.bins_x = (env_.W + kBin - 1) / kBin;
+  J.bins_y = (env_.H + kBin - 1) / kBin;
+  J.binbox_shift = env_.binbox_shift;
+  J.staging_slot = frame_.set();
 }
 
 void Context::size_bin_buffers(LaunchJob& J) {
   const int nb = J.bins_x * J.bins_y;
   // List stride = the largest number of draws any bin of any phase can receive: counted while the frame was recorded
   // (Lane::count_add / count_close per phase; lanes of pool threads add their own maxima: an upper bound)
-  J.list_stride = (stride_max_ + 7) & ~7;
+  J.list_stride = (frame_.list_stride() + 7) & ~7;
   reserve_quiet(d_lists_, (size_t)J.phases.size() * nb * J.list_stride);
   reserve_quiet(d_counts_, (size_t)J.phases.size() * nb);
   J.lists = d_lists_.ptr; J.counts = d_counts_.ptr;
   // clip nesting beyond the LDS stack (kMaskDepth levels): one global plane per extra level, 256 bytes per strip
   J.mask_spill = nullptr;
   J.spill_stride = (size_t)nb * 16 * 64;
-  if (deepest_clip_ > kMaskDepth) {
-    const size_t levels = (size_t)(deepest_clip_ - kMaskDepth);
+  if (frame_.deepest_clip() > kMaskDepth) {
+    const size_t levels = (size_t)(frame_.deepest_clip() - kMaskDepth);
     if (levels * J.spill_stride * sizeof(uint32_t) > ((size_t)2 << 30))
       throw Error(FDH_ERR_UNSUPPORTED, "clip masks nested too deep for this frame size (the spill plane would exceed 2 GiB)");
     reserve_quiet(d_mask_spill_, levels * J.spill_stride);
@@ -180,7 +180,7 @@ void Context::size_bin_buffers(LaunchJob& J) {
 // the one place that turns the layout into pointers and offsets the launches use
 void Context::layout_frame_block(LaunchJob& J) {
   FrameLayout& F = J.layout;
-  F.lay_out(n_total_, n_ext_total_, J.phases.size(), J.blurs);
+  F.lay_out(frame_.n_records(), frame_.n_extensions(), J.phases.size(), J.blurs);
   if (F.total >= ((size_t)1 << 32)) throw Error(FDH_ERR_UNSUPPORTED, "frame block beyond 4 GiB");
   reserve_quiet(d_frame_, F.total);
   uint8_t* const d = d_frame_.ptr;
@@ -205,23 +205,23 @@ void Context::layout_frame_block(LaunchJob& J) {
 // the clear colour: both passes as ONE kernel, out of place (k_blur_fx) -- launch_frame alternates between fb_ and alt_.
 // Which route is a matter of speed only -- the two give the same pixels bit for bit (tests/test_hip_parity.py): Context::pick_routes.
 void Context::choose_fused_blurs(LaunchJob& J) {
-  const bool fx_on = latency_routes_;  // (decided when the frame began: Context::pick_routes)
+  const bool fx_on = env_.latency_routes;  // (decided when the frame began: Context::pick_routes)
   J.blur_fused.assign(J.blurs.size(), 0);
   J.n_fused = 0;
   for (size_t i = 0; i < J.blurs.size(); i++) {
     const BlurJob& j = J.blurs[i];
     // (frames under 0.4 Mpx keep the two small-region passes, like every region of that size: launch_blur_h)
     static const bool any_size = [] { const char* e = std::getenv("FDH_FORCE_BLUR_PATH"); return e && std::atoi(e) == 3; }();
-    if (fx_on && clear_ && j.fuse_draw >= 0 && J.mx_w_h[i] && j.x0 == 0 && j.y0 == 0 && j.x1 == W_ && j.y1 == H_ && blur_fused_supported(j.taps.reach, W_, W_) &&
-        (any_size || (long long)W_ * H_ >= 384 * 1024)) {
+    if (fx_on && clear_ && j.fuse_draw >= 0 && J.mx_w_h[i] && j.x0 == 0 && j.y0 == 0 && j.x1 == env_.W && j.y1 == env_.H && blur_fused_supported(j.taps.reach, env_.W, env_.W) &&
+        (any_size || (long long)env_.W * env_.H >= 384 * 1024)) {
       J.blur_fused[i] = 1;
       J.n_fused++;
     }
   }
   if (J.n_fused > 0 && !alt_) {
-    FDH_HIP(hipMalloc((void**)&alt_, (size_t)W_ * H_ * 4));
-    poison_fresh(alt_, (size_t)W_ * H_ * 4);
-    FDH_HIP(hipMemsetAsync(alt_, 0, (size_t)W_ * H_ * 4, stream_));
+    FDH_HIP(hipMalloc((void**)&alt_, (size_t)env_.W * env_.H * 4));
+    poison_fresh(alt_, (size_t)env_.W * env_.H * 4);
+    FDH_HIP(hipMemsetAsync(alt_, 0, (size_t)env_.W * env_.H * 4, stream_));
   }
 }
 
@@ -235,14 +235,14 @@ void Context::choose_fused_blurs(LaunchJob& J) {
 Context::FoldGuard Context::fold_clear(LaunchJob& J) {
   FoldGuard g;
   static const bool fold_on = [] { const char* e = std::getenv("FDH_FOLD_CLEAR"); return !e || std::atoi(e) != 0; }();
-  if (fold_on && clear_ && !pieces_.empty() && J.phases[0].count > 0) {
-    const Piece& p0 = pieces_[0];
-    Lane& L = lane(p0.lane);
+  if (fold_on && clear_ && !frame_.pieces().empty() && J.phases[0].count > 0) {
+    const Piece& p0 = frame_.pieces()[0];
+    Lane& L = frame_.lane(p0.lane);
     BinRec& br = L.bins[p0.first];
     const DrawRec& r = L.recs[p0.first];
     const uint32_t om = r.op_mode;
     if (((om >> 12) & 15u) == OP_DRAW && (br.flags & LE_PLAIN) && !(br.flags & BR_CORE_REMOVED) && (br.flags & BR_HAS_CORE) && br.ix0 <= 0 && br.iy0 <= 0 &&
-        br.ix1 >= W_ && br.iy1 >= H_ && br.box.x0 <= 0 && br.box.y0 <= 0 && br.box.x1 >= W_ && br.box.y1 >= H_) {
+        br.ix1 >= env_.W && br.iy1 >= env_.H && br.box.x0 <= 0 && br.box.y0 <= 0 && br.box.x1 >= env_.W && br.box.y1 >= env_.H) {
       const float inv255 = 1.0f / 255.0f;
       const uint32_t c = r.col[0];
       float cf[3];
@@ -290,10 +290,10 @@ void Context::damage_frame_key(LaunchJob& J) const {
   auto mix = [&k](uint64_t v) { for (int b = 0; b < 8; b++) { k ^= (v >> (8 * b)) & 255u; k *= 1099511628211ull; } };
   uint32_t aa_bits = 0, ps_bits = 0;
   std::memcpy(&aa_bits, &ctx_aa_, 4); std::memcpy(&ps_bits, &pixel_scale_, 4);
-  mix((uint64_t)(uint32_t)W_ << 32 | (uint32_t)H_); mix((uint64_t)(uint32_t)J.bins_x << 32 | (uint32_t)J.bins_y);
+  mix((uint64_t)(uint32_t)env_.W << 32 | (uint32_t)env_.H); mix((uint64_t)(uint32_t)J.bins_x << 32 | (uint32_t)J.bins_y);
   mix((uint64_t)J.clear_rgba8 << 1 | (clear_ ? 1u : 0u)); mix((uint64_t)aa_bits << 32 | ps_bits);
   mix(atlas_.epoch()); mix((uint64_t)(uint32_t)atlas_.size());
-  mix((uint64_t)(latency_routes_ ? 1u : 0u) << 8 | (uint64_t)(uint32_t)cull_mode_);
+  mix((uint64_t)(env_.latency_routes ? 1u : 0u) << 8 | (uint64_t)(uint32_t)env_.cull_mode);
   J.damage_key = k;
 }
 
@@ -328,8 +328,8 @@ void Context::build_misc(const LaunchJob& J, bool tables_resident) {
     uint32_t* cb = reinterpret_cast<uint32_t*>(misc.data());
     for (size_t c = 0; c < F.n_chunks; c++) cb[c] = 0x7f7f7f7fu;
     size_t g = 0;
-    for (const Piece& p : pieces_) {
-      const uint32_t* bx = lane(p.lane).boxes.p + p.first;
+    for (const Piece& p : frame_.pieces()) {
+      const uint32_t* bx = frame_.lane(p.lane).boxes.p + p.first;
       for (uint32_t i = 0; i < p.n; i++, g++) {
         const uint32_t m = cb[g >> 8], v = bx[i];
         uint32_t o = 0;
@@ -379,14 +379,14 @@ void Context::build_misc(const LaunchJob& J, bool tables_resident) {
 // everywhere: comparing 110 KB to find that out, and keeping the shadow current, cost 12 us per frame -- only frames of a
 // retained scene take the diff route.)  False: the frame does not qualify, or too much of it differs -- gather_runs takes it whole.
 bool Context::patch_runs(LaunchJob& J, bool shadow_ok) {
-  if (!shadow_ok || pieces_.size() > 1 || (!pieces_.empty() && pieces_[0].lane != 0)) return false;
-  const Piece p0 = pieces_.empty() ? Piece{} : pieces_[0];
+  if (!shadow_ok || frame_.pieces().size() > 1 || (!frame_.pieces().empty() && frame_.pieces()[0].lane != 0)) return false;
+  const Piece p0 = frame_.pieces().empty() ? Piece{} : frame_.pieces()[0];
   if (p0.ext_first != 0) return false;  // (one piece of lane 0 starting at extension 0: the records' extension indices are the frame's already)
   const FrameLayout& F = J.layout;
   const std::vector<uint8_t>& misc = misc_host_;
   HostVec<uint8_t>& up_misc = misc_[J.staging_slot];
   const size_t o_misc = F.misc(), b_recs = F.n * sizeof(DrawRec), b_ext = F.n_ext * sizeof(QuadExt), b_bb = F.n * sizeof(BinRec);
-  Lane& L = lane(0);
+  Lane& L = frame_.lane(0);
   L.publish(0, 0, 0, 0);  // (the mirrors exist and fit the lane: their addresses are final, the device views may be taken)
   std::vector<UploadRun>& runs = J.runs;
   runs.clear();
@@ -434,10 +434,10 @@ void Context::gather_runs(LaunchJob& J, bool tables_resident) {
   };
   uint32_t at_rec = 0, at_ext = 0;
   std::memcpy(misc_[J.staging_slot].p, misc.data(), misc.size());
-  for (const Piece& p : pieces_) {
+  for (const Piece& p : frame_.pieces()) {
     // pieces the calling thread recorded are published here (clips open around a sibling group took the group's bounds after
     // their records were made); a pool thread published its pieces when it finished them
-    Lane& L = lane(p.lane);
+    Lane& L = frame_.lane(p.lane);
     if (p.lane <= 0) { HostTimer t(host_ns_[5]); L.publish(p.first, p.n, p.ext_first, p.n_ext); }
     add_run(L.d_recs + (size_t)p.first * sizeof(DrawRec), F.recs + (size_t)at_rec * sizeof(DrawRec), (size_t)p.n * sizeof(DrawRec), at_ext - p.ext_first, 2u);
     add_run(L.d_bins + (size_t)p.first * sizeof(BinRec), F.binrecs + (size_t)at_rec * sizeof(BinRec), (size_t)p.n * sizeof(BinRec), 0u, 1u);
@@ -453,8 +453,8 @@ void Context::gather_runs(LaunchJob& J, bool tables_resident) {
   if (shadow_.size() != F.total) shadow_.assign(F.total, 0);
   else if (!tables_resident) std::fill(shadow_.begin(), shadow_.end(), 0);
   size_t ar = 0, ae = 0;
-  for (const Piece& p : pieces_) {
-    const Lane& L = lane(p.lane);
+  for (const Piece& p : frame_.pieces()) {
+    const Lane& L = frame_.lane(p.lane);
     std::memcpy(shadow_.data() + F.recs + ar * sizeof(DrawRec), L.recs.p + p.first, (size_t)p.n * sizeof(DrawRec));
     if (p.ext_first != ae)  // (the device's copy holds frame-relative extension indices)
       for (size_t i = 0; i < p.n; i++) { DrawRec* r = reinterpret_cast<DrawRec*>(shadow_.data() + F.recs) + ar + i; if (r->op_mode & F_GENERAL) r->ext += (uint32_t)ae - p.ext_first; }
@@ -471,7 +471,7 @@ void Context::gather_runs(LaunchJob& J, bool tables_resident) {
 // a full-frame node; H read + H write + V read + V write + composite read) + records once
 void Context::account_frame(LaunchJob& J) {
   const size_t n = J.layout.n;
-  int64_t bytes = 4LL * W_ * H_ + (int64_t)n * (int64_t)sizeof(DrawRec), bytes_blur = 0, bytes_fused = 0, bytes_saved = 0;
+  int64_t bytes = 4LL * env_.W * env_.H + (int64_t)n * (int64_t)sizeof(DrawRec), bytes_blur = 0, bytes_fused = 0, bytes_saved = 0;
   // a cleared opaque surface stays opaque under SRC_ALPHA / ONE_MINUS_SRC_ALPHA blending (a' = sa + da (1 - sa), da = 1): a
   // fused vertical pass then replaces pixels under full coverage without reading them
   const bool surface_opaque = clear_ && (clear_rgba8_ >> 24) == 255u;
@@ -480,7 +480,7 @@ void Context::account_frame(LaunchJob& J) {
   stats_.bytes_blur_big_h = stats_.bytes_blur_big_v = 0;
   for (size_t bi = 0; bi < J.blurs.size(); bi++) {
     const BlurJob& j = J.blurs[bi];
-    const int ylo = std::max(0, j.y0 - j.taps.reach), yhi = std::min(H_, j.y1 + j.taps.reach);
+    const int ylo = std::max(0, j.y0 - j.taps.reach), yhi = std::min(env_.H, j.y1 + j.taps.reach);
     const int64_t a_h = (int64_t)(j.x1 - j.x0) * (yhi - ylo), a_v = (int64_t)(j.x1 - j.x0) * (j.y1 - j.y0);
     int64_t b_h = 4 * a_h + 4 * a_h, b_v = 4 * a_h + 4 * a_v;  // H read + H write; V read + V write
     // the consuming composite: fused into the V pass it reads the live surface there (where it has to blend); otherwise a
@@ -496,14 +496,14 @@ void Context::account_frame(LaunchJob& J) {
   }
   bytes += bytes_blur;
   stats_.bytes_blur = bytes_blur;
-  stats_.bytes_composite_main = 4LL * W_ * H_ * (clear_ ? 1 : 2) + (int64_t)J.phases[0].count * (int64_t)sizeof(DrawRec);
+  stats_.bytes_composite_main = 4LL * env_.W * env_.H * (clear_ ? 1 : 2) + (int64_t)J.phases[0].count * (int64_t)sizeof(DrawRec);
   // algorithmic flops of the phase-0 composite launch, SURVEY.md 8(d): per fragment ClipAA 25, DropShadow 35 + exp, InsetShadow
   // 70 + exp, AnnularAA 28 (other modes priced as ClipAA), elliptical corners + 30, blend + re-quantise + 16
-  for (int k = 0; k < 4; k++) stats_.fragments_main_by_mode[k] = frag_mode_[k];
-  stats_.fragments_main_elliptical = frag_ellip_;
-  stats_.fragments_main_other = frag_other_;
-  stats_.flops_composite_main = frag_mode_[0] * 25 + frag_mode_[1] * 36 + frag_mode_[2] * 71 + frag_mode_[3] * 28 + frag_other_ * 25 + frag_ellip_ * 30 +
-                                (frag_mode_[0] + frag_mode_[1] + frag_mode_[2] + frag_mode_[3] + frag_other_) * 16;
+  for (int k = 0; k < 4; k++) stats_.fragments_main_by_mode[k] = frame_.frag_mode()[k];
+  stats_.fragments_main_elliptical = frame_.frag_ellip();
+  stats_.fragments_main_other = frame_.frag_other();
+  stats_.flops_composite_main = frame_.frag_mode()[0] * 25 + frame_.frag_mode()[1] * 36 + frame_.frag_mode()[2] * 71 + frame_.frag_mode()[3] * 28 + frame_.frag_other() * 25 + frame_.frag_ellip() * 30 +
+                                (frame_.frag_mode()[0] + frame_.frag_mode()[1] + frame_.frag_mode()[2] + frame_.frag_mode()[3] + frame_.frag_other()) * 16;
   stats_.n_draws = (int32_t)n;
   stats_.n_phases = (int32_t)J.phases.size();
   stats_.n_blurs = (int32_t)J.blurs.size();
@@ -535,30 +535,27 @@ void Context::fence_staging() {
 void Context::pick_routes() {
   static const int fx_env = [] { const char* e = std::getenv("FDH_BLUR_FUSED"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }();
   const int route = blur_route_ >= 0 ? blur_route_ : fx_env;
-  latency_routes_ = route != 0;
+  frame_env_.latency_routes = route != 0;
 }
 
 // More pieces than the upload's run table holds (a frame with many parallel sibling groups): they are copied together into one
 // spare lane, in order, extension indices re-based -- the frame becomes one piece again.
 void Context::consolidate_pieces() {
-  std::unique_ptr<Lane>& slot = merge_lane_[(size_t)staging_i_];
-  if (!slot) { slot.reset(new Lane()); slot->set_pinned(!host_only_, device_); }
-  Lane& S = *slot;
-  S.clear();
-  S.recs.reserve(n_total_); S.bins.reserve(n_total_); S.exts.reserve(n_ext_total_);
-  for (const Piece& p : pieces_) {
-    const Lane& L = lane(p.lane);
+  Lane& S = frame_.merge_lane();
+  S.recs.reserve(frame_.n_records()); S.bins.reserve(frame_.n_records()); S.exts.reserve(frame_.n_extensions());
+  for (const Piece& p : frame_.pieces()) {
+    const Lane& L = frame_.lane(p.lane);
     const size_t r0 = S.recs.n, e0 = S.exts.n;
     S.recs.append(L.recs.p + p.first, p.n);
     S.bins.append(L.bins.p + p.first, p.n);
     S.exts.append(L.exts.p + p.ext_first, p.n_ext);
     S.boxes.append(L.boxes.p + p.first, p.n);
-    if (pick_frame_) S.tags.append(L.tags.p + p.first, p.n);
+    if (env_.pick_frame) S.tags.append(L.tags.p + p.first, p.n);
     for (size_t i = r0; i < S.recs.n; i++) if (S.recs[i].op_mode & F_GENERAL) S.recs[i].ext += (uint32_t)e0 - p.ext_first;
   }
   Piece all;
-  all.lane = -1; all.first = 0; all.n = n_total_; all.ext_first = 0; all.n_ext = n_ext_total_;
-  pieces_.assign(1, all);
+  all.lane = -1; all.first = 0; all.n = frame_.n_records(); all.ext_first = 0; all.n_ext = frame_.n_extensions();
+  frame_.replace_pieces(all);
 }
 
 }  // namespace fdh

@@ -12,7 +12,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "fdh_context.h"
+#include "fdh_recorder.h"
 #include "fdh_host.h"
 
 namespace fdh {
@@ -29,7 +29,7 @@ void Recorder::shrink_to_ink(const AtlasEntry& e, bool use_alpha, int level_t) {
   if ((r.op_mode & F_GENERAL) || b.x1 <= b.x0 || b.y1 <= b.y0) return;
   const InkBox ib = (use_alpha ? e.ink_a : e.ink_rgb)[std::min(level_t / 16, kInkLevels - 1)];
   if (ib.x1 <= ib.x0 || ib.y1 <= ib.y0) { b = BBox{0, 0, 0, 0}; r.bx0 = r.by0 = r.bx1 = r.by1 = 0; return; }  // nothing in the image reaches the level
-  const double S = (double)cx_->atlas_.size();
+  const double S = (double)env_.atlas->size();
   auto range = [&](double ua, double ut, double o, double inv, double lo_t, double hi_t, int& p0, int& p1) {
     // texel coordinate at pixel centre c: t(c) = (ua + (ut - ua) (c - o) inv) S - 0.5; pixels whose t lies in [lo_t - 3, hi_t + 2]
     const double A = (ut - ua) * inv * S, B = ua * S - 0.5 - A * o;
@@ -54,62 +54,40 @@ void Recorder::shrink_to_ink(const AtlasEntry& e, bool use_alpha, int level_t) {
 // (fdh_frontend.cpp): every BackendContext-level call between the two, as a JSON array of [name, args...] -- the format
 // oracle/figdraw_oracle.c records and oracle/ref_swiftshader.py replays.
 namespace {
-struct Rec {
-  std::string& s; bool& first; const bool on;
-  Rec(std::string& s_, bool& first_, bool on_, const char* name, size_t* mark, bool* mark_first) : s(s_), first(first_), on(on_) {
-    if (!on) return;
-    *mark = s.size(); *mark_first = first;  // (a call that turns out to be culled is taken back: Context::rec_drop_last)
-    s += first ? "[\"" : ",\n[\""; s += name; s += "\""; first = false;
-  }
-  ~Rec() { if (on) s += "]"; }
-  Rec& f(double v) { if (on) { char b[40]; std::snprintf(b, sizeof b, ",%.9g", v); s += b; } return *this; }
-  Rec& i(long long v) { if (on) { char b[32]; std::snprintf(b, sizeof b, ",%lld", v); s += b; } return *this; }
+struct Rec {  // one entry of the call log (CallLog::open), or nothing while the log is off
+  std::string* const s;
+  Rec(CallLog* log, const char* name) : s(log ? log->open(name) : nullptr) {}
+  ~Rec() { if (s) *s += "]"; }
+  Rec& f(double v) { if (s) { char b[40]; std::snprintf(b, sizeof b, ",%.9g", v); *s += b; } return *this; }
+  Rec& i(long long v) { if (s) { char b[32]; std::snprintf(b, sizeof b, ",%lld", v); *s += b; } return *this; }
   Rec& fv(const float* v, int n) {
-    if (on) { s += ",["; for (int k = 0; k < n; k++) { char b[40]; std::snprintf(b, sizeof b, "%s%.9g", k ? "," : "", (double)v[k]); s += b; } s += "]"; }
+    if (s) { *s += ",["; for (int k = 0; k < n; k++) { char b[40]; std::snprintf(b, sizeof b, "%s%.9g", k ? "," : "", (double)v[k]); *s += b; } *s += "]"; }
     return *this;
   }
-  Rec& col(FdhColor c) { if (on) { char b[48]; std::snprintf(b, sizeof b, ",[%d,%d,%d,%d]", c.r, c.g, c.b, c.a); s += b; } return *this; }
+  Rec& col(FdhColor c) { if (s) { char b[48]; std::snprintf(b, sizeof b, ",[%d,%d,%d,%d]", c.r, c.g, c.b, c.a); *s += b; } return *this; }
   Rec& cols(const FdhColor c[4]) {
-    if (on) { s += ",["; for (int k = 0; k < 4; k++) { char b[48]; std::snprintf(b, sizeof b, "%s[%d,%d,%d,%d]", k ? "," : "", c[k].r, c[k].g, c[k].b, c[k].a); s += b; } s += "]"; }
+    if (s) { *s += ",["; for (int k = 0; k < 4; k++) { char b[48]; std::snprintf(b, sizeof b, "%s[%d,%d,%d,%d]", k ? "," : "", c[k].r, c[k].g, c[k].b, c[k].a); *s += b; } *s += "]"; }
     return *this;
   }
   Rec& fill(const FdhFill& fl) {
-    if (on) {
+    if (s) {
       char b[200];
       std::snprintf(b, sizeof b, ",{\"kind\":%d,\"axis\":%d,\"start\":[%d,%d,%d,%d],\"mid\":[%d,%d,%d,%d],\"stop\":[%d,%d,%d,%d],\"mid_pos\":%d}", fl.kind, fl.axis,
                     fl.start.r, fl.start.g, fl.start.b, fl.start.a, fl.mid.r, fl.mid.g, fl.mid.b, fl.mid.a, fl.stop.r, fl.stop.g, fl.stop.b, fl.stop.a, fl.mid_pos);
-      s += b;
+      *s += b;
     }
     return *this;
   }
 };
 }  // namespace
-struct RecPause {  // a backend method that calls other backend methods records only itself
-  // (writes the flag only where it was on -- i.e. on the calling thread while the call recorder runs, when nothing is handed to the walk
-  // pool: written unconditionally, false over false, it was a data race between the pool's threads; ThreadSanitizer, profiles/r06_host_asan.txt)
-  bool& on; const bool was;
-  explicit RecPause(bool& o) : on(o), was(o) { if (was) on = false; }
-  ~RecPause() { if (was) on = true; }
-};
-// (the recorder only ever runs on the calling thread's recorder: while it is on nothing is handed to the walk pool)
-#define FDH_REC(name) Rec rec_scope_(cx_->rec_, cx_->rec_first_, cx_->rec_on_ && is_main_, name, &cx_->rec_mark_, &cx_->rec_mark_first_); rec_scope_
-// cull mode 2 (culling while the recorder runs): the draw call just recorded left no record -- it leaves no entry either
-#define FDH_CULLED() do { culled_draws_++; if (cx_->rec_on_ && is_main_) { cx_->rec_.resize(cx_->rec_mark_); cx_->rec_first_ = cx_->rec_mark_first_; } } while (0)
-void Context::record_begin() { rec_on_ = true; rec_first_ = true; rec_ = "["; }
-const char* Context::record_json() {
-  if (!rec_on_) return "[]";
-  rec_ += "\n]";
-  rec_on_ = false;
-  return rec_.c_str();
-}
-void Context::rec_begin_frame(bool clear, const float rgba[4]) { FDH_REC("begin_frame").i(clear ? 1 : 0).fv(rgba, 4); }
-void Context::rec_end_frame() { FDH_REC("end_frame"); }
+// (the log only ever runs on the calling thread's recorder: while it is on nothing is handed to the walk pool)
+#define FDH_REC(name) Rec rec_scope_(log_, name); rec_scope_
+void Recorder::log_begin_frame(bool clear, const float rgba[4]) { FDH_REC("begin_frame").i(clear ? 1 : 0).fv(rgba, 4); }
+void Recorder::log_end_frame() { FDH_REC("end_frame"); }
+void Recorder::culled() { culled_draws_++; if (log_) log_->drop_last(); }
 void Recorder::set_aa(float aa) { { FDH_REC("set_aa_factor").f(aa); } aa_ = aa; }
 void Recorder::set_subpixel_shift(float s) { { FDH_REC("set_text_subpixel_shift").f(s); } subpixel_shift_ = s; }  // setTextSubpixelShift figbackend.nim:663-686
-bool Recorder::subpixel_enabled() const { return cx_->subpixel_enabled_; }
-bool Recorder::subpixel_variants() const { return cx_->subpixel_variants_; }
-bool Recorder::culling() const { return cx_->cull_mode_ == 2 || (cx_->cull_mode_ == 1 && !cx_->rec_on_); }
-bool Recorder::bbox_visible(const BBox& b) const { return b.x1 > b.x0 && std::min<int>(b.y1, cx_->cull_y1_) > std::max<int>(b.y0, cx_->cull_y0_); }
+bool Recorder::bbox_visible(const BBox& b) const { return b.x1 > b.x0 && std::min<int>(b.y1, env_.cull_y1) > std::max<int>(b.y0, env_.cull_y0); }
 
 void Recorder::save_transform() { { FDH_REC("save_transform"); } mats_.push_back(mat_); }
 void Recorder::restore_transform() {
@@ -149,7 +127,7 @@ void Recorder::push_rec(BBox b) {  // (by value: callers pass bounds that live i
   lane_->recs.n++;
   lane_->bins.n++;
   lane_->boxes.n++;
-  if (cx_->pick_frame_) { *lane_->tags.slot() = tag_; lane_->tags.n++; }
+  if (env_.pick_frame) { *lane_->tags.slot() = tag_; lane_->tags.n++; }
 }
 
 // What k_bin_draws scans: 7-bit inclusive bounds in bin units, upper bounds complemented (x0 | y0 << 8 | (127 - x1) << 16 |
@@ -234,14 +212,14 @@ void Recorder::commit_bins(uint32_t idx) {
   br.flags = binrec_flags(r);
   const BBox b = br.box;
   if (op == OP_DRAW && (br.flags & BR_HAS_CORE) && !(br.flags & BR_GENERAL) && b.x0 == r.bx0 && b.y0 == r.by0 && b.x1 == r.bx1 && b.y1 == r.by1) br.flags |= BR_BOX_EXACT;
-  lane_->boxes[idx] = bin_box_of(b, 6 + cx_->binbox_shift_);
+  lane_->boxes[idx] = bin_box_of(b, 6 + env_.binbox_shift);
   lane_->count_add(b);
   bbox_union(sum_.u, b);
   // which compositor build the phase needs (mirrors the path selection of k_composite_tiles)
   const bool atlas_mode = mode == 0u || (mode >= 13u && mode <= 16u);
   if (op != OP_DRAW) sum_.has_masks = true;
   // 4-wide atlas path for axis-aligned atlas quads sampled from level 0
-  const bool atlas4 = atlas_mode && !(om & F_GENERAL) && op == OP_DRAW && !(mode == 0u && r.aux2 > 0.0f && cx_->atlas_.n_levels() >= 2);
+  const bool atlas4 = atlas_mode && !(om & F_GENERAL) && op == OP_DRAW && !(mode == 0u && r.aux2 > 0.0f && env_.atlas->n_levels() >= 2);
   if (atlas4) sum_.has_atlas = true;
   // (a rect mask under a rotated transform -- matY.x != 0 -- is set up one pixel slot at a time; an upright one runs 4-wide)
   else if ((op == OP_DRAW || op == OP_MASK_PUSH) && (om & F_GENERAL) && (om & F_EDGE32) && !atlas_mode && mode < 18u) sum_.has_rot = true;
@@ -265,87 +243,6 @@ void Recorder::commit_bins(uint32_t idx) {
       std::memcpy(&r.col[1], u, sizeof u);
     }
   }
-}
-
-// ------------------------------------------------------------------ publishing (Lane)
-// The mirrors grow with the lane (never shrink, never hold more than the lane); a mirror that had to move is filled again from the
-// lane up to what had been published -- from ordinary memory: pinned memory is not read.
-static void mirror_fit(Lane& L) {
-  auto fit = [](auto& up, const auto& src, size_t published, const uint8_t*& dev) {
-    if (up.cap >= src.cap) return;
-    up.n = 0;  // (nothing to carry over: reserve() would READ the old pinned block)
-    up.reserve(src.cap);
-    if (published) std::memcpy(static_cast<void*>(up.p), static_cast<const void*>(src.p), published * sizeof(*src.p));
-    dev = up.device_view();
-  };
-  fit(L.up_recs, L.recs, L.pub_recs, L.d_recs);
-  fit(L.up_bins, L.bins, L.pub_recs, L.d_bins);
-  fit(L.up_exts, L.exts, L.pub_exts, L.d_exts);
-}
-void Lane::publish(uint32_t first, uint32_t n, uint32_t ext_first, uint32_t n_ext) {
-  if (!device) return;
-  mirror_fit(*this);
-  if (n) {
-    std::memcpy(static_cast<void*>(up_recs.p + first), static_cast<const void*>(recs.p + first), (size_t)n * sizeof(DrawRec));
-    std::memcpy(static_cast<void*>(up_bins.p + first), static_cast<const void*>(bins.p + first), (size_t)n * sizeof(BinRec));
-    pub_recs = std::max(pub_recs, (size_t)first + n);
-  }
-  if (n_ext) {
-    std::memcpy(static_cast<void*>(up_exts.p + ext_first), static_cast<const void*>(exts.p + ext_first), (size_t)n_ext * sizeof(QuadExt));
-    pub_exts = std::max(pub_exts, (size_t)ext_first + n_ext);
-  }
-  if (up_recs.vram) store_fence();  // (write-combined stores into device memory: drained before this thread says the piece is there)
-}
-void Lane::publish_bytes(int array, size_t at, size_t len) {
-  if (!device || !len) return;
-  mirror_fit(*this);
-  uint8_t* dst = array == 0 ? reinterpret_cast<uint8_t*>(up_recs.p) : array == 1 ? reinterpret_cast<uint8_t*>(up_bins.p) : reinterpret_cast<uint8_t*>(up_exts.p);
-  const uint8_t* src = array == 0 ? reinterpret_cast<const uint8_t*>(recs.p) : array == 1 ? reinterpret_cast<const uint8_t*>(bins.p) : reinterpret_cast<const uint8_t*>(exts.p);
-  std::memcpy(dst + at, src + at, len);
-  if (up_recs.vram) store_fence();
-}
-
-// ------------------------------------------------------------------ list stride (Lane)
-void Lane::count_begin(int bins_x, int bins_y) {
-  if (dw != bins_x + 1 || dh != bins_y + 1) {
-    dw = bins_x + 1; dh = bins_y + 1;
-    diff.assign((size_t)dw * dh, 0);
-  } else if (touched) {
-    for (int y = ty0; y <= ty1; y++) std::fill(diff.begin() + (size_t)y * dw + tx0, diff.begin() + (size_t)y * dw + tx1 + 1, 0);
-  }
-  touched = false;
-}
-void Lane::count_add(const BBox& b) {
-  if (bbox_empty(b)) return;
-  constexpr int kBinShift = 6;
-  static_assert((1 << kBinShift) == kBin, "bins are 64 px");
-  const int bx0 = b.x0 >> kBinShift, by0 = b.y0 >> kBinShift, bx1 = ((b.x1 - 1) >> kBinShift) + 1, by1 = ((b.y1 - 1) >> kBinShift) + 1;  // [bx0,bx1) x [by0,by1)
-  if (bx1 >= dw || by1 >= dh) return;  // (bounds are clipped to the frame: cannot happen)
-  int* d = diff.data();
-  d[(size_t)by0 * dw + bx0]++; d[(size_t)by0 * dw + bx1]--; d[(size_t)by1 * dw + bx0]--; d[(size_t)by1 * dw + bx1]++;
-  if (!touched) { tx0 = bx0; ty0 = by0; tx1 = bx1; ty1 = by1; touched = true; }
-  else { tx0 = std::min(tx0, bx0); ty0 = std::min(ty0, by0); tx1 = std::max(tx1, bx1); ty1 = std::max(ty1, by1); }
-}
-// The largest number of records any bin received since the last close, counted exactly from the 2-D difference array
-// (O(records + bins reached)): sizing the lists for "every draw of the phase in every bin" cost 163 MB for the 10 001-draw glyph
-// frame; the exact bound is 2040 bins x a few dozen entries.
-int Lane::count_close() {
-  if (!touched) return 0;
-  int mx = 0;
-  for (int y = ty0; y < ty1; y++) {
-    int run = 0;
-    int* row = diff.data() + (size_t)y * dw;
-    const int* above = y > ty0 ? row - dw : nullptr;
-    for (int x = tx0; x < tx1; x++) {
-      run += row[x];
-      const int cell = run + (above ? above[x] : 0);  // column prefix over the row prefixes
-      row[x] = cell;
-      mx = std::max(mx, cell);
-    }
-  }
-  for (int y = ty0; y <= ty1; y++) std::fill(diff.begin() + (size_t)y * dw + tx0, diff.begin() + (size_t)y * dw + tx1 + 1, 0);
-  touched = false;
-  return mx;
 }
 
 // The part of an axis-aligned SDF quad where the coverage term is saturated (DrawRec::ix0..iy1).  Works in the
@@ -506,7 +403,7 @@ bool Recorder::rect_visible(const float rect[4], float pad) const {
   }
   const float lim = 1.0e6f;
   if (!(minx > -lim && maxx < lim && miny > -lim && maxy < lim)) return pad > 0.0f;  // (such a quad is recorded with empty bounds; an analytic mask has no quad)
-  const float W = (float)cx_->W_, H = (float)cx_->H_;
+  const float W = (float)env_.W, H = (float)env_.H;
   BBox b;
   b.x0 = (int16_t)clampf(minx - pad, 0.0f, W); b.x1 = (int16_t)clampf(maxx + pad, 0.0f, W);
   b.y0 = (int16_t)clampf(miny - pad, 0.0f, H); b.y1 = (int16_t)clampf(maxy + pad, 0.0f, H);
@@ -530,7 +427,7 @@ void Recorder::quad_corners(const float vx[4], const float vy[4], QuadPx& q) con
   q.b = BBox{0, 0, 0, 0};
   q.finite = minx > -lim && maxx < lim && miny > -lim && maxy < lim;
   if (!q.finite) return;
-  const float W = (float)cx_->W_, H = (float)cx_->H_;
+  const float W = (float)env_.W, H = (float)env_.H;
   q.b.x0 = (int16_t)clampf(minx, 0.0f, W); q.b.x1 = (int16_t)clampf(maxx, 0.0f, W);
   q.b.y0 = (int16_t)clampf(miny, 0.0f, H); q.b.y1 = (int16_t)clampf(maxy, 0.0f, H);
 }
@@ -554,10 +451,10 @@ bool Recorder::emit_corners(DrawRec& r, const QuadPx& q, bool count_fragments) {
   bool params_finite = true;
   for (const float v : fields) params_finite = params_finite && std::isfinite(v);
   if (!q.finite || !params_finite) {
-    if (cullable) { FDH_CULLED(); return false; }
+    if (cullable) { culled(); return false; }
     r.bx0 = r.by0 = r.bx1 = r.by1 = 0; push_rec(b); return true;
   }
-  if (cullable && !bbox_visible(b)) { FDH_CULLED(); return false; }
+  if (cullable && !bbox_visible(b)) { culled(); return false; }
   r.bx0 = b.x0; r.by0 = b.y0; r.bx1 = b.x1; r.by1 = b.y1;
   const bool aligned = px[3] == px[0] && px[2] == px[1] && py[3] == py[2] && py[0] == py[1] && px[1] > px[0] && py[0] > py[3];
   // A bezier stroke (modes 18 - 20) always takes the two-triangle form, upright or not: its distance is a closed-form cubic that turns a
@@ -584,7 +481,7 @@ bool Recorder::emit_corners(DrawRec& r, const QuadPx& q, bool count_fragments) {
     const float vu[4] = {uax, utx, utx, uax}, vv[4] = {uty, uty, uay, uay};
     // F_EDGE32 (fdh_types.h): may the compositor evaluate the edge functions in 32-bit arithmetic at every pixel of the frame's strips?
     bool edge32 = true;
-    const long long xm = 2LL * cx_->W_ + 129, ym = 2LL * cx_->H_ + 129;  // (every pixel of every 64 x 64 bin that overlaps the frame)
+    const long long xm = 2LL * env_.W + 129, ym = 2LL * env_.H + 129;  // (every pixel of every 64 x 64 bin that overlaps the frame)
     for (int t = 0; t < 2; t++) {
       long long X[3], Y[3];
       for (int k = 0; k < 3; k++) { X[k] = 2 * (long long)px[TRI[t][k]]; Y[k] = 2 * (long long)py[TRI[t][k]]; }
@@ -622,7 +519,7 @@ bool Recorder::emit_corners(DrawRec& r, const QuadPx& q, bool count_fragments) {
         const double dvdx = (dv1 * e2y - dv2 * e1y) / det, dvdy = (dv2 * e1x - dv1 * e2x) / det;
         q.fw_u[t] = (float)(std::fabs(dudx) + std::fabs(dudy));
         q.fw_v[t] = (float)(std::fabs(dvdx) + std::fabs(dvdy));
-        const double S = (double)cx_->atlas_.size();
+        const double S = (double)env_.atlas->size();
         const double rho = std::max(std::sqrt(dudx * dudx + dvdx * dvdx), std::sqrt(dudy * dudy + dvdy * dvdy)) * S;
         q.lod[t] = rho > 0.0 ? (float)std::log2(rho) : 0.0f;
       } else {
@@ -758,7 +655,7 @@ void Recorder::draw_rounded_rect_sdf(const float rect[4], const FdhColor colors[
                                     float factor, float spread, const float shape[2], int fill_mode, FdhColor mid, FdhColor stop,
                                     float mid_pos) {
   { FDH_REC("draw_rounded_rect_sdf").fv(rect, 4).cols(colors).fv(rx, 4).fv(ry, 4).i(mode).f(factor).f(spread).fv(shape, 2).i(fill_mode).col(mid).col(stop).f(mid_pos); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   if (!(rect[2] > 0.0f) || !(rect[3] > 0.0f)) return;  // (a NaN extent draws nothing)
   if (mode >= FDH_SDF_BEZIER_STROKE_AA) throw Error(FDH_ERR_INVALID, "bezier stroke modes go through drawQuadraticBezierSdf");
   QuadPx q;
@@ -768,7 +665,7 @@ void Recorder::draw_rounded_rect_sdf(const float rect[4], const FdhColor colors[
     quad_corners(vx, vy, q);
   }
   // (before the record is built: most of a long table is below the window)
-  if (culling() && (!q.finite || !bbox_visible(q.b))) { FDH_CULLED(); return; }
+  if (culling() && (!q.finite || !bbox_visible(q.b))) { culled(); return; }
   DrawRec& r = next_rec();
   fill_sdf_rec(r, rect, colors, rx, ry, mode, factor, spread, shape, fill_mode, mid, stop, mid_pos, aa_);
   if (mode == FDH_SDF_BACKDROP_BLUR) r.op_mode |= F_SELF_BACKDROP;  // a bare mode-17 call has no snapshot of its own
@@ -815,7 +712,7 @@ void Recorder::draw_rounded_rect_fill(const float rect[4], const FdhFill& fill, 
 
 // An image's entry and its uv rect: entries = rect / atlasSize.  e == nullptr: "missing image in context", warn + no-op (glcontext.nim:1310-1315)
 Recorder::EntryUV Recorder::entry_uv(int64_t key) const {
-  EntryUV u{cx_->atlas_.find(key), (float)cx_->atlas_.size(), 0.0f, 0.0f, 0.0f, 0.0f};
+  EntryUV u{env_.atlas->find(key), (float)env_.atlas->size(), 0.0f, 0.0f, 0.0f, 0.0f};
   if (u.e) { u.x = (float)u.e->x / u.S; u.y = (float)u.e->y / u.S; u.w = (float)u.e->w / u.S; u.h = (float)u.e->h / u.S; }
   return u;
 }
@@ -837,7 +734,7 @@ Recorder::PixelQuad Recorder::axis_lod(DrawRec& r, float S, float x0, float y0, 
 // drawImage / drawUvRect: glcontext.nim:1236-1302, 1350-1367
 void Recorder::draw_image(int64_t key, const float pos[2], const FdhColor colors[4], const float size[2], bool flip_y) {
   { FDH_REC("draw_image").i(key).fv(pos, 2).cols(colors).fv(size, 2).i(flip_y ? 1 : 0); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   const EntryUV u = entry_uv(key);
   if (!u.e) return;
   const AtlasEntry& e = *u.e;
@@ -851,7 +748,7 @@ void Recorder::draw_image(int64_t key, const float pos[2], const FdhColor colors
   for (int i = 0; i < 4; i++) r.col[i] = pack_color(colors[i]);
   if (r.col[0] == r.col[1] && r.col[1] == r.col[2] && r.col[2] == r.col[3]) r.op_mode |= F_SOLID;
   r.aa = aa_;
-  const bool subpixel_enabled_ = cx_->subpixel_enabled_;
+  const bool subpixel_enabled_ = env_.subpixel_enabled;
   if (subpixel_enabled_) {
     r.op_mode |= F_SUBPIXEL;
     r.aux = std::max(0.0f, std::min(subpixel_shift_, 0.999f));  // activeSubpixelShift glcontext.nim:819-822
@@ -877,7 +774,7 @@ void Recorder::draw_image(int64_t key, const float pos[2], const FdhColor colors
 // drawImageAdj: glcontext.nim:1369-1381 -- drawImage with the uv rect pulled in by two texels on every side (2 / atlasSize)
 void Recorder::draw_image_adj(int64_t key, const float pos[2], FdhColor color, const float size[2]) {
   { FDH_REC("draw_image_adj").i(key).fv(pos, 2).col(color).fv(size, 2); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   const EntryUV u = entry_uv(key);
   if (!u.e) return;
   const float S = u.S, ex = u.x, ey = u.y, ew = u.w, eh = u.h, adj = 2.0f / S;
@@ -886,7 +783,7 @@ void Recorder::draw_image_adj(int64_t key, const float pos[2], FdhColor color, c
   r.r[0] = ex + adj; r.r[1] = ey + adj; r.r[2] = ex + ew - adj; r.r[3] = ey + eh - adj;
   for (int i = 0; i < 4; i++) r.col[i] = pack_color(color);
   r.aa = aa_;
-  if (cx_->subpixel_enabled_) {
+  if (env_.subpixel_enabled) {
     r.op_mode |= F_SUBPIXEL;
     r.aux = std::max(0.0f, std::min(subpixel_shift_, 0.999f));
   }
@@ -899,7 +796,7 @@ void Recorder::draw_image_adj(int64_t key, const float pos[2], FdhColor color, c
 void Recorder::draw_msdf(int64_t key, const float pos[2], FdhColor color, const float size[2], float px_range, float sd_threshold,
                         float stroke_weight, bool mtsdf, bool flip_y) {
   { FDH_REC("draw_msdf").i(key).fv(pos, 2).col(color).fv(size, 2).f(px_range).f(sd_threshold).f(stroke_weight).i(mtsdf ? 1 : 0).i(flip_y ? 1 : 0); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   const EntryUV u = entry_uv(key);
   if (!u.e) return;
   const AtlasEntry& e = *u.e;
@@ -935,7 +832,7 @@ void Recorder::draw_msdf(int64_t key, const float pos[2], FdhColor color, const 
 void Recorder::draw_quadratic_bezier_sdf(const float rect[4], const FdhFill& fill, const float p0[2], const float p1[2],
                                         const float p2[2], float stroke_weight, int cap) {
   { FDH_REC("draw_quadratic_bezier_sdf").fv(rect, 4).fill(fill).fv(p0, 2).fv(p1, 2).fv(p2, 2).f(stroke_weight).i(cap); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   if (!(rect[2] > 0.0f) || !(rect[3] > 0.0f) || !(stroke_weight > 0.0f)) return;
   DrawRec& r = next_rec();
   r.p0 = rect[2] * 0.5f; r.p1 = rect[3] * 0.5f; r.p2 = p0[0]; r.p3 = p0[1];  // params = (quadHalf, p0)
@@ -965,11 +862,7 @@ void Recorder::draw_quadratic_bezier_sdf(const float rect[4], const FdhFill& fil
 // atlas space on first use exactly like the reference's -- on the calling thread: a pool thread that finds it missing hands its
 // sibling group back (SerialOnly).
 void Recorder::rect_entry() {
-  if (cx_->atlas_.has(kRectImageKey)) return;
-  if (!is_main_) throw SerialOnly{};
-  uint8_t white[4 * 4 * 4];
-  std::memset(white, 255, sizeof white);
-  cx_->put_image(kRectImageKey, 4, 4, white, nullptr);
+  if (!env_.atlas->has(kRectImageKey)) make_rect_image();
 }
 void Recorder::white_texel_uv(DrawRec& r) const {
   const EntryUV u = entry_uv(kRectImageKey);
@@ -979,7 +872,7 @@ void Recorder::white_texel_uv(DrawRec& r) const {
 // drawFilledQuad: glcontext.nim:963-982 (+ drawQuad :908-961): an arbitrary quad textured with one white texel
 void Recorder::draw_filled_quad(const float verts[8], const FdhColor colors[4]) {
   { FDH_REC("draw_filled_quad").fv(verts, 8).cols(colors); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   rect_entry();  // (may upload the image: before the record slot is taken)
   DrawRec& r = next_rec();
   r.op_mode = FDH_SDF_ATLAS;
@@ -993,7 +886,7 @@ void Recorder::draw_filled_quad(const float verts[8], const FdhColor colors[4]) 
 // drawRect: glcontext.nim:1410-1426
 void Recorder::draw_rect(const float rect[4], FdhColor color) {
   { FDH_REC("draw_rect").fv(rect, 4).col(color); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   rect_entry();
   DrawRec& r = next_rec();
   r.op_mode = FDH_SDF_ATLAS | F_SOLID;
@@ -1006,7 +899,7 @@ void Recorder::draw_rect(const float rect[4], FdhColor color) {
 // ------------------------------------------------------------------ masks (glcontext.nim:1873-1949)
 void Recorder::begin_mask(const float rect[4], const float rx[4], const float ry[4]) {
   { FDH_REC("begin_mask").fv(rect, 4).fv(rx, 4).fv(ry, 4); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   if (mask_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginMask has already been called.");
   mask_begun_ = true;
   mask_depth_++;  // (beyond kMaskDepth levels the compositor's stack spills to a global plane: Context::size_bin_buffers)
@@ -1049,7 +942,7 @@ void Recorder::pop_mask() {
 // makeRectMask glcontext.nim:831-850; beginRectMask :1932-1943
 void Recorder::begin_rect_mask(const float rect[4], const float rx[4], const float ry[4]) {
   { FDH_REC("begin_rect_mask").fv(rect, 4).fv(rx, 4).fv(ry, 4); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   if (mask_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginRectMask cannot start inside a mask.");
   if (rect_masks_.empty() && outer_rect_masks_ == 0 && rect[2] > 0.0f && rect[3] > 0.0f) {
     const float hx = rect[2] * 0.5f, hy = rect[3] * 0.5f;
@@ -1067,7 +960,7 @@ void Recorder::begin_rect_mask(const float rect[4], const float rx[4], const flo
     push_rec(BBox{0, 0, 0, 0});
     rect_masks_.push_back(RectMaskEntry{1});
   } else {
-    { const RecPause quiet(cx_->rec_on_);  // the fallback's own begin/end are this backend's business, not the caller's
+    { const CallLog::Pause quiet(log_);  // the fallback's own begin/end are this backend's business, not the caller's
       begin_mask(rect, rx, ry);
       end_mask(); }
     rect_masks_.push_back(RectMaskEntry{2});
@@ -1078,7 +971,7 @@ void Recorder::pop_rect_mask() {
   if (rect_masks_.empty()) throw Error(FDH_ERR_INVALID, "No rect mask has been pushed.");
   const RectMaskEntry e = rect_masks_.back();
   rect_masks_.pop_back();
-  if (e.kind == 2) { const RecPause quiet(cx_->rec_on_); pop_mask(); return; }
+  if (e.kind == 2) { const CallLog::Pause quiet(log_); pop_mask(); return; }
   const uint32_t begin_idx = open_ops_.back();
   open_ops_.pop_back();
   commit_bins(begin_idx);
@@ -1120,7 +1013,7 @@ BlurTaps make_taps(float blur_radius) {
 
 void Recorder::draw_backdrop_blur(const float rect[4], const float rx[4], const float ry[4], float blur_radius) {
   { FDH_REC("draw_backdrop_blur").fv(rect, 4).fv(rx, 4).fv(ry, 4).f(blur_radius); }
-  if (!cx_->frame_begun_) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
+  if (!env_.frame_begun) throw Error(FDH_ERR_INVALID, "ctx.beginFrame has not been called.");
   if (!(blur_radius > 0.0f) || !(rect[2] > 0.0f) || !(rect[3] > 0.0f)) return;  // (written so that a NaN draws nothing)
   const FdhColor white{255, 255, 255, 255}, zero{0, 0, 0, 0};
   const FdhColor cols[4] = {white, white, white, white};
@@ -1135,14 +1028,17 @@ void Recorder::draw_backdrop_blur(const float rect[4], const float rx[4], const 
     if (emit_quad(r, rect[0], rect[1], rect[0] + rect[2], rect[1] + rect[3], true)) commit_bins((uint32_t)lane_->recs.n - 1);
     return;
   }
-  if (culling() && !rect_visible(rect, 0.0f)) { FDH_CULLED(); return; }  // a blurred backdrop nobody sees: no snapshot, no phase
-  if (!is_main_) throw SerialOnly{};  // phases are the calling thread's
-  Context& C = *cx_;
-  // A blurred snapshot is a barrier in painter's order: close the phase, blur, continue in a new phase.  The open clips end
-  // with the phase (their bounds are final there) and are re-established, as new records, at the start of the next.
+  if (culling() && !rect_visible(rect, 0.0f)) { culled(); return; }  // a blurred backdrop nobody sees: no snapshot, no phase
+  blur_node(quad, rect, blur_radius);
+}
+// A blurred snapshot is a barrier in painter's order: close the phase, blur, continue in a new phase (Context::blur_node).  The open
+// clips end with the phase (their bounds are final there) and are re-established, as new records, at the start of the next.
+std::vector<DrawRec> Recorder::close_open_clips() {
   std::vector<DrawRec> reopen;
   for (auto idx : open_ops_) { reopen.push_back(lane_->recs[idx]); commit_bins(idx); }
-  C.split_phase((int)C.blurs_.size());
+  return reopen;
+}
+uint32_t Recorder::reopen_clips_and_emit(const std::vector<DrawRec>& reopen, const DrawRec& quad, const float rect[4]) {
   depth_now_ = 0;
   for (size_t i = 0; i < reopen.size(); i++) {
     open_ops_[i] = (uint32_t)lane_->recs.n;
@@ -1151,102 +1047,60 @@ void Recorder::draw_backdrop_blur(const float rect[4], const float rx[4], const 
     push_rec(BBox{0, 0, 0, 0});
     if (((nr.op_mode >> 12) & 15u) == OP_MASK_PUSH) { depth_now_++; sum_.deepest = std::max(sum_.deepest, depth_now_); }
   }
-  // no clip state to carry: the V pass can composite the quad itself -- unless the region is small enough for the one-kernel
-  // route, whose snapshot goes to the backdrop surface and is sampled by the phase's compositor launch (k_blur_small)
   DrawRec& r = next_rec();
   r = quad;
   if (!emit_quad(r, rect[0], rect[1], rect[0] + rect[2], rect[1] + rect[3], true)) throw Error(FDH_ERR_INVALID, "drawBackdropBlur: rect_visible and emit_quad disagree");
-  const uint32_t idx = (uint32_t)lane_->recs.n - 1;
-  const BBox fb = lane_->bins[idx].box;
-  BlurJob job;
-  job.taps = make_taps(blur_radius);
-  const bool fuse = open_ops_.empty() && !(C.latency_routes_ && blur_one_kernel_ok(fb.x1 - fb.x0, fb.y1 - fb.y0, job.taps.reach));
-  job.fuse_draw = -1;
-  if (fuse) {
-    job.fuse_draw = (int)C.global_index(idx);
-    lane_->bins[idx].box = BBox{0, 0, 0, 0};  // never binned: k_blur_v blends it
-  }
-  commit_bins(idx);
-  job.radius = blur_radius;
-  job.x0 = fb.x0; job.y0 = fb.y0; job.x1 = fb.x1; job.y1 = fb.y1;
-  C.blurs_.push_back(job);
+  return (uint32_t)lane_->recs.n - 1;
 }
 
-// ------------------------------------------------------------------ the frame: pieces and phases (calling thread)
-Lane& Context::ensure_lane(int i) {
-  auto& v = lanes_[(size_t)staging_i_];
-  while ((int)v.size() <= i) {
-    v.emplace_back(new Lane());
-    v.back()->set_pinned(!host_only_, device_);
-  }
-  return *v[(size_t)i];
-}
-uint32_t Context::global_count() const { return piece_open_ ? (uint32_t)lanes_[(size_t)staging_i_][0]->recs.n + g0_delta_ : n_total_; }
-void Context::open_piece() {
-  Lane& L = lane(0);
-  Piece p;
-  p.lane = 0; p.first = (uint32_t)L.recs.n; p.ext_first = (uint32_t)L.exts.n;
-  pieces_.push_back(p);
-  piece_open_ = true;
-  g0_delta_ = n_total_ - p.first;
-  phase_floor_ = (int)p.first;  // (LE_SHARE looks one record back in the lane: never across a piece boundary)
-}
-void Context::close_piece() {
-  if (!piece_open_) return;
-  Lane& L = lane(0);
-  Piece& p = pieces_.back();
-  p.n = (uint32_t)L.recs.n - p.first;
-  p.n_ext = (uint32_t)L.exts.n - p.ext_first;
-  n_total_ += p.n;
-  n_ext_total_ += p.n_ext;
-  piece_open_ = false;
-  if (p.n == 0) pieces_.pop_back();
-}
-void Context::add_sum(const PhaseSum& s, int depth_base) {
-  phases_.back().merge_flags(s);
-  bbox_union(phase_u_, s.u);
-  deepest_clip_ = std::max(deepest_clip_, depth_base + s.deepest);
-  if (phases_.size() == 1) {  // the phase-0 composite launch's work units
-    for (int k = 0; k < 4; k++) frag_mode_[k] += s.frag_mode[k];
-    frag_ellip_ += s.frag_ellip;
-    frag_other_ += s.frag_other;
-  }
-}
-// a pool thread's chunk of a sibling group takes its place in painter's order (the caller closed lane 0's piece before the group)
-void Context::add_piece(const Piece& p, const PhaseSum& s, const BBox& outer_union, int64_t fragments, int64_t culled) {
-  if (p.n) {
-    pieces_.push_back(p);
-    n_total_ += p.n;
-    n_ext_total_ += p.n_ext;
-  }
-  Lane& L = lane(0);
-  for (auto idx : open_ops_) bbox_union(L.bins[idx].box, outer_union);  // the clips open around the group reach what it drew
-  add_sum(s, depth_now_);
-  fragments_ += fragments;
-  culled_draws_ += culled;
-}
-// the phase ends here (a blur node, or the frame's end): its summary and its share of the list stride
-void Context::close_phase() {
-  add_sum(sum_, 0);
+// ------------------------------------------------------------------ a recorder's uses
+void Recorder::reset(Lane& lane) {
+  lane_ = &lane;
+  mask_begun_ = false; mask_depth_ = 0;
+  rect_masks_.clear(); outer_rect_masks_ = 0;
+  open_ops_.clear(); outer_open_ = false; outer_union_ = BBox{0, 0, 0, 0};
+  depth_now_ = 0;
   sum_ = PhaseSum{};
-  Phase& ph = phases_.back();
-  constexpr int kBinShift = 6;
-  const BBox u = phase_u_;
-  ph.bin_x0 = u.x0 >> kBinShift; ph.bin_y0 = u.y0 >> kBinShift;
-  ph.bin_x1 = bbox_empty(u) ? ph.bin_x0 : (u.x1 + kBin - 1) >> kBinShift;
-  ph.bin_y1 = bbox_empty(u) ? ph.bin_y0 : (u.y1 + kBin - 1) >> kBinShift;
-  phase_u_ = BBox{0, 0, 0, 0};
-  stride_max_ = std::max(stride_max_, lane(0).count_close() + phase_extra_);
-  phase_extra_ = 0;
-  ph.count = (int)(global_count() - (uint32_t)ph.first);
+  fragments_ = 0; culled_draws_ = 0;
+  phase_floor_ = (int)lane.recs.n;
+  tag_ = PickTag{-1, -1};
 }
-void Context::split_phase(int blur) {
-  close_phase();
-  Phase next;
-  next.first = (int)global_count();
-  next.blur = blur;
-  phases_.push_back(next);
-  phase_floor_ = (int)lane(0).recs.n;
+void Recorder::adopt(const Recorder& base, Lane& lane, int outer_rect_masks, bool outer_open) {
+  reset(lane);
+  mat_ = base.mat_; mats_.clear();
+  aa_ = base.aa_; subpixel_shift_ = base.subpixel_shift_;
+  outer_rect_masks_ = outer_rect_masks;
+  outer_open_ = outer_open;
+  tag_ = base.tag_;
+}
+int Recorder::absorb(const ChunkResult& c) {
+  for (auto idx : open_ops_) bbox_union(lane_->bins[idx].box, c.outer_union);
+  fragments_ += c.fragments;
+  culled_draws_ += c.culled;
+  return depth_now_;
+}
+// A retained root's cached records take their place in the lane (fdh_scene_render): a memcpy per array, the extension indices
+// moved to where the extensions landed, the list-stride count and the phase summary brought up to date.
+void Recorder::splice(const RetainedRoot& C) {
+  Lane& L = *lane_;
+  const uint32_t r0 = (uint32_t)L.recs.n, e0 = (uint32_t)L.exts.n;
+  L.recs.append(C.recs.data(), C.recs.size());
+  L.bins.append(C.bins.data(), C.bins.size());
+  L.exts.append(C.exts.data(), C.exts.size());
+  if (env_.pick_frame) L.tags.append(C.tags.data(), C.tags.size());  // (scene_render splices only tagged roots into a picking frame)
+  if (!C.exts.empty())
+    for (size_t i = r0; i < L.recs.n; i++) if (L.recs[i].op_mode & F_GENERAL) L.recs[i].ext += e0;
+  L.boxes.reserve(L.bins.n);
+  for (size_t i = r0; i < L.bins.n; i++) { L.count_add(L.bins[i].box); L.boxes[i] = bin_box_of(L.bins[i].box, 6 + env_.binbox_shift); }
+  L.boxes.n = L.bins.n;
+  sum_.merge(C.sum, depth_now_);
+  fragments_ += C.fragments;
+  if (!C.recs.empty()) link_share(r0);  // the record in front of the splice may share its distance field with the first one here
+}
+Recorder::RootSince Recorder::since(const RootMark& m) const {
+  RootSince s{fragments_ - m.fragments, sum_};
+  s.sum.deepest = std::max(0, sum_.deepest - m.depth);
+  return s;
 }
 
 }  // namespace fdh
