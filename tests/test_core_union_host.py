@@ -127,7 +127,7 @@ def saturated(rec, x0, y0, x1, y1):
     u = (xs + f32(0.5) - f32(rec.ox)) / f32(rec.w_px)
     v = (ys + f32(0.5) - f32(rec.oy)) / f32(rec.h_px)
     px, py = (u - f32(0.5)) * f32(2) * rec.p0, (v - f32(0.5)) * f32(2) * rec.p1
-    aa = f32(AA)
+    aa = f32(rec.aa)  # (AA in this file's sweep; tests/test_hostile_shapes_host.py sweeps the factor too)
     sd = (lambda qx, qy, bx, by: sd_elliptical_rounded_box(qx, qy, bx, by, rec.r)) if rec.ellip else (lambda qx, qy, bx, by: sd_rounded_box(qx, qy, bx, by, rec.r))
     clamp01 = lambda t: np.minimum(np.maximum(t, f32(0)), f32(1))
     if rec.mode == 9:
@@ -146,6 +146,9 @@ def saturated(rec, x0, y0, x1, y1):
         h = rec.f0 * f32(0.5)
         s = np.abs(dist + h) - h
         return int((f32(1) - clamp01(aa * s + f32(0.5)) != 0).sum())
+    if rec.mode == 11:  # (the hard-edged stroke: alpha exactly 0 inside)
+        h = rec.f0 * f32(0.5)
+        return int((np.abs(dist + h) - h < 0).sum())
     return int((f32(1) - clamp01(aa * dist + f32(0.5)) != f32(1)).sum())
 
 

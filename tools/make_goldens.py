@@ -68,6 +68,41 @@ def big_blur_goldens():
     return out
 
 
+def hostile_goldens():
+    """tests/hostile_cases.py: the direct form of every frame through the reference's shaders (ss_hostile_<name>.png), with the measured
+    oracle-vs-golden agreement and the coordinates of every pixel where the oracle is more than 1 LSB from the golden (the only pixels
+    the GPU test may leave out of its 2-LSB bar).  Node-level frames go through the stream recorded from the library's own front-end,
+    checked equal to the oracle's, as in main()."""
+    import hostile_cases as HC
+
+    out = {}
+    w, h = HC.W, HC.H
+    for name in HC.FRAMES:
+        o = O.Oracle(threads=8)
+        if HC.is_node_frame(name):
+            o.record_begin()
+            HC.render(o, name)
+            rec = HipContext(record_only=True)
+            rec.record_begin()
+            HC.render(rec, name)
+            calls = rec.record_calls()
+            rec.close()
+            _same(o.record_calls(), calls)
+        else:
+            HC.render(o, name)
+            calls = HC.calls(name)
+        img = o.read_pixels()
+        ss = R.replay(calls, w, h)
+        opaque = ss[..., :3] if (ss[..., 3] == 255).all() else ss  # (as the blur goldens: conftest.load_png reads RGB back as RGBA)
+        Image.fromarray(opaque).save(os.path.join(GOLD, f"ss_hostile_{name}.png"), optimize=True)
+        ys, xs = np.nonzero(np.abs(img.astype(int) - ss.astype(int)).max(axis=2) > 1)
+        out[f"hostile_{name}"] = {"width": w, "height": h, "n_calls": len(calls), "oracle_vs_swiftshader": stats(img, ss),
+                                  "oracle_gt1": [[int(x), int(y)] for x, y in zip(xs, ys)]}
+        assert len(xs) <= HC.MAX_GOLDEN_OUTLIERS, (name, "thin the frame: the oracle itself is > 1 LSB from the shaders on", len(xs), "pixels")
+        print("hostile", name, out[f"hostile_{name}"])
+    return out
+
+
 def main():
     assert R.available(), "needs /root/reference and SwiftShader"
     os.makedirs(GOLD, exist_ok=True)
@@ -138,15 +173,17 @@ def main():
         manifest[f"blur_r{radius:g}"] = {"oracle_vs_swiftshader": stats(O.blur_image(src, radius), out)}
         print("blur", radius, manifest[f"blur_r{radius:g}"])
     manifest.update(big_blur_goldens())
+    manifest.update(hostile_goldens())
     with open(os.path.join(GOLD, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] == ["big_blur"]:  # only the hostile-content blur frames (the manifest keeps its other entries)
+    if sys.argv[1:] in (["big_blur"], ["hostile"]):  # only the hostile blur frames / the hostile shapes (the manifest keeps its other entries)
+        assert R.available(), "needs /root/reference and SwiftShader"
         with open(os.path.join(GOLD, "manifest.json")) as f:
             m = json.load(f)
-        m.update(big_blur_goldens())
+        m.update(big_blur_goldens() if sys.argv[1] == "big_blur" else hostile_goldens())
         with open(os.path.join(GOLD, "manifest.json"), "w") as f:
             json.dump(m, f, indent=1, sort_keys=True)
     else:
