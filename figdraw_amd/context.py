@@ -195,6 +195,12 @@ def load():
     if hasattr(L, "fdh_set_damage_exact"):
         L.fdh_set_damage_exact.argtypes = [vp, C.c_int]
         L.fdh_damage_exact_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    # moved damage readback (include_readback/figdraw_hip_moves.h; likewise)
+    if hasattr(L, "fdh_read_damage_moved"):
+        L.fdh_read_damage_moved.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.fdh_decode_damage_moved.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int64]
+        L.fdh_find_damage_moves.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int)]
     # picking (include/figdraw_hip_pick.h; likewise absent from older libraries)
     if hasattr(L, "fdh_set_pick"):
         L.fdh_set_pick.argtypes = [vp, C.c_int]
@@ -791,6 +797,49 @@ class HipContext:
         a, b, f = C.c_int(), C.c_int(), C.c_int()
         self._ck(self.L.fdh_damage_exact_stats(self.h, C.byref(a), C.byref(b), C.byref(f)))
         return a.value, b.value, bool(f.value)
+
+    # ---- moved damage readback (include_readback/figdraw_hip_moves.h)
+    TILE_COPY = 4                                     # FDH_TILE_COPY
+    DAMAGE_MOVES_MAX, DAMAGE_SHIFT_MAX = 8, 256       # FDH_DAMAGE_MOVES_MAX, FDH_DAMAGE_SHIFT_MAX
+    DAMAGE_MOVE = np.dtype([("dx", "<i2"), ("dy", "<i2")])  # FdhDamageMove
+
+    def read_damage_moved(self, moves=()):
+        """read_damage_coded in stream version 2, with exact damage readback on: a changed tile that equals the rectangle at (dx, dy) from it
+        of the image the receiver holds, for the first such (dx, dy) of `moves` (at most 8 pairs), comes as a COPY entry without payload
+        -> (tiles, payload, full, n_copied).  Decode with decode_damage_moved."""
+        mv = np.ascontiguousarray(np.asarray(moves, dtype=np.int16).reshape(-1, 2))
+        t, p = C.c_void_p(), C.c_void_p()
+        n, full, copied, nbytes = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+        self._ck(self.L.fdh_read_damage_moved(self.h, mv.ctypes.data if len(mv) else None, len(mv), C.byref(t), C.byref(p), C.byref(n), C.byref(nbytes),
+                                              None, None, C.byref(full), C.byref(copied)))
+        if n.value == 0:
+            return np.zeros(0, self.CODED_TILE), b"", bool(full.value), 0
+        tiles = np.frombuffer(C.string_at(t.value, n.value * self.CODED_TILE.itemsize), self.CODED_TILE).copy()
+        return tiles, C.string_at(p.value, nbytes.value) if nbytes.value else b"", bool(full.value), copied.value
+
+    @staticmethod
+    def decode_damage_moved(image: np.ndarray, tiles, payload) -> None:
+        """host only: decode_damage for stream version 2 -- a COPY tile takes its pixels from `image` as it was before the call.  A stream
+        that does not validate raises FigdrawHipError and leaves the image as it was."""
+        L = load()
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 4 or image.strides[2] != 1 or image.strides[1] != 4:
+            raise ValueError("decode_damage_moved: the image must be uint8 (H, W, 4) with contiguous rows")
+        if not image.flags.writeable:
+            raise ValueError("decode_damage_moved: the image is read-only")
+        t = np.ascontiguousarray(np.asarray(tiles, dtype=HipContext.CODED_TILE).reshape(-1))
+        blob = np.frombuffer(bytes(payload), np.uint8) if not isinstance(payload, np.ndarray) else np.ascontiguousarray(payload, np.uint8).reshape(-1)
+        rc = L.fdh_decode_damage_moved(image.ctypes.data, image.strides[0], image.shape[1], image.shape[0], t.ctypes.data if len(t) else None, len(t),
+                                       blob.ctypes.data if blob.size else None, blob.size)
+        if rc != 0:
+            raise FigdrawHipError(rc, L.fdh_last_error().decode())
+
+    def find_damage_moves(self, max_shift: int = 64, cap: int = 8):
+        """the mover: the scroll vectors the pending bins of the last frame vote for against the image the receiver holds -> (moves int16
+        (n, 2): dx, dy; votes int32 (n,)), best first.  Changes nothing; what it proposes, read_damage_moved confirms pixel for pixel."""
+        mv, votes, n = np.zeros((max(cap, 0), 2), np.int16), np.zeros(max(cap, 0), np.int32), C.c_int()
+        self._ck(self.L.fdh_find_damage_moves(self.h, int(max_shift), mv.ctypes.data if cap > 0 else None, votes.ctypes.data if cap > 0 else None, int(cap),
+                                              C.byref(n)))
+        return mv[:n.value].copy(), votes[:n.value].copy()
 
     # ---- picking (include/figdraw_hip_pick.h)
     PICK_SHADOWS = 1  # FDH_PICK_SHADOWS

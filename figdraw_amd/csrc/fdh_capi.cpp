@@ -9,6 +9,7 @@
 #include "../../include/figdraw_hip_readback.h"
 #include "../../include/figdraw_hip_stream.h"
 #include "../../include/figdraw_hip_exact.h"
+#include "../../include_readback/figdraw_hip_moves.h"
 #include "../../include_glyphs/figdraw_hip_glyphs.h"
 #include "../../include_glyphs/figdraw_hip_coverage.h"
 #include "../../include_glyphs/figdraw_hip_cubic.h"
@@ -384,6 +385,17 @@ int64_t fdh_coded_damage_bound(int w, int h) { return fdh::coded_damage_bound(w,
 int fdh_set_damage_exact(FdhContext* c, int on) { return guard([&] { C(c)->set_damage_exact(on != 0); }); }
 int fdh_damage_exact_stats(FdhContext* c, int* n_pending, int* n_changed, int* fresh) {
   return guard([&] { C(c)->damage_exact_stats(n_pending, n_changed, fresh); });
+}
+int fdh_read_damage_moved(FdhContext* c, const FdhDamageMove* moves, int n_moves, const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles,
+                          int64_t* payload_bytes, int* frame_w, int* frame_h, int* full, int* n_copied) {
+  return guard([&] { C(c)->read_damage_moved(moves, n_moves, tiles, payload, n_tiles, payload_bytes, frame_w, frame_h, full, n_copied); });
+}
+int fdh_decode_damage_moved(uint8_t* image_rgba8, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload,
+                            int64_t payload_bytes) {
+  return guard([&] { fdh::decode_damage_moved(image_rgba8, pitch_bytes, w, h, tiles, n_tiles, payload, payload_bytes); });
+}
+int fdh_find_damage_moves(FdhContext* c, int max_shift, FdhDamageMove* out_moves, int* out_votes, int cap, int* n_out) {
+  return guard([&] { C(c)->find_damage_moves(max_shift, out_moves, out_votes, cap, n_out); });
 }
 int fdh_set_cull(FdhContext* c, int mode) { return guard([&] { C(c)->set_cull(mode); }); }
 int fdh_debug_host_times(FdhContext* c, int64_t out_ns[12]) {

@@ -765,6 +765,13 @@ void Context::damage_exact_stats(int* n_pending, int* n_changed, int* fresh) {
   drain();
   readback_.exact_stats(n_pending, n_changed, fresh);
 }
+void Context::read_damage_moved(const FdhDamageMove* moves, int n_moves, const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles,
+                                int64_t* payload_bytes, int* frame_w, int* frame_h, int* full, int* n_copied) {
+  readback_.read_moved(read_frame("fdh_read_damage_moved"), moves, n_moves, tiles, payload, n_tiles, payload_bytes, frame_w, frame_h, full, n_copied);
+}
+void Context::find_damage_moves(int max_shift, FdhDamageMove* out_moves, int* out_votes, int cap, int* n_out) {
+  readback_.find_moves(read_frame("fdh_find_damage_moves"), max_shift, out_moves, out_votes, cap, n_out);
+}
 
 void Context::frame_device_ptr(void** p, int* w, int* h, int64_t* pitch_bytes) {
   need_device("frame_device_ptr");

@@ -121,6 +121,9 @@ class Context : public Recorder {
   void read_damage_coded(const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w, int* frame_h, int* full);
   void set_damage_exact(bool on);
   void damage_exact_stats(int* n_pending, int* n_changed, int* fresh);
+  void read_damage_moved(const FdhDamageMove* moves, int n_moves, const FdhCodedTile** tiles, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes,
+                         int* frame_w, int* frame_h, int* full, int* n_copied);
+  void find_damage_moves(int max_shift, FdhDamageMove* out_moves, int* out_votes, int cap, int* n_out);
   // picking (include/figdraw_hip_pick.h; fdh_pick.cpp)
   void set_pick(bool on) { pick_on_ = on; }
   void set_pick_tag(int32_t z, int32_t id) { set_tag(PickTag{z, id}); }

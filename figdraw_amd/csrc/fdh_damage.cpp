@@ -1,11 +1,14 @@
 // fdh_damage.cpp -- damage tracking, damage readback, coded and exact damage readback on the host: the two components a device context holds
-// (DamageTracker, DamageReadback: fdh_damage_host.h) -- every launch of k_damage.hip, k_damage_codec.hip and k_damage_filter.hip, the
+// (DamageTracker, DamageReadback: fdh_damage_host.h) -- every launch of k_damage.hip, k_damage_codec.hip, k_damage_filter.hip and k_damage_move.hip, the
 // pending set, the page-locked buffers a read returns, exact mode's mirror -- and the host-only functions behind fdh_damage_closure, fdh_apply_damage, fdh_decode_damage and
 // fdh_coded_damage_bound.  What belongs to the context of an entry point (its refusals, the wait for the last frame) is fdh_context.cpp's.
 #include "fdh_context.h"
 #include "fdh_damage.h"
 #include "fdh_host.h"
+#include "fdh_tile_decode.h"  // decode_tiles, tile_in_image
 
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
 
 namespace fdh {
@@ -114,7 +117,7 @@ void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* r
 // ------------------------------------------------------------------ damage readback (include/figdraw_hip_readback.h, figdraw_hip_stream.h, figdraw_hip_exact.h)
 void DamageReadback::release() {
   pixels.release(); tiles.release(); code.release(); dir.release(); cursor.release(); stamp.release();
-  mirror.release(); arrivals.release();
+  mirror.release(); arrivals.release(); moved.release(); votes.release();
   mirror_valid = false;
   if (count) (void)hipHostFree((void*)count);
   count = nullptr;
@@ -147,7 +150,7 @@ void DamageReadback::turn_exact(bool on_now, hipStream_t s) {
   if (on_now && !exact) mirror_valid = have_stats = false;
   if (!on_now && exact) {
     if (mirror.ptr) FDH_HIP(hipStreamSynchronize(s));
-    mirror.release(); arrivals.release();
+    mirror.release(); arrivals.release(); moved.release(); votes.release();
     mirror_valid = false;
   }
   exact = on_now;
@@ -243,13 +246,25 @@ int DamageReadback::read(const char* who, const ReadFrame& F, int64_t* payload_b
   if (n <= 0) return n;
   return fetch(who, F, n, every, payload_bytes);
 }
-int DamageReadback::fetch(const char* who, const ReadFrame& F, int n, bool every, int64_t* payload_bytes) try {
+int DamageReadback::fetch(const char* who, const ReadFrame& F, int n, bool every, int64_t* payload_bytes, const DamageMoveList* moves) try {
   const bool coded = payload_bytes != nullptr;
   const int nb = F.bins_x * F.bins_y;
   const size_t bound = (size_t)coded_damage_bound(F.W, F.H);  // (= nb tiles of FDH_TILE_BYTES)
   uint32_t* const words = const_cast<uint32_t*>(count);
-  count[1] = count[2] = 0xFFFFFFFFu;
-  if (coded) {
+  count[1] = count[2] = count[4] = 0xFFFFFFFFu;
+  if (moves) {
+    code.reserve_exact(bound); dir.reserve_exact((size_t)nb); cursor.reserve(2);
+    DamageEncodeMovedParams Q;
+    DamageEncodeParams& P = Q.enc;
+    P.surf = F.surf; P.stamp = stamp.ptr;
+    P.payload = code.dev; P.dir = reinterpret_cast<uint2*>(dir.dev);
+    P.n_tiles = words + 1; P.payload_bytes = words + 2;
+    P.cursor = reinterpret_cast<unsigned long long*>(cursor.ptr);
+    P.epoch = epoch; P.n_pending = (uint32_t)n; P.W = F.W; P.H = F.H; P.bins_x = F.bins_x; P.bins_y = F.bins_y; P.all = every ? 1 : 0;
+    Q.moved = moved.ptr; Q.moves = *moves; Q.n_copied = words + 4;
+    FDH_HIP(hipMemsetAsync(cursor.ptr, 0, 2 * sizeof(uint32_t), F.stream));
+    launch_damage_encode_moved(F.stream, Q);
+  } else if (coded) {
     code.reserve_exact(bound); dir.reserve_exact((size_t)nb); cursor.reserve(2);
     DamageEncodeParams P;
     P.surf = F.surf; P.stamp = stamp.ptr;  // (`every`: the stamps are not read, and may not exist yet)
@@ -273,7 +288,8 @@ int DamageReadback::fetch(const char* who, const ReadFrame& F, int n, bool every
   if (count[1] != (uint32_t)n) throw Error(FDH_ERR_HIP, std::string(who) + ": the " + (coded ? "encoder's" : "pack's") + " tile count differs from the pending count");
   if (coded) {
     *payload_bytes = (int64_t)count[2];  // (the directory is not read here: the CPU's loads from page-locked memory are slow)
-    if (*payload_bytes > (int64_t)bound || *payload_bytes % 16 != 0) throw Error(FDH_ERR_HIP, "fdh_read_damage_coded: the encoder left no valid payload size");
+    if (*payload_bytes > (int64_t)bound || *payload_bytes % 16 != 0) throw Error(FDH_ERR_HIP, std::string(who) + ": the encoder left no valid payload size");
+    if (moves && count[4] > (uint32_t)n) throw Error(FDH_ERR_HIP, std::string(who) + ": the encoder left no valid count of COPY tiles");
   }
   consumed(F);
   return n;
@@ -304,6 +320,94 @@ void DamageReadback::read_coded(const ReadFrame& F, const FdhCodedTile** t, cons
   if (payload_bytes) *payload_bytes = bytes;
   report(F, n, n_tiles, frame_w, frame_h, full);
 }
+// ------------------------------------------------------------------ moved reads (include_readback/figdraw_hip_moves.h)
+// what both entry points refuse alike, before anything is touched
+static void need_exact(const char* who, const DamageReadback& rb) {
+  if (!rb.on || !rb.exact) throw Error(FDH_ERR_INVALID, std::string(who) + ": needs damage readback and exact damage readback on (fdh_set_damage_readback, fdh_set_damage_exact)");
+}
+// The match must see the mirror before the filter stores the new tiles into it, so it runs over the pending set as it is before the
+// filter -- a superset of the tiles the encoder will meet.  Both launches are in stream order; the filter's synchronise serves both.
+void DamageReadback::read_moved(const ReadFrame& F, const FdhDamageMove* moves, int n_moves, const FdhCodedTile** t, const uint8_t** payload, int* n_tiles,
+                                int64_t* payload_bytes, int* frame_w, int* frame_h, int* full, int* n_copied) {
+  const char* const who = "fdh_read_damage_moved";
+  need_exact(who, *this);
+  if (n_moves < 0 || n_moves > kDamageMovesMax) throw Error(FDH_ERR_INVALID, std::string(who) + ": n_moves outside 0 .. 8");
+  if (n_moves > 0 && !moves) throw Error(FDH_ERR_INVALID, std::string(who) + ": null moves");
+  DamageMoveList L{};
+  L.n = n_moves;
+  for (int i = 0; i < n_moves; i++) {
+    if (moves[i].dx == 0 && moves[i].dy == 0) throw Error(FDH_ERR_INVALID, std::string(who) + ": move " + std::to_string(i) + " is (0, 0)");
+    L.dx[i] = moves[i].dx; L.dy[i] = moves[i].dy;
+  }
+  if (F.W > INT16_MAX || F.H > INT16_MAX || (size_t)coded_damage_bound(F.W, F.H) > (size_t)UINT32_MAX)
+    throw Error(FDH_ERR_INVALID, std::string(who) + ": a directory entry holds coordinates up to 32767 and offsets of 32 bits");
+  bool every = false;
+  int n = pending(who, F, &every);
+  int64_t bytes = 0;
+  int copied = 0;
+  const bool fresh = !mirror_valid || mirror_w != F.W || mirror_h != F.H;
+  if (n_moves == 0 || fresh || n <= 0) {
+    n = read(who, F, &bytes);  // the coded read, byte for byte
+  } else {
+    const int nb = F.bins_x * F.bins_y;
+    moved.reserve((size_t)nb);  // (the stream is idle)
+    DamageMoveMatchParams M;
+    M.surf = F.surf; M.mirror = mirror.ptr; M.stamp = stamp.ptr; M.moved = moved.ptr; M.moves = L;
+    M.epoch = epoch; M.W = F.W; M.H = F.H; M.bins_x = F.bins_x; M.bins_y = F.bins_y; M.all = every ? 1 : 0;
+    launch_damage_move_match(F.stream, M);
+    FDH_HIP(hipGetLastError());  // (nothing has changed yet: a failure here leaves set and mirror as they were)
+    n = filter(who, F, n, &every);
+    if (n > 0) {
+      n = fetch(who, F, n, every, &bytes, &L);
+      copied = (int)count[4];
+    }
+  }
+  if (t) *t = dir.ptr;
+  if (payload) *payload = code.ptr;
+  if (payload_bytes) *payload_bytes = bytes;
+  if (n_copied) *n_copied = copied;
+  report(F, n, n_tiles, frame_w, frame_h, full);
+}
+void DamageReadback::find_moves(const ReadFrame& F, int max_shift, FdhDamageMove* out_moves, int* out_votes, int cap, int* n_out) {
+  const char* const who = "fdh_find_damage_moves";
+  need_exact(who, *this);
+  if (max_shift < 1 || max_shift > kDamageShiftMax) throw Error(FDH_ERR_INVALID, std::string(who) + ": max_shift outside 1 .. 256");
+  if (cap < 0 || (cap > 0 && (!out_moves || !out_votes))) throw Error(FDH_ERR_INVALID, std::string(who) + ": negative cap, or null arrays");
+  if (n_out) *n_out = 0;
+  bool every = false;
+  const int n = pending(who, F, &every);
+  if (n <= 0 || !mirror_valid || mirror_w != F.W || mirror_h != F.H) return;
+  constexpr int kWords = 2 * kDamageVoteSpan;
+  votes.reserve((size_t)kWords);
+  DamageMoveVotesParams P;
+  P.surf = F.surf; P.mirror = mirror.ptr; P.stamp = stamp.ptr; P.votes = votes.ptr;
+  P.epoch = epoch; P.W = F.W; P.H = F.H; P.bins_x = F.bins_x; P.bins_y = F.bins_y; P.all = every ? 1 : 0; P.max_shift = max_shift;
+  FDH_HIP(hipMemsetAsync(votes.ptr, 0, kWords * sizeof(uint32_t), F.stream));
+  launch_damage_move_votes(F.stream, P);
+  FDH_HIP(hipGetLastError());
+  std::vector<uint32_t> v((size_t)kWords);
+  FDH_HIP(hipMemcpyAsync(v.data(), votes.ptr, kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, F.stream));
+  FDH_HIP(hipStreamSynchronize(F.stream));
+  struct Cand { uint32_t votes; int d, horizontal; };
+  std::vector<Cand> cands;
+  for (int hz = 0; hz < 2; hz++)
+    for (int d = -max_shift; d <= max_shift; d++)
+      if (const uint32_t k = v[(size_t)(hz * kDamageVoteSpan + d + kDamageShiftMax)]) cands.push_back(Cand{k, d, hz});
+  // votes descending, then |d| ascending, then vertical before horizontal, then negative d first
+  std::sort(cands.begin(), cands.end(), [](const Cand& a, const Cand& b) {
+    if (a.votes != b.votes) return a.votes > b.votes;
+    if (std::abs(a.d) != std::abs(b.d)) return std::abs(a.d) < std::abs(b.d);
+    if (a.horizontal != b.horizontal) return a.horizontal < b.horizontal;
+    return a.d < b.d;
+  });
+  const int m = std::min(cap, (int)cands.size());
+  for (int i = 0; i < m; i++) {
+    out_moves[i].dx = (int16_t)(cands[(size_t)i].horizontal ? cands[(size_t)i].d : 0);
+    out_moves[i].dy = (int16_t)(cands[(size_t)i].horizontal ? 0 : cands[(size_t)i].d);
+    out_votes[i] = (int)cands[(size_t)i].votes;
+  }
+  if (n_out) *n_out = m;
+}
 // Tiles cross the link at no more bytes than they hold, but reach the mirror through a second pass on the CPU (fdh_apply_damage out of
 // page-locked memory: ~0.7 - 1 us a tile), which a whole-frame copy into the caller's memory does not pay (~0.3 us a bin).  From
 // kReadbackWholeNum / kReadbackWholeDen of the grid on, the whole frame is the cheaper way to the same mirror
@@ -331,10 +435,6 @@ void DamageReadback::read_into(const ReadFrame& F, uint8_t* image, int64_t pitch
 }
 
 // ------------------------------------------------------------------ host only: the receiver's side of both reads
-// is (x, y, tw, th) a bin clipped to an image of w x h pixels?
-static bool tile_in_image(int64_t x, int64_t y, int64_t tw, int64_t th, int w, int h) {
-  return tw >= 1 && tw <= FDH_TILE_PX && th >= 1 && th <= FDH_TILE_PX && x >= 0 && y >= 0 && x + tw <= w && y + th <= h;
-}
 void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles) {
   if (n_tiles < 0) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: negative tile count");
   if (w < 0 || h < 0 || pitch_bytes < (int64_t)4 * w) throw Error(FDH_ERR_INVALID, "fdh_apply_damage: the pitch is shorter than a row");
@@ -350,95 +450,13 @@ void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDa
   }
 }
 
-namespace {
-inline uint32_t load32(const uint8_t* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
-inline uint16_t load16(const uint8_t* p) { uint16_t v; std::memcpy(&v, p, 2); return v; }
-inline int pal_bits(int n) { return n <= 2 ? 1 : n <= 4 ? 2 : n <= 16 ? 4 : 8; }
-
-// what (mode, n, w, h) give as the payload's size; the tile's fields are in range when this is called
-inline uint32_t coded_size(const FdhCodedTile& t) {
-  const uint32_t px = (uint32_t)t.w * (uint32_t)t.h;
-  switch (t.mode) {
-    case FDH_TILE_PAL: return 4u * t.n + 4u * ((px * (uint32_t)pal_bits(t.n) + 31u) / 32u);
-    case FDH_TILE_RUNS: return 4u * ((6u * t.n + 3u) / 4u);
-    case FDH_TILE_RAW: return 4u * px;
-    default: return 0;
-  }
-}
-// nullptr, or why tile t of a w x h image with payload_bytes of payload cannot be decoded
-const char* coded_tile_fault(const FdhCodedTile& t, int w, int h, const uint8_t* payload, int64_t payload_bytes) {
-  if (!tile_in_image(t.x, t.y, t.w, t.h, w, h)) return "is not a bin inside the image";
-  const uint32_t px = (uint32_t)t.w * (uint32_t)t.h;
-  if (t.mode > FDH_TILE_RAW) return "has an unknown mode";
-  if (t.mode == FDH_TILE_PAL) {
-    if (t.n < 1 || t.n > 256) return "has a palette of no or of more than 256 colours";
-    if (t.bits != pal_bits(t.n)) return "has bits that do not match its palette's size";
-  } else if (t.bits != 0) return "has bits outside PAL";
-  if (t.mode == FDH_TILE_RUNS && (t.n < 1 || t.n > px)) return "has no runs, or more runs than pixels";
-  if ((t.mode == FDH_TILE_SOLID || t.mode == FDH_TILE_RAW) && t.n != 0) return "has a count its mode does not use";
-  if (t.mode != FDH_TILE_SOLID && t.solid != 0) return "has a colour outside SOLID";
-  if (t.size != coded_size(t)) return "has a size that is not its mode's";
-  if (t.mode == FDH_TILE_SOLID) return t.offset != 0 ? "has an offset without a payload" : nullptr;
-  if (t.offset % 16 != 0) return "has an offset that is not a multiple of 16";
-  if ((int64_t)t.offset + (int64_t)t.size > payload_bytes) return "reaches beyond the payload";
-  const uint8_t* p = payload + t.offset;
-  if (t.mode == FDH_TILE_PAL) {
-    const uint8_t* idx = p + 4 * (size_t)t.n;
-    const uint32_t mask = (1u << t.bits) - 1u;
-    for (uint32_t i = 0; i < px; i++) {
-      const uint32_t at = i * t.bits;
-      if (((load32(idx + 4 * (size_t)(at >> 5)) >> (at & 31u)) & mask) >= t.n) return "has a palette index beyond its palette";
-    }
-  } else if (t.mode == FDH_TILE_RUNS) {
-    const uint8_t* len = p + 4 * (size_t)t.n;
-    uint64_t sum = 0;
-    for (uint32_t k = 0; k < t.n; k++) sum += (uint64_t)load16(len + 2 * (size_t)k) + 1u;
-    if (sum != px) return "has run lengths that do not sum to its pixels";
-  }
-  return nullptr;
-}
-}  // namespace
-
 void decode_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload, int64_t payload_bytes) {
-  if (n_tiles < 0) throw Error(FDH_ERR_INVALID, "fdh_decode_damage: negative tile count");
-  if (payload_bytes < 0) throw Error(FDH_ERR_INVALID, "fdh_decode_damage: negative payload size");
-  if (w < 0 || h < 0 || pitch_bytes < (int64_t)4 * w) throw Error(FDH_ERR_INVALID, "fdh_decode_damage: the pitch is shorter than a row");
-  if (n_tiles == 0) return;
-  if (!image || !tiles || (!payload && payload_bytes > 0)) throw Error(FDH_ERR_INVALID, "fdh_decode_damage: null image, tiles or payload");
-  for (int i = 0; i < n_tiles; i++)  // every tile is checked, its payload included, before any byte is written
-    if (const char* why = coded_tile_fault(tiles[i], w, h, payload, payload_bytes))
-      throw Error(FDH_ERR_INVALID, "fdh_decode_damage: tile " + std::to_string(i) + " " + why);
-  uint32_t px[FDH_TILE_PX * FDH_TILE_PX];  // a tile, tight
-  for (int i = 0; i < n_tiles; i++) {
-    const FdhCodedTile& t = tiles[i];
-    const uint32_t n_px = (uint32_t)t.w * (uint32_t)t.h;
-    const uint8_t* p = t.mode == FDH_TILE_SOLID ? nullptr : payload + t.offset;
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(px);
-    if (t.mode == FDH_TILE_SOLID) {
-      for (uint32_t k = 0; k < n_px; k++) px[k] = t.solid;
-    } else if (t.mode == FDH_TILE_PAL) {
-      uint32_t pal[256];
-      std::memcpy(pal, p, 4 * (size_t)t.n);
-      const uint8_t* idx = p + 4 * (size_t)t.n;
-      const uint32_t bits = t.bits, mask = (1u << bits) - 1u, per = 32u / bits;
-      for (uint32_t k = 0; k < n_px; k += per) {  // a word of indices at a time
-        uint32_t v = load32(idx + 4 * (size_t)(k / per));
-        const uint32_t m = n_px - k < per ? n_px - k : per;
-        for (uint32_t j = 0; j < m; j++, v >>= bits) px[k + j] = pal[v & mask];
-      }
-    } else if (t.mode == FDH_TILE_RUNS) {
-      const uint8_t* len = p + 4 * (size_t)t.n;
-      uint32_t at = 0;
-      for (uint32_t k = 0; k < t.n; k++) {
-        const uint32_t c = load32(p + 4 * (size_t)k), m = (uint32_t)load16(len + 2 * (size_t)k) + 1u;
-        for (uint32_t j = 0; j < m; j++) px[at + j] = c;
-        at += m;
-      }
-    } else {
-      src = p;
-    }
-    for (int r = 0; r < t.h; r++) std::memcpy(image + (int64_t)(t.y + r) * pitch_bytes + (int64_t)4 * t.x, src + (size_t)r * 4 * t.w, (size_t)4 * t.w);
-  }
+  std::string why;
+  if (!decode_tiles("fdh_decode_damage", 1, image, pitch_bytes, w, h, tiles, n_tiles, payload, payload_bytes, &why)) throw Error(FDH_ERR_INVALID, why);
+}
+void decode_damage_moved(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload, int64_t payload_bytes) {
+  std::string why;
+  if (!decode_tiles("fdh_decode_damage_moved", 2, image, pitch_bytes, w, h, tiles, n_tiles, payload, payload_bytes, &why)) throw Error(FDH_ERR_INVALID, why);
 }
 
 }  // namespace fdh

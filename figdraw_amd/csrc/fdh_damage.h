@@ -13,6 +13,7 @@
 
 #include "fdh_kernels.h"
 #include "fdh_damage_read.h"  // the read kernels: k_damage_pack, k_damage_encode
+#include "fdh_damage_move.h"  // moved damage readback: k_damage_move_match, k_damage_encode_moved, k_damage_move_votes
 
 struct FdhDamageTile;  // include/figdraw_hip_readback.h
 struct FdhCodedTile;   // include/figdraw_hip_stream.h
@@ -126,10 +127,12 @@ void launch_composite_damage(hipStream_t s, const DrawRec* draws, const QuadExt*
 // in *n_pending (page-locked host memory: the host reads it after the stream's synchronise and launches nothing when it is 0).
 void launch_damage_accumulate(hipStream_t s, const uint8_t* mask, uint32_t* stamp, uint32_t epoch, int bins, uint32_t* n_pending);
 
-// Host only (fdh_damage.cpp): what fdh_damage_closure, fdh_apply_damage, fdh_decode_damage and fdh_coded_damage_bound run.
+// Host only (fdh_damage.cpp; the decoder itself is fdh_tile_decode.cpp): what fdh_damage_closure, fdh_apply_damage, fdh_decode_damage,
+// fdh_decode_damage_moved and fdh_coded_damage_bound run.
 void damage_closure(const uint8_t* changed, int bins_x, int bins_y, const int* rects, const float* radii, int n_nodes, uint8_t* out);
 void apply_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhDamageTile* tiles, const uint8_t* pixels, int n_tiles);
 void decode_damage(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload, int64_t payload_bytes);
+void decode_damage_moved(uint8_t* image, int64_t pitch_bytes, int w, int h, const FdhCodedTile* tiles, int n_tiles, const uint8_t* payload, int64_t payload_bytes);
 int64_t coded_damage_bound(int w, int h);
 
 }  // namespace fdh

@@ -8,6 +8,7 @@
 
 #include "../../include/figdraw_hip_readback.h"  // FdhDamageTile
 #include "../../include/figdraw_hip_stream.h"    // FdhCodedTile
+#include "../../include_readback/figdraw_hip_moves.h"  // FdhDamageMove
 #include "fdh_frame.h"    // LaunchJob
 #include "fdh_kernels.h"  // BinParams, CompositeParams
 #include "fdh_memory.h"   // DeviceBuf, PinnedBuf
@@ -16,6 +17,7 @@ namespace fdh {
 
 using LaunchSpan = std::function<void(bool)>;
 struct DamageReadback;
+struct DamageMoveList;  // fdh_damage_move.h
 // Damage tracking (include/figdraw_hip_damage.h; submission side but for `on`): the per-bin signatures of the last tracked frame, what its
 // resolve left, and the footprint a fused V pass of a node that did not run writes over (k_damage_guard).
 struct DamageTracker {
@@ -47,7 +49,7 @@ struct DamageReadback {
   uint32_t epoch = 1;  // the stamp of a pending bin
   int w = 0, h = 0;    // the frame size the stamps describe
   DeviceBuf<uint32_t> stamp, cursor;   // [bin]; k_damage_encode's claim counter
-  volatile uint32_t* count = nullptr;  // pinned, 3 words: pending bins after the last k_damage_accumulate; tiles of the last read; a coded read's payload bytes
+  volatile uint32_t* count = nullptr;  // pinned words: pending bins after the last k_damage_accumulate; tiles of the last read; a coded read's payload bytes; [3] the filter's count; [4] a moved read's COPY tiles
   PinnedBuf<uint8_t> pixels, code;     // what the reads return: [tile][64][256] with its tiles; the coded payload with its directory
   PinnedBuf<FdhDamageTile> tiles;
   PinnedBuf<FdhCodedTile> dir;
@@ -58,6 +60,9 @@ struct DamageReadback {
   DeviceBuf<uint32_t> mirror;
   DeviceBuf<unsigned long long> arrivals;
   int stat_pending = 0, stat_changed = 0, stat_fresh = 0;
+  // moved reads (include_readback/figdraw_hip_moves.h; need exact mode): k_damage_move_match's answer per bin; the mover's counters
+  DeviceBuf<uint8_t> moved;
+  DeviceBuf<uint32_t> votes;
   void turn(bool on_now, hipStream_t s);
   void turn_exact(bool on_now, hipStream_t s);
   void exact_stats(int* n_pending, int* n_changed, int* fresh) const;
@@ -72,7 +77,14 @@ struct DamageReadback {
   // the one read routine: pending(), filter(), fetch().  Returns the tile count.
   int read(const char* who, const ReadFrame& F, int64_t* payload_bytes);
   // its last step, over n > 0 pending bins: k_damage_pack into pixels / tiles, or (`payload_bytes`) k_damage_encode into code / dir; consumed()
-  int fetch(const char* who, const ReadFrame& F, int n, bool every, int64_t* payload_bytes);
+  // (`moves`: a moved read -- k_damage_encode_moved against moved[], and count[4] = the COPY tiles)
+  int fetch(const char* who, const ReadFrame& F, int n, bool every, int64_t* payload_bytes, const DamageMoveList* moves = nullptr);
+  // fdh_read_damage_moved: the coded read with k_damage_move_match in front of the filter and k_damage_encode_moved behind it -- one launch
+  // more than a coded exact read, and no synchronise more
+  void read_moved(const ReadFrame& F, const FdhDamageMove* moves, int n_moves, const FdhCodedTile** t, const uint8_t** payload, int* n_tiles,
+                  int64_t* payload_bytes, int* frame_w, int* frame_h, int* full, int* n_copied);
+  // fdh_find_damage_moves: k_damage_move_votes over the pending set as it stands, and the sort of its counters
+  void find_moves(const ReadFrame& F, int max_shift, FdhDamageMove* out_moves, int* out_votes, int cap, int* n_out);
   // fdh_read_damage, fdh_read_damage_coded, fdh_read_damage_into
   void read_raw(const ReadFrame& F, const FdhDamageTile** t, const uint8_t** px, int* n_tiles, int* frame_w, int* frame_h, int* full);
   void read_coded(const ReadFrame& F, const FdhCodedTile** t, const uint8_t** payload, int* n_tiles, int64_t* payload_bytes, int* frame_w, int* frame_h, int* full);

@@ -9,5 +9,6 @@
 #include "k_pick.hip"
 #include "k_damage_codec.hip"
 #include "k_damage_filter.hip"
+#include "k_damage_move.hip"
 #include "k_msdf.hip"
 #include "k_msdf_cubic.hip"
