@@ -132,6 +132,9 @@ def load():
     if hasattr(L, "fdh_put_glyph_outlines_cubic"):  # include_glyphs/figdraw_hip_cubic_batch.h
         L.fdh_put_glyph_outlines_cubic.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
         L.fdh_put_glyph_coverage_batch_cubic.argtypes = [vp, vp, C.c_int, C.c_uint32, vp]
+    if hasattr(L, "fdh_put_image_sdf"):  # include_glyphs/figdraw_hip_image_sdf.h
+        L.fdh_put_image_sdf.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int * 4]
+        L.fdh_put_image_sdf_of.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_uint32, C.c_int * 4]
     L.fdh_read_pixels.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.fdh_debug_read_surface.argtypes = [vp, C.c_int, vp]
     L.fdh_scene_retain.argtypes = [vp, vp, C.c_float, C.c_float, C.c_int, _F4]
@@ -465,6 +468,21 @@ class HipContext:
         out = (C.c_int * 4)()
         flag = 2 if lcd_filter == "context" else (1 if lcd_filter else 0)  # "context": follow set_text_lcd_filtering (FDH_GLYPH_LCD_CONTEXT)
         self._ck(self.L.fdh_put_glyph_image(self.h, int(key), rgba.shape[1], rgba.shape[0], rgba.ctypes.data, flag, out))
+        return tuple(out)
+
+    def put_image_sdf(self, key, rgba: np.ndarray, channel: int = 3, pad: int = 0, sdf_range: int = 0):
+        """the distance field of a coverage image (fdh_put_image_sdf, include_glyphs/figdraw_hip_image_sdf.h): byte `channel` of the h x w x 4
+        texels is the coverage; the field has `pad` texels more on every side and the range sdf_range (0: 4) and draws through draw_msdf.
+        -> the rectangle (x, y, w + 2 pad, h + 2 pad)"""
+        rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+        out = (C.c_int * 4)()
+        self._ck(self.L.fdh_put_image_sdf(self.h, int(key), rgba.shape[1], rgba.shape[0], rgba.ctypes.data, int(channel), int(pad), int(sdf_range) << 8, out))
+        return tuple(out)
+
+    def put_image_sdf_of(self, src_key, key, channel: int = 3, pad: int = 0, sdf_range: int = 0):
+        """put_image_sdf of the texels that src_key holds in the atlas (fdh_put_image_sdf_of): nothing crosses the bus.  -> the rectangle"""
+        out = (C.c_int * 4)()
+        self._ck(self.L.fdh_put_image_sdf_of(self.h, int(src_key), int(key), int(channel), int(pad), int(sdf_range) << 8, out))
         return tuple(out)
 
     def put_image_mips(self, key, mips):

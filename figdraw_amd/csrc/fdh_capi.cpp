@@ -13,6 +13,7 @@
 #include "../../include_glyphs/figdraw_hip_glyphs.h"
 #include "../../include_glyphs/figdraw_hip_coverage.h"
 #include "../../include_glyphs/figdraw_hip_cubic.h"
+#include "../../include_glyphs/figdraw_hip_image_sdf.h"
 
 using fdh::Context;
 
@@ -211,6 +212,12 @@ int fdh_put_glyph_coverage_batch(FdhContext* c, const FdhGlyphOutline* glyphs, i
 }
 int fdh_put_glyph_coverage_batch_cubic(FdhContext* c, const FdhGlyphOutline* glyphs, int n_glyphs, uint32_t flags, int (*out_rects)[4]) {
   return guard([&] { C(c)->put_glyph_coverage_batch_cubic(glyphs, n_glyphs, flags, out_rects); });
+}
+int fdh_put_image_sdf(FdhContext* c, int64_t key, int w, int h, const uint8_t* rgba, int channel, int pad, uint32_t flags, int out_rect[4]) {
+  return guard([&] { C(c)->put_image_sdf(key, w, h, rgba, channel, pad, flags, out_rect); });
+}
+int fdh_put_image_sdf_of(FdhContext* c, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) {
+  return guard([&] { C(c)->put_image_sdf_of(src_key, key, channel, pad, flags, out_rect); });
 }
 int fdh_glyph_coverage_batch_stats(FdhContext* c, FdhGlyphBatchStats* out) {
   return guard([&] {

@@ -15,7 +15,7 @@ namespace fdh {
 namespace mc = msdf::cubic;
 
 void GlyphMaker::release() {
-  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release();
+  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release(); glyph_src_.release();
 }
 namespace {
 // a refusal under the name of the call that makes it
@@ -222,6 +222,56 @@ void GlyphMaker::put_field(const SegmentFormat& fmt, FieldKernels kernels, hipSt
   // sampled at level 0 alone, and these texels have no other home: such a field gets that level.
   if (w == 1 || h == 1) launch_atlas_blit(s, atlas.level(0), atlas.size(), x, y, field, w, h);
   glyph_to_atlas(s, atlas, field, spare, w, h, x, y, 0u);  // (synchronises: `rec` stays alive until then)
+}
+
+// ---- distance fields from coverage images (the specification: include_glyphs/figdraw_hip_image_sdf.h).  What both calls ask of their arguments
+// beside the source; -> the range
+static int image_sdf_range(const Refusal& bad, int channel, int pad, uint32_t flags) {
+  if (channel < 0 || channel > 3) throw bad("channel must be in 0..3");
+  if (pad < 0 || pad > 64) throw bad("pad must be in 0..64");
+  if (flags & ~0xFF00u) throw bad("unknown flag (FDH_GLYPH_SDF_RANGE only)");
+  const uint32_t range = (flags >> 8) & 255u;
+  if (range > 64u) throw bad("a distance range is at most 64");
+  return range ? (int)range : 4;
+}
+void GlyphMaker::put_image_sdf(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const uint8_t* rgba, int channel, int pad, uint32_t flags, int out_rect[4]) {
+  const Refusal bad{"put_image_sdf"};
+  if (w <= 0 || h <= 0 || !rgba) throw bad("empty image");
+  const int range = image_sdf_range(bad, channel, pad, flags);
+  put_image_field(s, atlas, key, w, h, rgba, 0, 0, channel, pad, range, out_rect);
+}
+void GlyphMaker::put_image_sdf_of(hipStream_t s, Atlas& atlas, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) {
+  const Refusal bad{"put_image_sdf_of"};
+  const int range = image_sdf_range(bad, channel, pad, flags);
+  const AtlasEntry* src = atlas.find(src_key);
+  if (!src) throw bad("unknown source key");
+  if (src_key == key) throw bad("the source and the field need two keys");
+  put_image_field(s, atlas, key, src->w, src->h, nullptr, src->x, src->y, channel, pad, range, out_rect);  // (by value: the placement may drop `src`)
+}
+// The source goes to scratch -- from the host behind the placement, as every put copies; from the atlas AHEAD of it: a placement that grows
+// the atlas frees the levels the source is in (Atlas::alloc waits for the stream first) --, one launch makes the field, then the level
+// chain every glyph image takes, with the distance field's rule for an image 1 texel wide or high (put_field).
+void GlyphMaker::put_image_field(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const uint8_t* rgba, int from_x, int from_y, int channel, int pad, int range, int out_rect[4]) {
+  constexpr int64_t kNoAtlasTakes = 1 << 24;  // (a size beyond it fares as this one does, and the sums below stay ints)
+  const int ow = (int)std::min<int64_t>((int64_t)w + 2 * pad, kNoAtlasTakes), oh = (int)std::min<int64_t>((int64_t)h + 2 * pad, kNoAtlasTakes);
+  const bool device = atlas.has_device();
+  if (device) {
+    const size_t n = (size_t)ow * oh;
+    glyph_a_.reserve(n);
+    glyph_b_.reserve(n);
+    glyph_src_.reserve((size_t)w * h);
+    if (!rgba) {
+      const size_t S = (size_t)atlas.size();
+      FDH_HIP(hipMemcpy2DAsync(glyph_src_.ptr, (size_t)w * 4, atlas.level(0) + (size_t)from_y * S + from_x, S * 4, (size_t)w * 4, (size_t)h, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  const AtlasEntry& e = atlas.place(s, key, ow, oh, out_rect);
+  if (!device) return;
+  const int x = e.x, y = e.y;
+  if (rgba) FDH_HIP(hipMemcpyAsync(glyph_src_.ptr, rgba, (size_t)w * h * 4, hipMemcpyHostToDevice, s));
+  launch_image_sdf_generate(s, glyph_src_.ptr, w, h, w, channel, pad, range, glyph_a_.ptr);
+  if (ow == 1 || oh == 1) launch_atlas_blit(s, atlas.level(0), atlas.size(), x, y, glyph_a_.ptr, ow, oh);
+  glyph_to_atlas(s, atlas, glyph_a_.ptr, glyph_b_.ptr, ow, oh, x, y, 0u);  // (synchronises: `rgba` is free after)
 }
 
 // ---- the batches.  What n single puts do, in three passes: every glyph is validated; every glyph is placed, in order, through Atlas::place; then

@@ -32,6 +32,10 @@ class GlyphMaker {
   // fdh_put_glyph_coverage_batch_cubic (the specification: include_glyphs/figdraw_hip_cubic_batch.h): put_glyph_coverage_batch for segments of 8 floats
   void put_glyph_coverage_batch_cubic(hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
   const FdhGlyphBatchStats& glyph_coverage_batch_stats() const { return coverage_stats_; }
+  // fdh_put_image_sdf and fdh_put_image_sdf_of (the specification: include_glyphs/figdraw_hip_image_sdf.h): the distance field of a coverage image
+  // from the host, or of the texels an entry of the atlas holds
+  void put_image_sdf(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const uint8_t* rgba, int channel, int pad, uint32_t flags, int out_rect[4]);
+  void put_image_sdf_of(hipStream_t s, Atlas& atlas, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]);
   void release();  // the scratch buffers (the stream is idle)
 
  private:
@@ -43,6 +47,8 @@ class GlyphMaker {
   void put_lines(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const std::vector<float>& lines, uint32_t flags, int out_rect[4]);
   void put_field(const SegmentFormat& fmt, FieldKernels kernels, hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const float* segs, int n, float range, bool correct, int out_rect[4]);
   void glyph_to_atlas(hipStream_t s, const Atlas& atlas, uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags);
+  // the two image-field puts behind their validation: `rgba` from the host, or null and the w x h texels at (from_x, from_y) of the atlas's level 0
+  void put_image_field(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const uint8_t* rgba, int from_x, int from_y, int channel, int pad, int range, int out_rect[4]);
   // the batches: pass 1 in either format, then passes 2 and 3 of all four (the placement, the tables, the copies, `middle`'s launches, the level chain)
   void put_fields(const SegmentFormat& fmt, hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
   void put_coverage(const SegmentFormat& fmt, hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
@@ -52,6 +58,7 @@ class GlyphMaker {
   int batch_level_chain(hipStream_t s, const Atlas& atlas, int m, const BatchTables& T, uint32_t* field, uint32_t* spare);
 
   DeviceBuf<uint32_t> glyph_a_, glyph_b_;  // the device glyph pipeline: the raster and its filtered / minified successors
+  DeviceBuf<uint32_t> glyph_src_;          // the source texels of an image's distance field (put_image_field)
   DeviceBuf<float> glyph_lines_, glyph_acc_, glyph_edges_;  // flattened outline, area accumulators; the edge records of a distance field (fdh_msdf_host.h)
   DeviceBuf<uint32_t> glyph_tab_;  // the batches: the glyph records (msdf::BatchGlyph), the tile -> glyph words, the owner bits of the deep levels (fdh_glyph_tables.h)
   FdhGlyphBatchStats batch_stats_ = {}, coverage_stats_ = {};  // of the last put_glyph_outlines, of the last put_glyph_coverage_batch (either in either segment format)

@@ -164,6 +164,10 @@ void launch_minify2_batch(hipStream_t s, int l, const msdf::BatchGlyph* glyphs, 
 // of every glyph, from `src` into `dst`.  Bit for bit what launch_rasterize_lines and launch_lcd_filter make of each glyph.
 void launch_coverage_batch(hipStream_t s, const float4* lines, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, float* acc, uint32_t* out);
 void launch_lcd_filter_batch(hipStream_t s, const msdf::BatchGlyph* glyphs, const uint32_t* tile_glyph, int n_tiles, const uint32_t* src, uint32_t* dst);
+// fdh_put_image_sdf (include_glyphs/figdraw_hip_image_sdf.h; k_image_sdf.hip): byte `channel` of the sw x sh RGBA8 texels at `src`, `src_pitch`
+// texels from row to row, is a coverage image; `out` takes its distance field of range `range` (1 .. 64), (sw + 2 pad) x (sh + 2 pad)
+// texels, rows packed, the encoded distance in all four bytes
+void launch_image_sdf_generate(hipStream_t s, const uint32_t* src, int sw, int sh, int src_pitch, int channel, int pad, int range, uint32_t* out);
 // The frame upload (k_upload_frame): a table of runs, each `bytes` of pinned host memory (its device view) going to byte offset
 // dst_off of the frame block.  kind 0: 16-byte units; 1: BinRecs -- copied in 8-byte units, and the lane that carries a record's
 // pixel bounds also writes the draw's 4-byte bin box; 2: DrawRecs -- 16-byte units, and the `ext` of every F_GENERAL record gets
