@@ -52,6 +52,17 @@ class GlyphBatchStats(C.Structure):  # FdhGlyphBatchStats
                 ("launches", C.c_int32), ("bytes_copied", C.c_int64)]
 
 
+class AtlasMoveStats(C.Structure):  # FdhAtlasMoveStats (include_glyphs/figdraw_hip_atlas.h)
+    _fields_ = [("entries", C.c_int32), ("rects_moved", C.c_int32), ("texels", C.c_int64), ("tiles", C.c_int32), ("launches", C.c_int32),
+                ("size_before", C.c_int32), ("size_after", C.c_int32), ("packed_before", C.c_int64), ("packed_after", C.c_int64),
+                ("us_pack", C.c_int32), ("us_alloc", C.c_int32), ("us_tables", C.c_int32), ("us_move", C.c_int32)]
+
+
+class AtlasUsage(C.Structure):  # FdhAtlasUsage
+    _fields_ = [("size", C.c_int32), ("entries", C.c_int32), ("used_area", C.c_int64), ("packed_area", C.c_int64), ("epoch", C.c_uint64),
+                ("rebuilds", C.c_int64), ("compactions", C.c_int64)]
+
+
 def build(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 the C-ABI library in-tree (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -135,6 +146,13 @@ def load():
     if hasattr(L, "fdh_put_image_sdf"):  # include_glyphs/figdraw_hip_image_sdf.h
         L.fdh_put_image_sdf.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int * 4]
         L.fdh_put_image_sdf_of.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_uint32, C.c_int * 4]
+    if hasattr(L, "fdh_compact_atlas"):  # include_glyphs/figdraw_hip_atlas.h
+        L.fdh_compact_atlas.argtypes = [vp, C.c_int, C.POINTER(AtlasMoveStats)]
+        L.fdh_set_atlas_keep.argtypes = [vp, C.c_int]
+        L.fdh_get_atlas_keep.argtypes = [vp, C.POINTER(C.c_int)]
+        L.fdh_image_rect.argtypes = [vp, C.c_int64, C.c_int * 4]
+        L.fdh_atlas_usage.argtypes = [vp, C.POINTER(AtlasUsage)]
+        L.fdh_debug_read_atlas_level.argtypes = [vp, C.c_int, vp, C.c_int64]
     L.fdh_read_pixels.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.fdh_debug_read_surface.argtypes = [vp, C.c_int, vp]
     L.fdh_scene_retain.argtypes = [vp, vp, C.c_float, C.c_float, C.c_int, _F4]
@@ -512,6 +530,41 @@ class HipContext:
 
     def remove_image(self, key):
         self._ck(self.L.fdh_remove_image(self.h, int(key)))
+
+    def compact_atlas(self, size: int = 0) -> dict:
+        """repack the live entries into a fresh atlas of `size` (0: the current size), every entry kept (fdh_compact_atlas,
+        include_glyphs/figdraw_hip_atlas.h); rectangles of earlier puts are stale afterwards: image_rect.  -> the move's statistics"""
+        st = AtlasMoveStats()
+        self._ck(self.L.fdh_compact_atlas(self.h, int(size), C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in AtlasMoveStats._fields_}
+
+    def set_atlas_keep(self, on: bool = True):
+        """keep mode: a put that does not fit compacts or grows the atlas with every entry kept instead of emptying it (fdh_set_atlas_keep)"""
+        self._ck(self.L.fdh_set_atlas_keep(self.h, 1 if on else 0))
+
+    def atlas_keep(self) -> bool:
+        out = C.c_int()
+        self._ck(self.L.fdh_get_atlas_keep(self.h, C.byref(out)))
+        return bool(out.value)
+
+    def image_rect(self, key):
+        """where an entry is now: (x, y, w, h)"""
+        out = (C.c_int * 4)()
+        self._ck(self.L.fdh_image_rect(self.h, int(key), out))
+        return tuple(out)
+
+    def atlas_usage(self) -> dict:
+        """size, entries, used_area, packed_area, epoch, rebuilds, compactions (fdh_atlas_usage)"""
+        u = AtlasUsage()
+        self._ck(self.L.fdh_atlas_usage(self.h, C.byref(u)))
+        return {name: int(getattr(u, name)) for name, _ in AtlasUsage._fields_}
+
+    def read_atlas_level(self, level: int) -> np.ndarray:
+        """one whole level of the atlas, (size >> level)^2 x 4 bytes (fdh_debug_read_atlas_level)"""
+        ls = self.atlas_size() >> level
+        out = np.zeros((max(ls, 1), max(ls, 1), 4), dtype=np.uint8)
+        self._ck(self.L.fdh_debug_read_atlas_level(self.h, int(level), out.ctypes.data, out.nbytes))
+        return out
 
     def reset_atlas(self, minimum_size=0):
         self._ck(self.L.fdh_reset_atlas(self.h, int(minimum_size)))

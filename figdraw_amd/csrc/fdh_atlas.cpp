@@ -2,6 +2,7 @@
 #include "fdh_context.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <string>
 
@@ -16,11 +17,9 @@ void Atlas::init(int size, bool device, hipStream_t s) {
 // An empty atlas of `size` (rounded up to a power of two) takes the place of this one.  The new levels are allocated FIRST (DeviceBuf::reserve's
 // rule): a failing hipMalloc frees what it got and leaves the old atlas whole -- levels, entries, skyline, size and epoch.  For the
 // length of a grow both atlases exist: peak memory is the new one plus the old one.
-void Atlas::alloc(int size, hipStream_t s) {
-  int sz = 1;
-  while (sz < size) sz <<= 1;  // the samplers mask coordinates: keep the atlas a power of two
-  uint32_t* fresh[kMaxMips] = {};
+int Atlas::alloc_levels(int sz, hipStream_t s, uint32_t* fresh[kMaxMips]) const {
   int n = 0;
+  std::fill(fresh, fresh + kMaxMips, nullptr);
   try {
     for (int ls = sz; ls >= 1 && n < kMaxMips; ls >>= 1) {
       if (device_) {
@@ -31,9 +30,16 @@ void Atlas::alloc(int size, hipStream_t s) {
     }
     if (device_) FDH_HIP(hipStreamSynchronize(s));  // host uploads (upload_rect) are not ordered behind the stream: the zeros are there first
   } catch (...) {
-    for (auto l : fresh) if (l) (void)hipFree(l);
+    for (int l = 0; l < kMaxMips; l++) if (fresh[l]) (void)hipFree(fresh[l]);
     throw;
   }
+  return n;
+}
+void Atlas::alloc(int size, hipStream_t s) {
+  int sz = 1;
+  while (sz < size) sz <<= 1;  // the samplers mask coordinates: keep the atlas a power of two
+  uint32_t* fresh[kMaxMips] = {};
+  const int n = alloc_levels(sz, s, fresh);
   release_levels();
   std::copy(fresh, fresh + kMaxMips, levels_);
   size_ = sz;
@@ -49,6 +55,7 @@ void Atlas::reset(int minimum_size, hipStream_t s) {
   int sz = initial_size_;
   while (sz < minimum_size) sz *= 2;  // plannedAtlasSize
   alloc(sz, s);
+  rebuilds_++;
 }
 int64_t Atlas::packed_area() const {
   int64_t a = 0;
@@ -63,34 +70,144 @@ AtlasView Atlas::view() const {
 }
 // Every put's way into the directory: the skyline search (glcontext.nim:541-579), growing until the image fits, then the entry, the
 // epoch and the caller's out_rect.  The returned entry has no ink boxes.
-AtlasEntry& Atlas::place(hipStream_t s, int64_t key, int w, int h, int out_rect[4]) {
-  for (;;) {
-    const int S = size_, M = margin_;
-    const int iw = w + M * 2, ih = h + M * 2;
-    int lowest = S, at = 0;
-    for (int i = 0; i < S; i++) {
-      int v = heights_[i];
-      if (v < lowest) {
-        bool fit = true;
-        for (int j = 0; j <= iw; j++) {
-          if (i + j >= S) { fit = false; break; }
-          if ((int)heights_[i + j] > v) { fit = false; break; }
-        }
-        if (fit) { lowest = v; at = i; }
+bool Atlas::skyline_place(std::vector<uint16_t>& heights, int S, int M, int w, int h, int* x, int* y) {
+  const int iw = w + M * 2, ih = h + M * 2;
+  int lowest = S, at = 0;
+  for (int i = 0; i < S; i++) {
+    int v = heights[i];
+    if (v < lowest) {
+      bool fit = true;
+      for (int j = 0; j <= iw; j++) {
+        if (i + j >= S) { fit = false; break; }
+        if ((int)heights[i + j] > v) { fit = false; break; }
       }
+      if (fit) { lowest = v; at = i; }
     }
-    if (lowest + ih > S) {
-      if (S >= 16384) throw Error(FDH_ERR_ATLAS_FULL, "atlas full at 16384^2");
-      alloc(S * 2, s);  // grow(): resetImageAtlas(atlasSize * 2) drops every entry (glcontext.nim:536-539)
+  }
+  if (lowest + ih > S) return false;
+  for (int j = at; j < at + iw; j++) heights[j] = (uint16_t)(lowest + ih + M * 2);
+  *x = at + M; *y = lowest + M;
+  return true;
+}
+AtlasEntry& Atlas::place(hipStream_t s, int64_t key, int w, int h, int out_rect[4], Stored stored) {
+  for (;;) {
+    int x, y;
+    if (!skyline_place(heights_, size_, margin_, w, h, &x, &y)) {
+      if (size_ >= 16384) throw Error(FDH_ERR_ATLAS_FULL, "atlas full at 16384^2");
+      alloc(size_ * 2, s);  // grow(): resetImageAtlas(atlasSize * 2) drops every entry (glcontext.nim:536-539)
+      rebuilds_++;
       continue;
     }
-    for (int j = at; j < at + iw; j++) heights_[j] = (uint16_t)(lowest + ih + M * 2);
-    const int x = at + M, y = lowest + M;
-    AtlasEntry& e = entries_[key] = AtlasEntry{x, y, w, h, false, {}, {}};
+    AtlasEntry& e = entries_[key] = AtlasEntry{x, y, w, h, false, {}, {}, stored, nullptr};
     epoch_++;
     if (out_rect) { out_rect[0] = x; out_rect[1] = y; out_rect[2] = w; out_rect[3] = h; }
     return e;
   }
+}
+// ------------------------------------------------------------------ compaction and keep mode (include_glyphs/figdraw_hip_atlas.h)
+std::vector<const std::pair<const int64_t, AtlasEntry>*> Atlas::compaction_order() const {
+  std::vector<const std::pair<const int64_t, AtlasEntry>*> order;
+  order.reserve(entries_.size());
+  for (const auto& kv : entries_) order.push_back(&kv);
+  std::sort(order.begin(), order.end(), [](const auto* a, const auto* b) {
+    if (a->second.h != b->second.h) return a->second.h > b->second.h;
+    if (a->second.w != b->second.w) return a->second.w > b->second.w;
+    return a->first < b->first;
+  });
+  return order;
+}
+void Atlas::compact(hipStream_t s, int size, FdhAtlasMoveStats* out) {
+  if (size < 0 || size > 16384) throw Error(FDH_ERR_INVALID, "compact_atlas: size must be 0 (the current size) or in 1..16384");
+  int sz = size_;
+  if (size) for (sz = 1; sz < size;) sz <<= 1;
+  // ---- the trial: every live entry on a scratch skyline, before anything changes
+  using clock = std::chrono::steady_clock;
+  auto us_since = [](clock::time_point t) { return (int32_t)std::chrono::duration_cast<std::chrono::microseconds>(clock::now() - t).count(); };
+  const auto t_pack = clock::now();
+  const auto order = compaction_order();
+  std::vector<uint16_t> sky((size_t)sz, 0);
+  std::unordered_map<int64_t, AtlasEntry> fresh_entries;
+  fresh_entries.reserve(order.size());
+  std::vector<MovedEntry> moved;
+  moved.reserve(order.size());
+  for (const auto* kv : order) {
+    int x, y;
+    if (!skyline_place(sky, sz, margin_, kv->second.w, kv->second.h, &x, &y))
+      throw Error(FDH_ERR_ATLAS_FULL, "compact_atlas: the live entries do not fit an atlas of " + std::to_string(sz));
+    AtlasEntry& e = fresh_entries[kv->first] = kv->second;
+    e.x = x; e.y = y;
+    moved.push_back(MovedEntry{&e, kv->second.x, kv->second.y});
+  }
+  FdhAtlasMoveStats st{};
+  st.entries = (int32_t)order.size();
+  st.size_before = size_; st.size_after = sz;
+  st.packed_before = packed_area();
+  st.us_pack = us_since(t_pack);
+  // ---- the new levels first (a failed allocation leaves the old atlas whole), the texels, then the old levels go
+  uint32_t* fresh[kMaxMips] = {};
+  const auto t_alloc = clock::now();
+  const int n = alloc_levels(sz, s, fresh);
+  st.us_alloc = us_since(t_alloc);
+  if (device_) {
+    if (!mover_) throw Error(FDH_ERR_INVALID, "compact_atlas: no mover");
+    const AtlasView from = view();
+    uint32_t* old[kMaxMips];
+    std::copy(levels_, levels_ + kMaxMips, old);
+    const int old_size = size_, old_levels = n_levels_;
+    std::copy(fresh, fresh + kMaxMips, levels_);
+    size_ = sz; n_levels_ = n;
+    try {
+      mover_->move_entries(s, from, *this, moved, st);
+    } catch (...) {  // the old atlas is still whole: it takes its place again
+      release_levels();
+      std::copy(old, old + kMaxMips, levels_);
+      size_ = old_size; n_levels_ = old_levels;
+      throw;
+    }
+    const auto t_free = clock::now();
+    for (auto l : old) if (l) (void)hipFree(l);
+    st.us_alloc += us_since(t_free);
+  }
+  size_ = sz; n_levels_ = n;
+  heights_.swap(sky);
+  entries_.swap(fresh_entries);  // (`moved` pointed into it: nothing reads that any more)
+  epoch_++;
+  compactions_++;
+  st.packed_after = packed_area();
+  if (out) *out = st;
+}
+void Atlas::make_room(hipStream_t s, const int (*wh)[2], int n) {
+  if (!keep_ || n <= 0) return;
+  int x, y;
+  auto all_fit = [&](std::vector<uint16_t>& sky, int S) {
+    for (int i = 0; i < n; i++) if (!skyline_place(sky, S, margin_, wh[i][0], wh[i][1], &x, &y)) return false;
+    return true;
+  };
+  std::vector<uint16_t> sky = heights_;
+  if (all_fit(sky, size_)) return;  // no placement of this call grows the atlas
+  const auto order = compaction_order();
+  int target = 16384;
+  for (int S = size_; S <= 16384; S *= 2) {
+    sky.assign((size_t)S, 0);
+    bool fits = true;
+    for (const auto* kv : order) if (!skyline_place(sky, S, margin_, kv->second.w, kv->second.h, &x, &y)) { fits = false; break; }
+    if (fits && all_fit(sky, S)) { target = S; break; }
+  }
+  try {
+    compact(s, target, nullptr);
+  } catch (const Error& e) {
+    if (e.code != FDH_ERR_ATLAS_FULL) throw;  // (not even the live entries fit 16384 in compaction order: the call goes on as without keep)
+  }
+}
+void Atlas::usage(FdhAtlasUsage* out) const {
+  *out = FdhAtlasUsage{};
+  out->size = size_;
+  out->entries = (int32_t)entries_.size();
+  for (const auto& kv : entries_) out->used_area += (int64_t)kv.second.w * kv.second.h;
+  out->packed_area = packed_area();
+  out->epoch = epoch_;
+  out->rebuilds = rebuilds_;
+  out->compactions = compactions_;
 }
 void Atlas::upload_rect(int level, int x, int y, int w, int h, const uint8_t* rgba) {
   const int LS = size_ >> level;
@@ -160,6 +277,7 @@ static void measure_ink(AtlasEntry& e, const uint8_t* rgba) {
 }
 void Atlas::put_image(hipStream_t s, int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]) {
   if (w <= 0 || h <= 0 || !rgba) throw Error(FDH_ERR_INVALID, "put_image: empty image");
+  make_room(s, w, h);
   AtlasEntry& e = place(s, key, w, h, out_rect);
   measure_ink(e, rgba);
   put_levels(e.x, e.y, w, h, rgba);
@@ -213,7 +331,19 @@ void Atlas::put_mips(hipStream_t s, int64_t key, int n, const int* ws, const int
   if (n <= 0 || !ws || !hs || !premul_rgba) throw Error(FDH_ERR_INVALID, "put_mips: no mip levels");
   for (int l = 0; l < n; l++)
     if (ws[l] <= 0 || hs[l] <= 0 || !premul_rgba[l]) throw Error(FDH_ERR_INVALID, "put_mips: bad mip level");
-  const AtlasEntry& e = place(s, key, ws[0], hs[0], out_rect);
+  // what a move of the entry needs (Stored::levels): the sizes, and the texels of levels 1 .. as the caller gave them
+  auto kept = std::make_shared<KeptLevels>();
+  kept->n = std::min(n, (int)kMaxMips);
+  for (int l = 0; l < kept->n; l++) {
+    kept->w[l] = ws[l]; kept->h[l] = hs[l];
+    if (l == 0 || !device_) continue;
+    const size_t at = kept->texels.size(), texels = (size_t)ws[l] * hs[l];
+    kept->texels.resize(at + texels);
+    std::memcpy(kept->texels.data() + at, premul_rgba[l], texels * 4);
+  }
+  make_room(s, ws[0], hs[0]);
+  AtlasEntry& e = place(s, key, ws[0], hs[0], out_rect, Stored::levels);
+  e.kept = std::move(kept);
   for (int l = 0; l < n && l < n_levels_; l++) upload_rect(l, e.x >> l, e.y >> l, ws[l], hs[l], premul_rgba[l]);
 }
 void Atlas::put_flippy(hipStream_t s, int64_t key, const uint8_t* data, size_t n, int out_rect[4]) {
@@ -254,6 +384,10 @@ void Atlas::update_image(int64_t key, int w, int h, const uint8_t* rgba) {  // g
   if (!rgba) throw Error(FDH_ERR_INVALID, "update_image: null image");
   measure_ink(it->second, rgba);  // the new texels have bounds of their own (draws shrink to them: shrink_to_ink) ...
   epoch_++;                       // ... and records cached for retained scenes hold the old ones
+  if (it->second.stored == Stored::levels) {  // (an entry of put_mips gives up its own levels for what put_levels stores)
+    it->second.stored = Stored::chain;
+    it->second.kept.reset();
+  }
   put_levels(it->second.x, it->second.y, w, h, rgba);
 }
 

@@ -14,6 +14,7 @@
 #include "../../include_glyphs/figdraw_hip_coverage.h"
 #include "../../include_glyphs/figdraw_hip_cubic.h"
 #include "../../include_glyphs/figdraw_hip_image_sdf.h"
+#include "../../include_glyphs/figdraw_hip_atlas.h"
 
 using fdh::Context;
 
@@ -223,6 +224,33 @@ int fdh_glyph_coverage_batch_stats(FdhContext* c, FdhGlyphBatchStats* out) {
   return guard([&] {
     if (!out) throw fdh::Error(FDH_ERR_INVALID, "fdh_glyph_coverage_batch_stats: null pointer");
     *out = C(c)->glyph_coverage_batch_stats();
+  });
+}
+// atlas compaction (include_glyphs/figdraw_hip_atlas.h)
+int fdh_compact_atlas(FdhContext* c, int size, FdhAtlasMoveStats* out) { return guard([&] { C(c)->compact_atlas(size, out); }); }
+int fdh_set_atlas_keep(FdhContext* c, int on) { return guard([&] { C(c)->set_atlas_keep(on != 0); }); }
+int fdh_get_atlas_keep(FdhContext* c, int* out) {
+  return guard([&] {
+    if (!out) throw fdh::Error(FDH_ERR_INVALID, "fdh_get_atlas_keep: null pointer");
+    *out = C(c)->atlas_keep() ? 1 : 0;
+  });
+}
+int fdh_image_rect(FdhContext* c, int64_t key, int out_rect[4]) {
+  return guard([&] {
+    if (!out_rect) throw fdh::Error(FDH_ERR_INVALID, "fdh_image_rect: null pointer");
+    C(c)->image_rect(key, out_rect);
+  });
+}
+int fdh_atlas_usage(FdhContext* c, FdhAtlasUsage* out) {
+  return guard([&] {
+    if (!out) throw fdh::Error(FDH_ERR_INVALID, "fdh_atlas_usage: null pointer");
+    C(c)->atlas_usage(out);
+  });
+}
+int fdh_debug_read_atlas_level(FdhContext* c, int level, uint8_t* out, int64_t capacity_bytes) {
+  return guard([&] {
+    if (!out) throw fdh::Error(FDH_ERR_INVALID, "fdh_debug_read_atlas_level: null output buffer");
+    C(c)->debug_read_atlas_level(level, out, capacity_bytes);
   });
 }
 int fdh_has_image(FdhContext* c, int64_t key, int* out) { return guard([&] { *out = C(c)->has_image(key) ? 1 : 0; }); }

@@ -34,6 +34,7 @@ Context::Context(int atlas_size, float pixel_scale, int device, uint32_t flags)
     : Recorder(frame_env_, &call_log_), device_(device), flags_(flags), pixel_scale_(pixel_scale),
       frame_((flags & FDH_CREATE_RECORD_ONLY) != 0, device), host_only_((flags & FDH_CREATE_RECORD_ONLY) != 0) {
   frame_env_.atlas = &atlas_;
+  atlas_.set_mover(&glyphs_);
   if (host_only_) {  // a call recorder: the front-end and the atlas packer run, nothing is drawn, no device is touched
     atlas_.init(atlas_size, false, nullptr);
     return;

@@ -72,6 +72,13 @@ class Context : public Recorder {
   void reset_atlas(int minimum_size) { sync(); atlas_.reset(minimum_size, stream_); }
   int atlas_size() const { return atlas_.size(); }
   int64_t atlas_packed_area() const { return atlas_.packed_area(); }
+  // compaction and keep mode (include_glyphs/figdraw_hip_atlas.h): the atlas's; glyphs_ moves the texels for it (AtlasMover)
+  void compact_atlas(int size, FdhAtlasMoveStats* out) { sync(); atlas_.compact(stream_, size, out); }
+  void set_atlas_keep(bool on) { atlas_.set_keep(on); }
+  bool atlas_keep() const { return atlas_.keep(); }
+  void image_rect(int64_t key, int out_rect[4]) const;
+  void atlas_usage(FdhAtlasUsage* out) const { atlas_.usage(out); }
+  void debug_read_atlas_level(int level, uint8_t* out, int64_t capacity_bytes);  // (fdh_debug.cpp)
 
   // readback / interop
   void read_pixels(int x, int y, int w, int h, uint8_t* out);

@@ -147,6 +147,19 @@ void Context::debug_bin_digest(uint64_t out[8]) {
   out[0] = h;
 }
 
+void Context::image_rect(int64_t key, int out_rect[4]) const {
+  const AtlasEntry* e = atlas_.find(key);
+  if (!e) throw Error(FDH_ERR_INVALID, "fdh_image_rect: unknown key");
+  out_rect[0] = e->x; out_rect[1] = e->y; out_rect[2] = e->w; out_rect[3] = e->h;
+}
+void Context::debug_read_atlas_level(int level, uint8_t* out, int64_t capacity_bytes) {
+  need_device("fdh_debug_read_atlas_level");
+  if (level < 0 || level >= atlas_.n_levels()) throw Error(FDH_ERR_INVALID, "fdh_debug_read_atlas_level: the atlas has no such level");
+  const size_t LS = (size_t)(atlas_.size() >> level), bytes = LS * LS * 4;
+  if (capacity_bytes < (int64_t)bytes) throw Error(FDH_ERR_INVALID, "fdh_debug_read_atlas_level: the buffer is smaller than the level");
+  sync();
+  FDH_HIP(hipMemcpy(out, atlas_.level(level), bytes, hipMemcpyDeviceToHost));
+}
 void Context::debug_read_surface(int which, uint8_t* out) {
   need_device("debug_read_surface");
   drain();

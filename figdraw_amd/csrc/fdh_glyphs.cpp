@@ -4,18 +4,20 @@
 #include "fdh_glyphs.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <exception>
 #include <string>
 
 #include "fdh_kernels.h"
+#include "fdh_atlas_move.h"
 #include "fdh_msdf_cubic_host.h"
 
 namespace fdh {
 namespace mc = msdf::cubic;
 
 void GlyphMaker::release() {
-  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release(); glyph_src_.release();
+  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release(); glyph_src_.release(); move_tab_.release();
 }
 namespace {
 // a refusal under the name of the call that makes it
@@ -36,6 +38,7 @@ void GlyphMaker::put_glyph_image(hipStream_t s, Atlas& atlas, int64_t key, int w
   if (flags & ~kLcdFlags) throw bad("unknown flag");
   const size_t n = (size_t)w * h;
   if (atlas.has_device()) { glyph_a_.reserve(n); glyph_b_.reserve(n); }
+  atlas.make_room(s, w, h);
   const AtlasEntry& e = atlas.place(s, key, w, h, out_rect);
   if (!atlas.has_device()) return;
   FDH_HIP(hipMemcpyAsync(glyph_a_.ptr, rgba, n * 4, hipMemcpyHostToDevice, s));
@@ -181,6 +184,7 @@ void GlyphMaker::put_lines(hipStream_t s, Atlas& atlas, int64_t key, int w, int 
     glyph_lines_.reserve(std::max<size_t>(lines.size(), 4));
     glyph_acc_.reserve((size_t)h * (w + 2));
   }
+  atlas.make_room(s, w, h);
   const AtlasEntry& e = atlas.place(s, key, w, h, out_rect);
   if (!atlas.has_device()) return;
   if (m) FDH_HIP(hipMemcpyAsync(glyph_lines_.ptr, lines.data(), lines.size() * sizeof(float), hipMemcpyHostToDevice, s));
@@ -208,7 +212,8 @@ void GlyphMaker::put_field(const SegmentFormat& fmt, FieldKernels kernels, hipSt
     glyph_b_.reserve(npx);
     glyph_edges_.reserve(std::max<size_t>(rec.size(), fmt.stride));
   }
-  const AtlasEntry& e = atlas.place(s, key, w, h, out_rect);
+  atlas.make_room(s, w, h);
+  const AtlasEntry& e = atlas.place(s, key, w, h, out_rect, Stored::chain_or_level0);
   if (!device) return;
   const int x = e.x, y = e.y;
   if (!rec.empty()) FDH_HIP(hipMemcpyAsync(glyph_edges_.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, s));
@@ -265,13 +270,103 @@ void GlyphMaker::put_image_field(hipStream_t s, Atlas& atlas, int64_t key, int w
       FDH_HIP(hipMemcpy2DAsync(glyph_src_.ptr, (size_t)w * 4, atlas.level(0) + (size_t)from_y * S + from_x, S * 4, (size_t)w * 4, (size_t)h, hipMemcpyDeviceToDevice, s));
     }
   }
-  const AtlasEntry& e = atlas.place(s, key, ow, oh, out_rect);
+  atlas.make_room(s, ow, oh);  // (behind the copy: in keep mode the source may move)
+  const AtlasEntry& e = atlas.place(s, key, ow, oh, out_rect, Stored::chain_or_level0);
   if (!device) return;
   const int x = e.x, y = e.y;
   if (rgba) FDH_HIP(hipMemcpyAsync(glyph_src_.ptr, rgba, (size_t)w * h * 4, hipMemcpyHostToDevice, s));
   launch_image_sdf_generate(s, glyph_src_.ptr, w, h, w, channel, pad, range, glyph_a_.ptr);
   if (ow == 1 || oh == 1) launch_atlas_blit(s, atlas.level(0), atlas.size(), x, y, glyph_a_.ptr, ow, oh);
   glyph_to_atlas(s, atlas, glyph_a_.ptr, glyph_b_.ptr, ow, oh, x, y, 0u);  // (synchronises: `rgba` is free after)
+}
+
+// ---- fdh_compact_atlas (the specification: include_glyphs/figdraw_hip_atlas.h): the texels of every live entry from the old levels into the new
+// ones.  Level 0 of every entry that has a level chain goes into the field buffer (k_atlas_move, one launch), glyph after glyph as a batch
+// lays its images out, and the batches' own level chain makes every level of them from there -- level 0 included, with the batches' owner
+// bits in compaction order.  An entry with levels of its own (Stored::levels) follows in a second launch of k_atlas_move: its level 0 from
+// the old atlas, its other levels from the host's copy, with owner bits against every later rectangle of the new atlas.
+static_assert(move::kLevels == kMaxMips, "move::Views holds every level of an atlas");
+void GlyphMaker::move_entries(hipStream_t s, const AtlasView& from, const Atlas& to, const std::vector<MovedEntry>& moved, FdhAtlasMoveStats& st) {
+  const auto t_tables = std::chrono::steady_clock::now();
+  std::vector<msdf::BatchGlyph> tab;
+  std::vector<const MovedEntry*> chained;
+  std::vector<move::Rect> own_levels;  // the second launch: every rectangle below level 0 in compaction order, those of Stored::levels entries copied
+  std::vector<uint32_t> payload;       // ... whose kept levels, one entry after the other
+  bool any_own = false;
+  for (const MovedEntry& m : moved) {
+    const AtlasEntry& e = *m.e;
+    each_stored(e, to.size(), to.n_levels(), [&](int, int, int, int w, int h) { st.rects_moved++; st.texels += (int64_t)w * h; });
+    if (e.stored != Stored::levels) {
+      if ((e.w == 1 || e.h == 1) && e.stored != Stored::chain_or_level0) continue;  // nothing of it is stored
+      msdf::BatchGlyph t{};
+      t.w = e.w; t.h = e.h; t.x = e.x; t.y = e.y;
+      tab.push_back(t);
+      chained.push_back(&m);
+      each_stored(e, to.size(), to.n_levels(), [&](int l, int x, int y, int w, int h) {
+        if (l > 0) own_levels.push_back(move::Rect{0, 0, 0, l, x, y, w, h, false});
+      });
+      continue;
+    }
+    any_own = true;
+    const size_t base = payload.size();
+    payload.insert(payload.end(), e.kept->texels.begin(), e.kept->texels.end());
+    each_stored(e, to.size(), to.n_levels(), [&](int l, int x, int y, int w, int h) {
+      if (l == 0) { own_levels.push_back(move::Rect{0, m.old_x, m.old_y, 0, x, y, w, h, true}); return; }
+      size_t off = base;
+      for (int k = 1; k < l; k++) off += (size_t)e.kept->w[k] * e.kept->h[k];
+      own_levels.push_back(move::Rect{move::kBuffer, (int)off, 0, l, x, y, w, h, true});
+    });
+  }
+  // ---- the tables
+  const int m = (int)tab.size();
+  BatchTables T;
+  move::Tables G, O;
+  size_t field_texels = 0;
+  if (m) {
+    batch_tables(tab, 0, m, true, to.n_levels(), &T);
+    std::vector<move::Rect> gather;
+    gather.reserve((size_t)m);
+    for (int k = 0; k < m; k++) {
+      const AtlasEntry& e = *chained[(size_t)k]->e;
+      gather.push_back(move::Rect{0, chained[(size_t)k]->old_x, chained[(size_t)k]->old_y, move::kBuffer, (int)tab[(size_t)k].field_off, 0, e.w, e.h, true});
+      field_texels += (size_t)e.w * e.h;
+    }
+    move::build_tables(gather, &G);
+  }
+  if (any_own) move::build_tables(own_levels, &O);
+  const auto t_move = std::chrono::steady_clock::now();
+  st.us_tables = (int32_t)std::chrono::duration_cast<std::chrono::microseconds>(t_move - t_tables).count();
+  // ---- the device: buffers first, then the copies and the launches on the stream.  The kept levels lie behind the tables in move_tab_:
+  // glyph_src_ is not touched -- in keep mode fdh_put_image_sdf_of has parked its source there when the compaction runs (put_image_field)
+  // -- and what the other buffers held is not needed any more by any put that has come as far as its placement.
+  glyph_a_.reserve(std::max<size_t>(field_texels, 1));
+  glyph_b_.reserve(std::max<size_t>(field_texels, 1));
+  glyph_tab_.reserve(std::max<size_t>(T.words.size(), 1));
+  move_tab_.reserve(G.words.size() + O.words.size() + payload.size() + 1);
+  uint32_t* const d_payload = move_tab_.ptr + G.words.size() + O.words.size();
+  move::Views V{};
+  for (int l = 0; l < move::kLevels; l++) { V.from[l] = from.level[l]; V.to[l] = to.level(l); }
+  V.from_size = from.size; V.from_levels = from.n_levels; V.to_size = to.size(); V.to_levels = to.n_levels();
+  V.buf_in = d_payload; V.buf_out = glyph_a_.ptr;
+  auto launch = [&](const move::Tables& M, uint32_t* at) {
+    FDH_HIP(hipMemcpyAsync(at, M.words.data(), M.words.size() * 4, hipMemcpyHostToDevice, s));
+    const uint32_t* tiles = at + (size_t)M.n_records * move::kRecordWords;
+    launch_atlas_move(s, V, reinterpret_cast<const move::Record*>(at), tiles, (int)M.n_tiles, tiles + M.n_tiles);
+    st.tiles += (int32_t)M.n_tiles;
+    st.launches++;
+  };
+  if (m) {
+    launch(G, move_tab_.ptr);
+    FDH_HIP(hipMemcpyAsync(glyph_tab_.ptr, T.words.data(), T.words.size() * 4, hipMemcpyHostToDevice, s));
+    st.launches += batch_level_chain(s, to, m, T, glyph_a_.ptr, glyph_b_.ptr);
+  }
+  if (any_own) {
+    if (!payload.empty()) FDH_HIP(hipMemcpyAsync(d_payload, payload.data(), payload.size() * 4, hipMemcpyHostToDevice, s));
+    launch(O, move_tab_.ptr + G.words.size());
+  }
+  FDH_HIP(hipStreamSynchronize(s));  // (the tables and the payload stay alive until here)
+  FDH_HIP(hipGetLastError());
+  st.us_move = (int32_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_move).count();
 }
 
 // ---- the batches.  What n single puts do, in three passes: every glyph is validated; every glyph is placed, in order, through Atlas::place; then
@@ -298,13 +393,13 @@ static int64_t validate_batch(const Refusal& bad, const FdhGlyphOutline* glyphs,
 // Pass 2 of a batch: every glyph through place(), in order; tab[i] takes its place.  A placement that grows the atlas has dropped every entry
 // before it: glyph i is then the first of the new atlas (*first).  *placed: the glyphs that got a place; the exception that ended the loop
 // (FDH_ERR_ATLAS_FULL, or no memory for a larger atlas) is returned: the glyphs before that one get their texels, as after single calls.
-static std::exception_ptr place_batch(hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, int (*out_rects)[4], std::vector<msdf::BatchGlyph>& tab, int* first, int* placed) {
+static std::exception_ptr place_batch(hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, int (*out_rects)[4], std::vector<msdf::BatchGlyph>& tab, Stored stored, int* first, int* placed) {
   std::exception_ptr failed;
   int f = 0, p = 0;
   for (; p < n; p++) {
     const int before = atlas.size();
     try {
-      const AtlasEntry& e = atlas.place(s, glyphs[p].key, glyphs[p].width, glyphs[p].height, out_rects ? out_rects[p] : nullptr);
+      const AtlasEntry& e = atlas.place(s, glyphs[p].key, glyphs[p].width, glyphs[p].height, out_rects ? out_rects[p] : nullptr, stored);
       tab[(size_t)p].x = e.x; tab[(size_t)p].y = e.y;
     } catch (...) {
       failed = std::current_exception();
@@ -358,8 +453,14 @@ void GlyphMaker::place_and_make(hipStream_t s, Atlas& atlas, const FdhGlyphOutli
     glyph_tab_.reserve(batch_table_words(tab, thin_tiles, kMaxMips));  // (whatever atlas the batch ends in)
   }
   // ---- pass 2: the places
+  // (keep mode: room for all glyphs of the batch at once, before any of them has a place -- only entries that have their texels move)
+  if (atlas.keep()) {
+    std::vector<int> wh((size_t)n * 2);
+    for (int i = 0; i < n; i++) { wh[(size_t)i * 2] = glyphs[i].width; wh[(size_t)i * 2 + 1] = glyphs[i].height; }
+    atlas.make_room(s, reinterpret_cast<const int (*)[2]>(wh.data()), n);
+  }
   int first = 0, placed = 0;
-  std::exception_ptr failed = place_batch(s, atlas, glyphs, n, out_rects, tab, &first, &placed);
+  std::exception_ptr failed = place_batch(s, atlas, glyphs, n, out_rects, tab, thin_tiles ? Stored::chain_or_level0 : Stored::chain, &first, &placed);
   stats.written = placed - first;
   stats.dropped_by_growth = first;
   // ---- pass 3: the texels of glyphs first .. placed - 1

@@ -14,7 +14,7 @@
 
 namespace fdh {
 
-class GlyphMaker {
+class GlyphMaker final : public AtlasMover {
  public:
   // Every put validates, reserves the device buffers it needs and only then takes a place: one that throws before its texels are on their
   // way leaves no entry and no epoch bump behind.  Each waits for the stream once, at its end.  (`flags`: FDH_GLYPH_LCD_CONTEXT is resolved by the context.)
@@ -36,6 +36,8 @@ class GlyphMaker {
   // from the host, or of the texels an entry of the atlas holds
   void put_image_sdf(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const uint8_t* rgba, int channel, int pad, uint32_t flags, int out_rect[4]);
   void put_image_sdf_of(hipStream_t s, Atlas& atlas, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]);
+  // fdh_compact_atlas (the specification: include_glyphs/figdraw_hip_atlas.h): the atlas's mover
+  void move_entries(hipStream_t s, const AtlasView& from, const Atlas& to, const std::vector<MovedEntry>& moved, FdhAtlasMoveStats& stats) override;
   void release();  // the scratch buffers (the stream is idle)
 
  private:
@@ -61,6 +63,7 @@ class GlyphMaker {
   DeviceBuf<uint32_t> glyph_src_;          // the source texels of an image's distance field (put_image_field)
   DeviceBuf<float> glyph_lines_, glyph_acc_, glyph_edges_;  // flattened outline, area accumulators; the edge records of a distance field (fdh_msdf_host.h)
   DeviceBuf<uint32_t> glyph_tab_;  // the batches: the glyph records (msdf::BatchGlyph), the tile -> glyph words, the owner bits of the deep levels (fdh_glyph_tables.h)
+  DeviceBuf<uint32_t> move_tab_;   // fdh_compact_atlas: the tables of its k_atlas_move launches (fdh_atlas_move.h)
   FdhGlyphBatchStats batch_stats_ = {}, coverage_stats_ = {};  // of the last put_glyph_outlines, of the last put_glyph_coverage_batch (either in either segment format)
 };
 

@@ -168,6 +168,11 @@ void launch_lcd_filter_batch(hipStream_t s, const msdf::BatchGlyph* glyphs, cons
 // texels from row to row, is a coverage image; `out` takes its distance field of range `range` (1 .. 64), (sw + 2 pad) x (sh + 2 pad)
 // texels, rows packed, the encoded distance in all four bytes
 void launch_image_sdf_generate(hipStream_t s, const uint32_t* src, int sw, int sh, int src_pitch, int channel, int pad, int range, uint32_t* out);
+// fdh_compact_atlas (include_glyphs/figdraw_hip_atlas.h; k_atlas_move.hip): the rectangles of `records` (fdh_atlas_move.h) from the levels of one
+// atlas into those of another, or from / into the dense buffers of V; `tile_record`: the record of each of the n_tiles tiles, the 1-D grid;
+// `owner`: one bit per texel of the records that share texels with a later rectangle
+namespace move { struct Views; struct Record; }
+void launch_atlas_move(hipStream_t s, const move::Views& V, const move::Record* records, const uint32_t* tile_record, int n_tiles, const uint32_t* owner);
 // The frame upload (k_upload_frame): a table of runs, each `bytes` of pinned host memory (its device view) going to byte offset
 // dst_off of the frame block.  kind 0: 16-byte units; 1: BinRecs -- copied in 8-byte units, and the lane that carries a record's
 // pixel bounds also writes the draw's 4-byte bin box; 2: DrawRecs -- 16-byte units, and the `ext` of every F_GENERAL record gets
