@@ -366,7 +366,10 @@
           const uint32_t xrel = (uint32_t)(px0 - (int)r.bx0);
           const bool rowc = py >= r.by0 && py < r.by1;
           const uint32_t wcov = rowc ? (uint32_t)((int)r.bx1 - (int)r.bx0) : 0u;
-          const bool any_px = rowc & (px0 + 3 >= (int)r.bx0) & (px0 < (int)r.bx1);
+          // (wcov != 0, not rowc alone: a quad off the frame that was not culled -- fdh_set_cull(0) -- keeps an EMPTY box clamped to the
+          // frame's edge, bx0 == bx1 == W; a direct launch's box test lets it into a partial last bin column, and where W is no multiple
+          // of 4 the lane that holds the edge passed both column tests and read its run at the texel of a quad a million pixels away)
+          const bool any_px = (wcov != 0u) & (px0 + 3 >= (int)r.bx0) & (px0 < (int)r.bx1);
           const int tx = px0 + (int)r.ext, ty = py + (int)r._pad;
           // (the atlas is a power of two wide: a shift, not a multiply -- an expensive arm would bring a divergent branch back)
           const uint32_t off_in = ((((uint32_t)ty) << (uint32_t)__builtin_ctz((uint32_t)S)) + (uint32_t)tx) << 2;

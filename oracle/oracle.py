@@ -231,6 +231,26 @@ class Oracle:
             raise RuntimeError("bad flippy / atlas full")
         return tuple(out)
 
+    def put_image_mips(self, key, mips):
+        """an explicit mip chain of OPAQUE levels (level l goes to (x >> l, y >> l)), as HipContext.put_image_mips: through put_flippy
+        with a container made here -- its blocks are stored as snappy literals, and the premultiply on load leaves alpha 255 alone"""
+        data = b"flip" + (1).to_bytes(4, "little")
+        for m in mips:
+            m = np.ascontiguousarray(m, dtype=np.uint8)
+            assert m.ndim == 3 and m.shape[2] == 4 and (m[..., 3] == 255).all(), "put_image_mips: opaque RGBA levels only"
+            raw = m.tobytes()
+            n, block = len(raw), b""
+            while True:  # the length as a varint
+                block += bytes([(n & 0x7F) | (0x80 if n > 0x7F else 0)])
+                n >>= 7
+                if not n:
+                    break
+            for at in range(0, len(raw), 60):  # literals of at most 60 bytes: tag (len - 1) << 2
+                part = raw[at:at + 60]
+                block += bytes([(len(part) - 1) << 2]) + part
+            data += b"mip!" + m.shape[1].to_bytes(4, "little") + m.shape[0].to_bytes(4, "little") + len(block).to_bytes(4, "little") + block
+        return self.put_flippy(key, data)
+
     def read_pixels(self, x=0, y=0, w=0, h=0) -> np.ndarray:
         if w <= 0 or h <= 0:
             x, y, w, h = 0, 0, self.W, self.H

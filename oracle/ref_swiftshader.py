@@ -444,6 +444,25 @@ class RefGL:
             level += 1
         return x, y, w, h
 
+    def put_image_mips(self, key, mips):
+        """putFlippy (glcontext.nim:610-620) with the levels given: level l goes to (x >> l, y >> l) as it is"""
+        mips = [np.ascontiguousarray(m, dtype=np.uint8) for m in mips]
+        h, w = mips[0].shape[:2]
+        x, y, _, _ = self._find_empty_rect(w, h)
+        s = f32(self.atlas_size)
+        self.entries[key] = (f32(x) / s, f32(y) / s, f32(w) / s, f32(h) / s)
+        g = _gl
+        g.glBindTexture(GL_TEXTURE_2D, self.atlas_tex)
+        for level, img in enumerate(mips):
+            if (self.atlas_size >> level) < 1:
+                break
+            g.glTexSubImage2D(GL_TEXTURE_2D, level, x >> level, y >> level, img.shape[1], img.shape[0], GL_RGBA, GL_UNSIGNED_BYTE, img.ctypes.data)
+        return x, y, w, h
+
+    def set_text_subpixel(self, enabled, shift=0.0, glyph_variants=False):  # the context's switch (glcontext.nim:819-822), between frames
+        self.subpixel_enabled = bool(enabled)
+        self.subpixel_shift = f32(shift)
+
     # ---- transforms (glcontext.nim:1991-2017)
     def save_transform(self):
         self.mats.append(self.mat.copy())
@@ -634,6 +653,18 @@ class RefGL:
         uv = [(uv_at[0], uv_to[1]), (uv_to[0], uv_to[1]), (uv_to[0], uv_at[1]), (uv_at[0], uv_at[1])]
         z4 = (0, 0, 0, 0)
         self._draw_quad(p4, uv, colors, z4, z4, z4, z4, 0, (0, 0))
+
+    def draw_image_adj(self, key, pos, color, size):  # drawImageAdj glcontext.nim:1369-1381: the uv rect pulled in by two texels a side
+        if key not in self.entries:
+            return
+        ex, ey, ew, eh = self.entries[key]
+        adj = f32(f32(2) / f32(self.atlas_size))
+        uv_at, uv_to = (f32(ex + adj), f32(ey + adj)), (f32(f32(ex + ew) - adj), f32(f32(ey + eh) - adj))
+        px, py = f32(pos[0]), f32(pos[1])
+        p4 = self._quad_pos(px, py, f32(px + f32(size[0])), f32(py + f32(size[1])))
+        uv = [(uv_at[0], uv_to[1]), (uv_to[0], uv_to[1]), (uv_to[0], uv_at[1]), (uv_at[0], uv_at[1])]
+        z4 = (0, 0, 0, 0)
+        self._draw_quad(p4, uv, [color] * 4, z4, z4, z4, z4, 0, (0, 0))
 
     def draw_msdf(self, key, pos, color, size, px_range, sd_threshold=0.5, stroke_weight=0.0, mtsdf=False, flip_y=False):
         if key not in self.entries:
@@ -854,11 +885,15 @@ class RefGL:
 def replay(calls, width, height, atlas_size=1024, images=None) -> np.ndarray:
     """Replay a recorded BackendContext call stream (list of [name, *args]) and
     return the top-down RGBA8 frame.  ``images`` maps key -> HxWx4 uint8 and is
-    uploaded (in sorted-key order) before the frame begins."""
+    uploaded (in sorted-key order) before the frame begins; a list of arrays is a
+    mip chain given level by level (put_image_mips)."""
     gl = RefGL(width, height, atlas_size=atlas_size)
     try:
         for key in sorted(images or {}):
-            gl.put_image(key, images[key])
+            if isinstance(images[key], (list, tuple)):
+                gl.put_image_mips(key, images[key])
+            else:
+                gl.put_image(key, images[key])
         for call in calls:
             name, args = call[0], call[1:]
             getattr(gl, name)(*args)

@@ -103,6 +103,54 @@ def hostile_goldens():
     return out
 
 
+def hostile_atlas_goldens():
+    """tests/hostile_atlas_cases.py: the direct form of every frame that has a golden through the reference's shaders
+    (ss_hostile_atlas_<name>.png), as hostile_goldens() does it, over an atlas of 256 with the images put in sorted-key order.  The frames
+    without a golden (ORACLE_ONLY) get a manifest entry for information only: the oracle with its sampler on SwiftShader's 16-bit coordinate
+    grid (texcoord_model(1)) against a SwiftShader render made here."""
+    import hostile_atlas_cases as HA
+
+    out = {}
+    w, h, images = HA.W, HA.H, HA.images()
+    o = O.Oracle(atlas_size=HA.ATLAS, threads=8)
+    HA.put_images(o)
+    for name in HA.FRAMES:
+        if HA.is_node_frame(name):
+            o.record_begin()
+            HA.render(o, name)
+            rec = HipContext(atlas_size=HA.ATLAS, record_only=True)
+            HA.put_images(rec)
+            rec.record_begin()
+            HA.render(rec, name)
+            calls = rec.record_calls()
+            rec.close()
+            _same(o.record_calls(), calls)
+        else:
+            HA.render(o, name)
+            calls = HA.calls(name)
+        img = o.read_pixels().copy()
+        ss = R.replay(calls, w, h, atlas_size=HA.ATLAS, images=images)
+        key = f"hostile_atlas_{name}"
+        if name in HA.ORACLE_ONLY:
+            O.texcoord_model(1)
+            try:
+                HA.render(o, name)
+                out[key] = {"width": w, "height": h, "n_calls": len(calls), "atlas_size": HA.ATLAS, "golden": None,
+                            "oracle_vs_swiftshader": stats(img, ss), "grid16_oracle_vs_swiftshader": stats(o.read_pixels(), ss)}
+            finally:
+                O.texcoord_model(0)
+            print("hostile_atlas", name, out[key])
+            continue
+        opaque = ss[..., :3] if (ss[..., 3] == 255).all() else ss
+        Image.fromarray(opaque).save(os.path.join(GOLD, f"ss_hostile_atlas_{name}.png"), optimize=True)
+        ys, xs = np.nonzero(np.abs(img.astype(int) - ss.astype(int)).max(axis=2) > 1)
+        out[key] = {"width": w, "height": h, "n_calls": len(calls), "atlas_size": HA.ATLAS, "oracle_vs_swiftshader": stats(img, ss),
+                    "oracle_gt1": [[int(x), int(y)] for x, y in zip(xs, ys)]}
+        assert len(xs) <= HA.MAX_GOLDEN_OUTLIERS, (name, "thin the frame or move the draw to an oracle-only family: the oracle itself is > 1 LSB from the shaders on", len(xs), "pixels")
+        print("hostile_atlas", name, out[key])
+    return out
+
+
 def main():
     assert R.available(), "needs /root/reference and SwiftShader"
     os.makedirs(GOLD, exist_ok=True)
@@ -174,16 +222,17 @@ def main():
         print("blur", radius, manifest[f"blur_r{radius:g}"])
     manifest.update(big_blur_goldens())
     manifest.update(hostile_goldens())
+    manifest.update(hostile_atlas_goldens())
     with open(os.path.join(GOLD, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] in (["big_blur"], ["hostile"]):  # only the hostile blur frames / the hostile shapes (the manifest keeps its other entries)
+    if sys.argv[1:] in (["big_blur"], ["hostile"], ["hostile_atlas"]):  # only the hostile blur frames / shapes / atlas draws (the manifest keeps its other entries)
         assert R.available(), "needs /root/reference and SwiftShader"
         with open(os.path.join(GOLD, "manifest.json")) as f:
             m = json.load(f)
-        m.update(big_blur_goldens() if sys.argv[1] == "big_blur" else hostile_goldens())
+        m.update({"big_blur": big_blur_goldens, "hostile": hostile_goldens, "hostile_atlas": hostile_atlas_goldens}[sys.argv[1]]())
         with open(os.path.join(GOLD, "manifest.json"), "w") as f:
             json.dump(m, f, indent=1, sort_keys=True)
     else:
