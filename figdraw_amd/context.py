@@ -63,6 +63,43 @@ class AtlasUsage(C.Structure):  # FdhAtlasUsage
                 ("rebuilds", C.c_int64), ("compactions", C.c_int64)]
 
 
+class DeviceImage(C.Structure):  # FdhDeviceImage (include_glyphs/figdraw_hip_device_image.h)
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("pitch_bytes", C.c_int64), ("plane_bytes", C.c_int64),
+                ("format", C.c_uint32), ("channels", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+IMAGE_RGBA8, IMAGE_PLANAR_F32, IMAGE_PLANAR_F16 = 0, 1, 2  # FdhDeviceImage.format
+IMAGE_STRAIGHT_ALPHA = 1                                   # FdhDeviceImage.flags
+
+
+def tensor_image(t, straight_alpha: bool = False) -> DeviceImage:
+    """the FdhDeviceImage of a tensor: any object with data_ptr(), shape, stride(), dtype and element_size() (a torch tensor; torch is not
+    imported here).  H x W x 4 uint8 is RGBA8; C x H x W (C = 1, 3, 4) or H x W of float32 / float16 is planar.  A layout that is not a row
+    pitch plus a plane stride over unit-stride rows raises ValueError."""
+    shape, stride, es = tuple(int(v) for v in t.shape), tuple(int(v) for v in t.stride()), int(t.element_size())
+    dtype = str(t.dtype).split(".")[-1]
+    flags = IMAGE_STRAIGHT_ALPHA if straight_alpha else 0
+    if dtype == "uint8":
+        if len(shape) != 3 or shape[2] != 4:
+            raise ValueError(f"a uint8 image is H x W x 4 (RGBA8), not {shape}")
+        h, w = shape[:2]
+        if stride[2] != 1 or stride[1] != 4 or (h > 1 and stride[0] < 4 * w):
+            raise ValueError(f"strides {stride} of an H x W x 4 image are not a row pitch over packed texels")
+        return DeviceImage(t.data_ptr(), w, h, stride[0] if h > 1 else 4 * w, 0, IMAGE_RGBA8, 4, flags, 0)
+    if dtype not in ("float32", "float16"):
+        raise ValueError(f"dtype {t.dtype}: uint8 (H x W x 4), float32 or float16 (C x H x W or H x W)")
+    if len(shape) == 2:
+        shape, stride = (1,) + shape, (0,) + stride
+    if len(shape) != 3 or shape[0] not in (1, 3, 4):
+        raise ValueError(f"a planar image is C x H x W with C = 1, 3 or 4, or H x W, not {tuple(t.shape)}")
+    c, h, w = shape
+    pitch = stride[1] * es if h > 1 else w * es
+    plane = stride[0] * es if c > 1 else 0
+    if stride[2] != 1 or pitch < w * es or (c > 1 and plane < pitch * h):
+        raise ValueError(f"strides {tuple(t.stride())} are not a plane stride and a row pitch over unit-stride rows")
+    return DeviceImage(t.data_ptr(), w, h, pitch, plane, IMAGE_PLANAR_F32 if dtype == "float32" else IMAGE_PLANAR_F16, c, flags, 0)
+
+
 def build(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 the C-ABI library in-tree (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -146,6 +183,9 @@ def load():
     if hasattr(L, "fdh_put_image_sdf"):  # include_glyphs/figdraw_hip_image_sdf.h
         L.fdh_put_image_sdf.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int * 4]
         L.fdh_put_image_sdf_of.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_uint32, C.c_int * 4]
+    if hasattr(L, "fdh_put_image_device"):  # include_glyphs/figdraw_hip_device_image.h
+        L.fdh_put_image_device.argtypes = [vp, C.c_int64, C.POINTER(DeviceImage), C.c_int * 4]
+        L.fdh_update_image_device.argtypes = [vp, C.c_int64, C.POINTER(DeviceImage)]
     if hasattr(L, "fdh_compact_atlas"):  # include_glyphs/figdraw_hip_atlas.h
         L.fdh_compact_atlas.argtypes = [vp, C.c_int, C.POINTER(AtlasMoveStats)]
         L.fdh_set_atlas_keep.argtypes = [vp, C.c_int]
@@ -502,6 +542,31 @@ class HipContext:
         out = (C.c_int * 4)()
         self._ck(self.L.fdh_put_image_sdf_of(self.h, int(src_key), int(key), int(channel), int(pad), int(sdf_range) << 8, out))
         return tuple(out)
+
+    def put_image_device(self, key, ptr, width, height, pitch_bytes, format=IMAGE_RGBA8, channels=4, plane_bytes=0, straight_alpha=False):
+        """an image from device (or page-locked host) memory at address `ptr` (fdh_put_image_device, include_glyphs/figdraw_hip_device_image.h):
+        what put_image stores of the converted texels, made on the device.  Whatever wrote the source has finished, or is ordered on the
+        context's stream (set_stream).  -> the rectangle"""
+        img = DeviceImage(ptr, int(width), int(height), int(pitch_bytes), int(plane_bytes), int(format), int(channels), IMAGE_STRAIGHT_ALPHA if straight_alpha else 0, 0)
+        out = (C.c_int * 4)()
+        self._ck(self.L.fdh_put_image_device(self.h, int(key), C.byref(img), out))
+        return tuple(out)
+
+    def update_image_device(self, key, ptr, width, height, pitch_bytes, format=IMAGE_RGBA8, channels=4, plane_bytes=0, straight_alpha=False):
+        """new texels from device memory for an entry of the same size (fdh_update_image_device)"""
+        img = DeviceImage(ptr, int(width), int(height), int(pitch_bytes), int(plane_bytes), int(format), int(channels), IMAGE_STRAIGHT_ALPHA if straight_alpha else 0, 0)
+        self._ck(self.L.fdh_update_image_device(self.h, int(key), C.byref(img)))
+
+    def put_image_tensor(self, key, tensor, straight_alpha=False):
+        """put_image_device of a tensor (tensor_image: H x W x 4 uint8, or C x H x W / H x W float32 or float16).  -> the rectangle"""
+        img = tensor_image(tensor, straight_alpha)
+        out = (C.c_int * 4)()
+        self._ck(self.L.fdh_put_image_device(self.h, int(key), C.byref(img), out))
+        return tuple(out)
+
+    def update_image_tensor(self, key, tensor, straight_alpha=False):
+        img = tensor_image(tensor, straight_alpha)
+        self._ck(self.L.fdh_update_image_device(self.h, int(key), C.byref(img)))
 
     def put_image_mips(self, key, mips):
         """Upload an explicit mip chain (premultiplied RGBA8 arrays, level 0 first), as putFlippy does."""

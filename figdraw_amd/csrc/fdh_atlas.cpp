@@ -377,18 +377,25 @@ void Atlas::put_flippy(hipStream_t s, int64_t key, const uint8_t* data, size_t n
   for (auto& m : mips) ptrs.push_back(m.data());
   put_mips(s, key, (int)mips.size(), ws.data(), hs.data(), ptrs.data(), out_rect);
 }
-void Atlas::update_image(int64_t key, int w, int h, const uint8_t* rgba) {  // glcontext.nim:591-604
+// The first half of every update (fdh_update_image, fdh_update_image_device): the entry of `key`, which must have this size; the epoch moves
+// -- records cached for retained scenes hold the old texels' bounds --, and an entry of put_mips gives up its own levels for the chain
+// that the caller stores next.  `also_refused`: what else the caller has against the call (or null), said behind the key and the size.
+AtlasEntry& Atlas::begin_update(const char* who, int64_t key, int w, int h, const char* also_refused) {
   auto it = entries_.find(key);
-  if (it == entries_.end()) throw Error(FDH_ERR_INVALID, "update_image: unknown key");
-  if (it->second.w != w || it->second.h != h) throw Error(FDH_ERR_INVALID, "update_image: size mismatch");
-  if (!rgba) throw Error(FDH_ERR_INVALID, "update_image: null image");
-  measure_ink(it->second, rgba);  // the new texels have bounds of their own (draws shrink to them: shrink_to_ink) ...
-  epoch_++;                       // ... and records cached for retained scenes hold the old ones
-  if (it->second.stored == Stored::levels) {  // (an entry of put_mips gives up its own levels for what put_levels stores)
+  if (it == entries_.end()) throw Error(FDH_ERR_INVALID, std::string(who) + ": unknown key");
+  if (it->second.w != w || it->second.h != h) throw Error(FDH_ERR_INVALID, std::string(who) + ": size mismatch");
+  if (also_refused) throw Error(FDH_ERR_INVALID, std::string(who) + ": " + also_refused);
+  epoch_++;
+  if (it->second.stored == Stored::levels) {
     it->second.stored = Stored::chain;
     it->second.kept.reset();
   }
-  put_levels(it->second.x, it->second.y, w, h, rgba);
+  return it->second;
+}
+void Atlas::update_image(int64_t key, int w, int h, const uint8_t* rgba) {  // glcontext.nim:591-604
+  AtlasEntry& e = begin_update("update_image", key, w, h, rgba ? nullptr : "null image");
+  measure_ink(e, rgba);  // the new texels have bounds of their own (draws shrink to them: shrink_to_ink)
+  put_levels(e.x, e.y, w, h, rgba);
 }
 
 }  // namespace fdh

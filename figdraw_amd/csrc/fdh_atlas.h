@@ -109,6 +109,9 @@ class Atlas {
   void put_mips(hipStream_t s, int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]);
   void put_flippy(hipStream_t s, int64_t key, const uint8_t* data, size_t n, int out_rect[4]);
   void update_image(int64_t key, int w, int h, const uint8_t* rgba);
+  // the first half of every update, the host's and GlyphMaker's from device memory: the key is looked up, the size checked, the epoch
+  // bumped, an entry with levels of its own turned into a chain entry; the caller stores the new chain and the ink boxes
+  AtlasEntry& begin_update(const char* who, int64_t key, int w, int h, const char* also_refused = nullptr);
   void release() { release_levels(); }  // (the stream is idle)
 
  private:

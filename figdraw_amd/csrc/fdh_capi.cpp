@@ -14,6 +14,7 @@
 #include "../../include_glyphs/figdraw_hip_coverage.h"
 #include "../../include_glyphs/figdraw_hip_cubic.h"
 #include "../../include_glyphs/figdraw_hip_image_sdf.h"
+#include "../../include_glyphs/figdraw_hip_device_image.h"
 #include "../../include_glyphs/figdraw_hip_atlas.h"
 
 using fdh::Context;
@@ -216,6 +217,12 @@ int fdh_put_glyph_coverage_batch_cubic(FdhContext* c, const FdhGlyphOutline* gly
 }
 int fdh_put_image_sdf(FdhContext* c, int64_t key, int w, int h, const uint8_t* rgba, int channel, int pad, uint32_t flags, int out_rect[4]) {
   return guard([&] { C(c)->put_image_sdf(key, w, h, rgba, channel, pad, flags, out_rect); });
+}
+int fdh_put_image_device(FdhContext* c, int64_t key, const FdhDeviceImage* img, int out_rect[4]) {
+  return guard([&] { C(c)->put_image_device(key, img, out_rect); });
+}
+int fdh_update_image_device(FdhContext* c, int64_t key, const FdhDeviceImage* img) {
+  return guard([&] { C(c)->update_image_device(key, img); });
 }
 int fdh_put_image_sdf_of(FdhContext* c, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) {
   return guard([&] { C(c)->put_image_sdf_of(src_key, key, channel, pad, flags, out_rect); });

@@ -11,13 +11,15 @@
 
 #include "fdh_kernels.h"
 #include "fdh_atlas_move.h"
+#include "fdh_image_import.h"
 #include "fdh_msdf_cubic_host.h"
 
 namespace fdh {
 namespace mc = msdf::cubic;
+namespace ii = image_import;
 
 void GlyphMaker::release() {
-  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release(); glyph_src_.release(); move_tab_.release();
+  glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release(); glyph_src_.release(); move_tab_.release(); ink_host_.release();
 }
 namespace {
 // a refusal under the name of the call that makes it
@@ -278,6 +280,118 @@ void GlyphMaker::put_image_field(hipStream_t s, Atlas& atlas, int64_t key, int w
   launch_image_sdf_generate(s, glyph_src_.ptr, w, h, w, channel, pad, range, glyph_a_.ptr);
   if (ow == 1 || oh == 1) launch_atlas_blit(s, atlas.level(0), atlas.size(), x, y, glyph_a_.ptr, ow, oh);
   glyph_to_atlas(s, atlas, glyph_a_.ptr, glyph_b_.ptr, ow, oh, x, y, 0u);  // (synchronises: `rgba` is free after)
+}
+
+// ---- images from device memory (the specification: include_glyphs/figdraw_hip_device_image.h).  What both calls ask of the struct; -> whether the
+// source's rows are 16-byte aligned (a lane's run of four texels is then one load per plane)
+static_assert(ii::kLevels == kMaxMips, "image_import::Params holds every level of an atlas");
+static bool validate_device_image(const Refusal& bad, const FdhDeviceImage* img) {
+  if (!img || !img->data) throw bad("null image");
+  if (img->width <= 0 || img->height <= 0) throw bad("empty image");
+  if (img->format > FDH_IMAGE_PLANAR_F16) throw bad("unknown format");
+  if (img->flags & ~(uint32_t)FDH_IMAGE_STRAIGHT_ALPHA) throw bad("unknown flag");
+  if (img->reserved) throw bad("reserved must be 0");
+  const bool planar = img->format != FDH_IMAGE_RGBA8;
+  if (planar ? !(img->channels == 1 || img->channels == 3 || img->channels == 4) : img->channels != 4)
+    throw bad("channels must be 4 for RGBA8 and 1, 3 or 4 for a planar format");
+  const int64_t element = img->format == FDH_IMAGE_PLANAR_F16 ? 2 : 4;  // (an RGBA8 texel is one aligned word)
+  const bool planes = planar && img->channels > 1;
+  if ((uintptr_t)img->data % (uintptr_t)element || img->pitch_bytes % element) throw bad("data and pitch_bytes must be multiples of the element size");
+  if (img->pitch_bytes < (int64_t)img->width * element) throw bad("pitch_bytes is below a row's bytes");
+  if (planes && (__int128)img->plane_bytes < (__int128)img->pitch_bytes * img->height) throw bad("plane_bytes is below pitch_bytes * height");
+  if (planes && img->plane_bytes % element) throw bad("plane_bytes must be a multiple of the element size");
+  return (uintptr_t)img->data % 16 == 0 && img->pitch_bytes % 16 == 0 && (!planes || img->plane_bytes % 16 == 0);
+}
+// On a context with a device: the source as the device addresses it -- device memory of `device`, or page-locked host memory.  Anything
+// else (pageable memory, another device's, an address nobody has mapped) is refused, and the runtime's sticky error cleared behind it.
+static const void* device_address(const Refusal& bad, int device, const void* data) {
+  hipPointerAttribute_t attr{};
+  const hipError_t err = hipPointerGetAttributes(&attr, data);
+  (void)hipGetLastError();
+  if (err == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == device) return data;
+  if (err == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer) return attr.devicePointer;
+  throw bad("the source is neither device memory of the context's device nor page-locked host memory");
+}
+// the scratch of an import, ahead of the placement as every put reserves: the level-5 image and what k_minify2 makes of it
+static void reserve_import(DeviceBuf<uint32_t>& a, DeviceBuf<uint32_t>& b, PinnedBuf<int32_t>& ink_host, int w, int h) {
+  if (w > 16384 || h > 16384) return;  // (no atlas takes it: the placement says so)
+  const size_t w5 = (size_t)(w + 31) / 32, h5 = (size_t)(h + 31) / 32;
+  a.reserve(w5 * h5);
+  b.reserve(((w5 + 1) / 2) * ((h5 + 1) / 2));
+  ink_host.reserve_exact(ii::kInkTiles * ii::kInkWords);
+}
+void GlyphMaker::put_device_image(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhDeviceImage* img, int out_rect[4]) {
+  const Refusal bad{"put_image_device"};
+  const bool wide = validate_device_image(bad, img);
+  const FdhDeviceImage src = *img;
+  const void* data = nullptr;
+  if (atlas.has_device()) {
+    data = device_address(bad, device, src.data);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.width, src.height);
+  }
+  atlas.make_room(s, src.width, src.height);
+  AtlasEntry& e = atlas.place(s, key, src.width, src.height, out_rect);
+  if (atlas.has_device()) import_image(s, atlas, e, src, data, wide);
+}
+void GlyphMaker::update_device_image(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhDeviceImage* img) {
+  const Refusal bad{"update_image_device"};
+  const bool wide = validate_device_image(bad, img);
+  const FdhDeviceImage src = *img;
+  const AtlasEntry* old = atlas.find(key);  // (ahead of the pointer's check and the buffers; begin_update says the same again)
+  if (!old) throw bad("unknown key");
+  if (old->w != src.width || old->h != src.height) throw bad("size mismatch");
+  const void* data = nullptr;
+  if (atlas.has_device()) {
+    data = device_address(bad, device, src.data);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.width, src.height);
+  }
+  AtlasEntry& e = atlas.begin_update(bad.who, key, src.width, src.height);
+  e.has_ink = false;  // (the old texels' boxes; import_image measures the new ones)
+  if (atlas.has_device()) import_image(s, atlas, e, src, data, wide);
+}
+// Two launches for an image up to 2048 x 2048: k_image_import makes levels 0 .. 5, k_image_import_tail the rest from the level-5 image.
+// A larger level-5 image first takes k_minify2 / k_atlas_blit steps, as glyph_to_atlas does, until the tail's workgroup can hold it.
+// Waits for the stream once; the tiles' ink blocks are in page-locked memory by then (the kernel stores them there).  `data`: the source as the device addresses it; `wide`: its rows are 16-byte aligned.
+void GlyphMaker::import_image(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const FdhDeviceImage& img, const void* data, bool wide) {
+  ii::Params P{};
+  P.data = data; P.pitch_bytes = img.pitch_bytes; P.plane_bytes = img.plane_bytes;
+  P.w = img.width; P.h = img.height;
+  P.format = img.format; P.channels = img.channels; P.flags = img.flags;
+  P.wide = wide && e.w >= 4 ? 1 : 0;
+  P.x = e.x; P.y = e.y;
+  atlas.each_level(e.x, e.y, e.w, e.h, [&](int, int, int, int, int) { P.n_store++; });
+  P.ink = e.w <= ii::kInkMax && e.h <= ii::kInkMax;
+  for (int l = 0; l < ii::kTileLevels; l++) { P.lw[l] = (e.w + (1 << l) - 1) >> l; P.lh[l] = (e.h + (1 << l) - 1) >> l; }
+  for (int l = 0; l < atlas.n_levels(); l++) P.level[l] = atlas.level(l);
+  P.size = atlas.size();
+  uint32_t *cur = glyph_a_.ptr, *nxt = glyph_b_.ptr;
+  P.scratch = cur;
+  P.ink_block = ink_host_.dev;
+  launch_image_import(s, P);
+  int l = ii::kTileLevels - 1, cw = P.lw[l], ch = P.lh[l];
+  for (; (cw > ii::kTailMax || ch > ii::kTailMax) && l + 1 < P.n_store; std::swap(cur, nxt)) {
+    launch_minify2(s, cur, nxt, cw, ch);
+    l++; cw = (cw + 1) / 2; ch = (ch + 1) / 2;
+    launch_atlas_blit(s, atlas.level(l), atlas.size() >> l, e.x >> l, e.y >> l, nxt, cw, ch);
+  }
+  if (l + 1 < P.n_store) {
+    ii::TailParams T{};
+    T.src = cur; T.sw = cw; T.sh = ch; T.l0 = l; T.n_store = P.n_store;
+    T.x = e.x; T.y = e.y; T.size = P.size;
+    std::copy(P.level, P.level + ii::kLevels, T.level);
+    launch_image_import_tail(s, T);
+  }
+  FDH_HIP(hipStreamSynchronize(s));
+  FDH_HIP(hipGetLastError());
+  e.has_ink = P.ink != 0;
+  if (!P.ink) return;
+  int32_t got[ii::kInkWords];
+  ii::fold_ink(ink_host_.ptr, P.lw[ii::kTileLevels - 1] * P.lh[ii::kTileLevels - 1], got);
+  for (int k = 0; k < kInkLevels; k++) {  // (a box no texel grew: empty, at the origin)
+    const int32_t *a = got + 4 * k, *c = got + 32 + 4 * k;
+    e.ink_a[k] = a[2] ? InkBox{(int16_t)a[0], (int16_t)a[1], (int16_t)a[2], (int16_t)a[3]} : InkBox{0, 0, 0, 0};
+    e.ink_rgb[k] = c[2] ? InkBox{(int16_t)c[0], (int16_t)c[1], (int16_t)c[2], (int16_t)c[3]} : InkBox{0, 0, 0, 0};
+  }
 }
 
 // ---- fdh_compact_atlas (the specification: include_glyphs/figdraw_hip_atlas.h): the texels of every live entry from the old levels into the new

@@ -168,6 +168,12 @@ void launch_lcd_filter_batch(hipStream_t s, const msdf::BatchGlyph* glyphs, cons
 // texels from row to row, is a coverage image; `out` takes its distance field of range `range` (1 .. 64), (sw + 2 pad) x (sh + 2 pad)
 // texels, rows packed, the encoded distance in all four bytes
 void launch_image_sdf_generate(hipStream_t s, const uint32_t* src, int sw, int sh, int src_pitch, int channel, int pad, int range, uint32_t* out);
+// fdh_put_image_device and fdh_update_image_device (include_glyphs/figdraw_hip_device_image.h; k_image_import.hip; the parameter blocks:
+// fdh_image_import.h): a source in device memory becomes levels 0 .. 5 of its atlas entry, a workgroup per 32 x 32 tile of the image, its
+// level-5 image (a texel per tile) and, for a small image, its ink boxes; the tail makes the levels behind level P.l0 of that image
+namespace image_import { struct Params; struct TailParams; }
+void launch_image_import(hipStream_t s, const image_import::Params& P);
+void launch_image_import_tail(hipStream_t s, const image_import::TailParams& P);
 // fdh_compact_atlas (include_glyphs/figdraw_hip_atlas.h; k_atlas_move.hip): the rectangles of `records` (fdh_atlas_move.h) from the levels of one
 // atlas into those of another, or from / into the dense buffers of V; `tile_record`: the record of each of the n_tiles tiles, the 1-D grid;
 // `owner`: one bit per texel of the records that share texels with a later rectangle
