@@ -72,6 +72,34 @@ IMAGE_RGBA8, IMAGE_PLANAR_F32, IMAGE_PLANAR_F16 = 0, 1, 2  # FdhDeviceImage.form
 IMAGE_STRAIGHT_ALPHA = 1                                   # FdhDeviceImage.flags
 
 
+class VideoFrame(C.Structure):  # FdhVideoFrame (include_glyphs/figdraw_hip_video_frame.h)
+    _fields_ = [("planes", C.c_void_p * 2), ("pitch_bytes", C.c_int64 * 2), ("width", C.c_int32), ("height", C.c_int32),
+                ("format", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+VIDEO_BGRA8, VIDEO_NV12, VIDEO_P010 = 0, 1, 2                                     # FdhVideoFrame.format
+VIDEO_BT601, VIDEO_BT709, VIDEO_BT2020 = 0, 1, 2                                   # FdhVideoFrame.matrix
+VIDEO_LIMITED, VIDEO_FULL = 0, 1                                                   # FdhVideoFrame.range
+VIDEO_CHROMA_LINEAR, VIDEO_STRAIGHT_ALPHA, VIDEO_IGNORE_ALPHA = 1, 2, 4            # FdhVideoFrame.flags
+
+
+def video_frame(y_ptr, uv_ptr, width, height, pitch_y, pitch_uv, format, matrix=0, range=0, flags=0) -> VideoFrame:
+    f = VideoFrame()
+    f.planes[0], f.planes[1] = y_ptr or None, uv_ptr or None
+    f.pitch_bytes[0], f.pitch_bytes[1] = int(pitch_y), int(pitch_uv)
+    f.width, f.height, f.format, f.matrix, f.range, f.flags = int(width), int(height), int(format), int(matrix), int(range), int(flags)
+    return f
+
+
+def video_coefficients(format, matrix, range):
+    """Yoff, Coff, cY, cRV, cGU, cGV, cBU of the integer YCbCr -> RGB conversion (fdh_video_coefficients): host only, no context"""
+    L = load()
+    out = (C.c_int32 * 7)()
+    if L.fdh_video_coefficients(int(format), int(matrix), int(range), out) != 0:
+        raise FigdrawHipError(-1, L.fdh_last_error().decode())
+    return tuple(out)
+
+
 def tensor_image(t, straight_alpha: bool = False) -> DeviceImage:
     """the FdhDeviceImage of a tensor: any object with data_ptr(), shape, stride(), dtype and element_size() (a torch tensor; torch is not
     imported here).  H x W x 4 uint8 is RGBA8; C x H x W (C = 1, 3, 4) or H x W of float32 / float16 is planar.  A layout that is not a row
@@ -186,6 +214,10 @@ def load():
     if hasattr(L, "fdh_put_image_device"):  # include_glyphs/figdraw_hip_device_image.h
         L.fdh_put_image_device.argtypes = [vp, C.c_int64, C.POINTER(DeviceImage), C.c_int * 4]
         L.fdh_update_image_device.argtypes = [vp, C.c_int64, C.POINTER(DeviceImage)]
+    if hasattr(L, "fdh_put_video_frame"):  # include_glyphs/figdraw_hip_video_frame.h
+        L.fdh_put_video_frame.argtypes = [vp, C.c_int64, C.POINTER(VideoFrame), C.c_int * 4]
+        L.fdh_update_video_frame.argtypes = [vp, C.c_int64, C.POINTER(VideoFrame)]
+        L.fdh_video_coefficients.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
     if hasattr(L, "fdh_compact_atlas"):  # include_glyphs/figdraw_hip_atlas.h
         L.fdh_compact_atlas.argtypes = [vp, C.c_int, C.POINTER(AtlasMoveStats)]
         L.fdh_set_atlas_keep.argtypes = [vp, C.c_int]
@@ -556,6 +588,20 @@ class HipContext:
         """new texels from device memory for an entry of the same size (fdh_update_image_device)"""
         img = DeviceImage(ptr, int(width), int(height), int(pitch_bytes), int(plane_bytes), int(format), int(channels), IMAGE_STRAIGHT_ALPHA if straight_alpha else 0, 0)
         self._ck(self.L.fdh_update_image_device(self.h, int(key), C.byref(img)))
+
+    def put_video_frame(self, key, y_ptr, uv_ptr, width, height, pitch_y, pitch_uv, format=VIDEO_NV12, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0):
+        """a decoded frame from device (or page-locked host) memory (fdh_put_video_frame, include_glyphs/figdraw_hip_video_frame.h): NV12 or
+        P010 planes at `y_ptr` and `uv_ptr`, or BGRA8 texels at `y_ptr` (uv_ptr = 0, pitch_uv = 0, matrix = range = 0); what put_image stores
+        of the converted texels, made on the device.  -> the rectangle"""
+        f = video_frame(y_ptr, uv_ptr, width, height, pitch_y, pitch_uv, format, matrix, range, flags)
+        out = (C.c_int * 4)()
+        self._ck(self.L.fdh_put_video_frame(self.h, int(key), C.byref(f), out))
+        return tuple(out)
+
+    def update_video_frame(self, key, y_ptr, uv_ptr, width, height, pitch_y, pitch_uv, format=VIDEO_NV12, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0):
+        """the next frame for an entry of the same size (fdh_update_video_frame)"""
+        f = video_frame(y_ptr, uv_ptr, width, height, pitch_y, pitch_uv, format, matrix, range, flags)
+        self._ck(self.L.fdh_update_video_frame(self.h, int(key), C.byref(f)))
 
     def put_image_tensor(self, key, tensor, straight_alpha=False):
         """put_image_device of a tensor (tensor_image: H x W x 4 uint8, or C x H x W / H x W float32 or float16).  -> the rectangle"""

@@ -15,6 +15,7 @@
 #include "../../include_glyphs/figdraw_hip_cubic.h"
 #include "../../include_glyphs/figdraw_hip_image_sdf.h"
 #include "../../include_glyphs/figdraw_hip_device_image.h"
+#include "../../include_glyphs/figdraw_hip_video_frame.h"
 #include "../../include_glyphs/figdraw_hip_atlas.h"
 
 using fdh::Context;
@@ -223,6 +224,16 @@ int fdh_put_image_device(FdhContext* c, int64_t key, const FdhDeviceImage* img, 
 }
 int fdh_update_image_device(FdhContext* c, int64_t key, const FdhDeviceImage* img) {
   return guard([&] { C(c)->update_image_device(key, img); });
+}
+// decoded video frames (include_glyphs/figdraw_hip_video_frame.h)
+int fdh_put_video_frame(FdhContext* c, int64_t key, const FdhVideoFrame* frame, int out_rect[4]) {
+  return guard([&] { C(c)->put_video_frame(key, frame, out_rect); });
+}
+int fdh_update_video_frame(FdhContext* c, int64_t key, const FdhVideoFrame* frame) {
+  return guard([&] { C(c)->update_video_frame(key, frame); });
+}
+int fdh_video_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[7]) {
+  return guard([&] { fdh::video_coefficients(format, matrix, range, out); });
 }
 int fdh_put_image_sdf_of(FdhContext* c, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) {
   return guard([&] { C(c)->put_image_sdf_of(src_key, key, channel, pad, flags, out_rect); });

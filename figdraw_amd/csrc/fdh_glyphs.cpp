@@ -12,11 +12,13 @@
 #include "fdh_kernels.h"
 #include "fdh_atlas_move.h"
 #include "fdh_image_import.h"
+#include "fdh_video_import.h"
 #include "fdh_msdf_cubic_host.h"
 
 namespace fdh {
 namespace mc = msdf::cubic;
 namespace ii = image_import;
+namespace vi = video_import;
 
 void GlyphMaker::release() {
   glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release(); glyph_src_.release(); move_tab_.release(); ink_host_.release();
@@ -351,7 +353,8 @@ void GlyphMaker::update_device_image(hipStream_t s, Atlas& atlas, int device, in
 }
 // Two launches for an image up to 2048 x 2048: k_image_import makes levels 0 .. 5, k_image_import_tail the rest from the level-5 image.
 // A larger level-5 image first takes k_minify2 / k_atlas_blit steps, as glyph_to_atlas does, until the tail's workgroup can hold it.
-// Waits for the stream once; the tiles' ink blocks are in page-locked memory by then (the kernel stores them there).  `data`: the source as the device addresses it; `wide`: its rows are 16-byte aligned.
+// Waits for the stream once; the tiles' ink blocks are in page-locked memory by then (the kernel stores them there): finish_import, which
+// import_video shares.  `data`: the source as the device addresses it; `wide`: its rows are 16-byte aligned.
 void GlyphMaker::import_image(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const FdhDeviceImage& img, const void* data, bool wide) {
   ii::Params P{};
   P.data = data; P.pitch_bytes = img.pitch_bytes; P.plane_bytes = img.plane_bytes;
@@ -364,34 +367,155 @@ void GlyphMaker::import_image(hipStream_t s, const Atlas& atlas, AtlasEntry& e, 
   for (int l = 0; l < ii::kTileLevels; l++) { P.lw[l] = (e.w + (1 << l) - 1) >> l; P.lh[l] = (e.h + (1 << l) - 1) >> l; }
   for (int l = 0; l < atlas.n_levels(); l++) P.level[l] = atlas.level(l);
   P.size = atlas.size();
-  uint32_t *cur = glyph_a_.ptr, *nxt = glyph_b_.ptr;
-  P.scratch = cur;
+  P.scratch = glyph_a_.ptr;
   P.ink_block = ink_host_.dev;
   launch_image_import(s, P);
-  int l = ii::kTileLevels - 1, cw = P.lw[l], ch = P.lh[l];
-  for (; (cw > ii::kTailMax || ch > ii::kTailMax) && l + 1 < P.n_store; std::swap(cur, nxt)) {
+  finish_import(s, atlas, e, P.n_store, P.ink != 0);
+}
+void GlyphMaker::finish_import(hipStream_t s, const Atlas& atlas, AtlasEntry& e, int n_store, bool ink) {
+  uint32_t *cur = glyph_a_.ptr, *nxt = glyph_b_.ptr;
+  int l = ii::kTileLevels - 1, cw = (e.w + (1 << l) - 1) >> l, ch = (e.h + (1 << l) - 1) >> l;
+  const int tiles = cw * ch;
+  for (; (cw > ii::kTailMax || ch > ii::kTailMax) && l + 1 < n_store; std::swap(cur, nxt)) {
     launch_minify2(s, cur, nxt, cw, ch);
     l++; cw = (cw + 1) / 2; ch = (ch + 1) / 2;
     launch_atlas_blit(s, atlas.level(l), atlas.size() >> l, e.x >> l, e.y >> l, nxt, cw, ch);
   }
-  if (l + 1 < P.n_store) {
+  if (l + 1 < n_store) {
     ii::TailParams T{};
-    T.src = cur; T.sw = cw; T.sh = ch; T.l0 = l; T.n_store = P.n_store;
-    T.x = e.x; T.y = e.y; T.size = P.size;
-    std::copy(P.level, P.level + ii::kLevels, T.level);
+    T.src = cur; T.sw = cw; T.sh = ch; T.l0 = l; T.n_store = n_store;
+    T.x = e.x; T.y = e.y; T.size = atlas.size();
+    for (int k = 0; k < atlas.n_levels(); k++) T.level[k] = atlas.level(k);
     launch_image_import_tail(s, T);
   }
   FDH_HIP(hipStreamSynchronize(s));
   FDH_HIP(hipGetLastError());
-  e.has_ink = P.ink != 0;
-  if (!P.ink) return;
+  e.has_ink = ink;
+  if (!ink) return;
   int32_t got[ii::kInkWords];
-  ii::fold_ink(ink_host_.ptr, P.lw[ii::kTileLevels - 1] * P.lh[ii::kTileLevels - 1], got);
+  ii::fold_ink(ink_host_.ptr, tiles, got);
   for (int k = 0; k < kInkLevels; k++) {  // (a box no texel grew: empty, at the origin)
     const int32_t *a = got + 4 * k, *c = got + 32 + 4 * k;
     e.ink_a[k] = a[2] ? InkBox{(int16_t)a[0], (int16_t)a[1], (int16_t)a[2], (int16_t)a[3]} : InkBox{0, 0, 0, 0};
     e.ink_rgb[k] = c[2] ? InkBox{(int16_t)c[0], (int16_t)c[1], (int16_t)c[2], (int16_t)c[3]} : InkBox{0, 0, 0, 0};
   }
+}
+
+// ---- decoded video frames (the specification: include_glyphs/figdraw_hip_video_frame.h).  put_device_image's placement, scratch, tail, wait and
+// ink boxes; the struct, its rules and the first kernel are its own.
+struct GlyphMaker::VideoSource {
+  FdhVideoFrame frame;       // the caller's, copied
+  const void* planes[2];     // as the device addresses them (a record-only context: null)
+  bool wide_y, wide_c;       // a run of four luma samples / of two chroma pairs is one load (vi::Params)
+};
+// what both calls ask of the struct: no context, no device
+static void validate_video_frame(const Refusal& bad, const FdhVideoFrame* f, bool* wide_y, bool* wide_c) {
+  if (!f || !f->planes[0]) throw bad("null frame");
+  if (f->width <= 0 || f->height <= 0) throw bad("empty frame");
+  if (f->format > FDH_VIDEO_P010) throw bad("unknown format");
+  if (f->matrix > FDH_VIDEO_BT2020) throw bad("unknown matrix");
+  if (f->range > FDH_VIDEO_FULL) throw bad("unknown range");
+  if (f->flags & ~(uint32_t)(FDH_VIDEO_CHROMA_LINEAR | FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("unknown flag");
+  if (f->reserved[0] || f->reserved[1]) throw bad("reserved must be 0");
+  const bool bgra = f->format == FDH_VIDEO_BGRA8;
+  const uint32_t alpha = f->flags & (FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA);
+  if (bgra) {
+    if (f->matrix || f->range) throw bad("matrix and range must be 0 for BGRA8");
+    if (f->planes[1] || f->pitch_bytes[1]) throw bad("BGRA8 has one plane");
+    if (f->flags & FDH_VIDEO_CHROMA_LINEAR) throw bad("FDH_VIDEO_CHROMA_LINEAR needs a chroma plane");
+    if (alpha == (FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("FDH_VIDEO_STRAIGHT_ALPHA and FDH_VIDEO_IGNORE_ALPHA exclude each other");
+  } else {
+    if (!f->planes[1]) throw bad("null chroma plane");
+    if (alpha) throw bad("the alpha flags are BGRA8's");
+  }
+  const int64_t luma = bgra ? 4 : f->format == FDH_VIDEO_P010 ? 2 : 1, pair = 2 * luma;  // the planes' element sizes
+  if ((uintptr_t)f->planes[0] % (uintptr_t)luma || f->pitch_bytes[0] % luma) throw bad("planes[0] and pitch_bytes[0] must be multiples of the element size");
+  if (f->pitch_bytes[0] < (int64_t)f->width * luma) throw bad("pitch_bytes[0] is below a row's bytes");
+  const int64_t cw = ((int64_t)f->width + 1) / 2;
+  if (!bgra) {
+    if ((uintptr_t)f->planes[1] % (uintptr_t)pair || f->pitch_bytes[1] % pair) throw bad("planes[1] and pitch_bytes[1] must be multiples of a pair's size");
+    if (f->pitch_bytes[1] < cw * pair) throw bad("pitch_bytes[1] is below a row's bytes");
+  }
+  const uintptr_t run = (uintptr_t)(4 * luma);  // four luma samples or texels; two pairs
+  *wide_y = (uintptr_t)f->planes[0] % run == 0 && f->pitch_bytes[0] % (int64_t)run == 0 && f->width >= 4;
+  *wide_c = !bgra && (uintptr_t)f->planes[1] % run == 0 && f->pitch_bytes[1] % (int64_t)run == 0 && cw >= 2;
+}
+// on a context with a device: both planes as the device addresses them, neither of them inside the atlas
+static void video_planes(const Refusal& bad, int device, const Atlas& atlas, const FdhVideoFrame& f, const void* out[2]) {
+  const int64_t cw = ((int64_t)f.width + 1) / 2, ch = ((int64_t)f.height + 1) / 2;
+  const int64_t es = f.format == FDH_VIDEO_BGRA8 ? 4 : f.format == FDH_VIDEO_P010 ? 2 : 1;
+  const int64_t bytes[2] = {(f.height - 1) * f.pitch_bytes[0] + f.width * es, (ch - 1) * f.pitch_bytes[1] + cw * 2 * es};
+  out[0] = out[1] = nullptr;
+  for (int p = 0; p < (f.format == FDH_VIDEO_BGRA8 ? 1 : 2); p++) {
+    out[p] = device_address(bad, device, f.planes[p]);
+    const uintptr_t lo = (uintptr_t)out[p], hi = lo + (uintptr_t)bytes[p];
+    for (int l = 0; l < atlas.n_levels(); l++) {
+      const uintptr_t a = (uintptr_t)atlas.level(l), side = (uintptr_t)(atlas.size() >> l);
+      if (lo < a + side * side * 4 && a < hi) throw bad("a plane lies inside the context's own atlas");
+    }
+  }
+}
+void GlyphMaker::put_video_frame(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoFrame* frame, int out_rect[4]) {
+  const Refusal bad{"put_video_frame"};
+  VideoSource src{};
+  validate_video_frame(bad, frame, &src.wide_y, &src.wide_c);
+  src.frame = *frame;
+  if (atlas.has_device()) {
+    video_planes(bad, device, atlas, src.frame, src.planes);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.frame.width, src.frame.height);
+  }
+  atlas.make_room(s, src.frame.width, src.frame.height);
+  AtlasEntry& e = atlas.place(s, key, src.frame.width, src.frame.height, out_rect);
+  if (atlas.has_device()) import_video(s, atlas, e, src);
+}
+void GlyphMaker::update_video_frame(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoFrame* frame) {
+  const Refusal bad{"update_video_frame"};
+  VideoSource src{};
+  validate_video_frame(bad, frame, &src.wide_y, &src.wide_c);
+  src.frame = *frame;
+  const AtlasEntry* old = atlas.find(key);  // (ahead of the pointers' check and the buffers; begin_update says the same again)
+  if (!old) throw bad("unknown key");
+  if (old->w != src.frame.width || old->h != src.frame.height) throw bad("size mismatch");
+  if (atlas.has_device()) {
+    video_planes(bad, device, atlas, src.frame, src.planes);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.frame.width, src.frame.height);
+  }
+  AtlasEntry& e = atlas.begin_update(bad.who, key, src.frame.width, src.frame.height);
+  e.has_ink = false;  // (the old texels' boxes; import_video measures the new ones)
+  if (atlas.has_device()) import_video(s, atlas, e, src);
+}
+// k_video_import makes levels 0 .. 5; the rest is import_image's (finish_import)
+void GlyphMaker::import_video(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const VideoSource& src) {
+  const FdhVideoFrame& f = src.frame;
+  vi::Params P{};
+  P.luma = src.planes[0]; P.chroma = src.planes[1];
+  P.pitch_y = f.pitch_bytes[0]; P.pitch_c = f.pitch_bytes[1];
+  P.w = f.width; P.h = f.height; P.cw = (f.width + 1) / 2; P.ch = (f.height + 1) / 2;
+  P.format = f.format; P.flags = f.flags;
+  P.wide_y = src.wide_y; P.wide_c = src.wide_c;
+  if (f.format != FDH_VIDEO_BGRA8) {
+    const int32_t* c = vi::kCoefficients[f.format == FDH_VIDEO_P010][f.matrix][f.range];
+    P.yoff = c[0]; P.coff = c[1]; P.cy = c[2]; P.crv = c[3]; P.cgu = c[4]; P.cgv = c[5]; P.cbu = c[6];
+  }
+  P.x = e.x; P.y = e.y;
+  atlas.each_level(e.x, e.y, e.w, e.h, [&](int, int, int, int, int) { P.n_store++; });
+  P.ink = e.w <= ii::kInkMax && e.h <= ii::kInkMax;
+  for (int l = 0; l < ii::kTileLevels; l++) { P.lw[l] = (e.w + (1 << l) - 1) >> l; P.lh[l] = (e.h + (1 << l) - 1) >> l; }
+  for (int l = 0; l < atlas.n_levels(); l++) P.level[l] = atlas.level(l);
+  P.size = atlas.size();
+  P.scratch = glyph_a_.ptr;
+  P.ink_block = ink_host_.dev;
+  launch_video_import(s, P);
+  finish_import(s, atlas, e, P.n_store, P.ink != 0);
+}
+// fdh_video_coefficients: a row of the table (fdh_video_import.h)
+void video_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[7]) {
+  const Refusal bad{"video_coefficients"};
+  if (format != FDH_VIDEO_NV12 && format != FDH_VIDEO_P010) throw bad("the format has no conversion: FDH_VIDEO_NV12 or FDH_VIDEO_P010");
+  if (matrix > FDH_VIDEO_BT2020) throw bad("unknown matrix");
+  if (range > FDH_VIDEO_FULL) throw bad("unknown range");
+  if (!out) throw bad("null pointer");
+  std::copy(vi::kCoefficients[format == FDH_VIDEO_P010][matrix][range], vi::kCoefficients[format == FDH_VIDEO_P010][matrix][range] + 7, out);
 }
 
 // ---- fdh_compact_atlas (the specification: include_glyphs/figdraw_hip_atlas.h): the texels of every live entry from the old levels into the new

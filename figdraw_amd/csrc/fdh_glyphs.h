@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include_glyphs/figdraw_hip_device_image.h"  // FdhDeviceImage
+#include "../../include_glyphs/figdraw_hip_video_frame.h"   // FdhVideoFrame
 #include "../../include_glyphs/figdraw_hip_cubic_batch.h"  // the two cubic batches; and through it figdraw_hip_cubic.h (fdh_put_glyph_outline_cubic),
                                                             // figdraw_hip_coverage.h (the coverage batch), figdraw_hip_glyphs.h (FdhGlyphOutline, FdhGlyphBatchStats)
 #include "fdh_atlas.h"
@@ -41,6 +42,10 @@ class GlyphMaker final : public AtlasMover {
   // Atlas::update_image store, of a source in device memory; `device`: the context's (on a record-only context nothing is asked of it)
   void put_device_image(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhDeviceImage* img, int out_rect[4]);
   void update_device_image(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhDeviceImage* img);
+  // fdh_put_video_frame and fdh_update_video_frame (the specification: include_glyphs/figdraw_hip_video_frame.h): the same of an NV12, P010 or
+  // BGRA8 frame
+  void put_video_frame(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoFrame* frame, int out_rect[4]);
+  void update_video_frame(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoFrame* frame);
   // fdh_compact_atlas (the specification: include_glyphs/figdraw_hip_atlas.h): the atlas's mover
   void move_entries(hipStream_t s, const AtlasView& from, const Atlas& to, const std::vector<MovedEntry>& moved, FdhAtlasMoveStats& stats) override;
   void release();  // the scratch buffers (the stream is idle)
@@ -58,6 +63,10 @@ class GlyphMaker final : public AtlasMover {
   void put_image_field(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const uint8_t* rgba, int from_x, int from_y, int channel, int pad, int range, int out_rect[4]);
   // the two device-image calls behind their validation and their placement: the launches, the wait, the entry's ink boxes
   void import_image(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const FdhDeviceImage& img, const void* data, bool wide);
+  struct VideoSource;  // a validated FdhVideoFrame as the device addresses it (fdh_glyphs.cpp)
+  void import_video(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const VideoSource& src);
+  // behind the first launch of either: the rest of the chain from the level-5 image in glyph_a_, the wait, the entry's ink boxes
+  void finish_import(hipStream_t s, const Atlas& atlas, AtlasEntry& e, int n_store, bool ink);
   // the batches: pass 1 in either format, then passes 2 and 3 of all four (the placement, the tables, the copies, `middle`'s launches, the level chain)
   void put_fields(const SegmentFormat& fmt, hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
   void put_coverage(const SegmentFormat& fmt, hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
@@ -71,8 +80,11 @@ class GlyphMaker final : public AtlasMover {
   DeviceBuf<float> glyph_lines_, glyph_acc_, glyph_edges_;  // flattened outline, area accumulators; the edge records of a distance field (fdh_msdf_host.h)
   DeviceBuf<uint32_t> glyph_tab_;  // the batches: the glyph records (msdf::BatchGlyph), the tile -> glyph words, the owner bits of the deep levels (fdh_glyph_tables.h)
   DeviceBuf<uint32_t> move_tab_;   // fdh_compact_atlas: the tables of its k_atlas_move launches (fdh_atlas_move.h)
-  PinnedBuf<int32_t> ink_host_;    // the device-image calls: the tiles' ink blocks, which the kernel stores into page-locked memory (fdh_image_import.h)
+  PinnedBuf<int32_t> ink_host_;    // the device-image and video-frame calls: the tiles' ink blocks, which the kernel stores into page-locked memory (fdh_image_import.h)
   FdhGlyphBatchStats batch_stats_ = {}, coverage_stats_ = {};  // of the last put_glyph_outlines, of the last put_glyph_coverage_batch (either in either segment format)
 };
+
+// fdh_video_coefficients (include_glyphs/figdraw_hip_video_frame.h): a row of video_import::kCoefficients; no context
+void video_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[7]);
 
 }  // namespace fdh

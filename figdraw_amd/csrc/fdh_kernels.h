@@ -174,6 +174,10 @@ void launch_image_sdf_generate(hipStream_t s, const uint32_t* src, int sw, int s
 namespace image_import { struct Params; struct TailParams; }
 void launch_image_import(hipStream_t s, const image_import::Params& P);
 void launch_image_import_tail(hipStream_t s, const image_import::TailParams& P);
+// fdh_put_video_frame and fdh_update_video_frame (include_glyphs/figdraw_hip_video_frame.h; k_video_import.hip; the parameter block:
+// fdh_video_import.h): launch_image_import for an NV12, P010 or BGRA8 frame; launch_image_import_tail finishes its chain too
+namespace video_import { struct Params; }
+void launch_video_import(hipStream_t s, const video_import::Params& P);
 // fdh_compact_atlas (include_glyphs/figdraw_hip_atlas.h; k_atlas_move.hip): the rectangles of `records` (fdh_atlas_move.h) from the levels of one
 // atlas into those of another, or from / into the dense buffers of V; `tile_record`: the record of each of the n_tiles tiles, the 1-D grid;
 // `owner`: one bit per texel of the records that share texels with a later rectangle

@@ -11,6 +11,8 @@ Second check: k_composite_tiles<0|2|4|36> are compiled with -structurizecfg-skip
 k_composite.hip), which is only sound while its draw loop nest holds no divergent branch.  The loop nest -- every backward
 branch whose range holds the draw loop's s_ff1_i32_b64 -- must therefore not write the exec mask.
 
+Third check: no v_ashr_pk_{u8,i8}_i32 (FORBIDDEN_PACK below says why; DESIGN.md section 4, "Video frames").
+
 usage: lint_isa.py <library.so> [--allow-packed] [--allow-missing]   exit status 1 if a forbidden opcode is present, a uniform-build
 kernel writes exec inside its draw loop, or one of those kernels is not in the library at all"""
 import re
@@ -22,6 +24,10 @@ import tempfile
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 FORBIDDEN = re.compile(r"\bv_pk_(fma|mul|add)_f32\b|\bv_pk_mov_b32\b")
+# v_ashr_pk_{u8,i8}_i32 (two shifted, saturated bytes into bits 0 .. 15): hipcc takes bits 16 .. 31 of the destination for zero behind it; on
+# MI355X they keep what the register held.  k_video_import's first build ORed the green sum's upper half into blue that way (DESIGN.md
+# section 4, "Video frames"): clamp in front of the shift and the compiler does not form the opcode.
+FORBIDDEN_PACK = re.compile(r"\bv_ashr_pk_[ui]8_i32\b")
 
 
 def code_objects(blob: bytes):
@@ -150,6 +156,7 @@ def main():
     blob = open(path, "rb").read()
     found = False
     bad = {}
+    bad_pack = {}
     n_inst = 0
     uniform_lines = {}
     for triple, obj in code_objects(blob):
@@ -168,6 +175,10 @@ def main():
                 if uk in kernel:  # (one entry per KERNEL: a pattern matches several instantiations -- <., ., direct> -- and their lines must not be analysed as one)
                     uniform_lines.setdefault((uk, kernel), []).append(line)
             n_inst += 1
+            m = FORBIDDEN_PACK.search(line)
+            if m:
+                bad_pack.setdefault(kernel, 0)
+                bad_pack[kernel] += 1
             m = FORBIDDEN.search(line)
             if m:
                 bad.setdefault(kernel, {}).setdefault(m.group(0), 0)
@@ -178,6 +189,11 @@ def main():
     if bad and "--allow-packed" not in sys.argv:
         print(f"lint_isa: packed-FP32 instructions in {path} (build the device side with -packed-fp32-ops):")
         for k, v in sorted(bad.items()):
+            print(f"  {k[:100]}: {v}")
+        return 1
+    if bad_pack:
+        print(f"lint_isa: v_ashr_pk_*_i32 in {path} (its destination's upper half is not zero on MI355X: clamp in front of the shift):")
+        for k, v in sorted(bad_pack.items()):
             print(f"  {k[:100]}: {v}")
         return 1
     print(f"lint_isa: {path}: {n_inst} lines of gfx950 disassembly, packed-FP32 instructions: {sum(sum(v.values()) for v in bad.values())}")
