@@ -100,6 +100,39 @@ def video_coefficients(format, matrix, range):
     return tuple(out)
 
 
+class VideoTarget(C.Structure):  # FdhVideoTarget (include_video/figdraw_hip_video_out.h)
+    _fields_ = [("planes", C.c_void_p * 2), ("pitch_bytes", C.c_int64 * 2), ("rect", C.c_int32 * 4),
+                ("format", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def video_target(y_ptr, uv_ptr, pitch_y, pitch_uv, format=VIDEO_NV12, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None) -> VideoTarget:
+    t = VideoTarget()
+    t.planes[0], t.planes[1] = y_ptr or None, uv_ptr or None
+    t.pitch_bytes[0], t.pitch_bytes[1] = int(pitch_y), int(pitch_uv)
+    t.rect[0], t.rect[1], t.rect[2], t.rect[3] = (int(v) for v in (rect if rect is not None else (0, 0, 0, 0)))
+    t.format, t.matrix, t.range, t.flags = int(format), int(matrix), int(range), int(flags)
+    return t
+
+
+def video_out_coefficients(format, matrix, range):
+    """Yoff, Coff, kYR, kYG, kYB, kUR, kUG, kUB, kVR, kVG, kVB of the integer RGB -> YCbCr conversion (fdh_video_out_coefficients): host only,
+    no context"""
+    L = load()
+    out = (C.c_int32 * 11)()
+    if L.fdh_video_out_coefficients(int(format), int(matrix), int(range), out) != 0:
+        raise FigdrawHipError(-1, L.fdh_last_error().decode())
+    return tuple(out)
+
+
+def check_video_target(target, frame_w, frame_h):
+    """every rule of fdh_read_video_frame that needs no device, for a frame of frame_w x frame_h (fdh_check_video_target): raises
+    FigdrawHipError where the call would refuse `target` (a VideoTarget, or None)"""
+    L = load()
+    code = L.fdh_check_video_target(C.byref(target) if target is not None else None, int(frame_w), int(frame_h))
+    if code != 0:
+        raise FigdrawHipError(code, L.fdh_last_error().decode())
+
+
 def tensor_image(t, straight_alpha: bool = False) -> DeviceImage:
     """the FdhDeviceImage of a tensor: any object with data_ptr(), shape, stride(), dtype and element_size() (a torch tensor; torch is not
     imported here).  H x W x 4 uint8 is RGBA8; C x H x W (C = 1, 3, 4) or H x W of float32 / float16 is planar.  A layout that is not a row
@@ -218,6 +251,10 @@ def load():
         L.fdh_put_video_frame.argtypes = [vp, C.c_int64, C.POINTER(VideoFrame), C.c_int * 4]
         L.fdh_update_video_frame.argtypes = [vp, C.c_int64, C.POINTER(VideoFrame)]
         L.fdh_video_coefficients.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
+    if hasattr(L, "fdh_read_video_frame"):  # include_video/figdraw_hip_video_out.h
+        L.fdh_read_video_frame.argtypes = [vp, C.POINTER(VideoTarget)]
+        L.fdh_check_video_target.argtypes = [C.POINTER(VideoTarget), C.c_int, C.c_int]
+        L.fdh_video_out_coefficients.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
     if hasattr(L, "fdh_compact_atlas"):  # include_glyphs/figdraw_hip_atlas.h
         L.fdh_compact_atlas.argtypes = [vp, C.c_int, C.POINTER(AtlasMoveStats)]
         L.fdh_set_atlas_keep.argtypes = [vp, C.c_int]
@@ -602,6 +639,13 @@ class HipContext:
         """the next frame for an entry of the same size (fdh_update_video_frame)"""
         f = video_frame(y_ptr, uv_ptr, width, height, pitch_y, pitch_uv, format, matrix, range, flags)
         self._ck(self.L.fdh_update_video_frame(self.h, int(key), C.byref(f)))
+
+    def read_video_frame(self, y_ptr, uv_ptr, pitch_y, pitch_uv, format=VIDEO_NV12, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None):
+        """the last frame, or its rectangle `rect` = (x, y, w, h), out as NV12 or P010 planes at `y_ptr` and `uv_ptr`, or as BGRA8 texels at
+        `y_ptr` (uv_ptr = 0, pitch_uv = 0, matrix = range = 0), in device or page-locked host memory (fdh_read_video_frame,
+        include_video/figdraw_hip_video_out.h).  The planes are complete on return."""
+        t = video_target(y_ptr, uv_ptr, pitch_y, pitch_uv, format, matrix, range, flags, rect)
+        self._ck(self.L.fdh_read_video_frame(self.h, C.byref(t)))
 
     def put_image_tensor(self, key, tensor, straight_alpha=False):
         """put_image_device of a tensor (tensor_image: H x W x 4 uint8, or C x H x W / H x W float32 or float16).  -> the rectangle"""

@@ -17,6 +17,7 @@
 #include "../../include_glyphs/figdraw_hip_device_image.h"
 #include "../../include_glyphs/figdraw_hip_video_frame.h"
 #include "../../include_glyphs/figdraw_hip_atlas.h"
+#include "../../include_video/figdraw_hip_video_out.h"
 
 using fdh::Context;
 
@@ -234,6 +235,16 @@ int fdh_update_video_frame(FdhContext* c, int64_t key, const FdhVideoFrame* fram
 }
 int fdh_video_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[7]) {
   return guard([&] { fdh::video_coefficients(format, matrix, range, out); });
+}
+// the rendered frame out as NV12, P010 or BGRA8 (include_video/figdraw_hip_video_out.h)
+int fdh_read_video_frame(FdhContext* c, const FdhVideoTarget* target) {
+  return guard([&] { C(c)->read_video_frame(target); });
+}
+int fdh_check_video_target(const FdhVideoTarget* target, int frame_w, int frame_h) {
+  return guard([&] { fdh::video_out::check_target("check_video_target", target, frame_w, frame_h); });
+}
+int fdh_video_out_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[11]) {
+  return guard([&] { fdh::video_out::coefficients(format, matrix, range, out); });
 }
 int fdh_put_image_sdf_of(FdhContext* c, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) {
   return guard([&] { C(c)->put_image_sdf_of(src_key, key, channel, pad, flags, out_rect); });

@@ -32,6 +32,7 @@
 #include "fdh_glyphs.h"       // GlyphMaker, beside it: glyphs made on the device
 #include "fdh_damage_host.h"  // DamageTracker, DamageReadback: two members of Context
 #include "fdh_retained.h"     // RetainedScene: one member of Context
+#include "fdh_video_out.h"    // video_out::read, beside it: the frame out as NV12, P010, BGRA8
 
 namespace fdh {
 
@@ -86,6 +87,7 @@ class Context : public Recorder {
 
   // readback / interop
   void read_pixels(int x, int y, int w, int h, uint8_t* out);
+  void read_video_frame(const FdhVideoTarget* target);  // (include_video/figdraw_hip_video_out.h; fdh_video_out.h)
   void frame_device_ptr(void** p, int* w, int* h, int64_t* pitch_bytes);
   void debug_read_surface(int which, uint8_t* out);
   // call recorder (fdh_record_begin / fdh_record_json): the backend-level calls the scene front-end makes, as JSON

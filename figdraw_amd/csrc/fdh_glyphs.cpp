@@ -307,11 +307,7 @@ static bool validate_device_image(const Refusal& bad, const FdhDeviceImage* img)
 // On a context with a device: the source as the device addresses it -- device memory of `device`, or page-locked host memory.  Anything
 // else (pageable memory, another device's, an address nobody has mapped) is refused, and the runtime's sticky error cleared behind it.
 static const void* device_address(const Refusal& bad, int device, const void* data) {
-  hipPointerAttribute_t attr{};
-  const hipError_t err = hipPointerGetAttributes(&attr, data);
-  (void)hipGetLastError();
-  if (err == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == device) return data;
-  if (err == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer) return attr.devicePointer;
+  if (const void* view = device_view_of(device, data)) return view;  // (fdh_memory.h)
   throw bad("the source is neither device memory of the context's device nor page-locked host memory");
 }
 // the scratch of an import, ahead of the placement as every put reserves: the level-5 image and what k_minify2 makes of it

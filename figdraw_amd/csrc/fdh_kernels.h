@@ -178,6 +178,10 @@ void launch_image_import_tail(hipStream_t s, const image_import::TailParams& P);
 // fdh_video_import.h): launch_image_import for an NV12, P010 or BGRA8 frame; launch_image_import_tail finishes its chain too
 namespace video_import { struct Params; }
 void launch_video_import(hipStream_t s, const video_import::Params& P);
+// fdh_read_video_frame (include_video/figdraw_hip_video_out.h; k_video_export.hip; the parameter block: fdh_video_export.h): the P.w x P.h
+// texels at P.src out as NV12, P010 or BGRA8 planes, a workgroup per 128 x 16 tile of them
+namespace video_export { struct Params; }
+void launch_video_export(hipStream_t s, const video_export::Params& P);
 // fdh_compact_atlas (include_glyphs/figdraw_hip_atlas.h; k_atlas_move.hip): the rectangles of `records` (fdh_atlas_move.h) from the levels of one
 // atlas into those of another, or from / into the dense buffers of V; `tile_record`: the record of each of the n_tiles tiles, the 1-D grid;
 // `owner`: one bit per texel of the records that share texels with a later rectangle

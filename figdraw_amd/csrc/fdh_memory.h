@@ -15,6 +15,18 @@ namespace fdh {
 void hip_check(hipError_t e, const char* what);
 #define FDH_HIP(x) ::fdh::hip_check((x), #x)
 
+// A caller's pointer as the device addresses it: device memory of `device` as it is, page-locked host memory as its device view; null for
+// anything else (pageable memory, another device's, an address nobody has mapped), the runtime's sticky error cleared behind the question.
+// What fdh_put_image_device, fdh_put_video_frame and fdh_read_video_frame ask of a plane.
+inline void* device_view_of(int device, const void* data) {
+  hipPointerAttribute_t attr{};
+  const hipError_t err = hipPointerGetAttributes(&attr, data);
+  (void)hipGetLastError();
+  if (err == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == device) return const_cast<void*>(data);
+  if (err == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer) return attr.devicePointer;
+  return nullptr;
+}
+
 // Fault-hunting builds (-DFDH_POISON=<byte>): every fresh device allocation is filled with that byte before its first use -- a kernel that
 // reads memory nothing has written yet then reads the same garbage every time, not what the allocation's previous owner left.
 void poison_fresh(void* p, size_t bytes);  // fdh_context.cpp

@@ -1,0 +1,120 @@
+// fdh_video_out.cpp -- fdh_read_video_frame, fdh_check_video_target and fdh_video_out_coefficients (fdh_video_out.h; the specification:
+// include_video/figdraw_hip_video_out.h).  No state: a target is checked, turned into k_video_export's parameter block and launched.
+#include "fdh_video_out.h"
+
+#include <algorithm>
+#include <string>
+
+#include "fdh_kernels.h"
+#include "fdh_memory.h"  // FDH_HIP, device_view_of
+#include "fdh_plain.h"   // Error
+#include "fdh_video_export.h"
+
+namespace fdh {
+namespace video_out {
+namespace ve = video_export;
+
+namespace {
+struct Refusal {
+  const char* who;
+  Error operator()(const std::string& what) const { return Error(FDH_ERR_INVALID, std::string(who) + ": " + what); }
+};
+// what a checked target comes to: the rectangle, and the bytes from each plane's pointer to its last element's end
+struct Layout {
+  int x, y, w, h;
+  int64_t cw, ch;
+  __int128 bytes[2];
+  bool wide_y, wide_c;  // a run of four luma samples / of two chroma pairs is one store (ve::Params)
+};
+bool overlap(uintptr_t a, __int128 a_bytes, uintptr_t b, __int128 b_bytes) { return (__int128)a < (__int128)b + b_bytes && (__int128)b < (__int128)a + a_bytes; }
+
+Layout check(const Refusal& bad, const FdhVideoTarget* t, int frame_w, int frame_h) {
+  if (!t || !t->planes[0]) throw bad("null target");
+  if (t->format > FDH_VIDEO_P010) throw bad("unknown format");
+  if (t->matrix > FDH_VIDEO_BT2020) throw bad("unknown matrix");
+  if (t->range > FDH_VIDEO_FULL) throw bad("unknown range");
+  if (t->flags & ~(uint32_t)(FDH_VIDEO_CHROMA_LINEAR | FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("unknown flag");
+  if (t->reserved[0] || t->reserved[1]) throw bad("reserved must be 0");
+  if (t->flags & FDH_VIDEO_STRAIGHT_ALPHA) throw bad("FDH_VIDEO_STRAIGHT_ALPHA is for the way in: the surface's bytes go out as stored");
+  const bool bgra = t->format == FDH_VIDEO_BGRA8;
+  if (bgra) {
+    if (t->matrix || t->range) throw bad("matrix and range must be 0 for BGRA8");
+    if (t->planes[1] || t->pitch_bytes[1]) throw bad("BGRA8 has one plane");
+    if (t->flags & FDH_VIDEO_CHROMA_LINEAR) throw bad("FDH_VIDEO_CHROMA_LINEAR needs a chroma plane");
+  } else {
+    if (!t->planes[1]) throw bad("null chroma plane");
+    if (t->flags & FDH_VIDEO_IGNORE_ALPHA) throw bad("FDH_VIDEO_IGNORE_ALPHA is BGRA8's");
+  }
+  if (frame_w <= 0 || frame_h <= 0) throw bad("empty frame");
+  Layout L{};
+  L.x = t->rect[0]; L.y = t->rect[1]; L.w = t->rect[2]; L.h = t->rect[3];
+  if (L.w <= 0 || L.h <= 0) { L.x = 0; L.y = 0; L.w = frame_w; L.h = frame_h; }
+  if (L.x < 0 || L.y < 0 || (int64_t)L.x + L.w > frame_w || (int64_t)L.y + L.h > frame_h) throw bad("rectangle outside the frame");
+  if (!bgra && ((L.x | L.y) & 1)) throw bad("the rectangle's x and y must be even for NV12 / P010");
+  const int64_t luma = bgra ? 4 : t->format == FDH_VIDEO_P010 ? 2 : 1, pair = 2 * luma;  // the planes' element sizes
+  if ((uintptr_t)t->planes[0] % (uintptr_t)luma || t->pitch_bytes[0] % luma) throw bad("planes[0] and pitch_bytes[0] must be multiples of the element size");
+  if (t->pitch_bytes[0] < (int64_t)L.w * luma) throw bad("pitch_bytes[0] is below a row's bytes");
+  L.cw = ((int64_t)L.w + 1) / 2; L.ch = ((int64_t)L.h + 1) / 2;
+  L.bytes[0] = (__int128)(L.h - 1) * t->pitch_bytes[0] + (__int128)L.w * luma;
+  if (!bgra) {
+    if ((uintptr_t)t->planes[1] % (uintptr_t)pair || t->pitch_bytes[1] % pair) throw bad("planes[1] and pitch_bytes[1] must be multiples of a pair's size");
+    if (t->pitch_bytes[1] < L.cw * pair) throw bad("pitch_bytes[1] is below a row's bytes");
+    L.bytes[1] = (__int128)(L.ch - 1) * t->pitch_bytes[1] + (__int128)L.cw * pair;
+    if (overlap((uintptr_t)t->planes[0], L.bytes[0], (uintptr_t)t->planes[1], L.bytes[1])) throw bad("the two planes overlap");
+  }
+  const uintptr_t run = (uintptr_t)(4 * luma);  // four luma samples or texels; two pairs
+  L.wide_y = (uintptr_t)t->planes[0] % run == 0 && t->pitch_bytes[0] % (int64_t)run == 0 && L.w >= 4;
+  L.wide_c = !bgra && (uintptr_t)t->planes[1] % run == 0 && t->pitch_bytes[1] % (int64_t)run == 0 && L.cw >= 2;
+  return L;
+}
+}  // namespace
+
+void check_target(const char* who, const FdhVideoTarget* t, int frame_w, int frame_h) { (void)check(Refusal{who}, t, frame_w, frame_h); }
+
+void coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[11]) {
+  const Refusal bad{"video_out_coefficients"};
+  if (format != FDH_VIDEO_NV12 && format != FDH_VIDEO_P010) throw bad("the format has no conversion: FDH_VIDEO_NV12 or FDH_VIDEO_P010");
+  if (matrix > FDH_VIDEO_BT2020) throw bad("unknown matrix");
+  if (range > FDH_VIDEO_FULL) throw bad("unknown range");
+  if (!out) throw bad("null pointer");
+  std::copy(ve::kCoefficients[format == FDH_VIDEO_P010][matrix][range], ve::kCoefficients[format == FDH_VIDEO_P010][matrix][range] + 11, out);
+}
+
+void read(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoTarget* target, const Own* own, int n_own) {
+  const Refusal bad{"read_video_frame"};
+  const Layout L = check(bad, target, W, H);
+  const FdhVideoTarget t = *target;
+  const int n_planes = t.format == FDH_VIDEO_BGRA8 ? 1 : 2;
+  void* planes[2] = {nullptr, nullptr};
+  for (int p = 0; p < n_planes; p++) {
+    planes[p] = device_view_of(device, t.planes[p]);
+    if (!planes[p]) throw bad("a plane is neither device memory of the context's device nor page-locked host memory");
+    for (int k = 0; k < n_own; k++)
+      if (own[k].base && overlap((uintptr_t)planes[p], L.bytes[p], (uintptr_t)own[k].base, (__int128)own[k].bytes))
+        throw bad(std::string("a plane overlaps the context's own ") + own[k].what);
+  }
+  if (n_planes == 2 && overlap((uintptr_t)planes[0], L.bytes[0], (uintptr_t)planes[1], L.bytes[1])) throw bad("the two planes overlap");
+  ve::Params P{};
+  P.src = surface + (size_t)L.y * W + L.x;
+  P.src_pitch = W;
+  P.w = L.w; P.h = L.h;
+  P.luma = planes[0]; P.chroma = planes[1];
+  P.pitch_y = t.pitch_bytes[0]; P.pitch_c = t.pitch_bytes[1];
+  P.format = t.format; P.flags = t.flags;
+  P.wide_src = (uintptr_t)P.src % 16 == 0 && W % 4 == 0 && L.w >= 4;
+  // (a page-locked plane's device view need not be aligned as the caller's pointer is: the question is asked of the address the kernel gets)
+  const uintptr_t run = t.format == FDH_VIDEO_BGRA8 ? 16 : t.format == FDH_VIDEO_P010 ? 8 : 4;
+  P.wide_y = L.wide_y && (uintptr_t)planes[0] % run == 0;
+  P.wide_c = L.wide_c && (uintptr_t)planes[1] % run == 0;
+  if (t.format != FDH_VIDEO_BGRA8) {
+    const int32_t* c = ve::kCoefficients[t.format == FDH_VIDEO_P010][t.matrix][t.range];
+    P.yoff = c[0]; P.coff = c[1];
+    for (int k = 0; k < 3; k++) { P.ky[k] = c[2 + k]; P.ku[k] = c[5 + k]; P.kv[k] = c[8 + k]; }
+  }
+  launch_video_export(s, P);
+  FDH_HIP(hipStreamSynchronize(s));
+  FDH_HIP(hipGetLastError());
+}
+
+}  // namespace video_out
+}  // namespace fdh

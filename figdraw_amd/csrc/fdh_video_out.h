@@ -1,0 +1,26 @@
+// fdh_video_out.h -- fdh_read_video_frame's host side (the specification: include_video/figdraw_hip_video_out.h): the rules of an
+// FdhVideoTarget, the parameter block of k_video_export and its launch.  Free functions, no state: Context::read_video_frame drains,
+// checks that there is a frame, synchronises and hands over the stream, the surface that holds the frame and what may not be written.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include_video/figdraw_hip_video_out.h"  // FdhVideoTarget
+
+namespace fdh {
+namespace video_out {
+
+// fdh_check_video_target: every rule that needs no device, for a frame of frame_w x frame_h; throws Error(FDH_ERR_INVALID, who + ": " + why)
+void check_target(const char* who, const FdhVideoTarget* t, int frame_w, int frame_h);
+// fdh_video_out_coefficients: a row of video_export::kCoefficients (fdh_video_export.h)
+void coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[11]);
+// memory of the context's that no plane may touch: a frame surface, a level of the atlas
+struct Own { const void* base; size_t bytes; const char* what; };
+// fdh_read_video_frame behind the context's part: check_target, the planes' addresses on `device` and their distance from `own`, one
+// launch of k_video_export on `s` reading the W x H surface, and the wait for it
+void read(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoTarget* t, const Own* own, int n_own);
+
+}  // namespace video_out
+}  // namespace fdh
