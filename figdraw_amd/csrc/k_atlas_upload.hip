@@ -114,6 +114,8 @@ __global__ __launch_bounds__(64) void k_minify2_batch(int l, const msdf::BatchGl
 // no FMA contraction here so that both produce the same floats).  One lane owns one pixel row: it walks every line segment in
 // order and adds the signed areas of the part inside its row to the row's accumulation cells (global scratch, w + 2 floats per
 // row: nobody else touches them), then a running sum along the row turns areas into coverage.  Out: premultiplied white.
+// The part of a line inside one row that lies left of the image (x < 0) has the whole row to its right: its share of the row piece's
+// height goes to cell 0 as it is; the part right of the image (x > w) adds nothing; the part inside is accumulated with its own share.
 __device__ __forceinline__ void raster_row_line(float* acc, int w, int y, float x0, float y0, float x1, float y1) {
 #pragma clang fp contract(off)
   if (y0 == y1) return;
@@ -123,12 +125,18 @@ __device__ __forceinline__ void raster_row_line(float* acc, int w, int y, float 
   if (!(yb > ya)) return;
   const float dxdy = (x1 - x0) / (y1 - y0);
   const float xa = x0 + (ya - y0) * dxdy, xb = x0 + (yb - y0) * dxdy;
-  const float d = (yb - ya) * dir;
+  float d = (yb - ya) * dir;
   float xl = xa < xb ? xa : xb, xr = xa < xb ? xb : xa;
-  if (xl < 0.0f) xl = 0.0f;
-  if (xr < 0.0f) xr = 0.0f;
-  if (xl > (float)w) xl = (float)w;
-  if (xr > (float)w) xr = (float)w;
+  const float fw = (float)w;
+  if (xl < 0.0f || xr > fw) {  // the row piece leaves the image: cut at x = 0 and x = w, d shared out in proportion to x
+    if (!(xr > 0.0f)) { acc[0] += d; return; }  // wholly left of the image: everything at cell 0
+    if (!(xl < fw)) return;                      // wholly right of it: nothing
+    const float span = xr - xl;
+    const float xli = xl < 0.0f ? 0.0f : xl, xri = xr > fw ? fw : xr;
+    if (xl < 0.0f) acc[0] += d * ((0.0f - xl) / span);  // the outside share first, then what the inside part adds to cell 0
+    d = d * ((xri - xli) / span);
+    xl = xli; xr = xri;
+  }
   const float x0floor = __builtin_floorf(xl);
   const int x0i = (int)x0floor;
   const float x1ceil = __builtin_ceilf(xr);
@@ -202,7 +210,8 @@ void launch_minify2_batch(hipStream_t s, int l, const msdf::BatchGlyph* glyphs, 
 // glyphs' w x h images one after the other in the two field buffers.  k_rasterize_lines SCATTERS: a lane owns a row and every line adds to
 // the cells x0i .. x1i of that row.  Here a lane owns one accumulator cell (x, y) and GATHERS: it walks the glyph's lines in the same order
 // and adds what raster_row_line would add to acc[x] of row y -- the same expressions, picked by where x lies in [x0i, x1i].  A line adds
-// to a cell at most once, so the cell's value is the same sequence of float additions and the same bits; it lives in a register and is
+// to a cell at most once -- but to cell 0 twice where its row piece crosses x = 0: the share left of the image first, then the inside
+// part's, in raster_row_line's order -- so the cell's value is the same sequence of float additions and the same bits; it lives in a register and is
 // stored once (as a float, into the glyph's region of the spare field buffer).  Cells x >= w are never read by the running sum: they do
 // not exist here.  The line index is the loop counter, the tile and the glyph depend on blockIdx alone: scalar loads, wave-uniform culls.
 __device__ __forceinline__ void coverage_cell_line(float& acc, int w, int x, int y, float x0, float y0, float x1, float y1) {
@@ -214,12 +223,18 @@ __device__ __forceinline__ void coverage_cell_line(float& acc, int w, int x, int
   if (!(yb > ya)) return;
   const float dxdy = (x1 - x0) / (y1 - y0);
   const float xa = x0 + (ya - y0) * dxdy, xb = x0 + (yb - y0) * dxdy;
-  const float d = (yb - ya) * dir;
+  float d = (yb - ya) * dir;
   float xl = xa < xb ? xa : xb, xr = xa < xb ? xb : xa;
-  if (xl < 0.0f) xl = 0.0f;
-  if (xr < 0.0f) xr = 0.0f;
-  if (xl > (float)w) xl = (float)w;
-  if (xr > (float)w) xr = (float)w;
+  const float fw = (float)w;
+  if (xl < 0.0f || xr > fw) {  // raster_row_line's cut at x = 0 and x = w
+    if (!(xr > 0.0f)) { if (x == 0) acc += d; return; }
+    if (!(xl < fw)) return;
+    const float span = xr - xl;
+    const float xli = xl < 0.0f ? 0.0f : xl, xri = xr > fw ? fw : xr;
+    if (xl < 0.0f && x == 0) acc += d * ((0.0f - xl) / span);  // cell 0's first addition of this line; the inside part's follows below
+    d = d * ((xri - xli) / span);
+    xl = xli; xr = xri;
+  }
   const float x0floor = __builtin_floorf(xl);
   const int x0i = (int)x0floor;
   const float x1ceil = __builtin_ceilf(xr);
@@ -255,7 +270,11 @@ __device__ __forceinline__ void coverage_cell_line(float& acc, int w, int x, int
 // [0, w] as raster_row_line clamps, ends more than 2 cells left of the tile or starts 9 or more cells right of its first column.  (A row's xa and
 // xb are x0 + (y - y0) * dxdy with 0 <= y - y0 <= y1 - y0: within [min(x0, x1), max(x0, x1)] but for rounding, which at that size stays below
 // 0.06; the cells a row touches end at ceil(xr) or x0i + 1 and start at floor(xl): a whole cell of slack on either side.)  Lines left
-// of a tile reach it through the running sum, not through its cells.
+// of a tile reach it through the running sum, not through its cells.  The share of a row piece that lies left of the image goes to cell
+// 0, a cell of the row's first tile (tx0 = 0), and the cull keeps such a line for that tile: any line with a point at x < 0 -- or within
+// the rounding above of it -- has a clamped range that starts at 0 (or 0.06 from it), which neither ends left of -2 nor starts at 9 or
+// beyond; so does a line wholly left of the image, whose clamped range is [0, 0].  No other tile holds cell 0.  What lies right of the
+// image adds nothing anywhere: a line wholly right of it clamps to [w, w] and may be skipped or not, to the same end.
 __global__ __launch_bounds__(64) void k_coverage_cells_batch(const float4* __restrict__ lines, const msdf::BatchGlyph* __restrict__ glyphs,
                                                              const uint32_t* __restrict__ tile_glyph, float* __restrict__ acc) {
 #pragma clang fp contract(off)

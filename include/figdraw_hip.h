@@ -257,7 +257,13 @@ FDH_API int fdh_put_glyph_image(FdhContext*, int64_t key, int width, int height,
  * pixie's fillText for it, common/textrasters/pixie_raster.nim:83-87).  segs: n x 6 floats {x0, y0, cx, cy, x1, y1} in pixel units of
  * the width x height glyph image, y down: quadratic Bezier segments with control point (cx, cy), or straight lines when cx is
  * NaN; contours closed, non-zero winding.  Sub-pixel variants are the same outline shifted by variant / steps in x
- * (pixie_raster.nim:69-72).  Coverage = exact-area scanline accumulation (curves flattened to <= 0.025 px chord error), stored
+ * (pixie_raster.nim:69-72).  Coverage = exact-area scanline accumulation: a texel is floor(255 c + 0.5), c = min(1, |the sum over the
+ * contours of the signed area of the flattened outline inside the texel's square|), to float32 rounding (under 1/16 LSB of 255 c for
+ * coordinates up to 3000).  The outline may leave the image: what lies left of it (x < 0) covers the rows to its right as if the
+ * image went on there, what lies right of it (x > width), above or below adds nothing -- the image is a window on the outline's
+ * coverage, also where an edge crosses x = 0 or x = width in the middle of a pixel row.  Curves are flattened to <= 0.025 px chord
+ * error: a quadratic into ceil(sqrt(10 dev)) chords, dev = |P0 - 2 C + P1|, at most 64, so the figure holds while dev <= 409.6 px and
+ * grows as dev / 16384 beyond (the chord ends are float32: add up to 1e-6 of the coordinates' size).  Stored
  * premultiplied white like pixie's white paint; flags as for fdh_put_glyph_image.  pixie's own texels are third-party and
  * unpinned: the oracle restates the same published algorithm and the two agree bit for bit.
  * Many coverage glyphs in one call, the same texels from launches whose number does not depend on theirs: include_glyphs/figdraw_hip_coverage.h

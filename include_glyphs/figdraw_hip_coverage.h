@@ -31,7 +31,12 @@
  * out_rects may be NULL.
  *
  * Batch limits, each FDH_ERR_INVALID: n_glyphs <= 65535; the sum of width * height <= 2^24 texels; the sum of n_segs <= 2^20; the sum of
- * flattened lines (a straight segment is one, a curve 1..64 chords of at most 0.025 px error) <= 2^22.
+ * flattened lines (a straight segment is one, a curve 1..64 chords of at most 0.025 px error while |P0 - 2 C + P1| <= 409.6 px, where the
+ * cap of 64 is reached) <= 2^22.
+ *
+ * The texels are the single put's: exact areas of the flattened outline, floor(255 c + 0.5).  The parts of an outline outside the image:
+ * what lies left of it (x < 0) covers the rows to its right, what lies right of it (x > width), above or below adds nothing, also where
+ * an edge crosses x = 0 or x = width inside a pixel row (figdraw_hip.h, at fdh_put_glyph_outline).
  *
  * A record-only context packs the rectangles, makes no texels and reports launches = 0.
  *

@@ -17,7 +17,8 @@
  *   out_rect, every level of the atlas.
  * - Without FDH_GLYPH_MTSDF (coverage): each cubic is flattened on the host into k uniform chords of at most 0.025 px error,
  *   k = ceil(sqrt(30 dev)), dev = max(|P0 - 2 P1 + P2|, |P1 - 2 P2 + P3|), 1 <= k <= 256 (the error of a chord is at most max |B''| / (8 k^2)
- *   and |B''| <= 6 dev); lines and quadratics by fdh_put_glyph_outline's own formula; then that call's rasteriser and level chain, and the LCD
+ *   and |B''| <= 6 dev: the cap of 256 is reached at dev = 0.025 * 256^2 / 0.75 = 2184.5 px, and the figure holds up to there for exact chord ends; the ends are float32 and lie up to about 1e-6 of the coordinates' size off the
+ *   curve, 0.001 px at 1000, which is more than the formula's rounding up leaves below 0.025 once dev passes a few hundred px); lines and quadratics by fdh_put_glyph_outline's own formula; then that call's rasteriser and level chain, and the LCD
  *   flags mean what they mean there.
  * - With FDH_GLYPH_MTSDF: the field of figdraw_hip.h's DISTANCE FIELDS comment, steps 1 to 5, with the rules for cubic edges below;
  *   FDH_GLYPH_SDF_RANGE(R) and FDH_GLYPH_MTSDF_CORRECT are optional and mean what they mean there.  Validation is fdh_put_glyph_outline's

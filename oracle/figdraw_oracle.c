@@ -927,7 +927,11 @@ int fo_flatten_outline(const float* segs, int n, float* lines /* 4 floats each *
   }
   return m;
 }
-/* one pixel row of the accumulation: the part of line (x0,y0)-(x1,y1) inside rows [y, y + 1) adds to acc[0 .. w] */
+/* one pixel row of the accumulation: the part of line (x0,y0)-(x1,y1) inside rows [y, y + 1), the row piece, adds to acc[0 .. w].
+ * A row piece that leaves the image is cut at x = 0 and x = w, and its height d is shared out in proportion to x (it is straight):
+ * the part with x < 0 has the whole row to its right, so its share goes to cell 0 as it is -- first, before the inside part adds
+ * to cell 0 as well; the part with x > w has nothing of the image to its right and adds nothing; the part inside is accumulated
+ * with its own share.  A piece wholly inside keeps d untouched. */
 static void raster_row_line(float* acc, int w, int y, float x0, float y0, float x1, float y1) {
   if (y0 == y1) return;
   float dir = 1.0f;
@@ -938,11 +942,16 @@ static void raster_row_line(float* acc, int w, int y, float x0, float y0, float 
   float xa = x0 + (ya - y0) * dxdy, xb = x0 + (yb - y0) * dxdy;
   float d = (yb - ya) * dir;
   float xl = xa < xb ? xa : xb, xr = xa < xb ? xb : xa;
-  /* cells left of the image take everything at cell 0 (full coverage to their right), cells right of it nothing */
-  if (xl < 0.0f) xl = 0.0f;
-  if (xr < 0.0f) xr = 0.0f;
-  if (xl > (float)w) xl = (float)w;
-  if (xr > (float)w) xr = (float)w;
+  const float fw = (float)w;
+  if (xl < 0.0f || xr > fw) {
+    if (!(xr > 0.0f)) { acc[0] += d; return; } /* wholly left of the image: everything at cell 0 */
+    if (!(xl < fw)) return;                     /* wholly right of it: nothing */
+    const float span = xr - xl;
+    const float xli = xl < 0.0f ? 0.0f : xl, xri = xr > fw ? fw : xr;
+    if (xl < 0.0f) acc[0] += d * ((0.0f - xl) / span);
+    d = d * ((xri - xli) / span);
+    xl = xli; xr = xri;
+  }
   float x0floor = floorf(xl);
   int x0i = (int)x0floor;
   float x1ceil = ceilf(xr);

@@ -1,4 +1,4 @@
-"""Inputs of the coverage batch tests (test_coverage_batch_host.py, test_coverage_batch.py; tools/coverage_bench.py uses the font sets): the
+"""Inputs of the coverage batch tests (test_coverage_batch_host.py, test_coverage_batch.py; tools/coverage_bench.py uses the font sets; coverage_hostile_cases.py holds scaled() and shapes() to exact areas): the
 94 ASCII outlines of the font fixture and what is made of them, and the smallest shapes at which the batched kernels can go wrong."""
 import os
 
@@ -60,6 +60,7 @@ def shapes():
         ("3 x 70", poly([(0.4, 0.6), (2.7, 35.2), (1.1, 69.5)]), 3, 70),       # 9 bands of one tile
         ("integer rectangle", poly([(2, 2), (10, 2), (10, 8), (2, 8)]), 12, 10),  # lines on cell borders, horizontal lines
         ("leaves on all sides", poly([(-2, 4), (5, -3), (12, 4), (5, 11)]), 10, 8),  # cells clamped to 0 and to w
+        ("leaves on all sides mid-row", poly([(-2, 4.5), (5, -2.5), (12, 4.5), (5, 11.5)]), 10, 8),  # the one above crosses x = 0 and x = w on row borders; this one inside rows
         ("covers everything", poly([(-3, -2), (14, -2.5), (13, 11), (-4, 10)]), 10, 8),
         ("sliver", poly([(4.2, 1.1), (4.5, 1.1), (4.6, 7.9), (4.3, 7.9)]), 9, 9),  # narrower than a cell: the narrow branch
         ("steep in one cell", poly([(3.1, 2.1), (3.9, 2.2), (3.4, 6.7)]), 9, 9),

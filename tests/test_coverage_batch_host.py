@@ -219,7 +219,12 @@ def shim(tmp_path_factory):
 
 def batches():
     """-> {name: [(name, segs, w, h)]}"""
-    return {"font and variants": CC.variants(), "leaving the image and shapes": CC.scaled() + CC.shapes()}
+    import coverage_hostile_cases as H
+
+    # the families of coverage_hostile_cases.py that the second batch does not hold already (test_coverage_exact_host.py holds the oracle to
+    # exact areas on them); an outline with cubics goes in as the straight lines the cubic call makes of it
+    hostile = [(f"{family}: {name}", H.as6(segs), w, h) for family, name, segs, w, h in H.cases() if family not in ("font outlines scaled 3.7 x", "shapes")]
+    return {"font and variants": CC.variants(), "leaving the image and shapes": CC.scaled() + CC.shapes(), "hostile": hostile}
 
 
 @pytest.fixture(scope="module")
@@ -229,11 +234,11 @@ def oracle_images():
 
 
 @pytest.mark.parametrize("exe", ["wave", "wave_san"])
-@pytest.mark.parametrize("batch", ["font and variants", "leaving the image and shapes"])
+@pytest.mark.parametrize("batch", ["font and variants", "leaving the image and shapes", "hostile"])
 def test_the_batched_kernels_under_a_host_shim(shim, oracle_images, exe, batch):
     """every glyph's bytes are the single launcher's and the oracle's, unfiltered and filtered; no pad between the images is written, no input is"""
     glyphs = batches()[batch]
-    assert len(glyphs) == {"font and variants": 376, "leaving the image and shapes": 94 + 17}[batch]
+    assert len(glyphs) == {"font and variants": 376, "leaving the image and shapes": 94 + 18, "hostile": 64 + 80 + 4 + 2 + 8 + 8 + 6 + 3 + 4 + 4}[batch]
     n_lines = 0
     with open(shim / f"{exe}.raw", "wb") as f:
         f.write(struct.pack("<i", len(glyphs)))
