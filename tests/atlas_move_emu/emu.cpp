@@ -1,5 +1,5 @@
-// tests/atlas_move_emu/emu.cpp -- figdraw_amd/csrc/k_atlas_move.hip and the table builder fdh_atlas_move.h under the host shim beside this
-// file; both sources come from csrc, unmodified: tests/test_atlas_move_host.py copies them here.  Built twice: emu, and emu_san (the same
+// tests/atlas_move_emu/emu.cpp -- figdraw_amd/csrc/k_atlas_move.hip and the table builder fdh_atlas_move.h under the sequential host shim
+// (tests/emu/fdh_device.h); tests/test_atlas_move_host.py copies it here, and both sources from csrc, unmodified.  Built twice: emu, and emu_san (the same
 // stand-alone program under AddressSanitizer and UBSan).
 // usage: emu case.bin out.bin
 //   case.bin: int32 from_size, to_size, n_rects, buf_in_words, buf_out_words; the levels of the old atlas, level 0 first, down to 1 x 1 (or

@@ -1,4 +1,6 @@
-// tests/codec_emu/emu.cpp -- usage: emu W H frame.raw all(0|1) stamps.raw|-   (stamp 7 = pending) -> writes dir.bin and payload.bin, prints
+// tests/codec_emu/emu.cpp -- figdraw_amd/csrc/k_damage_codec.hip under the threaded host shim (tests/emu/fdh_device_threads.h as
+// fdh_device.h, and tests/emu/fdh_damage.h, copied beside this file with the kernel and fdh_damage_read.h: tests/test_damage_stream_host.py).
+// usage: emu W H frame.raw all(0|1) stamps.raw|-   (stamp 7 = pending) -> writes dir.bin and payload.bin, prints
 // n_tiles and payload_bytes; fails when a byte past either buffer was written
 #include "k_damage_codec.hip"
 #include <cstdio>

@@ -1,6 +1,6 @@
 // tests/coverage_batch_emu/emu.cpp -- the batched coverage kernels of figdraw_amd/csrc/k_atlas_upload.hip (k_coverage_cells_batch,
 // k_coverage_sum_batch, k_lcd_filter_batch: fdh_put_glyph_coverage_batch, include_glyphs/figdraw_hip_coverage.h) against the single launchers of the
-// same file (k_rasterize_lines, k_lcd_filter), under the host shim beside this file, which tests/test_coverage_batch_host.py copies into a
+// same file (k_rasterize_lines, k_lcd_filter), under the sequential host shim (tests/emu/fdh_device.h), which tests/test_coverage_batch_host.py copies into a
 // scratch directory together with k_atlas_upload.hip and fdh_msdf_host.h from csrc, unmodified.
 // usage: emu batch.raw out.raw     batch.raw: int32 n, then per glyph int32 w, h, n_lines and n_lines x 4 float32 (x0, y0, x1, y1)
 // The images of all glyphs lie in one buffer (and its twin) with 64 words of 0xEE before the first, between two and behind the last; the

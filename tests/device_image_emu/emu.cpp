@@ -1,4 +1,4 @@
-// tests/device_image_emu/emu.cpp -- figdraw_amd/csrc/k_image_import.hip under the host shim beside this file; the kernel's source and
+// tests/device_image_emu/emu.cpp -- figdraw_amd/csrc/k_image_import.hip under the sequential host shim (tests/emu/fdh_device.h); the kernel's source and
 // fdh_image_import.h come from csrc, unmodified: tests/test_device_image_host.py copies them here.  Built twice: emu, and emu_san (the same
 // under AddressSanitizer and UBSan).  The launches are GlyphMaker::import_image's (fdh_glyphs.cpp) for a source of up to 2048 x 2048.
 // usage: emu cases.bin out.bin

@@ -1,8 +1,11 @@
-// tests/move_emu/fdh_device.h -- NOT the library's header of that name: a host shim under which figdraw_amd/csrc/k_damage_move.hip, copied
-// beside it, compiles as plain C++20 (tests/test_damage_moves_host.py).  A workgroup is 256 std::threads, __syncthreads a std::barrier
-// of 256; a wave is 64 of them with a barrier of its own, through which the wave's shuffles and ballots go (the kernels call those in
-// wave-uniform, not workgroup-uniform, control flow).  LDS and global atomics are std::atomic_ref.  It checks the kernels' algorithms,
-// barriers and bounds on a CPU; it is no device.
+// tests/emu/fdh_device_threads.h -- NOT the library's fdh_device.h: the threaded host shim, which a test copies under that name beside
+// a kernel of the damage codec (figdraw_amd/csrc/k_damage_codec.hip, k_damage_filter.hip, k_damage_move.hip, unmodified), the stand-in
+// fdh_damage.h and a driver; they compile as one plain C++20 program (tests/emu_build.py).  A workgroup is 256 std::threads, __syncthreads
+// a std::barrier of 256; a wave is 64 of them with a barrier of its own, through which the wave's shuffles and ballots go (the kernels
+// call those in wave-uniform, not always workgroup-uniform, control flow).  LDS and global atomics are std::atomic_ref.  It checks the
+// kernels' algorithms, barriers and bounds on a CPU; it is no device.
+// It stays apart from the sequential shim (fdh_device.h, lanes run again from the top until every collective point is answered) because
+// these kernels shuffle values between lanes and read what atomics return: a lane run again would add again and hand on another value.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -51,7 +54,8 @@ inline uint32_t atomicAdd(uint32_t* p, uint32_t v) { return std::atomic_ref<uint
 inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { return std::atomic_ref<unsigned long long>(*p).fetch_add(v); }
 using std::min; using std::max;
 namespace fdh { constexpr int kBin = 64; }
-// one workgroup at a time (a kernel's __shared__ objects are statics), 256 threads; a thread that returns leaves both of its barriers
+// one workgroup at a time (a kernel's __shared__ objects are statics), 256 threads; a thread that returns leaves both of its barriers,
+// and so does one that a driver's stand-in takes out of the kernel with `throw 0`
 template <typename Kernel, typename Params>
 inline void emu_launch(Kernel kern, int grid, const Params& P) {
   gridDim.x = grid;
@@ -62,7 +66,7 @@ inline void emu_launch(Kernel kern, int grid, const Params& P) {
     g_bar = &bar;
     std::vector<std::thread> th;
     for (int t = 0; t < 256; t++)
-      th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; kern(P); g_wave_bar[t >> 6]->arrive_and_drop(); bar.arrive_and_drop(); });
+      th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; try { kern(P); } catch (int) {} g_wave_bar[t >> 6]->arrive_and_drop(); bar.arrive_and_drop(); });
     for (auto& x : th) x.join();
   }
 }

@@ -1,22 +1,8 @@
-// tests/exact_emu/emu.cpp -- figdraw_amd/csrc/k_damage_filter.hip under the host shim of tests/codec_emu (its two headers are copied beside
-// this file unmodified, the kernel and fdh_damage_read.h come from csrc: tests/test_damage_exact_host.py).
+// tests/exact_emu/emu.cpp -- figdraw_amd/csrc/k_damage_filter.hip under the threaded host shim (tests/emu/fdh_device_threads.h as
+// fdh_device.h, and tests/emu/fdh_damage.h, copied beside this file; the kernel and fdh_damage_read.h come from csrc, unmodified:
+// tests/test_damage_exact_host.py).
 // usage: emu W H frame.raw mirror.raw all(0|1) stamps.raw|- fill(0|1)   (stamp 7 = pending; mirror.raw: [bin][64][64] uint32)
 // -> writes mirror_out.raw and stamps_out.raw, prints the count word; fails when a byte past the mirror or the stamps was written
-#include "fdh_device.h"
-#include "fdh_damage.h"
-namespace fdh {
-void k_damage_filter(const DamageFilterParams P);
-// one workgroup at a time (the kernel's shared array is a static), 256 threads
-inline void emu_launch(int grid, const DamageFilterParams& P) {
-  for (int b = 0; b < grid; b++) {
-    std::barrier<> bar(256);
-    g_bar = &bar;
-    std::vector<std::thread> th;
-    for (int t = 0; t < 256; t++) th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; k_damage_filter(P); bar.arrive_and_drop(); });
-    for (auto& x : th) x.join();
-  }
-}
-}
 #include "k_damage_filter.hip"
 #include <cstdio>
 #include <cstdlib>

@@ -1,4 +1,4 @@
-// tests/image_sdf_emu/emu.cpp -- figdraw_amd/csrc/k_image_sdf.hip under the host shim beside this file; the kernel's source comes from csrc,
+// tests/image_sdf_emu/emu.cpp -- figdraw_amd/csrc/k_image_sdf.hip under the sequential host shim (tests/emu/fdh_device.h); the kernel's source comes from csrc,
 // unmodified: tests/test_image_sdf_host.py copies it here.  Built three ways: emu, emu_nocull (-DFDH_IMAGE_SDF_NO_CULL=1: no exit from the
 // walk, no shortcut) and emu_san (emu under AddressSanitizer and UBSan).
 // usage: emu cases.bin fields.bin

@@ -1,13 +1,13 @@
 // tests/msdf_batch_emu/emu.cpp -- the batched kernels of figdraw_amd/csrc/k_msdf.hip (k_msdf_generate_batch, k_msdf_generate_union_batch,
 // k_msdf_correct_batch, k_msdf_correct_union_batch: fdh_put_glyph_outlines, include_glyphs/figdraw_hip_glyphs.h) against the single launchers of the
-// same file, under the host shim of tests/msdf_correct_emu, which tests/test_msdf_batch_host.py copies here as fdh_device.h together with
+// same file, under the sequential host shim of tests/emu, which tests/test_msdf_batch_host.py copies here as fdh_device.h together with
 // k_msdf.hip and fdh_msdf_host.h from csrc, unmodified.
 // usage: emu batch.raw     batch.raw: int32 n, then per glyph int32 w, h, range, n_segs and n_segs x 6 float32 (cx = NaN for a line)
 // The fields of all glyphs lie in one buffer with 64 words of 0xEE before the first, between two and behind the last; the tables and the
 // records are sized exactly.  In all four flag combinations every glyph's bytes must be the single launcher's, no pad may be written, and
 // the correction must not write its input.
 // -> prints one line per combination and "glyphs N tiles T edges E"; exit 0: all equal; 1: a difference, an overrun or a written input;
-//    3: an open contour; 4: see the wave shim
+//    3: an open contour; 4: see the shim
 #include "fdh_device.h"
 #include "k_msdf.hip"
 #include <cstdio>

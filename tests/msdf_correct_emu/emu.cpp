@@ -1,5 +1,5 @@
-// tests/msdf_correct_emu/emu.cpp -- figdraw_amd/csrc/k_msdf.hip and fdh_msdf_host.h under the host shim beside this file (the two come from
-// csrc, unmodified: tests/test_msdf_correct_host.py copies them here): k_msdf_generate, then k_msdf_correct on what it made.
+// tests/msdf_correct_emu/emu.cpp -- figdraw_amd/csrc/k_msdf.hip and fdh_msdf_host.h under the sequential host shim (tests/emu/fdh_device.h;
+// tests/test_msdf_correct_host.py copies it here, and the two from csrc, unmodified): k_msdf_generate, then k_msdf_correct on what it made.
 // usage: emu W H RANGE segs.raw [field.raw]   (segs.raw: n x 6 float32, cx = NaN for a line; field.raw: W x H RGBA8 to correct in place of
 //                                              the generated texels)
 // -> writes texels.raw (W x H RGBA8, the uncorrected field) and corrected.raw, prints the workgroups, those that walked the edges and the

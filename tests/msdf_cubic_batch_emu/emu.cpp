@@ -1,6 +1,6 @@
 // tests/msdf_cubic_batch_emu/emu.cpp -- the batched kernels of figdraw_amd/csrc/k_msdf_cubic.hip (k_msdf_generate_cubic_batch,
 // k_msdf_correct_cubic_batch: fdh_put_glyph_outlines_cubic, include_glyphs/figdraw_hip_cubic_batch.h) against the single launchers of the same file
-// and, for a glyph without a cubic, against k_msdf.hip's, under the host shim of tests/msdf_cubic_emu, which
+// and, for a glyph without a cubic, against k_msdf.hip's, under the sequential host shim of tests/emu, which
 // tests/test_msdf_cubic_batch_host.py copies here as fdh_device.h together with k_msdf_cubic.hip, fdh_msdf_cubic_host.h, k_msdf.hip and
 // fdh_msdf_host.h from csrc, unmodified.
 // usage: emu batch.raw [FIRST]   batch.raw: int32 n, then per glyph int32 w, h, range, n_segs and n_segs x 8 float32 (c2x = NaN: a

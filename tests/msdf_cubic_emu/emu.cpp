@@ -1,5 +1,5 @@
 // tests/msdf_cubic_emu/emu.cpp -- figdraw_amd/csrc/k_msdf_cubic.hip and fdh_msdf_cubic_host.h (and k_msdf.hip with fdh_msdf_host.h, to compare
-// with) under the host shim beside this file; all four come from csrc, unmodified: tests/test_msdf_cubic_host.py copies them here.
+// with) under the sequential host shim (tests/emu/fdh_device.h); tests/test_msdf_cubic_host.py copies it here, and the four from csrc, unmodified.
 // k_msdf_generate_cubic, then k_msdf_correct_cubic on what it made.
 // usage: emu W H RANGE segs.raw   (segs.raw: n x 8 float32; c2x = NaN: a quadratic, c1x = NaN: a line)
 //        emu flatten segs.raw     -> writes lines.raw, m x 4 float32: the coverage path's lines of the outline (msdf::cubic::flatten_outline)

@@ -1,5 +1,5 @@
-// tests/msdf_emu/emu.cpp -- figdraw_amd/csrc/k_msdf.hip and fdh_msdf_host.h under the host shim beside this file (the two come from csrc,
-// unmodified: tests/test_msdf_host.py copies them here).
+// tests/msdf_emu/emu.cpp -- figdraw_amd/csrc/k_msdf.hip and fdh_msdf_host.h under the sequential host shim (tests/emu/fdh_device.h, built with
+// -DEMU_LANES_ALONE: waves of one lane; tests/test_msdf_host.py copies it here, and the two from csrc, unmodified).
 // usage: emu W H RANGE segs.raw          (segs.raw: n x 6 float32, cx = NaN for a line)
 // -> writes texels.raw (W x H RGBA8) and edges.raw (the records, kEdgeFloats float32 each, then one float32: the orientation);
 //    exit 3: an open contour; exit 1: a byte outside the image was written

@@ -1,12 +1,12 @@
 // tests/msdf_overlap_emu/emu.cpp -- figdraw_amd/csrc/k_msdf.hip and fdh_msdf_host.h (from csrc, unmodified: tests/test_msdf_overlap_host.py
-// copies them here) under one of the two existing host shims, which the test copies here as fdh_device.h:
-//   tests/msdf_correct_emu/fdh_device.h   64 lanes of a wave together, with the ballot: k_msdf_generate, k_msdf_generate_union, k_msdf_correct_union
-//   tests/msdf_emu/fdh_device.h           a lane at a time, with -DEMU_GENERATE_ONLY: the two generators alone (the 16 383-contour outline,
+// copies them here) under the sequential host shim, tests/emu/fdh_device.h, which the test copies here; built two ways:
+//   as it is                              64 lanes of a wave together, with the ballot: k_msdf_generate, k_msdf_generate_union, k_msdf_correct_union
+//   -DEMU_LANES_ALONE -DEMU_GENERATE_ONLY  a lane at a time: the two generators alone (the 16 383-contour outline,
 //                                         and the -DFDH_MSDF_NO_CULL=1 build)
 // usage: emu W H RANGE segs.raw     (segs.raw: n x 6 float32, cx = NaN for a line)
 // -> writes plain.raw (k_msdf_generate), union.raw (k_msdf_generate_union) and, unless EMU_GENERATE_ONLY, corrected.raw (k_msdf_correct_union
 //    on union.raw), each W x H RGBA8; prints the contours and how many are holes;
-//    exit 3: an open contour; exit 1: a byte outside an image was written, or the correction's input was; exit 4: see the wave shim
+//    exit 3: an open contour; exit 1: a byte outside an image was written, or the correction's input was; exit 4: see fdh_device.h
 #include "fdh_device.h"
 #include "k_msdf.hip"
 #include <cstdio>

@@ -2,7 +2,6 @@
 against a fresh context, transactions, keep mode, retained scenes --, the move tables and k_atlas_move's source under a host shim
 (tests/atlas_move_emu, plain and under AddressSanitizer + UBSan) against a numpy restatement, and the C99 smoke."""
 import os
-import shutil
 import struct
 import subprocess
 
@@ -10,6 +9,7 @@ import numpy as np
 import pytest
 
 import atlas_move_cases as AC
+import emu_build
 from figdraw_amd import context
 from figdraw_amd.context import HipContext
 
@@ -260,16 +260,9 @@ def test_a_retained_scene_is_rebuilt_after_a_compaction():
 # ------------------------------------------------------------------------------------------------------------------ 5. tables and kernel
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_atlas_move.hip and fdh_atlas_move.h compiled as plain C++ under tests/atlas_move_emu -> the directory of ./emu and ./emu_san"""
-    tmp = tmp_path_factory.mktemp("atlas_move_emu")
-    for name in ("fdh_device.h", "emu.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "atlas_move_emu", name), tmp)
-    for name in ("k_atlas_move.hip", "fdh_atlas_move.h"):
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    gxx = ["g++", "-std=c++17", "-O2", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(gxx + ["-o", "emu"], cwd=tmp)
-    subprocess.check_call(gxx + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "emu_san"], cwd=tmp)
-    return tmp
+    """k_atlas_move.hip and fdh_atlas_move.h compiled as plain C++ under the sequential shim of tests/emu with the driver of
+    tests/atlas_move_emu -> the directory of ./emu and ./emu_san"""
+    return emu_build.build(tmp_path_factory, "atlas_move_emu", ("k_atlas_move.hip", "fdh_atlas_move.h"), {"emu": (), "emu_san": emu_build.SAN}, opt="-O2")
 
 
 def _levels(size):

@@ -1,11 +1,10 @@
 """A batch of coverage glyphs in one call (fdh_put_glyph_coverage_batch, include_glyphs/figdraw_hip_coverage.h), what a CPU can check: the header and the
 C ABI; on record-only contexts the packing, the validation of the whole batch before anything is placed, the growth of the atlas and a full
 atlas, each against single calls of fdh_put_glyph_outline; and the source of the three batched kernels of k_atlas_upload.hip under the host
-shim of tests/coverage_batch_emu against the single launchers of the same file and against the oracle.  Everything here is equality."""
+shim of tests/emu (tests/coverage_batch_emu) against the single launchers of the same file and against the oracle.  Everything here is equality."""
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import coverage_cases as CC
+import emu_build
 from figdraw_amd import context
 from figdraw_amd.context import FigdrawHipError, GlyphOutline, HipContext
 from oracle import oracle as O
@@ -204,17 +204,10 @@ def test_atlas_full_in_the_middle():
 # ------------------------------------------------------------------------------------------------------------------ the kernels' source on a CPU
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_atlas_upload.hip + fdh_msdf_host.h compiled as plain C++ with tests/coverage_batch_emu/emu.cpp under the shim beside it -> the directory of
-    `wave` and of `wave_san`, the same stand-alone program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("coverage_batch_emu")
-    for name in ("fdh_device.h", "emu.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "coverage_batch_emu", name), tmp)
-    for name in ("k_atlas_upload.hip", "fdh_msdf_host.h"):  # the library's own files
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    cc = ["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(cc + ["-o", "wave"], cwd=tmp)
-    subprocess.check_call(cc + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "wave_san"], cwd=tmp)
-    return tmp
+    """k_atlas_upload.hip + fdh_msdf_host.h compiled as plain C++ with tests/coverage_batch_emu/emu.cpp under the sequential shim of tests/emu ->
+    the directory of `wave` and of `wave_san`, the same stand-alone program under AddressSanitizer and UBSan"""
+    return emu_build.build(tmp_path_factory, "coverage_batch_emu", ("k_atlas_upload.hip", "fdh_msdf_host.h"), {"wave": (), "wave_san": emu_build.SAN},
+                           flags=("-ffp-contract=off",))
 
 
 def batches():

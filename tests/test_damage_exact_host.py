@@ -1,13 +1,13 @@
 """Exact damage readback, the host side (include/figdraw_hip_exact.h): the header and the C ABI, and the source of k_damage_filter itself
-under the host shim of tests/codec_emu, against numpy.  Everything here is equality of bytes and of counts."""
+under the threaded host shim of tests/emu (tests/exact_emu), against numpy.  Everything here is equality of bytes and of counts."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 from figdraw_amd import context
 from figdraw_amd.context import FigdrawHipError, HipContext
 
@@ -80,15 +80,10 @@ def _differs(a, b):
 
 
 def test_the_filter_kernel_source_under_a_host_shim(tmp_path):
-    """figdraw_amd/csrc/k_damage_filter.hip itself, compiled as C++20 against the shim headers of tests/codec_emu (threads for lanes, a
-    barrier for __syncthreads): the stamps, the count and every byte of the mirror against numpy.  No device: the GPU tests hold the
-    compiled kernel to the same."""
-    for name in ("fdh_device.h", "fdh_damage.h"):  # the shim, unmodified
-        shutil.copy(os.path.join(ROOT, "tests", "codec_emu", name), tmp_path)
-    shutil.copy(os.path.join(ROOT, "tests", "exact_emu", "emu.cpp"), tmp_path)
-    for name in ("k_damage_filter.hip", "fdh_damage_read.h"):  # the library's own files
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp_path)
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-x", "c++", "emu.cpp", "-o", "emu", "-lpthread"], cwd=tmp_path)
+    """figdraw_amd/csrc/k_damage_filter.hip itself, compiled as C++20 against the threaded shim of tests/emu (threads for lanes, a
+    barrier for __syncthreads) with the driver of tests/exact_emu: the stamps, the count and every byte of the mirror against numpy.
+    No device: the GPU tests hold the compiled kernel to the same."""
+    emu_build.build(tmp_path, "exact_emu", ("k_damage_filter.hip", "fdh_damage_read.h"), {"emu": ()}, threads=True)
     runs = [0]
 
     def run(what, frame, mirror, pending=None, fill=False):

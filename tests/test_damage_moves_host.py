@@ -1,14 +1,15 @@
 """Moved damage readback, the host side (include_readback/figdraw_hip_moves.h): the header and the C ABI, the host-only decoder
 fdh_decode_damage_moved against tests/tilemove_ref.py -- stream version 2 and the mover in numpy, written from the header's text -- and the
-source of the three kernels of k_damage_move.hip under the host shim of tests/move_emu.  Everything here is equality of bytes and of counts."""
+source of the three kernels of k_damage_move.hip under the threaded host shim of tests/emu (tests/move_emu).  Everything here is equality of
+bytes and of counts."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import tilecode_ref as T
 import tilemove_ref as M
 from conftest import load_png
@@ -300,17 +301,10 @@ def _tile_major(px):
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_damage_move.hip, fdh_damage_move.h and fdh_damage_read.h compiled as plain C++20 under tests/move_emu -> the directory of ./emu and
-    ./emu_san, the same stand-alone program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("move_emu")
-    for name in ("fdh_device.h", "fdh_damage.h", "emu.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "move_emu", name), tmp)
-    for name in ("k_damage_move.hip", "fdh_damage_move.h", "fdh_damage_read.h"):  # the library's own files
-        shutil.copy(os.path.join(CSRC, name), tmp)
-    gxx = ["g++", "-std=c++20", "-O1", "-Wno-unknown-pragmas", "-x", "c++", "emu.cpp", "-lpthread"]
-    subprocess.check_call(gxx + ["-o", "emu"], cwd=tmp)
-    subprocess.check_call(gxx + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "emu_san"], cwd=tmp)
-    return tmp
+    """k_damage_move.hip, fdh_damage_move.h and fdh_damage_read.h compiled as plain C++20 under the threaded shim of tests/emu with the
+    driver of tests/move_emu -> the directory of ./emu and ./emu_san, the same stand-alone program under AddressSanitizer and UBSan"""
+    return emu_build.build(tmp_path_factory, "move_emu", ("k_damage_move.hip", "fdh_damage_move.h", "fdh_damage_read.h"), {"emu": (), "emu_san": emu_build.SAN},
+                           flags=("-Wno-unknown-pragmas",), threads=True)
 
 
 def _through_the_shim(tmp, what, old, new, moves, pre=None, max_shift=24, exe="./emu", garbage=False):

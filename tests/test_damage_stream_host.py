@@ -3,12 +3,12 @@ fdh_decode_damage against tests/tilecode_ref.py -- a numpy encoder and decoder w
 equality of bytes and of byte counts: the code is lossless, and its sizes are rules, not measurements."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import tilecode_ref as T
 from conftest import load_png
 from figdraw_amd import context
@@ -352,13 +352,11 @@ def test_the_binding_raises_on_a_refused_stream():
 
 # ------------------------------------------------------------------------------------------------------------------ the kernel's source on a CPU
 def test_the_encode_kernel_source_under_a_host_shim(tmp_path):
-    """figdraw_amd/csrc/k_damage_codec.hip itself, compiled as C++20 against tests/codec_emu (threads for lanes, a barrier for
-    __syncthreads): every entry and payload byte against tilecode_ref.  No device: the GPU tests hold the compiled kernel to the same."""
-    for name in ("fdh_device.h", "fdh_damage.h", "emu.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "codec_emu", name), tmp_path)
-    for name in ("k_damage_codec.hip", "fdh_damage_read.h"):  # the library's own files: the kernel, and the parameter block and device code it shares
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp_path)
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-x", "c++", "emu.cpp", "-o", "emu", "-lpthread"], cwd=tmp_path)
+    """figdraw_amd/csrc/k_damage_codec.hip itself, compiled as C++20 against the threaded shim of tests/emu (threads for lanes, a barrier
+    for __syncthreads) with the driver of tests/codec_emu: every entry and payload byte against tilecode_ref.  No device: the GPU tests
+    hold the compiled kernel to the same."""
+    # the library's own files: the kernel, and the parameter block and device code it shares
+    emu_build.build(tmp_path, "codec_emu", ("k_damage_codec.hip", "fdh_damage_read.h"), {"emu": ()}, threads=True)
 
     def check(what, px, mask=None):
         h, w = px.shape

@@ -1,10 +1,9 @@
 """Images from device memory (fdh_put_image_device, fdh_update_image_device; include_glyphs/figdraw_hip_device_image.h), what a CPU can
 check: known answers for the reference tests/device_image_ref.py itself, its chain pinned on the stored levels of img1.flippy; the calls'
 rules on a record-only context and through C99; the tensor convenience's layouts; and the source of k_image_import.hip under the host shim
-of tests/device_image_emu against that reference, byte for byte."""
+of tests/emu (tests/device_image_emu) against that reference, byte for byte."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 import device_image_cases as DC
 import device_image_ref as REF
+import emu_build
 from conftest import ROOT, load_flippy_levels
 from figdraw_amd import context
 from figdraw_amd.context import DeviceImage, FigdrawHipError, HipContext
@@ -287,17 +287,9 @@ def test_tensor_layouts():
 # ------------------------------------------------------------------------------------------------------------------ 4. the kernel's source
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_image_import.hip compiled as plain C++ under tests/device_image_emu -> the directory of ./emu and ./emu_san: the same stand-alone
-    program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("device_image_emu")
-    for name in ("fdh_device.h", "emu.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "device_image_emu", name), tmp)
-    for name in ("k_image_import.hip", "fdh_image_import.h"):
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    gxx = ["g++", "-std=c++17", "-O2", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(gxx + ["-o", "emu"], cwd=tmp)
-    subprocess.check_call(gxx + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "emu_san"], cwd=tmp)
-    return tmp
+    """k_image_import.hip compiled as plain C++ under the sequential shim of tests/emu with the driver of tests/device_image_emu -> the
+    directory of ./emu and ./emu_san: the same stand-alone program under AddressSanitizer and UBSan"""
+    return emu_build.build(tmp_path_factory, "device_image_emu", ("k_image_import.hip", "fdh_image_import.h"), {"emu": (), "emu_san": emu_build.SAN}, opt="-O2")
 
 
 def place_of(i, w, h):

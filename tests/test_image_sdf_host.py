@@ -1,14 +1,14 @@
 """Distance fields from coverage images (fdh_put_image_sdf, fdh_put_image_sdf_of; include_glyphs/figdraw_hip_image_sdf.h), what a CPU can
 check: known answers for the reference tests/image_sdf_ref.py itself; the calls' rules on a record-only context and through C99; and the
-source of k_image_sdf.hip under the host shim of tests/image_sdf_emu against that reference."""
+source of k_image_sdf.hip under the host shim of tests/emu (tests/image_sdf_emu) against that reference."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import image_sdf_cases as IC
 import image_sdf_ref as REF
 from figdraw_amd import context
@@ -208,17 +208,10 @@ def test_image_sdf_abi_smoke_in_c99(tmp_path):
 # ------------------------------------------------------------------------------------------------------------------ 3. the kernel's source
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_image_sdf.hip compiled as plain C++ under tests/image_sdf_emu -> the directory of ./emu, ./emu_nocull (no exit from the walk, no
-    shortcut) and ./emu_san: the same stand-alone program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("image_sdf_emu")
-    for name in ("fdh_device.h", "emu.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "image_sdf_emu", name), tmp)
-    shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", "k_image_sdf.hip"), tmp)
-    gxx = ["g++", "-std=c++17", "-O2", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(gxx + ["-o", "emu"], cwd=tmp)
-    subprocess.check_call(gxx + ["-DFDH_IMAGE_SDF_NO_CULL=1", "-o", "emu_nocull"], cwd=tmp)
-    subprocess.check_call(gxx + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "emu_san"], cwd=tmp)
-    return tmp
+    """k_image_sdf.hip compiled as plain C++ under the sequential shim of tests/emu with the driver of tests/image_sdf_emu -> the directory
+    of ./emu, ./emu_nocull (no exit from the walk, no shortcut) and ./emu_san: the same stand-alone program under AddressSanitizer and UBSan"""
+    return emu_build.build(tmp_path_factory, "image_sdf_emu", ("k_image_sdf.hip",), {"emu": (), "emu_nocull": ("-DFDH_IMAGE_SDF_NO_CULL=1",), "emu_san": emu_build.SAN},
+                           opt="-O2")
 
 
 def through_the_shim(tmp, cases, exe="./emu"):

@@ -1,17 +1,17 @@
 """A batch of distance-field glyphs in one call (fdh_put_glyph_outlines, include_glyphs/figdraw_hip_glyphs.h), what a CPU can check: the header and the
 C ABI; on record-only contexts the packing, the validation of the whole batch before anything is placed and the growth of the atlas, each
-against single calls of fdh_put_glyph_outline; and the source of the four batched kernels of k_msdf.hip under the host shim of
-tests/msdf_correct_emu (tests/msdf_batch_emu) against the single launchers of the same file.  Everything here is equality."""
+against single calls of fdh_put_glyph_outline; and the source of the four batched kernels of k_msdf.hip under the sequential host shim of
+tests/emu (tests/msdf_batch_emu) against the single launchers of the same file.  Everything here is equality."""
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import msdf_cases as MC
 import msdf_overlap_cases as OC
 from figdraw_amd import context
@@ -182,17 +182,9 @@ def test_growth_is_what_single_calls_leave():
 # ------------------------------------------------------------------------------------------------------------------ the kernels' source on a CPU
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_msdf.hip + fdh_msdf_host.h compiled as plain C++ with tests/msdf_batch_emu/emu.cpp under the shim of tests/msdf_correct_emu (64 lanes of
+    """k_msdf.hip + fdh_msdf_host.h compiled as plain C++ with tests/msdf_batch_emu/emu.cpp under the sequential shim of tests/emu (64 lanes of
     a wave together, with the ballot) -> the directory of `wave` and of `wave_san`, the same stand-alone program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("msdf_batch_emu")
-    shutil.copy(os.path.join(ROOT, "tests", "msdf_correct_emu", "fdh_device.h"), tmp)
-    shutil.copy(os.path.join(ROOT, "tests", "msdf_batch_emu", "emu.cpp"), tmp)
-    for name in ("k_msdf.hip", "fdh_msdf_host.h"):  # the library's own files
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    cc = ["g++", "-std=c++17", "-O1", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(cc + ["-o", "wave"], cwd=tmp)
-    subprocess.check_call(cc + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "wave_san"], cwd=tmp)
-    return tmp
+    return emu_build.build(tmp_path_factory, "msdf_batch_emu", ("k_msdf.hip", "fdh_msdf_host.h"), {"wave": (), "wave_san": emu_build.SAN})
 
 
 def batches():

@@ -1,17 +1,17 @@
 """The distance-field correction pass (fdh_put_glyph_outline with FDH_GLYPH_MTSDF | FDH_GLYPH_MTSDF_CORRECT, step 5 of the specification in
 include/figdraw_hip.h), what a CPU can check: the flag on a record-only context, known answers for the reference tests/msdf_correct_ref.py
 itself, that reference in float32 against float64 on all 106 + 71 inputs (the cap is a condition on the inputs), the source of
-k_msdf_correct under the host shim of tests/msdf_correct_emu against the reference on the same inputs, and what the pass does to the
+k_msdf_correct under the host shim of tests/emu (tests/msdf_correct_emu) against the reference on the same inputs, and what the pass does to the
 reconstruction of coverage through the oracle's draw_msdf (measured: profiles/msdf.txt, section 4)."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import msdf_cases as MC
 import msdf_correct_ref as CR
 import msdf_ref as M
@@ -185,16 +185,9 @@ def test_the_reference_in_float32_stays_inside_the_cap(reference):
 # ------------------------------------------------------------------------------------------------------------------ 4. the kernel's source on a CPU
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_msdf.hip + fdh_msdf_host.h compiled as plain C++ under tests/msdf_correct_emu -> the directory of ./emu, and of ./emu_san: the same
-    stand-alone program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("msdf_correct_emu")
-    for name in ("fdh_device.h", "emu.cpp"):  # the shim
-        shutil.copy(os.path.join(ROOT, "tests", "msdf_correct_emu", name), tmp)
-    for name in ("k_msdf.hip", "fdh_msdf_host.h"):  # the library's own files
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", "-x", "c++", "emu.cpp", "-o", "emu"], cwd=tmp)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-x", "c++", "emu.cpp", "-o", "emu_san"], cwd=tmp)
-    return tmp
+    """k_msdf.hip + fdh_msdf_host.h compiled as plain C++ under the sequential shim of tests/emu with the driver of tests/msdf_correct_emu
+    -> the directory of ./emu, and of ./emu_san: the same stand-alone program under AddressSanitizer and UBSan"""
+    return emu_build.build(tmp_path_factory, "msdf_correct_emu", ("k_msdf.hip", "fdh_msdf_host.h"), {"emu": (), "emu_san": emu_build.SAN})
 
 
 def _through_the_shim(tmp, name, segs, w, h, R, exe="./emu", field=None):

@@ -1,18 +1,18 @@
 """The two batches for outlines with cubic segments (fdh_put_glyph_outlines_cubic, fdh_put_glyph_coverage_batch_cubic;
 include_glyphs/figdraw_hip_cubic_batch.h), what a CPU can check: the header and the C ABI; on record-only contexts the packing, the validation of
 the whole batch before anything is placed, the growth of the atlas and a full atlas, each against single calls of
-fdh_put_glyph_outline_cubic; and the source of the two batched kernels of k_msdf_cubic.hip under the host shim of tests/msdf_cubic_emu
+fdh_put_glyph_outline_cubic; and the source of the two batched kernels of k_msdf_cubic.hip under the sequential host shim of tests/emu
 (tests/msdf_cubic_batch_emu) against the single launchers of the same file and of k_msdf.hip.  Everything here is equality."""
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import msdf_cases as MC
 import msdf_cubic_cases as CC
 from figdraw_amd import context
@@ -317,17 +317,10 @@ def test_atlas_full_in_the_middle(coverage):
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     """k_msdf_cubic.hip + fdh_msdf_cubic_host.h + k_msdf.hip + fdh_msdf_host.h compiled as plain C++ with tests/msdf_cubic_batch_emu/emu.cpp under the
-    shim of tests/msdf_cubic_emu (64 lanes of a wave together, with the ballot) -> the directory of `wave` and of `wave_san`, the same stand-alone
+    sequential shim of tests/emu (64 lanes of a wave together, with the ballot) -> the directory of `wave` and of `wave_san`, the same stand-alone
     program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("msdf_cubic_batch_emu")
-    shutil.copy(os.path.join(ROOT, "tests", "msdf_cubic_emu", "fdh_device.h"), tmp)
-    shutil.copy(os.path.join(ROOT, "tests", "msdf_cubic_batch_emu", "emu.cpp"), tmp)
-    for name in ("k_msdf_cubic.hip", "fdh_msdf_cubic_host.h", "k_msdf.hip", "fdh_msdf_host.h"):  # the library's own files
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    cc = ["g++", "-std=c++17", "-O1", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(cc + ["-o", "wave"], cwd=tmp)
-    subprocess.check_call(cc + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "wave_san"], cwd=tmp)
-    return tmp
+    return emu_build.build(tmp_path_factory, "msdf_cubic_batch_emu", ("k_msdf_cubic.hip", "fdh_msdf_cubic_host.h", "k_msdf.hip", "fdh_msdf_host.h"),
+                           {"wave": (), "wave_san": emu_build.SAN})
 
 
 def emulated_batch():

@@ -1,16 +1,16 @@
 """Glyph outlines with cubic segments (fdh_put_glyph_outline_cubic, include_glyphs/figdraw_hip_cubic.h), what a CPU can check: the call's
 rules on a record-only context and through C99; known answers for the reference tests/msdf_cubic_ref.py itself; the inputs of
 msdf_cubic_cases.py against the cap (the float32 reference against the float64 one); the source of k_msdf_cubic.hip and
-fdh_msdf_cubic_host.h under the host shim of tests/msdf_cubic_emu against that reference; and the host's flattening for the coverage path."""
+fdh_msdf_cubic_host.h under the host shim of tests/emu (tests/msdf_cubic_emu) against that reference; and the host's flattening for the coverage path."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import msdf_cases as MC
 import msdf_cubic_cases as CC
 import msdf_cubic_ref as R
@@ -215,18 +215,11 @@ def test_the_reference_in_float32_stays_inside_the_cap(reference):
 # ------------------------------------------------------------------------------------------------------------------ 3. the kernels' source on a CPU
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_msdf_cubic.hip + fdh_msdf_cubic_host.h (and k_msdf.hip + fdh_msdf_host.h) compiled as plain C++ under tests/msdf_cubic_emu -> the
-    directory of ./emu, ./emu_nocull (every tile walks every edge) and ./emu_san: the same stand-alone program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("msdf_cubic_emu")
-    for name in ("fdh_device.h", "emu.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "msdf_cubic_emu", name), tmp)
-    for name in ("k_msdf_cubic.hip", "fdh_msdf_cubic_host.h", "k_msdf.hip", "fdh_msdf_host.h"):
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    gxx = ["g++", "-std=c++17", "-O1", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(gxx + ["-o", "emu"], cwd=tmp)
-    subprocess.check_call(gxx + ["-DFDH_MSDF_NO_CULL=1", "-o", "emu_nocull"], cwd=tmp)
-    subprocess.check_call(gxx + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "emu_san"], cwd=tmp)
-    return tmp
+    """k_msdf_cubic.hip + fdh_msdf_cubic_host.h (and k_msdf.hip + fdh_msdf_host.h) compiled as plain C++ under the sequential shim of tests/emu
+    with the driver of tests/msdf_cubic_emu -> the directory of ./emu, ./emu_nocull (every tile walks every edge) and ./emu_san: the same
+    stand-alone program under AddressSanitizer and UBSan"""
+    return emu_build.build(tmp_path_factory, "msdf_cubic_emu", ("k_msdf_cubic.hip", "fdh_msdf_cubic_host.h", "k_msdf.hip", "fdh_msdf_host.h"),
+                           {"emu": (), "emu_nocull": ("-DFDH_MSDF_NO_CULL=1",), "emu_san": emu_build.SAN})
 
 
 def _through_the_shim(tmp, name, segs, w, h, Rr, exe="./emu"):

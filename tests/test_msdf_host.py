@@ -1,17 +1,17 @@
 """Distance-field generation (fdh_put_glyph_outline with FDH_GLYPH_MTSDF), what a CPU can check: the flag on a record-only context, known
 answers for the reference tests/msdf_ref.py itself, the source of k_msdf_generate and fdh_msdf_host.h under the host shim of
-tests/msdf_emu against that reference on all 94 + 12 inputs, the sign of the field against the winding test, the same on the hostile
+tests/emu (tests/msdf_emu) against that reference on all 94 + 12 inputs, the sign of the field against the winding test, the same on the hostile
 outlines of msdf_cases.hostile_inputs(), and how well the field reconstructs coverage through the oracle's draw_msdf (measured:
 profiles/msdf.txt)."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import msdf_cases as MC
 import msdf_ref as M
 from figdraw_amd.context import HipContext
@@ -141,19 +141,14 @@ def test_reference_known_answers():
 # ------------------------------------------------------------------------------------------------------------------ 3 - 5. the kernel's source on a CPU
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_msdf.hip + fdh_msdf_host.h compiled as plain C++, with and without tile culling -> the directory of ./emu and ./emu_nocull"""
-    tmp = tmp_path_factory.mktemp("msdf_emu")
-    for name in ("fdh_device.h", "emu.cpp"):  # the shim
-        shutil.copy(os.path.join(ROOT, "tests", "msdf_emu", name), tmp)
-    for name in ("k_msdf.hip", "fdh_msdf_host.h"):  # the library's own files
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", "-x", "c++", "emu.cpp", "-o", "emu"], cwd=tmp)
+    """k_msdf.hip + fdh_msdf_host.h compiled as plain C++ under the sequential shim of tests/emu with waves of one lane, with and without
+    tile culling -> the directory of ./emu and ./emu_nocull"""
+    # emu_nocull: the build without tile culling (tools/msdf_bench.py's second library): culling must not change a texel
+    tmp = emu_build.build(tmp_path_factory, "msdf_emu", ("k_msdf.hip", "fdh_msdf_host.h"), {"emu": (), "emu_nocull": ("-DFDH_MSDF_NO_CULL=1",)}, flags=("-DEMU_LANES_ALONE",))
     # fdh_msdf_host.h compiles standalone
     (tmp / "alone.cpp").write_text('#include "fdh_msdf_host.h"\nint main() { fdh::msdf::Shape s; return fdh::msdf::build_shape(nullptr, 0, &s) ? 0 : 1; }\n')
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "alone.cpp", "-o", "alone"], cwd=tmp)
     assert subprocess.run(["./alone"], cwd=tmp).returncode == 0
-    # the build without tile culling (tools/msdf_bench.py's second library): culling must not change a texel
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", "-DFDH_MSDF_NO_CULL=1", "-x", "c++", "emu.cpp", "-o", "emu_nocull"], cwd=tmp)
     return tmp
 
 

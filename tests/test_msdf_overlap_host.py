@@ -2,17 +2,17 @@
 specification in include/figdraw_hip.h), what a CPU can check: the flag on a record-only context; the reference tests/msdf_overlap_ref.py
 itself -- its sign against non-zero winding on the 16 overlapping outlines of msdf_overlap_cases.py, against msdf_ref on the font set, on
 single contours, under another contour order, in float32 against float64 --; and the source of k_msdf_generate_union and
-k_msdf_correct_union with fdh_msdf_host.h under the host shims of tests/msdf_emu and tests/msdf_correct_emu (tests/msdf_overlap_emu) against
-that reference."""
+k_msdf_correct_union with fdh_msdf_host.h under the sequential host shim of tests/emu, with a wave's ballot and with waves of one lane
+(tests/msdf_overlap_emu), against that reference."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import msdf_cases as MC
 import msdf_correct_ref as CR
 import msdf_overlap_cases as OC
@@ -180,23 +180,13 @@ def test_what_step_6_does_not_cover():
 # ------------------------------------------------------------------------------------------------------------------ 3. the kernels' source on a CPU
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_msdf.hip + fdh_msdf_host.h compiled as plain C++ with tests/msdf_overlap_emu/emu.cpp -> {program: its directory}: `wave` under the shim
-    of tests/msdf_correct_emu (and `wave_san`: the same stand-alone program under AddressSanitizer and UBSan), `lane` and `lane_nocull` under
-    the shim of tests/msdf_emu (the generators only)"""
-    dirs = {}
-    for tag, header in (("wave", "msdf_correct_emu"), ("lane", "msdf_emu")):
-        tmp = tmp_path_factory.mktemp("msdf_overlap_emu_" + tag)
-        shutil.copy(os.path.join(ROOT, "tests", header, "fdh_device.h"), tmp)
-        shutil.copy(os.path.join(ROOT, "tests", "msdf_overlap_emu", "emu.cpp"), tmp)
-        for name in ("k_msdf.hip", "fdh_msdf_host.h"):  # the library's own files
-            shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-        dirs[tag] = tmp
-    cc = ["g++", "-std=c++17", "-O1", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(cc + ["-o", "wave"], cwd=dirs["wave"])
-    subprocess.check_call(cc + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "wave_san"], cwd=dirs["wave"])
-    subprocess.check_call(cc + ["-DEMU_GENERATE_ONLY", "-o", "lane"], cwd=dirs["lane"])
-    subprocess.check_call(cc + ["-DEMU_GENERATE_ONLY", "-DFDH_MSDF_NO_CULL=1", "-o", "lane_nocull"], cwd=dirs["lane"])
-    return {"wave": dirs["wave"], "wave_san": dirs["wave"], "lane": dirs["lane"], "lane_nocull": dirs["lane"]}
+    """k_msdf.hip + fdh_msdf_host.h compiled as plain C++ with tests/msdf_overlap_emu/emu.cpp under the sequential shim of tests/emu ->
+    {program: its directory}: `wave` with the ballot (and `wave_san`: the same stand-alone program under AddressSanitizer and UBSan), `lane`
+    and `lane_nocull` with waves of one lane (-DEMU_LANES_ALONE: the generators only)"""
+    csrc = ("k_msdf.hip", "fdh_msdf_host.h")
+    wave = emu_build.build(tmp_path_factory, "msdf_overlap_emu", csrc, {"wave": (), "wave_san": emu_build.SAN})
+    lane = emu_build.build(tmp_path_factory, "msdf_overlap_emu", csrc, {"lane": (), "lane_nocull": ("-DFDH_MSDF_NO_CULL=1",)}, flags=("-DEMU_LANES_ALONE", "-DEMU_GENERATE_ONLY"))
+    return {"wave": wave, "wave_san": wave, "lane": lane, "lane_nocull": lane}
 
 
 def _through_the_shim(shim, exe, name, segs, w, h, R):

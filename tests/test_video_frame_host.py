@@ -1,15 +1,15 @@
 """Decoded video frames (fdh_put_video_frame, fdh_update_video_frame, fdh_video_coefficients; include_glyphs/figdraw_hip_video_frame.h), what a
 CPU can check: the coefficients against their derivation from the standards' constants; known answers of the reference
 tests/video_frame_ref.py; the integer rule against float64 within the bound the header derives; the calls' rules on a record-only context
-and through C99; and the source of k_video_import.hip under the host shim of tests/video_frame_emu against the reference, byte for byte."""
+and through C99; and the source of k_video_import.hip under the host shim of tests/emu (tests/video_frame_emu) against the reference, byte for byte."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import video_frame_cases as VC
 import video_frame_ref as REF
 from conftest import GOLDEN, ROOT
@@ -276,17 +276,10 @@ def test_video_frame_abi_smoke_in_c99(tmp_path):
 # ------------------------------------------------------------------------------------------------------------------ 3. the kernel's source
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_video_import.hip (and k_image_import.hip, for the tail) compiled as plain C++ under tests/video_frame_emu -> the directory of ./emu
-    and ./emu_san: the same stand-alone program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("video_frame_emu")
-    for name in ("fdh_device.h", "emu.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "video_frame_emu", name), tmp)
-    for name in ("k_video_import.hip", "fdh_video_import.h", "k_image_import.hip", "fdh_image_import.h"):
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    gxx = ["g++", "-std=c++17", "-O2", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(gxx + ["-o", "emu"], cwd=tmp)
-    subprocess.check_call(gxx + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "emu_san"], cwd=tmp)
-    return tmp
+    """k_video_import.hip (and k_image_import.hip, for the tail) compiled as plain C++ under the sequential shim of tests/emu with the driver
+    of tests/video_frame_emu -> the directory of ./emu and ./emu_san: the same stand-alone program under AddressSanitizer and UBSan"""
+    return emu_build.build(tmp_path_factory, "video_frame_emu", ("k_video_import.hip", "fdh_video_import.h", "k_image_import.hip", "fdh_image_import.h"),
+                           {"emu": (), "emu_san": emu_build.SAN}, opt="-O2")
 
 
 def place_of(i, w, h):

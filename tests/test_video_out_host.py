@@ -1,16 +1,16 @@
 """The rendered frame out as NV12, P010 or BGRA8 (fdh_read_video_frame, fdh_check_video_target, fdh_video_out_coefficients;
 include_video/figdraw_hip_video_out.h), what a CPU can check: the coefficients against their derivation from the standards' constants; known
 answers of the reference tests/video_out_ref.py; the integer rule against float64 within the bound the header derives; the target's rules
-without a device and through C99; the source of k_video_export.hip under the host shim of tests/video_out_emu against the reference, byte
+without a device and through C99; the source of k_video_export.hip under the host shim of tests/emu (tests/video_out_emu) against the reference, byte
 for byte, padding included; and what a round trip through fdh_put_video_frame's reference loses."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import video_frame_ref as IN
 import video_out_cases as VC
 import video_out_ref as REF
@@ -312,17 +312,9 @@ def test_video_out_abi_smoke_in_c99(tmp_path):
 # ------------------------------------------------------------------------------------------------------------------ 3. the kernel's source
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    """k_video_export.hip compiled as plain C++ under tests/video_out_emu -> the directory of ./emu and ./emu_san: the same stand-alone
-    program under AddressSanitizer and UBSan"""
-    tmp = tmp_path_factory.mktemp("video_out_emu")
-    for name in ("fdh_device.h", "emu.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "video_out_emu", name), tmp)
-    for name in ("k_video_export.hip", "fdh_video_export.h"):
-        shutil.copy(os.path.join(ROOT, "figdraw_amd", "csrc", name), tmp)
-    gxx = ["g++", "-std=c++17", "-O2", "-w", "-x", "c++", "emu.cpp"]
-    subprocess.check_call(gxx + ["-o", "emu"], cwd=tmp)
-    subprocess.check_call(gxx + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", "emu_san"], cwd=tmp)
-    return tmp
+    """k_video_export.hip compiled as plain C++ under the sequential shim of tests/emu with the driver of tests/video_out_emu -> the
+    directory of ./emu and ./emu_san: the same stand-alone program under AddressSanitizer and UBSan"""
+    return emu_build.build(tmp_path_factory, "video_out_emu", ("k_video_export.hip", "fdh_video_export.h"), {"emu": (), "emu_san": emu_build.SAN}, opt="-O2")
 
 
 def through_the_shim(tmp, cases, exe):

@@ -1,4 +1,4 @@
-// tests/video_frame_emu/emu.cpp -- figdraw_amd/csrc/k_video_import.hip under the host shim beside this file, with k_image_import.hip for
+// tests/video_frame_emu/emu.cpp -- figdraw_amd/csrc/k_video_import.hip under the sequential host shim (tests/emu/fdh_device.h), with k_image_import.hip for
 // the tail kernel; the kernels' sources and their two parameter headers come from csrc, unmodified: tests/test_video_frame_host.py copies
 // them here.  Built twice: emu, and emu_san (the same under AddressSanitizer and UBSan).  The launches are GlyphMaker::import_video's
 // (fdh_glyphs.cpp) for a frame of up to 2048 x 2048.

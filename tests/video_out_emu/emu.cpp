@@ -1,4 +1,4 @@
-// tests/video_out_emu/emu.cpp -- figdraw_amd/csrc/k_video_export.hip under the host shim beside this file; the kernel's source and its
+// tests/video_out_emu/emu.cpp -- figdraw_amd/csrc/k_video_export.hip under the sequential host shim (tests/emu/fdh_device.h); the kernel's source and its
 // parameter header come from csrc, unmodified: tests/test_video_out_host.py copies them here.  Built twice: emu, and emu_san (the same
 // under AddressSanitizer and UBSan, which also refuses a wide load or store at an address that is no multiple of its size).  The
 // parameter block is filled as video_out::read fills it (fdh_video_out.cpp).
