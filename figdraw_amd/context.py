@@ -133,6 +133,46 @@ def check_video_target(target, frame_w, frame_h):
         raise FigdrawHipError(code, L.fdh_last_error().decode())
 
 
+class VideoPlanes(C.Structure):  # FdhVideoPlanes (include_video/figdraw_hip_video_planar.h)
+    _fields_ = [("planes", C.c_void_p * 3), ("pitch_bytes", C.c_int64 * 3), ("width", C.c_int32), ("height", C.c_int32),
+                ("format", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class VideoPlanesTarget(C.Structure):  # FdhVideoPlanesTarget
+    _fields_ = [("planes", C.c_void_p * 3), ("pitch_bytes", C.c_int64 * 3), ("rect", C.c_int32 * 4),
+                ("format", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+VIDEO_I420, VIDEO_I010, VIDEO_I444, VIDEO_I410 = 3, 4, 5, 6                        # FdhVideoPlanes.format, FdhVideoPlanesTarget.format
+
+
+def video_planes(ptrs, width, height, pitches, format=VIDEO_I420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0) -> VideoPlanes:
+    """ptrs, pitches: of Y, Cb, Cr"""
+    f = VideoPlanes()
+    for p in (0, 1, 2):
+        f.planes[p], f.pitch_bytes[p] = ptrs[p] or None, int(pitches[p])
+    f.width, f.height, f.format, f.matrix, f.range, f.flags = int(width), int(height), int(format), int(matrix), int(range), int(flags)
+    return f
+
+
+def video_planes_target(ptrs, pitches, format=VIDEO_I420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None) -> VideoPlanesTarget:
+    t = VideoPlanesTarget()
+    for p in (0, 1, 2):
+        t.planes[p], t.pitch_bytes[p] = ptrs[p] or None, int(pitches[p])
+    t.rect[0], t.rect[1], t.rect[2], t.rect[3] = (int(v) for v in (rect if rect is not None else (0, 0, 0, 0)))
+    t.format, t.matrix, t.range, t.flags = int(format), int(matrix), int(range), int(flags)
+    return t
+
+
+def check_video_planes_target(target, frame_w, frame_h):
+    """every rule of fdh_read_video_planes that needs no device, for a frame of frame_w x frame_h (fdh_check_video_planes_target): raises
+    FigdrawHipError where the call would refuse `target` (a VideoPlanesTarget, or None)"""
+    L = load()
+    code = L.fdh_check_video_planes_target(C.byref(target) if target is not None else None, int(frame_w), int(frame_h))
+    if code != 0:
+        raise FigdrawHipError(code, L.fdh_last_error().decode())
+
+
 def tensor_image(t, straight_alpha: bool = False) -> DeviceImage:
     """the FdhDeviceImage of a tensor: any object with data_ptr(), shape, stride(), dtype and element_size() (a torch tensor; torch is not
     imported here).  H x W x 4 uint8 is RGBA8; C x H x W (C = 1, 3, 4) or H x W of float32 / float16 is planar.  A layout that is not a row
@@ -255,6 +295,11 @@ def load():
         L.fdh_read_video_frame.argtypes = [vp, C.POINTER(VideoTarget)]
         L.fdh_check_video_target.argtypes = [C.POINTER(VideoTarget), C.c_int, C.c_int]
         L.fdh_video_out_coefficients.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
+    if hasattr(L, "fdh_put_video_planes"):  # include_video/figdraw_hip_video_planar.h
+        L.fdh_put_video_planes.argtypes = [vp, C.c_int64, C.POINTER(VideoPlanes), C.c_int * 4]
+        L.fdh_update_video_planes.argtypes = [vp, C.c_int64, C.POINTER(VideoPlanes)]
+        L.fdh_read_video_planes.argtypes = [vp, C.POINTER(VideoPlanesTarget)]
+        L.fdh_check_video_planes_target.argtypes = [C.POINTER(VideoPlanesTarget), C.c_int, C.c_int]
     if hasattr(L, "fdh_compact_atlas"):  # include_glyphs/figdraw_hip_atlas.h
         L.fdh_compact_atlas.argtypes = [vp, C.c_int, C.POINTER(AtlasMoveStats)]
         L.fdh_set_atlas_keep.argtypes = [vp, C.c_int]
@@ -646,6 +691,27 @@ class HipContext:
         include_video/figdraw_hip_video_out.h).  The planes are complete on return."""
         t = video_target(y_ptr, uv_ptr, pitch_y, pitch_uv, format, matrix, range, flags, rect)
         self._ck(self.L.fdh_read_video_frame(self.h, C.byref(t)))
+
+    def put_video_planes(self, key, ptrs, width, height, pitches, format=VIDEO_I420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0):
+        """a three-plane frame from device (or page-locked host) memory (fdh_put_video_planes, include_video/figdraw_hip_video_planar.h):
+        I420, I010, I444 or I410; `ptrs` and `pitches` of Y, Cb, Cr (YV12: the chroma pointers swapped); what put_image stores of the
+        converted texels, made on the device.  -> the rectangle"""
+        f = video_planes(ptrs, width, height, pitches, format, matrix, range, flags)
+        out = (C.c_int * 4)()
+        self._ck(self.L.fdh_put_video_planes(self.h, int(key), C.byref(f), out))
+        return tuple(out)
+
+    def update_video_planes(self, key, ptrs, width, height, pitches, format=VIDEO_I420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0):
+        """the next frame for an entry of the same size (fdh_update_video_planes)"""
+        f = video_planes(ptrs, width, height, pitches, format, matrix, range, flags)
+        self._ck(self.L.fdh_update_video_planes(self.h, int(key), C.byref(f)))
+
+    def read_video_planes(self, ptrs, pitches, format=VIDEO_I420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None):
+        """the last frame, or its rectangle `rect` = (x, y, w, h), out as the three planes Y, Cb, Cr of I420, I010, I444 or I410 at `ptrs`,
+        in device or page-locked host memory (fdh_read_video_planes, include_video/figdraw_hip_video_planar.h).  The planes are complete
+        on return."""
+        t = video_planes_target(ptrs, pitches, format, matrix, range, flags, rect)
+        self._ck(self.L.fdh_read_video_planes(self.h, C.byref(t)))
 
     def put_image_tensor(self, key, tensor, straight_alpha=False):
         """put_image_device of a tensor (tensor_image: H x W x 4 uint8, or C x H x W / H x W float32 or float16).  -> the rectangle"""

@@ -18,6 +18,7 @@
 #include "../../include_glyphs/figdraw_hip_video_frame.h"
 #include "../../include_glyphs/figdraw_hip_atlas.h"
 #include "../../include_video/figdraw_hip_video_out.h"
+#include "../../include_video/figdraw_hip_video_planar.h"
 
 using fdh::Context;
 
@@ -245,6 +246,19 @@ int fdh_check_video_target(const FdhVideoTarget* target, int frame_w, int frame_
 }
 int fdh_video_out_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[11]) {
   return guard([&] { fdh::video_out::coefficients(format, matrix, range, out); });
+}
+// three-plane video in and out: I420, I010, I444, I410 (include_video/figdraw_hip_video_planar.h)
+int fdh_put_video_planes(FdhContext* c, int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) {
+  return guard([&] { C(c)->put_video_planes(key, frame, out_rect); });
+}
+int fdh_update_video_planes(FdhContext* c, int64_t key, const FdhVideoPlanes* frame) {
+  return guard([&] { C(c)->update_video_planes(key, frame); });
+}
+int fdh_read_video_planes(FdhContext* c, const FdhVideoPlanesTarget* target) {
+  return guard([&] { C(c)->read_video_planes(target); });
+}
+int fdh_check_video_planes_target(const FdhVideoPlanesTarget* target, int frame_w, int frame_h) {
+  return guard([&] { fdh::video_out::check_planes_target("check_video_planes_target", target, frame_w, frame_h); });
 }
 int fdh_put_image_sdf_of(FdhContext* c, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) {
   return guard([&] { C(c)->put_image_sdf_of(src_key, key, channel, pad, flags, out_rect); });

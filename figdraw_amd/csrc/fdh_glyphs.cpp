@@ -13,12 +13,14 @@
 #include "fdh_atlas_move.h"
 #include "fdh_image_import.h"
 #include "fdh_video_import.h"
+#include "fdh_video_planar.h"
 #include "fdh_msdf_cubic_host.h"
 
 namespace fdh {
 namespace mc = msdf::cubic;
 namespace ii = image_import;
 namespace vi = video_import;
+namespace vp = video_planar;
 
 void GlyphMaker::release() {
   glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release(); glyph_src_.release(); move_tab_.release(); ink_host_.release();
@@ -512,6 +514,102 @@ void video_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_
   if (range > FDH_VIDEO_FULL) throw bad("unknown range");
   if (!out) throw bad("null pointer");
   std::copy(vi::kCoefficients[format == FDH_VIDEO_P010][matrix][range], vi::kCoefficients[format == FDH_VIDEO_P010][matrix][range] + 7, out);
+}
+
+// ---- three-plane video frames (the specification: include_video/figdraw_hip_video_planar.h).  put_video_frame's steps; the struct, its
+// rules and the first kernel are its own.
+struct GlyphMaker::PlanarSource {
+  FdhVideoPlanes frame;      // the caller's, copied
+  const void* planes[3];     // as the device addresses them (a record-only context: null)
+  bool wide[3];              // a run of plane p is one load (vp::InParams)
+};
+// what both calls ask of the struct: no context, no device
+static void validate_video_planes(const Refusal& bad, const FdhVideoPlanes* f, bool wide[3]) {
+  if (!f || !f->planes[0] || !f->planes[1] || !f->planes[2]) throw bad("null frame or plane");
+  if (f->width <= 0 || f->height <= 0) throw bad("empty frame");
+  if (f->format < FDH_VIDEO_I420 || f->format > FDH_VIDEO_I410) throw bad("unknown format");
+  if (f->matrix > FDH_VIDEO_BT2020) throw bad("unknown matrix");
+  if (f->range > FDH_VIDEO_FULL) throw bad("unknown range");
+  if (f->flags & ~(uint32_t)(FDH_VIDEO_CHROMA_LINEAR | FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("unknown flag");
+  if (f->reserved[0] || f->reserved[1]) throw bad("reserved must be 0");
+  if (f->flags & (FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("the alpha flags are BGRA8's");
+  const bool full = vp::full_chroma(f->format);
+  if (full && (f->flags & FDH_VIDEO_CHROMA_LINEAR)) throw bad("FDH_VIDEO_CHROMA_LINEAR is for I420 / I010: a 4:4:4 frame has a chroma sample per texel");
+  const int64_t es = vp::ten_bit(f->format) ? 2 : 1;  // the sample size
+  const int64_t cw = full ? (int64_t)f->width : ((int64_t)f->width + 1) / 2;
+  for (int p = 0; p < 3; p++) {
+    const int64_t row = p ? cw : (int64_t)f->width, run = (p && !full ? vp::kRun / 2 : vp::kRun) * es;
+    if ((uintptr_t)f->planes[p] % (uintptr_t)es || f->pitch_bytes[p] % es) throw bad("planes[" + std::to_string(p) + "] and pitch_bytes[" + std::to_string(p) + "] must be multiples of the sample size");
+    if (f->pitch_bytes[p] < row * es) throw bad("pitch_bytes[" + std::to_string(p) + "] is below a row's bytes");
+    wide[p] = (uintptr_t)f->planes[p] % (uintptr_t)run == 0 && f->pitch_bytes[p] % run == 0 && row * es >= run;
+  }
+}
+// on a context with a device: the planes as the device addresses them, none of them inside the atlas
+static void video_planes_on_device(const Refusal& bad, int device, const Atlas& atlas, const FdhVideoPlanes& f, const void* out[3], bool wide[3]) {
+  const bool full = vp::full_chroma(f.format);
+  const int64_t es = vp::ten_bit(f.format) ? 2 : 1;
+  const int64_t cw = full ? (int64_t)f.width : ((int64_t)f.width + 1) / 2, ch = full ? (int64_t)f.height : ((int64_t)f.height + 1) / 2;
+  for (int p = 0; p < 3; p++) {
+    const int64_t bytes = ((p ? ch : (int64_t)f.height) - 1) * f.pitch_bytes[p] + (p ? cw : (int64_t)f.width) * es;
+    out[p] = device_address(bad, device, f.planes[p]);
+    const uintptr_t lo = (uintptr_t)out[p], hi = lo + (uintptr_t)bytes;
+    for (int l = 0; l < atlas.n_levels(); l++) {
+      const uintptr_t a = (uintptr_t)atlas.level(l), side = (uintptr_t)(atlas.size() >> l);
+      if (lo < a + side * side * 4 && a < hi) throw bad("a plane lies inside the context's own atlas");
+    }
+    // (a page-locked plane's device view need not be aligned as the caller's pointer is: the question is asked of the address the kernel gets)
+    wide[p] = wide[p] && lo % (uintptr_t)((p && !full ? vp::kRun / 2 : vp::kRun) * es) == 0;
+  }
+}
+void GlyphMaker::put_video_planes(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) {
+  const Refusal bad{"put_video_planes"};
+  PlanarSource src{};
+  validate_video_planes(bad, frame, src.wide);
+  src.frame = *frame;
+  if (atlas.has_device()) {
+    video_planes_on_device(bad, device, atlas, src.frame, src.planes, src.wide);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.frame.width, src.frame.height);
+  }
+  atlas.make_room(s, src.frame.width, src.frame.height);
+  AtlasEntry& e = atlas.place(s, key, src.frame.width, src.frame.height, out_rect);
+  if (atlas.has_device()) import_video_planes(s, atlas, e, src);
+}
+void GlyphMaker::update_video_planes(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame) {
+  const Refusal bad{"update_video_planes"};
+  PlanarSource src{};
+  validate_video_planes(bad, frame, src.wide);
+  src.frame = *frame;
+  const AtlasEntry* old = atlas.find(key);  // (ahead of the pointers' check and the buffers; begin_update says the same again)
+  if (!old) throw bad("unknown key");
+  if (old->w != src.frame.width || old->h != src.frame.height) throw bad("size mismatch");
+  if (atlas.has_device()) {
+    video_planes_on_device(bad, device, atlas, src.frame, src.planes, src.wide);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.frame.width, src.frame.height);
+  }
+  AtlasEntry& e = atlas.begin_update(bad.who, key, src.frame.width, src.frame.height);
+  e.has_ink = false;  // (the old texels' boxes; import_video_planes measures the new ones)
+  if (atlas.has_device()) import_video_planes(s, atlas, e, src);
+}
+// k_video_planar_import makes levels 0 .. 5; the rest is import_image's (finish_import)
+void GlyphMaker::import_video_planes(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const PlanarSource& src) {
+  const FdhVideoPlanes& f = src.frame;
+  const bool full = vp::full_chroma(f.format);
+  vp::InParams P{};
+  for (int p = 0; p < 3; p++) { P.plane[p] = src.planes[p]; P.pitch[p] = f.pitch_bytes[p]; P.wide[p] = src.wide[p]; }
+  P.w = f.width; P.h = f.height; P.cw = full ? f.width : (f.width + 1) / 2; P.ch = full ? f.height : (f.height + 1) / 2;
+  P.format = f.format; P.flags = f.flags;
+  const int32_t* c = vi::kCoefficients[vp::ten_bit(f.format)][f.matrix][f.range];  // (the NV12 row for 8 bit, the P010 row for 10)
+  P.yoff = c[0]; P.coff = c[1]; P.cy = c[2]; P.crv = c[3]; P.cgu = c[4]; P.cgv = c[5]; P.cbu = c[6];
+  P.x = e.x; P.y = e.y;
+  atlas.each_level(e.x, e.y, e.w, e.h, [&](int, int, int, int, int) { P.n_store++; });
+  P.ink = e.w <= ii::kInkMax && e.h <= ii::kInkMax;
+  for (int l = 0; l < ii::kTileLevels; l++) { P.lw[l] = (e.w + (1 << l) - 1) >> l; P.lh[l] = (e.h + (1 << l) - 1) >> l; }
+  for (int l = 0; l < atlas.n_levels(); l++) P.level[l] = atlas.level(l);
+  P.size = atlas.size();
+  P.scratch = glyph_a_.ptr;
+  P.ink_block = ink_host_.dev;
+  launch_video_planar_import(s, P);
+  finish_import(s, atlas, e, P.n_store, P.ink != 0);
 }
 
 // ---- fdh_compact_atlas (the specification: include_glyphs/figdraw_hip_atlas.h): the texels of every live entry from the old levels into the new

@@ -182,6 +182,13 @@ void launch_video_import(hipStream_t s, const video_import::Params& P);
 // texels at P.src out as NV12, P010 or BGRA8 planes, a workgroup per 128 x 16 tile of them
 namespace video_export { struct Params; }
 void launch_video_export(hipStream_t s, const video_export::Params& P);
+// fdh_put_video_planes, fdh_update_video_planes and fdh_read_video_planes (include_video/figdraw_hip_video_planar.h; k_video_planar_import.hip,
+// k_video_planar_export.hip; the parameter blocks: fdh_video_planar.h): the two launches above for three-plane frames, I420, I010, I444
+// and I410 -- a workgroup of 128 per 32 x 32 tile on the way in (launch_image_import_tail finishes its chain too), a workgroup of 256 per
+// 256 x 16 tile on the way out
+namespace video_planar { struct InParams; struct OutParams; }
+void launch_video_planar_import(hipStream_t s, const video_planar::InParams& P);
+void launch_video_planar_export(hipStream_t s, const video_planar::OutParams& P);
 // fdh_compact_atlas (include_glyphs/figdraw_hip_atlas.h; k_atlas_move.hip): the rectangles of `records` (fdh_atlas_move.h) from the levels of one
 // atlas into those of another, or from / into the dense buffers of V; `tile_record`: the record of each of the n_tiles tiles, the 1-D grid;
 // `owner`: one bit per texel of the records that share texels with a later rectangle

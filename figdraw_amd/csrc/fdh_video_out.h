@@ -7,7 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "../../include_video/figdraw_hip_video_out.h"  // FdhVideoTarget
+#include "../../include_video/figdraw_hip_video_out.h"     // FdhVideoTarget
+#include "../../include_video/figdraw_hip_video_planar.h"  // FdhVideoPlanesTarget
 
 namespace fdh {
 namespace video_out {
@@ -21,6 +22,12 @@ struct Own { const void* base; size_t bytes; const char* what; };
 // fdh_read_video_frame behind the context's part: check_target, the planes' addresses on `device` and their distance from `own`, one
 // launch of k_video_export on `s` reading the W x H surface, and the wait for it
 void read(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoTarget* t, const Own* own, int n_own);
+
+// The same for three planes, I420, I010, I444 and I410 (the specification: include_video/figdraw_hip_video_planar.h).
+// fdh_check_video_planes_target: every rule that needs no device
+void check_planes_target(const char* who, const FdhVideoPlanesTarget* t, int frame_w, int frame_h);
+// fdh_read_video_planes behind the context's part: one launch of k_video_planar_export on `s`, and the wait for it
+void read_planes(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoPlanesTarget* t, const Own* own, int n_own);
 
 }  // namespace video_out
 }  // namespace fdh
