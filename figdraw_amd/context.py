@@ -347,6 +347,8 @@ def load():
     L.fdh_replay_timed.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.fdh_profile.argtypes = [vp, C.c_int]
     L.fdh_get_frame_stats.argtypes = [vp, C.POINTER(FrameStats)]
+    if hasattr(L, "fdh_block_wave_bins"):  # (absent from libraries built before it, which FIGDRAW_HIP_LIB may name for an A/B)
+        L.fdh_block_wave_bins.argtypes = [vp, C.POINTER(C.c_int)]
     # damage tracking (include/figdraw_hip_damage.h; absent from libraries built before it, which FIGDRAW_HIP_LIB may name for an A/B)
     if hasattr(L, "fdh_set_damage_tracking"):
         L.fdh_set_damage_tracking.argtypes = [vp, C.c_int]
@@ -1237,3 +1239,9 @@ class HipContext:
         st = FrameStats()
         self._ck(self.L.fdh_get_frame_stats(self.h, C.byref(st)))
         return st
+
+    def block_wave_bins(self) -> int:
+        """bins of the last frame's full-frame compositor launch that had one wave per 32 x 32 block; -1: the launch did not take that form"""
+        n = C.c_int(0)
+        self._ck(self.L.fdh_block_wave_bins(self.h, C.byref(n)))
+        return n.value

@@ -9,6 +9,7 @@
 #include "../../include/figdraw_hip_readback.h"
 #include "../../include/figdraw_hip_stream.h"
 #include "../../include/figdraw_hip_exact.h"
+#include "../../include_schedule/figdraw_hip_schedule.h"
 #include "../../include_readback/figdraw_hip_moves.h"
 #include "../../include_glyphs/figdraw_hip_glyphs.h"
 #include "../../include_glyphs/figdraw_hip_coverage.h"
@@ -500,5 +501,6 @@ int fdh_replay_async(FdhContext* c, int times) { return guard([&] { C(c)->replay
 int fdh_replay_timed(FdhContext* c, int times, float* ms_out) { return guard([&] { C(c)->replay_timed(times, ms_out); }); }
 int fdh_profile(FdhContext* c, int times) { return guard([&] { C(c)->profile(times); }); }
 int fdh_get_frame_stats(FdhContext* c, FdhFrameStats* out) { return guard([&] { C(c)->frame_stats(out); }); }
+int fdh_block_wave_bins(FdhContext* c, int* out) { return guard([&] { *out = C(c)->block_wave_bins(); }); }
 
 }  // extern "C"

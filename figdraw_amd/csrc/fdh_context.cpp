@@ -482,15 +482,36 @@ Context::Schedule Context::schedule(const LaunchJob& J, bool direct, bool partia
   // draws, 46.4 with >= 40; four contexts in flight 30.3 / 31.1 / 28.9 us -- so 24 for a device's only context, 40 beside others.
   static const int deep_env = [] { const char* e = std::getenv("FDH_DEEP_MIN"); return e ? std::atoi(e) : -1; }();
   S.deep_min = deep_env >= 0 ? deep_env : (vram_contexts_alive(device_) > 1 ? kDeepMinInFlight : kDeepMinDefault);
-  if (sorting && S.deep_min > 0) {
+  // Block waves (blocks::k_composite_tiles): behind the bins with more than block_max draws -- counted by the same waves into
+  // the next eight words -- a wave shades the four strips of a 32 x 32 block.  Before a sorting wave has written them the words say "every
+  // bin": one wave per strip.  The threshold bounds what a wave does in series; FDH_BLOCK_MAX overrides it, FDH_BLOCK_WAVES=0 turns the form off.
+  // The form pays where frames of SEVERAL contexts are in flight (it spends a sixth fewer wave cycles on the bench frame, which the other
+  // contexts' launches use) and costs where a frame has the GPU to itself (a block's four strips in series, at the END of the launch: 26.8 us
+  // -> 27.3 at a threshold of 1, 38 at 8): it goes by whether another context has launched on the device in the last few milliseconds, not by
+  // whether one exists -- a second context that sits idle must not slow the first.  The sorting waves count against the threshold either way.
+  static const int block_env = [] {
+    const char* off = std::getenv("FDH_BLOCK_WAVES");
+    if (off && std::atoi(off) == 0) return 0;
+    const char* e = std::getenv("FDH_BLOCK_MAX");
+    return e ? std::min(std::max(std::atoi(e), 0), 254) : -1;
+  }();
+  const bool shared = device_shared_now(device_, this);
+  S.block_max = block_env >= 0 ? block_env : kBlockMaxInFlight;
+  const bool block_waves = S.block_max > 0 && (block_env >= 0 || shared);
+  if (sorting && (S.deep_min > 0 || S.block_max > 0)) {
     if (!deep_host_) {
       FDH_HIP(hipHostMalloc((void**)&deep_host_, 64, hipHostMallocDefault));
-      for (int c = 0; c < 8; c++) deep_host_[c] = 0;
+      for (int c = 0; c < 8; c++) { deep_host_[c] = 0; deep_host_[8 + c] = 0xffffffffu; }
     }
-    if (S.order_now) {
+    if (S.order_now && S.deep_min > 0) {
       uint32_t most = 0;
       for (int c = 0; c < 8; c++) most = std::max(most, (uint32_t)deep_host_[c]);
       S.deep_k8 = 8 * (int)std::min<uint32_t>(most, 1024u);
+    }
+    if (S.order_now && block_waves) {
+      uint32_t most = 0;
+      for (int c = 0; c < 8; c++) most = std::max(most, (uint32_t)deep_host_[8 + c]);
+      S.block_k8 = 8 * (int)std::min<uint32_t>(most, 1024u);
     }
   }
   return S;
@@ -577,7 +598,8 @@ CompositeParams Context::composite_params(const LaunchJob& J, int p, uint32_t* c
   C.deep_k8 = full ? S.deep_k8 : 0; C.deep_min = S.deep_min;
   static const int deep_strip_min = [] { const char* e = std::getenv("FDH_DEEP_STRIP_MIN"); return e ? std::atoi(e) : kDeepStripMinDefault; }();
   C.deep_strip_min = deep_strip_min;
-  C.deep_out = (full && S.order_next && S.deep_min > 0) ? const_cast<uint32_t*>(deep_host_) : nullptr;
+  C.deep_out = (full && S.order_next && (S.deep_min > 0 || S.block_max > 0)) ? const_cast<uint32_t*>(deep_host_) : nullptr;
+  C.block_max = S.block_max; C.block_k8 = full ? S.block_k8 : -1;
   C.has_slow = ph.has_slow; C.has_slow_atlas = ph.has_slow_atlas; C.has_rot = ph.has_rot; C.has_atlas = ph.has_atlas; C.has_masks = ph.has_masks;
   C.mask_spill = J.mask_spill; C.spill_stride = J.spill_stride;
   return C;
@@ -602,7 +624,11 @@ void Context::launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq
   for (int p = 0; p < (int)J.phases.size(); p++) {
     cur = launch_blur(J, p, cur, lo[p], hi[p], partial);
     CompositeParams C = composite_params(J, p, cur, lo[p], hi[p], direct, S);
-    if (C.load_fb == 0) stats_.deep_bins = (float)composite_build(C).deep_k8;  // (the launch that starts the frame: its deep strips)
+    if (C.load_fb == 0) {  // (the launch that starts the frame: its deep strips, its block waves)
+      const CompositeBuild cb = composite_build(C);
+      stats_.deep_bins = (float)cb.deep_k8;
+      block_wave_bins_ = cb.block && !partial ? std::max(C.bin_nx * C.bin_ny - cb.block_k8, 0) : -1;
+    }
     span_begin(p == 0 ? kSpanCompositeMain : kSpanCompositeLater);
     if (partial) damage_.composite(stream_, J, C);
     else launch_composite(stream_, J.dv.recs, J.dv.exts, C);

@@ -176,6 +176,7 @@ class Context : public Recorder {
   void replay_timed(int times, float* ms_out);
   void replay_async(int times);
   void profile(int times);
+  int block_wave_bins() { drain(); return block_wave_bins_; }
   void frame_stats(FdhFrameStats* out) { drain(); *out = stats_; out->ms_host_launch = launch_ms_.load(std::memory_order_relaxed); }
   // Submission is asynchronous: end_frame hands the recorded frame to the context's submit thread (the upload, the kernel
   // launches) and returns.  flush() returns once everything submitted so far has been ENQUEUED on the
@@ -230,7 +231,7 @@ class Context : public Recorder {
   void issue(LaunchJob& J);    // submit thread: upload + kernel launches
   void launch_frame(const LaunchJob& J, bool profile, uint32_t upload_seq = 0);  // upload_seq: the bin launch reports it to the host
   // launch_frame's stages, in the order it takes them
-  struct Schedule { const int* order_now = nullptr; int* order_next = nullptr; int deep_min = 0, deep_k8 = 0; };  // of the full-frame launch
+  struct Schedule { const int* order_now = nullptr; int* order_next = nullptr; int deep_min = 0, deep_k8 = 0, block_max = 0, block_k8 = -1; };  // of the full-frame launch
   void phase_rows(const LaunchJob& J, std::vector<int>& lo, std::vector<int>& hi) const;
   BinParams bin_params(const LaunchJob& J, uint32_t upload_seq) const;
   Schedule schedule(const LaunchJob& J, bool direct, bool partial);
@@ -344,7 +345,10 @@ class Context : public Recorder {
   hipEvent_t staging_ev_[kStaging] = {};
   char staging_busy_[kStaging] = {};     // 0: free; 1: until staging_ev_ fires; 2: until *seq_host_ reaches staging_seq_ (Context::issue)
   uint32_t staging_seq_[kStaging] = {};
-  volatile uint32_t* deep_host_ = nullptr;  // pinned, 8 words: bins per class with lists of at least deep_min draws, written by the compositor's sorting waves
+  // pinned, 16 words, written by the compositor's sorting waves: bins per class with lists of at least deep_min draws, then (words 8..15) of
+  // more than block_max draws
+  volatile uint32_t* deep_host_ = nullptr;
+  int block_wave_bins_ = -1;  // bins of the last full-frame launch whose blocks had one wave each (-1: the launch did not take the form)
   volatile uint32_t* seq_host_ = nullptr;  // pinned: the sequence number of the last frame whose bin launch has started (k_bin_draws)
   uint32_t upload_seq_ = 0;
   void wait_staging(int slot);             // calling thread: until the set's last upload has run

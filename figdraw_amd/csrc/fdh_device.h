@@ -22,6 +22,9 @@ namespace fdh {
 #ifndef FDH_STATS
 #define FDH_STATS 0  // `make stats`: per-strip draw classification counters (tools/strip_stats.py)
 #endif
+#ifndef FDH_ABLATE_SHADE
+#define FDH_ABLATE_SHADE 0  // `make variant NAME=ablate DEFS=-DFDH_ABLATE_SHADE=1`: the compositor's strips drop every list entry (k_composite_strip.inc)
+#endif
 #ifndef FDH_TIMING
 #define FDH_TIMING 0  // `make variant SINGLE=1 DEFS="-DFDH_STATS=1 -DFDH_TIMING=1"`: per-wave phase times (shader cycles) instead of counts
 #endif

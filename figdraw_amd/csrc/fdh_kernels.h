@@ -54,6 +54,10 @@ struct CompositeParams {
   int has_slow_atlas = 0;   // ... atlas quads among them: k_composite_tiles<19>, the same build at three waves per SIMD (168 registers)
   int has_rot;              // ... or rotated SDF quads the 4-wide path takes (k_composite_tiles<8>, or <3> with the others)
   int has_atlas;            // ... or axis-aligned atlas quads at >= 1:1 (k_composite_tiles<2>)
+  // block waves (blocks::k_composite_tiles): the positions of `order` from block_k8 on (a multiple of 8) get one wave per
+  // 32 x 32 block, those in front of it one per strip; < 0: the launch must not take the form.  (In the four bytes that were padding in
+  // front of `mask_spill`, as block_max below sits in those in front of `binrec`: the block keeps its size and every field its place.)
+  int block_k8 = -1;
   uint32_t* mask_spill;     // clip-stack levels beyond kMaskDepth: [level - kMaskDepth][strip][lane] (null when no frame nests that deep)
   size_t spill_stride;      // dwords per level = strips of the frame x 64
   AtlasView atlas;
@@ -63,6 +67,9 @@ struct CompositeParams {
   // a direct launch (round 6): the phase has at most 64 draws and no list -- the compositor's waves make their bin's entries themselves
   // from the bin records of draws [direct_first, direct_first + direct_n)
   int direct = 0, direct_first = 0, direct_n = 0;
+  // block waves: the sorting waves also count the bins with MORE than block_max draws per class, into deep_out[8..15] (0: they do not) --
+  // the next launches' block_k8
+  int block_max = 0;
   const BinRec* binrec = nullptr;
   int deep_k8 = 0;
   int deep_strip_min = 0;   // ... those of their strips that have at least this many draws to SHADE (strip_shade_count); the others keep their one wave
@@ -74,6 +81,8 @@ struct CompositeParams {
   uint32_t* deep_out = nullptr;
 };
 static_assert(offsetof(CompositeParams, deep_out) == offsetof(CompositeParams, opaque) + 4 && offsetof(CompositeParams, deep_out) + 8 == sizeof(CompositeParams), "`opaque` sits in what was padding");
+static_assert(offsetof(CompositeParams, mask_spill) == offsetof(CompositeParams, block_k8) + 4 && offsetof(CompositeParams, binrec) == offsetof(CompositeParams, block_max) + 4 &&
+              sizeof(CompositeParams) == 312, "`block_k8` and `block_max` sit in what was padding");
 
 struct BlurParams {
   const uint32_t* src;
@@ -107,7 +116,9 @@ inline int forced_kernel_paths() { static const int v = [] { const char* e = std
 // bytes, and the deep strips -- P.deep_k8 (a multiple of 8, at most the launch's bins rounded up to 8) where the launch can have them: the
 // full-frame launch of build <4> with both order pointers, then k_composite_deep's (deep); 0 elsewhere.  Applies FDH_FORCE_KERNEL_PATHS
 // to P's phase flags first (the kernels read them).
-struct CompositeBuild { int paths = 4; size_t lds = 0; int deep_k8 = 0; bool deep = false; };  // (paths: 4 | 32 = <4> for an opaque surface)
+// block: the full-frame launch of <4> / <4 | 32> takes the block-wave form, block_k8 = where in `order` its four-strip waves begin
+// (at most the launch's bins rounded up to 8: then no bin has them)
+struct CompositeBuild { int paths = 4; size_t lds = 0; int deep_k8 = 0; bool deep = false; bool block = false; int block_k8 = 0; };  // (paths: 4 | 32 = <4> for an opaque surface)
 CompositeBuild composite_build(CompositeParams& P);
 void launch_composite(hipStream_t s, const DrawRec* draws, const QuadExt* exts, CompositeParams P);
 void launch_blur_h(hipStream_t s, const BlurParams& P);

@@ -108,6 +108,8 @@ void* vram_block_acquire(int device, size_t bytes, size_t* size_class);  // thro
 void vram_block_release(int device, void* p, size_t size_class);
 size_t vram_store_bytes(int device);   // bytes the store of a device holds (released blocks)
 int vram_contexts_alive(int device);   // device contexts alive on `device` (the deep strips' threshold goes by it: Context::schedule)
+// another context has launched a frame on `device` within the last few milliseconds (block waves go by it: Context::schedule); stamps `who`
+bool device_shared_now(int device, const void* who);
 void vram_context_born(int device);    // a device context exists on `device` ...
 void vram_context_gone(int device);    // ... and is gone: with the last one, the device's store is trimmed to kVramStoreKeep
 constexpr size_t kVramStoreKeep = (size_t)16 << 20;

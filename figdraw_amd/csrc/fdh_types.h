@@ -29,6 +29,12 @@ constexpr int kMaskDepth = 16;                             // per-lane clip stac
 constexpr int kDeepMinDefault = 24;
 constexpr int kDeepMinInFlight = 40;      // ... when the device has other contexts (frames in flight beside this one's): fdh_context.cpp
 constexpr int kDeepStripMinDefault = 16;  // ... and of such a bin's strips, those with at least this many draws to shade (FDH_DEEP_STRIP_MIN)
+// Block waves (blocks::k_composite_tiles<4>, <4 | 32>): in the full-frame launch of a frame all of whose strips are whole, a bin whose
+// list holds at most this many draws gets one wave per 32 x 32 block -- a "workgroup" above, shaded as four strips one after the other --
+// instead of one per strip -- while other contexts have frames in flight on the device.  A frame that has the GPU to itself keeps one wave
+// per strip: alone, the launch is slower with the form at every threshold (FDH_BLOCK_MAX=n forces the form with threshold n, alone or not;
+// FDH_BLOCK_WAVES=0 turns it off).  Sweeps: profiles/block_waves.txt.
+constexpr int kBlockMaxInFlight = 8;
 constexpr int kMaxMips = 14;
 constexpr int kMaxBlurTaps = 36;
 

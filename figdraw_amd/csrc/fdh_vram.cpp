@@ -1,6 +1,7 @@
 // fdh_vram.cpp -- the per-device store of staging blocks in device memory (HostVec::vram), and who is alive on a device.
 #include "fdh_context.h"
 
+#include <chrono>
 #include <cstdlib>
 #include <mutex>
 #include <vector>
@@ -83,6 +84,24 @@ int vram_contexts_alive(int device) {
   if (device < 0 || device >= kMaxDevices) return 0;
   std::lock_guard<std::mutex> lk(g_vram_mu);
   return g_vram_contexts[device];
+}
+// Who launched frames on `device` last: two slots {context, time}.  A context that launches asks whether ANOTHER one has launched within
+// the last few milliseconds -- frames of several contexts in flight, as opposed to contexts that merely exist -- and leaves its own stamp.
+bool device_shared_now(int device, const void* who) {
+  using clock = std::chrono::steady_clock;
+  struct Slot { const void* who = nullptr; clock::time_point at{}; };
+  static std::mutex mu;
+  static Slot slots[kMaxDevices][2];
+  if (device < 0 || device >= kMaxDevices) return false;
+  constexpr auto kWindow = std::chrono::milliseconds(5);
+  const auto now = clock::now();
+  std::lock_guard<std::mutex> lk(mu);
+  Slot* s = slots[device];
+  bool shared = false;
+  for (int i = 0; i < 2; i++) shared = shared || (s[i].who != nullptr && s[i].who != who && now - s[i].at < kWindow);
+  Slot& mine = s[0].who == who ? s[0] : s[1].who == who ? s[1] : (s[0].at <= s[1].at ? s[0] : s[1]);
+  mine.who = who; mine.at = now;
+  return shared;
 }
 void vram_context_born(int device) {
   if (device < 0 || device >= kMaxDevices) return;

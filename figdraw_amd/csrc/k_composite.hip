@@ -7,6 +7,8 @@
 //                      only, <0> + clip masks, <2> + the 4-wide atlas path, <8> + rotated SDF quads, <3> + everything (one pixel slot at a time)
 //   k_composite_deep   the full-frame launch of a frame with deep lists (round 6): workgroups of four waves, the strips of the deepest
 //                      bins shaded by three waves and blended by a fourth
+//   blocks::k_composite_tiles  the full-frame launch of <4> / <4 | 32> while other contexts render: one wave per 32 x 32 block (four strips,
+//                      one after the other) in the bins with short lists
 //
 // Two translation units from this one file (csrc/Makefile).  FDH_TU 0 (this file as it is): the builds <3>, <19> and <8> and the
 // dispatch (composite_build).  FDH_TU 1 (k_composite_uniform.hip): <0>, <2>, <4>, k_composite_deep and their launchers only, compiled with
@@ -42,7 +44,7 @@ namespace fdh {
 // (round 6: the wave also leaves, in pinned host memory, how many bins of its class hold at least `deep_min` draws -- the exclusive
 // prefix of that bucket of the descending histogram.  The host sizes the NEXT launches' deep-strip part from it: k_composite_deep.)
 __device__ __forceinline__ void order_bins_wave(const uint32_t* __restrict__ counts, int* __restrict__ order, int nx, int nb, uint32_t* offs, int lane, int cls,
-                                                int deep_min = 0, uint32_t* __restrict__ deep_out = nullptr) {
+                                                int deep_min = 0, uint32_t* __restrict__ deep_out = nullptr, int block_max = 0) {
 #pragma unroll
   for (int k = 0; k < 4; k++) offs[lane + 64 * k] = 0;
   __builtin_amdgcn_wave_barrier();
@@ -73,6 +75,8 @@ __device__ __forceinline__ void order_bins_wave(const uint32_t* __restrict__ cou
   if (deep_out != nullptr && lane == 0) {
     const int m = min(max(deep_min, 1), 255);
     __hip_atomic_store(deep_out + cls, offs[256 - m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // (block waves: the bins of the class with MORE than block_max draws -- the positions of the order that keep one wave per strip)
+    if (block_max > 0) __hip_atomic_store(deep_out + 8 + cls, offs[255 - min(block_max, 254)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   __builtin_amdgcn_wave_barrier();
   for (int i0 = lane; i0 < nc; i0 += 64 * kU) {
@@ -262,10 +266,10 @@ __device__ __forceinline__ uint32_t strip_shade_count(const CompositeParams& P, 
   return n;
 }
 
-template <int kPaths, bool kFull, int kRole, bool kDirect = false>
+template <int kPaths, bool kFull, int kRole, bool kDirect = false, bool kInterior = false>
 __device__ __forceinline__ void composite_strip(const CompositeParams& P, const DrawRec* __restrict__ draws, const QuadExt* __restrict__ exts,
                                                 uint32_t* composite_lds, const int bin, const int sidx, const int sbit, const int tx0, const int ty0,
-                                                const int lane, const int shader_id);
+                                                const int lane, const int shader_id, const uint32_t cnt_in = 0);
 
 template <int kPaths, bool kFull, bool kDirect = false>
 __global__ __launch_bounds__(64, (kPaths & 16) ? kSlowAtlasWaves : (kPaths & 1) ? kSlowWaves : (kPaths & ~32) == 4 ? kUniformWaves : (kPaths & 2) ? kAtlasWaves : (kPaths & 8) ? kRotWaves : kFastWaves) void k_composite_tiles(
@@ -302,7 +306,7 @@ __global__ __launch_bounds__(64, (kPaths & 16) ? kSlowAtlasWaves : (kPaths & 1) 
     // One extra wavefront per full-frame launch sorts THIS frame's bin counts for the NEXT frame's launch (any
     // permutation is a correct schedule, and list lengths barely change from frame to frame).  As a kernel of its own the
     // sort was a ~6 us serial step of every frame; here it runs beside 32 000 compositing waves.
-    order_bins_wave(P.counts, P.order_next, P.bin_nx, P.bin_nx * P.bin_ny, &mask_stack[0][0][0], threadIdx.x, (int)blockIdx.x, (kPaths & ~32) == 4 ? P.deep_min : 0, (kPaths & ~32) == 4 ? P.deep_out : nullptr);
+    order_bins_wave(P.counts, P.order_next, P.bin_nx, P.bin_nx * P.bin_ny, &mask_stack[0][0][0], threadIdx.x, (int)blockIdx.x, (kPaths & ~32) == 4 ? P.deep_min : 0, (kPaths & ~32) == 4 ? P.deep_out : nullptr, (kPaths & ~32) == 4 ? P.block_max : 0);
     return;
   }
   int bin_local = xcd + 8 * (q / kStripsPerBin);
@@ -339,11 +343,73 @@ __global__ __launch_bounds__(64, (kPaths & 16) ? kSlowAtlasWaves : (kPaths & 1) 
 #else
   constexpr int kRole = 0;
   constexpr int shader_id = 0;
+  constexpr bool kInterior = false;
+  constexpr uint32_t cnt_in = 0;
   {  // (a scope of its own: the body names some of what the mapping above has named)
 #include "k_composite_strip.inc"
   }
 #endif
 }
+
+// ---- Block waves.  The full-frame launch of the no-clip builds for a frame ALL of whose strips are whole (composite_build: W a multiple of
+// 32, H of 8, pitch of 4, no stripe) and whose order is at hand, laid out as k_composite_deep lays out its parts: the first P.block_k8
+// positions of the order -- the bins with more than block_max draws, as the sorting waves of earlier frames counted them -- get sixteen
+// one-wave workgroups each, one strip per wave as in k_composite_tiles above; every later position gets FOUR, and a wave shades the four
+// vertically stacked strips 4 j .. 4 j + 3 of a 32 x 32 block one after the other: its dispatch and the dependent fetches of the order
+// entry and the count are paid once per block, and the launch spends a sixth fewer wave cycles on the bench frame.  That pays where other
+// contexts' launches take the wave slots, and costs where the frame has the GPU to itself -- a block's strips run in series at the END of
+// the launch -- so Context::schedule asks for it only while other contexts are launching (profiles/block_waves.txt).  Both parts' sizes
+// are multiples of 8: position p keeps XCD p % 8.  Any boundary gives the same pixels: the strip body is the same, with its prologue and
+// epilogue in their interior form (no partial row or 16-byte group: no branch on the lane, which the loop around the body must not
+// hold -- tools/lint_isa.py); a strip wholly below the frame is left out by the trip count.  The kernel keeps k_composite_tiles' name and
+// arguments in a namespace of its own: a row of its own in a kernel summary, and the lint finds it by the name.
+namespace blocks {
+template <int kPaths, bool kFull, bool kDirect>
+__global__ __launch_bounds__(64, kUniformWaves) void k_composite_tiles(
+    const int* __restrict__ a_order, int* __restrict__ a_order_next, const uint32_t* __restrict__ a_counts, const uint2* __restrict__ a_lists,
+    int a_bin_x0, int a_bin_y0, int a_bin_nx, int a_bin_ny, int a_bins_x, int a_stride, int a_row_lo, int a_row_hi,
+    const DrawRec* __restrict__ draws, const QuadExt* __restrict__ exts, const CompositeParams P_in) {
+  static_assert((kPaths & ~32) == 4 && kFull && !kDirect, "block waves: the no-clip builds' full-frame launch from the lists");
+  CompositeParams P = P_in;
+  P.order = a_order; P.order_next = a_order_next; P.counts = a_counts; P.lists = a_lists;
+  P.load_fb = 0;
+  P.bin_x0 = a_bin_x0; P.bin_y0 = a_bin_y0; P.bin_nx = a_bin_nx; P.bin_ny = a_bin_ny;
+  P.bins_x = a_bins_x; P.stride = a_stride; P.row_lo = a_row_lo; P.row_hi = a_row_hi;
+  extern __shared__ uint32_t composite_lds[];
+  constexpr int kStripsPerBin = kWgsPerBin * kWavesPerWg;  // 16
+  const int blk = (int)blockIdx.x - 8;  // (the launch has both order pointers: the first eight workgroups sort)
+  if (blk < 0) {
+    order_bins_wave(P.counts, P.order_next, P.bin_nx, P.bin_nx * P.bin_ny, composite_lds, threadIdx.x, (int)blockIdx.x, P.deep_min, P.deep_out, P.block_max);
+    return;
+  }
+  const int q = blk >> 3, xcd = blk & 7;
+  const int n_strip = P.block_k8 * kStripsPerBin;
+  int bin_local, s0, ns;
+  if (blk < n_strip) {
+    bin_local = xcd + 8 * (q / kStripsPerBin); s0 = q % kStripsPerBin; ns = 1;
+  } else {
+    const int q2 = (blk - n_strip) >> 3;
+    bin_local = P.block_k8 + xcd + 8 * (q2 >> 2); s0 = 4 * (q2 & 3); ns = 4;
+  }
+  if (bin_local >= P.bin_nx * P.bin_ny) return;
+  const int rc = P.order[bin_local];
+  const int bin_x = P.bin_x0 + (rc & 0xffff), bin_y = P.bin_y0 + (rc >> 16);
+  const int bin = bin_y * P.bins_x + bin_x;
+  const int jb = s0 >> 2;
+  const int tx0 = bin_x * kBin + (jb & 1) * kWgW;
+  const int ty0 = bin_y * kBin + (jb >> 1) * kWgH + (s0 & 3) * kTileH;
+  if (tx0 >= P.W) return;
+  ns = min(ns, (P.H - ty0) / kTileH);  // (H is a multiple of 8: a strip is inside the frame or below it)
+  if (ns <= 0) return;
+  const uint32_t cnt = P.counts[bin];
+  for (int k = 0; k < ns; k++) {
+    // (the lane index is derived again per strip, opaquely: what a strip computes from it is not kept in registers across the others' draw loops)
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    composite_strip<kPaths, true, 0, false, true>(P, draws, exts, composite_lds, bin, s0 + k, s0 + k, tx0, ty0 + k * kTileH, lane, 0, cnt);
+  }
+}
+}  // namespace blocks
 
 // The full-frame launch of a frame that HAS deep bins (P.deep_k8 > 0; k_composite_tiles<4, true> otherwise), workgroups of four waves:
 //   workgroups 0..7: wave 0 of each sorts one class of this frame's bin counts for the next frame (order_bins_wave);
@@ -362,7 +428,7 @@ __global__ __launch_bounds__(256, kUniformWaves) void k_composite_deep(const Dra
   const int lane = threadIdx.x & 63, wg_wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   int blk = (int)blockIdx.x - 8;
   if (blk < 0) {
-    if (wg_wave == 0) order_bins_wave(P.counts, P.order_next, P.bin_nx, P.bin_nx * P.bin_ny, composite_lds, lane, (int)blockIdx.x, P.deep_min, P.deep_out);
+    if (wg_wave == 0) order_bins_wave(P.counts, P.order_next, P.bin_nx, P.bin_nx * P.bin_ny, composite_lds, lane, (int)blockIdx.x, P.deep_min, P.deep_out, P.block_max);
     return;
   }
   const int n_deep = P.deep_k8 * kStripsPerBin;
@@ -401,10 +467,10 @@ __global__ __launch_bounds__(256, kUniformWaves) void k_composite_deep(const Dra
   else composite_strip<4, true, 2>(P, draws, exts, composite_lds, bin, sidx, sbit, tx0, ty0, lane, wg_wave - 1);
 }
 
-template <int kPaths, bool kFull, int kRole, bool kDirect>
+template <int kPaths, bool kFull, int kRole, bool kDirect, bool kInterior>
 __device__ __forceinline__ void composite_strip(const CompositeParams& P, const DrawRec* __restrict__ draws, const QuadExt* __restrict__ exts,
                                                 uint32_t* composite_lds, const int bin, const int sidx, const int sbit, const int tx0, const int ty0,
-                                                const int lane, const int shader_id) {
+                                                const int lane, const int shader_id, const uint32_t cnt_in) {
   [[maybe_unused]] const AtlasView& atlas_view = P.atlas;
 #include "k_composite_strip.inc"
 }
@@ -452,6 +518,11 @@ static void launch_tiles(hipStream_t s, const CompositeBuild& b, int grid, const
   FDH_LAUNCH((k_composite_tiles<kPaths, kFull, kDirect>), dim3(grid), dim3(64), b.lds, s, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0,
              P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P);
 }
+template <int kPaths>  // (block waves: the full-frame launch of <4> / <4 | 32>, launch_composite_uniform)
+[[maybe_unused]] static void launch_blocks(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P) {
+  FDH_LAUNCH((blocks::k_composite_tiles<kPaths, true, false>), dim3(grid), dim3(64), b.lds, s, P.order, P.order_next, P.counts, P.lists, P.bin_x0, P.bin_y0,
+             P.bin_nx, P.bin_ny, P.bins_x, P.stride, P.row_lo, P.row_hi, draws, exts, P);
+}
 template <int kPaths>  // (kFull: the launch that starts a frame)
 static void launch_damage(hipStream_t s, const CompositeBuild& b, int grid, const DrawRec* draws, const QuadExt* exts, const CompositeParams& P,
                           const int* list, const uint32_t* count) {
@@ -476,6 +547,9 @@ void launch_composite_uniform(hipStream_t s, const CompositeBuild& b, int grid, 
   if (b.deep) {  // build <4>'s full-frame launch with deep bins: four-wave workgroups (a direct frame has no sort, so no deep strips)
     const int bins8 = (P.bin_nx * P.bin_ny + 7) / 8;
     FDH_LAUNCH((k_composite_deep<FDH_TU>), dim3(8 + P.deep_k8 * 16 + 8 * bins8 * kWgsPerBin), dim3(256), b.lds, s, draws, exts, P);
+  } else if (b.block) {  // the full-frame launch of <4> / <4 | 32> with block waves (launch_composite has sized the grid for P.block_k8)
+    if (b.paths == (4 | 32)) launch_blocks<4 | 32>(s, b, grid, draws, exts, P);
+    else launch_blocks<4>(s, b, grid, draws, exts, P);
   } else if (b.paths == 2) launch_tiles_build<2>(s, b, grid, draws, exts, P);
   else if (b.paths == 0) launch_tiles_build<0>(s, b, grid, draws, exts, P);
   else if (b.paths == (4 | 32)) launch_tiles_build<4 | 32>(s, b, grid, draws, exts, P);
@@ -509,6 +583,12 @@ CompositeBuild composite_build(CompositeParams& P) {
   // an opaque surface (Context::prepare decides per frame): the no-clip build without the alpha lane, where the launch walks lists with one
   // wave per strip.  (FDH_FORCE_KERNEL_PATHS has set the phase flags above: a forced build is not <4> and stays what was asked for.)
   if (b.paths == 4 && P.opaque && !b.deep && !P.direct) b.paths = 4 | 32;
+  // block waves: the same launch -- one wave per strip, from the lists, with the order -- of a frame that has no partial strip
+  if ((b.paths & ~32) == 4 && P.load_fb == 0 && P.order && P.order_next && !b.deep && !P.direct && P.block_k8 >= 0 && P.W % kTileW == 0 &&
+      P.H % kTileH == 0 && P.pitch % 4 == 0 && P.row_lo <= 0 && P.row_hi >= P.H) {
+    b.block = true;
+    b.block_k8 = std::min(P.block_k8 & ~7, 8 * bins8);
+  }
   // the clip stack (4 KB; 1 KB, what the bin-ordering wavefront needs, without clips) + the texel window of the atlas path; the deep launch: its ring
   b.lds = b.deep ? sizeof(uint32_t) * kDeepLdsDwords
                  : (P.has_masks ? sizeof(uint32_t) * kMaskDepth * 64 : sizeof(uint32_t) * 256) +
@@ -533,7 +613,9 @@ void launch_composite(hipStream_t s, const DrawRec* draws, const QuadExt* exts, 
   P.n_wg = n;
   P.deep_k8 = b.deep_k8;
   const int bins8 = (P.bin_nx * P.bin_ny + 7) / 8;  // bins per XCD
-  const int grid = 8 * bins8 * kWgsPerBin * kWavesPerWg + (P.order_next ? 8 : 0);  // 16 strips per bin, one wavefront each (+ the sorting ones)
+  int grid = 8 * bins8 * kWgsPerBin * kWavesPerWg + (P.order_next ? 8 : 0);  // 16 strips per bin, one wavefront each (+ the sorting ones)
+  P.block_k8 = b.block ? b.block_k8 : -1;
+  if (b.block) grid = 8 + b.block_k8 * kWgsPerBin * kWavesPerWg + (8 * bins8 - b.block_k8) * kWgsPerBin;  // (one wavefront per block behind the boundary)
   if (b.paths == 19) launch_tiles_build<19>(s, b, grid, draws, exts, P);
   else if (b.paths == 3) launch_tiles_build<3>(s, b, grid, draws, exts, P);
   else if (b.paths == 8) launch_tiles_build<8>(s, b, grid, draws, exts, P);

@@ -1,9 +1,13 @@
 // k_composite_strip.inc -- the body that shades one strip: #included, as text, into k_composite_tiles (one wave, one strip) and into
 // composite_strip (the deep strips' roles), k_composite.hip.  Expects in scope: template / constexpr kPaths, kFull, kRole, kDirect; P, draws,
-// exts, composite_lds, bin, sidx, sbit, tx0, ty0, lane, shader_id, atlas_view (the atlas: P.atlas, or where P is a modified copy, the original's).  (Text, not a call: as a function the kernels that only ever shade one
+// exts, composite_lds, bin, sidx, sbit, tx0, ty0, lane, shader_id, kInterior, cnt_in, atlas_view (the atlas: P.atlas, or where P is a modified copy, the original's).  (Text, not a call: as a function the kernels that only ever shade one
 // strip per wave came out with other register allocations than round 5's -- the <3> build 9 KB larger than the instruction cache likes,
 // config 10 19 % slower; same-box A/B in profiles/r06_ab_r05g.txt.)
   static_assert(kRole == 0 || (kPaths == 4 && kFull), "deep strips: the no-clip build's full-frame launch only");
+  // kInterior (block waves, blocks::k_composite_tiles): the caller knows every row and every 16-byte group of the strip to be
+  // inside the frame and the launch to have no stripe, and has read the bin's count (cnt_in) -- the strip is shaded in a loop over the four
+  // of a block, where no branch of the body may depend on the lane: the tests on row_ok / vec_ok and on the stripe's rows are not made
+  static_assert(!kInterior || (kRole == 0 && kFull && !kDirect && (kPaths & ~32) == 4), "the interior form: block waves only");
   constexpr int kStripsPerBin = kWgsPerBin * kWavesPerWg;  // 16
   constexpr int mslot = 0;
   constexpr bool kBlender = kRole == 1, kShader = kRole == 2;
@@ -42,17 +46,21 @@
   // (a build of its own, kDirect: as a run-time branch of every build the entry code cost the bench frame's launch sixteen spilled
   // scalar registers and 1.6 us of its 26 -- same-box A/B against round 5's library, profiles/r06_ab_r05g.txt)
   constexpr bool direct = kDirect;
-  const uint32_t cnt = direct ? (uint32_t)P.direct_n : P.counts[bin];
+  const uint32_t cnt = kInterior ? cnt_in : direct ? (uint32_t)P.direct_n : P.counts[bin];
 #if FDH_TIMING
   T_cnt = FDH_NOW() - T0 + (cnt & 0u);
 #endif
   if (!kFull && cnt == 0 && P.load_fb) return;  // nothing lands in this bin: the surface already holds the result
 
-  const bool row_ok = py < P.H;
-  const bool vec_ok = row_ok && px0 + 3 < P.W && (P.pitch & 3) == 0;  // whole 16-byte group inside the frame
+  const bool row_ok = kInterior || py < P.H;
+  const bool vec_ok = kInterior || (row_ok && px0 + 3 < P.W && (P.pitch & 3) == 0);  // whole 16-byte group inside the frame
   const size_t pix = (size_t)py * P.pitch + px0;
   FT F0, F1, F2, F3;
-  F0 = F1 = F2 = F3 = unpack_texel<FT>(P.clear_rgba8);
+  uint32_t clear_w = P.clear_rgba8;
+  // (opaque per strip: unpacked once in front of the loop over a block's strips, the clear colour held four vector registers through every
+  // strip's draw loop -- the four that the <4> build then spilled)
+  if (kInterior) asm volatile("" : "+s"(clear_w));
+  F0 = F1 = F2 = F3 = unpack_texel<FT>(clear_w);
   if (!kFull && P.load_fb) {
     if (vec_ok) {
       const uint4 q = *reinterpret_cast<const uint4*>(P.fb + pix);
@@ -175,6 +183,11 @@
     }
 #if FDH_TIMING
     T_cull += FDH_NOW() - Tc0 + (m & 0ull);
+#endif
+#if FDH_ABLATE_SHADE
+    // (`make variant DEFS=-DFDH_ABLATE_SHADE=1`: every entry is dropped behind the list read -- what is left of a launch is what its waves
+    // cost before they shade: dispatch, the chain of fetches up to the entries, the store.  Wrong pixels; profiles/block_waves.txt)
+    { unsigned long long none = 0; asm volatile("" : "+s"(none)); m &= none; }
 #endif
     if (m == 0) continue;
     // Which straight-line path each surviving entry takes on this strip, decided for all 64 entries at once with vector
@@ -1464,6 +1477,12 @@
   int lane_e = threadIdx.x & 63;
   asm volatile("" : "+v"(lane_e));
   const int px0e = tx0 + (lane_e & 7) * 4, pye = ty0 + (lane_e >> 3);
+  if (kInterior) {  // (one unconditional 16-byte store per lane; `touched` is wave-uniform)
+    uint4 o = {P.clear_rgba8, P.clear_rgba8, P.clear_rgba8, P.clear_rgba8};
+    if (touched) o = uint4{pack255(F0), pack255(F1), pack255(F2), pack255(F3)};
+    *reinterpret_cast<uint4*>(P.fb + ((size_t)pye * P.pitch + px0e)) = o;
+    return;
+  }
   if (!(touched || kFull || !P.load_fb) || pye < P.row_lo || pye >= P.row_hi) return;
   const bool row_ok_e = pye < P.H;
   const size_t pixe = (size_t)pye * P.pitch + px0e;
