@@ -173,6 +173,18 @@ def check_video_planes_target(target, frame_w, frame_h):
         raise FigdrawHipError(code, L.fdh_last_error().decode())
 
 
+VIDEO_I422, VIDEO_I210, VIDEO_YUY2, VIDEO_UYVY = 7, 8, 9, 10                       # ... for the 4:2:2 calls (include_video/figdraw_hip_video_422.h)
+
+
+def check_video_422_target(target, frame_w, frame_h):
+    """every rule of fdh_read_video_422 that needs no device, for a frame of frame_w x frame_h (fdh_check_video_422_target): raises
+    FigdrawHipError where the call would refuse `target` (a VideoPlanesTarget, or None)"""
+    L = load()
+    code = L.fdh_check_video_422_target(C.byref(target) if target is not None else None, int(frame_w), int(frame_h))
+    if code != 0:
+        raise FigdrawHipError(code, L.fdh_last_error().decode())
+
+
 def tensor_image(t, straight_alpha: bool = False) -> DeviceImage:
     """the FdhDeviceImage of a tensor: any object with data_ptr(), shape, stride(), dtype and element_size() (a torch tensor; torch is not
     imported here).  H x W x 4 uint8 is RGBA8; C x H x W (C = 1, 3, 4) or H x W of float32 / float16 is planar.  A layout that is not a row
@@ -300,6 +312,11 @@ def load():
         L.fdh_update_video_planes.argtypes = [vp, C.c_int64, C.POINTER(VideoPlanes)]
         L.fdh_read_video_planes.argtypes = [vp, C.POINTER(VideoPlanesTarget)]
         L.fdh_check_video_planes_target.argtypes = [C.POINTER(VideoPlanesTarget), C.c_int, C.c_int]
+    if hasattr(L, "fdh_put_video_422"):  # include_video/figdraw_hip_video_422.h
+        L.fdh_put_video_422.argtypes = [vp, C.c_int64, C.POINTER(VideoPlanes), C.c_int * 4]
+        L.fdh_update_video_422.argtypes = [vp, C.c_int64, C.POINTER(VideoPlanes)]
+        L.fdh_read_video_422.argtypes = [vp, C.POINTER(VideoPlanesTarget)]
+        L.fdh_check_video_422_target.argtypes = [C.POINTER(VideoPlanesTarget), C.c_int, C.c_int]
     if hasattr(L, "fdh_compact_atlas"):  # include_glyphs/figdraw_hip_atlas.h
         L.fdh_compact_atlas.argtypes = [vp, C.c_int, C.POINTER(AtlasMoveStats)]
         L.fdh_set_atlas_keep.argtypes = [vp, C.c_int]
@@ -714,6 +731,27 @@ class HipContext:
         on return."""
         t = video_planes_target(ptrs, pitches, format, matrix, range, flags, rect)
         self._ck(self.L.fdh_read_video_planes(self.h, C.byref(t)))
+
+    def put_video_422(self, key, ptrs, width, height, pitches, format=VIDEO_I422, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0):
+        """a 4:2:2 frame from device (or page-locked host) memory (fdh_put_video_422, include_video/figdraw_hip_video_422.h): I422 or I210
+        with `ptrs` and `pitches` of Y, Cb, Cr, or YUY2 or UYVY with (ptr, 0, 0) and (pitch, 0, 0); what put_image stores of the converted
+        texels, made on the device.  -> the rectangle"""
+        f = video_planes(ptrs, width, height, pitches, format, matrix, range, flags)
+        out = (C.c_int * 4)()
+        self._ck(self.L.fdh_put_video_422(self.h, int(key), C.byref(f), out))
+        return tuple(out)
+
+    def update_video_422(self, key, ptrs, width, height, pitches, format=VIDEO_I422, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0):
+        """the next frame for an entry of the same size (fdh_update_video_422)"""
+        f = video_planes(ptrs, width, height, pitches, format, matrix, range, flags)
+        self._ck(self.L.fdh_update_video_422(self.h, int(key), C.byref(f)))
+
+    def read_video_422(self, ptrs, pitches, format=VIDEO_I422, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None):
+        """the last frame, or its rectangle `rect` = (x, y, w, h), out as I422 or I210 (the three planes Y, Cb, Cr at `ptrs`) or as YUY2 or
+        UYVY (one plane: (ptr, 0, 0) and (pitch, 0, 0)), in device or page-locked host memory (fdh_read_video_422,
+        include_video/figdraw_hip_video_422.h).  The planes are complete on return."""
+        t = video_planes_target(ptrs, pitches, format, matrix, range, flags, rect)
+        self._ck(self.L.fdh_read_video_422(self.h, C.byref(t)))
 
     def put_image_tensor(self, key, tensor, straight_alpha=False):
         """put_image_device of a tensor (tensor_image: H x W x 4 uint8, or C x H x W / H x W float32 or float16).  -> the rectangle"""

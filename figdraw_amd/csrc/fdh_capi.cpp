@@ -20,6 +20,7 @@
 #include "../../include_glyphs/figdraw_hip_atlas.h"
 #include "../../include_video/figdraw_hip_video_out.h"
 #include "../../include_video/figdraw_hip_video_planar.h"
+#include "../../include_video/figdraw_hip_video_422.h"
 
 using fdh::Context;
 
@@ -260,6 +261,19 @@ int fdh_read_video_planes(FdhContext* c, const FdhVideoPlanesTarget* target) {
 }
 int fdh_check_video_planes_target(const FdhVideoPlanesTarget* target, int frame_w, int frame_h) {
   return guard([&] { fdh::video_out::check_planes_target("check_video_planes_target", target, frame_w, frame_h); });
+}
+// 4:2:2 video in and out: I422, I210, YUY2, UYVY (include_video/figdraw_hip_video_422.h)
+int fdh_put_video_422(FdhContext* c, int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) {
+  return guard([&] { C(c)->put_video_422(key, frame, out_rect); });
+}
+int fdh_update_video_422(FdhContext* c, int64_t key, const FdhVideoPlanes* frame) {
+  return guard([&] { C(c)->update_video_422(key, frame); });
+}
+int fdh_read_video_422(FdhContext* c, const FdhVideoPlanesTarget* target) {
+  return guard([&] { C(c)->read_video_422(target); });
+}
+int fdh_check_video_422_target(const FdhVideoPlanesTarget* target, int frame_w, int frame_h) {
+  return guard([&] { fdh::video_out::check_422_target("check_video_422_target", target, frame_w, frame_h); });
 }
 int fdh_put_image_sdf_of(FdhContext* c, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) {
   return guard([&] { C(c)->put_image_sdf_of(src_key, key, channel, pad, flags, out_rect); });

@@ -14,6 +14,7 @@
 #include "fdh_image_import.h"
 #include "fdh_video_import.h"
 #include "fdh_video_planar.h"
+#include "fdh_video_422.h"
 #include "fdh_msdf_cubic_host.h"
 
 namespace fdh {
@@ -21,6 +22,7 @@ namespace mc = msdf::cubic;
 namespace ii = image_import;
 namespace vi = video_import;
 namespace vp = video_planar;
+namespace v2 = video_422;
 
 void GlyphMaker::release() {
   glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release(); glyph_src_.release(); move_tab_.release(); ink_host_.release();
@@ -609,6 +611,96 @@ void GlyphMaker::import_video_planes(hipStream_t s, const Atlas& atlas, AtlasEnt
   P.scratch = glyph_a_.ptr;
   P.ink_block = ink_host_.dev;
   launch_video_planar_import(s, P);
+  finish_import(s, atlas, e, P.n_store, P.ink != 0);
+}
+
+// ---- 4:2:2 video frames (the specification: include_video/figdraw_hip_video_422.h).  put_video_planes's steps, struct, placement and
+// finish_import; the formats, their rules and the first kernel are its own.  A packed format has planes[0] alone.
+// what both calls ask of the struct: no context, no device
+static void validate_video_422(const Refusal& bad, const FdhVideoPlanes* f, bool wide[3]) {
+  if (!f || !f->planes[0]) throw bad("null frame or plane");
+  if (f->width <= 0 || f->height <= 0) throw bad("empty frame");
+  if (!v2::known(f->format)) throw bad("unknown format");
+  if (f->matrix > FDH_VIDEO_BT2020) throw bad("unknown matrix");
+  if (f->range > FDH_VIDEO_FULL) throw bad("unknown range");
+  if (f->flags & ~(uint32_t)(FDH_VIDEO_CHROMA_LINEAR | FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("unknown flag");
+  if (f->reserved[0] || f->reserved[1]) throw bad("reserved must be 0");
+  if (f->flags & (FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("the alpha flags are BGRA8's");
+  const bool packed = v2::packed(f->format);
+  if (packed && (f->planes[1] || f->planes[2] || f->pitch_bytes[1] || f->pitch_bytes[2])) throw bad("planes[1], planes[2] and their pitches must be 0 for YUY2 / UYVY: one plane");
+  if (!packed && (!f->planes[1] || !f->planes[2])) throw bad("null frame or plane");
+  const int64_t es = v2::element_bytes(f->format), cw = ((int64_t)f->width + 1) / 2;
+  for (int p = 0; p < v2::n_planes(f->format); p++) {
+    const int64_t row = packed ? 4 * cw : (p ? cw : (int64_t)f->width) * es, run = v2::run_bytes(f->format, p);
+    if ((uintptr_t)f->planes[p] % (uintptr_t)es || f->pitch_bytes[p] % es)
+      throw bad("planes[" + std::to_string(p) + "] and pitch_bytes[" + std::to_string(p) + "] must be multiples of the " + (packed ? "group size" : "sample size"));
+    if (f->pitch_bytes[p] < row) throw bad("pitch_bytes[" + std::to_string(p) + "] is below a row's bytes");
+    wide[p] = (uintptr_t)f->planes[p] % (uintptr_t)run == 0 && f->pitch_bytes[p] % run == 0 && row >= run;
+  }
+}
+// on a context with a device: the planes as the device addresses them, none of them inside the atlas
+static void video_422_on_device(const Refusal& bad, int device, const Atlas& atlas, const FdhVideoPlanes& f, const void* out[3], bool wide[3]) {
+  const bool packed = v2::packed(f.format);
+  const int64_t es = v2::element_bytes(f.format), cw = ((int64_t)f.width + 1) / 2;
+  for (int p = 0; p < v2::n_planes(f.format); p++) {
+    const int64_t bytes = ((int64_t)f.height - 1) * f.pitch_bytes[p] + (packed ? 4 * cw : (p ? cw : (int64_t)f.width) * es);
+    out[p] = device_address(bad, device, f.planes[p]);
+    const uintptr_t lo = (uintptr_t)out[p], hi = lo + (uintptr_t)bytes;
+    for (int l = 0; l < atlas.n_levels(); l++) {
+      const uintptr_t a = (uintptr_t)atlas.level(l), side = (uintptr_t)(atlas.size() >> l);
+      if (lo < a + side * side * 4 && a < hi) throw bad("a plane lies inside the context's own atlas");
+    }
+    // (a page-locked plane's device view need not be aligned as the caller's pointer is: the question is asked of the address the kernel gets)
+    wide[p] = wide[p] && lo % (uintptr_t)v2::run_bytes(f.format, p) == 0;
+  }
+}
+void GlyphMaker::put_video_422(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) {
+  const Refusal bad{"put_video_422"};
+  PlanarSource src{};
+  validate_video_422(bad, frame, src.wide);
+  src.frame = *frame;
+  if (atlas.has_device()) {
+    video_422_on_device(bad, device, atlas, src.frame, src.planes, src.wide);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.frame.width, src.frame.height);
+  }
+  atlas.make_room(s, src.frame.width, src.frame.height);
+  AtlasEntry& e = atlas.place(s, key, src.frame.width, src.frame.height, out_rect);
+  if (atlas.has_device()) import_video_422(s, atlas, e, src);
+}
+void GlyphMaker::update_video_422(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame) {
+  const Refusal bad{"update_video_422"};
+  PlanarSource src{};
+  validate_video_422(bad, frame, src.wide);
+  src.frame = *frame;
+  const AtlasEntry* old = atlas.find(key);  // (ahead of the pointers' check and the buffers; begin_update says the same again)
+  if (!old) throw bad("unknown key");
+  if (old->w != src.frame.width || old->h != src.frame.height) throw bad("size mismatch");
+  if (atlas.has_device()) {
+    video_422_on_device(bad, device, atlas, src.frame, src.planes, src.wide);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.frame.width, src.frame.height);
+  }
+  AtlasEntry& e = atlas.begin_update(bad.who, key, src.frame.width, src.frame.height);
+  e.has_ink = false;  // (the old texels' boxes; import_video_422 measures the new ones)
+  if (atlas.has_device()) import_video_422(s, atlas, e, src);
+}
+// k_video_422_import makes levels 0 .. 5; the rest is import_image's (finish_import)
+void GlyphMaker::import_video_422(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const PlanarSource& src) {
+  const FdhVideoPlanes& f = src.frame;
+  v2::InParams P{};
+  for (int p = 0; p < v2::n_planes(f.format); p++) { P.plane[p] = src.planes[p]; P.pitch[p] = f.pitch_bytes[p]; P.wide[p] = src.wide[p]; }
+  P.w = f.width; P.h = f.height; P.cw = (f.width + 1) / 2;
+  P.format = f.format; P.flags = f.flags; P.order = f.format == v2::kUYVY;
+  const int32_t* c = vi::kCoefficients[v2::ten_bit(f.format)][f.matrix][f.range];  // (the NV12 row for 8 bit, the P010 row for 10)
+  P.yoff = c[0]; P.coff = c[1]; P.cy = c[2]; P.crv = c[3]; P.cgu = c[4]; P.cgv = c[5]; P.cbu = c[6];
+  P.x = e.x; P.y = e.y;
+  atlas.each_level(e.x, e.y, e.w, e.h, [&](int, int, int, int, int) { P.n_store++; });
+  P.ink = e.w <= ii::kInkMax && e.h <= ii::kInkMax;
+  for (int l = 0; l < ii::kTileLevels; l++) { P.lw[l] = (e.w + (1 << l) - 1) >> l; P.lh[l] = (e.h + (1 << l) - 1) >> l; }
+  for (int l = 0; l < atlas.n_levels(); l++) P.level[l] = atlas.level(l);
+  P.size = atlas.size();
+  P.scratch = glyph_a_.ptr;
+  P.ink_block = ink_host_.dev;
+  launch_video_422_import(s, P);
   finish_import(s, atlas, e, P.n_store, P.ink != 0);
 }
 

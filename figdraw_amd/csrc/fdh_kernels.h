@@ -200,6 +200,13 @@ void launch_video_export(hipStream_t s, const video_export::Params& P);
 namespace video_planar { struct InParams; struct OutParams; }
 void launch_video_planar_import(hipStream_t s, const video_planar::InParams& P);
 void launch_video_planar_export(hipStream_t s, const video_planar::OutParams& P);
+// fdh_put_video_422, fdh_update_video_422 and fdh_read_video_422 (include_video/figdraw_hip_video_422.h; k_video_422_import.hip,
+// k_video_422_export.hip; the parameter blocks: fdh_video_422.h): the same two launches for 4:2:2 frames, I422 and I210 in three planes
+// and YUY2 and UYVY in one -- a workgroup of 128 per 32 x 32 tile on the way in (launch_image_import_tail finishes its chain too), a
+// workgroup of 256 per 256 x 8 tile on the way out
+namespace video_422 { struct InParams; struct OutParams; }
+void launch_video_422_import(hipStream_t s, const video_422::InParams& P);
+void launch_video_422_export(hipStream_t s, const video_422::OutParams& P);
 // fdh_compact_atlas (include_glyphs/figdraw_hip_atlas.h; k_atlas_move.hip): the rectangles of `records` (fdh_atlas_move.h) from the levels of one
 // atlas into those of another, or from / into the dense buffers of V; `tile_record`: the record of each of the n_tiles tiles, the 1-D grid;
 // `owner`: one bit per texel of the records that share texels with a later rectangle

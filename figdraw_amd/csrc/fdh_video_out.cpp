@@ -1,7 +1,8 @@
 // fdh_video_out.cpp -- fdh_read_video_frame, fdh_check_video_target and fdh_video_out_coefficients (fdh_video_out.h; the specification:
 // include_video/figdraw_hip_video_out.h).  No state: a target is checked, turned into k_video_export's parameter block and launched.
 // Behind them the same for three planes: fdh_read_video_planes and fdh_check_video_planes_target (include_video/figdraw_hip_video_planar.h;
-// k_video_planar_export).
+// k_video_planar_export), and for 4:2:2: fdh_read_video_422 and fdh_check_video_422_target (include_video/figdraw_hip_video_422.h;
+// k_video_422_export).
 #include "fdh_video_out.h"
 
 #include <algorithm>
@@ -12,11 +13,13 @@
 #include "fdh_plain.h"   // Error
 #include "fdh_video_export.h"
 #include "fdh_video_planar.h"
+#include "fdh_video_422.h"
 
 namespace fdh {
 namespace video_out {
 namespace ve = video_export;
 namespace vp = video_planar;
+namespace v2 = video_422;
 
 namespace {
 struct Refusal {
@@ -195,6 +198,87 @@ void read_planes(hipStream_t s, int device, const uint32_t* surface, int W, int 
   P.yoff = c[0]; P.coff = c[1];
   for (int k = 0; k < 3; k++) { P.ky[k] = c[2 + k]; P.ku[k] = c[5 + k]; P.kv[k] = c[8 + k]; }
   launch_video_planar_export(s, P);
+  FDH_HIP(hipStreamSynchronize(s));
+  FDH_HIP(hipGetLastError());
+}
+
+// ---- 4:2:2: I422, I210 in three planes, YUY2, UYVY in one (the specification: include_video/figdraw_hip_video_422.h)
+namespace {
+// what a checked 4:2:2 target comes to: the rectangle, its planes, and per plane a row's bytes and the bytes from its pointer to its last row's end
+struct Layout422 {
+  int x, y, w, h, n;
+  int64_t row[3];
+  __int128 bytes[3];
+  bool wide[3];  // a run of plane p is one store (v2::OutParams)
+};
+
+Layout422 check_422(const Refusal& bad, const FdhVideoPlanesTarget* t, int frame_w, int frame_h) {
+  if (!t || !t->planes[0]) throw bad("null target or plane");
+  if (!v2::known(t->format)) throw bad("unknown format");
+  if (t->matrix > FDH_VIDEO_BT2020) throw bad("unknown matrix");
+  if (t->range > FDH_VIDEO_FULL) throw bad("unknown range");
+  if (t->flags & ~(uint32_t)(FDH_VIDEO_CHROMA_LINEAR | FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("unknown flag");
+  if (t->reserved[0] || t->reserved[1]) throw bad("reserved must be 0");
+  if (t->flags & (FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("the alpha flags are BGRA8's");
+  const bool packed = v2::packed(t->format);
+  if (packed && (t->planes[1] || t->planes[2] || t->pitch_bytes[1] || t->pitch_bytes[2])) throw bad("planes[1], planes[2] and their pitches must be 0 for YUY2 / UYVY: one plane");
+  if (!packed && (!t->planes[1] || !t->planes[2])) throw bad("null target or plane");
+  if (frame_w <= 0 || frame_h <= 0) throw bad("empty frame");
+  Layout422 L{};
+  L.x = t->rect[0]; L.y = t->rect[1]; L.w = t->rect[2]; L.h = t->rect[3];
+  if (L.w <= 0 || L.h <= 0) { L.x = 0; L.y = 0; L.w = frame_w; L.h = frame_h; }
+  if (L.x < 0 || L.y < 0 || (int64_t)L.x + L.w > frame_w || (int64_t)L.y + L.h > frame_h) throw bad("rectangle outside the frame");
+  if (L.x & 1) throw bad("the rectangle's x must be even for 4:2:2");
+  L.n = v2::n_planes(t->format);
+  const int64_t es = v2::element_bytes(t->format), cw = ((int64_t)L.w + 1) / 2;
+  for (int p = 0; p < L.n; p++) {
+    L.row[p] = packed ? 4 * cw : (p ? cw : (int64_t)L.w) * es;
+    if ((uintptr_t)t->planes[p] % (uintptr_t)es || t->pitch_bytes[p] % es)
+      throw bad("planes[" + std::to_string(p) + "] and pitch_bytes[" + std::to_string(p) + "] must be multiples of the " + (packed ? "group size" : "sample size"));
+    if (t->pitch_bytes[p] < L.row[p]) throw bad("pitch_bytes[" + std::to_string(p) + "] is below a row's bytes");
+    L.bytes[p] = (__int128)(L.h - 1) * t->pitch_bytes[p] + (__int128)L.row[p];
+    const int64_t run = v2::run_bytes(t->format, p);
+    L.wide[p] = (uintptr_t)t->planes[p] % (uintptr_t)run == 0 && t->pitch_bytes[p] % run == 0 && L.row[p] >= run;
+  }
+  for (int p = 0; p < L.n; p++)
+    for (int q = p + 1; q < L.n; q++)
+      if (overlap((uintptr_t)t->planes[p], L.bytes[p], (uintptr_t)t->planes[q], L.bytes[q])) throw bad("planes " + std::to_string(p) + " and " + std::to_string(q) + " overlap");
+  return L;
+}
+}  // namespace
+
+void check_422_target(const char* who, const FdhVideoPlanesTarget* t, int frame_w, int frame_h) { (void)check_422(Refusal{who}, t, frame_w, frame_h); }
+
+void read_422(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoPlanesTarget* target, const Own* own, int n_own) {
+  const Refusal bad{"read_video_422"};
+  const Layout422 L = check_422(bad, target, W, H);
+  const FdhVideoPlanesTarget t = *target;
+  void* planes[3] = {nullptr, nullptr, nullptr};
+  for (int p = 0; p < L.n; p++) {
+    planes[p] = device_view_of(device, t.planes[p]);
+    if (!planes[p]) throw bad("a plane is neither device memory of the context's device nor page-locked host memory");
+    for (int k = 0; k < n_own; k++)
+      if (own[k].base && overlap((uintptr_t)planes[p], L.bytes[p], (uintptr_t)own[k].base, (__int128)own[k].bytes))
+        throw bad(std::string("a plane overlaps the context's own ") + own[k].what);
+  }
+  for (int p = 0; p < L.n; p++)
+    for (int q = p + 1; q < L.n; q++)
+      if (overlap((uintptr_t)planes[p], L.bytes[p], (uintptr_t)planes[q], L.bytes[q])) throw bad("planes " + std::to_string(p) + " and " + std::to_string(q) + " overlap");
+  v2::OutParams P{};
+  P.src = surface + (size_t)L.y * W + L.x;
+  P.src_pitch = W;
+  P.w = L.w; P.h = L.h;
+  P.format = t.format; P.flags = t.flags; P.order = t.format == v2::kUYVY;
+  P.wide_src = (uintptr_t)P.src % 16 == 0 && W % 4 == 0 && L.w >= v2::kRun;
+  for (int p = 0; p < L.n; p++) {
+    P.plane[p] = planes[p]; P.pitch[p] = t.pitch_bytes[p];
+    // (a page-locked plane's device view need not be aligned as the caller's pointer is: the question is asked of the address the kernel gets)
+    P.wide[p] = L.wide[p] && (uintptr_t)planes[p] % (uintptr_t)v2::run_bytes(t.format, p) == 0;
+  }
+  const int32_t* c = ve::kCoefficients[v2::ten_bit(t.format)][t.matrix][t.range];  // (the NV12 row for 8 bit, the P010 row for 10)
+  P.yoff = c[0]; P.coff = c[1];
+  for (int k = 0; k < 3; k++) { P.ky[k] = c[2 + k]; P.ku[k] = c[5 + k]; P.kv[k] = c[8 + k]; }
+  launch_video_422_export(s, P);
   FDH_HIP(hipStreamSynchronize(s));
   FDH_HIP(hipGetLastError());
 }

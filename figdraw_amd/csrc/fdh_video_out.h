@@ -8,7 +8,7 @@
 #include <cstdint>
 
 #include "../../include_video/figdraw_hip_video_out.h"     // FdhVideoTarget
-#include "../../include_video/figdraw_hip_video_planar.h"  // FdhVideoPlanesTarget
+#include "../../include_video/figdraw_hip_video_422.h"  // FdhVideoPlanesTarget, through figdraw_hip_video_planar.h; the 4:2:2 formats
 
 namespace fdh {
 namespace video_out {
@@ -28,6 +28,12 @@ void read(hipStream_t s, int device, const uint32_t* surface, int W, int H, cons
 void check_planes_target(const char* who, const FdhVideoPlanesTarget* t, int frame_w, int frame_h);
 // fdh_read_video_planes behind the context's part: one launch of k_video_planar_export on `s`, and the wait for it
 void read_planes(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoPlanesTarget* t, const Own* own, int n_own);
+
+// The same for 4:2:2, I422 and I210 in three planes, YUY2 and UYVY in one (the specification: include_video/figdraw_hip_video_422.h).
+// fdh_check_video_422_target: every rule that needs no device
+void check_422_target(const char* who, const FdhVideoPlanesTarget* t, int frame_w, int frame_h);
+// fdh_read_video_422 behind the context's part: one launch of k_video_422_export on `s`, and the wait for it
+void read_422(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoPlanesTarget* t, const Own* own, int n_own);
 
 }  // namespace video_out
 }  // namespace fdh

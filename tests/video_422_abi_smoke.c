@@ -1,0 +1,91 @@
+/* fdh_put_video_422, fdh_update_video_422, fdh_read_video_422 and fdh_check_video_422_target through the C ABI in C99
+ * (include_video/figdraw_hip_video_422.h): no GPU needed -- the check needs no context, and a record-only context validates and places
+ * on the way in and refuses the read.  tests/test_video_422_host.py compiles this with -std=c99 -Wall -Wextra -Werror -pedantic
+ * -I include_video and runs it. */
+#include "figdraw_hip_video_422.h"
+#include <stdio.h>
+#include <string.h>
+
+#define CHECK(c) do { if (!(c)) { printf("FAILED line %d: %s (%s)\n", __LINE__, #c, fdh_last_error()); return 1; } } while (0)
+#define OK(call) CHECK((call) == FDH_OK)
+
+int main(void) {
+  FdhContext* c = NULL;
+  static uint32_t y[16 * 9], cb[16 * 9], cr[16 * 9];  /* stand for device memory: nothing here touches it */
+  const float black[4] = {0.0f, 0.0f, 0.0f, 1.0f};
+  FdhVideoPlanes f, badf;
+  FdhVideoPlanesTarget t, bad;
+  int rect[4], has = 0;
+  CHECK(sizeof(FdhVideoPlanes) == 80 && sizeof(FdhVideoPlanesTarget) == 88);
+  CHECK(FDH_VIDEO_I422 == 7 && FDH_VIDEO_I210 == 8 && FDH_VIDEO_YUY2 == 9 && FDH_VIDEO_UYVY == 10);
+  /* the way out: the rules that need no device */
+  memset(&t, 0, sizeof t);
+  t.planes[0] = y; t.planes[1] = cb; t.planes[2] = cr; t.pitch_bytes[0] = 16; t.pitch_bytes[1] = 8; t.pitch_bytes[2] = 8;
+  t.format = FDH_VIDEO_I422; t.matrix = FDH_VIDEO_BT709; t.range = FDH_VIDEO_LIMITED; t.flags = FDH_VIDEO_CHROMA_LINEAR;
+  OK(fdh_check_video_422_target(&t, 16, 9));
+  t.rect[0] = 2; t.rect[1] = 3; t.rect[2] = 13; t.rect[3] = 5;
+  OK(fdh_check_video_422_target(&t, 16, 9));                                     /* an odd y is fine */
+  bad = t; bad.rect[0] = 3;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);             /* an odd x is not */
+  CHECK(strstr(fdh_last_error(), "check_video_422_target: ") == fdh_last_error());
+  bad = t; bad.planes[2] = NULL;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);
+  bad = t; bad.format = FDH_VIDEO_I420;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);
+  bad = t; bad.format = 11;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);
+  bad = t; bad.flags = FDH_VIDEO_IGNORE_ALPHA;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);
+  bad = t; bad.reserved[1] = 1;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);
+  bad = t; bad.planes[2] = (char*)cb + 4;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);             /* Cb and Cr overlap */
+  bad = t; bad.format = FDH_VIDEO_I210; bad.pitch_bytes[0] = 32; bad.pitch_bytes[1] = 16; bad.pitch_bytes[2] = 16;
+  OK(fdh_check_video_422_target(&bad, 16, 9));
+  bad.planes[1] = (char*)cb + 1;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);             /* a 16-bit sample at an odd address */
+  bad = t; bad.format = FDH_VIDEO_UYVY;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);             /* a packed format has one plane */
+  bad.planes[1] = NULL; bad.planes[2] = NULL; bad.pitch_bytes[1] = 0; bad.pitch_bytes[2] = 0; bad.pitch_bytes[0] = 28;
+  OK(fdh_check_video_422_target(&bad, 16, 9));                                   /* 13 columns: seven groups */
+  bad.planes[0] = (char*)y + 2;
+  CHECK(fdh_check_video_422_target(&bad, 16, 9) == FDH_ERR_INVALID);             /* a group at an address that is no multiple of 4 */
+  CHECK(fdh_check_video_422_target(NULL, 16, 9) == FDH_ERR_INVALID);
+  /* the planar calls keep to their formats */
+  bad = t; bad.rect[0] = 2; bad.rect[1] = 2;
+  CHECK(fdh_check_video_planes_target(&bad, 16, 9) == FDH_ERR_INVALID);
+  /* the way in on a record-only context: validated and placed, no memory touched */
+  OK(fdh_create(&c, 256, 1.0f, 0, FDH_CREATE_RECORD_ONLY));
+  memset(&f, 0, sizeof f);
+  f.planes[0] = y; f.planes[1] = cb; f.planes[2] = cr; f.pitch_bytes[0] = 16; f.pitch_bytes[1] = 8; f.pitch_bytes[2] = 8;
+  f.width = 16; f.height = 9; f.format = FDH_VIDEO_I422; f.matrix = FDH_VIDEO_BT601; f.range = FDH_VIDEO_FULL;
+  CHECK(fdh_put_video_planes(c, 7, &f, rect) == FDH_ERR_INVALID);
+  OK(fdh_put_video_422(c, 7, &f, rect));
+  OK(fdh_has_image(c, 7, &has));
+  CHECK(rect[2] == 16 && rect[3] == 9 && has);
+  badf = f; badf.planes[2] = f.planes[1];
+  OK(fdh_update_video_422(c, 7, &badf));                                         /* the planes may alias on the way in */
+  badf = f; badf.format = FDH_VIDEO_YUY2; badf.planes[1] = NULL; badf.planes[2] = NULL; badf.pitch_bytes[0] = 32; badf.pitch_bytes[1] = 0; badf.pitch_bytes[2] = 0;
+  OK(fdh_update_video_422(c, 7, &badf));                                         /* the next frame may come in another format */
+  badf.pitch_bytes[2] = 8;
+  CHECK(fdh_update_video_422(c, 7, &badf) == FDH_ERR_INVALID);
+  badf = f; badf.width = 15;
+  CHECK(fdh_update_video_422(c, 7, &badf) == FDH_ERR_INVALID);
+  CHECK(strstr(fdh_last_error(), "update_video_422: ") == fdh_last_error());
+  CHECK(fdh_update_video_422(c, 8, &f) == FDH_ERR_INVALID);
+  badf = f; badf.pitch_bytes[1] = 7;
+  CHECK(fdh_put_video_422(c, 8, &badf, NULL) == FDH_ERR_INVALID);
+  OK(fdh_has_image(c, 8, &has));
+  CHECK(!has);
+  CHECK(fdh_put_video_422(c, 8, NULL, NULL) == FDH_ERR_INVALID);
+  /* ... and it has no frame to hand out */
+  OK(fdh_begin_frame(c, 16, 9, 1, black));
+  OK(fdh_end_frame(c));
+  t.rect[0] = 0; t.rect[1] = 0; t.rect[2] = 0; t.rect[3] = 0;
+  CHECK(fdh_read_video_422(c, &t) == FDH_ERR_INVALID);
+  CHECK(strstr(fdh_last_error(), "read_video_422: ") == fdh_last_error());
+  CHECK(fdh_read_video_422(NULL, &t) == FDH_ERR_INVALID);
+  fdh_destroy(c);
+  printf("video_422_abi_smoke: OK\n");
+  return 0;
+}
