@@ -185,6 +185,46 @@ def check_video_422_target(target, frame_w, frame_h):
         raise FigdrawHipError(code, L.fdh_last_error().decode())
 
 
+class VideoAlphaPlanes(C.Structure):  # FdhVideoAlphaPlanes (include_video/figdraw_hip_video_alpha.h)
+    _fields_ = [("planes", C.c_void_p * 4), ("pitch_bytes", C.c_int64 * 4), ("width", C.c_int32), ("height", C.c_int32),
+                ("format", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class VideoAlphaPlanesTarget(C.Structure):  # FdhVideoAlphaPlanesTarget
+    _fields_ = [("planes", C.c_void_p * 4), ("pitch_bytes", C.c_int64 * 4), ("rect", C.c_int32 * 4),
+                ("format", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+VIDEO_A420, VIDEO_A444, VIDEO_A410, VIDEO_UYVA = 11, 12, 13, 14                    # FdhVideoAlphaPlanes.format, FdhVideoAlphaPlanesTarget.format
+
+
+def video_alpha_planes(ptrs, width, height, pitches, format=VIDEO_A420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0) -> VideoAlphaPlanes:
+    """ptrs, pitches: of Y, Cb, Cr, A; UYVA: (the UYVY plane, 0, 0, A)"""
+    f = VideoAlphaPlanes()
+    for p in (0, 1, 2, 3):
+        f.planes[p], f.pitch_bytes[p] = ptrs[p] or None, int(pitches[p])
+    f.width, f.height, f.format, f.matrix, f.range, f.flags = int(width), int(height), int(format), int(matrix), int(range), int(flags)
+    return f
+
+
+def video_alpha_planes_target(ptrs, pitches, format=VIDEO_A420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None) -> VideoAlphaPlanesTarget:
+    t = VideoAlphaPlanesTarget()
+    for p in (0, 1, 2, 3):
+        t.planes[p], t.pitch_bytes[p] = ptrs[p] or None, int(pitches[p])
+    t.rect[0], t.rect[1], t.rect[2], t.rect[3] = (int(v) for v in (rect if rect is not None else (0, 0, 0, 0)))
+    t.format, t.matrix, t.range, t.flags = int(format), int(matrix), int(range), int(flags)
+    return t
+
+
+def check_video_alpha_target(target, frame_w, frame_h):
+    """every rule of fdh_read_video_alpha that needs no device, for a frame of frame_w x frame_h (fdh_check_video_alpha_target): raises
+    FigdrawHipError where the call would refuse `target` (a VideoAlphaPlanesTarget, or None)"""
+    L = load()
+    code = L.fdh_check_video_alpha_target(C.byref(target) if target is not None else None, int(frame_w), int(frame_h))
+    if code != 0:
+        raise FigdrawHipError(code, L.fdh_last_error().decode())
+
+
 def tensor_image(t, straight_alpha: bool = False) -> DeviceImage:
     """the FdhDeviceImage of a tensor: any object with data_ptr(), shape, stride(), dtype and element_size() (a torch tensor; torch is not
     imported here).  H x W x 4 uint8 is RGBA8; C x H x W (C = 1, 3, 4) or H x W of float32 / float16 is planar.  A layout that is not a row
@@ -317,6 +357,11 @@ def load():
         L.fdh_update_video_422.argtypes = [vp, C.c_int64, C.POINTER(VideoPlanes)]
         L.fdh_read_video_422.argtypes = [vp, C.POINTER(VideoPlanesTarget)]
         L.fdh_check_video_422_target.argtypes = [C.POINTER(VideoPlanesTarget), C.c_int, C.c_int]
+    if hasattr(L, "fdh_put_video_alpha"):  # include_video/figdraw_hip_video_alpha.h
+        L.fdh_put_video_alpha.argtypes = [vp, C.c_int64, C.POINTER(VideoAlphaPlanes), C.c_int * 4]
+        L.fdh_update_video_alpha.argtypes = [vp, C.c_int64, C.POINTER(VideoAlphaPlanes)]
+        L.fdh_read_video_alpha.argtypes = [vp, C.POINTER(VideoAlphaPlanesTarget)]
+        L.fdh_check_video_alpha_target.argtypes = [C.POINTER(VideoAlphaPlanesTarget), C.c_int, C.c_int]
     if hasattr(L, "fdh_compact_atlas"):  # include_glyphs/figdraw_hip_atlas.h
         L.fdh_compact_atlas.argtypes = [vp, C.c_int, C.POINTER(AtlasMoveStats)]
         L.fdh_set_atlas_keep.argtypes = [vp, C.c_int]
@@ -752,6 +797,27 @@ class HipContext:
         include_video/figdraw_hip_video_422.h).  The planes are complete on return."""
         t = video_planes_target(ptrs, pitches, format, matrix, range, flags, rect)
         self._ck(self.L.fdh_read_video_422(self.h, C.byref(t)))
+
+    def put_video_alpha(self, key, ptrs, width, height, pitches, format=VIDEO_A420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0):
+        """a frame with an alpha plane from device (or page-locked host) memory (fdh_put_video_alpha, include_video/figdraw_hip_video_alpha.h):
+        A420, A444 or A410 with `ptrs` and `pitches` of Y, Cb, Cr, A, or UYVA with (ptr, 0, 0, alpha ptr) and (pitch, 0, 0, alpha pitch);
+        flags: VIDEO_CHROMA_LINEAR, VIDEO_STRAIGHT_ALPHA; what put_image stores of the converted texels, made on the device.  -> the rectangle"""
+        f = video_alpha_planes(ptrs, width, height, pitches, format, matrix, range, flags)
+        out = (C.c_int * 4)()
+        self._ck(self.L.fdh_put_video_alpha(self.h, int(key), C.byref(f), out))
+        return tuple(out)
+
+    def update_video_alpha(self, key, ptrs, width, height, pitches, format=VIDEO_A420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0):
+        """the next frame for an entry of the same size (fdh_update_video_alpha)"""
+        f = video_alpha_planes(ptrs, width, height, pitches, format, matrix, range, flags)
+        self._ck(self.L.fdh_update_video_alpha(self.h, int(key), C.byref(f)))
+
+    def read_video_alpha(self, ptrs, pitches, format=VIDEO_A420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None):
+        """the last frame, or its rectangle `rect` = (x, y, w, h), out as A420, A444 or A410 (the four planes Y, Cb, Cr, A at `ptrs`) or as
+        UYVA ((ptr, 0, 0, alpha ptr) and (pitch, 0, 0, alpha pitch)), in device or page-locked host memory; with VIDEO_STRAIGHT_ALPHA the colour
+        is un-premultiplied first (fdh_read_video_alpha, include_video/figdraw_hip_video_alpha.h).  The planes are complete on return."""
+        t = video_alpha_planes_target(ptrs, pitches, format, matrix, range, flags, rect)
+        self._ck(self.L.fdh_read_video_alpha(self.h, C.byref(t)))
 
     def put_image_tensor(self, key, tensor, straight_alpha=False):
         """put_image_device of a tensor (tensor_image: H x W x 4 uint8, or C x H x W / H x W float32 or float16).  -> the rectangle"""

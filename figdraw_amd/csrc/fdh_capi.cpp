@@ -21,6 +21,7 @@
 #include "../../include_video/figdraw_hip_video_out.h"
 #include "../../include_video/figdraw_hip_video_planar.h"
 #include "../../include_video/figdraw_hip_video_422.h"
+#include "../../include_video/figdraw_hip_video_alpha.h"
 
 using fdh::Context;
 
@@ -274,6 +275,19 @@ int fdh_read_video_422(FdhContext* c, const FdhVideoPlanesTarget* target) {
 }
 int fdh_check_video_422_target(const FdhVideoPlanesTarget* target, int frame_w, int frame_h) {
   return guard([&] { fdh::video_out::check_422_target("check_video_422_target", target, frame_w, frame_h); });
+}
+// video with an alpha plane in and out: A420, A444, A410, UYVA (include_video/figdraw_hip_video_alpha.h)
+int fdh_put_video_alpha(FdhContext* c, int64_t key, const FdhVideoAlphaPlanes* frame, int out_rect[4]) {
+  return guard([&] { C(c)->put_video_alpha(key, frame, out_rect); });
+}
+int fdh_update_video_alpha(FdhContext* c, int64_t key, const FdhVideoAlphaPlanes* frame) {
+  return guard([&] { C(c)->update_video_alpha(key, frame); });
+}
+int fdh_read_video_alpha(FdhContext* c, const FdhVideoAlphaPlanesTarget* target) {
+  return guard([&] { C(c)->read_video_alpha(target); });
+}
+int fdh_check_video_alpha_target(const FdhVideoAlphaPlanesTarget* target, int frame_w, int frame_h) {
+  return guard([&] { fdh::video_out::check_alpha_target("check_video_alpha_target", target, frame_w, frame_h); });
 }
 int fdh_put_image_sdf_of(FdhContext* c, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) {
   return guard([&] { C(c)->put_image_sdf_of(src_key, key, channel, pad, flags, out_rect); });

@@ -773,6 +773,19 @@ void Context::read_video_422(const FdhVideoPlanesTarget* target) {
   FDH_HIP(hipStreamSynchronize(stream_));
   video_out::read_422(stream_, device_, fb_, surf_w_, surf_h_, target, own.data(), (int)own.size());
 }
+// fdh_read_video_alpha (include_video/figdraw_hip_video_alpha.h): the same for the formats with an alpha plane
+void Context::read_video_alpha(const FdhVideoAlphaPlanesTarget* target) {
+  if (host_only_) throw Error(FDH_ERR_INVALID, "read_video_alpha: this context was created with FDH_CREATE_RECORD_ONLY (it records calls, it draws nothing)");
+  drain();
+  if (!have_frame_ || !fb_ || job_.W != surf_w_ || job_.H != surf_h_) throw Error(FDH_ERR_INVALID, "read_video_alpha: no frame has been submitted");
+  if (stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, "read_video_alpha: not under fdh_set_stripe");
+  FDH_HIP(hipSetDevice(device_));
+  const size_t surface = (size_t)surf_w_ * surf_h_ * 4;
+  std::vector<video_out::Own> own = {{fb_, surface, "frame surface"}, {alt_, surface, "frame surface"}, {backdrop_, surface, "backdrop surface"}, {blur_tmp_, surface, "blur surface"}};
+  for (int l = 0; l < atlas_.n_levels(); l++) own.push_back({atlas_.level(l), (size_t)(atlas_.size() >> l) * (atlas_.size() >> l) * 4, "atlas"});
+  FDH_HIP(hipStreamSynchronize(stream_));
+  video_out::read_alpha(stream_, device_, fb_, surf_w_, surf_h_, target, own.data(), (int)own.size());
+}
 // ------------------------------------------------------------------ damage tracking, damage readback: the context's part (fdh_damage.cpp)
 void Context::set_damage_tracking(bool on) {
   if (on && host_only_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_tracking: a record-only context composites nothing");

@@ -77,6 +77,8 @@ class Context : public Recorder {
   void update_video_planes(int64_t key, const FdhVideoPlanes* frame) { sync(); glyphs_.update_video_planes(stream_, atlas_, device_, key, frame); }
   void put_video_422(int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) { sync(); glyphs_.put_video_422(stream_, atlas_, device_, key, frame, out_rect); }
   void update_video_422(int64_t key, const FdhVideoPlanes* frame) { sync(); glyphs_.update_video_422(stream_, atlas_, device_, key, frame); }
+  void put_video_alpha(int64_t key, const FdhVideoAlphaPlanes* frame, int out_rect[4]) { sync(); glyphs_.put_video_alpha(stream_, atlas_, device_, key, frame, out_rect); }
+  void update_video_alpha(int64_t key, const FdhVideoAlphaPlanes* frame) { sync(); glyphs_.update_video_alpha(stream_, atlas_, device_, key, frame); }
   bool has_image(int64_t key) const { return atlas_.has(key); }
   void reset_atlas(int minimum_size) { sync(); atlas_.reset(minimum_size, stream_); }
   int atlas_size() const { return atlas_.size(); }
@@ -94,6 +96,7 @@ class Context : public Recorder {
   void read_video_frame(const FdhVideoTarget* target);  // (include_video/figdraw_hip_video_out.h; fdh_video_out.h)
   void read_video_planes(const FdhVideoPlanesTarget* target);  // (include_video/figdraw_hip_video_planar.h; fdh_video_out.h)
   void read_video_422(const FdhVideoPlanesTarget* target);     // (include_video/figdraw_hip_video_422.h; fdh_video_out.h)
+  void read_video_alpha(const FdhVideoAlphaPlanesTarget* target);  // (include_video/figdraw_hip_video_alpha.h; fdh_video_out.h)
   void frame_device_ptr(void** p, int* w, int* h, int64_t* pitch_bytes);
   void debug_read_surface(int which, uint8_t* out);
   // call recorder (fdh_record_begin / fdh_record_json): the backend-level calls the scene front-end makes, as JSON

@@ -15,6 +15,7 @@
 #include "fdh_video_import.h"
 #include "fdh_video_planar.h"
 #include "fdh_video_422.h"
+#include "fdh_video_alpha.h"
 #include "fdh_msdf_cubic_host.h"
 
 namespace fdh {
@@ -23,6 +24,7 @@ namespace ii = image_import;
 namespace vi = video_import;
 namespace vp = video_planar;
 namespace v2 = video_422;
+namespace va = video_alpha;
 
 void GlyphMaker::release() {
   glyph_a_.release(); glyph_b_.release(); glyph_lines_.release(); glyph_acc_.release(); glyph_edges_.release(); glyph_tab_.release(); glyph_src_.release(); move_tab_.release(); ink_host_.release();
@@ -701,6 +703,105 @@ void GlyphMaker::import_video_422(hipStream_t s, const Atlas& atlas, AtlasEntry&
   P.scratch = glyph_a_.ptr;
   P.ink_block = ink_host_.dev;
   launch_video_422_import(s, P);
+  finish_import(s, atlas, e, P.n_store, P.ink != 0);
+}
+
+// ---- video frames with an alpha plane (the specification: include_video/figdraw_hip_video_alpha.h).  put_video_422's steps, placement and
+// finish_import; the struct has four slots, and the formats, their rules and the first kernel are its own.  UYVA has planes[0] and [3].
+struct GlyphMaker::AlphaSource {
+  FdhVideoAlphaPlanes frame;      // the caller's, copied
+  const void* planes[va::kPlanes];  // as the device addresses them (a record-only context: null)
+  bool wide[va::kPlanes];           // a run of plane p is one load (va::InParams)
+};
+// what both calls ask of the struct: no context, no device
+static void validate_video_alpha(const Refusal& bad, const FdhVideoAlphaPlanes* f, bool wide[va::kPlanes]) {
+  if (!f || !f->planes[0] || !f->planes[va::kAlpha]) throw bad("null frame or plane");
+  if (f->width <= 0 || f->height <= 0) throw bad("empty frame");
+  if (!va::known(f->format)) throw bad("unknown format");
+  if (f->matrix > FDH_VIDEO_BT2020) throw bad("unknown matrix");
+  if (f->range > FDH_VIDEO_FULL) throw bad("unknown range");
+  if (f->flags & ~(uint32_t)(FDH_VIDEO_CHROMA_LINEAR | FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("unknown flag");
+  if (f->reserved[0] || f->reserved[1]) throw bad("reserved must be 0");
+  if (f->flags & FDH_VIDEO_IGNORE_ALPHA) throw bad("FDH_VIDEO_IGNORE_ALPHA is the sibling call: these formats carry an alpha plane");
+  if (va::full_chroma(f->format) && (f->flags & FDH_VIDEO_CHROMA_LINEAR)) throw bad("FDH_VIDEO_CHROMA_LINEAR is for A420 / UYVA: a 4:4:4 frame has a chroma sample per texel");
+  const bool packed = va::packed(f->format);
+  if (packed && (f->planes[1] || f->planes[2] || f->pitch_bytes[1] || f->pitch_bytes[2])) throw bad("planes[1], planes[2] and their pitches must be 0 for UYVA: a UYVY plane and an alpha plane");
+  if (!packed && (!f->planes[1] || !f->planes[2])) throw bad("null frame or plane");
+  for (int p = 0; p < va::kPlanes; p++) {
+    wide[p] = false;
+    if (!va::has_plane(f->format, p)) continue;
+    const int64_t es = va::element_bytes(f->format, p), row = va::row_bytes(f->format, p, f->width), run = va::run_bytes(f->format, p);
+    if ((uintptr_t)f->planes[p] % (uintptr_t)es || f->pitch_bytes[p] % es)
+      throw bad("planes[" + std::to_string(p) + "] and pitch_bytes[" + std::to_string(p) + "] must be multiples of the " + (es == 4 ? "group size" : "sample size"));
+    if (f->pitch_bytes[p] < row) throw bad("pitch_bytes[" + std::to_string(p) + "] is below a row's bytes");
+    wide[p] = (uintptr_t)f->planes[p] % (uintptr_t)run == 0 && f->pitch_bytes[p] % run == 0 && row >= run;
+  }
+}
+// on a context with a device: the planes as the device addresses them, none of them inside the atlas
+static void video_alpha_on_device(const Refusal& bad, int device, const Atlas& atlas, const FdhVideoAlphaPlanes& f, const void* out[va::kPlanes], bool wide[va::kPlanes]) {
+  for (int p = 0; p < va::kPlanes; p++) {
+    if (!va::has_plane(f.format, p)) continue;
+    const int64_t bytes = (va::rows(f.format, p, f.height) - 1) * f.pitch_bytes[p] + va::row_bytes(f.format, p, f.width);
+    out[p] = device_view_of(device, f.planes[p]);
+    if (!out[p]) throw bad("a plane is neither device memory of the context's device nor page-locked host memory");
+    const uintptr_t lo = (uintptr_t)out[p], hi = lo + (uintptr_t)bytes;
+    for (int l = 0; l < atlas.n_levels(); l++) {
+      const uintptr_t a = (uintptr_t)atlas.level(l), side = (uintptr_t)(atlas.size() >> l);
+      if (lo < a + side * side * 4 && a < hi) throw bad("a plane lies inside the context's own atlas");
+    }
+    // (a page-locked plane's device view need not be aligned as the caller's pointer is: the question is asked of the address the kernel gets)
+    wide[p] = wide[p] && lo % (uintptr_t)va::run_bytes(f.format, p) == 0;
+  }
+}
+void GlyphMaker::put_video_alpha(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoAlphaPlanes* frame, int out_rect[4]) {
+  const Refusal bad{"put_video_alpha"};
+  AlphaSource src{};
+  validate_video_alpha(bad, frame, src.wide);
+  src.frame = *frame;
+  if (atlas.has_device()) {
+    video_alpha_on_device(bad, device, atlas, src.frame, src.planes, src.wide);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.frame.width, src.frame.height);
+  }
+  atlas.make_room(s, src.frame.width, src.frame.height);
+  AtlasEntry& e = atlas.place(s, key, src.frame.width, src.frame.height, out_rect);
+  if (atlas.has_device()) import_video_alpha(s, atlas, e, src);
+}
+void GlyphMaker::update_video_alpha(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoAlphaPlanes* frame) {
+  const Refusal bad{"update_video_alpha"};
+  AlphaSource src{};
+  validate_video_alpha(bad, frame, src.wide);
+  src.frame = *frame;
+  const AtlasEntry* old = atlas.find(key);  // (ahead of the pointers' check and the buffers; begin_update says the same again)
+  if (!old) throw bad("unknown key");
+  if (old->w != src.frame.width || old->h != src.frame.height) throw bad("size mismatch");
+  if (atlas.has_device()) {
+    video_alpha_on_device(bad, device, atlas, src.frame, src.planes, src.wide);
+    reserve_import(glyph_a_, glyph_b_, ink_host_, src.frame.width, src.frame.height);
+  }
+  AtlasEntry& e = atlas.begin_update(bad.who, key, src.frame.width, src.frame.height);
+  e.has_ink = false;  // (the old texels' boxes; import_video_alpha measures the new ones)
+  if (atlas.has_device()) import_video_alpha(s, atlas, e, src);
+}
+// k_video_alpha_import makes levels 0 .. 5; the rest is import_image's (finish_import)
+void GlyphMaker::import_video_alpha(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const AlphaSource& src) {
+  const FdhVideoAlphaPlanes& f = src.frame;
+  va::InParams P{};
+  for (int p = 0; p < va::kPlanes; p++)
+    if (va::has_plane(f.format, p)) { P.plane[p] = src.planes[p]; P.pitch[p] = f.pitch_bytes[p]; P.wide[p] = src.wide[p]; }
+  P.w = f.width; P.h = f.height;
+  P.cw = va::full_chroma(f.format) ? f.width : (f.width + 1) / 2; P.ch = (int)va::rows(f.format, 1, f.height);
+  P.format = f.format; P.flags = f.flags;
+  const int32_t* c = vi::kCoefficients[va::ten_bit(f.format)][f.matrix][f.range];  // (the NV12 row for 8 bit, the P010 row for 10)
+  P.yoff = c[0]; P.coff = c[1]; P.cy = c[2]; P.crv = c[3]; P.cgu = c[4]; P.cgv = c[5]; P.cbu = c[6];
+  P.x = e.x; P.y = e.y;
+  atlas.each_level(e.x, e.y, e.w, e.h, [&](int, int, int, int, int) { P.n_store++; });
+  P.ink = e.w <= ii::kInkMax && e.h <= ii::kInkMax;
+  for (int l = 0; l < ii::kTileLevels; l++) { P.lw[l] = (e.w + (1 << l) - 1) >> l; P.lh[l] = (e.h + (1 << l) - 1) >> l; }
+  for (int l = 0; l < atlas.n_levels(); l++) P.level[l] = atlas.level(l);
+  P.size = atlas.size();
+  P.scratch = glyph_a_.ptr;
+  P.ink_block = ink_host_.dev;
+  launch_video_alpha_import(s, P);
   finish_import(s, atlas, e, P.n_store, P.ink != 0);
 }
 

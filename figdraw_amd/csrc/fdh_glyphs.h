@@ -8,7 +8,8 @@
 
 #include "../../include_glyphs/figdraw_hip_device_image.h"  // FdhDeviceImage
 #include "../../include_glyphs/figdraw_hip_video_frame.h"   // FdhVideoFrame
-#include "../../include_video/figdraw_hip_video_422.h"      // FdhVideoPlanes, through figdraw_hip_video_planar.h; the 4:2:2 formats
+#include "../../include_video/figdraw_hip_video_alpha.h"    // FdhVideoAlphaPlanes; through it figdraw_hip_video_422.h (the 4:2:2 formats) and
+                                                            // figdraw_hip_video_planar.h (FdhVideoPlanes)
 #include "../../include_glyphs/figdraw_hip_cubic_batch.h"  // the two cubic batches; and through it figdraw_hip_cubic.h (fdh_put_glyph_outline_cubic),
                                                             // figdraw_hip_coverage.h (the coverage batch), figdraw_hip_glyphs.h (FdhGlyphOutline, FdhGlyphBatchStats)
 #include "fdh_atlas.h"
@@ -55,6 +56,10 @@ class GlyphMaker final : public AtlasMover {
   // I210 in three planes, YUY2 or UYVY in one
   void put_video_422(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame, int out_rect[4]);
   void update_video_422(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame);
+  // fdh_put_video_alpha and fdh_update_video_alpha (the specification: include_video/figdraw_hip_video_alpha.h): the same of a frame with an
+  // alpha plane, A420, A444 or A410 in four planes, UYVA in two
+  void put_video_alpha(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoAlphaPlanes* frame, int out_rect[4]);
+  void update_video_alpha(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoAlphaPlanes* frame);
   // fdh_compact_atlas (the specification: include_glyphs/figdraw_hip_atlas.h): the atlas's mover
   void move_entries(hipStream_t s, const AtlasView& from, const Atlas& to, const std::vector<MovedEntry>& moved, FdhAtlasMoveStats& stats) override;
   void release();  // the scratch buffers (the stream is idle)
@@ -77,6 +82,8 @@ class GlyphMaker final : public AtlasMover {
   struct PlanarSource;  // a validated FdhVideoPlanes as the device addresses it (fdh_glyphs.cpp)
   void import_video_planes(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const PlanarSource& src);
   void import_video_422(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const PlanarSource& src);  // (the same struct, the 4:2:2 formats)
+  struct AlphaSource;  // a validated FdhVideoAlphaPlanes as the device addresses it (fdh_glyphs.cpp)
+  void import_video_alpha(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const AlphaSource& src);
   // behind the first launch of either: the rest of the chain from the level-5 image in glyph_a_, the wait, the entry's ink boxes
   void finish_import(hipStream_t s, const Atlas& atlas, AtlasEntry& e, int n_store, bool ink);
   // the batches: pass 1 in either format, then passes 2 and 3 of all four (the placement, the tables, the copies, `middle`'s launches, the level chain)

@@ -207,6 +207,13 @@ void launch_video_planar_export(hipStream_t s, const video_planar::OutParams& P)
 namespace video_422 { struct InParams; struct OutParams; }
 void launch_video_422_import(hipStream_t s, const video_422::InParams& P);
 void launch_video_422_export(hipStream_t s, const video_422::OutParams& P);
+// fdh_put_video_alpha, fdh_update_video_alpha and fdh_read_video_alpha (include_video/figdraw_hip_video_alpha.h; k_video_alpha_import.hip,
+// k_video_alpha_export.hip; the parameter blocks: fdh_video_alpha.h): the same two launches for frames with an alpha plane, A420, A444,
+// A410 and UYVA -- a workgroup of 128 per 32 x 32 tile on the way in (launch_image_import_tail finishes its chain too), a workgroup of
+// 256 per 256 x 16 tile (A420) or 256 x 8 tile (the others) on the way out
+namespace video_alpha { struct InParams; struct OutParams; }
+void launch_video_alpha_import(hipStream_t s, const video_alpha::InParams& P);
+void launch_video_alpha_export(hipStream_t s, const video_alpha::OutParams& P);
 // fdh_compact_atlas (include_glyphs/figdraw_hip_atlas.h; k_atlas_move.hip): the rectangles of `records` (fdh_atlas_move.h) from the levels of one
 // atlas into those of another, or from / into the dense buffers of V; `tile_record`: the record of each of the n_tiles tiles, the 1-D grid;
 // `owner`: one bit per texel of the records that share texels with a later rectangle

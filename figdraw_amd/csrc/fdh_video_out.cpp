@@ -2,7 +2,8 @@
 // include_video/figdraw_hip_video_out.h).  No state: a target is checked, turned into k_video_export's parameter block and launched.
 // Behind them the same for three planes: fdh_read_video_planes and fdh_check_video_planes_target (include_video/figdraw_hip_video_planar.h;
 // k_video_planar_export), and for 4:2:2: fdh_read_video_422 and fdh_check_video_422_target (include_video/figdraw_hip_video_422.h;
-// k_video_422_export).
+// k_video_422_export), and with an alpha plane: fdh_read_video_alpha and fdh_check_video_alpha_target
+// (include_video/figdraw_hip_video_alpha.h; k_video_alpha_export).
 #include "fdh_video_out.h"
 
 #include <algorithm>
@@ -14,12 +15,14 @@
 #include "fdh_video_export.h"
 #include "fdh_video_planar.h"
 #include "fdh_video_422.h"
+#include "fdh_video_alpha.h"
 
 namespace fdh {
 namespace video_out {
 namespace ve = video_export;
 namespace vp = video_planar;
 namespace v2 = video_422;
+namespace va = video_alpha;
 
 namespace {
 struct Refusal {
@@ -279,6 +282,89 @@ void read_422(hipStream_t s, int device, const uint32_t* surface, int W, int H, 
   P.yoff = c[0]; P.coff = c[1];
   for (int k = 0; k < 3; k++) { P.ky[k] = c[2 + k]; P.ku[k] = c[5 + k]; P.kv[k] = c[8 + k]; }
   launch_video_422_export(s, P);
+  FDH_HIP(hipStreamSynchronize(s));
+  FDH_HIP(hipGetLastError());
+}
+
+// ---- with an alpha plane: A420, A444, A410 in four planes, UYVA in two (the specification: include_video/figdraw_hip_video_alpha.h)
+namespace {
+// what a checked target with an alpha plane comes to: the rectangle, and per plane it has the bytes from its pointer to its last row's end
+struct LayoutAlpha {
+  int x, y, w, h;
+  __int128 bytes[va::kPlanes];
+  bool wide[va::kPlanes];  // a run of plane p is one store (va::OutParams)
+};
+
+LayoutAlpha check_alpha(const Refusal& bad, const FdhVideoAlphaPlanesTarget* t, int frame_w, int frame_h) {
+  if (!t || !t->planes[0] || !t->planes[va::kAlpha]) throw bad("null target or plane");
+  if (!va::known(t->format)) throw bad("unknown format");
+  if (t->matrix > FDH_VIDEO_BT2020) throw bad("unknown matrix");
+  if (t->range > FDH_VIDEO_FULL) throw bad("unknown range");
+  if (t->flags & ~(uint32_t)(FDH_VIDEO_CHROMA_LINEAR | FDH_VIDEO_STRAIGHT_ALPHA | FDH_VIDEO_IGNORE_ALPHA)) throw bad("unknown flag");
+  if (t->reserved[0] || t->reserved[1]) throw bad("reserved must be 0");
+  if (t->flags & FDH_VIDEO_IGNORE_ALPHA) throw bad("FDH_VIDEO_IGNORE_ALPHA is the sibling call: these formats carry an alpha plane");
+  if (va::full_chroma(t->format) && (t->flags & FDH_VIDEO_CHROMA_LINEAR)) throw bad("FDH_VIDEO_CHROMA_LINEAR is for A420 / UYVA: a 4:4:4 frame has a chroma sample per texel");
+  const bool packed = va::packed(t->format);
+  if (packed && (t->planes[1] || t->planes[2] || t->pitch_bytes[1] || t->pitch_bytes[2])) throw bad("planes[1], planes[2] and their pitches must be 0 for UYVA: a UYVY plane and an alpha plane");
+  if (!packed && (!t->planes[1] || !t->planes[2])) throw bad("null target or plane");
+  if (frame_w <= 0 || frame_h <= 0) throw bad("empty frame");
+  LayoutAlpha L{};
+  L.x = t->rect[0]; L.y = t->rect[1]; L.w = t->rect[2]; L.h = t->rect[3];
+  if (L.w <= 0 || L.h <= 0) { L.x = 0; L.y = 0; L.w = frame_w; L.h = frame_h; }
+  if (L.x < 0 || L.y < 0 || (int64_t)L.x + L.w > frame_w || (int64_t)L.y + L.h > frame_h) throw bad("rectangle outside the frame");
+  if (t->format == va::kA420 && ((L.x | L.y) & 1)) throw bad("the rectangle's x and y must be even for A420");
+  if (packed && (L.x & 1)) throw bad("the rectangle's x must be even for UYVA");
+  for (int p = 0; p < va::kPlanes; p++) {
+    if (!va::has_plane(t->format, p)) continue;
+    const int64_t es = va::element_bytes(t->format, p), row = va::row_bytes(t->format, p, L.w), run = va::run_bytes(t->format, p);
+    if ((uintptr_t)t->planes[p] % (uintptr_t)es || t->pitch_bytes[p] % es)
+      throw bad("planes[" + std::to_string(p) + "] and pitch_bytes[" + std::to_string(p) + "] must be multiples of the " + (es == 4 ? "group size" : "sample size"));
+    if (t->pitch_bytes[p] < row) throw bad("pitch_bytes[" + std::to_string(p) + "] is below a row's bytes");
+    L.bytes[p] = (__int128)(va::rows(t->format, p, L.h) - 1) * t->pitch_bytes[p] + (__int128)row;
+    L.wide[p] = (uintptr_t)t->planes[p] % (uintptr_t)run == 0 && t->pitch_bytes[p] % run == 0 && row >= run;
+  }
+  for (int p = 0; p < va::kPlanes; p++)
+    for (int q = p + 1; q < va::kPlanes; q++)
+      if (va::has_plane(t->format, p) && va::has_plane(t->format, q) && overlap((uintptr_t)t->planes[p], L.bytes[p], (uintptr_t)t->planes[q], L.bytes[q]))
+        throw bad("planes " + std::to_string(p) + " and " + std::to_string(q) + " overlap");
+  return L;
+}
+}  // namespace
+
+void check_alpha_target(const char* who, const FdhVideoAlphaPlanesTarget* t, int frame_w, int frame_h) { (void)check_alpha(Refusal{who}, t, frame_w, frame_h); }
+
+void read_alpha(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoAlphaPlanesTarget* target, const Own* own, int n_own) {
+  const Refusal bad{"read_video_alpha"};
+  const LayoutAlpha L = check_alpha(bad, target, W, H);
+  const FdhVideoAlphaPlanesTarget t = *target;
+  void* planes[va::kPlanes] = {nullptr, nullptr, nullptr, nullptr};
+  for (int p = 0; p < va::kPlanes; p++) {
+    if (!va::has_plane(t.format, p)) continue;
+    planes[p] = device_view_of(device, t.planes[p]);
+    if (!planes[p]) throw bad("a plane is neither device memory of the context's device nor page-locked host memory");
+    for (int k = 0; k < n_own; k++)
+      if (own[k].base && overlap((uintptr_t)planes[p], L.bytes[p], (uintptr_t)own[k].base, (__int128)own[k].bytes))
+        throw bad(std::string("a plane overlaps the context's own ") + own[k].what);
+  }
+  for (int p = 0; p < va::kPlanes; p++)
+    for (int q = p + 1; q < va::kPlanes; q++)
+      if (planes[p] && planes[q] && overlap((uintptr_t)planes[p], L.bytes[p], (uintptr_t)planes[q], L.bytes[q])) throw bad("planes " + std::to_string(p) + " and " + std::to_string(q) + " overlap");
+  va::OutParams P{};
+  P.src = surface + (size_t)L.y * W + L.x;
+  P.src_pitch = W;
+  P.w = L.w; P.h = L.h;
+  P.format = t.format; P.flags = t.flags;
+  P.wide_src = (uintptr_t)P.src % 16 == 0 && W % 4 == 0 && L.w >= va::kRun;
+  for (int p = 0; p < va::kPlanes; p++) {
+    if (!planes[p]) continue;
+    P.plane[p] = planes[p]; P.pitch[p] = t.pitch_bytes[p];
+    // (a page-locked plane's device view need not be aligned as the caller's pointer is: the question is asked of the address the kernel gets)
+    P.wide[p] = L.wide[p] && (uintptr_t)planes[p] % (uintptr_t)va::run_bytes(t.format, p) == 0;
+  }
+  const int32_t* c = ve::kCoefficients[va::ten_bit(t.format)][t.matrix][t.range];  // (the NV12 row for 8 bit, the P010 row for 10)
+  P.yoff = c[0]; P.coff = c[1];
+  for (int k = 0; k < 3; k++) { P.ky[k] = c[2 + k]; P.ku[k] = c[5 + k]; P.kv[k] = c[8 + k]; }
+  launch_video_alpha_export(s, P);
   FDH_HIP(hipStreamSynchronize(s));
   FDH_HIP(hipGetLastError());
 }

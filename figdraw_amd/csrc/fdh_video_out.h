@@ -8,7 +8,8 @@
 #include <cstdint>
 
 #include "../../include_video/figdraw_hip_video_out.h"     // FdhVideoTarget
-#include "../../include_video/figdraw_hip_video_422.h"  // FdhVideoPlanesTarget, through figdraw_hip_video_planar.h; the 4:2:2 formats
+#include "../../include_video/figdraw_hip_video_alpha.h"  // FdhVideoAlphaPlanesTarget; through it figdraw_hip_video_422.h (the 4:2:2 formats) and
+                                                          // figdraw_hip_video_planar.h (FdhVideoPlanesTarget)
 
 namespace fdh {
 namespace video_out {
@@ -34,6 +35,12 @@ void read_planes(hipStream_t s, int device, const uint32_t* surface, int W, int 
 void check_422_target(const char* who, const FdhVideoPlanesTarget* t, int frame_w, int frame_h);
 // fdh_read_video_422 behind the context's part: one launch of k_video_422_export on `s`, and the wait for it
 void read_422(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoPlanesTarget* t, const Own* own, int n_own);
+
+// The same with an alpha plane, A420, A444 and A410 in four planes, UYVA in two (the specification: include_video/figdraw_hip_video_alpha.h).
+// fdh_check_video_alpha_target: every rule that needs no device
+void check_alpha_target(const char* who, const FdhVideoAlphaPlanesTarget* t, int frame_w, int frame_h);
+// fdh_read_video_alpha behind the context's part: one launch of k_video_alpha_export on `s`, and the wait for it
+void read_alpha(hipStream_t s, int device, const uint32_t* surface, int W, int H, const FdhVideoAlphaPlanesTarget* t, const Own* own, int n_own);
 
 }  // namespace video_out
 }  // namespace fdh

@@ -75,7 +75,7 @@
  * refusing every format value from FDH_VIDEO_I422 on, and these calls refuse every value outside FDH_VIDEO_I422 .. FDH_VIDEO_UYVY.
  *
  * NOT HERE.  The semi-planar 4:2:2 formats NV16 and P210 / P216, the packed 10-bit formats Y210 and v210, transfer functions, and calls
- * that do not wait for the stream.
+ * that do not wait for the stream.  Alpha planes are in figdraw_hip_video_alpha.h: UYVA there is this header's UYVY plane and an alpha plane.
  *
  * ON THE DEVICE.  One kernel each way, a lane per run of EIGHT texels of one row: eight luma samples and four of either chroma plane, or
  * the four groups, 16 bytes, of a packed row.  The way in, k_video_422_import: a workgroup of 128 per 32 x 32 tile of the image; level 0

@@ -65,7 +65,8 @@
  * refusing every format value above FDH_VIDEO_P010.
  *
  * NOT HERE.  4:2:2 (I422, I210, YUY2, UYVY) has calls of its own, with these structs: figdraw_hip_video_422.h; its formats take the values
- * from 7 on, which the calls here refuse.  Transfer functions, alpha planes and calls that do not wait for the stream are out of scope as well.
+ * from 7 on, which the calls here refuse.  Alpha planes (A420, A444, A410, UYVA) have calls of their own too: figdraw_hip_video_alpha.h, values
+ * from 11 on.  Transfer functions and calls that do not wait for the stream are out of scope.
  *
  * ON THE DEVICE.  One kernel each way, a lane per run of EIGHT texels, so that a lane's narrowest access is the four bytes of an I420
  * chroma run (a run of four texels, the siblings' shape, would touch two bytes of either chroma plane).  The way in,
