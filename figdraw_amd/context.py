@@ -68,6 +68,11 @@ class DeviceImage(C.Structure):  # FdhDeviceImage (include_glyphs/figdraw_hip_de
                 ("format", C.c_uint32), ("channels", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ImageBatchStats(C.Structure):  # FdhImageBatchStats (include_glyphs/figdraw_hip_device_images.h)
+    _fields_ = [("images", C.c_int32), ("written", C.c_int32), ("dropped_by_growth", C.c_int32), ("tiles", C.c_int32), ("launches", C.c_int32),
+                ("reserved", C.c_int32), ("bytes_copied", C.c_int64)]
+
+
 IMAGE_RGBA8, IMAGE_PLANAR_F32, IMAGE_PLANAR_F16 = 0, 1, 2  # FdhDeviceImage.format
 IMAGE_STRAIGHT_ALPHA = 1                                   # FdhDeviceImage.flags
 
@@ -253,6 +258,33 @@ def tensor_image(t, straight_alpha: bool = False) -> DeviceImage:
     return DeviceImage(t.data_ptr(), w, h, pitch, plane, IMAGE_PLANAR_F32 if dtype == "float32" else IMAGE_PLANAR_F16, c, flags, 0)
 
 
+class _TensorSlice:
+    """index i along the first axis of a tensor, as tensor_image reads a tensor: the same memory, no copy"""
+
+    def __init__(self, t, i):
+        self.dtype, self.shape, self._stride, self._es = t.dtype, tuple(t.shape)[1:], tuple(t.stride())[1:], int(t.element_size())
+        self._ptr = int(t.data_ptr()) + i * int(t.stride()[0]) * self._es
+
+    def data_ptr(self):
+        return self._ptr
+
+    def stride(self):
+        return self._stride
+
+    def element_size(self):
+        return self._es
+
+
+def tensor_images(tensors, straight_alpha: bool = False):
+    """the FdhDeviceImages of a sequence of what tensor_image takes, or of one N x C x H x W / N x H x W x 4 tensor cut along its first axis
+    without a copy"""
+    if hasattr(tensors, "data_ptr") and hasattr(tensors, "shape"):
+        if len(tensors.shape) != 4:
+            raise ValueError(f"one tensor for a batch is N x C x H x W or N x H x W x 4, not {tuple(tensors.shape)}")
+        tensors = [_TensorSlice(tensors, i) for i in range(int(tensors.shape[0]))]
+    return [tensor_image(t, straight_alpha) for t in tensors]
+
+
 def build(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 the C-ABI library in-tree (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -339,6 +371,11 @@ def load():
     if hasattr(L, "fdh_put_image_device"):  # include_glyphs/figdraw_hip_device_image.h
         L.fdh_put_image_device.argtypes = [vp, C.c_int64, C.POINTER(DeviceImage), C.c_int * 4]
         L.fdh_update_image_device.argtypes = [vp, C.c_int64, C.POINTER(DeviceImage)]
+    if hasattr(L, "fdh_put_images_device"):  # include_glyphs/figdraw_hip_device_images.h
+        L.fdh_put_images_device.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.fdh_update_images_device.argtypes = [vp, vp, vp, C.c_int]
+        L.fdh_image_batch_stats.argtypes = [vp, C.POINTER(ImageBatchStats)]
+        L.fdh_sizeof_device_image.argtypes = []
     if hasattr(L, "fdh_put_video_frame"):  # include_glyphs/figdraw_hip_video_frame.h
         L.fdh_put_video_frame.argtypes = [vp, C.c_int64, C.POINTER(VideoFrame), C.c_int * 4]
         L.fdh_update_video_frame.argtypes = [vp, C.c_int64, C.POINTER(VideoFrame)]
@@ -818,6 +855,62 @@ class HipContext:
         is un-premultiplied first (fdh_read_video_alpha, include_video/figdraw_hip_video_alpha.h).  The planes are complete on return."""
         t = video_alpha_planes_target(ptrs, pitches, format, matrix, range, flags, rect)
         self._ck(self.L.fdh_read_video_alpha(self.h, C.byref(t)))
+
+    @staticmethod
+    def _device_image_arrays(items):
+        """items: (key, DeviceImage), or (key, ptr, width, height, pitch_bytes[, format, channels, plane_bytes, straight_alpha]) as
+        put_image_device takes them -> (n, the keys, the FdhDeviceImage array)"""
+        items = list(items)
+        n = len(items)
+        keys, arr = (C.c_int64 * max(n, 1))(), (DeviceImage * max(n, 1))()
+        for i, it in enumerate(items):
+            keys[i] = int(it[0])
+            if isinstance(it[1], DeviceImage):
+                C.memmove(C.byref(arr, i * C.sizeof(DeviceImage)), C.byref(it[1]), C.sizeof(DeviceImage))
+                continue
+            ptr, width, height, pitch = it[1:5]
+            fmt, channels, plane, straight = (tuple(it[5:]) + (IMAGE_RGBA8, 4, 0, False)[len(it) - 5:])[:4]
+            arr[i] = DeviceImage(ptr, int(width), int(height), int(pitch), int(plane), int(fmt), int(channels), IMAGE_STRAIGHT_ALPHA if straight else 0, 0)
+        return n, keys, arr
+
+    def put_images_device(self, items):
+        """a batch of images from device (or page-locked host) memory in one call (fdh_put_images_device, include_glyphs/
+        figdraw_hip_device_images.h): `items` is a sequence of (key, DeviceImage) or of (key, ptr, width, height, pitch_bytes[, format, channels,
+        plane_bytes, straight_alpha]).  What the same put_image_device calls in order would leave, from at most four launches and one wait.
+        -> the rectangles, one (x, y, w, h) per item"""
+        n, keys, arr = self._device_image_arrays(items)
+        out = ((C.c_int * 4) * max(n, 1))()
+        self._ck(self.L.fdh_put_images_device(self.h, C.addressof(keys), C.addressof(arr), n, C.addressof(out)))
+        return [tuple(out[i]) for i in range(n)]
+
+    def update_images_device(self, items):
+        """new texels for a batch of entries of the same sizes (fdh_update_images_device); `items` as in put_images_device"""
+        n, keys, arr = self._device_image_arrays(items)
+        self._ck(self.L.fdh_update_images_device(self.h, C.addressof(keys), C.addressof(arr), n))
+
+    def image_batch_stats(self) -> dict:
+        """what the last put_images_device or update_images_device that passed validation did: images, written, dropped_by_growth, tiles,
+        launches, bytes_copied"""
+        st = ImageBatchStats()
+        self._ck(self.L.fdh_image_batch_stats(self.h, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in ImageBatchStats._fields_ if name != "reserved"}
+
+    def put_image_tensors(self, keys, tensors, straight_alpha=False):
+        """put_images_device of tensors (tensor_images: a sequence of what put_image_tensor takes, or one N x C x H x W / N x H x W x 4 tensor
+        cut along its first axis without a copy).  -> the rectangles"""
+        images = tensor_images(tensors, straight_alpha)
+        keys = list(keys)
+        if len(keys) != len(images):
+            raise ValueError(f"{len(keys)} keys for {len(images)} images")
+        return self.put_images_device(zip(keys, images))
+
+    def update_image_tensors(self, keys, tensors, straight_alpha=False):
+        """update_images_device of tensors, as put_image_tensors takes them"""
+        images = tensor_images(tensors, straight_alpha)
+        keys = list(keys)
+        if len(keys) != len(images):
+            raise ValueError(f"{len(keys)} keys for {len(images)} images")
+        self.update_images_device(zip(keys, images))
 
     def put_image_tensor(self, key, tensor, straight_alpha=False):
         """put_image_device of a tensor (tensor_image: H x W x 4 uint8, or C x H x W / H x W float32 or float16).  -> the rectangle"""

@@ -16,6 +16,7 @@
 #include "../../include_glyphs/figdraw_hip_cubic.h"
 #include "../../include_glyphs/figdraw_hip_image_sdf.h"
 #include "../../include_glyphs/figdraw_hip_device_image.h"
+#include "../../include_glyphs/figdraw_hip_device_images.h"
 #include "../../include_glyphs/figdraw_hip_video_frame.h"
 #include "../../include_glyphs/figdraw_hip_atlas.h"
 #include "../../include_video/figdraw_hip_video_out.h"
@@ -230,6 +231,20 @@ int fdh_put_image_device(FdhContext* c, int64_t key, const FdhDeviceImage* img, 
 int fdh_update_image_device(FdhContext* c, int64_t key, const FdhDeviceImage* img) {
   return guard([&] { C(c)->update_image_device(key, img); });
 }
+// batches of them (include_glyphs/figdraw_hip_device_images.h)
+int fdh_put_images_device(FdhContext* c, const int64_t* keys, const FdhDeviceImage* images, int n, int (*out_rects)[4]) {
+  return guard([&] { C(c)->put_images_device(keys, images, n, out_rects); });
+}
+int fdh_update_images_device(FdhContext* c, const int64_t* keys, const FdhDeviceImage* images, int n) {
+  return guard([&] { C(c)->update_images_device(keys, images, n); });
+}
+int fdh_image_batch_stats(FdhContext* c, FdhImageBatchStats* out) {
+  return guard([&] {
+    if (!out) throw fdh::Error(FDH_ERR_INVALID, "fdh_image_batch_stats: null pointer");
+    *out = C(c)->image_batch_stats();
+  });
+}
+int fdh_sizeof_device_image(void) { return (int)sizeof(FdhDeviceImage); }
 // decoded video frames (include_glyphs/figdraw_hip_video_frame.h)
 int fdh_put_video_frame(FdhContext* c, int64_t key, const FdhVideoFrame* frame, int out_rect[4]) {
   return guard([&] { C(c)->put_video_frame(key, frame, out_rect); });

@@ -71,6 +71,9 @@ class Context : public Recorder {
   void put_image_sdf_of(int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) { sync(); glyphs_.put_image_sdf_of(stream_, atlas_, src_key, key, channel, pad, flags, out_rect); }
   void put_image_device(int64_t key, const FdhDeviceImage* img, int out_rect[4]) { sync(); glyphs_.put_device_image(stream_, atlas_, device_, key, img, out_rect); }
   void update_image_device(int64_t key, const FdhDeviceImage* img) { sync(); glyphs_.update_device_image(stream_, atlas_, device_, key, img); }
+  void put_images_device(const int64_t* keys, const FdhDeviceImage* images, int n, int (*out_rects)[4]) { sync(); glyphs_.put_device_images(stream_, atlas_, device_, keys, images, n, out_rects); }
+  void update_images_device(const int64_t* keys, const FdhDeviceImage* images, int n) { sync(); glyphs_.update_device_images(stream_, atlas_, device_, keys, images, n); }
+  const FdhImageBatchStats& image_batch_stats() const { return glyphs_.image_batch_stats(); }
   void put_video_frame(int64_t key, const FdhVideoFrame* frame, int out_rect[4]) { sync(); glyphs_.put_video_frame(stream_, atlas_, device_, key, frame, out_rect); }
   void update_video_frame(int64_t key, const FdhVideoFrame* frame) { sync(); glyphs_.update_video_frame(stream_, atlas_, device_, key, frame); }
   void put_video_planes(int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) { sync(); glyphs_.put_video_planes(stream_, atlas_, device_, key, frame, out_rect); }

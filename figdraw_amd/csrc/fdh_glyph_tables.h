@@ -22,11 +22,12 @@ inline int level_size(int v, int l) { return (v + (1 << l) - 1) >> l; }
 inline size_t batch_tiles(const msdf::BatchGlyph& t, bool thin_tiles) {
   return thin_tiles || (t.w > 1 && t.h > 1) ? (size_t)((t.w + 7) / 8) * ((t.h + 7) / 8) : 0;
 }
-inline size_t owner_bits(const msdf::BatchGlyph& t, int n_levels) {
+inline size_t owner_bits(int w, int h, int n_levels) {
   size_t bits = 0;
-  for (int l = msdf::kOwnerLevel; l < n_levels && level_size(t.w, l) > 1 && level_size(t.h, l) > 1; l++) bits += (size_t)level_size(t.w, l) * level_size(t.h, l);
+  for (int l = msdf::kOwnerLevel; l < n_levels && level_size(w, l) > 1 && level_size(h, l) > 1; l++) bits += (size_t)level_size(w, l) * level_size(h, l);
   return bits;
 }
+inline size_t owner_bits(const msdf::BatchGlyph& t, int n_levels) { return owner_bits(t.w, t.h, n_levels); }
 // the words of the tables of a whole batch in an atlas of at most `n_levels` levels: what the table buffer is reserved for before the
 // first placement, whatever atlas the batch ends in
 inline size_t batch_table_words(const std::vector<msdf::BatchGlyph>& tab, bool thin_tiles, int n_levels) {
@@ -36,6 +37,41 @@ inline size_t batch_table_words(const std::vector<msdf::BatchGlyph>& tab, bool t
     all_owner_words += (owner_bits(t, n_levels) + 31) / 32;
   }
   return tab.size() * kBatchGlyphWords + all_tiles + all_owner_words + 1;
+}
+// The owner bits of m placed rectangles r[0 .. m - 1] (records with x, y, w, h and owner_off, the record's first bit; a batch of glyphs here, a
+// batch of images in fdh_image_batch.h): level after level from msdf::kOwnerLevel on, the level rectangles painted in array order into a
+// map of the box they span; a record gets the bits of the texels that are still its own.  `owner`: zeroed words.
+template <typename Rect>
+inline void paint_owner_bits(const Rect* r, int m, int n_levels, uint32_t* owner) {
+  std::vector<int32_t> map;
+  for (int l = msdf::kOwnerLevel; l < n_levels; l++) {
+    int bx0 = INT_MAX, by0 = INT_MAX, bx1 = 0, by1 = 0;
+    auto has_level = [&](const Rect& t) { return level_size(t.w, l) > 1 && level_size(t.h, l) > 1; };
+    for (int k = 0; k < m; k++) {
+      const Rect& t = r[k];
+      if (!has_level(t)) continue;
+      bx0 = std::min(bx0, t.x >> l); by0 = std::min(by0, t.y >> l);
+      bx1 = std::max(bx1, (t.x >> l) + level_size(t.w, l)); by1 = std::max(by1, (t.y >> l) + level_size(t.h, l));
+    }
+    if (bx1 <= bx0) break;  // no rectangle reaches this level, nor a deeper one
+    const int bw = bx1 - bx0;
+    map.assign((size_t)bw * (by1 - by0), -1);
+    for (int k = 0; k < m; k++) {
+      const Rect& t = r[k];
+      if (!has_level(t)) continue;
+      for (int j = 0; j < level_size(t.h, l); j++)
+        for (int i = 0; i < level_size(t.w, l); i++) map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] = k;
+    }
+    for (int k = 0; k < m; k++) {
+      const Rect& t = r[k];
+      if (!has_level(t)) continue;
+      uint32_t bit = t.owner_off;
+      for (int d = msdf::kOwnerLevel; d < l; d++) bit += (uint32_t)(level_size(t.w, d) * level_size(t.h, d));
+      for (int j = 0; j < level_size(t.h, l); j++)
+        for (int i = 0; i < level_size(t.w, l); i++, bit++)
+          if (map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] == k) owner[bit >> 5] |= 1u << (bit & 31u);
+    }
+  }
 }
 // The tables of glyphs first .. first + m - 1 as the batched kernels read them: the glyph records (their offsets filled in here, edge_off
 // made relative to the first glyph's), one word per tile naming its glyph, and the owner bits: level after level from msdf::kOwnerLevel
@@ -61,35 +97,7 @@ inline void batch_tables(std::vector<msdf::BatchGlyph>& tab, int first, int m, b
     const uint32_t end = k + 1 < m ? tab[(size_t)(first + k + 1)].first_tile : n_tiles;
     for (uint32_t j = t.first_tile; j < end; j++) tile_glyph[j] = (uint32_t)k;
   }
-  std::vector<int32_t> map;
-  for (int l = msdf::kOwnerLevel; l < n_levels; l++) {
-    int bx0 = INT_MAX, by0 = INT_MAX, bx1 = 0, by1 = 0;
-    auto has_level = [&](const msdf::BatchGlyph& t) { return level_size(t.w, l) > 1 && level_size(t.h, l) > 1; };
-    for (int k = 0; k < m; k++) {
-      const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
-      if (!has_level(t)) continue;
-      bx0 = std::min(bx0, t.x >> l); by0 = std::min(by0, t.y >> l);
-      bx1 = std::max(bx1, (t.x >> l) + level_size(t.w, l)); by1 = std::max(by1, (t.y >> l) + level_size(t.h, l));
-    }
-    if (bx1 <= bx0) break;  // no glyph reaches this level, nor a deeper one
-    const int bw = bx1 - bx0;
-    map.assign((size_t)bw * (by1 - by0), -1);
-    for (int k = 0; k < m; k++) {
-      const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
-      if (!has_level(t)) continue;
-      for (int j = 0; j < level_size(t.h, l); j++)
-        for (int i = 0; i < level_size(t.w, l); i++) map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] = k;
-    }
-    for (int k = 0; k < m; k++) {
-      const msdf::BatchGlyph& t = tab[(size_t)(first + k)];
-      if (!has_level(t)) continue;
-      uint32_t bit = t.owner_off;
-      for (int d = msdf::kOwnerLevel; d < l; d++) bit += (uint32_t)(level_size(t.w, d) * level_size(t.h, d));
-      for (int j = 0; j < level_size(t.h, l); j++)
-        for (int i = 0; i < level_size(t.w, l); i++, bit++)
-          if (map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] == k) owner[bit >> 5] |= 1u << (bit & 31u);
-    }
-  }
+  paint_owner_bits(&tab[(size_t)first], m, n_levels, owner);
   T->n_tiles = n_tiles; T->n_edges = n_edges;
 }
 

@@ -6,12 +6,14 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <exception>
 #include <string>
+#include <unordered_set>
 
 #include "fdh_kernels.h"
 #include "fdh_atlas_move.h"
-#include "fdh_image_import.h"
+#include "fdh_image_batch.h"  // and through it fdh_image_import.h
 #include "fdh_video_import.h"
 #include "fdh_video_planar.h"
 #include "fdh_video_422.h"
@@ -21,6 +23,7 @@
 namespace fdh {
 namespace mc = msdf::cubic;
 namespace ii = image_import;
+namespace ib = image_batch;
 namespace vi = video_import;
 namespace vp = video_planar;
 namespace v2 = video_422;
@@ -374,6 +377,15 @@ void GlyphMaker::import_image(hipStream_t s, const Atlas& atlas, AtlasEntry& e, 
   launch_image_import(s, P);
   finish_import(s, atlas, e, P.n_store, P.ink != 0);
 }
+// an entry's sixteen ink boxes from the folded blocks (fold_ink)
+static void set_ink(AtlasEntry& e, const int32_t got[ii::kInkWords]) {
+  for (int k = 0; k < kInkLevels; k++) {  // (a box no texel grew: empty, at the origin)
+    const int32_t *a = got + 4 * k, *c = got + 32 + 4 * k;
+    e.ink_a[k] = a[2] ? InkBox{(int16_t)a[0], (int16_t)a[1], (int16_t)a[2], (int16_t)a[3]} : InkBox{0, 0, 0, 0};
+    e.ink_rgb[k] = c[2] ? InkBox{(int16_t)c[0], (int16_t)c[1], (int16_t)c[2], (int16_t)c[3]} : InkBox{0, 0, 0, 0};
+  }
+  e.has_ink = true;
+}
 void GlyphMaker::finish_import(hipStream_t s, const Atlas& atlas, AtlasEntry& e, int n_store, bool ink) {
   uint32_t *cur = glyph_a_.ptr, *nxt = glyph_b_.ptr;
   int l = ii::kTileLevels - 1, cw = (e.w + (1 << l) - 1) >> l, ch = (e.h + (1 << l) - 1) >> l;
@@ -396,10 +408,219 @@ void GlyphMaker::finish_import(hipStream_t s, const Atlas& atlas, AtlasEntry& e,
   if (!ink) return;
   int32_t got[ii::kInkWords];
   ii::fold_ink(ink_host_.ptr, tiles, got);
-  for (int k = 0; k < kInkLevels; k++) {  // (a box no texel grew: empty, at the origin)
-    const int32_t *a = got + 4 * k, *c = got + 32 + 4 * k;
-    e.ink_a[k] = a[2] ? InkBox{(int16_t)a[0], (int16_t)a[1], (int16_t)a[2], (int16_t)a[3]} : InkBox{0, 0, 0, 0};
-    e.ink_rgb[k] = c[2] ? InkBox{(int16_t)c[0], (int16_t)c[1], (int16_t)c[2], (int16_t)c[3]} : InkBox{0, 0, 0, 0};
+  set_ink(e, got);
+}
+
+// ---- batches of device images (the specification: include_glyphs/figdraw_hip_device_images.h).  What n single calls do, in the glyph batches'
+// three passes: every image is validated; every image is placed (an update: begun), in order; then the images that are still in the atlas
+// get their texels from one launch per format present and one for the tails, over the tables of fdh_image_batch.h.
+template <typename Item, typename PlacedAt>  // (pass 2 of every batch; with the glyph batches below)
+static std::exception_ptr place_batch(hipStream_t s, Atlas& atlas, int n, int (*out_rects)[4], Stored stored, Item item, PlacedAt placed_at, int* first, int* placed);
+struct GlyphMaker::ImageBatch {
+  std::vector<ii::BatchImage> tab;    // pass 1: the source as the device addresses it, extents, format, channels, flags, wide; pass 2: the place
+  std::vector<AtlasEntry*> entries;   // pass 2: the entries (a placement never moves the ones behind the last growth)
+  std::vector<const void*> sources;   // the callers' pointers: what a copy to the host starts from
+};
+// the source's bytes from `data` to its last element's end
+static int64_t source_bytes(const FdhDeviceImage& g) {
+  const int64_t element = g.format == FDH_IMAGE_PLANAR_F16 ? 2 : 4;
+  const int64_t planes = g.format != FDH_IMAGE_RGBA8 && g.channels > 1 ? g.channels : 1;
+  return (planes - 1) * g.plane_bytes + (int64_t)(g.height - 1) * g.pitch_bytes + (int64_t)g.width * element;
+}
+// Pass 1 of both batches.  Nothing behind it refuses an image.
+void GlyphMaker::validate_device_images(const char* who, const Atlas& atlas, int device, const int64_t* keys, const FdhDeviceImage* images, int n, bool update, ImageBatch* B) {
+  const Refusal bad{who};
+  if (n < 0 || (n > 0 && (!keys || !images))) throw bad("bad image array");
+  if (n > ib::kMaxImages) throw bad("at most 65535 images");
+  B->tab.assign((size_t)n, ii::BatchImage{});
+  B->entries.assign((size_t)n, nullptr);
+  B->sources.assign((size_t)n, nullptr);
+  std::unordered_set<int64_t> seen;
+  int64_t tiles = 0;
+  for (int i = 0; i < n; i++) {
+    const FdhDeviceImage& g = images[i];
+    const bool wide = validate_device_image(bad, &g);
+    if (g.width > ii::kBatchMaxExtent || g.height > ii::kBatchMaxExtent) throw bad("an image of a batch is at most 2048 x 2048");
+    if (!seen.insert(keys[i]).second) throw bad("a key occurs twice");
+    if (update) {
+      const AtlasEntry* old = atlas.find(keys[i]);
+      if (!old) throw bad("unknown key");
+      if (old->w != g.width || old->h != g.height) throw bad("size mismatch");
+    }
+    tiles += (int64_t)ib::covered_tiles(g.width, g.height);
+    ii::BatchImage& t = B->tab[(size_t)i];
+    t.data = g.data; t.pitch_bytes = g.pitch_bytes; t.plane_bytes = g.plane_bytes;
+    t.w = g.width; t.h = g.height;
+    t.format = g.format; t.channels = g.channels; t.flags = g.flags;
+    t.wide = wide && g.width >= 4 ? 1 : 0;
+    B->sources[(size_t)i] = g.data;
+  }
+  if (tiles > ib::kMaxTiles) throw bad("at most 2^18 tiles in a batch");
+  if (!atlas.has_device()) return;
+  for (int i = 0; i < n; i++) {
+    ii::BatchImage& t = B->tab[(size_t)i];
+    t.data = device_address(bad, device, images[i].data);
+    const char *lo = static_cast<const char*>(t.data), *hi = lo + source_bytes(images[i]);
+    for (int l = 0; l < atlas.n_levels(); l++) {
+      const char* level = reinterpret_cast<const char*>(atlas.level(l));
+      if (lo < level + ((size_t)(atlas.size() >> l) * (atlas.size() >> l)) * 4 && level < hi) throw bad("the source lies in the context's own atlas");
+    }
+  }
+}
+void GlyphMaker::put_device_images(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhDeviceImage* images, int n, int (*out_rects)[4]) {
+  ImageBatch B;
+  validate_device_images("put_images_device", atlas, device, keys, images, n, false, &B);
+  image_stats_ = FdhImageBatchStats{};
+  image_stats_.images = n;
+  if (n == 0) return;
+  if (atlas.has_device()) reserve_image_batch(B);
+  // ---- pass 2: the places (keep mode: room for all images of the batch at once, before any of them has a place)
+  if (atlas.keep()) {
+    std::vector<int> wh((size_t)n * 2);
+    for (int i = 0; i < n; i++) { wh[(size_t)i * 2] = images[i].width; wh[(size_t)i * 2 + 1] = images[i].height; }
+    atlas.make_room(s, reinterpret_cast<const int (*)[2]>(wh.data()), n);
+  }
+  int first = 0, placed = 0;
+  std::exception_ptr failed = place_batch(s, atlas, n, out_rects, Stored::chain,
+                                          [&](int i, int64_t* key, int* w, int* h) { *key = keys[i]; *w = images[i].width; *h = images[i].height; },
+                                          [&](int i, AtlasEntry& e) { B.tab[(size_t)i].x = e.x; B.tab[(size_t)i].y = e.y; B.entries[(size_t)i] = &e; }, &first, &placed);
+  image_stats_.written = placed - first;
+  image_stats_.dropped_by_growth = first;
+  // ---- pass 3: the texels of images first .. placed - 1
+  if (placed > first) make_device_images(s, atlas, B, first, placed - first);
+  if (failed) std::rethrow_exception(failed);
+}
+void GlyphMaker::update_device_images(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhDeviceImage* images, int n) {
+  ImageBatch B;
+  validate_device_images("update_images_device", atlas, device, keys, images, n, true, &B);
+  image_stats_ = FdhImageBatchStats{};
+  image_stats_.images = n;
+  if (n == 0) return;
+  if (atlas.has_device()) reserve_image_batch(B);
+  for (int i = 0; i < n; i++) {
+    AtlasEntry& e = atlas.begin_update("update_images_device", keys[i], images[i].width, images[i].height);
+    e.has_ink = false;  // (the old texels' boxes; pass 3 measures the new ones)
+    B.tab[(size_t)i].x = e.x; B.tab[(size_t)i].y = e.y;
+    B.entries[(size_t)i] = &e;
+  }
+  image_stats_.written = n;
+  make_device_images(s, atlas, B, 0, n);
+}
+// the buffers of a whole batch, before any placement as every put reserves: the tables whatever atlas the batch ends in, a texel of
+// scratch per tile, an ink block per tile of an image that gets ink boxes
+void GlyphMaker::reserve_image_batch(const ImageBatch& B) {
+  size_t tiles = 0, ink_tiles = 0;
+  for (const ii::BatchImage& t : B.tab) {
+    const size_t n = ib::table_tiles(t.w, t.h);
+    tiles += n;
+    if (ib::has_ink(t.w, t.h)) ink_tiles += n;
+  }
+  glyph_tab_.reserve(ib::table_words(B.tab, kMaxMips));
+  glyph_a_.reserve(std::max<size_t>(tiles, 1));
+  ink_host_.reserve_exact(std::max<size_t>(ink_tiles, ii::kInkTiles) * ii::kInkWords);
+}
+// A planar value as the texel's byte, the kernels' import_byte (k_image_import.hip) for the few elements the host converts itself: the one
+// row or column of an image 1 texel wide or high, of which nothing is stored and which therefore has no tile in any launch.
+static uint32_t host_import_byte(float v) {
+  if (v != v) return 0u;
+  const float c = std::fmin(std::fmax(v, 0.0f), 1.0f);
+  return (uint32_t)std::nearbyint(c * 255.0f);
+}
+// the texels of such an image from `raw`: its planes one after the other, each n = w * h elements
+static void host_import_line(const ii::BatchImage& t, const uint8_t* raw, std::vector<uint32_t>* out) {
+  const size_t n = (size_t)t.w * t.h;
+  out->resize(n);
+  const bool straight = (t.flags & ii::kStraightAlpha) != 0;
+  for (size_t i = 0; i < n; i++) {
+    uint32_t r, g, b, a;
+    if (t.format == ii::kRgba8) {
+      uint32_t px;
+      std::memcpy(&px, raw + 4 * i, 4);
+      r = px & 255u; g = (px >> 8) & 255u; b = (px >> 16) & 255u; a = px >> 24;
+    } else {
+      auto value = [&](uint32_t plane) {
+        if (t.format == ii::kPlanarF32) { float f; std::memcpy(&f, raw + 4 * ((size_t)plane * n + i), 4); return f; }
+        uint16_t bits;
+        std::memcpy(&bits, raw + 2 * ((size_t)plane * n + i), 2);
+        return (float)__builtin_bit_cast(_Float16, bits);
+      };
+      r = g = b = host_import_byte(value(0)); a = 255u;
+      if (t.channels >= 3u) { g = host_import_byte(value(1)); b = host_import_byte(value(2)); }
+      if (t.channels == 4u) a = host_import_byte(value(3));
+    }
+    if (straight) { r = r * a / 255u; g = g * a / 255u; b = b * a / 255u; }
+    (*out)[i] = r | (g << 8) | (b << 16) | (a << 24);
+  }
+}
+// Pass 3 of both batches for images first .. first + m - 1, which have their entries: one copy of the tables, at most four launches, one
+// wait; then the ink blocks folded per image.  A record-only context counts the tiles and is done.
+void GlyphMaker::make_device_images(hipStream_t s, const Atlas& atlas, ImageBatch& B, int first, int m) {
+  if (!atlas.has_device()) {
+    for (int k = 0; k < m; k++) image_stats_.tiles += (int32_t)ib::table_tiles(B.tab[(size_t)(first + k)].w, B.tab[(size_t)(first + k)].h);
+    return;
+  }
+  ib::Tables T;
+  ib::tables(B.tab, first, m, atlas.n_levels(), &T);
+  int launches = 0;
+  if (T.n_tiles) {
+    FDH_HIP(hipMemcpyAsync(glyph_tab_.ptr, T.words.data(), T.words.size() * 4, hipMemcpyHostToDevice, s));
+    const ii::BatchImage* d_images = reinterpret_cast<const ii::BatchImage*>(glyph_tab_.ptr);
+    const uint32_t* d_owner = glyph_tab_.ptr + T.owner_at;
+    ii::BatchAtlas A{};
+    for (int l = 0; l < atlas.n_levels(); l++) A.level[l] = atlas.level(l);
+    A.size = atlas.size();
+    for (int f = 0; f < ib::kFormats; f++) {
+      if (!T.tile_count[f]) continue;
+      launch_image_import_batch(s, (uint32_t)f, d_images, glyph_tab_.ptr + T.tiles_at + T.tile_first[f], (int)T.tile_count[f], A, glyph_a_.ptr, ink_host_.dev, d_owner);
+      launches++;
+    }
+    if (T.n_tails) {
+      launch_image_import_tail_batch(s, d_images, glyph_tab_.ptr + T.tails_at, (int)T.n_tails, A, glyph_a_.ptr, d_owner);
+      launches++;
+    }
+    image_stats_.bytes_copied = (int64_t)(T.words.size() * 4);
+  }
+  // (an image 1 texel wide or high: its one row or column to the host, plane after plane)
+  std::vector<std::vector<uint8_t>> lines((size_t)m);
+  for (int k = 0; k < m; k++) {
+    const ii::BatchImage& t = B.tab[(size_t)(first + k)];
+    if (ib::table_tiles(t.w, t.h) || !ib::has_ink(t.w, t.h)) continue;
+    const size_t element = t.format == ii::kPlanarF16 ? 2 : 4, planes = t.format != ii::kRgba8 && t.channels > 1u ? t.channels : 1u;
+    const size_t row = (size_t)t.w * element, plane = row * t.h;
+    lines[(size_t)k].resize(planes * plane);
+    for (size_t c = 0; c < planes; c++)
+      FDH_HIP(hipMemcpy2DAsync(lines[(size_t)k].data() + c * plane, row, static_cast<const char*>(B.sources[(size_t)(first + k)]) + (int64_t)c * t.plane_bytes, (size_t)t.pitch_bytes, row, (size_t)t.h,
+                               hipMemcpyDefault, s));
+  }
+  FDH_HIP(hipStreamSynchronize(s));  // (`T` and `lines` stay alive until here)
+  FDH_HIP(hipGetLastError());
+  image_stats_.tiles = (int32_t)T.n_tiles;
+  image_stats_.launches = launches;
+  std::vector<uint32_t> texels;
+  for (int k = 0; k < m; k++) {
+    const ii::BatchImage& t = reinterpret_cast<const ii::BatchImage*>(T.words.data())[k];  // (its offsets are in the tables' copy)
+    AtlasEntry& e = *B.entries[(size_t)(first + k)];
+    int32_t got[ii::kInkWords];
+    if (t.ink) {
+      ii::fold_ink(ink_host_.ptr + (size_t)t.ink_off * ii::kInkWords, t.lw[ii::kTileLevels - 1] * t.lh[ii::kTileLevels - 1], got);
+    } else if (!lines[(size_t)k].empty()) {
+      host_import_line(t, lines[(size_t)k].data(), &texels);
+      for (int i = 0; i < ii::kInkWords; i++) got[i] = (i & 2) ? 0 : ii::kInkEmpty;
+      for (int i = 0; i < t.w * t.h; i++) {
+        const uint32_t px = texels[(size_t)i];
+        const int x = t.w == 1 ? 0 : i, y = t.w == 1 ? i : 0;
+        const int value[2] = {(int)(px >> 24), (int)std::max(px & 255u, std::max((px >> 8) & 255u, (px >> 16) & 255u))};
+        for (int kind = 0; kind < 2; kind++)
+          for (int j = 0; j < kInkLevels && value[kind] > 16 * j; j++) {
+            int32_t* box = got + 32 * kind + 4 * j;
+            box[0] = std::min(box[0], x); box[1] = std::min(box[1], y); box[2] = std::max(box[2], x + 1); box[3] = std::max(box[3], y + 1);
+          }
+      }
+    } else {
+      e.has_ink = false;
+      continue;
+    }
+    set_ink(e, got);
   }
 }
 
@@ -915,17 +1136,21 @@ static int64_t validate_batch(const Refusal& bad, const FdhGlyphOutline* glyphs,
   if (texels > ((int64_t)1 << 24)) throw bad("at most 2^24 texels in a batch");
   return texels;
 }
-// Pass 2 of a batch: every glyph through place(), in order; tab[i] takes its place.  A placement that grows the atlas has dropped every entry
-// before it: glyph i is then the first of the new atlas (*first).  *placed: the glyphs that got a place; the exception that ended the loop
-// (FDH_ERR_ATLAS_FULL, or no memory for a larger atlas) is returned: the glyphs before that one get their texels, as after single calls.
-static std::exception_ptr place_batch(hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, int (*out_rects)[4], std::vector<msdf::BatchGlyph>& tab, Stored stored, int* first, int* placed) {
+// Pass 2 of a batch of glyphs or of images: every item through place(), in order; item(i, &key, &w, &h) names it, placed_at(i, entry) takes its
+// place.  A placement that grows the atlas has dropped every entry before it: item i is then the first of the new atlas (*first).  *placed:
+// the items that got a place; the exception that ended the loop (FDH_ERR_ATLAS_FULL, or no memory for a larger atlas) is returned: the items
+// before that one get their texels, as after single calls.
+template <typename Item, typename PlacedAt>
+static std::exception_ptr place_batch(hipStream_t s, Atlas& atlas, int n, int (*out_rects)[4], Stored stored, Item item, PlacedAt placed_at, int* first, int* placed) {
   std::exception_ptr failed;
   int f = 0, p = 0;
   for (; p < n; p++) {
     const int before = atlas.size();
     try {
-      const AtlasEntry& e = atlas.place(s, glyphs[p].key, glyphs[p].width, glyphs[p].height, out_rects ? out_rects[p] : nullptr, stored);
-      tab[(size_t)p].x = e.x; tab[(size_t)p].y = e.y;
+      int64_t key;
+      int w, h;
+      item(p, &key, &w, &h);
+      placed_at(p, atlas.place(s, key, w, h, out_rects ? out_rects[p] : nullptr, stored));
     } catch (...) {
       failed = std::current_exception();
     }
@@ -985,7 +1210,9 @@ void GlyphMaker::place_and_make(hipStream_t s, Atlas& atlas, const FdhGlyphOutli
     atlas.make_room(s, reinterpret_cast<const int (*)[2]>(wh.data()), n);
   }
   int first = 0, placed = 0;
-  std::exception_ptr failed = place_batch(s, atlas, glyphs, n, out_rects, tab, thin_tiles ? Stored::chain_or_level0 : Stored::chain, &first, &placed);
+  std::exception_ptr failed = place_batch(s, atlas, n, out_rects, thin_tiles ? Stored::chain_or_level0 : Stored::chain,
+                                          [&](int i, int64_t* key, int* w, int* h) { *key = glyphs[i].key; *w = glyphs[i].width; *h = glyphs[i].height; },
+                                          [&](int i, AtlasEntry& e) { tab[(size_t)i].x = e.x; tab[(size_t)i].y = e.y; }, &first, &placed);
   stats.written = placed - first;
   stats.dropped_by_growth = first;
   // ---- pass 3: the texels of glyphs first .. placed - 1

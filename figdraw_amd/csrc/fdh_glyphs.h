@@ -6,7 +6,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "../../include_glyphs/figdraw_hip_device_image.h"  // FdhDeviceImage
+#include "../../include_glyphs/figdraw_hip_device_images.h"  // FdhImageBatchStats; and through it figdraw_hip_device_image.h (FdhDeviceImage)
 #include "../../include_glyphs/figdraw_hip_video_frame.h"   // FdhVideoFrame
 #include "../../include_video/figdraw_hip_video_alpha.h"    // FdhVideoAlphaPlanes; through it figdraw_hip_video_422.h (the 4:2:2 formats) and
                                                             // figdraw_hip_video_planar.h (FdhVideoPlanes)
@@ -44,6 +44,11 @@ class GlyphMaker final : public AtlasMover {
   // Atlas::update_image store, of a source in device memory; `device`: the context's (on a record-only context nothing is asked of it)
   void put_device_image(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhDeviceImage* img, int out_rect[4]);
   void update_device_image(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhDeviceImage* img);
+  // fdh_put_images_device and fdh_update_images_device (the specification: include_glyphs/figdraw_hip_device_images.h): n device images, validated
+  // as a whole, placed (their updates begun) in order, made in at most four launches
+  void put_device_images(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhDeviceImage* images, int n, int (*out_rects)[4]);
+  void update_device_images(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhDeviceImage* images, int n);
+  const FdhImageBatchStats& image_batch_stats() const { return image_stats_; }
   // fdh_put_video_frame and fdh_update_video_frame (the specification: include_glyphs/figdraw_hip_video_frame.h): the same of an NV12, P010 or
   // BGRA8 frame
   void put_video_frame(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoFrame* frame, int out_rect[4]);
@@ -77,6 +82,11 @@ class GlyphMaker final : public AtlasMover {
   void put_image_field(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const uint8_t* rgba, int from_x, int from_y, int channel, int pad, int range, int out_rect[4]);
   // the two device-image calls behind their validation and their placement: the launches, the wait, the entry's ink boxes
   void import_image(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const FdhDeviceImage& img, const void* data, bool wide);
+  // the two device-image batches: pass 1 of both, and pass 3 -- the tables, the launches, the wait, the ink boxes -- of entries first .. first + m - 1
+  struct ImageBatch;
+  void validate_device_images(const char* who, const Atlas& atlas, int device, const int64_t* keys, const FdhDeviceImage* images, int n, bool update, ImageBatch* B);
+  void reserve_image_batch(const ImageBatch& B);
+  void make_device_images(hipStream_t s, const Atlas& atlas, ImageBatch& B, int first, int m);
   struct VideoSource;  // a validated FdhVideoFrame as the device addresses it (fdh_glyphs.cpp)
   void import_video(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const VideoSource& src);
   struct PlanarSource;  // a validated FdhVideoPlanes as the device addresses it (fdh_glyphs.cpp)
@@ -100,6 +110,7 @@ class GlyphMaker final : public AtlasMover {
   DeviceBuf<uint32_t> glyph_tab_;  // the batches: the glyph records (msdf::BatchGlyph), the tile -> glyph words, the owner bits of the deep levels (fdh_glyph_tables.h)
   DeviceBuf<uint32_t> move_tab_;   // fdh_compact_atlas: the tables of its k_atlas_move launches (fdh_atlas_move.h)
   PinnedBuf<int32_t> ink_host_;    // the device-image and video-frame calls: the tiles' ink blocks, which the kernel stores into page-locked memory (fdh_image_import.h)
+  FdhImageBatchStats image_stats_ = {};  // of the last put_device_images or update_device_images
   FdhGlyphBatchStats batch_stats_ = {}, coverage_stats_ = {};  // of the last put_glyph_outlines, of the last put_glyph_coverage_batch (either in either segment format)
 };
 

@@ -1,6 +1,7 @@
 // fdh_image_import.h -- the parameter blocks of k_image_import and k_image_import_tail (k_image_import.hip), the kernels behind
 // fdh_put_image_device and fdh_update_image_device (the specification: include_glyphs/figdraw_hip_device_image.h).  Plain C++, no HIP and no
 // atlas: GlyphMaker fills the blocks (fdh_glyphs.cpp), tests/device_image_emu compiles them as they stand, with the kernels beside them.
+// At the end: what the batched kernels read (fdh_put_images_device, fdh_update_images_device).
 #pragma once
 #include <cstdint>
 
@@ -58,6 +59,33 @@ struct TailParams {
   int32_t sw, sh, l0, n_store;
   int32_t x, y, size;
   uint32_t* level[kLevels];
+};
+
+// ---- the batches: fdh_put_images_device and fdh_update_images_device (the specification: include_glyphs/figdraw_hip_device_images.h).
+// k_image_import_batch<format> runs over the tiles of all images of one format, k_image_import_tail_batch over the images whose chain
+// goes beyond level 5.  What Params holds per image is a record in device memory; the atlas stays a launch argument.  The host builds the
+// records, the tile words and the owner bits in fdh_image_batch.h.
+constexpr int kOwnerLevel = 4;        // msdf::kOwnerLevel (fdh_image_batch.h asserts it): from this level on two rectangles of a batch can meet
+constexpr int kBatchMaxExtent = 2048; // of an image of a batch: its level-5 image is what the tail's workgroup holds (kTailMax)
+// a tile's word: the image's index in the records | the tile's column << 16 | its row << 22 (64 tiles each way at the most)
+inline uint32_t batch_tile_word(uint32_t image, uint32_t tx, uint32_t ty) { return image | (tx << 16) | (ty << 22); }
+struct BatchImage {
+  const void* data;      // as Params::data
+  int64_t pitch_bytes, plane_bytes;
+  int32_t w, h;
+  uint32_t format, channels, flags;
+  int32_t wide;
+  int32_t x, y, n_store, ink;
+  int32_t lw[kTileLevels], lh[kTileLevels];
+  uint32_t scratch_off;  // the image's level-5 image in the batch's scratch, in texels
+  uint32_t ink_off;      // the image's first ink block in the batch's blocks, in blocks (an image with ink boxes only)
+  uint32_t owner_off;    // the image's first owner bit: per level from kOwnerLevel on lw x lh bits, rows packed; set: the texel is this image's
+  uint32_t reserved;
+};
+static_assert(sizeof(BatchImage) == 128, "the records are copied to the device as words");
+struct BatchAtlas {
+  uint32_t* level[kLevels];
+  int32_t size;
 };
 
 }  // namespace image_import

@@ -185,6 +185,14 @@ void launch_image_sdf_generate(hipStream_t s, const uint32_t* src, int sw, int s
 namespace image_import { struct Params; struct TailParams; }
 void launch_image_import(hipStream_t s, const image_import::Params& P);
 void launch_image_import_tail(hipStream_t s, const image_import::TailParams& P);
+// fdh_put_images_device and fdh_update_images_device (include_glyphs/figdraw_hip_device_images.h): the same for the tiles of all images of one
+// format of a batch -- a word per tile naming its image and its place in it, a record per image, the owner bits of the deep levels
+// (fdh_image_batch.h) --, and the tails of all images that have one
+namespace image_import { struct BatchImage; struct BatchAtlas; }
+void launch_image_import_batch(hipStream_t s, uint32_t format, const image_import::BatchImage* images, const uint32_t* tiles, int n_tiles, const image_import::BatchAtlas& A,
+                               uint32_t* scratch, int32_t* ink_blocks, const uint32_t* owner);
+void launch_image_import_tail_batch(hipStream_t s, const image_import::BatchImage* images, const uint32_t* tails, int n_tails, const image_import::BatchAtlas& A, const uint32_t* scratch,
+                                    const uint32_t* owner);
 // fdh_put_video_frame and fdh_update_video_frame (include_glyphs/figdraw_hip_video_frame.h; k_video_import.hip; the parameter block:
 // fdh_video_import.h): launch_image_import for an NV12, P010 or BGRA8 frame; launch_image_import_tail finishes its chain too
 namespace video_import { struct Params; }

@@ -5,6 +5,9 @@
 // in LDS; the tile is then minified there to 16 x 16, 8 x 8, 4 x 4, 2 x 2 and one texel with minify_by2_host's integer rule (fdh_atlas.cpp),
 // each block stored to its atlas level on the way, and the last texel goes into a compact level-5 image.  k_image_import_tail: one
 // workgroup takes that image (at most 64 x 64) through the rest of the chain in LDS.  Two launches where glyph_to_atlas issues two a level.
+// The batches (fdh_put_images_device, fdh_update_images_device; include_glyphs/figdraw_hip_device_images.h): k_image_import_batch<format> and
+// k_image_import_tail_batch run the same two bodies -- import_tile, import_tail: one statement of the conversion and of the chain -- over a
+// table of tiles and a record per image, and store into level kOwnerLevel or deeper only where the image's owner bit is set.
 #include "fdh_device.h"
 #include "fdh_image_import.h"
 
@@ -95,13 +98,25 @@ __device__ __forceinline__ void import_load_f16(const char* row, int x0, const i
 // LDS of a tile: the levels one after the other, 32 x 32, 16 x 16, .. 1 (no level is written twice)
 constexpr int kTileWords = 1024 + 256 + 64 + 16 + 4 + 1;
 
-template <uint32_t kFormat>
-__global__ __launch_bounds__(ii::kGroup) void k_image_import(const ii::Params P) {
-  __shared__ __attribute__((aligned(16))) uint32_t tile[kTileWords + 3];
-  __shared__ uint32_t lines[2 * ii::kTile];  // per row of the tile, then per column: the largest alpha | the largest colour byte << 8
+// May level l's texel (i, j) of an image of a batch be stored?  Single puts overwrite one another where two rectangles meet in a deep level;
+// one launch has no order, so the host has painted the rectangles in array order (fdh_image_batch.h) and `owner` holds, from bit `bit0` on,
+// a bit per texel of the image's levels kOwnerLevel .., rows packed: set where the texel is still this image's.  The single kernels
+// (kBatch false) own every texel.
+template <bool kBatch>
+__device__ __forceinline__ bool import_owns(const uint32_t* owner, uint32_t bit0, uint32_t bit) {
+  if (!kBatch) return true;
+  bit += bit0;
+  return (owner[bit >> 5] >> (bit & 31u)) & 1u;
+}
+
+// The body of a tile: tile (bx, by) of the image P describes, staged in `tile` (kTileWords + 3 words of LDS, 16-byte aligned) with `lines`
+// (2 * kTile words of LDS).  k_image_import calls it for its own block, k_image_import_batch<format> for the tile its table word names, with
+// the owner bits of its image: every read of P is wave-uniform in both.
+template <uint32_t kFormat, bool kBatch>
+__device__ __forceinline__ void import_tile(const ii::Params& P, const int bx, const int by, const uint32_t* owner, const uint32_t owner_bit0, uint32_t* tile, uint32_t* lines) {
   const int lane = (int)threadIdx.x;
   const int r = lane >> 3, c0 = (lane & 7) * 4;  // a wave covers eight whole rows of the tile
-  const int X0 = (int)blockIdx.x * ii::kTile + c0, Y = (int)blockIdx.y * ii::kTile + r;
+  const int X0 = bx * ii::kTile + c0, Y = by * ii::kTile + r;
   // ---- the loads.  Every address is valid -- row and columns clamped into the image -- and what lies outside is replaced behind the
   // conversion: no load waits for a branch on the texel's place, and all of a lane's loads go out before the first conversion.
   const int yc = min(Y, P.h - 1);
@@ -175,18 +190,19 @@ __global__ __launch_bounds__(ii::kGroup) void k_image_import(const ii::Params P)
   // ---- the chain in LDS.  Level l of the tile is (32 >> l)^2 texels at image texel (blockIdx * (32 >> l)); whether a texel has a full
   // 2 x 2 block under it is decided by the IMAGE's extent at level l - 1 (the host derived them), not by the tile.
   int from = 0, side = ii::kTile;
+  uint32_t level_bit = 0u;  // (a batch) the first owner bit of level l, behind the image's own first
 #pragma unroll
   for (int l = 1; l < ii::kTileLevels; l++) {
     const int to = from + side * side, half = side >> 1;
     if (lane < half * half) {
       const int i = lane & (half - 1), j = lane / half;
-      const int X = (int)blockIdx.x * half + i, Yl = (int)blockIdx.y * half + j;
+      const int X = bx * half + i, Yl = by * half + j;
       uint32_t o = 0u;
       if (X < P.lw[l] && Yl < P.lh[l]) {
         const uint32_t* s = tile + from + (2 * j) * side + 2 * i;
         o = import_minify(s[0], s[1], s[side], s[side + 1], 2 * X + 1 < P.lw[l - 1], 2 * Yl + 1 < P.lh[l - 1]);
-        if (l < P.n_store) import_store(P.level, P.size, P.x, P.y, l, X, Yl, o);
-        if (l == ii::kTileLevels - 1) P.scratch[(size_t)blockIdx.y * P.lw[l] + blockIdx.x] = o;
+        if (l < P.n_store && (l < ii::kOwnerLevel || import_owns<kBatch>(owner, owner_bit0, level_bit + (uint32_t)(Yl * P.lw[l] + X)))) import_store(P.level, P.size, P.x, P.y, l, X, Yl, o);
+        if (l == ii::kTileLevels - 1) P.scratch[(size_t)by * P.lw[l] + bx] = o;
       }
       tile[to + j * half + i] = o;
     }
@@ -199,37 +215,91 @@ __global__ __launch_bounds__(ii::kGroup) void k_image_import(const ii::Params P)
       int lo = ii::kTile, hi = 0;
       for (int i = 0; i < ii::kTile; i++)
         if ((int)((line[i] >> (8 * kind)) & 255u) > level) { lo = min(lo, i); hi = i + 1; }
-      const int origin = (int)(xy ? blockIdx.y : blockIdx.x) * ii::kTile;
+      const int origin = (xy ? by : bx) * ii::kTile;
       const int word = hi == 0 ? (far ? 0 : ii::kInkEmpty) : origin + (far ? hi : lo);
-      P.ink_block[((size_t)blockIdx.y * P.lw[ii::kTileLevels - 1] + blockIdx.x) * ii::kInkWords + lane] = word;
+      P.ink_block[((size_t)by * P.lw[ii::kTileLevels - 1] + bx) * ii::kInkWords + lane] = word;
     }
+    if (kBatch && l >= ii::kOwnerLevel) level_bit += (uint32_t)(P.lw[l] * P.lh[l]);
     from = to; side = half;
   }
+}
+
+template <uint32_t kFormat>
+__global__ __launch_bounds__(ii::kGroup) void k_image_import(const ii::Params P) {
+  __shared__ __attribute__((aligned(16))) uint32_t tile[kTileWords + 3];
+  __shared__ uint32_t lines[2 * ii::kTile];  // per row of the tile, then per column: the largest alpha | the largest colour byte << 8
+  import_tile<kFormat, false>(P, (int)blockIdx.x, (int)blockIdx.y, nullptr, 0u, tile, lines);
+}
+
+// The batch: a 1-D grid over the tiles of all images of one format (tiles: this format's words, ii::batch_tile_word).  The image's index
+// comes from the block index alone, so every read of its record is wave-uniform and the body's branches on channels, `wide` and `ink`
+// stay uniform.  The record is read whole before the first store, into the single kernel's parameter block.
+template <uint32_t kFormat>
+__global__ __launch_bounds__(ii::kGroup) void k_image_import_batch(const ii::BatchImage* __restrict__ images, const uint32_t* __restrict__ tiles, const ii::BatchAtlas A,
+                                                                   uint32_t* scratch, int32_t* ink_blocks, const uint32_t* __restrict__ owner) {
+  __shared__ __attribute__((aligned(16))) uint32_t tile[kTileWords + 3];
+  __shared__ uint32_t lines[2 * ii::kTile];
+  const uint32_t word = tiles[blockIdx.x];
+  const ii::BatchImage& I = images[word & 0xFFFFu];
+  ii::Params P;
+  P.data = I.data; P.pitch_bytes = I.pitch_bytes; P.plane_bytes = I.plane_bytes;
+  P.w = I.w; P.h = I.h; P.format = kFormat; P.channels = I.channels; P.flags = I.flags; P.wide = I.wide;
+  P.x = I.x; P.y = I.y; P.n_store = I.n_store; P.ink = I.ink;
+#pragma unroll
+  for (int l = 0; l < ii::kTileLevels; l++) { P.lw[l] = I.lw[l]; P.lh[l] = I.lh[l]; }
+#pragma unroll
+  for (int l = 0; l < ii::kLevels; l++) P.level[l] = A.level[l];
+  P.size = A.size;
+  P.scratch = scratch + I.scratch_off;
+  P.ink_block = ink_blocks + (size_t)I.ink_off * ii::kInkWords;
+  import_tile<kFormat, true>(P, (int)((word >> 16) & 63u), (int)(word >> 22), owner, I.owner_off, tile, lines);
 }
 
 // LDS of the tail: the levels one after the other from 64 x 64 down
 constexpr int kTailWords = 4096 + 1024 + 256 + 64 + 16 + 4 + 1;
 
-__global__ __launch_bounds__(ii::kGroup) void k_image_import_tail(const ii::TailParams P) {
-  __shared__ uint32_t img[kTailWords + 3];
+// The body of the tail: `src` (sw x sh texels at level l0) through levels l0 + 1 .. n_store - 1 in `img` (kTailWords + 3 words of LDS); the
+// entry at (x, y) of the atlas `level` of `size`.  kBatch: the owner bits as in import_tile; owner_bit0: the first bit of level l0 + 1.
+// (`level` stays a pointer to the launch's arguments: the loop indexes it by a level that is no constant.)
+template <bool kBatch>
+__device__ __forceinline__ void import_tail(const uint32_t* src, int sw, int sh, const int l0, const int n_store, const int x, const int y, const int size, uint32_t* const* level,
+                                            const uint32_t* owner, const uint32_t owner_bit0, uint32_t* img) {
   const int lane = (int)threadIdx.x;
-  int sw = P.sw, sh = P.sh;
-  for (int t = lane; t < sw * sh; t += ii::kGroup) img[t] = P.src[t];
+  for (int t = lane; t < sw * sh; t += ii::kGroup) img[t] = src[t];
   __syncthreads();
   int from = 0;
-  for (int l = P.l0 + 1; l < P.n_store; l++) {  // (n_store holds the chain's end: both extents of level l - 1 exceed 1)
+  uint32_t level_bit = 0u;
+  for (int l = l0 + 1; l < n_store; l++) {  // (n_store holds the chain's end: both extents of level l - 1 exceed 1)
     const int nw = (sw + 1) >> 1, nh = (sh + 1) >> 1, to = from + sw * sh;
     for (int t = lane; t < nw * nh; t += ii::kGroup) {
       const int j = t / nw, i = t - j * nw;
       const bool col_pair = 2 * i + 1 < sw, row_pair = 2 * j + 1 < sh;
       const uint32_t* s = img + from + (2 * j) * sw + 2 * i;
       const uint32_t o = import_minify(s[0], col_pair ? s[1] : 0u, row_pair ? s[sw] : 0u, col_pair && row_pair ? s[sw + 1] : 0u, col_pair, row_pair);
-      import_store(P.level, P.size, P.x, P.y, l, i, j, o);
+      if (import_owns<kBatch>(owner, owner_bit0, level_bit + (uint32_t)t)) import_store(level, size, x, y, l, i, j, o);
       img[to + t] = o;
     }
     __syncthreads();
+    if (kBatch) level_bit += (uint32_t)(nw * nh);
     from = to; sw = nw; sh = nh;
   }
+}
+
+__global__ __launch_bounds__(ii::kGroup) void k_image_import_tail(const ii::TailParams P) {
+  __shared__ uint32_t img[kTailWords + 3];
+  import_tail<false>(P.src, P.sw, P.sh, P.l0, P.n_store, P.x, P.y, P.size, P.level, nullptr, 0u, img);
+}
+
+// The batch's tail: a workgroup per image whose chain goes beyond level 5 (tails: their indices in the records), on that image's level-5
+// texels in the scratch.  (An image of a batch is at most kBatchMaxExtent each way: its level-5 image is at most kTailMax.)
+__global__ __launch_bounds__(ii::kGroup) void k_image_import_tail_batch(const ii::BatchImage* __restrict__ images, const uint32_t* __restrict__ tails, const ii::BatchAtlas A,
+                                                                        const uint32_t* scratch, const uint32_t* __restrict__ owner) {
+  __shared__ uint32_t img[kTailWords + 3];
+  const ii::BatchImage& I = images[tails[blockIdx.x]];
+  uint32_t bit0 = I.owner_off;  // level 6's first bit lies behind levels kOwnerLevel .. 5
+#pragma unroll
+  for (int l = ii::kOwnerLevel; l < ii::kTileLevels; l++) bit0 += (uint32_t)(I.lw[l] * I.lh[l]);
+  import_tail<true>(scratch + I.scratch_off, I.lw[ii::kTileLevels - 1], I.lh[ii::kTileLevels - 1], ii::kTileLevels - 1, I.n_store, I.x, I.y, A.size, A.level, owner, bit0, img);
 }
 
 void launch_image_import(hipStream_t s, const ii::Params& P) {
@@ -242,6 +312,19 @@ void launch_image_import(hipStream_t s, const ii::Params& P) {
 void launch_image_import_tail(hipStream_t s, const ii::TailParams& P) {
   if (P.sw <= 0 || P.sh <= 0 || P.sw > ii::kTailMax || P.sh > ii::kTailMax || P.l0 + 1 >= P.n_store) return;
   FDH_LAUNCH(k_image_import_tail, dim3(1), dim3(ii::kGroup), 0, s, P);
+}
+// the batch's launches: n_tiles tiles of `format` (their words at `tiles`), and n_tails images with a tail
+void launch_image_import_batch(hipStream_t s, uint32_t format, const ii::BatchImage* images, const uint32_t* tiles, int n_tiles, const ii::BatchAtlas& A, uint32_t* scratch,
+                               int32_t* ink_blocks, const uint32_t* owner) {
+  if (n_tiles <= 0) return;
+  const dim3 grid(n_tiles), block(ii::kGroup);
+  if (format == ii::kRgba8) FDH_LAUNCH(k_image_import_batch<ii::kRgba8>, grid, block, 0, s, images, tiles, A, scratch, ink_blocks, owner);
+  else if (format == ii::kPlanarF32) FDH_LAUNCH(k_image_import_batch<ii::kPlanarF32>, grid, block, 0, s, images, tiles, A, scratch, ink_blocks, owner);
+  else FDH_LAUNCH(k_image_import_batch<ii::kPlanarF16>, grid, block, 0, s, images, tiles, A, scratch, ink_blocks, owner);
+}
+void launch_image_import_tail_batch(hipStream_t s, const ii::BatchImage* images, const uint32_t* tails, int n_tails, const ii::BatchAtlas& A, const uint32_t* scratch, const uint32_t* owner) {
+  if (n_tails <= 0) return;
+  FDH_LAUNCH(k_image_import_tail_batch, dim3(n_tails), dim3(ii::kGroup), 0, s, images, tails, A, scratch, owner);
 }
 
 }  // namespace fdh
