@@ -77,6 +77,11 @@ IMAGE_RGBA8, IMAGE_PLANAR_F32, IMAGE_PLANAR_F16 = 0, 1, 2  # FdhDeviceImage.form
 IMAGE_STRAIGHT_ALPHA = 1                                   # FdhDeviceImage.flags
 
 
+class VideoBatchStats(C.Structure):  # FdhVideoBatchStats (include_glyphs/figdraw_hip_video_frames.h)
+    _fields_ = [("frames", C.c_int32), ("written", C.c_int32), ("dropped_by_growth", C.c_int32), ("tiles", C.c_int32), ("launches", C.c_int32),
+                ("reserved", C.c_int32), ("bytes_copied", C.c_int64)]
+
+
 class VideoFrame(C.Structure):  # FdhVideoFrame (include_glyphs/figdraw_hip_video_frame.h)
     _fields_ = [("planes", C.c_void_p * 2), ("pitch_bytes", C.c_int64 * 2), ("width", C.c_int32), ("height", C.c_int32),
                 ("format", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -380,6 +385,13 @@ def load():
         L.fdh_put_video_frame.argtypes = [vp, C.c_int64, C.POINTER(VideoFrame), C.c_int * 4]
         L.fdh_update_video_frame.argtypes = [vp, C.c_int64, C.POINTER(VideoFrame)]
         L.fdh_video_coefficients.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
+    if hasattr(L, "fdh_put_video_frames"):  # include_glyphs/figdraw_hip_video_frames.h
+        L.fdh_put_video_frames.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.fdh_update_video_frames.argtypes = [vp, vp, vp, C.c_int]
+        L.fdh_video_batch_stats.argtypes = [vp, C.POINTER(VideoBatchStats)]
+        L.fdh_sizeof_video_frame.argtypes = []
+        if L.fdh_sizeof_video_frame() != C.sizeof(VideoFrame):  # (the arrays of a batch are laid out here)
+            raise ImportError(f"FdhVideoFrame is {L.fdh_sizeof_video_frame()} bytes in the library and {C.sizeof(VideoFrame)} in the binding")
     if hasattr(L, "fdh_read_video_frame"):  # include_video/figdraw_hip_video_out.h
         L.fdh_read_video_frame.argtypes = [vp, C.POINTER(VideoTarget)]
         L.fdh_check_video_target.argtypes = [C.POINTER(VideoTarget), C.c_int, C.c_int]
@@ -855,6 +867,41 @@ class HipContext:
         is un-premultiplied first (fdh_read_video_alpha, include_video/figdraw_hip_video_alpha.h).  The planes are complete on return."""
         t = video_alpha_planes_target(ptrs, pitches, format, matrix, range, flags, rect)
         self._ck(self.L.fdh_read_video_alpha(self.h, C.byref(t)))
+
+    @staticmethod
+    def _video_frame_arrays(items):
+        """items: (key, VideoFrame), or (key, y_ptr, uv_ptr, width, height, pitch_y, pitch_uv[, format, matrix, range, flags]) as
+        put_video_frame takes them -> (n, the keys, the FdhVideoFrame array)"""
+        items = list(items)
+        n = len(items)
+        keys, arr = (C.c_int64 * max(n, 1))(), (VideoFrame * max(n, 1))()
+        for i, it in enumerate(items):
+            keys[i] = int(it[0])
+            f = it[1] if isinstance(it[1], VideoFrame) else video_frame(*it[1:7], *(tuple(it[7:]) + (VIDEO_NV12, VIDEO_BT709, VIDEO_LIMITED, 0)[len(it) - 7:])[:4])
+            C.memmove(C.byref(arr, i * C.sizeof(VideoFrame)), C.byref(f), C.sizeof(VideoFrame))
+        return n, keys, arr
+
+    def put_video_frames(self, items):
+        """a batch of decoded frames from device (or page-locked host) memory in one call (fdh_put_video_frames, include_glyphs/
+        figdraw_hip_video_frames.h): `items` is a sequence of (key, VideoFrame) or of (key, y_ptr, uv_ptr, width, height, pitch_y, pitch_uv[,
+        format, matrix, range, flags]).  What the same put_video_frame calls in order would leave, from at most six launches and one wait.
+        -> the rectangles, one (x, y, w, h) per item"""
+        n, keys, arr = self._video_frame_arrays(items)
+        out = ((C.c_int * 4) * max(n, 1))()
+        self._ck(self.L.fdh_put_video_frames(self.h, C.addressof(keys), C.addressof(arr), n, C.addressof(out)))
+        return [tuple(out[i]) for i in range(n)]
+
+    def update_video_frames(self, items):
+        """the next frames for a batch of entries of the same sizes (fdh_update_video_frames); `items` as in put_video_frames"""
+        n, keys, arr = self._video_frame_arrays(items)
+        self._ck(self.L.fdh_update_video_frames(self.h, C.addressof(keys), C.addressof(arr), n))
+
+    def video_batch_stats(self) -> dict:
+        """what the last put_video_frames or update_video_frames that passed validation did: frames, written, dropped_by_growth, tiles,
+        launches, bytes_copied"""
+        st = VideoBatchStats()
+        self._ck(self.L.fdh_video_batch_stats(self.h, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in VideoBatchStats._fields_ if name != "reserved"}
 
     @staticmethod
     def _device_image_arrays(items):

@@ -252,6 +252,19 @@ int fdh_put_video_frame(FdhContext* c, int64_t key, const FdhVideoFrame* frame, 
 int fdh_update_video_frame(FdhContext* c, int64_t key, const FdhVideoFrame* frame) {
   return guard([&] { C(c)->update_video_frame(key, frame); });
 }
+int fdh_put_video_frames(FdhContext* c, const int64_t* keys, const FdhVideoFrame* frames, int n, int (*out_rects)[4]) {
+  return guard([&] { C(c)->put_video_frames(keys, frames, n, out_rects); });
+}
+int fdh_update_video_frames(FdhContext* c, const int64_t* keys, const FdhVideoFrame* frames, int n) {
+  return guard([&] { C(c)->update_video_frames(keys, frames, n); });
+}
+int fdh_video_batch_stats(FdhContext* c, FdhVideoBatchStats* out) {
+  return guard([&] {
+    if (!out) throw fdh::Error(FDH_ERR_INVALID, "fdh_video_batch_stats: null pointer");
+    *out = C(c)->video_batch_stats();
+  });
+}
+int fdh_sizeof_video_frame(void) { return (int)sizeof(FdhVideoFrame); }
 int fdh_video_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[7]) {
   return guard([&] { fdh::video_coefficients(format, matrix, range, out); });
 }

@@ -76,6 +76,9 @@ class Context : public Recorder {
   const FdhImageBatchStats& image_batch_stats() const { return glyphs_.image_batch_stats(); }
   void put_video_frame(int64_t key, const FdhVideoFrame* frame, int out_rect[4]) { sync(); glyphs_.put_video_frame(stream_, atlas_, device_, key, frame, out_rect); }
   void update_video_frame(int64_t key, const FdhVideoFrame* frame) { sync(); glyphs_.update_video_frame(stream_, atlas_, device_, key, frame); }
+  void put_video_frames(const int64_t* keys, const FdhVideoFrame* frames, int n, int (*out_rects)[4]) { sync(); glyphs_.put_video_frames(stream_, atlas_, device_, keys, frames, n, out_rects); }
+  void update_video_frames(const int64_t* keys, const FdhVideoFrame* frames, int n) { sync(); glyphs_.update_video_frames(stream_, atlas_, device_, keys, frames, n); }
+  const FdhVideoBatchStats& video_batch_stats() const { return glyphs_.video_batch_stats(); }
   void put_video_planes(int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) { sync(); glyphs_.put_video_planes(stream_, atlas_, device_, key, frame, out_rect); }
   void update_video_planes(int64_t key, const FdhVideoPlanes* frame) { sync(); glyphs_.update_video_planes(stream_, atlas_, device_, key, frame); }
   void put_video_422(int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) { sync(); glyphs_.put_video_422(stream_, atlas_, device_, key, frame, out_rect); }

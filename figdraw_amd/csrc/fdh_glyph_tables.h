@@ -43,33 +43,39 @@ inline size_t batch_table_words(const std::vector<msdf::BatchGlyph>& tab, bool t
 // map of the box they span; a record gets the bits of the texels that are still its own.  `owner`: zeroed words.
 template <typename Rect>
 inline void paint_owner_bits(const Rect* r, int m, int n_levels, uint32_t* owner) {
+  // (A level's rectangles are taken into locals first and the map is walked row by row: written as loops over r[k]'s own fields, whose
+  // stores into the map may alias them, a 1920 x 1080 rectangle cost 40 us here -- more than the launch it was painted for.)
+  struct LevelRect { int k, x, y, w, h; uint32_t bit; };
+  std::vector<LevelRect> at;
   std::vector<int32_t> map;
   for (int l = msdf::kOwnerLevel; l < n_levels; l++) {
     int bx0 = INT_MAX, by0 = INT_MAX, bx1 = 0, by1 = 0;
-    auto has_level = [&](const Rect& t) { return level_size(t.w, l) > 1 && level_size(t.h, l) > 1; };
+    at.clear();
     for (int k = 0; k < m; k++) {
       const Rect& t = r[k];
-      if (!has_level(t)) continue;
+      const int w = level_size(t.w, l), h = level_size(t.h, l);
+      if (!(w > 1 && h > 1)) continue;
+      uint32_t bit = t.owner_off;
+      for (int d = msdf::kOwnerLevel; d < l; d++) bit += (uint32_t)(level_size(t.w, d) * level_size(t.h, d));
+      at.push_back(LevelRect{k, t.x >> l, t.y >> l, w, h, bit});
       bx0 = std::min(bx0, t.x >> l); by0 = std::min(by0, t.y >> l);
-      bx1 = std::max(bx1, (t.x >> l) + level_size(t.w, l)); by1 = std::max(by1, (t.y >> l) + level_size(t.h, l));
+      bx1 = std::max(bx1, (t.x >> l) + w); by1 = std::max(by1, (t.y >> l) + h);
     }
     if (bx1 <= bx0) break;  // no rectangle reaches this level, nor a deeper one
     const int bw = bx1 - bx0;
     map.assign((size_t)bw * (by1 - by0), -1);
-    for (int k = 0; k < m; k++) {
-      const Rect& t = r[k];
-      if (!has_level(t)) continue;
-      for (int j = 0; j < level_size(t.h, l); j++)
-        for (int i = 0; i < level_size(t.w, l); i++) map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] = k;
-    }
-    for (int k = 0; k < m; k++) {
-      const Rect& t = r[k];
-      if (!has_level(t)) continue;
-      uint32_t bit = t.owner_off;
-      for (int d = msdf::kOwnerLevel; d < l; d++) bit += (uint32_t)(level_size(t.w, d) * level_size(t.h, d));
-      for (int j = 0; j < level_size(t.h, l); j++)
-        for (int i = 0; i < level_size(t.w, l); i++, bit++)
-          if (map[(size_t)((t.y >> l) + j - by0) * bw + ((t.x >> l) + i - bx0)] == k) owner[bit >> 5] |= 1u << (bit & 31u);
+    for (const LevelRect& t : at)
+      for (int j = 0; j < t.h; j++) std::fill_n(map.data() + (size_t)(t.y + j - by0) * bw + (t.x - bx0), t.w, t.k);
+    for (const LevelRect& t : at) {
+      uint32_t bit = t.bit, word = 0u;  // (the bits of a word are gathered in a register: a read-modify-write of owner[] per texel waits for the last)
+      for (int j = 0; j < t.h; j++) {
+        const int32_t* row = map.data() + (size_t)(t.y + j - by0) * bw + (t.x - bx0);
+        for (int i = 0; i < t.w; i++, bit++) {
+          word |= (uint32_t)(row[i] == t.k) << (bit & 31u);
+          if ((bit & 31u) == 31u) { owner[bit >> 5] |= word; word = 0u; }
+        }
+      }
+      if (bit & 31u) owner[bit >> 5] |= word;
     }
   }
 }

@@ -14,7 +14,7 @@
 #include "fdh_kernels.h"
 #include "fdh_atlas_move.h"
 #include "fdh_image_batch.h"  // and through it fdh_image_import.h
-#include "fdh_video_import.h"
+#include "fdh_video_batch.h"  // and through it fdh_video_import.h
 #include "fdh_video_planar.h"
 #include "fdh_video_422.h"
 #include "fdh_video_alpha.h"
@@ -25,6 +25,7 @@ namespace mc = msdf::cubic;
 namespace ii = image_import;
 namespace ib = image_batch;
 namespace vi = video_import;
+namespace vb = video_batch;
 namespace vp = video_planar;
 namespace v2 = video_422;
 namespace va = video_alpha;
@@ -739,6 +740,145 @@ void video_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_
   if (range > FDH_VIDEO_FULL) throw bad("unknown range");
   if (!out) throw bad("null pointer");
   std::copy(vi::kCoefficients[format == FDH_VIDEO_P010][matrix][range], vi::kCoefficients[format == FDH_VIDEO_P010][matrix][range] + 7, out);
+}
+
+// ---- batches of decoded video frames (the specification: include_glyphs/figdraw_hip_video_frames.h).  put_device_images' three passes: every
+// frame is validated; every frame is placed (an update: begun), in order; then the frames that are still in the atlas get their texels from
+// one launch per group present (vi::batch_group) and one for the tails, over the tables of fdh_video_batch.h.
+struct GlyphMaker::VideoBatch {
+  std::vector<vi::BatchFrame> tab;   // pass 1: planes as the device addresses them, pitches, extents, format, flags, wide, the conversion; pass 2: the place
+  std::vector<AtlasEntry*> entries;  // pass 2: the entries (a placement never moves the ones behind the last growth)
+};
+// Pass 1 of both batches.  Nothing behind it refuses a frame.
+void GlyphMaker::validate_video_frames(const char* who, const Atlas& atlas, int device, const int64_t* keys, const FdhVideoFrame* frames, int n, bool update, VideoBatch* B) {
+  const Refusal bad{who};
+  if (n < 0 || (n > 0 && (!keys || !frames))) throw bad("bad frame array");
+  if (n > vb::kMaxFrames) throw bad("at most 65535 frames");
+  B->tab.assign((size_t)n, vi::BatchFrame{});
+  B->entries.assign((size_t)n, nullptr);
+  std::unordered_set<int64_t> seen;
+  int64_t tiles = 0;
+  for (int i = 0; i < n; i++) {
+    const FdhVideoFrame& f = frames[i];
+    bool wide_y, wide_c;
+    validate_video_frame(bad, &f, &wide_y, &wide_c);
+    if (f.width > ii::kBatchMaxExtent || f.height > ii::kBatchMaxExtent) throw bad("a frame of a batch is at most 2048 x 2048");
+    if (!seen.insert(keys[i]).second) throw bad("a key occurs twice");
+    if (update) {
+      const AtlasEntry* old = atlas.find(keys[i]);
+      if (!old) throw bad("unknown key");
+      if (old->w != f.width || old->h != f.height) throw bad("size mismatch");
+    }
+    tiles += (int64_t)vb::tiles_of(f.width, f.height);
+    vi::BatchFrame& t = B->tab[(size_t)i];
+    t.pitch_y = f.pitch_bytes[0]; t.pitch_c = f.pitch_bytes[1];
+    t.w = f.width; t.h = f.height; t.cw = (f.width + 1) / 2; t.ch = (f.height + 1) / 2;
+    t.format = f.format; t.flags = f.flags;
+    t.wide_y = wide_y; t.wide_c = wide_c;
+    if (f.format != FDH_VIDEO_BGRA8) {
+      const int32_t* c = vi::kCoefficients[f.format == FDH_VIDEO_P010][f.matrix][f.range];
+      t.yoff = c[0]; t.coff = c[1]; t.cy = c[2]; t.crv = c[3]; t.cgu = c[4]; t.cgv = c[5]; t.cbu = c[6];
+    }
+  }
+  if (tiles > vb::kMaxTiles) throw bad("at most 2^18 tiles in a batch");
+  if (!atlas.has_device()) return;
+  for (int i = 0; i < n; i++) {
+    const void* planes[2];
+    video_planes(bad, device, atlas, frames[i], planes);
+    B->tab[(size_t)i].luma = planes[0]; B->tab[(size_t)i].chroma = planes[1];
+  }
+}
+void GlyphMaker::put_video_frames(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhVideoFrame* frames, int n, int (*out_rects)[4]) {
+  VideoBatch B;
+  validate_video_frames("put_video_frames", atlas, device, keys, frames, n, false, &B);
+  video_stats_ = FdhVideoBatchStats{};
+  video_stats_.frames = n;
+  if (n == 0) return;
+  if (atlas.has_device()) reserve_video_batch(B);
+  // ---- pass 2: the places (keep mode: room for all frames of the batch at once, before any of them has a place)
+  if (atlas.keep()) {
+    std::vector<int> wh((size_t)n * 2);
+    for (int i = 0; i < n; i++) { wh[(size_t)i * 2] = frames[i].width; wh[(size_t)i * 2 + 1] = frames[i].height; }
+    atlas.make_room(s, reinterpret_cast<const int (*)[2]>(wh.data()), n);
+  }
+  int first = 0, placed = 0;
+  std::exception_ptr failed = place_batch(s, atlas, n, out_rects, Stored::chain,
+                                          [&](int i, int64_t* key, int* w, int* h) { *key = keys[i]; *w = frames[i].width; *h = frames[i].height; },
+                                          [&](int i, AtlasEntry& e) { B.tab[(size_t)i].x = e.x; B.tab[(size_t)i].y = e.y; B.entries[(size_t)i] = &e; }, &first, &placed);
+  video_stats_.written = placed - first;
+  video_stats_.dropped_by_growth = first;
+  // ---- pass 3: the texels of frames first .. placed - 1
+  if (placed > first) make_video_frames(s, atlas, B, first, placed - first);
+  if (failed) std::rethrow_exception(failed);
+}
+void GlyphMaker::update_video_frames(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhVideoFrame* frames, int n) {
+  VideoBatch B;
+  validate_video_frames("update_video_frames", atlas, device, keys, frames, n, true, &B);
+  video_stats_ = FdhVideoBatchStats{};
+  video_stats_.frames = n;
+  if (n == 0) return;
+  if (atlas.has_device()) reserve_video_batch(B);
+  for (int i = 0; i < n; i++) {
+    AtlasEntry& e = atlas.begin_update("update_video_frames", keys[i], frames[i].width, frames[i].height);
+    e.has_ink = false;  // (the old texels' boxes; pass 3 measures the new ones)
+    B.tab[(size_t)i].x = e.x; B.tab[(size_t)i].y = e.y;
+    B.entries[(size_t)i] = &e;
+  }
+  video_stats_.written = n;
+  make_video_frames(s, atlas, B, 0, n);
+}
+// the buffers of a whole batch, before any placement as every put reserves: the tables whatever atlas the batch ends in, a texel of
+// scratch per tile, an ink block per tile of a frame that gets ink boxes
+void GlyphMaker::reserve_video_batch(const VideoBatch& B) {
+  size_t tiles = 0, ink_tiles = 0;
+  for (const vi::BatchFrame& t : B.tab) {
+    const size_t n = vb::tiles_of(t.w, t.h);
+    tiles += n;
+    if (vb::has_ink(t.w, t.h)) ink_tiles += n;
+  }
+  glyph_tab_.reserve(vb::table_words(B.tab, kMaxMips));
+  glyph_a_.reserve(std::max<size_t>(tiles, 1));
+  ink_host_.reserve_exact(std::max<size_t>(ink_tiles, ii::kInkTiles) * ii::kInkWords);
+}
+// Pass 3 of both batches for frames first .. first + m - 1, which have their entries: one copy of the tables, at most six launches, one
+// wait; then the ink blocks folded per frame.  A record-only context counts the tiles and is done.
+void GlyphMaker::make_video_frames(hipStream_t s, const Atlas& atlas, VideoBatch& B, int first, int m) {
+  if (!atlas.has_device()) {
+    for (int k = 0; k < m; k++) video_stats_.tiles += (int32_t)vb::tiles_of(B.tab[(size_t)(first + k)].w, B.tab[(size_t)(first + k)].h);
+    return;
+  }
+  vb::Tables T;
+  vb::tables(B.tab, first, m, atlas.n_levels(), &T);
+  FDH_HIP(hipMemcpyAsync(glyph_tab_.ptr, T.words.data(), T.words.size() * 4, hipMemcpyHostToDevice, s));
+  const vi::BatchFrame* d_frames = reinterpret_cast<const vi::BatchFrame*>(glyph_tab_.ptr);
+  const uint32_t* d_owner = glyph_tab_.ptr + T.owner_at;
+  ii::BatchAtlas A{};
+  for (int l = 0; l < atlas.n_levels(); l++) A.level[l] = atlas.level(l);
+  A.size = atlas.size();
+  int launches = 0;
+  for (int g = 0; g < vb::kGroups; g++) {
+    if (!T.tile_count[g]) continue;
+    launch_video_import_batch(s, g, d_frames, glyph_tab_.ptr + T.tiles_at + T.tile_first[g], (int)T.tile_count[g], A, glyph_a_.ptr, ink_host_.dev, d_owner);
+    launches++;
+  }
+  if (T.n_tails) {
+    launch_image_import_tail_batch(s, reinterpret_cast<const ii::BatchImage*>(glyph_tab_.ptr + T.tail_records_at), glyph_tab_.ptr + T.tails_at, (int)T.n_tails, A, glyph_a_.ptr, d_owner);
+    launches++;
+  }
+  FDH_HIP(hipStreamSynchronize(s));  // (`T` stays alive until here)
+  FDH_HIP(hipGetLastError());
+  video_stats_.bytes_copied = (int64_t)(T.words.size() * 4);
+  video_stats_.tiles = (int32_t)T.n_tiles;
+  video_stats_.launches = launches;
+  for (int k = 0; k < m; k++) {
+    const vi::BatchFrame& t = B.tab[(size_t)(first + k)];  // (tables() filled in its offsets)
+    AtlasEntry& e = *B.entries[(size_t)(first + k)];
+    e.has_ink = t.ink != 0;
+    if (!t.ink) continue;
+    int32_t got[ii::kInkWords];
+    ii::fold_ink(ink_host_.ptr + (size_t)t.ink_off * ii::kInkWords, t.lw[ii::kTileLevels - 1] * t.lh[ii::kTileLevels - 1], got);
+    set_ink(e, got);
+  }
 }
 
 // ---- three-plane video frames (the specification: include_video/figdraw_hip_video_planar.h).  put_video_frame's steps; the struct, its

@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "../../include_glyphs/figdraw_hip_device_images.h"  // FdhImageBatchStats; and through it figdraw_hip_device_image.h (FdhDeviceImage)
-#include "../../include_glyphs/figdraw_hip_video_frame.h"   // FdhVideoFrame
+#include "../../include_glyphs/figdraw_hip_video_frames.h"  // FdhVideoBatchStats; and through it figdraw_hip_video_frame.h (FdhVideoFrame)
 #include "../../include_video/figdraw_hip_video_alpha.h"    // FdhVideoAlphaPlanes; through it figdraw_hip_video_422.h (the 4:2:2 formats) and
                                                             // figdraw_hip_video_planar.h (FdhVideoPlanes)
 #include "../../include_glyphs/figdraw_hip_cubic_batch.h"  // the two cubic batches; and through it figdraw_hip_cubic.h (fdh_put_glyph_outline_cubic),
@@ -53,6 +53,11 @@ class GlyphMaker final : public AtlasMover {
   // BGRA8 frame
   void put_video_frame(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoFrame* frame, int out_rect[4]);
   void update_video_frame(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoFrame* frame);
+  // fdh_put_video_frames and fdh_update_video_frames (the specification: include_glyphs/figdraw_hip_video_frames.h): n such frames, validated as a
+  // whole, placed (their updates begun) in order, made in at most six launches
+  void put_video_frames(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhVideoFrame* frames, int n, int (*out_rects)[4]);
+  void update_video_frames(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhVideoFrame* frames, int n);
+  const FdhVideoBatchStats& video_batch_stats() const { return video_stats_; }
   // fdh_put_video_planes and fdh_update_video_planes (the specification: include_video/figdraw_hip_video_planar.h): the same of a three-plane
   // I420, I010, I444 or I410 frame
   void put_video_planes(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame, int out_rect[4]);
@@ -89,6 +94,11 @@ class GlyphMaker final : public AtlasMover {
   void make_device_images(hipStream_t s, const Atlas& atlas, ImageBatch& B, int first, int m);
   struct VideoSource;  // a validated FdhVideoFrame as the device addresses it (fdh_glyphs.cpp)
   void import_video(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const VideoSource& src);
+  // the two video-frame batches: pass 1 of both, and pass 3 -- the tables, the launches, the wait, the ink boxes -- of entries first .. first + m - 1
+  struct VideoBatch;
+  void validate_video_frames(const char* who, const Atlas& atlas, int device, const int64_t* keys, const FdhVideoFrame* frames, int n, bool update, VideoBatch* B);
+  void reserve_video_batch(const VideoBatch& B);
+  void make_video_frames(hipStream_t s, const Atlas& atlas, VideoBatch& B, int first, int m);
   struct PlanarSource;  // a validated FdhVideoPlanes as the device addresses it (fdh_glyphs.cpp)
   void import_video_planes(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const PlanarSource& src);
   void import_video_422(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const PlanarSource& src);  // (the same struct, the 4:2:2 formats)
@@ -111,6 +121,7 @@ class GlyphMaker final : public AtlasMover {
   DeviceBuf<uint32_t> move_tab_;   // fdh_compact_atlas: the tables of its k_atlas_move launches (fdh_atlas_move.h)
   PinnedBuf<int32_t> ink_host_;    // the device-image and video-frame calls: the tiles' ink blocks, which the kernel stores into page-locked memory (fdh_image_import.h)
   FdhImageBatchStats image_stats_ = {};  // of the last put_device_images or update_device_images
+  FdhVideoBatchStats video_stats_ = {};  // of the last put_video_frames or update_video_frames
   FdhGlyphBatchStats batch_stats_ = {}, coverage_stats_ = {};  // of the last put_glyph_outlines, of the last put_glyph_coverage_batch (either in either segment format)
 };
 

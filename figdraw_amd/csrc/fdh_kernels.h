@@ -197,6 +197,12 @@ void launch_image_import_tail_batch(hipStream_t s, const image_import::BatchImag
 // fdh_video_import.h): launch_image_import for an NV12, P010 or BGRA8 frame; launch_image_import_tail finishes its chain too
 namespace video_import { struct Params; }
 void launch_video_import(hipStream_t s, const video_import::Params& P);
+// fdh_put_video_frames and fdh_update_video_frames (include_glyphs/figdraw_hip_video_frames.h): the same for the tiles of all frames of one
+// group of a batch (video_import::batch_group) -- a word per tile naming its frame and its place in it, a record per frame, the owner bits
+// of the deep levels (fdh_video_batch.h); launch_image_import_tail_batch finishes the chains
+namespace video_import { struct BatchFrame; }
+void launch_video_import_batch(hipStream_t s, int group, const video_import::BatchFrame* frames, const uint32_t* tiles, int n_tiles, const image_import::BatchAtlas& A, uint32_t* scratch,
+                               int32_t* ink_blocks, const uint32_t* owner);
 // fdh_read_video_frame (include_video/figdraw_hip_video_out.h; k_video_export.hip; the parameter block: fdh_video_export.h): the P.w x P.h
 // texels at P.src out as NV12, P010 or BGRA8 planes, a workgroup per 128 x 16 tile of them
 namespace video_export { struct Params; }

@@ -2,6 +2,7 @@
 // fdh_update_video_frame (the specification: include_glyphs/figdraw_hip_video_frame.h), and the table of the conversion's coefficients.
 // Plain C++, no HIP and no atlas: GlyphMaker fills the block (fdh_glyphs.cpp), tests/video_frame_emu compiles it as it stands, with the
 // kernel beside it.  The tile, the ink blocks and the tail are k_image_import's (fdh_image_import.h).
+// At the end: what the batched kernel reads (fdh_put_video_frames, fdh_update_video_frames).
 #pragma once
 #include <cstdint>
 
@@ -43,6 +44,28 @@ struct Params {
   uint32_t* scratch;     // takes the level-5 image, lw[5] x lh[5] texels, rows packed: a texel per tile (image_import::TailParams::src)
   int32_t* ink_block;    // image_import::kInkWords words per tile, as the device addresses them
 };
+
+// ---- the batches: fdh_put_video_frames and fdh_update_video_frames (the specification: include_glyphs/figdraw_hip_video_frames.h).
+// k_video_import_batch<format, linear> runs over the tiles of all frames of one group of a batch; what Params holds per frame is a record
+// in device memory, the atlas stays a launch argument (image_import::BatchAtlas), a tile's word is image_import::batch_tile_word.  The host
+// builds the records, the tile words, the tails' records and the owner bits in fdh_video_batch.h.
+constexpr int kBatchGroups = 5;  // the builds of k_video_import: BGRA8, then NV12, NV12 linear, P010, P010 linear
+inline int batch_group(uint32_t format, uint32_t flags) { return format == kBgra8 ? 0 : 1 + 2 * (format == kP010) + (int)(flags & kChromaLinear); }
+struct BatchFrame {
+  const void* luma;      // as Params's, field for field
+  const void* chroma;
+  int64_t pitch_y, pitch_c;
+  int32_t w, h, cw, ch;
+  uint32_t format, flags;
+  int32_t wide_y, wide_c;
+  int32_t yoff, coff, cy, crv, cgu, cgv, cbu;
+  int32_t x, y, n_store, ink;
+  int32_t lw[image_import::kTileLevels], lh[image_import::kTileLevels];
+  uint32_t scratch_off;  // the frame's level-5 image in the batch's scratch, in texels
+  uint32_t ink_off;      // the frame's first ink block in the batch's blocks, in blocks (a frame with ink boxes only)
+  uint32_t owner_off;    // the frame's first owner bit, as image_import::BatchImage's
+};
+static_assert(sizeof(BatchFrame) == 168, "the records are copied to the device as words");
 
 }  // namespace video_import
 }  // namespace fdh

@@ -6,6 +6,9 @@
 // tile goes the way k_image_import's goes: level 0 into the atlas, levels 1 .. 5 through LDS, the last texel into the compact level-5
 // image, the ink block.  k_image_import_tail finishes the chain.  The tile body is restated here, not shared: k_image_import.hip and its
 // code objects stay as they are.  No float arithmetic anywhere in this unit.
+// The batches (fdh_put_video_frames, fdh_update_video_frames; include_glyphs/figdraw_hip_video_frames.h): k_video_import_batch<format, linear>
+// runs video_batch_tile over a table of tiles and a record per frame (vi::BatchFrame), and stores into level ii::kOwnerLevel or deeper only
+// where the frame's owner bit is set; k_image_import_tail_batch finishes the chains.
 #include "fdh_device.h"
 #include "fdh_video_import.h"
 
@@ -246,6 +249,159 @@ __global__ __launch_bounds__(ii::kGroup) void k_video_import(const vi::Params P)
   }
 }
 
+// ---- the batches (fdh_put_video_frames, fdh_update_video_frames; include_glyphs/figdraw_hip_video_frames.h).
+// May level l's texel of a frame of a batch be stored?  k_image_import.hip's import_owns: `owner` holds, from bit `bit0` on, a bit per
+// texel of the frame's levels ii::kOwnerLevel .., rows packed, set where the texel is still this frame's after the host painted the
+// batch's rectangles in array order (fdh_video_batch.h).
+__device__ __forceinline__ bool video_owns(const uint32_t* owner, uint32_t bit0, uint32_t bit) {
+  bit += bit0;
+  return (owner[bit >> 5] >> (bit & 31u)) & 1u;
+}
+
+// The body of a tile of a batch: tile (bx, by) of the frame P describes, staged in `tile` (vi::kTileWords + 3 words of LDS, 16-byte
+// aligned) with `lines` (2 * ii::kTile words of LDS), with the owner bits of its frame.  It is k_video_import's body statement for
+// statement -- the loads, the conversion, the chain and the ink block come from the functions above, which both call -- but for the tile's
+// place, which is an argument here, and the owner bits in front of a store into level ii::kOwnerLevel or deeper.  It is a second statement
+// and not a shared one because k_video_import, handed its own body as a function of its parameter block, is compiled to other code (20
+// more SGPRs in all five builds; profiles/video_frame_batch.txt), and the single calls keep the code they were measured with.
+template <uint32_t kFormat, bool kLinear>
+__device__ __forceinline__ void video_batch_tile(const vi::Params& P, const int bx, const int by, const uint32_t* owner, const uint32_t owner_bit0, uint32_t* tile, uint32_t* lines) {
+  const int lane = (int)threadIdx.x;
+  const int r = lane >> 3, c0 = (lane & 7) * 4;  // a wave covers eight whole rows of the tile
+  const int X0 = bx * ii::kTile + c0, Y = by * ii::kTile + r;
+  // ---- the loads.  Every address is valid -- rows, columns and pairs clamped into their plane -- and what lies outside the image is
+  // replaced behind the conversion: no load waits for a branch on the texel's place, and all of a lane's loads go out before the first
+  // conversion.
+  const int yc = min(Y, P.h - 1);
+  int xc[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) xc[i] = min(X0 + i, P.w - 1);
+  const bool wide = P.wide_y != 0, whole = wide && X0 + 4 <= P.w;
+  const char* row = static_cast<const char*>(P.luma) + (int64_t)yc * P.pitch_y;
+  uint32_t px[4];
+  if (kFormat == vi::kBgra8) {
+    uint32_t t[4];
+    vi::load_bgra(row, X0, xc, wide, whole, t);
+#pragma unroll
+    for (int i = 0; i < 4; i++) px[i] = vi::bgra_texel(t[i], P.flags);
+  } else {
+    // the run's luma columns X0 .. X0 + 3 lie over the pairs i0 and i0 + 1; kLinear also reads min(i0 + 2, cw - 1), and a second row
+    const int i0 = X0 >> 1, j = yc >> 1;
+    int pc[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) pc[k] = min(i0 + k, P.cw - 1);
+    const bool wide_c = P.wide_c != 0, whole_c = wide_c && i0 + 2 <= P.cw;
+    const char* crow = static_cast<const char*>(P.chroma) + (int64_t)j * P.pitch_c;
+    int Ys[4], cb[3], cr[3];
+    vi::load_luma<kFormat>(row, X0, xc, wide, whole, Ys);
+    if (!kLinear) {
+      vi::load_chroma<kFormat, 2>(crow, i0, pc, wide_c, whole_c, cb, cr);
+#pragma unroll
+      for (int i = 0; i < 4; i++) px[i] = vi::yuv_texel(P, Ys[i], cb[i >> 1], cr[i >> 1]);
+    } else {
+      const int jn = (yc & 1) ? min(j + 1, P.ch - 1) : max(j - 1, 0);
+      const char* nrow = static_cast<const char*>(P.chroma) + (int64_t)jn * P.pitch_c;
+      int fb[3], fr[3];
+      vi::load_chroma<kFormat, 3>(crow, i0, pc, wide_c, whole_c, cb, cr);
+      vi::load_chroma<kFormat, 3>(nrow, i0, pc, wide_c, whole_c, fb, fr);
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int k = i >> 1;
+        const int u = (i & 1) ? vi::chroma_odd(cb[k], fb[k], cb[k + 1], fb[k + 1]) : vi::chroma_even(cb[k], fb[k]);
+        const int v = (i & 1) ? vi::chroma_odd(cr[k], fr[k], cr[k + 1], fr[k + 1]) : vi::chroma_even(cr[k], fr[k]);
+        px[i] = vi::yuv_texel(P, Ys[i], u, v);
+      }
+    }
+  }
+  // ---- from here on the tile goes k_image_import's way.  Level 0 into the atlas (dword stores: the entry's x need not be a multiple of
+  // four) and, as packed words, into LDS
+  const bool row_in = Y < P.h;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const bool in = row_in && X0 + i < P.w;
+    if (in && P.n_store > 0) vi::store(P.level, P.size, P.x, P.y, 0, X0 + i, Y, px[i]);
+    if (!in) px[i] = 0u;
+  }
+  uint4 run;
+  run.x = px[0]; run.y = px[1]; run.z = px[2]; run.w = px[3];
+  *reinterpret_cast<uint4*>(tile + r * ii::kTile + c0) = run;
+  __syncthreads();
+  // ---- the ink boxes, first half: 32 lanes take a row of the staged tile each (its words rotated by the row, so that the lanes read 32
+  // banks), 32 a column: the largest alpha and the largest colour byte in it
+  if (P.ink && lane < 2 * ii::kTile) {
+    const int n = lane & (ii::kTile - 1);
+    uint32_t a = 0u, c = 0u;
+    for (int i = 0; i < ii::kTile; i++) {
+      const uint32_t t = lane < ii::kTile ? tile[n * ii::kTile + ((i + n) & (ii::kTile - 1))] : tile[i * ii::kTile + n];
+      a = max(a, t >> 24);
+      c = max(c, max(t & 255u, max((t >> 8) & 255u, (t >> 16) & 255u)));
+    }
+    lines[lane] = a | (c << 8);
+  }
+  // ---- the chain in LDS.  Level l of the tile is (32 >> l)^2 texels at image texel (blockIdx * (32 >> l)); whether a texel has a full
+  // 2 x 2 block under it is decided by the IMAGE's extent at level l - 1 (the host derived them), not by the tile.
+  int from = 0, side = ii::kTile;
+  uint32_t level_bit = 0u;  // the first owner bit of level l, behind the frame's own first
+#pragma unroll
+  for (int l = 1; l < ii::kTileLevels; l++) {
+    const int to = from + side * side, half = side >> 1;
+    if (lane < half * half) {
+      const int i = lane & (half - 1), jj = lane / half;
+      const int X = bx * half + i, Yl = by * half + jj;
+      uint32_t o = 0u;
+      if (X < P.lw[l] && Yl < P.lh[l]) {
+        const uint32_t* s = tile + from + (2 * jj) * side + 2 * i;
+        o = vi::minify(s[0], s[1], s[side], s[side + 1], 2 * X + 1 < P.lw[l - 1], 2 * Yl + 1 < P.lh[l - 1]);
+        if (l < P.n_store && (l < ii::kOwnerLevel || video_owns(owner, owner_bit0, level_bit + (uint32_t)(Yl * P.lw[l] + X)))) vi::store(P.level, P.size, P.x, P.y, l, X, Yl, o);
+        if (l == ii::kTileLevels - 1) P.scratch[(size_t)by * P.lw[l] + bx] = o;
+      }
+      tile[to + jj * half + i] = o;
+    }
+    __syncthreads();
+    // The ink boxes, second half (behind the barrier: `lines` is whole): lane = kind * 32 + k * 4 + {x0, y0, x1, y1} spans the columns or
+    // the rows above level 16 k and stores its word of the tile's block -- plain stores into page-locked memory, the block whole.
+    if (l == 1 && P.ink && lane < ii::kInkWords) {
+      const int kind = lane >> 5, level = 16 * ((lane >> 2) & 7), xy = lane & 1, far = lane & 2;
+      const uint32_t* line = lines + (xy ? 0 : ii::kTile);
+      int lo = ii::kTile, hi = 0;
+      for (int i = 0; i < ii::kTile; i++)
+        if ((int)((line[i] >> (8 * kind)) & 255u) > level) { lo = min(lo, i); hi = i + 1; }
+      const int origin = (xy ? by : bx) * ii::kTile;
+      const int word = hi == 0 ? (far ? 0 : ii::kInkEmpty) : origin + (far ? hi : lo);
+      P.ink_block[((size_t)by * P.lw[ii::kTileLevels - 1] + bx) * ii::kInkWords + lane] = word;
+    }
+    if (l >= ii::kOwnerLevel) level_bit += (uint32_t)(P.lw[l] * P.lh[l]);
+    from = to; side = half;
+  }
+}
+
+// The batch: a 1-D grid over the tile words of one group of a batch (vi::batch_group: BGRA8, or NV12 / P010 without or with
+// FDH_VIDEO_CHROMA_LINEAR).  The frame's index comes from the block index alone, so every read of its record is wave-uniform and the body's
+// branches on `wide_y`, `wide_c`, the flags and `ink` stay uniform.  The record is read whole before the first store, into the single
+// kernel's parameter block.  A frame 1 texel wide or high has its tiles here (n_store == 0: nothing of it is stored, its ink blocks are).
+template <uint32_t kFormat, bool kLinear>
+__global__ __launch_bounds__(ii::kGroup) void k_video_import_batch(const vi::BatchFrame* __restrict__ frames, const uint32_t* __restrict__ tiles, const ii::BatchAtlas A,
+                                                                   uint32_t* scratch, int32_t* ink_blocks, const uint32_t* __restrict__ owner) {
+  __shared__ __attribute__((aligned(16))) uint32_t tile[vi::kTileWords + 3];
+  __shared__ uint32_t lines[2 * ii::kTile];
+  const uint32_t word = tiles[blockIdx.x];
+  const vi::BatchFrame& F = frames[word & 0xFFFFu];
+  vi::Params P;
+  P.luma = F.luma; P.chroma = F.chroma; P.pitch_y = F.pitch_y; P.pitch_c = F.pitch_c;
+  P.w = F.w; P.h = F.h; P.cw = F.cw; P.ch = F.ch;
+  P.format = kFormat; P.flags = F.flags; P.wide_y = F.wide_y; P.wide_c = F.wide_c;
+  P.yoff = F.yoff; P.coff = F.coff; P.cy = F.cy; P.crv = F.crv; P.cgu = F.cgu; P.cgv = F.cgv; P.cbu = F.cbu;
+  P.x = F.x; P.y = F.y; P.n_store = F.n_store; P.ink = F.ink;
+#pragma unroll
+  for (int l = 0; l < ii::kTileLevels; l++) { P.lw[l] = F.lw[l]; P.lh[l] = F.lh[l]; }
+#pragma unroll
+  for (int l = 0; l < ii::kLevels; l++) P.level[l] = A.level[l];
+  P.size = A.size;
+  P.scratch = scratch + F.scratch_off;
+  P.ink_block = ink_blocks + (size_t)F.ink_off * ii::kInkWords;
+  video_batch_tile<kFormat, kLinear>(P, (int)((word >> 16) & 63u), (int)(word >> 22), owner, F.owner_off, tile, lines);
+}
+
 void launch_video_import(hipStream_t s, const vi::Params& P) {
   if (P.w <= 0 || P.h <= 0) return;
   const dim3 grid((P.w + ii::kTile - 1) / ii::kTile, (P.h + ii::kTile - 1) / ii::kTile), block(ii::kGroup);
@@ -255,6 +411,18 @@ void launch_video_import(hipStream_t s, const vi::Params& P) {
   else if (P.format == vi::kNv12) FDH_LAUNCH((k_video_import<vi::kNv12, true>), grid, block, 0, s, P);
   else if (!linear) FDH_LAUNCH((k_video_import<vi::kP010, false>), grid, block, 0, s, P);
   else FDH_LAUNCH((k_video_import<vi::kP010, true>), grid, block, 0, s, P);
+}
+
+// the batch's launch of one group (vi::batch_group): n_tiles tiles, their words at `tiles`
+void launch_video_import_batch(hipStream_t s, int group, const vi::BatchFrame* frames, const uint32_t* tiles, int n_tiles, const ii::BatchAtlas& A, uint32_t* scratch, int32_t* ink_blocks,
+                               const uint32_t* owner) {
+  if (n_tiles <= 0) return;
+  const dim3 grid(n_tiles), block(ii::kGroup);
+  if (group == 0) FDH_LAUNCH((k_video_import_batch<vi::kBgra8, false>), grid, block, 0, s, frames, tiles, A, scratch, ink_blocks, owner);
+  else if (group == 1) FDH_LAUNCH((k_video_import_batch<vi::kNv12, false>), grid, block, 0, s, frames, tiles, A, scratch, ink_blocks, owner);
+  else if (group == 2) FDH_LAUNCH((k_video_import_batch<vi::kNv12, true>), grid, block, 0, s, frames, tiles, A, scratch, ink_blocks, owner);
+  else if (group == 3) FDH_LAUNCH((k_video_import_batch<vi::kP010, false>), grid, block, 0, s, frames, tiles, A, scratch, ink_blocks, owner);
+  else FDH_LAUNCH((k_video_import_batch<vi::kP010, true>), grid, block, 0, s, frames, tiles, A, scratch, ink_blocks, owner);
 }
 
 }  // namespace fdh
