@@ -93,7 +93,7 @@ class Atlas {
   // ---- what the kernels sample, and level 0 for fdh_debug_read_surface
   AtlasView view() const;
   const uint32_t* level0() const { return levels_[0]; }
-  // ---- what a put from outside (GlyphMaker) needs: THE placement -- rect (growing as needed, which drops every entry), entry, epoch,
+  // ---- what a put from outside (GlyphMaker, Importer) needs: THE placement -- rect (growing as needed, which drops every entry), entry, epoch,
   // out_rect; whether the levels exist; a level's texels (valid until the next placement); and updateSubImage's level chain
   // (textures.nim:106-119): step(level, x, y, w, h) for the image minified `level` times, while width > 1 and height > 1
   // `stored`: what the put will store of the image (AtlasEntry::stored); put_mips sets its own
@@ -109,7 +109,7 @@ class Atlas {
   void put_mips(hipStream_t s, int64_t key, int n, const int* ws, const int* hs, const uint8_t* const* premul_rgba, int out_rect[4]);
   void put_flippy(hipStream_t s, int64_t key, const uint8_t* data, size_t n, int out_rect[4]);
   void update_image(int64_t key, int w, int h, const uint8_t* rgba);
-  // the first half of every update, the host's and GlyphMaker's from device memory: the key is looked up, the size checked, the epoch
+  // the first half of every update, the host's and the Importer's from device memory: the key is looked up, the size checked, the epoch
   // bumped, an entry with levels of its own turned into a chain entry; the caller stores the new chain and the ink boxes
   AtlasEntry& begin_update(const char* who, int64_t key, int w, int h, const char* also_refused = nullptr);
   void release() { release_levels(); }  // (the stream is idle)

@@ -86,6 +86,7 @@ void Context::release_device_state() {
   for (auto& e : ev_pool_) (void)hipEventDestroy(e);
   atlas_.release();
   glyphs_.release();
+  importer_.release();
   if (fb_) (void)hipFree(fb_);
   if (backdrop_) (void)hipFree(backdrop_);
   if (blur_tmp_) (void)hipFree(blur_tmp_);

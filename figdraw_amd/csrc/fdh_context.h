@@ -30,6 +30,7 @@
 #include "fdh_atlas.h"        // AtlasEntry, Atlas: one member of Context
 #include "fdh_recorder.h"     // Recorder (Context is lane 0's), FrameEnv, CallLog
 #include "fdh_glyphs.h"       // GlyphMaker, beside it: glyphs made on the device
+#include "fdh_import.h"       // Importer, beside both: images and video frames from device memory
 #include "fdh_damage_host.h"  // DamageTracker, DamageReadback: two members of Context
 #include "fdh_retained.h"     // RetainedScene: one member of Context
 #include "fdh_video_out.h"    // video_out::read, beside it: the frame out as NV12, P010, BGRA8
@@ -52,7 +53,8 @@ class Context : public Recorder {
   void comm_info(int* rank, int* world) const { *rank = comm_ ? comm_rank_ : 0; *world = comm_ ? comm_world_ : 1; }
 
   // atlas (fdh_atlas.h): the context's part of a call that changes texels is sync() -- a frame in flight may still sample the atlas -- and
-  // what FDH_GLYPH_LCD_CONTEXT means here; the rest is atlas_'s, and for glyphs made on the device glyphs_' (fdh_glyphs.h), which places them in atlas_
+  // what FDH_GLYPH_LCD_CONTEXT means here; the rest is atlas_'s, for glyphs made on the device glyphs_' (fdh_glyphs.h) and for images and video
+  // frames from device memory importer_'s (fdh_import.h), which place them in atlas_
   void put_image(int64_t key, int w, int h, const uint8_t* rgba, int out_rect[4]) { sync(); atlas_.put_image(stream_, key, w, h, rgba, out_rect); }
   void put_glyph_image(int64_t key, int w, int h, const uint8_t* rgba, uint32_t flags, int out_rect[4]) { sync(); glyphs_.put_glyph_image(stream_, atlas_, key, w, h, rgba, resolve_lcd(flags), out_rect); }
   void put_glyph_outline(int64_t key, int w, int h, const float* segs, int n, uint32_t flags, int out_rect[4]) { sync(); glyphs_.put_glyph_outline(stream_, atlas_, key, w, h, segs, n, resolve_lcd(flags), out_rect); }
@@ -69,22 +71,22 @@ class Context : public Recorder {
   const FdhGlyphBatchStats& glyph_coverage_batch_stats() const { return glyphs_.glyph_coverage_batch_stats(); }
   void put_image_sdf(int64_t key, int w, int h, const uint8_t* rgba, int channel, int pad, uint32_t flags, int out_rect[4]) { sync(); glyphs_.put_image_sdf(stream_, atlas_, key, w, h, rgba, channel, pad, flags, out_rect); }
   void put_image_sdf_of(int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]) { sync(); glyphs_.put_image_sdf_of(stream_, atlas_, src_key, key, channel, pad, flags, out_rect); }
-  void put_image_device(int64_t key, const FdhDeviceImage* img, int out_rect[4]) { sync(); glyphs_.put_device_image(stream_, atlas_, device_, key, img, out_rect); }
-  void update_image_device(int64_t key, const FdhDeviceImage* img) { sync(); glyphs_.update_device_image(stream_, atlas_, device_, key, img); }
-  void put_images_device(const int64_t* keys, const FdhDeviceImage* images, int n, int (*out_rects)[4]) { sync(); glyphs_.put_device_images(stream_, atlas_, device_, keys, images, n, out_rects); }
-  void update_images_device(const int64_t* keys, const FdhDeviceImage* images, int n) { sync(); glyphs_.update_device_images(stream_, atlas_, device_, keys, images, n); }
-  const FdhImageBatchStats& image_batch_stats() const { return glyphs_.image_batch_stats(); }
-  void put_video_frame(int64_t key, const FdhVideoFrame* frame, int out_rect[4]) { sync(); glyphs_.put_video_frame(stream_, atlas_, device_, key, frame, out_rect); }
-  void update_video_frame(int64_t key, const FdhVideoFrame* frame) { sync(); glyphs_.update_video_frame(stream_, atlas_, device_, key, frame); }
-  void put_video_frames(const int64_t* keys, const FdhVideoFrame* frames, int n, int (*out_rects)[4]) { sync(); glyphs_.put_video_frames(stream_, atlas_, device_, keys, frames, n, out_rects); }
-  void update_video_frames(const int64_t* keys, const FdhVideoFrame* frames, int n) { sync(); glyphs_.update_video_frames(stream_, atlas_, device_, keys, frames, n); }
-  const FdhVideoBatchStats& video_batch_stats() const { return glyphs_.video_batch_stats(); }
-  void put_video_planes(int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) { sync(); glyphs_.put_video_planes(stream_, atlas_, device_, key, frame, out_rect); }
-  void update_video_planes(int64_t key, const FdhVideoPlanes* frame) { sync(); glyphs_.update_video_planes(stream_, atlas_, device_, key, frame); }
-  void put_video_422(int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) { sync(); glyphs_.put_video_422(stream_, atlas_, device_, key, frame, out_rect); }
-  void update_video_422(int64_t key, const FdhVideoPlanes* frame) { sync(); glyphs_.update_video_422(stream_, atlas_, device_, key, frame); }
-  void put_video_alpha(int64_t key, const FdhVideoAlphaPlanes* frame, int out_rect[4]) { sync(); glyphs_.put_video_alpha(stream_, atlas_, device_, key, frame, out_rect); }
-  void update_video_alpha(int64_t key, const FdhVideoAlphaPlanes* frame) { sync(); glyphs_.update_video_alpha(stream_, atlas_, device_, key, frame); }
+  void put_image_device(int64_t key, const FdhDeviceImage* img, int out_rect[4]) { sync(); importer_.put_device_image(stream_, atlas_, device_, key, img, out_rect); }
+  void update_image_device(int64_t key, const FdhDeviceImage* img) { sync(); importer_.update_device_image(stream_, atlas_, device_, key, img); }
+  void put_images_device(const int64_t* keys, const FdhDeviceImage* images, int n, int (*out_rects)[4]) { sync(); importer_.put_device_images(stream_, atlas_, device_, keys, images, n, out_rects); }
+  void update_images_device(const int64_t* keys, const FdhDeviceImage* images, int n) { sync(); importer_.update_device_images(stream_, atlas_, device_, keys, images, n); }
+  const FdhImageBatchStats& image_batch_stats() const { return importer_.image_batch_stats(); }
+  void put_video_frame(int64_t key, const FdhVideoFrame* frame, int out_rect[4]) { sync(); importer_.put_video_frame(stream_, atlas_, device_, key, frame, out_rect); }
+  void update_video_frame(int64_t key, const FdhVideoFrame* frame) { sync(); importer_.update_video_frame(stream_, atlas_, device_, key, frame); }
+  void put_video_frames(const int64_t* keys, const FdhVideoFrame* frames, int n, int (*out_rects)[4]) { sync(); importer_.put_video_frames(stream_, atlas_, device_, keys, frames, n, out_rects); }
+  void update_video_frames(const int64_t* keys, const FdhVideoFrame* frames, int n) { sync(); importer_.update_video_frames(stream_, atlas_, device_, keys, frames, n); }
+  const FdhVideoBatchStats& video_batch_stats() const { return importer_.video_batch_stats(); }
+  void put_video_planes(int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) { sync(); importer_.put_video_planes(stream_, atlas_, device_, key, frame, out_rect); }
+  void update_video_planes(int64_t key, const FdhVideoPlanes* frame) { sync(); importer_.update_video_planes(stream_, atlas_, device_, key, frame); }
+  void put_video_422(int64_t key, const FdhVideoPlanes* frame, int out_rect[4]) { sync(); importer_.put_video_422(stream_, atlas_, device_, key, frame, out_rect); }
+  void update_video_422(int64_t key, const FdhVideoPlanes* frame) { sync(); importer_.update_video_422(stream_, atlas_, device_, key, frame); }
+  void put_video_alpha(int64_t key, const FdhVideoAlphaPlanes* frame, int out_rect[4]) { sync(); importer_.put_video_alpha(stream_, atlas_, device_, key, frame, out_rect); }
+  void update_video_alpha(int64_t key, const FdhVideoAlphaPlanes* frame) { sync(); importer_.update_video_alpha(stream_, atlas_, device_, key, frame); }
   bool has_image(int64_t key) const { return atlas_.has(key); }
   void reset_atlas(int minimum_size) { sync(); atlas_.reset(minimum_size, stream_); }
   int atlas_size() const { return atlas_.size(); }
@@ -367,6 +369,7 @@ class Context : public Recorder {
 
   Atlas atlas_;  // (fdh_atlas.h)
   GlyphMaker glyphs_;  // (fdh_glyphs.h)
+  Importer importer_;  // (fdh_import.h)
 
   FdhFrameStats stats_ = {};
  public:

@@ -1,15 +1,13 @@
 // fdh_glyphs.h -- glyphs made on the device (fdh_glyphs.cpp): class GlyphMaker, one member of Context beside the atlas.  A glyph image, an
-// outline (coverage or a distance field, segments of 6 or of 8 floats) or a batch of outlines is validated, gets its scratch buffers and only
-// then a place in the atlas (Atlas::place); its texels are made by kernels on the stream the context hands over with every call, the atlas's
-// level chain included.  The maker knows neither the context nor how the atlas packs.
+// outline (coverage or a distance field, segments of 6 or of 8 floats), a batch of outlines or a coverage image that becomes a distance
+// field is validated, gets its scratch buffers and only then a place in the atlas (Atlas::place); its texels are made by kernels on the
+// stream the context hands over with every call, the atlas's level chain included.  The maker is also the atlas's mover (fdh_compact_atlas):
+// the batches' level chain remakes the moved entries.  It knows neither the context nor how the atlas packs.  Images and video frames from
+// device memory are the Importer's (fdh_import.h).
 #pragma once
 #include <cstdint>
 #include <vector>
 
-#include "../../include_glyphs/figdraw_hip_device_images.h"  // FdhImageBatchStats; and through it figdraw_hip_device_image.h (FdhDeviceImage)
-#include "../../include_glyphs/figdraw_hip_video_frames.h"  // FdhVideoBatchStats; and through it figdraw_hip_video_frame.h (FdhVideoFrame)
-#include "../../include_video/figdraw_hip_video_alpha.h"    // FdhVideoAlphaPlanes; through it figdraw_hip_video_422.h (the 4:2:2 formats) and
-                                                            // figdraw_hip_video_planar.h (FdhVideoPlanes)
 #include "../../include_glyphs/figdraw_hip_cubic_batch.h"  // the two cubic batches; and through it figdraw_hip_cubic.h (fdh_put_glyph_outline_cubic),
                                                             // figdraw_hip_coverage.h (the coverage batch), figdraw_hip_glyphs.h (FdhGlyphOutline, FdhGlyphBatchStats)
 #include "fdh_atlas.h"
@@ -40,36 +38,6 @@ class GlyphMaker final : public AtlasMover {
   // from the host, or of the texels an entry of the atlas holds
   void put_image_sdf(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const uint8_t* rgba, int channel, int pad, uint32_t flags, int out_rect[4]);
   void put_image_sdf_of(hipStream_t s, Atlas& atlas, int64_t src_key, int64_t key, int channel, int pad, uint32_t flags, int out_rect[4]);
-  // fdh_put_image_device and fdh_update_image_device (the specification: include_glyphs/figdraw_hip_device_image.h): what Atlas::put_image and
-  // Atlas::update_image store, of a source in device memory; `device`: the context's (on a record-only context nothing is asked of it)
-  void put_device_image(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhDeviceImage* img, int out_rect[4]);
-  void update_device_image(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhDeviceImage* img);
-  // fdh_put_images_device and fdh_update_images_device (the specification: include_glyphs/figdraw_hip_device_images.h): n device images, validated
-  // as a whole, placed (their updates begun) in order, made in at most four launches
-  void put_device_images(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhDeviceImage* images, int n, int (*out_rects)[4]);
-  void update_device_images(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhDeviceImage* images, int n);
-  const FdhImageBatchStats& image_batch_stats() const { return image_stats_; }
-  // fdh_put_video_frame and fdh_update_video_frame (the specification: include_glyphs/figdraw_hip_video_frame.h): the same of an NV12, P010 or
-  // BGRA8 frame
-  void put_video_frame(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoFrame* frame, int out_rect[4]);
-  void update_video_frame(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoFrame* frame);
-  // fdh_put_video_frames and fdh_update_video_frames (the specification: include_glyphs/figdraw_hip_video_frames.h): n such frames, validated as a
-  // whole, placed (their updates begun) in order, made in at most six launches
-  void put_video_frames(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhVideoFrame* frames, int n, int (*out_rects)[4]);
-  void update_video_frames(hipStream_t s, Atlas& atlas, int device, const int64_t* keys, const FdhVideoFrame* frames, int n);
-  const FdhVideoBatchStats& video_batch_stats() const { return video_stats_; }
-  // fdh_put_video_planes and fdh_update_video_planes (the specification: include_video/figdraw_hip_video_planar.h): the same of a three-plane
-  // I420, I010, I444 or I410 frame
-  void put_video_planes(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame, int out_rect[4]);
-  void update_video_planes(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame);
-  // fdh_put_video_422 and fdh_update_video_422 (the specification: include_video/figdraw_hip_video_422.h): the same of a 4:2:2 frame, I422 or
-  // I210 in three planes, YUY2 or UYVY in one
-  void put_video_422(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame, int out_rect[4]);
-  void update_video_422(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoPlanes* frame);
-  // fdh_put_video_alpha and fdh_update_video_alpha (the specification: include_video/figdraw_hip_video_alpha.h): the same of a frame with an
-  // alpha plane, A420, A444 or A410 in four planes, UYVA in two
-  void put_video_alpha(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoAlphaPlanes* frame, int out_rect[4]);
-  void update_video_alpha(hipStream_t s, Atlas& atlas, int device, int64_t key, const FdhVideoAlphaPlanes* frame);
   // fdh_compact_atlas (the specification: include_glyphs/figdraw_hip_atlas.h): the atlas's mover
   void move_entries(hipStream_t s, const AtlasView& from, const Atlas& to, const std::vector<MovedEntry>& moved, FdhAtlasMoveStats& stats) override;
   void release();  // the scratch buffers (the stream is idle)
@@ -85,27 +53,6 @@ class GlyphMaker final : public AtlasMover {
   void glyph_to_atlas(hipStream_t s, const Atlas& atlas, uint32_t* cur, uint32_t* nxt, int w, int h, int x, int y, uint32_t flags);
   // the two image-field puts behind their validation: `rgba` from the host, or null and the w x h texels at (from_x, from_y) of the atlas's level 0
   void put_image_field(hipStream_t s, Atlas& atlas, int64_t key, int w, int h, const uint8_t* rgba, int from_x, int from_y, int channel, int pad, int range, int out_rect[4]);
-  // the two device-image calls behind their validation and their placement: the launches, the wait, the entry's ink boxes
-  void import_image(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const FdhDeviceImage& img, const void* data, bool wide);
-  // the two device-image batches: pass 1 of both, and pass 3 -- the tables, the launches, the wait, the ink boxes -- of entries first .. first + m - 1
-  struct ImageBatch;
-  void validate_device_images(const char* who, const Atlas& atlas, int device, const int64_t* keys, const FdhDeviceImage* images, int n, bool update, ImageBatch* B);
-  void reserve_image_batch(const ImageBatch& B);
-  void make_device_images(hipStream_t s, const Atlas& atlas, ImageBatch& B, int first, int m);
-  struct VideoSource;  // a validated FdhVideoFrame as the device addresses it (fdh_glyphs.cpp)
-  void import_video(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const VideoSource& src);
-  // the two video-frame batches: pass 1 of both, and pass 3 -- the tables, the launches, the wait, the ink boxes -- of entries first .. first + m - 1
-  struct VideoBatch;
-  void validate_video_frames(const char* who, const Atlas& atlas, int device, const int64_t* keys, const FdhVideoFrame* frames, int n, bool update, VideoBatch* B);
-  void reserve_video_batch(const VideoBatch& B);
-  void make_video_frames(hipStream_t s, const Atlas& atlas, VideoBatch& B, int first, int m);
-  struct PlanarSource;  // a validated FdhVideoPlanes as the device addresses it (fdh_glyphs.cpp)
-  void import_video_planes(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const PlanarSource& src);
-  void import_video_422(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const PlanarSource& src);  // (the same struct, the 4:2:2 formats)
-  struct AlphaSource;  // a validated FdhVideoAlphaPlanes as the device addresses it (fdh_glyphs.cpp)
-  void import_video_alpha(hipStream_t s, const Atlas& atlas, AtlasEntry& e, const AlphaSource& src);
-  // behind the first launch of either: the rest of the chain from the level-5 image in glyph_a_, the wait, the entry's ink boxes
-  void finish_import(hipStream_t s, const Atlas& atlas, AtlasEntry& e, int n_store, bool ink);
   // the batches: pass 1 in either format, then passes 2 and 3 of all four (the placement, the tables, the copies, `middle`'s launches, the level chain)
   void put_fields(const SegmentFormat& fmt, hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
   void put_coverage(const SegmentFormat& fmt, hipStream_t s, Atlas& atlas, const FdhGlyphOutline* glyphs, int n, uint32_t flags, int (*out_rects)[4]);
@@ -119,13 +66,7 @@ class GlyphMaker final : public AtlasMover {
   DeviceBuf<float> glyph_lines_, glyph_acc_, glyph_edges_;  // flattened outline, area accumulators; the edge records of a distance field (fdh_msdf_host.h)
   DeviceBuf<uint32_t> glyph_tab_;  // the batches: the glyph records (msdf::BatchGlyph), the tile -> glyph words, the owner bits of the deep levels (fdh_glyph_tables.h)
   DeviceBuf<uint32_t> move_tab_;   // fdh_compact_atlas: the tables of its k_atlas_move launches (fdh_atlas_move.h)
-  PinnedBuf<int32_t> ink_host_;    // the device-image and video-frame calls: the tiles' ink blocks, which the kernel stores into page-locked memory (fdh_image_import.h)
-  FdhImageBatchStats image_stats_ = {};  // of the last put_device_images or update_device_images
-  FdhVideoBatchStats video_stats_ = {};  // of the last put_video_frames or update_video_frames
   FdhGlyphBatchStats batch_stats_ = {}, coverage_stats_ = {};  // of the last put_glyph_outlines, of the last put_glyph_coverage_batch (either in either segment format)
 };
-
-// fdh_video_coefficients (include_glyphs/figdraw_hip_video_frame.h): a row of video_import::kCoefficients; no context
-void video_coefficients(uint32_t format, uint32_t matrix, uint32_t range, int32_t out[7]);
 
 }  // namespace fdh

@@ -1,5 +1,5 @@
-// fdh_image_batch.h -- the tables a batch of device images hands to the batched kernels of k_image_import.hip (GlyphMaker::put_device_images,
-// fdh_glyphs.cpp): the image records (image_import::BatchImage, fdh_image_import.h, beside the single kernels' blocks), one word per 32 x 32
+// fdh_image_batch.h -- the tables a batch of device images hands to the batched kernels of k_image_import.hip (Importer::put_device_images,
+// fdh_import.cpp): the image records (image_import::BatchImage, fdh_image_import.h, beside the single kernels' blocks), one word per 32 x 32
 // tile naming its image and the tile's place in it, grouped by format -- a launch per format runs over its group --, the indices of the
 // images whose chain goes beyond level 5, and the owner bits that give a batch the painter's order of single puts.  Plain C++, no HIP and
 // no atlas: the placed images and the atlas's level count in, words out (tests/image_batch_tables_emu compiles it as it stands).

@@ -1,4 +1,4 @@
-// fdh_video_batch.h -- the tables a batch of decoded video frames hands to the batched kernels (GlyphMaker::put_video_frames, fdh_glyphs.cpp):
+// fdh_video_batch.h -- the tables a batch of decoded video frames hands to the batched kernels (Importer::put_video_frames, fdh_import.cpp):
 // the frame records (video_import::BatchFrame, fdh_video_import.h, beside the single kernel's block), one word per 32 x 32 tile naming its
 // frame and the tile's place in it, grouped by the five builds of k_video_import_batch (video_import::batch_group) -- a launch per group
 // runs over its words --, the records and indices k_image_import_tail_batch reads of the frames whose chain goes beyond level 5

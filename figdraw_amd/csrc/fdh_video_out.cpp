@@ -12,6 +12,7 @@
 #include "fdh_kernels.h"
 #include "fdh_memory.h"  // FDH_HIP, device_view_of
 #include "fdh_plain.h"   // Error
+#include "fdh_place_batch.h"  // Refusal
 #include "fdh_video_export.h"
 #include "fdh_video_planar.h"
 #include "fdh_video_422.h"
@@ -25,10 +26,6 @@ namespace v2 = video_422;
 namespace va = video_alpha;
 
 namespace {
-struct Refusal {
-  const char* who;
-  Error operator()(const std::string& what) const { return Error(FDH_ERR_INVALID, std::string(who) + ": " + what); }
-};
 // what a checked target comes to: the rectangle, and the bytes from each plane's pointer to its last element's end
 struct Layout {
   int x, y, w, h;

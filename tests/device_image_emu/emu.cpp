@@ -1,6 +1,6 @@
 // tests/device_image_emu/emu.cpp -- figdraw_amd/csrc/k_image_import.hip under the sequential host shim (tests/emu/fdh_device.h); the kernel's source and
 // fdh_image_import.h come from csrc, unmodified: tests/test_device_image_host.py copies them here.  Built twice: emu, and emu_san (the same
-// under AddressSanitizer and UBSan).  The launches are GlyphMaker::import_image's (fdh_glyphs.cpp) for a source of up to 2048 x 2048.
+// under AddressSanitizer and UBSan).  The launches are Importer::import_one's for an ImageSource (fdh_import.cpp) for a source of up to 2048 x 2048.
 // usage: emu cases.bin out.bin
 //   cases.bin: per case fourteen int32 -- w, h, format, channels, flags, pitch_bytes, plane_bytes, data_offset, source_bytes, x, y,
 //              atlas_size, n_levels, 0 -- and source_bytes bytes: the source, which the kernel gets at an address data_offset past a

@@ -1,7 +1,7 @@
 // tests/device_images_emu/emu.cpp -- the batched kernels of figdraw_amd/csrc/k_image_import.hip under the sequential host shim (tests/emu/fdh_device.h),
 // over the tables fdh_image_batch.h makes; the kernel's source and the headers come from csrc, unmodified: tests/test_device_images_host.py
 // copies them here.  Built twice: emu, and emu_san (the same under AddressSanitizer and UBSan).  The launches are
-// GlyphMaker::make_device_images' (fdh_glyphs.cpp): one per format present, one for the tails.
+// Importer::make's for an ImageBatch (fdh_import.cpp): one per format present, one for the tails.
 // usage: emu batch.bin out.bin
 //   batch.bin: four int32 -- n, atlas_size, n_levels, out_rows -- then per image twelve int32 -- w, h, format, channels, flags, pitch_bytes,
 //              plane_bytes, data_offset, source_bytes, x, y, 0 -- and source_bytes bytes: the source, which the kernel gets at an address

@@ -458,7 +458,7 @@ def check_batch(cases, rects, size, got):
             raise AssertionError(f"level {l} differs in {len(xs)} texels, the first at ({xs[0]}, {ys[0]}): {a[ys[0], xs[0]]} != {b[ys[0], xs[0]]}")
     for case, (x, y, w, h), block in zip(cases, rects, inks):
         boxes = REF.ink_boxes(DC.texels(case))
-        if boxes is None or w == 1 or h == 1:  # (a line has no tile: the host measures its boxes, GlyphMaker::make_device_images)
+        if boxes is None or w == 1 or h == 1:  # (a line has no tile: the host measures its boxes, Importer::make)
             assert block.reshape(16, 4).tolist() == [[32767, 32767, 0, 0]] * 16, case[0]
         else:
             got_boxes = block.reshape(16, 4).astype(np.int64)

@@ -1,8 +1,8 @@
 // tests/video_422_in_emu/emu.cpp -- figdraw_amd/csrc/k_video_422_import.hip under the sequential host shim (tests/emu/fdh_device.h), with
 // k_image_import.hip for the tail kernel; the kernels' sources and their parameter headers come from csrc, unmodified:
 // tests/test_video_422_host.py copies them here.  Built twice: emu, and emu_san (the same stand-alone program under AddressSanitizer and
-// UBSan, which also refuses a wide load at an address that is no multiple of its size).  The launches are GlyphMaker::import_video_422's
-// (fdh_glyphs.cpp) for a frame of up to 2048 x 2048.
+// UBSan, which also refuses a wide load at an address that is no multiple of its size).  The launches are Importer::import_one's
+// for a Source422 (fdh_import.cpp) for a frame of up to 2048 x 2048.
 // usage: emu cases.bin out.bin
 //   cases.bin: per case twenty int32 -- w, h, format, matrix, range, flags, pitch[3], offset[3], bytes[3], x, y, atlas_size, n_levels, 0 --
 //              and bytes[0] + bytes[1] + bytes[2] bytes: the planes Y, Cb, Cr, or the one packed plane (pitch, offset and bytes of the

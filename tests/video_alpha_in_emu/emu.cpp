@@ -2,7 +2,7 @@
 // with k_image_import.hip for the tail kernel; the kernels' sources and their parameter headers come from csrc, unmodified:
 // tests/test_video_alpha_host.py copies them here.  Built twice: emu, and emu_san (the same stand-alone program under AddressSanitizer
 // and UBSan, which also refuses a wide load at an address that is no multiple of its size).  The launches are
-// GlyphMaker::import_video_alpha's (fdh_glyphs.cpp) for a frame of up to 2048 x 2048.
+// Importer::import_one's for an AlphaSource (fdh_import.cpp) for a frame of up to 2048 x 2048.
 // usage: emu cases.bin out.bin
 //   cases.bin: per case twenty-four int32 -- w, h, format, matrix, range, flags, pitch[4], offset[4], bytes[4], x, y, atlas_size, n_levels,
 //              0, 0 -- and bytes[0] + .. + bytes[3] bytes: the planes Y, Cb, Cr, A, or the UYVY plane and A (pitch, offset and bytes of

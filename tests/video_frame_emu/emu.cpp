@@ -1,7 +1,7 @@
 // tests/video_frame_emu/emu.cpp -- figdraw_amd/csrc/k_video_import.hip under the sequential host shim (tests/emu/fdh_device.h), with k_image_import.hip for
 // the tail kernel; the kernels' sources and their two parameter headers come from csrc, unmodified: tests/test_video_frame_host.py copies
-// them here.  Built twice: emu, and emu_san (the same under AddressSanitizer and UBSan).  The launches are GlyphMaker::import_video's
-// (fdh_glyphs.cpp) for a frame of up to 2048 x 2048.
+// them here.  Built twice: emu, and emu_san (the same under AddressSanitizer and UBSan).  The launches are Importer::import_one's
+// for a VideoSource (fdh_import.cpp) for a frame of up to 2048 x 2048.
 // usage: emu cases.bin out.bin
 //   cases.bin: per case sixteen int32 -- w, h, format, matrix, range, flags, pitch_y, pitch_c, offset_y, offset_c, bytes_y, bytes_c, x, y,
 //              atlas_size, n_levels -- and bytes_y + bytes_c bytes: the luma plane, then the chroma plane (bytes_c = 0: none).  The kernel

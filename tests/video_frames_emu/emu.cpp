@@ -1,7 +1,7 @@
 // tests/video_frames_emu/emu.cpp -- the batched kernels of figdraw_amd/csrc/k_video_import.hip, and k_image_import_tail_batch of k_image_import.hip,
 // under the sequential host shim (tests/emu/fdh_device.h), over the tables fdh_video_batch.h makes; the kernels' sources and the headers
 // come from csrc, unmodified: tests/test_video_frames_host.py copies them here.  Built twice: emu, and emu_san (the same under
-// AddressSanitizer and UBSan).  The launches are GlyphMaker::make_video_frames' (fdh_glyphs.cpp): one per group present, one for the tails.
+// AddressSanitizer and UBSan).  The launches are Importer::make's for a VideoBatch (fdh_import.cpp): one per group present, one for the tails.
 // usage: emu batch.bin out.bin
 //   batch.bin: four int32 -- n, atlas_size, n_levels, out_rows -- then per frame sixteen int32 -- w, h, format, matrix, range, flags, pitch_y,
 //              pitch_c, offset_y, offset_c, bytes_y, bytes_c, x, y, 0, 0 -- and bytes_y + bytes_c bytes: the luma plane, then the chroma plane

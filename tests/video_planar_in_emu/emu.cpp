@@ -1,7 +1,7 @@
 // tests/video_planar_in_emu/emu.cpp -- figdraw_amd/csrc/k_video_planar_import.hip under the sequential host shim (tests/emu/fdh_device.h), with
 // k_image_import.hip for the tail kernel; the kernels' sources and their parameter headers come from csrc, unmodified:
 // tests/test_video_planar_host.py copies them here.  Built twice: emu, and emu_san (the same under AddressSanitizer and UBSan, which also
-// refuses a wide load at an address that is no multiple of its size).  The launches are GlyphMaker::import_video_planes's (fdh_glyphs.cpp)
+// refuses a wide load at an address that is no multiple of its size).  The launches are Importer::import_one's for a PlanarSource (fdh_import.cpp)
 // for a frame of up to 2048 x 2048.
 // usage: emu cases.bin out.bin
 //   cases.bin: per case twenty int32 -- w, h, format, matrix, range, flags, pitch[3], offset[3], bytes[3], x, y, atlas_size, n_levels, 0 --
