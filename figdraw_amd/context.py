@@ -110,18 +110,30 @@ def video_coefficients(format, matrix, range):
     return tuple(out)
 
 
+def _video_target(t, ptrs, pitches, format, matrix, range, flags, rect):
+    """the fields of a fresh VideoTarget, VideoPlanesTarget or VideoAlphaPlanesTarget: as many planes as it has"""
+    for p, _ in enumerate(t.planes):
+        t.planes[p], t.pitch_bytes[p] = ptrs[p] or None, int(pitches[p])
+    t.rect[0], t.rect[1], t.rect[2], t.rect[3] = (int(v) for v in (rect if rect is not None else (0, 0, 0, 0)))
+    t.format, t.matrix, t.range, t.flags = int(format), int(matrix), int(range), int(flags)
+    return t
+
+
+def _check_video(call, target, frame_w, frame_h):
+    """one of the four fdh_check_video_*_target on `target`, or on None"""
+    L = load()
+    code = getattr(L, call)(C.byref(target) if target is not None else None, int(frame_w), int(frame_h))
+    if code != 0:
+        raise FigdrawHipError(code, L.fdh_last_error().decode())
+
+
 class VideoTarget(C.Structure):  # FdhVideoTarget (include_video/figdraw_hip_video_out.h)
     _fields_ = [("planes", C.c_void_p * 2), ("pitch_bytes", C.c_int64 * 2), ("rect", C.c_int32 * 4),
                 ("format", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 def video_target(y_ptr, uv_ptr, pitch_y, pitch_uv, format=VIDEO_NV12, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None) -> VideoTarget:
-    t = VideoTarget()
-    t.planes[0], t.planes[1] = y_ptr or None, uv_ptr or None
-    t.pitch_bytes[0], t.pitch_bytes[1] = int(pitch_y), int(pitch_uv)
-    t.rect[0], t.rect[1], t.rect[2], t.rect[3] = (int(v) for v in (rect if rect is not None else (0, 0, 0, 0)))
-    t.format, t.matrix, t.range, t.flags = int(format), int(matrix), int(range), int(flags)
-    return t
+    return _video_target(VideoTarget(), (y_ptr, uv_ptr), (pitch_y, pitch_uv), format, matrix, range, flags, rect)
 
 
 def video_out_coefficients(format, matrix, range):
@@ -137,10 +149,7 @@ def video_out_coefficients(format, matrix, range):
 def check_video_target(target, frame_w, frame_h):
     """every rule of fdh_read_video_frame that needs no device, for a frame of frame_w x frame_h (fdh_check_video_target): raises
     FigdrawHipError where the call would refuse `target` (a VideoTarget, or None)"""
-    L = load()
-    code = L.fdh_check_video_target(C.byref(target) if target is not None else None, int(frame_w), int(frame_h))
-    if code != 0:
-        raise FigdrawHipError(code, L.fdh_last_error().decode())
+    _check_video("fdh_check_video_target", target, frame_w, frame_h)
 
 
 class VideoPlanes(C.Structure):  # FdhVideoPlanes (include_video/figdraw_hip_video_planar.h)
@@ -166,21 +175,13 @@ def video_planes(ptrs, width, height, pitches, format=VIDEO_I420, matrix=VIDEO_B
 
 
 def video_planes_target(ptrs, pitches, format=VIDEO_I420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None) -> VideoPlanesTarget:
-    t = VideoPlanesTarget()
-    for p in (0, 1, 2):
-        t.planes[p], t.pitch_bytes[p] = ptrs[p] or None, int(pitches[p])
-    t.rect[0], t.rect[1], t.rect[2], t.rect[3] = (int(v) for v in (rect if rect is not None else (0, 0, 0, 0)))
-    t.format, t.matrix, t.range, t.flags = int(format), int(matrix), int(range), int(flags)
-    return t
+    return _video_target(VideoPlanesTarget(), ptrs, pitches, format, matrix, range, flags, rect)
 
 
 def check_video_planes_target(target, frame_w, frame_h):
     """every rule of fdh_read_video_planes that needs no device, for a frame of frame_w x frame_h (fdh_check_video_planes_target): raises
     FigdrawHipError where the call would refuse `target` (a VideoPlanesTarget, or None)"""
-    L = load()
-    code = L.fdh_check_video_planes_target(C.byref(target) if target is not None else None, int(frame_w), int(frame_h))
-    if code != 0:
-        raise FigdrawHipError(code, L.fdh_last_error().decode())
+    _check_video("fdh_check_video_planes_target", target, frame_w, frame_h)
 
 
 VIDEO_I422, VIDEO_I210, VIDEO_YUY2, VIDEO_UYVY = 7, 8, 9, 10                       # ... for the 4:2:2 calls (include_video/figdraw_hip_video_422.h)
@@ -189,10 +190,7 @@ VIDEO_I422, VIDEO_I210, VIDEO_YUY2, VIDEO_UYVY = 7, 8, 9, 10                    
 def check_video_422_target(target, frame_w, frame_h):
     """every rule of fdh_read_video_422 that needs no device, for a frame of frame_w x frame_h (fdh_check_video_422_target): raises
     FigdrawHipError where the call would refuse `target` (a VideoPlanesTarget, or None)"""
-    L = load()
-    code = L.fdh_check_video_422_target(C.byref(target) if target is not None else None, int(frame_w), int(frame_h))
-    if code != 0:
-        raise FigdrawHipError(code, L.fdh_last_error().decode())
+    _check_video("fdh_check_video_422_target", target, frame_w, frame_h)
 
 
 class VideoAlphaPlanes(C.Structure):  # FdhVideoAlphaPlanes (include_video/figdraw_hip_video_alpha.h)
@@ -218,21 +216,13 @@ def video_alpha_planes(ptrs, width, height, pitches, format=VIDEO_A420, matrix=V
 
 
 def video_alpha_planes_target(ptrs, pitches, format=VIDEO_A420, matrix=VIDEO_BT709, range=VIDEO_LIMITED, flags=0, rect=None) -> VideoAlphaPlanesTarget:
-    t = VideoAlphaPlanesTarget()
-    for p in (0, 1, 2, 3):
-        t.planes[p], t.pitch_bytes[p] = ptrs[p] or None, int(pitches[p])
-    t.rect[0], t.rect[1], t.rect[2], t.rect[3] = (int(v) for v in (rect if rect is not None else (0, 0, 0, 0)))
-    t.format, t.matrix, t.range, t.flags = int(format), int(matrix), int(range), int(flags)
-    return t
+    return _video_target(VideoAlphaPlanesTarget(), ptrs, pitches, format, matrix, range, flags, rect)
 
 
 def check_video_alpha_target(target, frame_w, frame_h):
     """every rule of fdh_read_video_alpha that needs no device, for a frame of frame_w x frame_h (fdh_check_video_alpha_target): raises
     FigdrawHipError where the call would refuse `target` (a VideoAlphaPlanesTarget, or None)"""
-    L = load()
-    code = L.fdh_check_video_alpha_target(C.byref(target) if target is not None else None, int(frame_w), int(frame_h))
-    if code != 0:
-        raise FigdrawHipError(code, L.fdh_last_error().decode())
+    _check_video("fdh_check_video_alpha_target", target, frame_w, frame_h)
 
 
 def tensor_image(t, straight_alpha: bool = False) -> DeviceImage:

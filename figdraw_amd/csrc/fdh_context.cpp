@@ -733,60 +733,28 @@ void Context::read_pixels(int x, int y, int w, int h, uint8_t* out) {
   FDH_HIP(hipStreamSynchronize(stream_));
   FDH_HIP(hipMemcpy2D(out, (size_t)w * 4, fb_ + (size_t)y * env_.W + x, (size_t)env_.W * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost));
 }
-// fdh_read_video_frame (include_video/figdraw_hip_video_out.h): the context's part -- the last frame is complete, and where it lies (a frame
-// with a fused full-frame blur ends in the other surface: fb_ behind drain(), as read_pixels takes it); the rest is fdh_video_out.cpp's
-void Context::read_video_frame(const FdhVideoTarget* target) {
-  if (host_only_) throw Error(FDH_ERR_INVALID, "read_video_frame: this context was created with FDH_CREATE_RECORD_ONLY (it records calls, it draws nothing)");
+// fdh_read_video_frame, fdh_read_video_planes, fdh_read_video_422 and fdh_read_video_alpha (include_video/): the context's part -- the last
+// frame is complete, and where it lies (a frame with a fused full-frame blur ends in the other surface: fb_ behind drain(), as read_pixels
+// takes it); the rest is fdh_video_out.cpp's
+template <class Target>
+void Context::read_video(const char* who, void (*read)(hipStream_t, int, const uint32_t*, int, int, const Target*, const video_out::Own*, int), const Target* target) {
+  const std::string name = who;
+  if (host_only_) throw Error(FDH_ERR_INVALID, name + ": this context was created with FDH_CREATE_RECORD_ONLY (it records calls, it draws nothing)");
   drain();
   // (a begin_frame of another size has made new surfaces: the last frame is gone with the old ones)
-  if (!have_frame_ || !fb_ || job_.W != surf_w_ || job_.H != surf_h_) throw Error(FDH_ERR_INVALID, "read_video_frame: no frame has been submitted");
-  if (stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, "read_video_frame: not under fdh_set_stripe");
+  if (!have_frame_ || !fb_ || job_.W != surf_w_ || job_.H != surf_h_) throw Error(FDH_ERR_INVALID, name + ": no frame has been submitted");
+  if (stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, name + ": not under fdh_set_stripe");
   FDH_HIP(hipSetDevice(device_));
   const size_t surface = (size_t)surf_w_ * surf_h_ * 4;
   std::vector<video_out::Own> own = {{fb_, surface, "frame surface"}, {alt_, surface, "frame surface"}, {backdrop_, surface, "backdrop surface"}, {blur_tmp_, surface, "blur surface"}};
   for (int l = 0; l < atlas_.n_levels(); l++) own.push_back({atlas_.level(l), (size_t)(atlas_.size() >> l) * (atlas_.size() >> l) * 4, "atlas"});
   FDH_HIP(hipStreamSynchronize(stream_));
-  video_out::read(stream_, device_, fb_, surf_w_, surf_h_, target, own.data(), (int)own.size());
+  read(stream_, device_, fb_, surf_w_, surf_h_, target, own.data(), (int)own.size());
 }
-// fdh_read_video_planes (include_video/figdraw_hip_video_planar.h): the same for three planes
-void Context::read_video_planes(const FdhVideoPlanesTarget* target) {
-  if (host_only_) throw Error(FDH_ERR_INVALID, "read_video_planes: this context was created with FDH_CREATE_RECORD_ONLY (it records calls, it draws nothing)");
-  drain();
-  if (!have_frame_ || !fb_ || job_.W != surf_w_ || job_.H != surf_h_) throw Error(FDH_ERR_INVALID, "read_video_planes: no frame has been submitted");
-  if (stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, "read_video_planes: not under fdh_set_stripe");
-  FDH_HIP(hipSetDevice(device_));
-  const size_t surface = (size_t)surf_w_ * surf_h_ * 4;
-  std::vector<video_out::Own> own = {{fb_, surface, "frame surface"}, {alt_, surface, "frame surface"}, {backdrop_, surface, "backdrop surface"}, {blur_tmp_, surface, "blur surface"}};
-  for (int l = 0; l < atlas_.n_levels(); l++) own.push_back({atlas_.level(l), (size_t)(atlas_.size() >> l) * (atlas_.size() >> l) * 4, "atlas"});
-  FDH_HIP(hipStreamSynchronize(stream_));
-  video_out::read_planes(stream_, device_, fb_, surf_w_, surf_h_, target, own.data(), (int)own.size());
-}
-// fdh_read_video_422 (include_video/figdraw_hip_video_422.h): the same for the 4:2:2 formats
-void Context::read_video_422(const FdhVideoPlanesTarget* target) {
-  if (host_only_) throw Error(FDH_ERR_INVALID, "read_video_422: this context was created with FDH_CREATE_RECORD_ONLY (it records calls, it draws nothing)");
-  drain();
-  if (!have_frame_ || !fb_ || job_.W != surf_w_ || job_.H != surf_h_) throw Error(FDH_ERR_INVALID, "read_video_422: no frame has been submitted");
-  if (stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, "read_video_422: not under fdh_set_stripe");
-  FDH_HIP(hipSetDevice(device_));
-  const size_t surface = (size_t)surf_w_ * surf_h_ * 4;
-  std::vector<video_out::Own> own = {{fb_, surface, "frame surface"}, {alt_, surface, "frame surface"}, {backdrop_, surface, "backdrop surface"}, {blur_tmp_, surface, "blur surface"}};
-  for (int l = 0; l < atlas_.n_levels(); l++) own.push_back({atlas_.level(l), (size_t)(atlas_.size() >> l) * (atlas_.size() >> l) * 4, "atlas"});
-  FDH_HIP(hipStreamSynchronize(stream_));
-  video_out::read_422(stream_, device_, fb_, surf_w_, surf_h_, target, own.data(), (int)own.size());
-}
-// fdh_read_video_alpha (include_video/figdraw_hip_video_alpha.h): the same for the formats with an alpha plane
-void Context::read_video_alpha(const FdhVideoAlphaPlanesTarget* target) {
-  if (host_only_) throw Error(FDH_ERR_INVALID, "read_video_alpha: this context was created with FDH_CREATE_RECORD_ONLY (it records calls, it draws nothing)");
-  drain();
-  if (!have_frame_ || !fb_ || job_.W != surf_w_ || job_.H != surf_h_) throw Error(FDH_ERR_INVALID, "read_video_alpha: no frame has been submitted");
-  if (stripe_y1_ > stripe_y0_) throw Error(FDH_ERR_INVALID, "read_video_alpha: not under fdh_set_stripe");
-  FDH_HIP(hipSetDevice(device_));
-  const size_t surface = (size_t)surf_w_ * surf_h_ * 4;
-  std::vector<video_out::Own> own = {{fb_, surface, "frame surface"}, {alt_, surface, "frame surface"}, {backdrop_, surface, "backdrop surface"}, {blur_tmp_, surface, "blur surface"}};
-  for (int l = 0; l < atlas_.n_levels(); l++) own.push_back({atlas_.level(l), (size_t)(atlas_.size() >> l) * (atlas_.size() >> l) * 4, "atlas"});
-  FDH_HIP(hipStreamSynchronize(stream_));
-  video_out::read_alpha(stream_, device_, fb_, surf_w_, surf_h_, target, own.data(), (int)own.size());
-}
+void Context::read_video_frame(const FdhVideoTarget* target) { read_video("read_video_frame", video_out::read, target); }
+void Context::read_video_planes(const FdhVideoPlanesTarget* target) { read_video("read_video_planes", video_out::read_planes, target); }
+void Context::read_video_422(const FdhVideoPlanesTarget* target) { read_video("read_video_422", video_out::read_422, target); }
+void Context::read_video_alpha(const FdhVideoAlphaPlanesTarget* target) { read_video("read_video_alpha", video_out::read_alpha, target); }
 // ------------------------------------------------------------------ damage tracking, damage readback: the context's part (fdh_damage.cpp)
 void Context::set_damage_tracking(bool on) {
   if (on && host_only_) throw Error(FDH_ERR_INVALID, "fdh_set_damage_tracking: a record-only context composites nothing");

@@ -333,6 +333,9 @@ class Context : public Recorder {
   DamageTracker damage_;
   DamageReadback readback_;
   ReadFrame read_frame(const char* who);  // a read's first steps: the last frame is complete; what the read needs of it
+  // the context's part of fdh_read_video_frame, _planes, _422 and _alpha: the last frame is complete, where it lies and what no plane may touch
+  template <class Target>
+  void read_video(const char* who, void (*read)(hipStream_t, int, const uint32_t*, int, int, const Target*, const video_out::Own*, int), const Target* target);
   // picking: fdh_set_pick (calling thread), latched per frame at begin_frame (FrameEnv::pick_frame: the lanes keep tags); the pick launches' buffers
   bool pick_on_ = false;
   void pick_check(const char* who, int threshold, uint32_t flags);

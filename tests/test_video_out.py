@@ -272,3 +272,44 @@ def test_a_plane_on_another_device_is_refused(memory):
             ctx.read_video_frame(y_ptr, uv_ptr, 16, 16)
         assert e.value.code == -1 and "neither device memory of the context's device" in str(e.value)
     ctx.close()
+
+
+def test_the_order_of_the_refusals_that_need_the_device(memory):
+    """the device half of the four calls asks plane by plane, in plane order -- whether the plane can be addressed, then whether it touches
+    memory of the context's own -- and the planes' overlap with each other last; a plane a format does not have is not asked.  A refused
+    call writes nothing: every block, the pageable array and the frame are as they were"""
+    from figdraw_amd.context import VIDEO_A444, VIDEO_UYVA, FigdrawHipError, HipContext
+
+    ctx = HipContext(atlas_size=256, device=0)
+    frame = render(ctx, 16, 9, OPAQUE)
+    surface = ctx.frame_device_ptr()[0]
+    pageable = np.full(512, VC.FILL, np.uint8)
+    block = memory.filled(4 * 512)  # a plane of the 16 x 9 frame has at most 288 bytes
+    calls = [  # the call, which planes the format has, the text for planes that overlap each other
+        ("read_video_frame", lambda p: ctx.read_video_frame(p[0], p[1], 16, 16), (1, 1), "the two planes overlap"),
+        ("read_video_planes", lambda p: ctx.read_video_planes(p, (16, 8, 8)), (1, 1, 1), "planes 0 and 1 overlap"),
+        ("read_video_422", lambda p: ctx.read_video_422(p, (16, 8, 8)), (1, 1, 1), "planes 0 and 1 overlap"),
+        ("read_video_alpha", lambda p: ctx.read_video_alpha(p, (16, 16, 16, 16), format=VIDEO_A444), (1, 1, 1, 1), "planes 0 and 1 overlap"),
+        ("read_video_alpha", lambda p: ctx.read_video_alpha(p, (32, 0, 0, 16), format=VIDEO_UYVA), (1, 0, 0, 1), "planes 0 and 3 overlap"),
+    ]
+    n = 0
+    for name, call, present, overlap in calls:
+        valid = [block + 512 * p if there else 0 for p, there in enumerate(present)]
+        second = present.index(1, 1)  # the format's next plane after plane 0
+
+        def refused(text, plane_0, plane_second):
+            nonlocal n
+            ptrs = list(valid)
+            ptrs[0], ptrs[second] = plane_0, plane_second
+            with pytest.raises(FigdrawHipError) as e:
+                call(ptrs)
+            assert e.value.code == -1 and str(e.value).endswith(f"{name}: {text}"), str(e.value)
+            assert untouched(memory, block, 4 * 512) and (pageable == VC.FILL).all()
+            n += 1
+
+        refused("a plane is neither device memory of the context's device nor page-locked host memory", pageable.ctypes.data, surface)
+        refused("a plane overlaps the context's own frame surface", surface, pageable.ctypes.data)
+        refused(overlap, valid[0], valid[0] + 4)
+    assert n == 15 and memory.hip.hipGetLastError() == 0
+    assert np.array_equal(ctx.read_pixels(), frame)
+    ctx.close()

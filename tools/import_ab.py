@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
-"""The host cost of the image and video imports, this tree's library against another build's (the parent commit's), on one MI355X in one
-session -> the timing part of profiles/import_refactor.txt.
+"""The host cost of the image and video imports, or of the video exports, this tree's library against another build's (the parent
+commit's), on one MI355X in one session -> the timing part of profiles/import_refactor.txt, profiles/video_out_refactor.txt.
 
-  import_ab.py OUT --parent-lib LIB [--rounds N] [--warmup W] [--bench-runs K]
+  import_ab.py OUT --parent-lib LIB [--rows import|out] [--rounds N] [--warmup W] [--bench-runs K]
   import_ab.py --first                       one process: the first imports of a context that has made glyphs; one JSON line
 
 The rows are steps of the import benchmarks -- tools/device_image_bench.py (single and batch), tools/video_frame_bench.py,
 tools/video_frame_batch_bench.py, tools/video_alpha_bench.py -- at their smallest sizes, where the host side is the larger share of a call,
-each step a process of its own on the library FIGDRAW_HIP_LIB names; then bench.py --gpus 1 --steps 200 --warmup 20.  A row runs parent,
-tree, parent, tree, parent: the yardstick is the parent against itself.  A leg is marked only where every run of the tree is slower than
+each step a process of its own on the library FIGDRAW_HIP_LIB names (--rows out: the way out of tools/video_out_bench.py,
+tools/video_planar_bench.py, tools/video_422_bench.py and tools/video_alpha_bench.py at 256 x 256 instead, and no first-call rows); then
+bench.py --gpus 1 --steps 200 --warmup 20.  A row runs parent, tree, parent, tree, parent: the yardstick is the parent against itself.  A leg is marked only where every run of the tree is slower than
 every run of the parent; whatever comes out is written down.  The first-call rows are numbers, not verdicts: the tree's importer allocates
 its own scratch there.  Every step runs under its own time limit and nothing is started after a failure."""
 import argparse
@@ -22,10 +23,11 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ROWS = [("device_image_bench.py", s) for s in ("32:put:device", "32:update:device", "256:put:device", "256:update:device", "batch:32:put:batch", "batch:32:update:batch")]
-ROWS += [("video_frame_bench.py", s) for s in ("256x256:put:video", "256x256:update:video")]
-ROWS += [("video_frame_batch_bench.py", s) for s in ("thumbs:put:batch", "thumbs:update:batch")]
-ROWS += [("video_alpha_bench.py", "256x256:in")]
+ROWS = {"import": [("device_image_bench.py", s) for s in ("32:put:device", "32:update:device", "256:put:device", "256:update:device", "batch:32:put:batch", "batch:32:update:batch")]}
+ROWS["import"] += [("video_frame_bench.py", s) for s in ("256x256:put:video", "256x256:update:video")]
+ROWS["import"] += [("video_frame_batch_bench.py", s) for s in ("thumbs:put:batch", "thumbs:update:batch")]
+ROWS["import"] += [("video_alpha_bench.py", "256x256:in")]
+ROWS["out"] = [("video_out_bench.py", "256x256:video"), ("video_planar_bench.py", "256x256:out"), ("video_422_bench.py", "256x256:out"), ("video_alpha_bench.py", "256x256:out")]
 ORDER = ("parent", "tree", "parent", "tree", "parent")
 
 
@@ -77,6 +79,7 @@ def main():
     ap.add_argument("out", nargs="?")
     ap.add_argument("--first", action="store_true")
     ap.add_argument("--parent-lib")
+    ap.add_argument("--rows", choices=sorted(ROWS), default="import")
     ap.add_argument("--rounds", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--bench-runs", type=int, default=3)
@@ -103,7 +106,7 @@ def main():
             marked.append(where)
         return "   EVERY RUN OF THE TREE SLOWER THAN EVERY RUN OF THE PARENT" if worst else ""
 
-    for tool, step in ROWS:
+    for tool, step in ROWS[args.rows]:
         cmd = [sys.executable, os.path.join(ROOT, "tools", tool), "--step", step, "--rounds", str(args.rounds), "--warmup", str(args.warmup)]
         runs = []
         for side in ORDER:
@@ -118,13 +121,14 @@ def main():
                 continue
             parent, tree = [g[leg][0] for s, g in runs if s == "parent"], [g[leg][0] for s, g in runs if s == "tree"]
             say(f"    {leg:22s} {'  '.join(f'{x:8.1f}' for x in parent)}  | {'  '.join(f'{x:8.1f}' for x in tree)}{verdict(f'{step} {leg}', parent, tree)}")
-    say("first imports on a context that has made glyphs (tools/import_ab.py --first), microseconds; numbers, not verdicts")
     runs = []
-    for side in ORDER:
-        got = child([sys.executable, os.path.abspath(__file__), "--first"], libs[side], 120) if ok else None
-        ok = ok and got is not None
-        runs.append((side, got))
-    for leg in (runs[0][1] or {}) if ok else ():
+    if args.rows == "import":
+        say("first imports on a context that has made glyphs (tools/import_ab.py --first), microseconds; numbers, not verdicts")
+        for side in ORDER:
+            got = child([sys.executable, os.path.abspath(__file__), "--first"], libs[side], 120) if ok else None
+            ok = ok and got is not None
+            runs.append((side, got))
+    for leg in (runs[0][1] or {}) if ok and runs else ():
         say(f"    {leg:40s} {'  '.join(f'{g[leg]:8.1f}' for s, g in runs if s == 'parent')}  | {'  '.join(f'{g[leg]:8.1f}' for s, g in runs if s == 'tree')}")
     say("bench.py --gpus 1 --steps 200 --warmup 20: value (Mpixels/s), parent and tree by turns")
     values = {"parent": [], "tree": []}
